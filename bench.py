@@ -14,9 +14,14 @@ un-permutation into the frame.  For N > 1 the frame is sharded by interleaved 32
     python bench.py --gpus 1 --steps 16 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 
-Prints ONE JSON line on rank 0: the metric, `roofline` (what binds the dominant kernel: VALU issue, priced with measured issue ceilings; the SURVEY 8(d) bytes beside it),
-`cpu_baseline` / `cpu_baseline_1t` (the CPU checker on the host cores), and -- N = 1 -- `parity` (a crop of the frame against the checker), `latency` (1-spp and 16-spp calls)
-and `whole_frame`; DESIGN.md 5 describes every field.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the metric (`value`, `ms_per_step`, `step_ms`, the timed steps' own
+`kernel_ms_per_step`, `config`, `bvh`).  `--full` adds what needs runs or measurements of its own: `roofline` (what binds the dominant kernel: VALU issue, priced with
+measured issue ceilings; the SURVEY 8(d) bytes beside it), `shade`, `rates`, `whole_frame`, `kernel_ms_per_step_alone`, `scaling_model`, `cpu_baseline` / `cpu_baseline_1t`
+(the CPU checker on the host cores), and -- N = 1 -- `parity` (a crop of the frame against the checker), `latency` (1-spp and 16-spp calls) and `general_scene`;
+DESIGN.md 5 describes every field.  `--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).
+
+    python bench.py --full                                             # the whole record
+    python bench.py --steps 4 --warmup 1 --dump-outputs bench_outputs  # same arguments, same inputs: compare bench_outputs/*.npy of two builds
 """
 import argparse
 import json
@@ -550,6 +555,25 @@ def general_scene_block(local_rank, tmpdir, bw, spp=540, steps=2, warmup=1, pool
     return out
 
 
+DUMP_PIXELS = 1 << 19  # pixels per dumped buffer: at 21 + 4 floats per pixel (six layers + a presented frame) at most 52 MB in all
+
+
+def dump_outputs(out_dir, buffers, width, height):
+    """write each (H, W[, 4]) float32 device tensor of `buffers` as out_dir/<name>.npy, restricted to one fixed sample of pixels (seed 0, the same for every buffer, in
+    row-major order; every pixel where the frame has no more than DUMP_PIXELS): arrays of shape (n, 4) or (n,).  Rendering is deterministic, so equal arguments give equal
+    files on a correct build"""
+    import numpy as np
+    import torch
+
+    n = width * height
+    idx = np.arange(n) if n <= DUMP_PIXELS else np.sort(np.random.default_rng(0).choice(n, DUMP_PIXELS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in buffers.items():
+        flat = t.reshape(n, -1) if t.dim() == 3 else t.reshape(n)
+        a = flat[torch.from_numpy(idx).to(t.device)].cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n_gpus, argv=None):
     """start `n_gpus` ranks of this script on this node (one process per GPU, rendezvous on 127.0.0.1, a free port) and wait: returns the launcher's exit code, which is
     non-zero when any rank failed"""
@@ -577,7 +601,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras of the N = 1 line (parity crop, small-launch latency)")
     ap.add_argument("--no-general-scene", action="store_true", help="skip the configs[3] leg the default (configs[2], N = 1) run appends as `general_scene`")
     ap.add_argument("--check-frame", action="store_true", help="N > 1: rank 0 re-renders the whole frame unsharded and compares it bit for bit with the gathered one")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the HBM bandwidth probe, the serial and counting replays with the roofline / shade / rates / whole-frame "
+                    "records, the scaling model and -- N = 1 -- parity crop, latency, CPU baselines and the general-scene leg (each --no-* option above still drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one left in the caller's buffers as DIR/<name>.npy (float32): the "
+                    "render layers (N = 1) and the presented frame where it is another buffer (post chain, N > 1 gather), at a fixed seeded sample of at most DUMP_PIXELS pixels")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts the N ranks through torch.distributed.run as CHILD processes -- it has made no GPU call (torch is
@@ -636,7 +666,7 @@ def main():
     # every device buffer of the run is allocated BEFORE the path pools are sized by what is left
     bufs = {n: torch.zeros((HEIGHT, WIDTH) if n == "depth" else (HEIGHT, WIDTH, 4), dtype=torch.float32, device=dev) for n in F.RenderLayer.NAMES}
     layers = F.RenderLayer(r, WIDTH, HEIGHT, pointers={n: t.data_ptr() for n, t in bufs.items()})
-    extras = world == 1 and not args.no_extras
+    extras = world == 1 and args.full and not args.no_extras
     bufs2 = {n: torch.zeros((HEIGHT, WIDTH) if n == "depth" else (HEIGHT, WIDTH, 4), dtype=torch.float32, device=dev) for n in F.RenderLayer.NAMES} if extras else None
     layers2 = F.RenderLayer(r, WIDTH, HEIGHT, pointers={n: t.data_ptr() for n, t in bufs2.items()}) if extras else None
     n_owned = r.owned_pixel_count()
@@ -652,7 +682,7 @@ def main():
     # path-pool slots = owned pixels x samples per pass, one pool per pass in flight (pass_size above)
     pool_spp, slot_bytes, n_pools = pass_size(r, torch, local_rank, n_owned, spp, args.pool_spp, args.pool_gb)
     r.set_path_pool(max(int(n_owned * pool_spp), 1))
-    bw_read, bw_copy = r.measure_bandwidth(1 << 30, 6) if rank == 0 else (0.0, 0.0)  # measured HBM roofline of this GPU
+    bw_read, bw_copy = r.measure_bandwidth(1 << 30, 6) if (args.full and rank == 0) else (0.0, 0.0)  # measured HBM roofline of this GPU, --full only
     torch.cuda.synchronize()
 
     # N > 1: the collective runs on torch's stream, the renderer on the library's.  The two are ordered by events, never through the host: torch's stream waits for the
@@ -714,32 +744,39 @@ def main():
     timed = r.stats()
     pool_bytes_timed, pool_paths_timed = r.path_pool_allocated()
 
-    # ---- which kernel dominates: with two passes in flight a HIP-event span also contains the other stream's work (the register-heavy shade
-    # kernels wait for CUs the traversal kernels hold), so the ranking comes from one more, untimed step whose passes run one after the other
-    # (FH_FLAG_SERIAL_PASSES): every kernel alone on the GPU.  The roofline's launch time stays the one measured over the timed region.
-    r.set_flags(N.FLAG_TIME_KERNELS | N.FLAG_SERIAL_PASSES)
-    r.reset_stats()
-    r.render(cam, w["bg"], layers, spp, MAX_DEPTH)
-    r.wait_for_completion()
-    alone = r.stats()
+    if args.dump_outputs and rank == 0:  # what the caller holds after the last timed step, before any --full replay renders into the same layers
+        shown = {"presented": pp_bufs[2]} if post else ({"presented": frame} if world > 1 else {})
+        dump_outputs(args.dump_outputs, dict(bufs if world == 1 else {}, **shown), WIDTH, HEIGHT)
 
-    # ---- algorithmic bytes of the traversal kernels: one instrumented (counting) replay of a step, untimed.
-    # Deterministic sampling makes every step trace the same number of rays/nodes/triangles up to the sample index.
-    r.set_flags(N.FLAG_COUNT_TRAVERSAL)
-    r.reset_stats()
-    r.render(cam, w["bg"], layers, spp, MAX_DEPTH)
-    r.wait_for_completion()
-    cnt = r.stats()
-    # ... and once more with every ray started at the root (FH_FLAG_ROOT_START): what the same hits cost in tests when no ray starts at the node of its face
-    r.set_flags(N.FLAG_COUNT_TRAVERSAL | N.FLAG_ROOT_START)
-    r.reset_stats()
-    r.render(cam, w["bg"], layers, spp, MAX_DEPTH)
-    r.wait_for_completion()
-    cnt_root = r.stats()
+    extra_steps = 0  # steps rendered into the local layers after the timed region
+    if args.full:
+        # ---- which kernel dominates: with two passes in flight a HIP-event span also contains the other stream's work (the register-heavy shade
+        # kernels wait for CUs the traversal kernels hold), so the ranking comes from one more, untimed step whose passes run one after the other
+        # (FH_FLAG_SERIAL_PASSES): every kernel alone on the GPU.  The roofline's launch time stays the one measured over the timed region.
+        r.set_flags(N.FLAG_TIME_KERNELS | N.FLAG_SERIAL_PASSES)
+        r.reset_stats()
+        r.render(cam, w["bg"], layers, spp, MAX_DEPTH)
+        r.wait_for_completion()
+        alone = r.stats()
+
+        # ---- algorithmic bytes of the traversal kernels: one instrumented (counting) replay of a step, untimed.
+        # Deterministic sampling makes every step trace the same number of rays/nodes/triangles up to the sample index.
+        r.set_flags(N.FLAG_COUNT_TRAVERSAL)
+        r.reset_stats()
+        r.render(cam, w["bg"], layers, spp, MAX_DEPTH)
+        r.wait_for_completion()
+        cnt = r.stats()
+        # ... and once more with every ray started at the root (FH_FLAG_ROOT_START): what the same hits cost in tests when no ray starts at the node of its face
+        r.set_flags(N.FLAG_COUNT_TRAVERSAL | N.FLAG_ROOT_START)
+        r.reset_stats()
+        r.render(cam, w["bg"], layers, spp, MAX_DEPTH)
+        r.wait_for_completion()
+        cnt_root = r.stats()
+        extra_steps = 3
     r.set_flags(0)
 
     if args.check_frame and world > 1 and rank == 0:
-        total_spp = spp * (warmup + steps + 3)  # + the serial step + the two counting replays, which only the local layers saw
+        total_spp = spp * (warmup + steps + extra_steps)  # + (--full) the serial step and the two counting replays, which only the local layers saw
         r2 = F.Renderer(local_rank)
         r2.load_scene(sc)
         r2.build_ias()
@@ -752,15 +789,16 @@ def main():
         others["beauty"] = full
         layers2 = F.RenderLayer(r2, WIDTH, HEIGHT, pointers={n: t.data_ptr() for n, t in others.items()})
         # 1. the frame assembled from every rank's tiles after the last timed step against an unsharded render of as many samples
-        r2.render(cam, w["bg"], layers2, total_spp - 3 * spp, MAX_DEPTH)
+        r2.render(cam, w["bg"], layers2, total_spp - extra_steps * spp, MAX_DEPTH)
         r2.wait_for_completion()
         whole = bool((full.view(torch.int32) == frame.view(torch.int32)).all().item())
         print(f"check-frame: frame gathered from {world} ranks bit-identical to the unsharded render: {whole}", file=sys.stderr, flush=True)
         if not whole:
             raise SystemExit("gathered frame differs from the unsharded one")
-        # 2. this rank's tiles after the serial step and the counting replays (three more steps that only the local layers saw)
-        r2.render(cam, w["bg"], layers2, 3 * spp, MAX_DEPTH)
-        r2.wait_for_completion()
+        # 2. this rank's tiles after the serial step and the counting replays of --full (three more steps that only the local layers saw)
+        if extra_steps:
+            r2.render(cam, w["bg"], layers2, extra_steps * spp, MAX_DEPTH)
+            r2.wait_for_completion()
         own0 = torch.from_numpy(D.tile_ownership(WIDTH, HEIGHT, 0, world).astype(np.int64)).to(dev)
         r.pack_owned(bufs["beauty"].data_ptr(), 4, packed.data_ptr())
         r.wait_for_completion()
@@ -772,123 +810,6 @@ def main():
     if rank == 0:
         samples = WIDTH * HEIGHT * spp * steps
         value = samples / dt / 1e6
-        node_bytes = timed["bvh_node_bytes"] / max(timed["bvh_nodes"], 1)  # 64 B wide nodes (64 B for the binary fallback too)
-        paths_per_step = cnt["paths"]
-        small_tree = timed["bvh_nodes"] < 4096  # traced in fixed 64-ray batches (render.hip: render_submit), everything else by the streaming kernels
-        # every timed kernel family: summed HIP-event ms over the timed steps, launches, algorithmic bytes per step from the counted replay, ms of one step alone
-        fam = {
-            "k_trace_closest_stream": dict(ms=timed["trace_closest_ms"], launches=timed["n_closest_launches"], alone=alone["trace_closest_ms"], key="closest",
-                                           bytes=cnt["rays_closest"] * (RAY_BYTES + HIT_BYTES) + cnt["nodes_closest"] * node_bytes + cnt["tris_closest"] * TRI_BYTES),
-            "k_trace_secondary_stream": dict(ms=timed["trace_shadow_ms"], launches=timed["n_shadow_launches"], alone=alone["trace_shadow_ms"], key="shadow",
-                                             bytes=cnt["rays_shadow"] * (RAY_BYTES + HIT_BYTES) + cnt["nodes_shadow"] * node_bytes + cnt["tris_shadow"] * TRI_BYTES),
-            "k_shade": dict(ms=timed["shade_ms"], launches=timed["n_shade_launches"], alone=alone["shade_ms"], bytes=cnt["shaded_hits"] * SHADE_BYTES_PER_HIT),
-            "k_tail": dict(ms=timed["tail_ms"], launches=timed["n_tail_launches"], alone=alone["tail_ms"], bytes=None),
-            "k_generate": dict(ms=timed["generate_ms"], launches=timed["n_generate_launches"], alone=alone["generate_ms"], bytes=paths_per_step * GENERATE_BYTES_PER_PATH),
-            "k_accumulate": dict(ms=timed["accumulate_ms"], launches=timed["n_accumulate_launches"], alone=alone["accumulate_ms"], bytes=paths_per_step * ACCUMULATE_BYTES_PER_SAMPLE),
-        }
-        dom = max((k for k in fam if fam[k]["bytes"] is not None), key=lambda k: fam[k]["alone"])  # (the fused tail has no counted bytes of its own)
-        f = fam[dom]
-        launches = max(f["launches"], 1)
-        bytes_per_launch = f["bytes"] * steps / launches
-        avg_ms = f["ms"] / launches
-        avg_alone_ms = f["alone"] / max(launches / steps, 1)
-        alg_gbs = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        # the dominant kernel's own counters, from a counter run of THIS pass size or not at all (a shard's launches are not the launches the counters saw either)
-        pmc_k, unusable = usable_counters(args.config, dom, spp, timed["n_passes"], steps) if world == 1 else (None, None)
-        pmc = pmc_k
-        traffic = pmc_k.get("traffic_bytes_per_launch") if pmc_k else None
-        kernel_name = dom.replace("_stream", "_coop") if dom.startswith("k_trace") and small_tree else dom
-        where = ("rank 0 shard" if world > 1 else "whole frame")
-        if dom.startswith("k_trace"):
-            roof = traversal_roofline(cnt, timed, f["key"], steps, launches, avg_ms, avg_alone_ms, bytes_per_launch, kernel_name, where, (bw_read, bw_copy), traffic)
-        elif pmc_k and pmc_k.get("valu_insts_per_launch") and dom in STATIC_FMA_SHARE and avg_ms > 0:
-            # ---- the shade / generate kernels are VALU-issue-bound as well (software transcendentals, hashing, divisions): executed VALU instructions per launch (counter
-            # run of the same launch size) x the issue cycles an instruction of the kernel's mix costs, against the issue cycles the chip has
-            share = STATIC_FMA_SHARE[dom]
-            cyc = max(share / VALU_FMA_PEAK_PER_CYCLE, (1.0 - share) / VALU_OTHER_PEAK_PER_CYCLE)
-            issue_cycles_per_launch = pmc_k["valu_insts_per_launch"] * cyc
-            achieved = issue_cycles_per_launch / (avg_ms * 1e-3) / 1e9
-            peak = N_SIMDS * NOMINAL_CLOCK_GHZ
-            roof = {"bound": "valu_issue", "kernel": kernel_name, "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "G SIMD issue cycles/s", "frac": round(achieved / peak, 5), "traffic": traffic,
-                    "avg_launch_ms": round(avg_ms, 4), "launches": int(f["launches"]), "avg_launch_ms_alone": round(avg_alone_ms, 4),
-                    "frac_alone": round(issue_cycles_per_launch / (avg_alone_ms * 1e-3) / 1e9 / peak, 5) if avg_alone_ms > 0 else None,
-                    "issue_model": {"valu_insts_per_launch": pmc_k["valu_insts_per_launch"], "fma_class_share": share, "cycles_per_instruction_of_this_mix": round(cyc, 3),
-                                    "source": "SQ_INSTS_VALU of the kernel (" + str(pmc_k.get("file")) + "), class rates from profiles/r03_issue_peak.txt, class share from the code object (tools/isa_stats.py)"},
-                    "algorithmic_bytes_per_launch": int(bytes_per_launch), "algorithmic_gbs": round(alg_gbs, 1), "algorithmic_gbs_over_hbm_peak": round(alg_gbs / HBM_PEAK_GBS, 5),
-                    "measured_hbm_gbs": {"read": round(bw_read, 1), "copy": round(bw_copy, 1)},
-                    "note": where + "; achieved = executed VALU instructions per launch x issue cycles per instruction of the kernel's mix / launch time inside the timed region (passes on the other streams share the "
-                            "GPU with the launch: *_alone is the same launch with the GPU to itself); algorithmic_* = DESIGN.md 4 bytes per hit, for reference"}
-        else:
-            roof = {"bound": "hbm", "kernel": kernel_name, "achieved": round(alg_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(alg_gbs / HBM_PEAK_GBS, 5), "traffic": traffic,
-                    "avg_launch_ms": round(avg_ms, 4), "launches": int(f["launches"]), "algorithmic_bytes_per_launch": int(bytes_per_launch), "avg_launch_ms_alone": round(avg_alone_ms, 4),
-                    "frac_alone": round(bytes_per_launch / (avg_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if avg_alone_ms > 0 else None,
-                    "measured_hbm_gbs": {"read": round(bw_read, 1), "copy": round(bw_copy, 1)}, "algorithmic_gbs_over_measured_copy": round(alg_gbs / bw_copy, 5) if bw_copy > 0 else None,  # (a ratio, not a fraction of a roof: cache-served bytes can exceed the copy rate)
-                    "note": where + "; achieved = algorithmic bytes (DESIGN.md 4) / kernel time inside the timed region; the kernel waits on scattered 16-byte accesses to path and face records and on VALU "
-                            "(BSDF, software transcendentals), so the algorithmic figure is a lower bound of what moves"}
-        if dom.startswith("k_trace"):
-            roof["kernel_info"] = r.kernel_info(0 if f.get("key") == "closest" else 1)  # registers / LDS / scratch / workgroups per CU of the variant that ran
-            # `frac` counts the tests that were DONE.  Where the library starts first-hit rays at the node of the face they leave, the same hits need fewer
-            # tests than a walk from the root: the replay with FH_FLAG_ROOT_START counts those, and the same launch time priced with them is what `frac` would be if the
-            # avoided tests still counted as work
-            im_, key_ = issue_model(), f["key"]
-            ck_ = "closest" if key_ == "closest" else "shadow"
-            wn0, wt0 = cnt_root[f"wave_node_steps_{key_}"], cnt_root[f"wave_tri_steps_{key_}"]
-            cyc0 = (wn0 * im_["node"] + wt0 * im_["tri"]) * steps / launches
-            roof["from_root"] = {"nodes_per_ray": round(cnt_root[f"nodes_{ck_}"] / max(cnt_root[f"rays_{ck_}"], 1), 2), "triangles_per_ray": round(cnt_root[f"tris_{ck_}"] / max(cnt_root[f"rays_{ck_}"], 1), 2),
-                                 "wave_node_tests_per_launch": int(wn0 * steps / launches), "wave_tri_tests_per_launch": int(wt0 * steps / launches),
-                                 "share_of_those_tests_done": round((cnt[f"wave_node_steps_{key_}"] * im_["node"] + cnt[f"wave_tri_steps_{key_}"] * im_["tri"]) / max(wn0 * im_["node"] + wt0 * im_["tri"], 1.0), 4),
-                                 "frac_priced_with_these_tests": round(cyc0 / (avg_ms * 1e-3) / 1e9 / (N_SIMDS * NOMINAL_CLOCK_GHZ), 5) if avg_ms > 0 else None,
-                                 "note": "the counting replay with every ray started at the root (FH_FLAG_ROOT_START): the tests a walk from the root needs for the same hits; frac counts the tests done, "
-                                         "so it falls when tests are avoided -- frac_priced_with_these_tests is this run's launch time priced with the root-start test counts"}
-        if pmc_k and avg_alone_ms > 0:  # the counters are collected with the kernels serialised, so they are priced against the kernel's time alone
-            if traffic:
-                # what the fabric-side counters saw of this kernel against the HBM peak (2 x FETCH_SIZE + WRITE_SIZE of the counter run over this run's launch time alone)
-                roof["frac_hbm_measured"] = roof["hbm_traffic_frac"] = round(traffic / (avg_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-            if pmc_k.get("valu_insts_per_launch"):
-                per_cycle = pmc_k["valu_insts_per_launch"] / N_SIMDS / (avg_alone_ms * 1e-3) / 1e9 / (roof.get("clock_ghz_in_kernel") or NOMINAL_CLOCK_GHZ)
-                fs = fma_share_of(pmc_k.get("kernel", ""))
-                if fs:
-                    # MEASURED VALU busy share: executed VALU instructions per cycle and SIMD (SQ_INSTS_VALU of the counter run / this run's launch time alone x 1024 SIMDs x the clock held)
-                    # x the issue cycles an instruction of the kernel's static mix costs (FMA-class 2.2, everything else 4.1 cycles, the two classes side by side)
-                    cyc_mix = max(fs["share"] / VALU_FMA_PEAK_PER_CYCLE, (1.0 - fs["share"]) / VALU_OTHER_PEAK_PER_CYCLE)
-                    roof["valu_busy_measured"] = round(per_cycle * cyc_mix, 4)
-                    roof["valu_busy_formula"] = {"fma_class_share_static": fs["share"], "share_from": fs["source"], "share_stale": fs["stale"], "cycles_per_instruction_of_this_mix": round(cyc_mix, 3),
-                                                 "is": "SQ_INSTS_VALU per launch / (avg_launch_ms_alone x 1024 SIMDs x clock_ghz_in_kernel) x max(share x 2.2, (1 - share) x 4.1)"}
-                roof["valu"] = {"insts_per_launch": pmc_k["valu_insts_per_launch"], "insts_per_cycle_per_simd": round(per_cycle, 4),
-                                "peak_per_cycle_per_simd": {"fma_mul_add_f32": round(VALU_FMA_PEAK_PER_CYCLE, 3), "everything_else": round(VALU_OTHER_PEAK_PER_CYCLE, 3)},
-                                "lane_utilisation": pmc_k.get("valu_lane_utilisation"), "wait_any_frac_of_wave_cycles": pmc_k.get("wait_any_frac_of_wave_cycles")}
-            if pmc_k.get("vl1d"):
-                # the second limit of the traversal kernels: every lane of a node or triangle load asks the vector L1 for its own line (profiles/r03_issue_peak.txt,
-                # "global_load_dwordx4, 64 lanes in 64 L1-resident lines", holds the rate the L1 serves such loads at)
-                roof["vl1d"] = dict(pmc_k["vl1d"], note="TCP_TOTAL_CACHE_ACCESSES_sum / 256 CUs / (GRBM_GUI_ACTIVE / 8 XCDs) and TA_TA_BUSY_sum likewise, kernels serialised")
-            roof["counters_from"] = pmc_k.get("file")
-            # the counters were collected by another process, possibly from another build: they describe THIS library only if the device sources and the kernel's
-            # registers / LDS / scratch are what they were then (tools/collect_profile4.py stores both in the file)
-            now = {"source_fingerprint": source_fingerprint(), "kernel_info": r.kernel_info(0 if f.get("key") == "closest" else 1) if dom.startswith("k_trace") else None}
-            then = {"source_fingerprint": pmc_k.get("source_fingerprint"), "kernel_info": pmc_k.get("kernel_info")}
-            same_kernel = then["kernel_info"] is None or now["kernel_info"] is None or all(then["kernel_info"].get(k) == now["kernel_info"].get(k) for k in ("vgprs", "static_lds_bytes", "scratch_bytes"))
-            roof["counters_stale"] = not (then["source_fingerprint"] == now["source_fingerprint"] and same_kernel)
-            roof["counters_built_from"] = {"git_head": pmc_k.get("git_head"), "source_fingerprint": then["source_fingerprint"], "this_run": now["source_fingerprint"]}
-        if unusable:
-            roof["counters_unusable"] = unusable
-        freeze_roofline_fields(roof)
-        shade = shade_record(r, args.config, spp, timed, alone, cnt, steps) if world == 1 else None
-        sec = lambda k: fam[k]["alone"] * 1e-3  # seconds per step with the kernel alone on the GPU
-        rates = {"closest_hit_grays_per_s": round(cnt["rays_closest"] / sec("k_trace_closest_stream") / 1e9, 3) if sec("k_trace_closest_stream") > 0 else None,
-                 "secondary_grays_per_s": round(cnt["rays_shadow"] / sec("k_trace_secondary_stream") / 1e9, 3) if sec("k_trace_secondary_stream") > 0 else None,
-                 "shaded_ghits_per_s": round(cnt["shaded_hits"] / sec("k_shade") / 1e9, 3) if sec("k_shade") > 0 else None,
-                 "per_sample": {"closest_rays": round(cnt["rays_closest"] / max(paths_per_step, 1), 4), "secondary_rays": round(cnt["rays_shadow"] / max(paths_per_step, 1), 4),
-                                "shaded_hits": round(cnt["shaded_hits"] / max(paths_per_step, 1), 4)},
-                 "note": "each kernel alone on the GPU; per_sample: what one camera sample of this workload costs -- on configs[2] 84 % of the camera rays miss the scene bounds (the thin-lens model "
-                         "puts the lens a focal length behind the camera origin) and end in k_generate, so Msamples/s of this workload is not a general-scene number: configs[3] (an interior, every ray hits) is"}
-        # ---- the whole frame: algorithmic bytes of every counted kernel family over the step, and the fabric-side bytes the counters saw over a step
-        alg_step = sum(v["bytes"] for v in fam.values() if v["bytes"] is not None)
-        whole = {"algorithmic_bytes_per_step": int(alg_step), "algorithmic_gbs": round(alg_step / (dt / steps) / 1e9, 1), "algorithmic_gbs_over_hbm_peak": round(alg_step / (dt / steps) / 1e9 / HBM_PEAK_GBS, 5),
-                 "note": "traversal + shade + generate + accumulate bytes (DESIGN.md 4) over the wall time of a step; the fused tail, route and sort kernels are not counted"}
-        if pmc and pmc.get("frame_traffic_bytes_per_spp"):
-            fb = pmc["frame_traffic_bytes_per_spp"] * spp
-            whole.update({"fabric_bytes_per_step": int(fb), "fabric_gbs": round(fb / (dt / steps) / 1e9, 1), "fabric_frac_of_hbm_peak": round(fb / (dt / steps) / 1e9 / HBM_PEAK_GBS, 5),
-                          "fabric_from": pmc.get("file")})
         sm = sorted(step_ms)
         out = {
             "metric": "Msamples/s at 1920x1080, max_depth=8" if args.config in (1, 2, 3) else f"Msamples/s at {WIDTH}x{HEIGHT}, max_depth={MAX_DEPTH}", "value": round(value, 3), "unit": "Msamples/s",
@@ -902,36 +823,154 @@ def main():
                        "post": "bloom + chromatic aberration + tone map on the whole frame, inside the timed region" if post else "none"},
             "step_ms": {"min": round(sm[0], 3), "median": round(sm[len(sm) // 2], 3), "max": round(sm[-1], 3)},
             "source_fingerprint": source_fingerprint(),  # of the device sources this library was built from (what profiles/*_traffic_config*.json are checked against)
-            "roofline": roof, **({"shade": shade} if shade else {}), "rates": rates, "whole_frame": whole,
             "kernel_ms_per_step": {"trace_closest": round(timed["trace_closest_ms"] / steps, 3), "trace_secondary": round(timed["trace_shadow_ms"] / steps, 3), "shade": round(timed["shade_ms"] / steps, 3),
                                    "tail": round(timed["tail_ms"] / steps, 3), "generate": round(timed["generate_ms"] / steps, 3), "accumulate": round(timed["accumulate_ms"] / steps, 3),
                                    "route_and_sort": round(timed["queue_ms"] / steps, 3), "render_total": round(timed["render_ms"] / steps, 3),
                                    "note": "HIP-event spans on the library's three streams; passes overlap, so the spans do not add up to render_total"},
-            "kernel_ms_per_step_alone": {"trace_closest": round(alone["trace_closest_ms"], 3), "trace_secondary": round(alone["trace_shadow_ms"], 3), "shade": round(alone["shade_ms"], 3),
-                                         "tail": round(alone["tail_ms"], 3), "generate": round(alone["generate_ms"], 3), "accumulate": round(alone["accumulate_ms"], 3),
-                                         "route_and_sort": round(alone["queue_ms"], 3), "render_total": round(alone["render_ms"], 3),
-                                         "note": "one untimed step with FH_FLAG_SERIAL_PASSES: every kernel alone on the GPU (these add up)"},
             **({"post_chain": {"ms_per_frame": round(timed["post_ms"] / max(timed["n_post_launches"], 1), 3), "frames": int(timed["n_post_launches"]),
                                "algorithmic_gbs": round(WIDTH * HEIGHT * (16 + 16 + 16 + 16 + 16 + 16 + 16) / (timed["post_ms"] / max(timed["n_post_launches"], 1) * 1e-3) / 1e9, 1) if timed["post_ms"] > 0 else None,
                                "note": "bloom threshold (16 B in, 16 out per pixel) + 33x33 blur through a 48x48 LDS tile (16 + 16 in, 16 out) + tone map (16 in, 16 out); the blur is LDS-bound: 1089 LDS taps per pixel"}}
                if post else {}),
             "bvh": {"build_ms": round(timed["bvh_build_ms"], 2), "nodes": timed["bvh_nodes"], "node_bytes": timed["bvh_node_bytes"], "tri_bytes": timed["bvh_tri_bytes"], "depth": timed["bvh_depth"]},
         }
-        if world == 1:
-            sm_ = scaling_model(args.config, spp)
-            if sm_:
-                out["scaling_model"] = sm_
-        if extras:
-            rows = (HEIGHT // 2 - 4, HEIGHT // 2 + 4)  # eight rows through the middle of the frame (every configuration has geometry there)
-            out["parity"] = parity_block(r, w, cam, layers2, bufs2, rows, 2)
-            out["latency"] = latency_block(r, w, cam, layers2)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(w)
-            out["cpu_baseline_1t"] = cpu_baseline_1t()
-        if extras and args.config == 2 and not args.no_general_scene:
-            r.close()  # (the headline's path pools go back to the device first)
-            r = None
-            out["general_scene"] = general_scene_block(local_rank, tmp.name, (bw_read, bw_copy), pool_gb=args.pool_gb)
+        if args.full:
+            node_bytes = timed["bvh_node_bytes"] / max(timed["bvh_nodes"], 1)  # 64 B wide nodes (64 B for the binary fallback too)
+            paths_per_step = cnt["paths"]
+            small_tree = timed["bvh_nodes"] < 4096  # traced in fixed 64-ray batches (render.hip: render_submit), everything else by the streaming kernels
+            # every timed kernel family: summed HIP-event ms over the timed steps, launches, algorithmic bytes per step from the counted replay, ms of one step alone
+            fam = {
+                "k_trace_closest_stream": dict(ms=timed["trace_closest_ms"], launches=timed["n_closest_launches"], alone=alone["trace_closest_ms"], key="closest",
+                                               bytes=cnt["rays_closest"] * (RAY_BYTES + HIT_BYTES) + cnt["nodes_closest"] * node_bytes + cnt["tris_closest"] * TRI_BYTES),
+                "k_trace_secondary_stream": dict(ms=timed["trace_shadow_ms"], launches=timed["n_shadow_launches"], alone=alone["trace_shadow_ms"], key="shadow",
+                                                 bytes=cnt["rays_shadow"] * (RAY_BYTES + HIT_BYTES) + cnt["nodes_shadow"] * node_bytes + cnt["tris_shadow"] * TRI_BYTES),
+                "k_shade": dict(ms=timed["shade_ms"], launches=timed["n_shade_launches"], alone=alone["shade_ms"], bytes=cnt["shaded_hits"] * SHADE_BYTES_PER_HIT),
+                "k_tail": dict(ms=timed["tail_ms"], launches=timed["n_tail_launches"], alone=alone["tail_ms"], bytes=None),
+                "k_generate": dict(ms=timed["generate_ms"], launches=timed["n_generate_launches"], alone=alone["generate_ms"], bytes=paths_per_step * GENERATE_BYTES_PER_PATH),
+                "k_accumulate": dict(ms=timed["accumulate_ms"], launches=timed["n_accumulate_launches"], alone=alone["accumulate_ms"], bytes=paths_per_step * ACCUMULATE_BYTES_PER_SAMPLE),
+            }
+            dom = max((k for k in fam if fam[k]["bytes"] is not None), key=lambda k: fam[k]["alone"])  # (the fused tail has no counted bytes of its own)
+            f = fam[dom]
+            launches = max(f["launches"], 1)
+            bytes_per_launch = f["bytes"] * steps / launches
+            avg_ms = f["ms"] / launches
+            avg_alone_ms = f["alone"] / max(launches / steps, 1)
+            alg_gbs = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            # the dominant kernel's own counters, from a counter run of THIS pass size or not at all (a shard's launches are not the launches the counters saw either)
+            pmc_k, unusable = usable_counters(args.config, dom, spp, timed["n_passes"], steps) if world == 1 else (None, None)
+            pmc = pmc_k
+            traffic = pmc_k.get("traffic_bytes_per_launch") if pmc_k else None
+            kernel_name = dom.replace("_stream", "_coop") if dom.startswith("k_trace") and small_tree else dom
+            where = ("rank 0 shard" if world > 1 else "whole frame")
+            if dom.startswith("k_trace"):
+                roof = traversal_roofline(cnt, timed, f["key"], steps, launches, avg_ms, avg_alone_ms, bytes_per_launch, kernel_name, where, (bw_read, bw_copy), traffic)
+            elif pmc_k and pmc_k.get("valu_insts_per_launch") and dom in STATIC_FMA_SHARE and avg_ms > 0:
+                # ---- the shade / generate kernels are VALU-issue-bound as well (software transcendentals, hashing, divisions): executed VALU instructions per launch (counter
+                # run of the same launch size) x the issue cycles an instruction of the kernel's mix costs, against the issue cycles the chip has
+                share = STATIC_FMA_SHARE[dom]
+                cyc = max(share / VALU_FMA_PEAK_PER_CYCLE, (1.0 - share) / VALU_OTHER_PEAK_PER_CYCLE)
+                issue_cycles_per_launch = pmc_k["valu_insts_per_launch"] * cyc
+                achieved = issue_cycles_per_launch / (avg_ms * 1e-3) / 1e9
+                peak = N_SIMDS * NOMINAL_CLOCK_GHZ
+                roof = {"bound": "valu_issue", "kernel": kernel_name, "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "G SIMD issue cycles/s", "frac": round(achieved / peak, 5), "traffic": traffic,
+                        "avg_launch_ms": round(avg_ms, 4), "launches": int(f["launches"]), "avg_launch_ms_alone": round(avg_alone_ms, 4),
+                        "frac_alone": round(issue_cycles_per_launch / (avg_alone_ms * 1e-3) / 1e9 / peak, 5) if avg_alone_ms > 0 else None,
+                        "issue_model": {"valu_insts_per_launch": pmc_k["valu_insts_per_launch"], "fma_class_share": share, "cycles_per_instruction_of_this_mix": round(cyc, 3),
+                                        "source": "SQ_INSTS_VALU of the kernel (" + str(pmc_k.get("file")) + "), class rates from profiles/r03_issue_peak.txt, class share from the code object (tools/isa_stats.py)"},
+                        "algorithmic_bytes_per_launch": int(bytes_per_launch), "algorithmic_gbs": round(alg_gbs, 1), "algorithmic_gbs_over_hbm_peak": round(alg_gbs / HBM_PEAK_GBS, 5),
+                        "measured_hbm_gbs": {"read": round(bw_read, 1), "copy": round(bw_copy, 1)},
+                        "note": where + "; achieved = executed VALU instructions per launch x issue cycles per instruction of the kernel's mix / launch time inside the timed region (passes on the other streams share the "
+                                "GPU with the launch: *_alone is the same launch with the GPU to itself); algorithmic_* = DESIGN.md 4 bytes per hit, for reference"}
+            else:
+                roof = {"bound": "hbm", "kernel": kernel_name, "achieved": round(alg_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(alg_gbs / HBM_PEAK_GBS, 5), "traffic": traffic,
+                        "avg_launch_ms": round(avg_ms, 4), "launches": int(f["launches"]), "algorithmic_bytes_per_launch": int(bytes_per_launch), "avg_launch_ms_alone": round(avg_alone_ms, 4),
+                        "frac_alone": round(bytes_per_launch / (avg_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if avg_alone_ms > 0 else None,
+                        "measured_hbm_gbs": {"read": round(bw_read, 1), "copy": round(bw_copy, 1)}, "algorithmic_gbs_over_measured_copy": round(alg_gbs / bw_copy, 5) if bw_copy > 0 else None,  # (a ratio, not a fraction of a roof: cache-served bytes can exceed the copy rate)
+                        "note": where + "; achieved = algorithmic bytes (DESIGN.md 4) / kernel time inside the timed region; the kernel waits on scattered 16-byte accesses to path and face records and on VALU "
+                                "(BSDF, software transcendentals), so the algorithmic figure is a lower bound of what moves"}
+            if dom.startswith("k_trace"):
+                roof["kernel_info"] = r.kernel_info(0 if f.get("key") == "closest" else 1)  # registers / LDS / scratch / workgroups per CU of the variant that ran
+                # `frac` counts the tests that were DONE.  Where the library starts first-hit rays at the node of the face they leave, the same hits need fewer
+                # tests than a walk from the root: the replay with FH_FLAG_ROOT_START counts those, and the same launch time priced with them is what `frac` would be if the
+                # avoided tests still counted as work
+                im_, key_ = issue_model(), f["key"]
+                ck_ = "closest" if key_ == "closest" else "shadow"
+                wn0, wt0 = cnt_root[f"wave_node_steps_{key_}"], cnt_root[f"wave_tri_steps_{key_}"]
+                cyc0 = (wn0 * im_["node"] + wt0 * im_["tri"]) * steps / launches
+                roof["from_root"] = {"nodes_per_ray": round(cnt_root[f"nodes_{ck_}"] / max(cnt_root[f"rays_{ck_}"], 1), 2), "triangles_per_ray": round(cnt_root[f"tris_{ck_}"] / max(cnt_root[f"rays_{ck_}"], 1), 2),
+                                     "wave_node_tests_per_launch": int(wn0 * steps / launches), "wave_tri_tests_per_launch": int(wt0 * steps / launches),
+                                     "share_of_those_tests_done": round((cnt[f"wave_node_steps_{key_}"] * im_["node"] + cnt[f"wave_tri_steps_{key_}"] * im_["tri"]) / max(wn0 * im_["node"] + wt0 * im_["tri"], 1.0), 4),
+                                     "frac_priced_with_these_tests": round(cyc0 / (avg_ms * 1e-3) / 1e9 / (N_SIMDS * NOMINAL_CLOCK_GHZ), 5) if avg_ms > 0 else None,
+                                     "note": "the counting replay with every ray started at the root (FH_FLAG_ROOT_START): the tests a walk from the root needs for the same hits; frac counts the tests done, "
+                                             "so it falls when tests are avoided -- frac_priced_with_these_tests is this run's launch time priced with the root-start test counts"}
+            if pmc_k and avg_alone_ms > 0:  # the counters are collected with the kernels serialised, so they are priced against the kernel's time alone
+                if traffic:
+                    # what the fabric-side counters saw of this kernel against the HBM peak (2 x FETCH_SIZE + WRITE_SIZE of the counter run over this run's launch time alone)
+                    roof["frac_hbm_measured"] = roof["hbm_traffic_frac"] = round(traffic / (avg_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                if pmc_k.get("valu_insts_per_launch"):
+                    per_cycle = pmc_k["valu_insts_per_launch"] / N_SIMDS / (avg_alone_ms * 1e-3) / 1e9 / (roof.get("clock_ghz_in_kernel") or NOMINAL_CLOCK_GHZ)
+                    fs = fma_share_of(pmc_k.get("kernel", ""))
+                    if fs:
+                        # MEASURED VALU busy share: executed VALU instructions per cycle and SIMD (SQ_INSTS_VALU of the counter run / this run's launch time alone x 1024 SIMDs x the clock held)
+                        # x the issue cycles an instruction of the kernel's static mix costs (FMA-class 2.2, everything else 4.1 cycles, the two classes side by side)
+                        cyc_mix = max(fs["share"] / VALU_FMA_PEAK_PER_CYCLE, (1.0 - fs["share"]) / VALU_OTHER_PEAK_PER_CYCLE)
+                        roof["valu_busy_measured"] = round(per_cycle * cyc_mix, 4)
+                        roof["valu_busy_formula"] = {"fma_class_share_static": fs["share"], "share_from": fs["source"], "share_stale": fs["stale"], "cycles_per_instruction_of_this_mix": round(cyc_mix, 3),
+                                                     "is": "SQ_INSTS_VALU per launch / (avg_launch_ms_alone x 1024 SIMDs x clock_ghz_in_kernel) x max(share x 2.2, (1 - share) x 4.1)"}
+                    roof["valu"] = {"insts_per_launch": pmc_k["valu_insts_per_launch"], "insts_per_cycle_per_simd": round(per_cycle, 4),
+                                    "peak_per_cycle_per_simd": {"fma_mul_add_f32": round(VALU_FMA_PEAK_PER_CYCLE, 3), "everything_else": round(VALU_OTHER_PEAK_PER_CYCLE, 3)},
+                                    "lane_utilisation": pmc_k.get("valu_lane_utilisation"), "wait_any_frac_of_wave_cycles": pmc_k.get("wait_any_frac_of_wave_cycles")}
+                if pmc_k.get("vl1d"):
+                    # the second limit of the traversal kernels: every lane of a node or triangle load asks the vector L1 for its own line (profiles/r03_issue_peak.txt,
+                    # "global_load_dwordx4, 64 lanes in 64 L1-resident lines", holds the rate the L1 serves such loads at)
+                    roof["vl1d"] = dict(pmc_k["vl1d"], note="TCP_TOTAL_CACHE_ACCESSES_sum / 256 CUs / (GRBM_GUI_ACTIVE / 8 XCDs) and TA_TA_BUSY_sum likewise, kernels serialised")
+                roof["counters_from"] = pmc_k.get("file")
+                # the counters were collected by another process, possibly from another build: they describe THIS library only if the device sources and the kernel's
+                # registers / LDS / scratch are what they were then (tools/collect_profile4.py stores both in the file)
+                now = {"source_fingerprint": source_fingerprint(), "kernel_info": r.kernel_info(0 if f.get("key") == "closest" else 1) if dom.startswith("k_trace") else None}
+                then = {"source_fingerprint": pmc_k.get("source_fingerprint"), "kernel_info": pmc_k.get("kernel_info")}
+                same_kernel = then["kernel_info"] is None or now["kernel_info"] is None or all(then["kernel_info"].get(k) == now["kernel_info"].get(k) for k in ("vgprs", "static_lds_bytes", "scratch_bytes"))
+                roof["counters_stale"] = not (then["source_fingerprint"] == now["source_fingerprint"] and same_kernel)
+                roof["counters_built_from"] = {"git_head": pmc_k.get("git_head"), "source_fingerprint": then["source_fingerprint"], "this_run": now["source_fingerprint"]}
+            if unusable:
+                roof["counters_unusable"] = unusable
+            freeze_roofline_fields(roof)
+            shade = shade_record(r, args.config, spp, timed, alone, cnt, steps) if world == 1 else None
+            sec = lambda k: fam[k]["alone"] * 1e-3  # seconds per step with the kernel alone on the GPU
+            rates = {"closest_hit_grays_per_s": round(cnt["rays_closest"] / sec("k_trace_closest_stream") / 1e9, 3) if sec("k_trace_closest_stream") > 0 else None,
+                     "secondary_grays_per_s": round(cnt["rays_shadow"] / sec("k_trace_secondary_stream") / 1e9, 3) if sec("k_trace_secondary_stream") > 0 else None,
+                     "shaded_ghits_per_s": round(cnt["shaded_hits"] / sec("k_shade") / 1e9, 3) if sec("k_shade") > 0 else None,
+                     "per_sample": {"closest_rays": round(cnt["rays_closest"] / max(paths_per_step, 1), 4), "secondary_rays": round(cnt["rays_shadow"] / max(paths_per_step, 1), 4),
+                                    "shaded_hits": round(cnt["shaded_hits"] / max(paths_per_step, 1), 4)},
+                     "note": "each kernel alone on the GPU; per_sample: what one camera sample of this workload costs -- on configs[2] 84 % of the camera rays miss the scene bounds (the thin-lens model "
+                             "puts the lens a focal length behind the camera origin) and end in k_generate, so Msamples/s of this workload is not a general-scene number: configs[3] (an interior, every ray hits) is"}
+            # ---- the whole frame: algorithmic bytes of every counted kernel family over the step, and the fabric-side bytes the counters saw over a step
+            alg_step = sum(v["bytes"] for v in fam.values() if v["bytes"] is not None)
+            whole = {"algorithmic_bytes_per_step": int(alg_step), "algorithmic_gbs": round(alg_step / (dt / steps) / 1e9, 1), "algorithmic_gbs_over_hbm_peak": round(alg_step / (dt / steps) / 1e9 / HBM_PEAK_GBS, 5),
+                     "note": "traversal + shade + generate + accumulate bytes (DESIGN.md 4) over the wall time of a step; the fused tail, route and sort kernels are not counted"}
+            if pmc and pmc.get("frame_traffic_bytes_per_spp"):
+                fb = pmc["frame_traffic_bytes_per_spp"] * spp
+                whole.update({"fabric_bytes_per_step": int(fb), "fabric_gbs": round(fb / (dt / steps) / 1e9, 1), "fabric_frac_of_hbm_peak": round(fb / (dt / steps) / 1e9 / HBM_PEAK_GBS, 5),
+                              "fabric_from": pmc.get("file")})
+            out.update({"roofline": roof, **({"shade": shade} if shade else {}), "rates": rates, "whole_frame": whole,
+                        "kernel_ms_per_step_alone": {"trace_closest": round(alone["trace_closest_ms"], 3), "trace_secondary": round(alone["trace_shadow_ms"], 3), "shade": round(alone["shade_ms"], 3),
+                                                     "tail": round(alone["tail_ms"], 3), "generate": round(alone["generate_ms"], 3), "accumulate": round(alone["accumulate_ms"], 3),
+                                                     "route_and_sort": round(alone["queue_ms"], 3), "render_total": round(alone["render_ms"], 3),
+                                                     "note": "one untimed step with FH_FLAG_SERIAL_PASSES: every kernel alone on the GPU (these add up)"}})
+            if world == 1:
+                sm_ = scaling_model(args.config, spp)
+                if sm_:
+                    out["scaling_model"] = sm_
+            if extras:
+                rows = (HEIGHT // 2 - 4, HEIGHT // 2 + 4)  # eight rows through the middle of the frame (every configuration has geometry there)
+                out["parity"] = parity_block(r, w, cam, layers2, bufs2, rows, 2)
+                out["latency"] = latency_block(r, w, cam, layers2)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(w)
+                out["cpu_baseline_1t"] = cpu_baseline_1t()
+            if extras and args.config == 2 and not args.no_general_scene:
+                r.close()  # (the headline's path pools go back to the device first)
+                r = None
+                out["general_scene"] = general_scene_block(local_rank, tmp.name, (bw_read, bw_copy), pool_gb=args.pool_gb)
         refused = refuse_bad_fracs(out)
         if refused:
             out["fractions_refused"] = [{"field": k, "value": v} for k, v in refused]

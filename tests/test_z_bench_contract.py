@@ -41,7 +41,7 @@ def test_two_rank_bench_step_gathers_the_unsharded_frame(tmp_path, launcher):
 
 @pytest.mark.parametrize("cfg,spp", [(1, 8), (2, 12)])
 def test_bench_line_contract(tmp_path, cfg, spp):
-    """one short run of bench.py per kind of dominant kernel (shade on the Cornell box, traversal on the soup): ONE JSON line with the metric, the roofline record
+    """one short `--full` run of bench.py per kind of dominant kernel (shade on the Cornell box, traversal on the soup): ONE JSON line with the metric, the roofline record
     (no fraction above 1, a bound that is named, launch times from HIP events), parity against the checker (bit-identical crop), the small-launch latencies and the
     whole-frame figures"""
     import json
@@ -49,7 +49,7 @@ def test_bench_line_contract(tmp_path, cfg, spp):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", str(cfg), "--spp", str(spp), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", str(cfg), "--spp", str(spp), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -95,6 +95,45 @@ def test_bench_line_contract(tmp_path, cfg, spp):
         assert r["issue_model"]["stale"] in (True, False)
         gr = g["roofline"]  # the general-scene leg of this short run is 512 spp in five passes, which is what its counter file saw: used, and then it says from where
         assert (gr.get("counters_from") and "counters_stale" in gr and gr.get("traffic")) or (gr.get("counters_unusable") and gr.get("traffic") is None and "frac_hbm_measured" not in gr)
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """a plain run (no --full) prints the headline without the records that need runs of their own, and --dump-outputs writes the last timed step's layers as float32
+    .npy files (a fixed pixel sample, at most 64 MB).  That exactly --steps steps were timed is checked twice over: ms_per_step (the timed region's wall time over --steps)
+    lies between the fastest and the slowest step the run timed one by one -- more or fewer steps in the region would move it outside -- and the layers accumulate every
+    call, so runs of --warmup 1 --steps 3 and of --warmup 2 --steps 2 (four calls of 4 spp each) must leave the same bits, while --warmup 1 --steps 2 (three calls) must not"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for i, (warmup, steps) in enumerate(((1, 3), (2, 2), (1, 2))):
+        d = tmp_path / f"dump{i}"
+        run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "1", "--spp", "4", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert run.returncode == 0, run.stderr[-3000:]
+        lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["warmup"] == warmup and out["unit"] == "Msamples/s" and out["dtype"] == "f32" and out["higher_is_better"] is True and out["ms_per_step"] > 0
+        assert abs(out["value"] - 1920 * 1080 * 4 / (out["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * out["value"]
+        sm = out["step_ms"]  # (the region also holds the final fence: a fraction of a millisecond)
+        assert sm["min"] - 2e-3 <= out["ms_per_step"] <= 1.2 * sm["max"] + 0.2, (out["ms_per_step"], sm)
+        for k in ("roofline", "shade", "rates", "whole_frame", "kernel_ms_per_step_alone", "parity", "latency", "cpu_baseline", "cpu_baseline_1t", "general_scene", "scaling_model"):
+            assert k not in out, k
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in ("beauty", "position", "depth", "normal", "texcoord", "albedo"))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 and a.shape[0] == arrs["beauty.npy"].shape[0] for a in arrs.values())
+        assert np.isfinite(arrs["beauty.npy"]).all() and arrs["beauty.npy"][:, :3].mean() > 0
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f].view(np.uint32), dumps[1][f].view(np.uint32)), f
+    assert not np.array_equal(dumps[0]["beauty.npy"].view(np.uint32), dumps[2]["beauty.npy"].view(np.uint32))
 
 
 def test_rccl_leg_on_two_gpus(tmp_path):

@@ -1,6 +1,6 @@
 """The gate of a round's end (CPU; sorts last so that a red gate hides nothing else).
 
-tools/round_end.sh runs, on a CLEAN tree and in one gpurun call, `pytest -m gpu -x -q`, `__graft_entry__.smoke()` and the default `python bench.py`, and commits the log as
+tools/round_end.sh runs, on a CLEAN tree and in one remote GPU run, `pytest -m gpu -x -q`, `__graft_entry__.smoke()` and `python bench.py --full`, and commits the log as
 profiles/rNN_final_gpu_tests.log.  The log begins with HEAD, a hash over HEAD's tree entries of every path that run depends on (tools/covered_tree_hash.py: fredholm_amd,
 include, oracle, bench.py, __graft_entry__.py, tests, profiles/*traffic*.json, profiles/*issue_peak.json) and bench.py's source fingerprint.  This test fails when the newest such log is not green or is
 about other contents than HEAD's: nothing under those paths may be committed after the round's final GPU run (round 4 committed a counter file after it, which changed what a

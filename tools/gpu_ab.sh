@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of library variants (tools/build_variant.sh) on the bench configurations: tools/gpu_ab.sh "<variant names, '' = the default build>" "<configs>"
 cd $GRAFT_REPO_ROOT
+set -- "$1" "$2" "--full ${3:-}"  # the alone-kernel times printed below need bench.py --full
 for cfg in $2; do
   for v in $1; do
     lib=fredholm_amd/libfredholm_hip.so; [ "$v" != base ] && lib=fredholm_amd/libfredholm_hip_$v.so

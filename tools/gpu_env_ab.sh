@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of environment switches on the bench configurations: tools/gpu_env_ab.sh "<VAR=val ...>" "<configs>" [extra bench args]
 cd $GRAFT_REPO_ROOT
+set -- "$1" "$2" "--full ${3:-}"  # the alone-kernel times printed below need bench.py --full
 for cfg in $2; do
   for v in $1; do
     env $v timeout -k 10 400 python3 bench.py --config $cfg --no-cpu-baseline $3 > gpurun_out/env_${v}_$cfg.json 2> gpurun_out/env_${v}_$cfg.err || { echo "$v config $cfg FAILED"; tail -3 gpurun_out/env_${v}_$cfg.err; continue; }

@@ -1,6 +1,7 @@
 #!/bin/bash
 # same-box A/B of an environment switch: tools/gpu_env_ab3.sh "<VAR=value>" "<configs>" "<bench args>"   (each configuration: off, on, off, on)
 cd $GRAFT_REPO_ROOT
+set -- "$1" "$2" "--full ${3:-}"  # the alone-kernel times printed below need bench.py --full
 mkdir -p gpurun_out
 for cfg in $2; do
   for rep in 1 2; do

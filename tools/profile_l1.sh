@@ -5,7 +5,7 @@
 tag=${1:-r03_l1}; cfg=${2:-2}; pspp=${3:-384}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python3 $R/bench.py --config $cfg"
+B="python3 $R/bench.py --full --config $cfg"
 run() { name=$1; shift
   timeout -k 5 200 rocprofv3 --pmc "$@" --output-format csv -d $R/gpurun_out/${tag}_$name -- $B --steps 1 --warmup 1 --spp $pspp --no-cpu-baseline --no-extras > $R/gpurun_out/${tag}_$name.log 2>&1; echo "pmc $name rc=$?"
 }

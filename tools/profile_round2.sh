@@ -5,7 +5,7 @@
 tag=${1:-r02_x}; cfg=${2:-2}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python3 $R/bench.py --config $cfg"
+B="python3 $R/bench.py --full --config $cfg"
 $B > $R/gpurun_out/${tag}_bench.json 2> $R/gpurun_out/${tag}_bench.err; echo "bench rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${tag}_stats -- $B --steps 4 --warmup 1 --no-cpu-baseline > $R/gpurun_out/${tag}_stats.log 2>&1
 find $R/gpurun_out/${tag}_stats -name "*kernel_stats.csv" -exec cp {} $R/gpurun_out/${tag}_kernel_stats.csv \;

@@ -1,7 +1,8 @@
 #!/bin/bash
 # tools/round_end.sh [rNN] -- the gate at the end of a round ("Next" 1c): ONE gpurun call on a CLEAN tree
 #   1. `git status --porcelain` must be empty: what runs on the GPU box is exactly HEAD
-#   2. on the box (tools/round_end_gpu.sh): pytest -m gpu -x -q, __graft_entry__.smoke(), python bench.py (the driver's default line)
+#   2. on the GPU machine (tools/round_end_gpu.sh): pytest -m gpu -x -q, __graft_entry__.smoke(), a plain python bench.py timed as a whole process (at most
+#      30 s outside its steps), python bench.py --full (the whole record)
 #   3. the log comes back as profiles/rNN_final_gpu_tests.log and begins with HEAD, the hash of the paths the GPU run depends on (tools/covered_tree_hash.py) and bench.py's
 #      source_fingerprint; tests/test_zz_round_end.py (CPU) fails when HEAD's covered paths are no longer what the log saw.
 # Nothing under the covered paths may be committed after this; the log itself (profiles/rNN_final_*) is not covered.

@@ -1,5 +1,5 @@
 """Cross-check of roofline.avg_launch_ms (HIP events on the library's streams inside bench.py's timed region) against rocprofv3's kernel trace of the SAME command:
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tr -o tr -- python3 bench.py --steps 16 --warmup 2 --no-cpu-baseline --no-extras --no-general-scene > line.json
+    rocprofv3 --kernel-trace --output-format csv -d <trace dir> -o tr -- python3 bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --no-extras --no-general-scene > line.json
     python3 tools/timed_region_avg.py <kernel_trace.csv> line.json
 The trace holds the dominant kernel's launches of the warm-up steps, the timed steps and the untimed serial step (the two counting replays run instrumented instantiations, other
 names).  The launches of the timed region are those in the middle: the first warmup / steps x N and the last N / steps are dropped (N = the line's roofline.launches), and the
