@@ -842,6 +842,32 @@ int fh_init_render_states(fh_ctx* ctx)
   return FH_OK;
 }
 
+// known-answer hooks of the sample-index tests: both per-pixel counters at once, after everything queued on the context has finished (the passes of a call in flight
+// read and write them)
+int fh_kat_set_sample_counts(fh_ctx* ctx, const uint32_t* counts, uint32_t n_pixels)
+{
+  CTX_CHECK(ctx);
+  if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_kat_set_sample_counts: resolution not set");
+  if (!counts || (uint64_t)n_pixels != (uint64_t)ctx->width * ctx->height) return fail(ctx, FH_E_INVALID, "fh_kat_set_sample_counts: one count per pixel of the frame");
+  const int rc = fh_sync(ctx);
+  if (rc) return rc;
+  FH_HIP(hipMemcpy(ctx->d_sample_count, counts, 4ull * n_pixels, hipMemcpyHostToDevice));
+  FH_HIP(hipMemcpy(ctx->d_sample_issued, counts, 4ull * n_pixels, hipMemcpyHostToDevice));
+  return FH_OK;
+}
+
+int fh_kat_sample_counts(fh_ctx* ctx, uint32_t* sample_count, uint32_t* issued, uint32_t n_pixels)
+{
+  CTX_CHECK(ctx);
+  if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_kat_sample_counts: resolution not set");
+  if ((uint64_t)n_pixels != (uint64_t)ctx->width * ctx->height) return fail(ctx, FH_E_INVALID, "fh_kat_sample_counts: one count per pixel of the frame");
+  const int rc = fh_sync(ctx);
+  if (rc) return rc;
+  if (sample_count) FH_HIP(hipMemcpy(sample_count, ctx->d_sample_count, 4ull * n_pixels, hipMemcpyDeviceToHost));
+  if (issued) FH_HIP(hipMemcpy(issued, ctx->d_sample_issued, 4ull * n_pixels, hipMemcpyDeviceToHost));
+  return FH_OK;
+}
+
 int fh_set_resolution(fh_ctx* ctx, uint32_t w, uint32_t h)
 {
   CTX_CHECK(ctx);

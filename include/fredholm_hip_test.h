@@ -56,6 +56,13 @@ int fh_kat_alpha_records(fh_ctx* ctx, uint32_t* out, uint32_t n_faces);
    the face they leave; out[1..2] = shaded paths the probing passes have counted from the root / from the face, out[3..4] = their test cycles by the issue model's weights */
 int fh_kat_ray_start(fh_ctx* ctx, double out[5]);
 
+/* every pixel's two sample counters, the running-mean count (sample_count: k_accumulate, k_sky_pixels) and the issued count (the sample index k_generate starts from),
+   so that tests can start a frame at any sample index; n_pixels = width * height.  Both wait for the work queued on the context first.  fh_init_render_states and
+   fh_set_resolution zero both counters again */
+int fh_kat_set_sample_counts(fh_ctx* ctx, const uint32_t* counts, uint32_t n_pixels);
+/* read both back (either pointer may be NULL) */
+int fh_kat_sample_counts(fh_ctx* ctx, uint32_t* sample_count, uint32_t* issued, uint32_t n_pixels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -308,6 +308,36 @@ def test_progressive_launches_accumulate_running_mean(oracle):
     assert (a["depth"] > 0).mean() > 0.9
 
 
+def test_render_of_a_crop_of_rows_equals_those_rows_of_the_whole_frame(oracle):
+    """The GPU tests compare the library with the checker on a crop of rows (rows=) of frames too big for the checker, from per-pixel start indices that
+    include wrapping ones (tests/test_gpu_sample_index.py): rendering only rows [y0, y1) has to give those rows' bits of a whole-frame render, and advance
+    sample_count only inside the crop."""
+    sc = scenes.cornell_box()
+    S = oracle.Scene(sc)
+    cam = Camera(**scenes.CORNELL_CAMERA).params()
+    w, h = 40, 30
+    wrap = (1 << 32) // (w * h)
+    edges = np.array([0, 15, 16, 17, 2071, wrap - 1, wrap, wrap + 1, 2 * wrap + 1, (1 << 24) - 1, 1 << 24, (1 << 24) + 1, 0xFFFFFFFE, 0xFFFFFFFF], np.uint32)
+    rng = np.random.default_rng(7)
+    start = rng.choice(edges, size=(h, w)).astype(np.uint32)
+    full, crop = S.new_layers(w, h), S.new_layers(w, h)
+    for name in ("beauty", "position", "depth", "normal", "texcoord", "albedo"):
+        full[name][...] = rng.uniform(0.1, 2.0, size=full[name].shape).astype(np.float32)
+        crop[name][...] = full[name]
+    full["sample_count"][...] = start
+    crop["sample_count"][...] = start
+    before = {k: v.copy() for k, v in crop.items()}
+    y0, y1 = 11, 19
+    for n in (1, 3):
+        S.render(cam, w, h, full, n, 4, n_threads=4)
+        S.render(cam, w, h, crop, n, 4, n_threads=4, rows=(y0, y1))
+    for name, a in crop.items():
+        assert np.array_equal(a[y0:y1].view(np.uint32), full[name][y0:y1].view(np.uint32)), name
+        assert np.array_equal(np.delete(a, np.s_[y0:y1], axis=0), np.delete(before[name], np.s_[y0:y1], axis=0)), name
+    assert np.array_equal(crop["sample_count"][y0:y1], start[y0:y1] + np.uint32(4))
+    assert (start[y0:y1] > 0xFFFFFFFB).any() and (full["sample_count"] < start).any()  # the crop holds pixels whose counter itself wraps
+
+
 def test_multisample_launch_keeps_reference_firsthit_quirk(oracle):
     # pt.cu:432 declares the payload outside the spp loop: after the first hitting sample of a launch,
     # directly visible emitters are no longer added (SURVEY.md 3-D-2).  The checker reproduces it.
