@@ -253,17 +253,18 @@ struct Bsdf {
     return p.base_color * (on_A + on_B * cmax * s_alpha * t_beta) / kPi;
   }
 
-  // ---- mixture
-  FH_HD f3 eval(f3 wo, f3 wi) const
+  // ---- mixture.  `only` keeps a subset of the lobes in the sums (the test entry fh_kat_bsdf_lobes); the shade kernels pass
+  // nothing, so it is the constant LOBES and every test below folds away
+  FH_HD f3 eval(f3 wo, f3 wi, uint32_t only = LOBES) const
   {
     f3 coat = mk3(0.0f), metal = mk3(0.0f), spec = mk3(0.0f), trans = mk3(0.0f), sheen = mk3(0.0f), dt = mk3(0.0f), dr = mk3(0.0f);
-    if (has(L_COAT) && p.coat * coat_lum > 0.0f) coat = zero_if_bad(ggx_refl_dielectric_eval(a_coat, wo, wi));
-    if (has(L_METAL) && p.metalness > 0.0f) metal = zero_if_bad(metal_eval(wo, wi));
-    if (has(L_SPEC) && p.specular * spec_lum > 0.0f) spec = zero_if_bad(ggx_refl_dielectric_eval(a_spec, wo, wi));
-    if (has(L_TRANS) && p.transmission > 0.0f) trans = zero_if_bad(trans_eval(wo, wi));
-    if (has(L_SHEEN) && p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(sheen_eval(wo, wi));
-    if (has(L_DT) && p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(oren_nayar_eval(wo, wi));
-    if (has(L_DIFF) && p.diffuse > 0.0f) dr = zero_if_bad(oren_nayar_eval(wo, wi));
+    if (has(L_COAT) && (only & L_COAT) && p.coat * coat_lum > 0.0f) coat = zero_if_bad(ggx_refl_dielectric_eval(a_coat, wo, wi));
+    if (has(L_METAL) && (only & L_METAL) && p.metalness > 0.0f) metal = zero_if_bad(metal_eval(wo, wi));
+    if (has(L_SPEC) && (only & L_SPEC) && p.specular * spec_lum > 0.0f) spec = zero_if_bad(ggx_refl_dielectric_eval(a_spec, wo, wi));
+    if (has(L_TRANS) && (only & L_TRANS) && p.transmission > 0.0f) trans = zero_if_bad(trans_eval(wo, wi));
+    if (has(L_SHEEN) && (only & L_SHEEN) && p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(sheen_eval(wo, wi));
+    if (has(L_DT) && (only & L_DT) && p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(oren_nayar_eval(wo, wi));
+    if (has(L_DIFF) && (only & L_DIFF) && p.diffuse > 0.0f) dr = zero_if_bad(oren_nayar_eval(wo, wi));
     f3 ret = mk3(0.0f), m = mk3(1.0f);
     ret += p.coat * coat;
     m *= coat_absorption;
@@ -281,16 +282,16 @@ struct Bsdf {
     return ret;
   }
 
-  FH_HD float eval_pdf(f3 wo, f3 wi) const
+  FH_HD float eval_pdf(f3 wo, f3 wi, uint32_t only = LOBES) const
   {
     float coat = 0, metal = 0, spec = 0, trans = 0, sheen = 0, dt = 0, dr = 0;
-    if (has(L_COAT) && p.coat * coat_lum > 0.0f) coat = zero_if_bad(ggx_refl_pdf(a_coat, wo, wi));
-    if (has(L_METAL) && p.metalness > 0.0f) metal = zero_if_bad(ggx_refl_pdf(a_spec, wo, wi));
-    if (has(L_SPEC) && p.specular * spec_lum > 0.0f) spec = zero_if_bad(ggx_refl_pdf(a_spec, wo, wi));
-    if (has(L_TRANS) && p.transmission > 0.0f) trans = zero_if_bad(trans_pdf(wo, wi));
-    if (has(L_SHEEN) && p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(abs_cos(wi) / kPi);
-    if (has(L_DT) && p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(abs_cos(wi) / kPi);
-    if (has(L_DIFF) && p.diffuse > 0.0f) dr = zero_if_bad(abs_cos(wi) / kPi);
+    if (has(L_COAT) && (only & L_COAT) && p.coat * coat_lum > 0.0f) coat = zero_if_bad(ggx_refl_pdf(a_coat, wo, wi));
+    if (has(L_METAL) && (only & L_METAL) && p.metalness > 0.0f) metal = zero_if_bad(ggx_refl_pdf(a_spec, wo, wi));
+    if (has(L_SPEC) && (only & L_SPEC) && p.specular * spec_lum > 0.0f) spec = zero_if_bad(ggx_refl_pdf(a_spec, wo, wi));
+    if (has(L_TRANS) && (only & L_TRANS) && p.transmission > 0.0f) trans = zero_if_bad(trans_pdf(wo, wi));
+    if (has(L_SHEEN) && (only & L_SHEEN) && p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(abs_cos(wi) / kPi);
+    if (has(L_DT) && (only & L_DT) && p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(abs_cos(wi) / kPi);
+    if (has(L_DIFF) && (only & L_DIFF) && p.diffuse > 0.0f) dr = zero_if_bad(abs_cos(wi) / kPi);
     return pmf(0) * coat + pmf(1) * metal + pmf(2) * spec + pmf(3) * trans + pmf(4) * sheen + pmf(5) * dt + pmf(6) * dr;
   }
 

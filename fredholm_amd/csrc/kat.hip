@@ -100,7 +100,7 @@ FH_D MatParams params_of(const MaterialDev& m)
 }
 
 template <uint32_t LOBES>
-__global__ void k_bsdf(MaterialDev mat, int entering, float eta_given, BsdfTables lut, uint32_t n, const float* wo, const float* wi, const float* u1, const float* u2, float* out)
+__global__ void k_bsdf(MaterialDev mat, int entering, float eta_given, uint32_t only, BsdfTables lut, uint32_t n, const float* wo, const float* wi, const float* u1, const float* u2, float* out)
 {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -108,12 +108,12 @@ __global__ void k_bsdf(MaterialDev mat, int entering, float eta_given, BsdfTable
   Bsdf<LOBES> b;
   b.init(o, params_of(mat), entering != 0, lut);
   if (eta_given > 0.0f) { b.ni = 1.0f; b.nt = eta_given; b.eta = eta_given; }  // fh_kat_bsdf_ior: the lobes at a relative index other than the constructor's
-  const f3 e = b.eval(o, in);
+  const f3 e = b.eval(o, in, only);
   f3 f;
   float pdf;
   const f3 s = b.sample(o, u1[i], mk2(u2[2 * i], u2[2 * i + 1]), f, pdf);
   float* r = out + 18 * i;
-  r[0] = e.x; r[1] = e.y; r[2] = e.z; r[3] = b.eval_pdf(o, in);
+  r[0] = e.x; r[1] = e.y; r[2] = e.z; r[3] = b.eval_pdf(o, in, only);
   r[4] = s.x; r[5] = s.y; r[6] = s.z; r[7] = f.x; r[8] = f.y; r[9] = f.z; r[10] = pdf;
   for (int k = 0; k < 7; ++k) r[11 + k] = b.pmf(k);
 }
@@ -367,7 +367,7 @@ int fh_kat_warp(fh_ctx* ctx, int kind, uint32_t n, const float* u2, const float*
   FH_HIP(o.down(out));
   return FH_OK;
 }
-static int kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, float eta_given, uint32_t lobes_mask, uint32_t n, const float* wo3, const float* wi3, const float* u1, const float* u2, float* out18)
+static int kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, float eta_given, uint32_t lobes_mask, uint32_t only, uint32_t n, const float* wo3, const float* wi3, const float* u1, const float* u2, float* out18)
 {
   KCTX(ctx);
   if (!material) return FH_E_INVALID;
@@ -378,11 +378,11 @@ static int kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, floa
   FH_HIP(a.up(wo3, 3ull * n)); FH_HIP(b.up(wi3, 3ull * n)); FH_HIP(c.up(u1, n)); FH_HIP(d.up(u2, 2ull * n)); FH_HIP(o.up(nullptr, 18ull * n));
   const dim3 g(blocks(n)), t(256);
   switch (lobes_mask) {
-    case L_DIFF: hipLaunchKernelGGL(k_bsdf<L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    case L_METAL: hipLaunchKernelGGL(k_bsdf<L_METAL>, g, t, 0, ctx->stream, m, entering, eta_given, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    case L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    case L_METAL | L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_METAL | L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    default: hipLaunchKernelGGL(k_bsdf<L_ALL>, g, t, 0, ctx->stream, m, entering, eta_given, lut, n, a.p, b.p, c.p, d.p, o.p); break;
+    case L_DIFF: hipLaunchKernelGGL(k_bsdf<L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
+    case L_METAL: hipLaunchKernelGGL(k_bsdf<L_METAL>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
+    case L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
+    case L_METAL | L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_METAL | L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
+    default: hipLaunchKernelGGL(k_bsdf<L_ALL>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
   }
   FH_HIP(hipStreamSynchronize(ctx->stream));
   FH_HIP(o.down(out18));
@@ -390,12 +390,17 @@ static int kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, floa
 }
 int fh_kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, uint32_t lobes_mask, uint32_t n, const float* wo3, const float* wi3, const float* u1, const float* u2, float* out18)
 {
-  return kat_bsdf(ctx, material, entering, 0.0f, lobes_mask, n, wo3, wi3, u1, u2, out18);
+  return kat_bsdf(ctx, material, entering, 0.0f, lobes_mask, L_ALL, n, wo3, wi3, u1, u2, out18);
+}
+int fh_kat_bsdf_lobes(fh_ctx* ctx, const fh_material* material, int entering, uint32_t only, uint32_t n, const float* wo3, const float* wi3, const float* u1, const float* u2, float* out18)
+{
+  if (only == 0 || (only & ~(uint32_t)L_ALL)) return FH_E_INVALID;
+  return kat_bsdf(ctx, material, entering, 0.0f, L_ALL, only, n, wo3, wi3, u1, u2, out18);
 }
 int fh_kat_bsdf_ior(fh_ctx* ctx, const fh_material* material, float eta, uint32_t lobes_mask, uint32_t n, const float* wo3, const float* wi3, const float* u1, const float* u2, float* out18)
 {
   if (!(eta > 0.0f)) return FH_E_INVALID;
-  return kat_bsdf(ctx, material, 1, eta, lobes_mask, n, wo3, wi3, u1, u2, out18);
+  return kat_bsdf(ctx, material, 1, eta, lobes_mask, L_ALL, n, wo3, wi3, u1, u2, out18);
 }
 int fh_kat_sky(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3)
 {

@@ -351,16 +351,17 @@ struct Bsdf {
     diff_l.init(p.base_color, p.diffuse_roughness);
   }
 
-  V3 eval(V3 wo, V3 wi) const
+  // `only` keeps a subset of the lobes (bits coat 1, metal 2, specular 4, transmission 8, sheen 16, diffuse transmission 32, diffuse 64) in the sums
+  V3 eval(V3 wo, V3 wi, uint32_t only = 127) const
   {
     V3 coat = v3(0.0f), metal = v3(0.0f), spec = v3(0.0f), trans = v3(0.0f), sheen = v3(0.0f), dt = v3(0.0f), dr = v3(0.0f);
-    if (p.coat * coat_lum > 0.0f) coat = zero_if_bad(coat_l.eval(wo, wi));
-    if (p.metalness > 0.0f) metal = zero_if_bad(metal_l.eval(wo, wi));
-    if (p.specular * spec_lum > 0.0f) spec = zero_if_bad(spec_l.eval(wo, wi));
-    if (p.transmission > 0.0f) trans = zero_if_bad(trans_l.eval(wo, wi));
-    if (p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(sheen_l.eval(wo, wi));
-    if (p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(dt_l.eval(wo, wi));
-    if (p.diffuse > 0.0f) dr = zero_if_bad(diff_l.eval(wo, wi));
+    if ((only & 1) && p.coat * coat_lum > 0.0f) coat = zero_if_bad(coat_l.eval(wo, wi));
+    if ((only & 2) && p.metalness > 0.0f) metal = zero_if_bad(metal_l.eval(wo, wi));
+    if ((only & 4) && p.specular * spec_lum > 0.0f) spec = zero_if_bad(spec_l.eval(wo, wi));
+    if ((only & 8) && p.transmission > 0.0f) trans = zero_if_bad(trans_l.eval(wo, wi));
+    if ((only & 16) && p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(sheen_l.eval(wo, wi));
+    if ((only & 32) && p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(dt_l.eval(wo, wi));
+    if ((only & 64) && p.diffuse > 0.0f) dr = zero_if_bad(diff_l.eval(wo, wi));
     V3 ret = v3(0.0f), m = v3(1.0f);
     ret += p.coat * coat;
     m *= coat_absorption;
@@ -410,16 +411,16 @@ struct Bsdf {
     return wi;
   }
 
-  float eval_pdf(V3 wo, V3 wi) const
+  float eval_pdf(V3 wo, V3 wi, uint32_t only = 127) const
   {
     float coat = 0, metal = 0, spec = 0, trans = 0, sheen = 0, dt = 0, dr = 0;
-    if (p.coat * coat_lum > 0.0f) coat = zero_if_bad(coat_l.pdf(wo, wi));
-    if (p.metalness > 0.0f) metal = zero_if_bad(metal_l.pdf(wo, wi));
-    if (p.specular * spec_lum > 0.0f) spec = zero_if_bad(spec_l.pdf(wo, wi));
-    if (p.transmission > 0.0f) trans = zero_if_bad(trans_l.pdf(wo, wi));
-    if (p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(sheen_l.pdf(wo, wi));
-    if (p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(dt_l.pdf(wo, wi));
-    if (p.diffuse > 0.0f) dr = zero_if_bad(diff_l.pdf(wo, wi));
+    if ((only & 1) && p.coat * coat_lum > 0.0f) coat = zero_if_bad(coat_l.pdf(wo, wi));
+    if ((only & 2) && p.metalness > 0.0f) metal = zero_if_bad(metal_l.pdf(wo, wi));
+    if ((only & 4) && p.specular * spec_lum > 0.0f) spec = zero_if_bad(spec_l.pdf(wo, wi));
+    if ((only & 8) && p.transmission > 0.0f) trans = zero_if_bad(trans_l.pdf(wo, wi));
+    if ((only & 16) && p.sheen * sheen_lum > 0.0f) sheen = zero_if_bad(sheen_l.pdf(wo, wi));
+    if ((only & 32) && p.subsurface * p.thin_walled > 0.0f) dt = zero_if_bad(dt_l.pdf(wo, wi));
+    if ((only & 64) && p.diffuse > 0.0f) dr = zero_if_bad(diff_l.pdf(wo, wi));
     return dist.pmf(0) * coat + dist.pmf(1) * metal + dist.pmf(2) * spec + dist.pmf(3) * trans + dist.pmf(4) * sheen + dist.pmf(5) * dt + dist.pmf(6) * dr;
   }
 };

@@ -107,6 +107,19 @@ def bsdf(material, entering, wo, wi, u1, u2):
     return out
 
 
+def bsdf_lobes(material, entering, only, wo, wi, u1, u2):
+    """orc_bsdf with eval / eval_pdf (columns 0:4) summed over the lobes whose bits are set in `only` (1 coat ... 64 diffuse); the rest as orc_bsdf"""
+    m = np.ascontiguousarray(material)
+    assert m.dtype.itemsize == 180 and 0 < only <= 127
+    wo = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
+    wi = np.ascontiguousarray(wi, dtype=np.float32).reshape(-1, 3)
+    u1 = np.ascontiguousarray(u1, dtype=np.float32)
+    u2 = np.ascontiguousarray(u2, dtype=np.float32).reshape(-1, 2)
+    out = np.zeros((wo.shape[0], 18), dtype=np.float32)
+    lib().orc_bsdf_lobes(_p(m), int(bool(entering)), C.c_uint32(only), int(wo.shape[0]), _p(wo), _p(wi), _p(u1), _p(u2), _p(out))
+    return out
+
+
 def bsdf_ior(material, eta, wo, wi, u1, u2):
     """orc_bsdf with the relative index of refraction given (the reference's constructor fixes 1.5 / (1 / 1.5), bsdf.cu:16-18)"""
     m = np.ascontiguousarray(material)

@@ -1,0 +1,240 @@
+"""Each BSDF sampler against the density it claims: sampled directions histogrammed over the sphere and compared (chi-square) with a
+float64 quadrature of the density, the mass the sampler loses, every sample's (f, pdf) against the chosen lobe's eval / eval_pdf, and
+for a lobe too sharp for the cells, E[f |cos| / pdf] against the quadrature of eval |cos|.
+
+The CPU tests draw through the checker (oracle.bsdf), one wo per case; the GPU tests draw through the device's fh_kat_bsdf at four
+view angles and both sides.  The lobe values in the model come from the same side's per-lobe entry (orc_bsdf_lobes /
+fh_kat_bsdf_lobes), so a failure here is a sampler, a pdf or the mixing -- not the model's copy of a lobe.
+Quirk modelled (the reference's own): the sheen lobe draws its half vector cosine-distributed but reports |cos wi| / pi
+(bxdf.cu:758-777), see expectation_model.sampled_density.
+"""
+import ctypes as C
+import zlib
+
+import numpy as np
+import pytest
+
+import expectation_model as M
+from fredholm_amd import native as N
+from test_gpu_parity import BSDF_CASES, L_ALL, L_METAL, _material
+
+P_FAIL = 1e-5
+ETA = 1.5
+
+
+def _cpu_sides(oracle):
+    return (lambda mat, entering, lobes, wo, wi, u1, u2: oracle.bsdf(mat, entering, wo, wi, u1, u2),
+            lambda mat, entering, only, wo, wi, u1, u2: oracle.bsdf_lobes(mat, entering, only, wo, wi, u1, u2))
+
+
+def _gpu_sides(renderer):
+    def call(fn, mat, entering, mask, wo, wi, u1, u2):
+        n = wo.shape[0]
+        out = np.zeros((n, 18), np.float32)
+        args = [np.ascontiguousarray(a, dtype=np.float32) for a in (wo, wi, u1, u2)]
+        rc = getattr(N.lib(), fn)(renderer._ctx, N.ptr(np.ascontiguousarray(mat)), int(entering), C.c_uint32(mask), n, *[N.ptr(a) for a in args], N.ptr(out))
+        N.check(renderer._ctx, rc, fn)
+        return out
+    return (lambda *a: call("fh_kat_bsdf", *a), lambda *a: call("fh_kat_bsdf_lobes", *a))
+
+
+def _alpha(mat):
+    r = float(np.clip(mat["specular_roughness"][0], 0.01, 1.0))
+    return r * r
+
+
+def _ggx_dvis(a, wo, h):
+    """float64 GGX visible-normal density of h (isotropic alpha a), for the total-internal-reflection branch only"""
+    lam = 0.5 * (-1.0 + np.sqrt(1.0 + a * a * (wo[0] ** 2 + wo[2] ** 2) / wo[1] ** 2))
+    t = (h[:, 0] ** 2 + h[:, 2] ** 2) / (a * a) + h[:, 1] ** 2
+    d = 1.0 / (np.pi * a * a * t * t)
+    return np.abs(h @ wo) * d / (abs(wo[1]) * (1.0 + lam))
+
+
+def _tir(wo, h, entering):
+    ni, nt = (1.0, ETA) if entering else (ETA, 1.0)
+    c = h @ wo
+    return (ni / nt) ** 2 * (1.0 - c * c) > 1.0
+
+
+def _true_density(mat, entering, wo, dirs, per_lobe):
+    """pmf-weighted density the whole mixture's sampler draws at dirs (see expectation_model.sampled_density)"""
+    wo64 = np.asarray(wo, np.float64)
+    pmf = per_lobe[1]
+    dens = np.zeros(dirs.shape[0])
+    for bit, (f, pp) in per_lobe[0].items():
+        k = M.LOBE_BITS.index(bit)
+        if pmf[k] == 0 or not np.isfinite(pmf[k]):
+            continue
+        if bit == M.L_SHEEN:
+            dens += pmf[k] * M.sheen_density(wo64, dirs)
+        elif bit == M.L_TRANS:
+            ni, nt = (1.0, ETA) if entering else (ETA, 1.0)
+            h = -(ni * wo64[None, :] + nt * dirs)
+            h /= np.linalg.norm(h, axis=1, keepdims=True)
+            h = np.where(h[:, 1:2] < 0, -h, h)
+            refr = (h @ wo64 > 0) & (np.einsum("ij,ij->i", dirs, h) < 0) & ~_tir(wo64, h, entering)
+            dens += np.where(refr, pp, 0.0)
+            hr = wo64[None, :] + dirs
+            hr /= np.linalg.norm(hr, axis=1, keepdims=True)
+            refl = (hr[:, 1] > 0) & _tir(wo64, hr, entering)
+            dens += np.where(refl, pmf[k] * _ggx_dvis(_alpha(mat), wo64, hr) / (4.0 * np.abs(hr @ wo64)), 0.0)
+        else:
+            dens += M.sampled_density(bit, wo64, entering, dirs, pp)
+    return dens
+
+
+def _draw(sample, mat, entering, lobes, wo, n, seed):
+    rng = np.random.default_rng(seed)
+    u1 = rng.uniform(0, 1, n).astype(np.float32)
+    u2 = rng.uniform(0, 1, (n, 2)).astype(np.float32)
+    wo32 = np.repeat(np.asarray(wo, np.float32)[None, :], n, axis=0)
+    return sample(mat, entering, lobes, wo32, wo32, u1, u2), u1, u2
+
+
+def _check_density(sides, name, mat, lobes, entering, cos_o, n):
+    sample, lobe_eval = sides
+    wo = M.wo_at(cos_o)
+    dirs, w, cell = M.sphere_grid(wo, entering)
+    per_lobe = M.lobes(lambda m, e, only, a, b, c, d: lobe_eval(m, e, only, a, b, c, d), mat, entering, wo, dirs)
+    dens = _true_density(mat, entering, wo, dirs, per_lobe)
+    n_cells = 24 * 24
+    expected = np.bincount(cell, weights=w * dens, minlength=n_cells)
+    mass = expected.sum()
+    out, _, _ = _draw(sample, mat, entering, lobes, wo, n, seed=zlib.crc32(f"{name} {entering} {cos_o}".encode()))
+    wi, f, pdf = out[:, 4:7], out[:, 7:10], out[:, 10]
+    valid = np.isfinite(pdf) & (pdf > 0) & np.isfinite(wi).all(axis=1) & np.isfinite(f).all(axis=1)
+    observed = np.bincount(M.cell_of(wi[valid]), minlength=n_cells)
+    stat, dof = M.chi2_pooled(observed, n * expected)
+    p = M.chi2_sf(stat, dof)
+    assert p > P_FAIL, f"{name} entering={entering} cos_o={cos_o}: chi2 {stat:.1f} on {dof} dof, p = {p:.2e}"
+    # lost mass: the draws that come back unusable are the density's missing mass (binomial, 5 sigma plus the quadrature's 1e-4)
+    lost = 1.0 - valid.mean()
+    assert abs(lost - (1.0 - mass)) <= 5.0 * np.sqrt(max(mass * (1 - mass), 1.0 / n) / n) + 1e-4, (name, lost, 1.0 - mass)
+
+
+DENSITY_CASES = [c for c in BSDF_CASES if c[0] != "default via generic kernel"] + [
+    ("anisotropy-free rough metal", _material(metalness=1.0, base_color=(0.95, 0.9, 0.8), specular_roughness=0.6), L_METAL),
+]
+INSIDE = {"glass", "thin diffuse transmission", "kitchen sink"}  # the lobes that survive entering = false
+# From inside glass the refracted and the totally reflected draws meet along a curve the (theta, phi) grid does not follow, which
+# leaves the quadrature a few 1e-4 of mass off; those sides are held by the sample-against-eval tests, TIR branch included.
+DENSITY_INSIDE = {"thin diffuse transmission"}
+
+
+def _ids(cases):
+    return [c[0] for c in cases]
+
+
+@pytest.mark.parametrize("name,mat,lobes", DENSITY_CASES, ids=_ids(DENSITY_CASES))
+def test_checker_sampler_draws_its_density(oracle, name, mat, lobes):
+    for entering in ((True, False) if name in DENSITY_INSIDE else (True,)):
+        _check_density(_cpu_sides(oracle), name, mat, lobes, entering, 0.7, 1 << 18)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,mat,lobes", DENSITY_CASES, ids=_ids(DENSITY_CASES))
+def test_device_sampler_draws_its_density(renderer, name, mat, lobes):
+    for entering in ((True, False) if name in DENSITY_INSIDE else (True,)):
+        for cos_o in (1.0, 0.7, 0.3, 0.05):
+            _check_density(_gpu_sides(renderer), name, mat, lobes, entering, cos_o, 1 << 20)
+
+
+def _check_sample_against_eval(sides, name, mat, lobes, entering, cos_o, n):
+    """every sample's (f, pdf) is the chosen lobe's weighted eval and pmf * eval_pdf at the returned wi; the lobe is the first whose
+    running pmf sum exceeds u1 (Bsdf::sample).  Transmission draws that totally internally reflect are checked against the float64
+    reflection density of their half vector instead (bxdf.cu:660-679)."""
+    sample, lobe_eval = sides
+    wo = M.wo_at(cos_o)
+    out, u1, u2 = _draw(sample, mat, entering, lobes, wo, n, seed=7)
+    pmf = out[0, 11:18]
+    c = np.add.accumulate(pmf.astype(np.float32), dtype=np.float32)
+    idx = np.argmax(u1[:, None] < c[None, :], axis=1)
+    idx[~(u1[:, None] < c[None, :]).any(axis=1)] = 6
+    wi = out[:, 4:7]
+    wo32 = np.repeat(np.asarray(wo, np.float32)[None, :], n, axis=0)
+    ok_all = np.isfinite(out[:, 10]) & (out[:, 10] > 0)
+    n_tir = 0
+    for k, bit in enumerate(M.LOBE_BITS):
+        sel = (idx == k) & ok_all
+        if not sel.any():
+            continue
+        e = lobe_eval(mat, entering, bit, wo32[sel], wi[sel], u1[sel], u2[sel])
+        f, pdf = out[sel, 7:10].astype(np.float64), out[sel, 10].astype(np.float64)
+        if bit == M.L_TRANS:
+            # each draw is a refraction (pdf = pmf * eval_pdf) or a total internal reflection (bxdf.cu:660-679), whose pdf is the
+            # reflection density of h = normalize(wo + wi); either side of the surface can receive both.  Only far-tail draws, where
+            # float32 wi cannot pin h down, may match neither (<= 1e-3 of them).
+            wo64 = wo.astype(np.float64)
+            h = wo64[None, :] + wi[sel].astype(np.float64)
+            h /= np.linalg.norm(h, axis=1, keepdims=True)
+            ref = pmf[k] * _ggx_dvis(_alpha(mat), wo64, h) / (4.0 * np.abs(np.einsum("ij,ij->i", wi[sel].astype(np.float64), h)))
+            refr = np.abs(pdf - e[:, 3]) <= 1e-5 * np.abs(e[:, 3])
+            tir = ~refr & _tir(wo64, h, entering) & np.isclose(pdf, ref, rtol=2e-3, atol=0)
+            assert (~(refr | tir)).sum() <= max(2, 1e-3 * len(pdf)), f"{name}: {(~(refr | tir)).sum()} transmission draws match neither branch"
+            n_tir += int(tir.sum())
+            keep = refr
+            f, pdf, e = f[keep], pdf[keep], e[keep]
+        rel = lambda a, b: np.abs(a - b) / np.maximum(np.abs(b), 1e-30)  # noqa: E731
+        assert (rel(pdf, e[:, 3].astype(np.float64)) <= 1e-5).all(), f"{name} lobe {bit}: sample pdf != pmf * eval_pdf"
+        scale = np.maximum(np.abs(e[:, 0:3]).max(axis=1, keepdims=True), 1e-30)
+        assert (np.abs(f - e[:, 0:3]) <= 1e-5 * scale).all(), f"{name} lobe {bit}: sample f != eval"
+    return n_tir
+
+
+@pytest.mark.parametrize("name,mat,lobes", DENSITY_CASES, ids=_ids(DENSITY_CASES))
+def test_checker_sample_equals_eval_of_the_chosen_lobe(oracle, name, mat, lobes):
+    for entering in ((True, False) if name in INSIDE else (True,)):
+        _check_sample_against_eval(_cpu_sides(oracle), name, mat, lobes, entering, 0.7, 1 << 15)
+
+
+def test_checker_transmission_total_internal_reflection_branch(oracle):
+    """from inside glass at a grazing view most transmission draws reflect totally; their pdf is the reflection density of the half vector"""
+    mat = dict((c[0], c[1]) for c in BSDF_CASES)["glass"]
+    assert _check_sample_against_eval(_cpu_sides(oracle), "glass", mat, L_ALL, False, 0.3, 1 << 15) > 1000
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,mat,lobes", DENSITY_CASES, ids=_ids(DENSITY_CASES))
+def test_device_sample_equals_eval_of_the_chosen_lobe(renderer, name, mat, lobes):
+    n_tir = 0
+    for entering in ((True, False) if name in INSIDE else (True,)):
+        for cos_o in (1.0, 0.7, 0.3, 0.05):
+            n_tir += _check_sample_against_eval(_gpu_sides(renderer), name, mat, lobes, entering, cos_o, 1 << 16)
+    if name == "glass":
+        assert n_tir > 1000
+
+
+def test_opaque_back_face_gives_nan_pdf(oracle):
+    """the reference's quirk, kept on purpose: seen from behind, an opaque material has every lobe weight 0, so the pmf and the
+    sampled pdf are NaN (fh_bsdf.h header); the renderer then drops the path.  Not part of the density tests."""
+    mat = _material(specular=0.0, base_color=(0.6, 0.3, 0.2))
+    out, _, _ = _draw(lambda m, e, lobes, a, b, c, d: oracle.bsdf(m, e, a, b, c, d), mat, False, 0, M.wo_at(0.7), 256, seed=3)
+    assert np.isnan(out[:, 10]).all() and np.isnan(out[:, 11:18]).all()
+
+
+def _check_sharp(sides, mat, lobes, cos_o, n):
+    sample, lobe_eval = sides
+    wo = M.wo_at(cos_o)
+    dirs, w, _ = M.sphere_grid(wo, True, n_gl=10)
+    per_lobe, _ = M.lobes(lobe_eval, mat, True, wo, dirs)
+    want = sum((w * np.abs(dirs[:, 1])) @ f for f, _ in per_lobe.values())
+    out, _, _ = _draw(sample, mat, True, lobes, wo, n, seed=11)
+    x = out[:, 7:10].astype(np.float64) * np.abs(out[:, 5:6].astype(np.float64)) / out[:, 10:11]
+    x = np.where(np.isfinite(x), x, 0.0)
+    got, se = x.mean(axis=0), x.std(axis=0) / np.sqrt(n)
+    assert (np.abs(got - want) <= 5 * se + 1e-4 * want).all(), (got, want, se)
+
+
+SHARP = _material(metalness=1.0, base_color=(0.9, 0.6, 0.3), specular_roughness=0.05)
+
+
+def test_checker_sharp_metal_mean_weight_is_the_albedo(oracle):
+    """roughness 0.05 (alpha 0.0025): no cell resolves the lobe, so E[f |cos| / pdf] is held to the quadrature of eval |cos| instead"""
+    _check_sharp(_cpu_sides(oracle), SHARP, L_METAL, 0.7, 1 << 18)
+
+
+@pytest.mark.gpu
+def test_device_sharp_metal_mean_weight_is_the_albedo(renderer):
+    for cos_o in (1.0, 0.7, 0.3):
+        _check_sharp(_gpu_sides(renderer), SHARP, L_METAL, cos_o, 1 << 20)

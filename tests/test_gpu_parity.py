@@ -189,6 +189,13 @@ def test_bsdf_eval_sample_pdf_identical(renderer, oracle, name, mat, lobes, ente
     out = np.zeros((n, 18), np.float32)
     _kat(renderer, "fh_kat_bsdf", N.ptr(mat), int(entering), C.c_uint32(lobes), n, N.ptr(wo), N.ptr(wi), N.ptr(u1), N.ptr(u2), N.ptr(out))
     assert _same(out, oracle.bsdf(mat, entering, wo, wi, u1, u2))
+    # one lobe at a time through the generic kernel (fh_kat_bsdf_lobes / orc_bsdf_lobes): the f_i and pmf_i * pdf_i the float64 models of
+    # tests/expectation_model.py take, bit for bit; the full mask is the mixture itself
+    for only in (L_COAT, L_METAL, L_SPEC, L_TRANS, L_SHEEN, L_DT, L_DIFF, L_ALL):
+        _kat(renderer, "fh_kat_bsdf_lobes", N.ptr(mat), int(entering), C.c_uint32(only), n, N.ptr(wo), N.ptr(wi), N.ptr(u1), N.ptr(u2), N.ptr(out))
+        assert _same(out, oracle.bsdf_lobes(mat, entering, only, wo, wi, u1, u2)), only
+        if only == L_ALL:
+            assert _same(out, oracle.bsdf(mat, entering, wo, wi, u1, u2))
 
 
 def test_hosek_sky_identical(renderer, oracle):
