@@ -141,3 +141,149 @@ def chi2_pooled(observed, expected, min_expected=5.0):
         return np.inf, max(int(keep.sum()) - 1, 1)
     o, e = o[keep], e[keep]
     return float(((o - e) ** 2 / e).sum()), len(e) - 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The mixture's sampled density, lobe by lobe (used by test_bsdf_sampling_density.py and the estimator expectations below)
+def alpha_of(mat):
+    r = float(np.clip(mat["specular_roughness"][0], 0.01, 1.0))
+    return r * r
+
+
+def ggx_dvis(a, wo, h):
+    """float64 GGX visible-normal density of h (isotropic alpha a), for the total-internal-reflection branch only"""
+    lam = 0.5 * (-1.0 + np.sqrt(1.0 + a * a * (wo[0] ** 2 + wo[2] ** 2) / wo[1] ** 2))
+    t = (h[:, 0] ** 2 + h[:, 2] ** 2) / (a * a) + h[:, 1] ** 2
+    d = 1.0 / (np.pi * a * a * t * t)
+    return np.abs(h @ wo) * d / (abs(wo[1]) * (1.0 + lam))
+
+
+def tir(wo, h, entering, eta=1.5):
+    ni, nt = (1.0, eta) if entering else (eta, 1.0)
+    c = h @ wo
+    return (ni / nt) ** 2 * (1.0 - c * c) > 1.0
+
+
+def lobe_densities(mat, entering, wo, dirs, per_lobe, eta=1.5):
+    """per lobe bit: pmf_i * (the density lobe i's sampler really draws at dirs), see sampled_density; the transmission lobe's
+    total-internal-reflection branch (bxdf.cu:660-679) draws the reflection density of its half vector instead"""
+    wo64 = np.asarray(wo, np.float64)
+    lobe_vals, pmf = per_lobe
+    out = {}
+    for bit, (f, pp) in lobe_vals.items():
+        k = LOBE_BITS.index(bit)
+        if pmf[k] == 0 or not np.isfinite(pmf[k]):
+            continue
+        if bit == L_SHEEN:
+            out[bit] = pmf[k] * sheen_density(wo64, dirs)
+        elif bit == L_TRANS:
+            ni, nt = (1.0, eta) if entering else (eta, 1.0)
+            h = -(ni * wo64[None, :] + nt * dirs)
+            h /= np.linalg.norm(h, axis=1, keepdims=True)
+            h = np.where(h[:, 1:2] < 0, -h, h)
+            refr = (h @ wo64 > 0) & (np.einsum("ij,ij->i", dirs, h) < 0) & ~tir(wo64, h, entering, eta)
+            dens = np.where(refr, pp, 0.0)
+            hr = wo64[None, :] + dirs
+            hr /= np.linalg.norm(hr, axis=1, keepdims=True)
+            refl = (hr[:, 1] > 0) & tir(wo64, hr, entering, eta)
+            out[bit] = dens + np.where(refl, pmf[k] * ggx_dvis(alpha_of(mat), wo64, hr) / (4.0 * np.abs(hr @ wo64)), 0.0)
+        else:
+            out[bit] = sampled_density(bit, wo64, entering, dirs, pp, eta)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Expectations of what pt.cu's closest-hit program adds at a surface point (pt.cu:680-944), in float64.
+# Every weight goes through regularize_weight (pt.cu:372-375): clamp(w, 0, 1) per channel, i.e. fmaxf(0, fminf(w, 1)), so NaN -> 1.
+def regularize(w):
+    return np.fmax(0.0, np.fmin(w, 1.0))
+
+
+def _weight(mis_pdf, other_pdf, f, cos_i, pdf):
+    """pt.cu:786-790, :817-821, :881-885, :919-921: regularize_weight(throughput * mis_weight * f * |cos wi| / pdf) at throughput 1,
+    mis_weight = pdf0 / (pdf0 + pdf1) (compute_mis_weight, pt.cu:365-369); returns (clamped, unclamped) (N, 3)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = (mis_pdf / (mis_pdf + other_pdf))[:, None] * f * (cos_i / pdf)[:, None]
+    return regularize(w), w
+
+
+def first_vertex_constant_background(bsdf_lobes, mat, cos_o, entering=True, n_gl=6):
+    """Expected regularized weight (rgb, per unit background radiance) that one visit of pt.cu's closest-hit program adds at a point
+    of an open convex surface under a constant background, seen at cos theta_o, throughput 1.  Both rays escape, so each carries
+    the background (miss programs, pt.cu:531-543); nothing else is lit.
+    - sky NEE (pt.cu:842-857): wi cosine-distributed on the hemisphere above the shading normal only, pdf = |cos wi| / pi, MIS
+      against the whole mixture's eval_pdf, f = the whole mixture's eval;
+    - the BSDF-sampled light ray (pt.cu:893-925): lobe i chosen with pmf_i, wi drawn with lobe i's real density anywhere on the
+      sphere, (f, pdf) = (f_i, pmf_i * pdf_i) of the chosen lobe (Bsdf::sample), and on a miss pdf_light = |cos wi| / pi (:911-913).
+    Lost draws (the density's missing mass) come back with a NaN or zero pdf, whose weight the clamp turns into 1 (NaN -> 1).
+    Returns (expected weight (3,), largest unclamped weight with nonzero density, lost mass)."""
+    wo = wo_at(cos_o)
+    dirs, w, _ = sphere_grid(wo, entering, n_gl=n_gl)
+    per_lobe = lobes(bsdf_lobes, mat, entering, wo, dirs)
+    c = np.abs(dirs[:, 1])
+    p_cos = c / np.pi
+    r_all = bsdf_lobes(mat, entering, 127, np.repeat(wo[None, :].astype(np.float32), len(dirs), 0), dirs.astype(np.float32),
+                       np.zeros(len(dirs), np.float32), np.full((len(dirs), 2), 0.5, np.float32)).astype(np.float64)
+    up = dirs[:, 1] > 0
+    wsky, raw = _weight(p_cos, r_all[:, 3], r_all[:, 0:3], c, p_cos)
+    total = ((w * p_cos * up) @ wsky)
+    peak = float(np.nanmax(np.where(up[:, None], raw, -np.inf)))
+    mass = 0.0
+    for bit, dens in lobe_densities(mat, entering, wo, dirs, per_lobe).items():
+        f_i, r_i = per_lobe[0][bit]
+        wb, raw = _weight(r_i, p_cos, f_i, c, r_i)
+        live = dens > 0
+        total = total + (w * dens) @ np.where(live[:, None], wb, 0.0)
+        if live.any():
+            peak = max(peak, float(np.nanmax(raw[live])))
+        mass += float(w @ dens)
+    lost = max(1.0 - mass, 0.0)
+    return total + lost, peak, lost
+
+
+def first_vertex_directional(bsdf_lobes, mat, cos_o, angle_deg, entering=True, n_r=24, n_phi=48):
+    """Expected regularized weight (rgb, per unit Le) of pt.cu's directional-light NEE (pt.cu:772-793) at a point whose shading
+    normal is the light's direction, seen at cos theta_o.  The shadow ray aims at a point drawn uniformly on a disk of radius
+    1e9 tan(angle / 2) at distance 1e9 (sample_position_on_directional_light, pt.cu:324-342), so wi = normalize(n + tan(angle / 2) d)
+    with d uniform on the unit disk of the plane; pdf = 1, MIS against eval_pdf.  Returns (expected weight (3,), largest unclamped)."""
+    x, wx = np.polynomial.legendre.leggauss(n_r)
+    rr, wr = 0.5 * (x + 1.0), 0.5 * wx
+    ph, wp = np.polynomial.legendre.leggauss(n_phi)
+    ph, wp = np.pi * (ph + 1.0), np.pi * wp
+    R, P = np.meshgrid(rr, ph, indexing="ij")
+    W = ((wr * rr)[:, None] * wp[None, :] / np.pi).ravel()  # uniform on the unit disk: r dr dphi / pi
+    t = np.tan(np.radians(0.5 * angle_deg))
+    d = np.stack([t * R * np.cos(P), np.ones_like(R), t * R * np.sin(P)], axis=-1).reshape(-1, 3)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    wo = wo_at(cos_o)
+    n = len(d)
+    r = bsdf_lobes(mat, entering, 127, np.repeat(wo[None, :].astype(np.float32), n, 0), d.astype(np.float32), np.zeros(n, np.float32),
+                   np.full((n, 2), 0.5, np.float32)).astype(np.float64)
+    wc, raw = _weight(np.ones(n), r[:, 3], r[:, 0:3], np.abs(d[:, 1]), np.ones(n))
+    return W @ wc, float(raw.max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+def polygon_irradiance(x, normal, poly):
+    """Lambert's formula: the irradiance at x (normal `normal`) from a uniform polygon of unit radiance, fully above x's tangent
+    plane: (1/2) sum_k angle(v_k, v_k+1) * dot(normal, normalize(v_k x v_k+1)), v_k = poly_k - x.  x (N, 3), poly (K, 3)."""
+    x = np.asarray(x, np.float64)
+    v = np.asarray(poly, np.float64)[None, :, :] - x[:, None, :]
+    v /= np.linalg.norm(v, axis=2, keepdims=True)
+    a, b = v, np.roll(v, -1, axis=1)
+    cr = np.cross(a, b)
+    ang = np.arctan2(np.linalg.norm(cr, axis=2), np.einsum("nkj,nkj->nk", a, b))
+    g = cr / np.maximum(np.linalg.norm(cr, axis=2, keepdims=True), 1e-300)
+    return np.abs(0.5 * (ang * (g @ np.asarray(normal, np.float64))).sum(axis=1))
+
+
+def two_plane_radiance(rho_floor, rho_ceiling, le, max_depth):
+    """Expected radiance of pt.cu's loop (pt.cu:455-472) at a grey Lambertian floor under a parallel, infinite, grey Lambertian
+    ceiling that emits le downwards, constant background 0.  At the floor (depths 0, 2, 4, ...) NEE and the BSDF-sampled light ray
+    together add rho_floor * le (their MIS weights sum to 1); at the ceiling (depths 1, 3, ...) nothing is added: its emission
+    counts only at a first hit (pt.cu:752-759), its own plane lies on its horizon and its light ray finds the floor, le = 0.  Each
+    continuation multiplies the throughput by the albedo, and roulette divides it back to 1 (prr = luminance(throughput) = albedo,
+    the throughput / prr of pt.cu:457-462), so the floor's k-th visit adds (rho_floor rho_ceiling)^k rho_floor le."""
+    n_floor = (int(max_depth) + 1) // 2
+    q = rho_floor * rho_ceiling
+    return rho_floor * le * sum(q ** k for k in range(n_floor))

@@ -38,50 +38,9 @@ def _gpu_sides(renderer):
     return (lambda *a: call("fh_kat_bsdf", *a), lambda *a: call("fh_kat_bsdf_lobes", *a))
 
 
-def _alpha(mat):
-    r = float(np.clip(mat["specular_roughness"][0], 0.01, 1.0))
-    return r * r
-
-
-def _ggx_dvis(a, wo, h):
-    """float64 GGX visible-normal density of h (isotropic alpha a), for the total-internal-reflection branch only"""
-    lam = 0.5 * (-1.0 + np.sqrt(1.0 + a * a * (wo[0] ** 2 + wo[2] ** 2) / wo[1] ** 2))
-    t = (h[:, 0] ** 2 + h[:, 2] ** 2) / (a * a) + h[:, 1] ** 2
-    d = 1.0 / (np.pi * a * a * t * t)
-    return np.abs(h @ wo) * d / (abs(wo[1]) * (1.0 + lam))
-
-
-def _tir(wo, h, entering):
-    ni, nt = (1.0, ETA) if entering else (ETA, 1.0)
-    c = h @ wo
-    return (ni / nt) ** 2 * (1.0 - c * c) > 1.0
-
-
 def _true_density(mat, entering, wo, dirs, per_lobe):
-    """pmf-weighted density the whole mixture's sampler draws at dirs (see expectation_model.sampled_density)"""
-    wo64 = np.asarray(wo, np.float64)
-    pmf = per_lobe[1]
-    dens = np.zeros(dirs.shape[0])
-    for bit, (f, pp) in per_lobe[0].items():
-        k = M.LOBE_BITS.index(bit)
-        if pmf[k] == 0 or not np.isfinite(pmf[k]):
-            continue
-        if bit == M.L_SHEEN:
-            dens += pmf[k] * M.sheen_density(wo64, dirs)
-        elif bit == M.L_TRANS:
-            ni, nt = (1.0, ETA) if entering else (ETA, 1.0)
-            h = -(ni * wo64[None, :] + nt * dirs)
-            h /= np.linalg.norm(h, axis=1, keepdims=True)
-            h = np.where(h[:, 1:2] < 0, -h, h)
-            refr = (h @ wo64 > 0) & (np.einsum("ij,ij->i", dirs, h) < 0) & ~_tir(wo64, h, entering)
-            dens += np.where(refr, pp, 0.0)
-            hr = wo64[None, :] + dirs
-            hr /= np.linalg.norm(hr, axis=1, keepdims=True)
-            refl = (hr[:, 1] > 0) & _tir(wo64, hr, entering)
-            dens += np.where(refl, pmf[k] * _ggx_dvis(_alpha(mat), wo64, hr) / (4.0 * np.abs(hr @ wo64)), 0.0)
-        else:
-            dens += M.sampled_density(bit, wo64, entering, dirs, pp)
-    return dens
+    """pmf-weighted density the whole mixture's sampler draws at dirs (see expectation_model.sampled_density, lobe_densities)"""
+    return sum(M.lobe_densities(mat, entering, wo, dirs, per_lobe, ETA).values(), np.zeros(dirs.shape[0]))
 
 
 def _draw(sample, mat, entering, lobes, wo, n, seed):
@@ -168,9 +127,9 @@ def _check_sample_against_eval(sides, name, mat, lobes, entering, cos_o, n):
             wo64 = wo.astype(np.float64)
             h = wo64[None, :] + wi[sel].astype(np.float64)
             h /= np.linalg.norm(h, axis=1, keepdims=True)
-            ref = pmf[k] * _ggx_dvis(_alpha(mat), wo64, h) / (4.0 * np.abs(np.einsum("ij,ij->i", wi[sel].astype(np.float64), h)))
+            ref = pmf[k] * M.ggx_dvis(M.alpha_of(mat), wo64, h) / (4.0 * np.abs(np.einsum("ij,ij->i", wi[sel].astype(np.float64), h)))
             refr = np.abs(pdf - e[:, 3]) <= 1e-5 * np.abs(e[:, 3])
-            tir = ~refr & _tir(wo64, h, entering) & np.isclose(pdf, ref, rtol=2e-3, atol=0)
+            tir = ~refr & M.tir(wo64, h, entering, ETA) & np.isclose(pdf, ref, rtol=2e-3, atol=0)
             assert (~(refr | tir)).sum() <= max(2, 1e-3 * len(pdf)), f"{name}: {(~(refr | tir)).sum()} transmission draws match neither branch"
             n_tir += int(tir.sum())
             keep = refr
