@@ -4,6 +4,8 @@
 //
 //   rtcamp --scene a.obj [--scene b.gltf ...] [--out DIR] [--width W --height H --spp N --depth D]
 //          [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--fov deg --F f --focus d]
+//          [--noise-threshold T [--min-spp M --adaptive-step S]]   (adaptive sampling: --spp is the per-pixel cap, the frame renders in calls of S samples
+//                                                                    until no pixel is active; prints the frame's mean spp)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -31,6 +33,8 @@ int main(int argc, char** argv)
   int width = 1920, height = 1080, n_spp = 16, max_depth = 5;
   float fps = 24.0f, max_time = 9.5f, fov_deg = 60.0f, F = 100.0f, focus = 8.0f;
   bool bloom = false, sun = false, sky = false, reference_launches = false;
+  float noise_threshold = -1.0f;  // --noise-threshold T: adaptive sampling, --spp becomes the per-pixel cap
+  int min_spp = 64, adaptive_step = 16;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value after %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -50,9 +54,13 @@ int main(int argc, char** argv)
     else if (a == "--sun") sun = true;
     else if (a == "--sky") sky = true;
     else if (a == "--reference-launches") reference_launches = true;  // one launch of --spp samples per frame exactly as the reference computes it (firsthit quirk)
+    else if (a == "--noise-threshold") noise_threshold = float(std::atof(next()));
+    else if (a == "--min-spp") min_spp = std::atoi(next());
+    else if (a == "--adaptive-step") adaptive_step = std::atoi(next());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S]]\n", argv[0]); return 2; }
+  if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   const float time_step = 1.0f / fps;
   try {
     std::filesystem::create_directories(out_dir);
@@ -83,6 +91,7 @@ int main(int argc, char** argv)
     camera.m_fov = fov_deg / 180.0f * float(M_PI);
     camera.m_F = F;
     camera.m_focus = focus;
+    cwl::CUDABuffer<uint32_t> sample_counts(n_px);  // (--noise-threshold: the per-pixel counts a frame ends with)
     fredholm::RenderLayer render_layer{layer_beauty.get_device_ptr(), layer_position.get_device_ptr(), layer_depth.get_device_ptr(), layer_normal.get_device_ptr(),
                                        layer_texcoord.get_device_ptr(), layer_albedo.get_device_ptr()};
     if (sun) renderer.set_directional_light(make_float3(20, 20, 20), make_float3(-0.1f, 1, 0.1f), 1.0f);  // rtcamp8.cpp:133-134
@@ -104,7 +113,23 @@ int main(int argc, char** argv)
           layer_beauty.clear(); layer_position.clear(); layer_normal.clear(); layer_depth.clear(); layer_texcoord.clear(); layer_albedo.clear();
           renderer.init_render_states();
           renderer.set_time(time);
-          renderer.render(camera, make_float3(0, 0, 0), render_layer, uint32_t(n_spp), uint32_t(max_depth));
+          if (noise_threshold < 0.0f) {
+            renderer.render(camera, make_float3(0, 0, 0), render_layer, uint32_t(n_spp), uint32_t(max_depth));
+          } else {  // calls of --adaptive-step samples until every pixel has stopped or reached --spp
+            renderer.set_adaptive_sampling(noise_threshold, uint32_t(min_spp), uint32_t(adaptive_step));
+            for (int done = 0; done < n_spp;) {
+              const int k = n_spp - done < adaptive_step ? n_spp - done : adaptive_step;
+              renderer.render(camera, make_float3(0, 0, 0), render_layer, uint32_t(k), uint32_t(max_depth));
+              done += k;
+              if (done < n_spp && renderer.active_pixel_count() == 0) break;
+            }
+            renderer.get_sample_counts(sample_counts);
+            std::vector<uint32_t> counts;
+            sample_counts.copy_from_device_to_host(counts);
+            double sum = 0.0;
+            for (uint32_t c : counts) sum += c;
+            std::printf("[Adaptive] frame %d: mean spp %.1f of at most %d\n", frame_idx, sum / double(counts.size()), n_spp);
+          }
           CUDA_SYNC_CHECK();
           denoiser.denoise();
           PostProcessParams params{bloom, 2.0f, 5.0f, 80.0f, 1.0f};  // rtcamp8.cpp:57-60,207-212

@@ -3,6 +3,7 @@
 // Mirrors the host duties of fredholm::Renderer (fredholm/include/fredholm/renderer.h).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -583,7 +584,8 @@ int fh_ctx_destroy(fh_ctx* ctx)
   void* ptrs[] = {ctx->d_sample_issued, ctx->d_sobol, ctx->d_sobol_bytes, ctx->d_alpha_rec, ctx->d_lut_refl, ctx->d_lut_sheen, ctx->d_face_rec, ctx->d_face_cls, ctx->d_materials, ctx->d_lights, ctx->d_bvh2_nodes, ctx->d_bvh2_tris,
                   ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_sample_count, ctx->d_owned, ctx->d_trace_counters, ctx->d_texels, ctx->d_textures, ctx->d_srgb_lut, ctx->d_ibl,
                   ctx->d_bloom_weights, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
-                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node};
+                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
+                  ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (fh_ctx::ShardList& c : ctx->shard_lists)
@@ -591,6 +593,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
   if (ctx->frame_map.d_all) (void)hipFree(ctx->frame_map.d_all);
   for (int k = 0; k < 4; ++k) if (ctx->d_split[k]) (void)hipFree(ctx->d_split[k]);
   if (ctx->d_split_counters) (void)hipFree(ctx->d_split_counters);
+  if (ctx->h_active_count) (void)hipHostFree(ctx->h_active_count);
   if (ctx->sky_stream) { (void)hipStreamSynchronize(ctx->sky_stream); (void)hipStreamDestroy(ctx->sky_stream); }
   if (ctx->ev_sky) (void)hipEventDestroy(ctx->ev_sky);
   for (auto& s : ctx->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
@@ -833,13 +836,81 @@ int fh_clear_ibl(fh_ctx* ctx)
   return FH_OK;
 }
 
+// the moments of adaptive sampling start at sample 0: allocated and cleared whenever the mode is on and the counters are reset (0 * inf would poison a reset's
+// running means otherwise), and when the mode is turned on
+static int adaptive_reset(fh_ctx* ctx)
+{
+  ctx->adapt_total = 0;
+  if (!ctx->adaptive) return FH_OK;
+  const size_t px = (size_t)ctx->width * ctx->height;
+  if (!ctx->d_moments) FH_HIP(hipMalloc((void**)&ctx->d_moments, 8ull * px));
+  if (!ctx->d_sky_taken) {
+    FH_HIP(hipMalloc((void**)&ctx->d_sky_taken, sizeof(unsigned long long)));
+    FH_HIP(hipMemsetAsync(ctx->d_sky_taken, 0, sizeof(unsigned long long), ctx->stream));
+  }
+  FH_HIP(hipMemsetAsync(ctx->d_moments, 0, 8ull * px, ctx->stream));
+  return adaptive_upload(ctx);
+}
+
 int fh_init_render_states(fh_ctx* ctx)
 {
   CTX_CHECK(ctx);
   if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "resolution not set");
   FH_HIP(hipMemsetAsync(ctx->d_sample_count, 0, 4ull * ctx->width * ctx->height, ctx->stream));
   FH_HIP(hipMemsetAsync(ctx->d_sample_issued, 0, 4ull * ctx->width * ctx->height, ctx->stream));
+  ctx->accumulated = false;
+  return adaptive_reset(ctx);
+}
+
+int fh_set_adaptive_sampling(fh_ctx* ctx, const fh_adaptive_params* p)
+{
+  CTX_CHECK(ctx);
+  if (!p) { ctx->adaptive = false; return FH_OK; }
+  if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold)) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_sampling: threshold must be finite and >= 0");
+  if (!(p->floor > 0.0f) || !std::isfinite(p->floor)) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_sampling: floor must be finite and > 0");
+  if (p->min_samples < 2u) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_sampling: min_samples must be >= 2");
+  if (p->step < 1u) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_sampling: step must be >= 1");
+  if (ctx->adaptive && std::memcmp(&ctx->adapt, p, sizeof *p) == 0) return FH_OK;
+  if (ctx->accumulated) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_sampling: samples were accumulated since fh_init_render_states / fh_set_resolution (the moments must start at sample 0)");
+  if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_sampling: resolution not set");
+  ctx->adapt = *p;
+  ctx->adaptive = true;
+  return adaptive_reset(ctx);
+}
+
+int fh_get_adaptive_sampling(fh_ctx* ctx, int* enabled, fh_adaptive_params* p)
+{
+  CTX_CHECK(ctx);
+  if (enabled) *enabled = ctx->adaptive ? 1 : 0;
+  if (p) *p = ctx->adapt;
   return FH_OK;
+}
+
+int fh_get_sample_counts(fh_ctx* ctx, uint32_t* counts)
+{
+  CTX_CHECK(ctx);
+  if (!counts) return fail(ctx, FH_E_INVALID, "fh_get_sample_counts: null argument");
+  if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_get_sample_counts: resolution not set");
+  FH_HIP(hipMemcpyAsync(counts, ctx->d_sample_count, 4ull * ctx->width * ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+  return FH_OK;
+}
+
+int fh_get_luminance_moments(fh_ctx* ctx, float* m)
+{
+  CTX_CHECK(ctx);
+  if (!m) return fail(ctx, FH_E_INVALID, "fh_get_luminance_moments: null argument");
+  if (!ctx->adaptive || !ctx->d_moments) return fail(ctx, FH_E_INVALID, "fh_get_luminance_moments: adaptive sampling is off");
+  FH_HIP(hipMemcpyAsync(m, ctx->d_moments, 8ull * ctx->width * ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+  return FH_OK;
+}
+
+int fh_active_pixel_count(fh_ctx* ctx, uint32_t* out)
+{
+  CTX_CHECK(ctx);
+  if (!out) return fail(ctx, FH_E_INVALID, "fh_active_pixel_count: null argument");
+  if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_active_pixel_count: resolution not set");
+  if (!ctx->adaptive) { *out = ctx->n_owned; return FH_OK; }
+  return adaptive_select(ctx, ctx->stream, ctx->d_owned, ctx->d_owned_xy, ctx->n_owned, out);
 }
 
 // known-answer hooks of the sample-index tests: both per-pixel counters at once, after everything queued on the context has finished (the passes of a call in flight
@@ -853,6 +924,17 @@ int fh_kat_set_sample_counts(fh_ctx* ctx, const uint32_t* counts, uint32_t n_pix
   if (rc) return rc;
   FH_HIP(hipMemcpy(ctx->d_sample_count, counts, 4ull * n_pixels, hipMemcpyHostToDevice));
   FH_HIP(hipMemcpy(ctx->d_sample_issued, counts, 4ull * n_pixels, hipMemcpyHostToDevice));
+  return FH_OK;
+}
+
+int fh_kat_set_issued(fh_ctx* ctx, const uint32_t* issued, uint32_t n_pixels)
+{
+  CTX_CHECK(ctx);
+  if (!ctx->d_sample_issued) return fail(ctx, FH_E_INVALID, "fh_kat_set_issued: resolution not set");
+  if (!issued || (uint64_t)n_pixels != (uint64_t)ctx->width * ctx->height) return fail(ctx, FH_E_INVALID, "fh_kat_set_issued: one count per pixel of the frame");
+  const int rc = fh_sync(ctx);
+  if (rc) return rc;
+  FH_HIP(hipMemcpy(ctx->d_sample_issued, issued, 4ull * n_pixels, hipMemcpyHostToDevice));
   return FH_OK;
 }
 
@@ -876,6 +958,7 @@ int fh_set_resolution(fh_ctx* ctx, uint32_t w, uint32_t h)
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->d_sample_count) { (void)hipFree(ctx->d_sample_count); ctx->d_sample_count = nullptr; }
   if (ctx->d_sample_issued) { (void)hipFree(ctx->d_sample_issued); ctx->d_sample_issued = nullptr; }
+  if (ctx->d_moments) { (void)hipFree(ctx->d_moments); ctx->d_moments = nullptr; }  // (fh_init_render_states below makes it again at the new size if the mode is on)
   ctx->width = w; ctx->height = h;
   FH_HIP(hipMalloc((void**)&ctx->d_sample_count, 4ull * w * h));
   FH_HIP(hipMalloc((void**)&ctx->d_sample_issued, 4ull * w * h));
@@ -1007,6 +1090,14 @@ int fh_sync(fh_ctx* ctx)
     ctx->event_pool.push_back(s.b);
   }
   ctx->spans.clear();
+  if (ctx->sky_taken_pending) {  // samples the adaptive k_sky_pixels took (it stops pixels on the device)
+    unsigned long long taken = 0;
+    FH_HIP(hipMemcpy(&taken, ctx->d_sky_taken, sizeof taken, hipMemcpyDeviceToHost));
+    FH_HIP(hipMemset(ctx->d_sky_taken, 0, sizeof taken));
+    ctx->stats.paths += taken;
+    ctx->stats.sky_pixel_samples += taken;
+    ctx->sky_taken_pending = false;
+  }
   if (ctx->stats.sky_pixel_samples && ctx->d_split_counters) {  // k_sky_pixels re-runs the scene-bounds test of every sample it renders: a hit there means the conservative split was wrong
     uint32_t violations = 0;
     FH_HIP(hipMemcpy(&violations, ctx->d_split_counters + 2, 4, hipMemcpyDeviceToHost));

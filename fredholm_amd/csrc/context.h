@@ -113,6 +113,19 @@ struct fh_ctx {
   struct FrameMap { uint32_t world = 0, width = 0, height = 0, tile_w = 0, tile_h = 0; uint32_t* d_all = nullptr; std::vector<uint32_t> start; };
   FrameMap frame_map;
   std::vector<ShardList> shard_lists;  // ownership lists of other ranks' shards, built on first use by fh_unpack_shard and kept (freed with the context)
+  // adaptive sampling (fh_set_adaptive_sampling; render.hip: k_adaptive_select and the round loop of render_submit)
+  bool adaptive = false;
+  fh_adaptive_params adapt{};
+  float2* d_moments = nullptr;         // (m1, m2) per pixel of the frame, cleared by fh_init_render_states
+  bool accumulated = false;            // a call has submitted samples since fh_init_render_states / fh_set_resolution
+  uint32_t adapt_total = 0;            // samples requested since then: the count every pixel still active shares (rounds end where it is a multiple of step)
+  uint32_t* d_active[2] = {nullptr, nullptr};  // the active pixels of the round: image indices, x | y << 16 (a stable compaction of the call's base list)
+  uint32_t* d_active_blocks = nullptr; // per-workgroup counts, then their exclusive scan; word [capacity blocks] = the active count
+  uint32_t active_capacity = 0;
+  uint32_t* h_active_count = nullptr;  // pinned: the count read back at every boundary
+  unsigned long long* d_sky_taken = nullptr;  // samples the adaptive k_sky_pixels took since the last fh_sync (fh_stats.paths)
+  bool sky_taken_pending = false;
+  void* d_sky_adaptive = nullptr;      // the adaptive k_sky_pixels' arguments beyond the plain form's (render.hip: SkyAdaptive)
 
   // environment (renderer.h:819-827)
   bool has_dir = false;
@@ -226,6 +239,8 @@ int fail(fh_ctx* ctx, int code, const std::string& msg);
 SceneDev scene_dev(const fh_ctx* ctx);
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);  // render.hip
+int adaptive_upload(fh_ctx* ctx);  // render.hip
+int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, uint32_t* n_active);  // render.hip (synchronising)
 int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity);   // render.hip
 uint64_t pool_bytes_per_path(const fh_ctx* ctx);            // capi.hip
 void pool_release(fh_ctx* ctx);

@@ -35,6 +35,7 @@
 
 #include "context.h"
 #include "fh_bsdf.h"
+#include "fh_tonemap.h"
 #include "fh_trace.h"
 
 namespace fh {
@@ -297,10 +298,54 @@ __global__ void __launch_bounds__(kBlock) k_split_pixels(FrameDev fr, SplitDev s
   }
 }
 
-// all `n_samples` samples of this call for the sky pixels: k_generate's path for a ray that misses the scene bounds and k_accumulate's update of the running means, fused
-__global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev layers, uint32_t* issued, const uint32_t* sky_px, const uint32_t* sky_xy, uint32_t n_sky, uint32_t n_samples,
-                                                     uint32_t* violations)
+// ------------------------------------------------------------------------------------------------
+// Adaptive sampling (fh_set_adaptive_sampling).  The moments (m1, m2) are running means of the luminance y of the NaN-guarded radiance and of y * y, updated with the
+// beauty layer's coefficients; a pixel whose count n is a boundary (n >= min_samples, n % step == 0) and whose relative error estimate is within the threshold gets
+// no further samples.  Its state then no longer changes, so the predicate keeps holding until fh_init_render_states: the selection below can re-evaluate it from the
+// state alone, and a pixel that stops after s samples holds the bits a plain render holds after s samples.
+struct AdaptiveDev {
+  float2* moments;
+  const uint32_t* count;  // sample_count
+  float threshold, floor;
+  uint32_t min_samples, step;
+};
+
+FH_D bool adaptive_converged(const AdaptiveDev& ad, uint32_t n, float m1, float m2)
 {
+  if (n < ad.min_samples || n % ad.step != 0u) return false;
+  float d = m2 - m1 * m1;
+  if (d < 0.0f) d = 0.0f;  // (NaN stays NaN)
+  const float var = d * ((float)n / (float)(n - 1u));
+  const float e2 = var / (float)n;
+  const float ref = m1 > ad.floor ? m1 : ad.floor;  // (NaN m1: floor)
+  const float t = ad.threshold * ref;
+  return ad.threshold > 0.0f && e2 <= t * t;  // (any NaN: not converged)
+}
+
+FH_D void moments_update(float& m1, float& m2, float coef, float fn, f3 radiance)
+{
+  const float y = luminance_rgb(radiance.x, radiance.y, radiance.z);
+  m1 = coef * (fn * m1 + y);
+  m2 = coef * (fn * m2 + y * y);
+}
+
+// all `n_samples` samples of this call for the sky pixels: k_generate's path for a ray that misses the scene bounds and k_accumulate's update of the running means, fused.
+// ADAPTIVE: also the moments, and a pixel stops at the first boundary where it is converged (issued = first + samples taken, counted in SkyAdaptive::taken for fh_stats.paths).
+// The adaptive form takes its extra state through the pointer in place of `violations`: the kernel arguments of the plain form stay as they are.
+struct SkyAdaptive {
+  AdaptiveDev ad;
+  uint32_t* violations;
+  unsigned long long* taken;
+};
+template <bool ADAPTIVE>
+__global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev layers, uint32_t* issued, const uint32_t* sky_px, const uint32_t* sky_xy, uint32_t n_sky, uint32_t n_samples,
+                                                     std::conditional_t<ADAPTIVE, const SkyAdaptive*, uint32_t*> violations_or_adaptive)
+{
+  uint32_t* violations;
+  AdaptiveDev ad{};
+  if constexpr (ADAPTIVE) { ad = violations_or_adaptive->ad; violations = violations_or_adaptive->violations; }
+  else violations = violations_or_adaptive;
+  unsigned long long n_taken = 0;
   __shared__ SobolRows<1> rows;
   __shared__ HosekSky s_sky;
   stage_sky(fr, s_sky);
@@ -317,7 +362,11 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev la
     bool violated = false;
     uint32_t blk = 0xffffffffu;  // sixteen consecutive samples share most of their two CMJ draws (fh_sampler.h: cmj_block)
     CmjBlock b0{}, b1{};
+    float2 m = make_float2(0.0f, 0.0f);
+    if constexpr (ADAPTIVE) m = ad.moments[image_idx];
+    uint32_t taken = n_samples;
     for (uint32_t k = 0; k < n_samples; ++k) {
+      if constexpr (ADAPTIVE) { if (adaptive_converged(ad, n_spp, m.x, m.y)) { taken = k; break; } }
       f3 org, dir;
       const uint32_t n = first + k;
       if ((n >> 4) != blk) {
@@ -342,10 +391,12 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev la
       tcx = coef * (fn * tcx + 0.0f);
       tcy = coef * (fn * tcy + 0.0f);
       albedo = coef * (fn * albedo + mk3(0.0f));
+      if constexpr (ADAPTIVE) moments_update(m.x, m.y, coef, fn, radiance);
       n_spp++;
     }
     if (violated) atomicAdd(violations, 1u);
-    issued[image_idx] = first + n_samples;
+    if constexpr (ADAPTIVE) { ad.moments[image_idx] = m; n_taken += taken; issued[image_idx] = first + taken; }
+    else issued[image_idx] = first + n_samples;
     layers.sample_count[image_idx] = n_spp;
     layers.beauty[image_idx] = mk4(beauty, 1.0f);
     layers.position[image_idx] = mk4(position, 1.0f);
@@ -353,7 +404,72 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev la
     layers.depth[image_idx] = depth;
     layers.texcoord[image_idx] = make_float4(tcx, tcy, 0.0f, 1.0f);
     layers.albedo[image_idx] = mk4(albedo, 1.0f);
+  }  if constexpr (ADAPTIVE) {  // (one global atomic per workgroup)
+    __shared__ unsigned long long s_taken;
+    if (threadIdx.x == 0u) s_taken = 0ull;
+    __syncthreads();
+    if (n_taken) atomicAdd(&s_taken, n_taken);
+    __syncthreads();
+    if (threadIdx.x == 0u && s_taken) atomicAdd(violations_or_adaptive->taken, s_taken);
   }
+}
+
+// The stable compaction of a base list (the owned pixels, or the pixels the passes render when the call splits off the sky) into the pixels still active:
+// per-workgroup counts, one scan of them, and a scatter that keeps the base list's order (the 8x8 pixel blocks of the ownership list stay together).
+// `blocks` holds one count per workgroup of 256 base entries, then the total.
+FH_D bool adaptive_active(const AdaptiveDev& ad, uint32_t image_idx)
+{
+  const float2 m = ad.moments[image_idx];
+  return !adaptive_converged(ad, ad.count[image_idx], m.x, m.y);
+}
+
+__global__ void __launch_bounds__(kBlock) k_adaptive_count(AdaptiveDev ad, const uint32_t* base_px, uint32_t n_base, uint32_t* blocks)
+{
+  __shared__ uint32_t s_w[kBlock / 64];
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool act = i < n_base && adaptive_active(ad, base_px[i]);
+  const unsigned long long m = __ballot(act);
+  if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0u) blocks[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// one workgroup: exclusive scan of the n_blocks counts in place, the total after them
+__global__ void __launch_bounds__(kBlock) k_adaptive_scan(uint32_t* blocks, uint32_t n_blocks)
+{
+  __shared__ uint32_t s[kBlock];
+  const uint32_t per = (n_blocks + kBlock - 1u) / kBlock;
+  const uint32_t lo = threadIdx.x * per < n_blocks ? threadIdx.x * per : n_blocks;
+  const uint32_t hi = lo + per < n_blocks ? lo + per : n_blocks;
+  uint32_t sum = 0;
+  for (uint32_t b = lo; b < hi; ++b) sum += blocks[b];
+  s[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    uint32_t t = 0;
+    for (uint32_t k = 0; k < (uint32_t)kBlock; ++k) { const uint32_t v = s[k]; s[k] = t; t += v; }
+    blocks[n_blocks] = t;
+  }
+  __syncthreads();
+  uint32_t run = s[threadIdx.x];
+  for (uint32_t b = lo; b < hi; ++b) { const uint32_t v = blocks[b]; blocks[b] = run; run += v; }
+}
+
+__global__ void __launch_bounds__(kBlock) k_adaptive_select(AdaptiveDev ad, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, const uint32_t* blocks,
+                                                          uint32_t* out_px, uint32_t* out_xy)
+{
+  __shared__ uint32_t s_w[kBlock / 64];
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t px = 0;
+  bool act = false;
+  if (i < n_base) { px = base_px[i]; act = adaptive_active(ad, px); }
+  const unsigned long long m = __ballot(act);
+  if (lane == 0u) s_w[wave] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t pos = blocks[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  for (uint32_t w = 0; w < wave; ++w) pos += s_w[w];
+  if (act) { out_px[pos] = px; out_xy[pos] = base_xy[i]; }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1545,9 +1661,12 @@ __global__ void __launch_bounds__(kBlock) k_firsthit_scan(PoolDev pool, const ui
 }
 
 // ------------------------------------------------------------------------------------------------
-template <bool QUIRK>
-__global__ void __launch_bounds__(kBlock) k_accumulate(PoolDev pool, LayersDev layers, const uint32_t* owned, uint32_t n_owned, uint32_t n_batch, float4* carry)
+// ADAPTIVE: the luminance moments too, through the pointer in place of `carry` (the bug-compat mode's; the two do not combine)
+template <bool QUIRK, bool ADAPTIVE = false>
+__global__ void __launch_bounds__(kBlock) k_accumulate(PoolDev pool, LayersDev layers, const uint32_t* owned, uint32_t n_owned, uint32_t n_batch,
+                                                     std::conditional_t<ADAPTIVE, float2, float4>* carry)
 {
+  static_assert(!(QUIRK && ADAPTIVE), "FH_FLAG_REFERENCE_FIRSTHIT does not combine with adaptive sampling");
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_owned; i += gridDim.x * blockDim.x) {
     const uint32_t image_idx = owned[i];
     uint32_t n_spp = layers.sample_count[image_idx];
@@ -1558,11 +1677,13 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(PoolDev pool, LayersDev l
     // bug-compat mode: the payload's AOVs persist from the launch's first hit (pt.cu:483-487); carried across the passes of the launch
     f3 apos = mk3(0.0f), anrm = mk3(0.0f), aalb = mk3(0.0f);
     float au = 0.0f, av = 0.0f, ad = 0.0f;
-    if (QUIRK) {
+    if constexpr (QUIRK) {
       apos = mk3(carry[4 * (size_t)image_idx]); anrm = mk3(carry[4 * (size_t)image_idx + 1]); aalb = mk3(carry[4 * (size_t)image_idx + 2]);
       const float4 td = carry[4 * (size_t)image_idx + 3];
       au = td.x; av = td.y; ad = td.z;
     }
+    float2 m = make_float2(0.0f, 0.0f);
+    if constexpr (ADAPTIVE) m = carry[image_idx];
     for (uint32_t k = 0; k < n_batch; ++k) {
       const uint32_t p = k * n_owned + i;
       const f3 L = mk3(pool.rad[p]);
@@ -1584,9 +1705,11 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(PoolDev pool, LayersDev l
       tcx = coef * (fn * tcx + au);
       tcy = coef * (fn * tcy + av);
       albedo = coef * (fn * albedo + aalb);
+      if constexpr (ADAPTIVE) moments_update(m.x, m.y, coef, fn, radiance);
       n_spp++;
     }
-    if (QUIRK) {
+    if constexpr (ADAPTIVE) carry[image_idx] = m;
+    if constexpr (QUIRK) {
       carry[4 * (size_t)image_idx] = mk4(apos, 0.0f); carry[4 * (size_t)image_idx + 1] = mk4(anrm, 0.0f); carry[4 * (size_t)image_idx + 2] = mk4(aalb, 0.0f);
       carry[4 * (size_t)image_idx + 3] = make_float4(au, av, ad, 0.0f);
     }
@@ -1938,12 +2061,60 @@ static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
   return FH_OK;
 }
 
+static AdaptiveDev adaptive_dev(const fh_ctx* ctx)
+{
+  return AdaptiveDev{ctx->d_moments, ctx->d_sample_count, ctx->adapt.threshold, ctx->adapt.floor, ctx->adapt.min_samples, ctx->adapt.step};
+}
+
+// the device copy of the adaptive k_sky_pixels' state: made again whenever the parameters or the moments buffer change (capi.hip: adaptive_reset), when no launch reads it
+int adaptive_upload(fh_ctx* ctx)
+{
+  if (!ctx->d_sky_adaptive) FH_HIP(hipMalloc(&ctx->d_sky_adaptive, sizeof(SkyAdaptive)));
+  const SkyAdaptive h{adaptive_dev(ctx), ctx->d_split_counters + 2, ctx->d_sky_taken};
+  FH_HIP(hipStreamSynchronize(ctx->stream));  // (earlier calls have joined the main stream)
+  FH_HIP(hipMemcpy(ctx->d_sky_adaptive, &h, sizeof h, hipMemcpyHostToDevice));
+  return FH_OK;
+}
+
+// the active pixels of a base list into ctx->d_active, ordered on `st`; waits for the count (the passes of a round are sized with it)
+int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, uint32_t* n_active)
+{
+  if (ctx->active_capacity < ctx->n_owned || !ctx->h_active_count) {
+    FH_HIP(hipDeviceSynchronize());  // (launches of earlier calls may still read the old lists)
+    for (int k = 0; k < 2; ++k) { if (ctx->d_active[k]) (void)hipFree(ctx->d_active[k]); ctx->d_active[k] = nullptr; }
+    if (ctx->d_active_blocks) (void)hipFree(ctx->d_active_blocks);
+    ctx->d_active_blocks = nullptr;
+    ctx->active_capacity = 0;
+    for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&ctx->d_active[k], 4ull * ctx->n_owned));
+    FH_HIP(hipMalloc((void**)&ctx->d_active_blocks, 4ull * ((ctx->n_owned + kBlock - 1u) / kBlock + 1u)));
+    if (!ctx->h_active_count) FH_HIP(hipHostMalloc((void**)&ctx->h_active_count, 4, hipHostMallocDefault));
+    ctx->active_capacity = ctx->n_owned;
+  }
+  if (n_base > ctx->active_capacity) return fail(ctx, FH_E_INVALID, "adaptive_select: base list longer than the owned pixels");
+  *n_active = 0;
+  if (n_base == 0) return FH_OK;
+  const AdaptiveDev ad = adaptive_dev(ctx);
+  const uint32_t n_blocks = (n_base + kBlock - 1u) / kBlock;
+  hipLaunchKernelGGL(k_adaptive_count, dim3(n_blocks), dim3(kBlock), 0, st, ad, base_px, n_base, ctx->d_active_blocks);
+  hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, st, ctx->d_active_blocks, n_blocks);
+  hipLaunchKernelGGL(k_adaptive_select, dim3(n_blocks), dim3(kBlock), 0, st, ad, base_px, base_xy, n_base, ctx->d_active_blocks, ctx->d_active[0], ctx->d_active[1]);
+  FH_HIP(hipMemcpyAsync(ctx->h_active_count, ctx->d_active_blocks + n_blocks, 4, hipMemcpyDeviceToHost, st));
+  FH_HIP(hipStreamSynchronize(st));
+  *n_active = *ctx->h_active_count;
+  if (*n_active > n_base) return fail(ctx, FH_E_HIP, "adaptive_select: count beyond the base list");
+  return FH_OK;
+}
+
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed)
 {
   if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_render: scene not uploaded or BVH not built");
   if (ctx->width == 0 || ctx->height == 0 || !ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_render: resolution not set");
   if (max_depth > 64) return fail(ctx, FH_E_INVALID, "fh_render: max_depth > 64 is not supported");
   if (ctx->n_owned == 0 || n_samples == 0) return FH_OK;
+  const bool adaptive = ctx->adaptive;
+  if (adaptive && (ctx->flags & FH_FLAG_REFERENCE_FIRSTHIT) != 0 && n_samples > 1)
+    return fail(ctx, FH_E_INVALID, "fh_render: FH_FLAG_REFERENCE_FIRSTHIT with n_samples > 1 does not combine with adaptive sampling (its first-hit state is per launch)");
+  ctx->accumulated = true;
   // The default pool size (32 Mi paths per pool) is a wish: whenever a pool has to be allocated -- the first frame, after fh_scene_upload changed what a path record
   // holds, after a release -- all pools together are kept within A QUARTER of what the device has free at that moment, counting what the pools already hold as free.
   // (A pool is allocated for the paths a pass really starts -- the pixels that can see the scene x the samples of the pass, pool_ensure -- so the cap is an upper bound.)
@@ -2030,21 +2201,25 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
       n_px = ctx->n_wave_px; n_sky = ctx->n_sky_px;
     }
   }
-  uint32_t target = ctx->pool_target > ctx->n_owned ? ctx->pool_target : ctx->n_owned;
-  uint32_t batch = n_px ? target / n_px : n_samples;
-  if (batch > n_samples) batch = n_samples;
-  if (batch > 65535u) batch = 65535u;  // (k_generate's grid has one row per sample of the pass)
-  if (batch < 1) batch = 1;
-  if (batch < n_samples) {  // equal passes, and whole rounds of the passes in flight: a call of 1024 samples with room for 248 per pass runs six passes of 171, not four of
-    // 248 and a runt of 32 -- the last pass of an incomplete round has nothing to overlap with (configs[2]: 3 / 4 / 5 / 6 passes measure 7700 / 7577 / 7578 / 7598 Msamples/s, r5-5)
-    uint32_t passes = (n_samples + batch - 1u) / batch;
-    const uint32_t slots = (uint32_t)ctx->n_slots;
-    if (slots > 1u && passes > slots && passes % slots != 0u && (passes / slots + 1u) * slots <= n_samples) passes = (passes / slots + 1u) * slots;
-    batch = (n_samples + passes - 1u) / passes;
-  }
-  // (the passes of a call overlap, three in flight: a big call that would fit one or two passes is cut into three of the same size -- unless its passes run one after
-  // the other anyway: the bug-compat mode and the measuring mode, where a split is pure overhead)
-  if (!quirk_call && (ctx->flags & FH_FLAG_SERIAL_PASSES) == 0 && (n_samples + batch - 1u) / batch < (uint32_t)ctx->n_slots && n_samples >= (uint32_t)ctx->n_slots && (unsigned long long)n_samples * n_px >= 3ull << 24) batch = (n_samples + (uint32_t)ctx->n_slots - 1u) / (uint32_t)ctx->n_slots;
+  const uint32_t target = ctx->pool_target > ctx->n_owned ? ctx->pool_target : ctx->n_owned;
+  // samples per pass of a run of n_samples samples over n_px pixels (the whole call; in adaptive mode, one round)
+  auto batch_for = [&](uint32_t n_px, uint32_t n_samples) {
+    uint32_t batch = n_px ? target / n_px : n_samples;
+    if (batch > n_samples) batch = n_samples;
+    if (batch > 65535u) batch = 65535u;  // (k_generate's grid has one row per sample of the pass)
+    if (batch < 1) batch = 1;
+    if (batch < n_samples) {  // equal passes, and whole rounds of the passes in flight: a call of 1024 samples with room for 248 per pass runs six passes of 171, not four of
+      // 248 and a runt of 32 -- the last pass of an incomplete round has nothing to overlap with (configs[2]: 3 / 4 / 5 / 6 passes measure 7700 / 7577 / 7578 / 7598 Msamples/s, r5-5)
+      uint32_t passes = (n_samples + batch - 1u) / batch;
+      const uint32_t slots = (uint32_t)ctx->n_slots;
+      if (slots > 1u && passes > slots && passes % slots != 0u && (passes / slots + 1u) * slots <= n_samples) passes = (passes / slots + 1u) * slots;
+      batch = (n_samples + passes - 1u) / passes;
+    }
+    // (the passes of a call overlap, three in flight: a big call that would fit one or two passes is cut into three of the same size -- unless its passes run one after
+    // the other anyway: the bug-compat mode and the measuring mode, where a split is pure overhead)
+    if (!quirk_call && (ctx->flags & FH_FLAG_SERIAL_PASSES) == 0 && (n_samples + batch - 1u) / batch < (uint32_t)ctx->n_slots && n_samples >= (uint32_t)ctx->n_slots && (unsigned long long)n_samples * n_px >= 3ull << 24) batch = (n_samples + (uint32_t)ctx->n_slots - 1u) / (uint32_t)ctx->n_slots;
+    return batch;
+  };
 
   const SceneDev sc_all = scene_dev(ctx);
   const SceneDev& sc = sc_all;  // (the passes below shadow this with their own copy: where rays start is a per-pass choice)
@@ -2083,9 +2258,15 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
     Span sp(ctx, sky_st, 4);
     uint32_t sky_grid = grid_for(n_sky);
     if (ctx->tun.sky_blocks_per_cu && sky_grid > ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu) sky_grid = ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu;
-    hipLaunchKernelGGL(k_sky_pixels, dim3(sky_grid), dim3(kBlock), 0, sky_st, fr, L, ctx->d_sample_issued, ctx->d_split[2], ctx->d_split[3], n_sky, n_samples, ctx->d_split_counters + 2);
-    ctx->stats.paths += (uint64_t)n_sky * n_samples;
-    ctx->stats.sky_pixel_samples += (uint64_t)n_sky * n_samples;
+    if (adaptive) {  // (the samples it takes are counted on the device: fh_sync adds them to the stats)
+      hipLaunchKernelGGL(k_sky_pixels<true>, dim3(sky_grid), dim3(kBlock), 0, sky_st, fr, L, ctx->d_sample_issued, ctx->d_split[2], ctx->d_split[3], n_sky, n_samples,
+                         (const SkyAdaptive*)ctx->d_sky_adaptive);
+      ctx->sky_taken_pending = true;
+    } else {
+      hipLaunchKernelGGL(k_sky_pixels<false>, dim3(sky_grid), dim3(kBlock), 0, sky_st, fr, L, ctx->d_sample_issued, ctx->d_split[2], ctx->d_split[3], n_sky, n_samples, ctx->d_split_counters + 2);
+      ctx->stats.paths += (uint64_t)n_sky * n_samples;
+      ctx->stats.sky_pixel_samples += (uint64_t)n_sky * n_samples;
+    }
   }
 
   // device facts and developer switches were read once at fh_ctx_create (context.h: Tunables)
@@ -2093,7 +2274,6 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   // wave-cooperative triangle tests (default for the wide BVH): queued candidates that trigger a round.  48 (r5-12) -- but ONE-PASS calls of scenes without cut-outs keep 32
   // (r5-13, profiles/r05_latency_defaults.log: the soup's fh_render(1 / 4 / 16) take 2.02 / 3.37 / 7.02 ms with 32 and 2.21 / 3.62 / 7.32 with 48 -- a launch of few rays
   // waits longer for 48 candidates; the interior with cut-outs is 1 % faster with 48 there too).  FH_COOP_T fixes it for every call.
-  const uint32_t coop_flush = (!tun.coop_flush_fixed && batch >= n_samples && !sc.has_alpha && tun.coop_flush > 32u) ? 32u : tun.coop_flush;
   const bool coop = sc.use_bvh8 != 0 && sc.bvh8.n_tris < kCoopMaxTris && tun.coop;
   // streaming form (FH_STREAM=0: one fixed batch per wave).  Through a small tree every ray takes the same few steps: nothing to rebalance, and the fixed
   // batches run without the refill machinery (1000-triangle soup: closest 7.4 -> 4.6 ms, secondary 2.6 -> 1.0 ms per 256 spp; even at ~2 K nodes; behind at 20 K)
@@ -2198,8 +2378,28 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
 
   // (Small calls -- the reference's callers: 1 sample per call in the GUI, controller.cpp:224, 16 in rtcamp8, rtcamp8.cpp:183-189 -- cut into PIXEL sub-passes, each a pass of
   // its own in its own pool on its own stream, were built and measured in round 5: slower, configs[3] 1 spp 6.45 -> 8.24 ms.  tools/patches/r6_pruned_switches.patch, r5-4.)
-  for (uint32_t done = 0; done < n_samples && n_px; done += batch) {
-    const uint32_t nb = (n_samples - done) < batch ? (n_samples - done) : batch;
+  // Rounds: a plain call is one.  In adaptive mode a round ends where the samples requested since fh_init_render_states are a multiple of `step`, and the pixels
+  // still active are selected from the call's base list at the start of every round (a call that starts between two boundaries selects too: that only drops the
+  // pixels that stopped before).  The selection waits for the round before it, and its count, read back, sizes the passes of the round.
+  const uint32_t* const base_px = px_list;
+  const uint32_t* const base_xy = xy_list;
+  const uint32_t n_base = n_px;
+  bool ran = false;
+  for (uint32_t call_done = 0; call_done < n_samples;) {
+  uint32_t n_round = n_samples - call_done;
+  if (adaptive) {
+    const uint32_t to_boundary = ctx->adapt.step - ctx->adapt_total % ctx->adapt.step;
+    if (n_round > to_boundary) n_round = to_boundary;
+    if (ran && last_slot != 0) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
+    const int rc = adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px);
+    if (rc) return rc;
+    px_list = ctx->d_active[0]; xy_list = ctx->d_active[1];
+  }
+  const uint32_t batch = batch_for(n_px, n_round);
+  const uint32_t coop_flush = (!tun.coop_flush_fixed && batch >= n_round && !sc.has_alpha && tun.coop_flush > 32u) ? 32u : tun.coop_flush;
+  for (uint32_t done = 0; done < n_round && n_px; done += batch) {
+    const uint32_t nb = (n_round - done) < batch ? (n_round - done) : batch;
+    ran = true;
     const uint32_t n_paths = n_px * nb;
     const uint32_t grid = grid_for(n_paths);
     // n_slots passes in flight (three by default, FH_PIPELINE): pass j lives in pool j % n_slots on the stream of that slot.  Only two things order consecutive passes: the sample
@@ -2219,7 +2419,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
     // each end in a few long rays.  The secondary rays of bounce b and the closest-hit launch of bounce b + 1 do not depend on each other -- the secondary launch reads the
     // secondary-ray records and adds to the radiance, the closest-hit launch and the routing read rays and write hits -- so the secondary launch goes to a second stream;
     // the shade kernels of bounce b + 1, which overwrite the records it reads, wait for it.  (Calls of several passes overlap whole passes instead.)
-    const bool single_pass = !serial && batch >= n_samples && n_samples == nb;
+    const bool single_pass = !serial && batch >= n_round && n_round == nb;
     // ... or, where the streaming kernels trace the scene, both in ONE launch (k_trace_merged_stream): one end instead of two, no second stream (FH_MERGE=0: the two-stream form)
     const bool merge = single_pass && stream && !count && tun.merge_trace;
     const bool overlap = single_pass && tun.overlap_secondary && !merge;
@@ -2424,8 +2624,9 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
     if (prev != slot && ctx->acc_valid[prev]) FH_HIP(hipStreamWaitEvent(st, ctx->ev_acc[prev], 0));
     {
       Span sp(ctx, st, 5);
-      if (quirk) hipLaunchKernelGGL(k_accumulate<true>, dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, ctx->d_quirk_aov);
-      else hipLaunchKernelGGL(k_accumulate<false>, dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, (float4*)nullptr);
+      if (quirk) hipLaunchKernelGGL((k_accumulate<true>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, ctx->d_quirk_aov);
+      else if (adaptive) hipLaunchKernelGGL((k_accumulate<false, true>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, ctx->d_moments);
+      else hipLaunchKernelGGL((k_accumulate<false>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, (float4*)nullptr);
       ctx->stats.n_accumulate_launches++;
     }
     FH_HIP(hipEventRecord(ctx->ev_acc[slot], st));
@@ -2439,9 +2640,13 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
       ctx->counters_bu[slot] = pass_bu;
     }
   }
+  call_done += n_round;
+  ctx->adapt_total += n_round;
+  if (adaptive && n_px == 0) { ctx->adapt_total += n_samples - call_done; break; }  // (the active set only shrinks: no later round has a pixel)
+  }
   // join: later work on the main stream (pack, post-process, copies, the caller's clears) sees every pass of this call
   // (the accumulates form a chain across the streams, so the last one implies all the others)
-  if (last_slot != 0 && n_px) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
+  if (last_slot != 0 && ran) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
   if (n_sky && sky_st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky_st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
   FH_HIP(hipGetLastError());
   return FH_OK;

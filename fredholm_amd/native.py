@@ -108,7 +108,24 @@ EXPORTS = [
     "fh_free", "fh_memset", "fh_copy_to_device", "fh_copy_to_host", "fh_copy_on_device", "fh_image_load_rgba8", "fh_image_free", "fh_stream", "fh_trace_rays", "fh_kernel_info", "fh_kat_hash", "fh_kat_cmj",
     "fh_kat_sobol", "fh_kat_elementary", "fh_kat_warp", "fh_kat_bsdf", "fh_kat_bsdf_lobes", "fh_kat_bsdf_ior", "fh_kat_sky", "fh_kat_hosek_state", "fh_kat_camera",
     "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
+    "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued",
 ]
+
+
+class AdaptiveParamsC(C.Structure):
+    """fh_adaptive_params (include/fredholm_hip.h)"""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32), ("step", C.c_uint32)]
+
+
+# argument types of the entry points declared with them (the adaptive-sampling ABI); every entry point returns int
+SIGNATURES = {
+    "fh_set_adaptive_sampling": [C.c_void_p, C.POINTER(AdaptiveParamsC)],
+    "fh_get_adaptive_sampling": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(AdaptiveParamsC)],
+    "fh_get_sample_counts": [C.c_void_p, C.c_void_p],
+    "fh_get_luminance_moments": [C.c_void_p, C.c_void_p],
+    "fh_active_pixel_count": [C.c_void_p, C.POINTER(C.c_uint32)],
+    "fh_kat_set_issued": [C.c_void_p, C.c_void_p, C.c_uint32],
+}
 
 _lib = None
 
@@ -134,6 +151,8 @@ def load_library(path=None):
         fn = getattr(L, name)
         if name not in ("fh_last_error", "fh_stream"):
             fn.restype = C.c_int
+        if name in SIGNATURES:
+            fn.argtypes = SIGNATURES[name]
     _lib = L
     return L
 

@@ -370,6 +370,66 @@ class Renderer:
     def wait_for_completion(self):
         self._ck(N.lib().fh_sync(self._ctx), "fh_sync")
 
+    # -- adaptive sampling (an extension beyond the reference class; include/fredholm_hip.h: fh_set_adaptive_sampling)
+    def set_adaptive_sampling(self, threshold, min_samples=64, step=16, floor=0.01):
+        """stop a pixel at the first count n (n >= min_samples, n % step == 0) where its relative error estimate is within `threshold`; accepted only before the
+        first sample after init_render_states / set_resolution.  render(n) then adds at most n samples per pixel."""
+        p = N.AdaptiveParamsC(float(threshold), float(floor), int(min_samples), int(step))
+        self._ck(N.lib().fh_set_adaptive_sampling(self._ctx, C.byref(p)), "fh_set_adaptive_sampling")
+
+    def clear_adaptive_sampling(self):
+        self._ck(N.lib().fh_set_adaptive_sampling(self._ctx, None), "fh_set_adaptive_sampling")
+
+    def adaptive_sampling(self):
+        """None while off, else the parameters as a dict"""
+        on, p = C.c_int(0), N.AdaptiveParamsC()
+        self._ck(N.lib().fh_get_adaptive_sampling(self._ctx, C.byref(on), C.byref(p)), "fh_get_adaptive_sampling")
+        return {"threshold": p.threshold, "floor": p.floor, "min_samples": p.min_samples, "step": p.step} if on.value else None
+
+    def get_sample_counts(self, device_ptr):
+        """width * height uint32 sample counts into a device buffer (ordered on the context stream)"""
+        self._ck(N.lib().fh_get_sample_counts(self._ctx, C.c_void_p(int(device_ptr))), "fh_get_sample_counts")
+
+    def get_luminance_moments(self, device_ptr):
+        """width * height float2 (m1, m2) into a device buffer (adaptive sampling must be on)"""
+        self._ck(N.lib().fh_get_luminance_moments(self._ctx, C.c_void_p(int(device_ptr))), "fh_get_luminance_moments")
+
+    def active_pixel_count(self):
+        """owned pixels the next render() would sample (synchronising)"""
+        out = C.c_uint32(0)
+        self._ck(N.lib().fh_active_pixel_count(self._ctx, C.byref(out)), "fh_active_pixel_count")
+        return int(out.value)
+
+    def sample_counts(self):
+        """(height, width) uint32"""
+        b = DeviceBuffer(self, 4 * self.m_width * self.m_height)
+        try:
+            self.get_sample_counts(b.ptr)
+            return b.download(np.uint32, (self.m_height, self.m_width))
+        finally:
+            b.free()
+
+    def luminance_moments(self):
+        """(height, width, 2) float32: the running means of the luminance and of its square"""
+        b = DeviceBuffer(self, 8 * self.m_width * self.m_height)
+        try:
+            self.get_luminance_moments(b.ptr)
+            return b.download(np.float32, (self.m_height, self.m_width, 2))
+        finally:
+            b.free()
+
+    def relative_error(self):
+        """(height, width) float32 display map of the estimate the stop rule tests: sqrt(e2) / max(m1, floor), e2 = max(m2 - m1^2, 0) * n / (n - 1) / n (NaN below two samples)"""
+        p = self.adaptive_sampling()
+        if p is None:
+            raise N.FredholmError("relative_error: adaptive sampling is off")
+        m = self.luminance_moments().astype(np.float64)
+        n = self.sample_counts().astype(np.float64)
+        var = np.maximum(m[..., 1] - m[..., 0] ** 2, 0.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            e2 = np.where(n >= 2, var * n / (n - 1) / n, np.nan)
+            return (np.sqrt(e2) / np.maximum(m[..., 0], p["floor"])).astype(np.float32)
+
     def stats(self):
         s = N.StatsC()
         self._ck(N.lib().fh_get_stats(self._ctx, C.byref(s)), "fh_get_stats")

@@ -15,6 +15,7 @@
 #endif
 #endif
 
+#include "../cwl/buffer.h"
 #include "../cwl/util.h"
 #include "../optwl/optwl.h"
 #include "camera.h"
@@ -101,6 +102,30 @@ class Renderer
     uint32_t flags = 0;  // (only this bit changes: timing / counting / serial-pass flags set through the C ABI stay as they are)
     cwl::check(m_ctx, fh_get_flags(m_ctx, &flags), "fh_get_flags");
     cwl::check(m_ctx, fh_set_flags(m_ctx, on ? (flags | FH_FLAG_REFERENCE_FIRSTHIT) : (flags & ~FH_FLAG_REFERENCE_FIRSTHIT)), "fh_set_flags");
+  }
+
+  // not in the reference: adaptive sampling (include/fredholm_hip.h: fh_set_adaptive_sampling).  A pixel stops at the first count n >= min_samples with
+  // n % step == 0 where its relative error estimate is within `threshold`; render(n) then adds at most n samples per pixel.  Set it right after
+  // init_render_states / set_resolution, before the first render of the frame.
+  void set_adaptive_sampling(float threshold, uint32_t min_samples = 64, uint32_t step = 16, float floor = 0.01f)
+  {
+    const fh_adaptive_params p{threshold, floor, min_samples, step};
+    cwl::check(m_ctx, fh_set_adaptive_sampling(m_ctx, &p), "fh_set_adaptive_sampling");
+  }
+  void clear_adaptive_sampling() { cwl::check(m_ctx, fh_set_adaptive_sampling(m_ctx, nullptr), "fh_set_adaptive_sampling"); }
+  void get_sample_counts(cwl::CUDABuffer<uint32_t>& counts)  // width * height
+  {
+    cwl::check(m_ctx, fh_get_sample_counts(m_ctx, counts.get_device_ptr()), "fh_get_sample_counts");
+  }
+  void get_luminance_moments(cwl::CUDABuffer<float2>& moments)  // width * height (m1, m2); adaptive sampling must be on
+  {
+    cwl::check(m_ctx, fh_get_luminance_moments(m_ctx, reinterpret_cast<float*>(moments.get_device_ptr())), "fh_get_luminance_moments");
+  }
+  uint32_t active_pixel_count()  // synchronising: owned pixels the next render would sample
+  {
+    uint32_t n = 0;
+    cwl::check(m_ctx, fh_active_pixel_count(m_ctx, &n), "fh_active_pixel_count");
+    return n;
   }
 
  private:

@@ -207,6 +207,29 @@ int fh_sync(fh_ctx* ctx); /* Renderer::wait_for_completion (renderer.h:736) */
 int fh_get_stats(fh_ctx* ctx, fh_stats* out);
 int fh_reset_stats(fh_ctx* ctx);
 
+/* -- adaptive sampling (an extension beyond the reference).  While it is on, every accumulated sample also updates two running means per pixel, m1 of the
+ * luminance y of the NaN-guarded radiance and m2 of y * y, with the beauty layer's coefficients.  At a pixel's sample count n with n >= min_samples and
+ * n % step == 0 the pixel is converged when threshold > 0 and e2 <= (threshold * max(m1, floor))^2, e2 = max(m2 - m1^2, 0) * n / (n - 1) / n; a converged
+ * pixel gets no further samples until fh_init_render_states / fh_set_resolution.  fh_render(n) then adds AT MOST n samples per owned pixel, and the bits of
+ * every pixel are those of a plain render at its sample count, however the samples are split into calls.  threshold = 0 tracks the moments and stops nothing. */
+typedef struct fh_adaptive_params {
+  float threshold;       /* >= 0, finite */
+  float floor;           /* > 0, finite: the smallest mean the relative error is taken of */
+  uint32_t min_samples;  /* >= 2 */
+  uint32_t step;         /* >= 1; 16 keeps every stop at the end of a CMJ 4x4 block */
+} fh_adaptive_params;
+/* NULL: off (the default).  Turning it on or changing its parameters is FH_E_INVALID once a sample has been accumulated since fh_init_render_states /
+ * fh_set_resolution (the moments start at sample 0); turning it off is accepted at any time.  FH_FLAG_REFERENCE_FIRSTHIT calls of n_samples > 1 are
+ * FH_E_INVALID while it is on. */
+int fh_set_adaptive_sampling(fh_ctx* ctx, const fh_adaptive_params* params);
+int fh_get_adaptive_sampling(fh_ctx* ctx, int* enabled, fh_adaptive_params* params);
+/* device buffer of width * height sample counts, copied on the context stream (works with the mode off too) */
+int fh_get_sample_counts(fh_ctx* ctx, uint32_t* counts);
+/* device buffer of width * height float2 (m1, m2), copied on the context stream; FH_E_INVALID while the mode is off */
+int fh_get_luminance_moments(fh_ctx* ctx, float* moments);
+/* synchronising: the owned pixels the next fh_render would sample (all of them while the mode is off) */
+int fh_active_pixel_count(fh_ctx* ctx, uint32_t* out);
+
 /* -- post chain: post_process_kernel_launch (fredholm/kernels/src/post-process.cu:5-35); all device pointers, float4 images */
 int fh_post_process(fh_ctx* ctx, const float* beauty_in, float* beauty_high_luminance, float* beauty_temp, int width, int height, const fh_post_params* params, float* beauty_out);
 

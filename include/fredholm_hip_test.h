@@ -65,6 +65,9 @@ int fh_kat_ray_start(fh_ctx* ctx, double out[5]);
 int fh_kat_set_sample_counts(fh_ctx* ctx, const uint32_t* counts, uint32_t n_pixels);
 /* read both back (either pointer may be NULL) */
 int fh_kat_sample_counts(fh_ctx* ctx, uint32_t* sample_count, uint32_t* issued, uint32_t n_pixels);
+/* the issued counters alone (sample_count keeps its value), after the work queued on the context has finished: with sample_count 0 and cleared layers a
+   one-sample render then leaves exactly sample issued[i]'s NaN-guarded radiance in pixel i's beauty (the adaptive-sampling tests replay the moments from it) */
+int fh_kat_set_issued(fh_ctx* ctx, const uint32_t* issued, uint32_t n_pixels);
 
 #ifdef __cplusplus
 }
