@@ -6,6 +6,7 @@
 //          [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--fov deg --F f --focus d]
 //          [--noise-threshold T [--min-spp M --adaptive-step S]]   (adaptive sampling: --spp is the per-pixel cap, the frame renders in calls of S samples
 //                                                                    until no pixel is active; prints the frame's mean spp)
+//          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -35,6 +36,7 @@ int main(int argc, char** argv)
   bool bloom = false, sun = false, sky = false, reference_launches = false;
   float noise_threshold = -1.0f;  // --noise-threshold T: adaptive sampling, --spp becomes the per-pixel cap
   int min_spp = 64, adaptive_step = 16;
+  std::vector<int> devices;  // --devices: empty = FH_DEVICES, or device 0
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value after %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -57,15 +59,21 @@ int main(int argc, char** argv)
     else if (a == "--noise-threshold") noise_threshold = float(std::atof(next()));
     else if (a == "--min-spp") min_spp = std::atoi(next());
     else if (a == "--adaptive-step") adaptive_step = std::atoi(next());
+    else if (a == "--devices") {
+      try { devices = cwl::parse_device_list(next(), "--devices"); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
+    }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S]]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S]] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   const float time_step = 1.0f / fps;
   try {
     std::filesystem::create_directories(out_dir);
+    if (!devices.empty()) cwl::check(nullptr, cwl::create_context(devices, &cwl::default_context()), "--devices");  // (before anything asks for the process-wide context)
     optwl::Context context;
     fredholm::Renderer renderer(context.get_context());
+    renderer.set_gather_layers(FH_LAYER_BEAUTY | FH_LAYER_NORMAL | FH_LAYER_ALBEDO);  // what the denoise / post / PNG chain below reads (a plain context ignores it)
+    if (renderer.group_size() > 1) std::printf("rendering on a group of %u members\n", renderer.group_size());
     renderer.create_module("pt.ptx");
     renderer.create_program_group();
     renderer.create_pipeline();

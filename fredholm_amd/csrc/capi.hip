@@ -27,6 +27,7 @@ int fail(fh_ctx* ctx, int code, const std::string& msg)
 {
   g_create_error = msg;
   if (ctx) ctx->err = msg;
+  if (ctx && ctx->owner) ctx->owner->err = "member " + std::to_string(ctx->member_index) + ": " + msg;
   return code;
 }
 
@@ -431,6 +432,36 @@ int rebuild_ownership(fh_ctx* ctx)
   return FH_OK;
 }
 
+}  // namespace
+
+// the ownership lists of all `world` ranks one after the other (fh_unpack_shards, and the gather of a group: group.hip)
+int frame_map_ensure(fh_ctx* ctx, uint32_t world)
+{
+  // built once per (world, resolution, tile size) and kept, so a presented frame is ONE asynchronous launch
+  fh_ctx::FrameMap& fm = ctx->frame_map;
+  if (!(fm.d_all && fm.world == world && fm.width == ctx->width && fm.height == ctx->height && fm.tile_w == ctx->tile_w && fm.tile_h == ctx->tile_h)) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (fm.d_all) (void)hipFree(fm.d_all);
+    fm = fh_ctx::FrameMap{};
+    std::vector<uint32_t> all;
+    fm.start.assign(world + 1u, 0u);
+    for (uint32_t r = 0; r < world; ++r) { owned_list(ctx->width, ctx->height, ctx->tile_w, ctx->tile_h, r, world, all, nullptr); fm.start[r + 1u] = (uint32_t)all.size(); }
+    FH_HIP(hipMalloc((void**)&fm.d_all, all.empty() ? 16 : all.size() * 4));
+    if (!all.empty()) FH_HIP(hipMemcpy(fm.d_all, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+    fm.world = world; fm.width = ctx->width; fm.height = ctx->height; fm.tile_w = ctx->tile_w; fm.tile_h = ctx->tile_h;
+  }
+  return FH_OK;
+}
+
+uint32_t owned_count(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, uint32_t rank, uint32_t world)
+{
+  std::vector<uint32_t> owned;
+  owned_list(width, height, tw, th, rank, world, owned, nullptr);
+  return (uint32_t)owned.size();
+}
+
+namespace {
+
 __global__ void k_pack(const float* layer, const uint32_t* owned, uint32_t n, uint32_t fpp, float* packed)
 {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n * fpp; i += gridDim.x * blockDim.x) packed[i] = layer[(size_t)owned[i / fpp] * fpp + i % fpp];
@@ -577,6 +608,7 @@ int fh_ctx_create(int device, fh_ctx** out)
 
 int fh_ctx_destroy(fh_ctx* ctx)
 {
+  FH_GROUP(ctx, group_destroy(ctx));
   if (!ctx) return FH_E_INVALID;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
@@ -620,12 +652,14 @@ const char* fh_last_error(fh_ctx* ctx) { return ctx ? ctx->err.c_str() : g_creat
 
 int fh_set_flags(fh_ctx* ctx, uint32_t flags)
 {
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_flags(m_, flags));
   CTX_CHECK(ctx);
   ctx->flags = flags;
   return FH_OK;
 }
 int fh_get_flags(fh_ctx* ctx, uint32_t* flags)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!flags) return fail(ctx, FH_E_INVALID, "fh_get_flags: null argument");
   *flags = ctx->flags;
@@ -634,6 +668,7 @@ int fh_get_flags(fh_ctx* ctx, uint32_t* flags)
 
 int fh_set_path_pool(fh_ctx* ctx, uint32_t target)
 {
+  FH_GROUP_EACH(ctx, kGroupCallFrame, fh_set_path_pool(m_, target));
   CTX_CHECK(ctx);
   if (target == 0) return fail(ctx, FH_E_INVALID, "fh_set_path_pool: zero");
   (void)hipStreamSynchronize(ctx->stream);
@@ -645,6 +680,7 @@ int fh_set_path_pool(fh_ctx* ctx, uint32_t target)
 
 int fh_path_pool_bytes(fh_ctx* ctx, uint64_t* bytes_per_path, uint32_t* pools)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!bytes_per_path || !pools) return fail(ctx, FH_E_INVALID, "fh_path_pool_bytes: null argument");
   *bytes_per_path = pool_bytes_per_path(ctx);
@@ -654,6 +690,7 @@ int fh_path_pool_bytes(fh_ctx* ctx, uint64_t* bytes_per_path, uint32_t* pools)
 
 int fh_kat_face_classes(fh_ctx* ctx, uint8_t* out, uint32_t n)
 {
+  FH_GROUP_REFUSE(ctx, "fh_kat_face_classes");
   CTX_CHECK(ctx);
   if (!out || n != ctx->n_faces) return fail(ctx, FH_E_INVALID, "fh_kat_face_classes: one byte per face of the uploaded scene");
   if (n) FH_HIP(hipMemcpy(out, ctx->d_face_cls, n, hipMemcpyDeviceToHost));
@@ -662,6 +699,7 @@ int fh_kat_face_classes(fh_ctx* ctx, uint8_t* out, uint32_t n)
 
 int fh_alpha_face_counts(fh_ctx* ctx, uint32_t counts[4])
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!counts) return fail(ctx, FH_E_INVALID, "fh_alpha_face_counts: null argument");
   for (int k = 0; k < 4; ++k) counts[k] = ctx->alpha_face_counts[k];
@@ -670,6 +708,7 @@ int fh_alpha_face_counts(fh_ctx* ctx, uint32_t counts[4])
 
 int fh_alpha_cell_counts(fh_ctx* ctx, uint64_t counts[3])
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!counts) return fail(ctx, FH_E_INVALID, "fh_alpha_cell_counts: null argument");
   for (int k = 0; k < 3; ++k) counts[k] = ctx->alpha_cell_counts[k];
@@ -678,6 +717,7 @@ int fh_alpha_cell_counts(fh_ctx* ctx, uint64_t counts[3])
 
 int fh_kat_alpha_records(fh_ctx* ctx, uint32_t* out, uint32_t n_faces)
 {
+  FH_GROUP_REFUSE(ctx, "fh_kat_alpha_records");
   CTX_CHECK(ctx);
   if (!out || n_faces != ctx->n_faces) return fail(ctx, FH_E_INVALID, "fh_kat_alpha_records: 32 words per face of the uploaded scene");
   if (!ctx->d_alpha_rec) { std::memset(out, 0, 128ull * n_faces); return FH_OK; }
@@ -687,6 +727,7 @@ int fh_kat_alpha_records(fh_ctx* ctx, uint32_t* out, uint32_t n_faces)
 
 int fh_path_pool_allocated(fh_ctx* ctx, uint64_t* bytes, uint64_t* paths)
 {
+  FH_GROUP(ctx, group_path_pool_allocated(ctx, bytes, paths));
   CTX_CHECK(ctx);
   if (!bytes || !paths) return fail(ctx, FH_E_INVALID, "fh_path_pool_allocated: null argument");
   *bytes = 0; *paths = 0;
@@ -696,6 +737,7 @@ int fh_path_pool_allocated(fh_ctx* ctx, uint64_t* bytes, uint64_t* paths)
 
 int fh_set_tail_depth(fh_ctx* ctx, uint32_t depth)
 {
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_tail_depth(m_, depth));
   CTX_CHECK(ctx);
   ctx->tail_depth = depth;  // 0 = adaptive; bounce 0 always runs as wavefront kernels (it writes the first-hit AOVs)
   return FH_OK;
@@ -703,6 +745,7 @@ int fh_set_tail_depth(fh_ctx* ctx, uint32_t depth)
 
 int fh_scene_upload(fh_ctx* ctx, const fh_scene_desc* s)
 {
+  FH_GROUP_EACH(ctx, kGroupCallUpload, fh_scene_upload(m_, s));
   CTX_CHECK(ctx);
   if (!s || !s->vertices || !s->normals || !s->texcoords || !s->indices || !s->material_ids || !s->materials || s->n_materials == 0)
     return fail(ctx, FH_E_INVALID, "fh_scene_upload: missing arrays");
@@ -742,6 +785,7 @@ int fh_scene_upload(fh_ctx* ctx, const fh_scene_desc* s)
 
 int fh_set_transforms(fh_ctx* ctx, uint32_t n, const float* o2w, const float* w2o)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_transforms(m_, n, o2w, w2o));
   CTX_CHECK(ctx);
   if (!ctx->scene_loaded || !o2w || !w2o || n == 0) return fail(ctx, FH_E_INVALID, "fh_set_transforms: no scene / null arrays");
   // a frame of an animation that only moves the camera (rtcamp8's scene) leaves every instance where it was: keep the world-space
@@ -761,6 +805,7 @@ int fh_set_transforms(fh_ctx* ctx, uint32_t n, const float* o2w, const float* w2
 
 int fh_bvh_build(fh_ctx* ctx)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_bvh_build(m_));
   CTX_CHECK(ctx);
   if (!ctx->scene_loaded) return fail(ctx, FH_E_INVALID, "fh_bvh_build: no scene");
   if (ctx->bvh_valid) return FH_OK;  // geometry unchanged since the last build
@@ -769,6 +814,7 @@ int fh_bvh_build(fh_ctx* ctx)
 
 int fh_scene_n_lights(fh_ctx* ctx, uint32_t* out)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!out) return FH_E_INVALID;
   *out = ctx->n_lights;
@@ -777,6 +823,7 @@ int fh_scene_n_lights(fh_ctx* ctx, uint32_t* out)
 
 int fh_set_directional_light(fh_ctx* ctx, const float* le, const float* dir, float angle)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_directional_light(m_, le, dir, angle));
   CTX_CHECK(ctx);
   if (!le || !dir) return FH_E_INVALID;
   const f3 d = normalize(mk3(dir[0], dir[1], dir[2]));  // renderer.h:560
@@ -789,18 +836,21 @@ int fh_set_directional_light(fh_ctx* ctx, const float* le, const float* dir, flo
 }
 int fh_clear_directional_light(fh_ctx* ctx)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_clear_directional_light(m_));
   CTX_CHECK(ctx);
   ctx->has_dir = false;
   return FH_OK;
 }
 int fh_set_sky_intensity(fh_ctx* ctx, float v)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_sky_intensity(m_, v));
   CTX_CHECK(ctx);
   ctx->sky_intensity = v;
   return FH_OK;
 }
 int fh_load_arhosek_sky(fh_ctx* ctx, float turbidity, float albedo)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_load_arhosek_sky(m_, turbidity, albedo));
   CTX_CHECK(ctx);
   if (!(turbidity >= 1.0f && turbidity <= 10.0f)) return fail(ctx, FH_E_INVALID, "turbidity must be in [1,10]");
   const float elevation = (float)(0.5f * 3.14159265358979323846 - fhe_acos(clampf(ctx->sun_dir[1], -1.0f, 1.0f)));  // renderer.h:592-601
@@ -812,12 +862,14 @@ int fh_load_arhosek_sky(fh_ctx* ctx, float turbidity, float albedo)
 }
 int fh_clear_arhosek_sky(fh_ctx* ctx)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_clear_arhosek_sky(m_));
   CTX_CHECK(ctx);
   ctx->has_hosek = false;
   return FH_OK;
 }
 int fh_load_ibl(fh_ctx* ctx, const float* rgba, uint32_t w, uint32_t h)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_load_ibl(m_, rgba, w, h));
   CTX_CHECK(ctx);
   if (!rgba || w == 0 || h == 0) return fail(ctx, FH_E_INVALID, "fh_load_ibl: empty image");
   (void)hipStreamSynchronize(ctx->stream);
@@ -830,6 +882,7 @@ int fh_load_ibl(fh_ctx* ctx, const float* rgba, uint32_t w, uint32_t h)
 }
 int fh_clear_ibl(fh_ctx* ctx)
 {
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_clear_ibl(m_));
   CTX_CHECK(ctx);
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->d_ibl) { (void)hipFree(ctx->d_ibl); ctx->d_ibl = nullptr; }
@@ -854,6 +907,7 @@ static int adaptive_reset(fh_ctx* ctx)
 
 int fh_init_render_states(fh_ctx* ctx)
 {
+  FH_GROUP(ctx, group_init_render_states(ctx));
   CTX_CHECK(ctx);
   if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "resolution not set");
   FH_HIP(hipMemsetAsync(ctx->d_sample_count, 0, 4ull * ctx->width * ctx->height, ctx->stream));
@@ -864,6 +918,7 @@ int fh_init_render_states(fh_ctx* ctx)
 
 int fh_set_adaptive_sampling(fh_ctx* ctx, const fh_adaptive_params* p)
 {
+  FH_GROUP_EACH(ctx, kGroupCallFrame, fh_set_adaptive_sampling(m_, p));
   CTX_CHECK(ctx);
   if (!p) { ctx->adaptive = false; return FH_OK; }
   if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold)) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_sampling: threshold must be finite and >= 0");
@@ -880,6 +935,7 @@ int fh_set_adaptive_sampling(fh_ctx* ctx, const fh_adaptive_params* p)
 
 int fh_get_adaptive_sampling(fh_ctx* ctx, int* enabled, fh_adaptive_params* p)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (enabled) *enabled = ctx->adaptive ? 1 : 0;
   if (p) *p = ctx->adapt;
@@ -888,6 +944,7 @@ int fh_get_adaptive_sampling(fh_ctx* ctx, int* enabled, fh_adaptive_params* p)
 
 int fh_get_sample_counts(fh_ctx* ctx, uint32_t* counts)
 {
+  FH_GROUP(ctx, group_get_sample_counts(ctx, counts));
   CTX_CHECK(ctx);
   if (!counts) return fail(ctx, FH_E_INVALID, "fh_get_sample_counts: null argument");
   if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_get_sample_counts: resolution not set");
@@ -897,6 +954,7 @@ int fh_get_sample_counts(fh_ctx* ctx, uint32_t* counts)
 
 int fh_get_luminance_moments(fh_ctx* ctx, float* m)
 {
+  FH_GROUP(ctx, group_get_luminance_moments(ctx, m));
   CTX_CHECK(ctx);
   if (!m) return fail(ctx, FH_E_INVALID, "fh_get_luminance_moments: null argument");
   if (!ctx->adaptive || !ctx->d_moments) return fail(ctx, FH_E_INVALID, "fh_get_luminance_moments: adaptive sampling is off");
@@ -906,6 +964,7 @@ int fh_get_luminance_moments(fh_ctx* ctx, float* m)
 
 int fh_active_pixel_count(fh_ctx* ctx, uint32_t* out)
 {
+  FH_GROUP(ctx, group_active_pixel_count(ctx, out));
   CTX_CHECK(ctx);
   if (!out) return fail(ctx, FH_E_INVALID, "fh_active_pixel_count: null argument");
   if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_active_pixel_count: resolution not set");
@@ -917,6 +976,7 @@ int fh_active_pixel_count(fh_ctx* ctx, uint32_t* out)
 // read and write them)
 int fh_kat_set_sample_counts(fh_ctx* ctx, const uint32_t* counts, uint32_t n_pixels)
 {
+  FH_GROUP_REFUSE(ctx, "fh_kat_set_sample_counts");
   CTX_CHECK(ctx);
   if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_kat_set_sample_counts: resolution not set");
   if (!counts || (uint64_t)n_pixels != (uint64_t)ctx->width * ctx->height) return fail(ctx, FH_E_INVALID, "fh_kat_set_sample_counts: one count per pixel of the frame");
@@ -929,6 +989,7 @@ int fh_kat_set_sample_counts(fh_ctx* ctx, const uint32_t* counts, uint32_t n_pix
 
 int fh_kat_set_issued(fh_ctx* ctx, const uint32_t* issued, uint32_t n_pixels)
 {
+  FH_GROUP_REFUSE(ctx, "fh_kat_set_issued");
   CTX_CHECK(ctx);
   if (!ctx->d_sample_issued) return fail(ctx, FH_E_INVALID, "fh_kat_set_issued: resolution not set");
   if (!issued || (uint64_t)n_pixels != (uint64_t)ctx->width * ctx->height) return fail(ctx, FH_E_INVALID, "fh_kat_set_issued: one count per pixel of the frame");
@@ -940,6 +1001,7 @@ int fh_kat_set_issued(fh_ctx* ctx, const uint32_t* issued, uint32_t n_pixels)
 
 int fh_kat_sample_counts(fh_ctx* ctx, uint32_t* sample_count, uint32_t* issued, uint32_t n_pixels)
 {
+  FH_GROUP_REFUSE(ctx, "fh_kat_sample_counts");
   CTX_CHECK(ctx);
   if (!ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_kat_sample_counts: resolution not set");
   if ((uint64_t)n_pixels != (uint64_t)ctx->width * ctx->height) return fail(ctx, FH_E_INVALID, "fh_kat_sample_counts: one count per pixel of the frame");
@@ -952,6 +1014,7 @@ int fh_kat_sample_counts(fh_ctx* ctx, uint32_t* sample_count, uint32_t* issued, 
 
 int fh_set_resolution(fh_ctx* ctx, uint32_t w, uint32_t h)
 {
+  FH_GROUP(ctx, group_set_resolution(ctx, w, h));
   CTX_CHECK(ctx);
   if (w == 0 || h == 0) return fail(ctx, FH_E_INVALID, "zero resolution");
   if (w > 65535u || h > 65535u) return fail(ctx, FH_E_UNSUPPORTED, "frames wider or higher than 65535 pixels are not supported");  // (before anything is changed: the context keeps its resolution)
@@ -969,6 +1032,7 @@ int fh_set_resolution(fh_ctx* ctx, uint32_t w, uint32_t h)
 
 int fh_set_tile_shard(fh_ctx* ctx, uint32_t rank, uint32_t world, uint32_t tw, uint32_t th)
 {
+  FH_GROUP(ctx, group_set_tile_shard(ctx, rank, world, tw, th));
   CTX_CHECK(ctx);
   if (world == 0 || rank >= world || tw == 0 || th == 0) return fail(ctx, FH_E_INVALID, "bad shard");
   (void)hipStreamSynchronize(ctx->stream);
@@ -978,6 +1042,7 @@ int fh_set_tile_shard(fh_ctx* ctx, uint32_t rank, uint32_t world, uint32_t tw, u
 
 int fh_owned_pixel_count(fh_ctx* ctx, uint32_t* out)
 {
+  FH_GROUP(ctx, group_owned_pixel_count(ctx, out));
   CTX_CHECK(ctx);
   if (!out) return FH_E_INVALID;
   *out = ctx->n_owned;
@@ -986,6 +1051,7 @@ int fh_owned_pixel_count(fh_ctx* ctx, uint32_t* out)
 
 int fh_pack_owned(fh_ctx* ctx, const float* layer, uint32_t fpp, float* packed)
 {
+  FH_GROUP_REFUSE(ctx, "fh_pack_owned");
   CTX_CHECK(ctx);
   if (!layer || !packed || fpp == 0) return FH_E_INVALID;
   if (ctx->n_owned) hipLaunchKernelGGL(k_pack, dim3((ctx->n_owned * fpp + 255) / 256), dim3(256), 0, ctx->stream, layer, ctx->d_owned, ctx->n_owned, fpp, packed);
@@ -995,6 +1061,7 @@ int fh_pack_owned(fh_ctx* ctx, const float* layer, uint32_t fpp, float* packed)
 
 int fh_unpack_shard(fh_ctx* ctx, uint32_t rank, uint32_t world, const float* packed, uint32_t fpp, float* layer)
 {
+  FH_GROUP_REFUSE(ctx, "fh_unpack_shard");
   CTX_CHECK(ctx);
   if (!layer || !packed || fpp == 0 || world == 0 || rank >= world) return FH_E_INVALID;
   if (ctx->width > 65535u || ctx->height > 65535u) return fail(ctx, FH_E_UNSUPPORTED, "frames wider or higher than 65535 pixels are not supported");
@@ -1024,6 +1091,7 @@ int fh_unpack_shard(fh_ctx* ctx, uint32_t rank, uint32_t world, const float* pac
 
 int fh_unpack_shards(fh_ctx* ctx, uint32_t world, const float* const* packed, uint32_t fpp, float* layer)
 {
+  FH_GROUP_REFUSE(ctx, "fh_unpack_shards");
   CTX_CHECK(ctx);
   if (!layer || !packed || fpp == 0 || world == 0) return FH_E_INVALID;
   for (uint32_t r = 0; r < world; ++r)
@@ -1033,19 +1101,9 @@ int fh_unpack_shards(fh_ctx* ctx, uint32_t world, const float* const* packed, ui
     return FH_OK;
   }
   if (ctx->width > 65535u || ctx->height > 65535u) return fail(ctx, FH_E_UNSUPPORTED, "frames wider or higher than 65535 pixels are not supported");
-  // the ownership lists of all `world` ranks, one after the other: built once per (world, resolution, tile size) and kept, so a presented frame is ONE asynchronous launch
+  const int rc_map = frame_map_ensure(ctx, world);
+  if (rc_map) return rc_map;
   fh_ctx::FrameMap& fm = ctx->frame_map;
-  if (!(fm.d_all && fm.world == world && fm.width == ctx->width && fm.height == ctx->height && fm.tile_w == ctx->tile_w && fm.tile_h == ctx->tile_h)) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (fm.d_all) (void)hipFree(fm.d_all);
-    fm = fh_ctx::FrameMap{};
-    std::vector<uint32_t> all;
-    fm.start.assign(world + 1u, 0u);
-    for (uint32_t r = 0; r < world; ++r) { owned_list(ctx->width, ctx->height, ctx->tile_w, ctx->tile_h, r, world, all, nullptr); fm.start[r + 1u] = (uint32_t)all.size(); }
-    FH_HIP(hipMalloc((void**)&fm.d_all, all.empty() ? 16 : all.size() * 4));
-    if (!all.empty()) FH_HIP(hipMemcpy(fm.d_all, all.data(), all.size() * 4, hipMemcpyHostToDevice));
-    fm.world = world; fm.width = ctx->width; fm.height = ctx->height; fm.tile_w = ctx->tile_w; fm.tile_h = ctx->tile_h;
-  }
   ShardSources src{};
   src.world = world;
   for (uint32_t r = 0; r < world; ++r) { src.packed[r] = packed[r]; src.start[r] = fm.start[r]; }
@@ -1058,6 +1116,7 @@ int fh_unpack_shards(fh_ctx* ctx, uint32_t world, const float* const* packed, ui
 
 int fh_render(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed)
 {
+  FH_GROUP(ctx, group_render(ctx, cam, bg, layers, n_samples, max_depth, seed));
   CTX_CHECK(ctx);
   if (!cam || !bg || !layers || !layers->beauty || !layers->position || !layers->depth || !layers->normal || !layers->texcoord || !layers->albedo)
     return fail(ctx, FH_E_INVALID, "fh_render: null argument");
@@ -1066,6 +1125,7 @@ int fh_render(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_rende
 
 int fh_sync(fh_ctx* ctx)
 {
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_sync(m_));
   CTX_CHECK(ctx);
   if (ctx->render_pending) (void)hipEventRecord(ctx->ev_render_end, ctx->stream);
   FH_HIP(hipStreamSynchronize(ctx->stream));
@@ -1125,6 +1185,7 @@ int fh_sync(fh_ctx* ctx)
 
 int fh_get_stats(fh_ctx* ctx, fh_stats* out)
 {
+  FH_GROUP(ctx, group_get_stats(ctx, out));
   CTX_CHECK(ctx);
   if (!out) return FH_E_INVALID;
   *out = ctx->stats;
@@ -1132,6 +1193,7 @@ int fh_get_stats(fh_ctx* ctx, fh_stats* out)
 }
 int fh_kernel_info(fh_ctx* ctx, int which, uint32_t out[6])
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!out || which < 0 || which > 1 + (int)kMaxClasses) return fail(ctx, FH_E_INVALID, "fh_kernel_info: which must be 0 (closest hit), 1 (secondary rays) or 2 + a shading class of the scene");
   return kernel_info(ctx, which, out);
@@ -1139,6 +1201,7 @@ int fh_kernel_info(fh_ctx* ctx, int which, uint32_t out[6])
 // test hook (fredholm_hip_test.h): where the scene's first-hit rays start, and what the probing passes have counted so far
 int fh_kat_ray_start(fh_ctx* ctx, double out[5])
 {
+  FH_GROUP_REFUSE(ctx, "fh_kat_ray_start");
   CTX_CHECK(ctx);
   if (!out) return fail(ctx, FH_E_INVALID, "fh_kat_ray_start: null argument");
   out[0] = (double)ctx->bu_choice; out[1] = ctx->bu_items[0]; out[2] = ctx->bu_items[1]; out[3] = ctx->bu_cost[0]; out[4] = ctx->bu_cost[1];
@@ -1146,6 +1209,7 @@ int fh_kat_ray_start(fh_ctx* ctx, double out[5])
 }
 int fh_reset_stats(fh_ctx* ctx)
 {
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_reset_stats(m_));
   CTX_CHECK(ctx);
   const double build_ms = ctx->stats.bvh_build_ms;
   const uint64_t nodes = ctx->stats.bvh_nodes, nb = ctx->stats.bvh_node_bytes, tb = ctx->stats.bvh_tri_bytes, depth = ctx->stats.bvh_depth;
@@ -1157,6 +1221,7 @@ int fh_reset_stats(fh_ctx* ctx)
 
 int fh_post_process(fh_ctx* ctx, const float* in, float* hi, float* tmp, int w, int h, const fh_post_params* pp, float* out)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!in || !hi || !tmp || !out || !pp || w <= 0 || h <= 0) return fail(ctx, FH_E_INVALID, "fh_post_process: bad argument");
   return post_process_submit(ctx, in, hi, tmp, w, h, pp, out);
@@ -1164,6 +1229,7 @@ int fh_post_process(fh_ctx* ctx, const float* in, float* hi, float* tmp, int w, 
 
 int fh_denoise(fh_ctx* ctx, uint32_t width, uint32_t height, const float* beauty, const float* normal, const float* albedo, float* denoised, int upscale2x)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!beauty || !normal || !albedo || !denoised || width == 0 || height == 0 || width > 32768 || height > 32768) return fail(ctx, FH_E_INVALID, "fh_denoise: bad argument");
   return denoise_submit(ctx, (int)width, (int)height, beauty, normal, albedo, denoised, upscale2x ? 1 : 0);
@@ -1173,6 +1239,7 @@ int fh_denoise(fh_ctx* ctx, uint32_t width, uint32_t height, const float* beauty
 // unregistered in the destructor).  Needs a current OpenGL context on the calling thread, like the reference.
 int fh_gl_register_buffer(fh_ctx* ctx, unsigned int gl_buffer, void** resource, void** device_ptr, uint64_t* bytes)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!resource || !device_ptr) return fail(ctx, FH_E_INVALID, "fh_gl_register_buffer: null argument");
   *resource = nullptr; *device_ptr = nullptr;
@@ -1192,6 +1259,7 @@ int fh_gl_register_buffer(fh_ctx* ctx, unsigned int gl_buffer, void** resource, 
 }
 int fh_gl_unregister_buffer(fh_ctx* ctx, void* resource)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!resource) return FH_OK;
   hipGraphicsResource_t res = (hipGraphicsResource_t)resource;
@@ -1203,6 +1271,7 @@ int fh_gl_unregister_buffer(fh_ctx* ctx, void* resource)
 
 int fh_malloc(fh_ctx* ctx, uint64_t bytes, void** out)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   if (!out) return FH_E_INVALID;
   FH_HIP(hipMalloc(out, bytes ? bytes : 16));
@@ -1210,18 +1279,21 @@ int fh_malloc(fh_ctx* ctx, uint64_t bytes, void** out)
 }
 int fh_free(fh_ctx* ctx, void* p)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   FH_HIP(hipFree(p));
   return FH_OK;
 }
 int fh_memset(fh_ctx* ctx, void* p, int v, uint64_t bytes)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   FH_HIP(hipMemsetAsync(p, v, bytes, ctx->stream));
   return FH_OK;
 }
 int fh_copy_to_device(fh_ctx* ctx, void* dst, const void* src, uint64_t bytes)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   FH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
@@ -1245,17 +1317,23 @@ int fh_image_load_rgba8(const char* path, int flip_vertically, uint32_t* width, 
 void fh_image_free(uint8_t* rgba8) { std::free(rgba8); }
 int fh_copy_on_device(fh_ctx* ctx, void* dst, const void* src, uint64_t bytes)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   FH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   return FH_OK;
 }
 int fh_copy_to_host(fh_ctx* ctx, void* dst, const void* src, uint64_t bytes)
 {
+  FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   FH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
   return FH_OK;
 }
-void* fh_stream(fh_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+void* fh_stream(fh_ctx* ctx)
+{
+  FH_GROUP_LEAD(ctx);
+  return ctx ? (void*)ctx->stream : nullptr;
+}
 
 }  // extern "C"

@@ -4,13 +4,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/fredholm_hip.h"
 #include "fh_device.h"
 
+struct fh_group;  // group.hip
+
 struct fh_ctx {
+  // a handle made by fh_ctx_create_group(n > 1) holds nothing but `group` and the lead's device; its members are plain contexts that name it as their `owner`
+  fh_group* group = nullptr;
+  fh_ctx* owner = nullptr;
+  uint32_t member_index = 0;
   int device = 0;
   hipStream_t stream = nullptr;   // main stream: everything the caller can observe is ordered on it
   hipStream_t aux_stream[2] = {nullptr, nullptr};  // passes j % n_slots != 0 of fh_render run here, overlapping the latency-bound ends of the passes before
@@ -146,6 +153,7 @@ struct fh_ctx {
   // samples to fill them; unless the caller chose the size (fh_set_path_pool), fh_render keeps all pools together within half of the device memory that is free when the first one is made
   uint32_t pool_target_default = 1u << 25, pool_target = 1u << 25;  // (pool_target: the default as capped by the free device memory whenever a pool is (re)allocated, or the caller's size)
   bool pool_target_by_caller = false;
+  uint32_t pool_share = 1;          // contexts of one group on this device: each takes its share of the default cap (group.hip)
   uint32_t tail_depth = 0;          // bounces run as wavefront kernels before k_tail finishes the survivors; 0 = adaptive
   uint32_t auto_wave_depth = 2;     // adaptive choice of the pass submitted last (kept for the debug print)
   // the adaptive choice is made per pass from the SHARE of a pass's paths still alive at each depth, taken from the newest snapshot of an earlier pass's counters: a share is a
@@ -235,6 +243,32 @@ int fail(fh_ctx* ctx, int code, const std::string& msg);
     hipError_t e_ = (call);                                                                                            \
     if (e_ != hipSuccess) return fh::fail(ctx, FH_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
   } while (0)
+
+// group dispatch at the top of the entry points (group.hip).  A plain context pays the one branch.
+#define FH_GROUP(ctx, call) \
+  if ((ctx) && (ctx)->group) return fh::call
+#define FH_GROUP_EACH(ctx, kind, call) \
+  if ((ctx) && (ctx)->group) return fh::group_each(ctx, kind, [&](fh_ctx* m_, uint32_t i_) { (void)i_; return call; })
+#define FH_GROUP_LEAD(ctx) \
+  if ((ctx) && (ctx)->group) ctx = fh::group_lead(ctx)
+#define FH_GROUP_REFUSE(ctx, name) \
+  if ((ctx) && (ctx)->group) return fh::fail(ctx, FH_E_UNSUPPORTED, name ": not available on a group (a plain context does hand-rolled gathers and known-answer runs)")
+enum { kGroupCallPlain = 0, kGroupCallScene = 1, kGroupCallFrame = 2, kGroupCallUpload = 3 };  // what a broadcast that fails half way leaves in doubt: nothing, the scene, the frame state; fh_scene_upload itself
+fh_ctx* group_lead(fh_ctx* g);
+int group_each(fh_ctx* g, int kind, const std::function<int(fh_ctx*, uint32_t)>& call);
+int group_destroy(fh_ctx* g);
+int group_set_resolution(fh_ctx* g, uint32_t w, uint32_t h);
+int group_set_tile_shard(fh_ctx* g, uint32_t rank, uint32_t world, uint32_t tw, uint32_t th);
+int group_init_render_states(fh_ctx* g);
+int group_render(fh_ctx* g, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);
+int group_get_sample_counts(fh_ctx* g, uint32_t* counts);
+int group_get_luminance_moments(fh_ctx* g, float* moments);
+int group_active_pixel_count(fh_ctx* g, uint32_t* out);
+int group_owned_pixel_count(fh_ctx* g, uint32_t* out);
+int group_get_stats(fh_ctx* g, fh_stats* out);
+int group_path_pool_allocated(fh_ctx* g, uint64_t* bytes, uint64_t* paths);
+int frame_map_ensure(fh_ctx* ctx, uint32_t world);  // capi.hip: ctx->frame_map for `world` ranks at the context's resolution and tile size
+uint32_t owned_count(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, uint32_t rank, uint32_t world);  // capi.hip
 
 SceneDev scene_dev(const fh_ctx* ctx);
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip

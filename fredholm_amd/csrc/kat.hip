@@ -285,12 +285,14 @@ using namespace fh;
 
 #define KCTX(ctx)                  \
   if (!(ctx)) return FH_E_INVALID; \
+  FH_GROUP_REFUSE(ctx, "fh_kat_*"); \
   if (hipSetDevice((ctx)->device) != hipSuccess) return fh::fail(ctx, FH_E_HIP, "hipSetDevice failed")
 
 extern "C" {
 
 int fh_trace_rays(fh_ctx* ctx, uint32_t n, const float* rays7, int any_hit, float* tuv, uint32_t* prim)
 {
+  FH_GROUP_LEAD(ctx);
   KCTX(ctx);
   if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_trace_rays: scene/BVH missing");
   if (n == 0) return FH_OK;
@@ -477,6 +479,7 @@ int fh_kat_math(fh_ctx* ctx, int kind, uint32_t n, const float* in, float* out)
 }
 int fh_measure_bandwidth(fh_ctx* ctx, uint64_t bytes, uint32_t iters, double* read_gbs, double* copy_gbs)
 {
+  FH_GROUP_LEAD(ctx);
   KCTX(ctx);
   if (!read_gbs || !copy_gbs || bytes < (1ull << 20) || iters == 0) return fail(ctx, FH_E_INVALID, "fh_measure_bandwidth: bad argument");
   const size_t n = (size_t)(bytes / 16);

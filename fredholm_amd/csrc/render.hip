@@ -2130,7 +2130,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
       size_t free_b = 0, total_b = 0;
       ctx->pool_target = ctx->pool_target_default;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const unsigned long long cap = ((unsigned long long)free_b + held) / 4ull / ((unsigned long long)ctx->n_slots * pool_bytes_per_path(ctx));
+        const unsigned long long cap = ((unsigned long long)free_b + held) / (4ull * ctx->pool_share) / ((unsigned long long)ctx->n_slots * pool_bytes_per_path(ctx));  // (pool_share: the members of a group on this device)
         if (cap < ctx->pool_target) ctx->pool_target = cap > ctx->n_owned ? (uint32_t)cap : ctx->n_owned;
       }
       // (pools that exist already keep their size unless they have to be re-made: pool_ensure only grows)

@@ -12,6 +12,8 @@ FLAG_TIME_KERNELS = 1
 FLAG_COUNT_TRAVERSAL = 2
 FLAG_SERIAL_PASSES = 8
 FLAG_ROOT_START = 16  # (measurements) every ray starts its traversal at the root
+# gather mask of a group (fh_group_set_gather_layers): bit k = layer k of RenderLayer.NAMES
+LAYER_BEAUTY, LAYER_POSITION, LAYER_DEPTH, LAYER_NORMAL, LAYER_TEXCOORD, LAYER_ALBEDO, LAYER_ALL = 1, 2, 4, 8, 16, 32, 63
 FLAG_REFERENCE_FIRSTHIT = 4  # one fh_render(n_samples = k) = ONE reference launch of k samples, firsthit quirk included (pt.cu:432-433)
 
 MATERIAL_DTYPE = np.dtype([
@@ -109,6 +111,7 @@ EXPORTS = [
     "fh_kat_sobol", "fh_kat_elementary", "fh_kat_warp", "fh_kat_bsdf", "fh_kat_bsdf_lobes", "fh_kat_bsdf_ior", "fh_kat_sky", "fh_kat_hosek_state", "fh_kat_camera",
     "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
     "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued",
+    "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
 
@@ -125,7 +128,21 @@ SIGNATURES = {
     "fh_get_luminance_moments": [C.c_void_p, C.c_void_p],
     "fh_active_pixel_count": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_kat_set_issued": [C.c_void_p, C.c_void_p, C.c_uint32],
+    "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
+    "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],
+    "fh_ctx_member": [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)],
+    "fh_group_set_gather_layers": [C.c_void_p, C.c_uint32],
+    "fh_group_gather_times": [C.c_void_p, C.POINTER(C.c_double)],
+    "fh_group_shard_layout": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)],
 }
+
+
+def group_shard_layout(width, height, n, mask=LAYER_ALL, tile_w=32, tile_h=32):
+    """fh_group_shard_layout: the n + 1 byte offsets of the members' packed shards in the lead's staging area (host only, no GPU)"""
+    out = (C.c_uint64 * (int(n) + 1))()
+    rc = lib().fh_group_shard_layout(int(width), int(height), int(tile_w), int(tile_h), int(n), int(mask), out)
+    check(None, rc, "fh_group_shard_layout")
+    return [int(v) for v in out]
 
 _lib = None
 

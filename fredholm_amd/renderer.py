@@ -143,14 +143,22 @@ class Renderer:
     create_pipeline / create_sbt, renderer.h:124-352) are accepted and ignored: there is no OptiX
     pipeline, the HIP kernels are compiled into the library."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, devices=None):
+        """device: one GPU (a plain context).  devices=[0, 1, 2, 3]: a group, one member per entry, that renders every frame split by pixel tile
+        across them and is used like a plain renderer; buffers belong to devices[0] (include/fredholm_hip.h: fh_ctx_create_group)."""
         self._ctx = C.c_void_p()
         L = N.load_library()
-        rc = L.fh_ctx_create(int(device), C.byref(self._ctx))
+        if devices is None:
+            what = "fh_ctx_create"
+            rc = L.fh_ctx_create(int(device), C.byref(self._ctx))
+        else:
+            what = "fh_ctx_create_group"
+            devs = [int(d) for d in devices]
+            rc = L.fh_ctx_create_group((C.c_int * max(len(devs), 1))(*devs), len(devs), C.byref(self._ctx))
         if rc != N.FH_OK:
             msg = L.fh_last_error(None)
             self._ctx = None
-            raise N.FredholmError(f"fh_ctx_create failed ({rc}): {msg.decode() if msg else ''}")
+            raise N.FredholmError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
         self.m_width = self.m_height = 0
         self.seed = 1  # params.seed = 1 (renderer.h:664)
         self._keep = None
@@ -182,6 +190,31 @@ class Renderer:
 
     def _ck(self, rc, what):
         N.check(self._ctx, rc, what)
+
+    # -- groups (fh_ctx_create_group)
+    @property
+    def group_size(self):
+        """members of the group; 1 for a plain renderer"""
+        n = C.c_uint32(0)
+        self._ck(N.lib().fh_ctx_group_size(self._ctx, C.byref(n)), "fh_ctx_group_size")
+        return int(n.value)
+
+    def set_gather_layers(self, mask):
+        """layers (native.LAYER_* bits) a group brings back from its other members after every render; the rest receive only the lead's tiles"""
+        self._ck(N.lib().fh_group_set_gather_layers(self._ctx, C.c_uint32(int(mask))), "fh_group_set_gather_layers")
+
+    def member_stats(self, i):
+        """fh_get_stats of member i alone (stats() of a group aggregates them)"""
+        m, s = C.c_void_p(), N.StatsC()
+        self._ck(N.lib().fh_ctx_member(self._ctx, C.c_uint32(int(i)), C.byref(m)), "fh_ctx_member")
+        N.check(m, N.lib().fh_get_stats(m, C.byref(s)), "fh_get_stats")
+        return s.as_dict()
+
+    def gather_times(self):
+        """(k_pack_layers, copies, k_unpack_group) ms of the last gather, HIP events, with FLAG_TIME_KERNELS set; synchronising"""
+        ms = (C.c_double * 3)()
+        self._ck(N.lib().fh_group_gather_times(self._ctx, ms), "fh_group_gather_times")
+        return tuple(float(v) for v in ms)
 
     def set_flags(self, flags):
         self._ck(N.lib().fh_set_flags(self._ctx, C.c_uint32(flags)), "fh_set_flags")

@@ -104,6 +104,15 @@ class Renderer
     cwl::check(m_ctx, fh_set_flags(m_ctx, on ? (flags | FH_FLAG_REFERENCE_FIRSTHIT) : (flags & ~FH_FLAG_REFERENCE_FIRSTHIT)), "fh_set_flags");
   }
 
+  // not in the reference: a context over several GPUs (FH_DEVICES, include/fredholm_hip.h: fh_ctx_create_group).  group_size() is 1 for a plain context;
+  // set_gather_layers(mask of FH_LAYER_*) names the layers a group brings back from its other members after every render (default: all six)
+  uint32_t group_size()
+  {
+    uint32_t n = 1;
+    cwl::check(m_ctx, fh_ctx_group_size(m_ctx, &n), "fh_ctx_group_size");
+    return n;
+  }
+  void set_gather_layers(uint32_t mask) { cwl::check(m_ctx, fh_group_set_gather_layers(m_ctx, mask), "fh_group_set_gather_layers"); }
   // not in the reference: adaptive sampling (include/fredholm_hip.h: fh_set_adaptive_sampling).  A pixel stops at the first count n >= min_samples with
   // n % step == 0 where its relative error estimate is within `threshold`; render(n) then adds at most n samples per pixel.  Set it right after
   // init_render_states / set_resolution, before the first render of the frame.

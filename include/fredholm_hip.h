@@ -143,6 +143,44 @@ typedef struct fh_stats {
 /* -- context: replaces optwl::Context + Renderer ctor/dtor (optwl.h:41-81, renderer.h:32-122) */
 int fh_ctx_create(int device, fh_ctx** out);
 int fh_ctx_destroy(fh_ctx* ctx);
+
+/* -- one frame on several GPUs from a single context (an extension beyond the reference; DESIGN.md 6, INTEGRATION.md "multi-GPU").
+ * n = 1 returns a plain context, exactly what fh_ctx_create(devices[0]) returns.
+ * 2 <= n <= 16: a GROUP: one member context per entry of devices[] (an index may repeat: several members on one GPU).  Member i renders the tiles t with t % n == i.
+ * Device pointers the caller passes (layers, fh_malloc results, post / denoise images) belong to devices[0], the LEAD.  The handle is used like any context:
+ * state-setting calls reach every member, fh_render fans out and gathers on the device, memory / post / denoise / query calls go to the lead, and
+ * fh_pack_owned, fh_unpack_shard, fh_unpack_shards and the known-answer hooks of fredholm_hip_test.h return FH_E_UNSUPPORTED (INTEGRATION.md has the table).
+ * fh_set_tile_shard(group, 0, 1, tw, th) sets the tile size; any other rank / world is FH_E_INVALID, because a group is the whole frame.
+ * When a call fails on member i, its code is returned and fh_last_error(group) gives its message prefixed with "member i: "; where the members could then disagree
+ * (a scene or frame-state call that did not reach all of them) fh_render returns FH_E_INVALID until fh_scene_upload / fh_set_resolution succeeded again.
+ * n = 0, n > 16, a null pointer (all refused before any HIP call) and a device index out of range are FH_E_INVALID; nothing is left behind.
+ *
+ * fh_render on a group: the lead renders its tiles straight into the caller's six buffers.  Every other member accumulates in six full-size layers of its own
+ * (zero-filled by fh_set_resolution and fh_init_render_states), packs the owned pixels of the layers in the gather mask after its passes, and one asynchronous copy
+ * per member and one un-permuting launch on the lead's stream (the one fh_stream returns) put them into the caller's buffers: work queued on that stream afterwards
+ * sees the whole frame, and after fh_sync(group) so does the host.  What a caller may observe:
+ *  - layers outside the gather mask receive only the lead's tiles;
+ *  - swapping the layer buffers in the middle of an accumulation gives the lead's tiles accumulated in the new buffers and the other tiles copied in;
+ *  - at the first sample after fh_init_render_states a pixel of a non-lead member starts from a zeroed mean, where a plain context starts from what the caller's
+ *    buffer holds.  The update is coef * (fn * old + x) with fn = 0 at count 0 (k_accumulate and k_sky_pixels alike), so the two agree unless the caller's buffer held
+ *    Inf or NaN there (0 * old is NaN), or a negative old value met x = -0.0 (-0.0 where a zeroed buffer gives +0.0). */
+int fh_ctx_create_group(const int* devices, uint32_t n, fh_ctx** out);
+int fh_ctx_group_size(fh_ctx* ctx, uint32_t* n);             /* 1 for a plain context */
+int fh_ctx_member(fh_ctx* ctx, uint32_t i, fh_ctx** member); /* borrowed, for stats and diagnostics only; member 0 of a plain context is the context */
+#define FH_LAYER_BEAUTY 1u
+#define FH_LAYER_POSITION 2u
+#define FH_LAYER_DEPTH 4u
+#define FH_LAYER_NORMAL 8u
+#define FH_LAYER_TEXCOORD 16u
+#define FH_LAYER_ALBEDO 32u
+#define FH_LAYER_ALL 63u
+int fh_group_set_gather_layers(fh_ctx* ctx, uint32_t mask); /* default FH_LAYER_ALL; a plain context accepts and ignores it */
+/* synchronising: HIP-event times (ms) of the last gather of a group whose flags had FH_FLAG_TIME_KERNELS: [0] k_pack_layers and [1] the copies, each summed over the
+ * members, [2] k_unpack_group.  Zeros for a plain context. */
+int fh_group_gather_times(fh_ctx* ctx, double ms[3]);
+/* host only, no context: where each member's packed shard begins in the lead's staging area for a frame, a tile size, n members and a gather mask: n + 1 byte offsets
+ * (a shard is layer after layer in ownership-list order, 16 or 4 bytes per pixel, each layer padded to 16 bytes; the lead packs nothing, so offsets[0] = offsets[1] = 0) */
+int fh_group_shard_layout(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t n, uint32_t mask, uint64_t* offsets);
 const char* fh_last_error(fh_ctx* ctx); /* ctx may be NULL for creation errors */
 int fh_set_flags(fh_ctx* ctx, uint32_t flags);
 int fh_get_flags(fh_ctx* ctx, uint32_t* flags); /* (a caller that wants to change one flag reads, edits and sets) */
