@@ -6,6 +6,8 @@
 //          [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--fov deg --F f --focus d]
 //          [--noise-threshold T [--min-spp M --adaptive-step S]]   (adaptive sampling: --spp is the per-pixel cap, the frame renders in calls of S samples
 //                                                                    until no pixel is active; prints the frame's mean spp)
+//          [--adaptive-block G --adaptive-growth K]   (with --noise-threshold: G x G pixel blocks (1, 2, 4, 8) stop together; K = 2 tests at M, 2M, 4M ... only,
+//                                                       and the frame renders in calls that end on those boundaries)
 //          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
 #include <chrono>
 #include <cmath>
@@ -35,7 +37,7 @@ int main(int argc, char** argv)
   float fps = 24.0f, max_time = 9.5f, fov_deg = 60.0f, F = 100.0f, focus = 8.0f;
   bool bloom = false, sun = false, sky = false, reference_launches = false;
   float noise_threshold = -1.0f;  // --noise-threshold T: adaptive sampling, --spp becomes the per-pixel cap
-  int min_spp = 64, adaptive_step = 16;
+  int min_spp = 64, adaptive_step = 16, adaptive_block = 1, adaptive_growth = 1;
   std::vector<int> devices;  // --devices: empty = FH_DEVICES, or device 0
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -59,13 +61,17 @@ int main(int argc, char** argv)
     else if (a == "--noise-threshold") noise_threshold = float(std::atof(next()));
     else if (a == "--min-spp") min_spp = std::atoi(next());
     else if (a == "--adaptive-step") adaptive_step = std::atoi(next());
+    else if (a == "--adaptive-block") adaptive_block = std::atoi(next());
+    else if (a == "--adaptive-growth") adaptive_growth = std::atoi(next());
     else if (a == "--devices") {
       try { devices = cwl::parse_device_list(next(), "--devices"); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S]] [--devices 0,1,...]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
+  if (adaptive_block != 1 && adaptive_block != 2 && adaptive_block != 4 && adaptive_block != 8) { std::fprintf(stderr, "--adaptive-block must be 1, 2, 4 or 8\n"); return 2; }
+  if (adaptive_growth != 1 && adaptive_growth != 2) { std::fprintf(stderr, "--adaptive-growth must be 1 or 2\n"); return 2; }
   const float time_step = 1.0f / fps;
   try {
     std::filesystem::create_directories(out_dir);
@@ -124,9 +130,12 @@ int main(int argc, char** argv)
           if (noise_threshold < 0.0f) {
             renderer.render(camera, make_float3(0, 0, 0), render_layer, uint32_t(n_spp), uint32_t(max_depth));
           } else {  // calls of --adaptive-step samples until every pixel has stopped or reached --spp
+            renderer.set_adaptive_policy(uint32_t(adaptive_block), uint32_t(adaptive_growth));
             renderer.set_adaptive_sampling(noise_threshold, uint32_t(min_spp), uint32_t(adaptive_step));
             for (int done = 0; done < n_spp;) {
-              const int k = n_spp - done < adaptive_step ? n_spp - done : adaptive_step;
+              // (growth 2: a call that ended between two boundaries would end a round there, and the schedule would buy nothing)
+              const uint32_t call = adaptive_growth == 2 ? renderer.adaptive_next_boundary() : uint32_t(adaptive_step);
+              const int k = uint32_t(n_spp - done) < call ? n_spp - done : int(call);
               renderer.render(camera, make_float3(0, 0, 0), render_layer, uint32_t(k), uint32_t(max_depth));
               done += k;
               if (done < n_spp && renderer.active_pixel_count() == 0) break;

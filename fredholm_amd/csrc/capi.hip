@@ -617,7 +617,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
                   ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_sample_count, ctx->d_owned, ctx->d_trace_counters, ctx->d_texels, ctx->d_textures, ctx->d_srgb_lut, ctx->d_ibl,
                   ctx->d_bloom_weights, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
                   ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
-                  ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
+                  ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active[2], ctx->d_active[3], ctx->d_block_marks, ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (fh_ctx::ShardList& c : ctx->shard_lists)
@@ -942,6 +942,39 @@ int fh_get_adaptive_sampling(fh_ctx* ctx, int* enabled, fh_adaptive_params* p)
   return FH_OK;
 }
 
+int fh_set_adaptive_policy(fh_ctx* ctx, uint32_t block, uint32_t growth)
+{
+  FH_GROUP_EACH(ctx, kGroupCallFrame, fh_set_adaptive_policy(m_, block, growth));
+  CTX_CHECK(ctx);
+  if (block != 1u && block != 2u && block != 4u && block != 8u) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_policy: block must be 1, 2, 4 or 8");
+  if (growth != 1u && growth != 2u) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_policy: growth must be 1 or 2");
+  if (block == ctx->adapt_block && growth == ctx->adapt_growth) return FH_OK;
+  if (ctx->accumulated) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_policy: samples were accumulated since fh_init_render_states / fh_set_resolution (every stop so far followed the old policy)");
+  if (ctx->tile_w % block != 0u || ctx->tile_h % block != 0u) return fail(ctx, FH_E_INVALID, "fh_set_adaptive_policy: tile width and height must be multiples of block (a guard block has one owner)");
+  ctx->adapt_block = block;
+  ctx->adapt_growth = growth;
+  return ctx->adaptive ? adaptive_upload(ctx) : FH_OK;  // (the device copy of the parameters, the marks of the guard blocks)
+}
+
+int fh_get_adaptive_policy(fh_ctx* ctx, uint32_t* block, uint32_t* growth)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (block) *block = ctx->adapt_block;
+  if (growth) *growth = ctx->adapt_growth;
+  return FH_OK;
+}
+
+int fh_adaptive_next_boundary(fh_ctx* ctx, uint32_t* samples)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!samples) return fail(ctx, FH_E_INVALID, "fh_adaptive_next_boundary: null argument");
+  if (!ctx->adaptive) return fail(ctx, FH_E_INVALID, "fh_adaptive_next_boundary: adaptive sampling is off");
+  *samples = adaptive_to_boundary(ctx);
+  return FH_OK;
+}
+
 int fh_get_sample_counts(fh_ctx* ctx, uint32_t* counts)
 {
   FH_GROUP(ctx, group_get_sample_counts(ctx, counts));
@@ -1035,6 +1068,7 @@ int fh_set_tile_shard(fh_ctx* ctx, uint32_t rank, uint32_t world, uint32_t tw, u
   FH_GROUP(ctx, group_set_tile_shard(ctx, rank, world, tw, th));
   CTX_CHECK(ctx);
   if (world == 0 || rank >= world || tw == 0 || th == 0) return fail(ctx, FH_E_INVALID, "bad shard");
+  if (tw % ctx->adapt_block != 0u || th % ctx->adapt_block != 0u) return fail(ctx, FH_E_INVALID, "fh_set_tile_shard: tile width and height must be multiples of the adaptive policy's block (a guard block has one owner)");
   (void)hipStreamSynchronize(ctx->stream);
   ctx->shard_rank = rank; ctx->shard_world = world; ctx->tile_w = tw; ctx->tile_h = th;
   return rebuild_ownership(ctx);

@@ -126,10 +126,15 @@ struct fh_ctx {
   float2* d_moments = nullptr;         // (m1, m2) per pixel of the frame, cleared by fh_init_render_states
   bool accumulated = false;            // a call has submitted samples since fh_init_render_states / fh_set_resolution
   uint32_t adapt_total = 0;            // samples requested since then: the count every pixel still active shares (rounds end where it is a multiple of step)
-  uint32_t* d_active[2] = {nullptr, nullptr};  // the active pixels of the round: image indices, x | y << 16 (a stable compaction of the call's base list)
-  uint32_t* d_active_blocks = nullptr; // per-workgroup counts, then their exclusive scan; word [capacity blocks] = the active count
+  uint32_t* d_active[4] = {nullptr, nullptr, nullptr, nullptr};  // the active pixels of the round: image indices, x | y << 16 (a stable compaction of the call's base list); [2] / [3]: of its sky list (guard blocks only)
+  uint32_t* d_active_blocks = nullptr; // per-workgroup counts, then their exclusive scan; word [capacity blocks] = the active count (twice: the base list, the sky list)
   uint32_t active_capacity = 0;
-  uint32_t* h_active_count = nullptr;  // pinned: the count read back at every boundary
+  uint32_t* h_active_count = nullptr;  // pinned: the counts read back at every boundary (base list, sky list)
+  // fh_set_adaptive_policy: guard blocks of adapt_block x adapt_block pixels stop together, boundaries grow by adapt_growth (render.hip: k_adaptive_mark, adaptive_to_boundary)
+  uint32_t adapt_block = 1, adapt_growth = 1;
+  uint32_t* d_block_marks = nullptr;   // one word per guard block of the frame: the sequence number of the last selection that found an unconverged pixel in it
+  size_t marks_capacity = 0;
+  uint32_t mark_seq = 0;
   unsigned long long* d_sky_taken = nullptr;  // samples the adaptive k_sky_pixels took since the last fh_sync (fh_stats.paths)
   bool sky_taken_pending = false;
   void* d_sky_adaptive = nullptr;      // the adaptive k_sky_pixels' arguments beyond the plain form's (render.hip: SkyAdaptive)
@@ -274,7 +279,9 @@ SceneDev scene_dev(const fh_ctx* ctx);
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);  // render.hip
 int adaptive_upload(fh_ctx* ctx);  // render.hip
-int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, uint32_t* n_active);  // render.hip (synchronising)
+int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, uint32_t* n_active, const uint32_t* sky_px = nullptr,
+                    const uint32_t* sky_xy = nullptr, uint32_t n_sky = 0, uint32_t* n_sky_active = nullptr);  // render.hip (synchronising)
+uint32_t adaptive_to_boundary(const fh_ctx* ctx);  // render.hip: samples from adapt_total to the next boundary
 int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity);   // render.hip
 uint64_t pool_bytes_per_path(const fh_ctx* ctx);            // capi.hip
 void pool_release(fh_ctx* ctx);

@@ -303,16 +303,31 @@ __global__ void __launch_bounds__(kBlock) k_split_pixels(FrameDev fr, SplitDev s
 // beauty layer's coefficients; a pixel whose count n is a boundary (n >= min_samples, n % step == 0) and whose relative error estimate is within the threshold gets
 // no further samples.  Its state then no longer changes, so the predicate keeps holding until fh_init_render_states: the selection below can re-evaluate it from the
 // state alone, and a pixel that stops after s samples holds the bits a plain render holds after s samples.
+// fh_set_adaptive_policy: with growth 2 the boundaries are b0 * 2^k only (b0: the first multiple of step >= min_samples).  With guard blocks (block > 1) a pixel gets
+// no further samples when every pixel of its aligned block x block square is converged: k_adaptive_mark writes the sequence number of the selection into the word of
+// every block that holds an unconverged pixel, and a pixel is active when its block's word holds that number.  All pixels of a block share their count, so a stopped
+// block stays stopped, and the rule is as stateless as the per-pixel one.
 struct AdaptiveDev {
   float2* moments;
   const uint32_t* count;  // sample_count
   float threshold, floor;
   uint32_t min_samples, step;
+  uint32_t growth, b0;           // b0 = 0: no boundary fits 32 bits
+  uint32_t* marks;               // null: the per-pixel rule
+  uint32_t tag, block_shift, blocks_x, width;
 };
+
+FH_D bool adaptive_boundary(const AdaptiveDev& ad, uint32_t n)
+{
+  if (ad.growth == 1u) return n >= ad.min_samples && n % ad.step == 0u;
+  if (ad.b0 == 0u || n < ad.b0 || n % ad.b0 != 0u) return false;
+  const uint32_t q = n / ad.b0;
+  return (q & (q - 1u)) == 0u;
+}
 
 FH_D bool adaptive_converged(const AdaptiveDev& ad, uint32_t n, float m1, float m2)
 {
-  if (n < ad.min_samples || n % ad.step != 0u) return false;
+  if (!adaptive_boundary(ad, n)) return false;
   float d = m2 - m1 * m1;
   if (d < 0.0f) d = 0.0f;  // (NaN stays NaN)
   const float var = d * ((float)n / (float)(n - 1u));
@@ -331,6 +346,7 @@ FH_D void moments_update(float& m1, float& m2, float coef, float fn, f3 radiance
 
 // all `n_samples` samples of this call for the sky pixels: k_generate's path for a ray that misses the scene bounds and k_accumulate's update of the running means, fused.
 // ADAPTIVE: also the moments, and a pixel stops at the first boundary where it is converged (issued = first + samples taken, counted in SkyAdaptive::taken for fh_stats.paths).
+// With guard blocks the launch is one round of the pixels the selection left active: it stops nothing itself (a pixel that is converged alone follows its block).
 // The adaptive form takes its extra state through the pointer in place of `violations`: the kernel arguments of the plain form stay as they are.
 struct SkyAdaptive {
   AdaptiveDev ad;
@@ -366,7 +382,7 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev la
     if constexpr (ADAPTIVE) m = ad.moments[image_idx];
     uint32_t taken = n_samples;
     for (uint32_t k = 0; k < n_samples; ++k) {
-      if constexpr (ADAPTIVE) { if (adaptive_converged(ad, n_spp, m.x, m.y)) { taken = k; break; } }
+      if constexpr (ADAPTIVE) { if (!ad.marks && adaptive_converged(ad, n_spp, m.x, m.y)) { taken = k; break; } }
       f3 org, dir;
       const uint32_t n = first + k;
       if ((n >> 4) != blk) {
@@ -417,10 +433,33 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev la
 // The stable compaction of a base list (the owned pixels, or the pixels the passes render when the call splits off the sky) into the pixels still active:
 // per-workgroup counts, one scan of them, and a scatter that keeps the base list's order (the 8x8 pixel blocks of the ownership list stay together).
 // `blocks` holds one count per workgroup of 256 base entries, then the total.
-FH_D bool adaptive_active(const AdaptiveDev& ad, uint32_t image_idx)
+FH_D bool adaptive_unconverged(const AdaptiveDev& ad, uint32_t image_idx)
 {
   const float2 m = ad.moments[image_idx];
   return !adaptive_converged(ad, ad.count[image_idx], m.x, m.y);
+}
+
+FH_D bool adaptive_active(const AdaptiveDev& ad, uint32_t image_idx)
+{
+  if (ad.marks) {
+    const uint32_t y = image_idx / ad.width, x = image_idx - y * ad.width;
+    return ad.marks[(y >> ad.block_shift) * ad.blocks_x + (x >> ad.block_shift)] == ad.tag;
+  }
+  return adaptive_unconverged(ad, image_idx);
+}
+
+// one lane per owned pixel (sky pixels included), blocks addressed by image coordinates: the order of the list changes nothing.  Every writer of a word writes the
+// same value, so plain stores do; a lane whose neighbour below holds an unconverged pixel of the same block leaves the store to it (the list keeps rows of a block together).
+__global__ void __launch_bounds__(kBlock) k_adaptive_mark(AdaptiveDev ad, const uint32_t* owned_px, const uint32_t* owned_xy, uint32_t n_owned)
+{
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t key = 0xffffffffu;  // (no block has this index: a frame has at most 65535 x 65535 pixels and a block at least four)
+  if (i < n_owned && adaptive_unconverged(ad, owned_px[i])) {
+    const uint32_t xy = owned_xy[i];
+    key = ((xy >> 16) >> ad.block_shift) * ad.blocks_x + ((xy & 0xffffu) >> ad.block_shift);
+  }
+  const uint32_t below = __shfl_up(key, 1);
+  if (key != 0xffffffffu && ((threadIdx.x & 63u) == 0u || below != key)) ad.marks[key] = ad.tag;
 }
 
 __global__ void __launch_bounds__(kBlock) k_adaptive_count(AdaptiveDev ad, const uint32_t* base_px, uint32_t n_base, uint32_t* blocks)
@@ -2061,47 +2100,104 @@ static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
   return FH_OK;
 }
 
-static AdaptiveDev adaptive_dev(const fh_ctx* ctx)
+// the first boundary: the smallest multiple of step that is >= min_samples
+static unsigned long long adaptive_b0(const fh_ctx* ctx)
 {
-  return AdaptiveDev{ctx->d_moments, ctx->d_sample_count, ctx->adapt.threshold, ctx->adapt.floor, ctx->adapt.min_samples, ctx->adapt.step};
+  const unsigned long long step = ctx->adapt.step ? ctx->adapt.step : 1u;
+  return (ctx->adapt.min_samples + step - 1ull) / step * step;
 }
 
-// the device copy of the adaptive k_sky_pixels' state: made again whenever the parameters or the moments buffer change (capi.hip: adaptive_reset), when no launch reads it
+static AdaptiveDev adaptive_dev(const fh_ctx* ctx)
+{
+  const unsigned long long b0 = adaptive_b0(ctx);
+  uint32_t shift = 0;
+  while ((1u << shift) < ctx->adapt_block) ++shift;
+  return AdaptiveDev{ctx->d_moments, ctx->d_sample_count, ctx->adapt.threshold, ctx->adapt.floor, ctx->adapt.min_samples, ctx->adapt.step,
+                     ctx->adapt_growth, b0 <= 0xffffffffull ? (uint32_t)b0 : 0u,
+                     ctx->adapt_block > 1u ? ctx->d_block_marks : nullptr, ctx->mark_seq, shift, (ctx->width + ctx->adapt_block - 1u) >> shift, ctx->width};
+}
+
+// samples from the count requested since fh_init_render_states to the next boundary of the policy (fh_adaptive_next_boundary; the rounds of growth 2)
+uint32_t adaptive_to_boundary(const fh_ctx* ctx)
+{
+  const unsigned long long t = ctx->adapt_total, b0 = adaptive_b0(ctx);
+  unsigned long long next = b0;
+  if (t >= b0) {
+    if (ctx->adapt_growth == 1u) next = t - t % ctx->adapt.step + ctx->adapt.step;
+    else while (next <= t) next *= 2ull;
+  }
+  return next - t > 0xffffffffull ? 0xffffffffu : (uint32_t)(next - t);
+}
+
+// the device copy of the adaptive k_sky_pixels' state: made again whenever the parameters, the policy or the moments buffer change (capi.hip: adaptive_reset), when no
+// launch reads it; with guard blocks also their marks (cleared, sequence 0: no block is marked)
 int adaptive_upload(fh_ctx* ctx)
 {
   if (!ctx->d_sky_adaptive) FH_HIP(hipMalloc(&ctx->d_sky_adaptive, sizeof(SkyAdaptive)));
-  const SkyAdaptive h{adaptive_dev(ctx), ctx->d_split_counters + 2, ctx->d_sky_taken};
   FH_HIP(hipStreamSynchronize(ctx->stream));  // (earlier calls have joined the main stream)
+  if (ctx->adapt_block > 1u) {
+    const size_t b = ctx->adapt_block, words = (size_t)((ctx->width + b - 1u) / b) * ((ctx->height + b - 1u) / b);
+    if (words > ctx->marks_capacity) {
+      if (ctx->d_block_marks) (void)hipFree(ctx->d_block_marks);
+      ctx->d_block_marks = nullptr;
+      ctx->marks_capacity = 0;
+      FH_HIP(hipMalloc((void**)&ctx->d_block_marks, 4ull * words));
+      ctx->marks_capacity = words;
+    }
+    FH_HIP(hipMemsetAsync(ctx->d_block_marks, 0, 4ull * ctx->marks_capacity, ctx->stream));  // (the selections run on this stream)
+    ctx->mark_seq = 0;
+  }
+  const SkyAdaptive h{adaptive_dev(ctx), ctx->d_split_counters + 2, ctx->d_sky_taken};
   FH_HIP(hipMemcpy(ctx->d_sky_adaptive, &h, sizeof h, hipMemcpyHostToDevice));
   return FH_OK;
 }
 
-// the active pixels of a base list into ctx->d_active, ordered on `st`; waits for the count (the passes of a round are sized with it)
-int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, uint32_t* n_active)
+// the active pixels of a base list into ctx->d_active, ordered on `st`; waits for the count (the passes of a round are sized with it).  With guard blocks the blocks are
+// marked first, from all owned pixels, and a sky list (the round's k_sky_pixels launch) is compacted next to the base list: d_active[2] / [3], one wait for both counts.
+int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, uint32_t* n_active, const uint32_t* sky_px, const uint32_t* sky_xy,
+                    uint32_t n_sky, uint32_t* n_sky_active)
 {
-  if (ctx->active_capacity < ctx->n_owned || !ctx->h_active_count) {
+  const bool blocks = ctx->adapt_block > 1u;
+  if (ctx->active_capacity < ctx->n_owned || !ctx->h_active_count || (blocks && !ctx->d_active[2])) {
     FH_HIP(hipDeviceSynchronize());  // (launches of earlier calls may still read the old lists)
-    for (int k = 0; k < 2; ++k) { if (ctx->d_active[k]) (void)hipFree(ctx->d_active[k]); ctx->d_active[k] = nullptr; }
+    for (int k = 0; k < 4; ++k) { if (ctx->d_active[k]) (void)hipFree(ctx->d_active[k]); ctx->d_active[k] = nullptr; }
     if (ctx->d_active_blocks) (void)hipFree(ctx->d_active_blocks);
     ctx->d_active_blocks = nullptr;
     ctx->active_capacity = 0;
-    for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&ctx->d_active[k], 4ull * ctx->n_owned));
-    FH_HIP(hipMalloc((void**)&ctx->d_active_blocks, 4ull * ((ctx->n_owned + kBlock - 1u) / kBlock + 1u)));
-    if (!ctx->h_active_count) FH_HIP(hipHostMalloc((void**)&ctx->h_active_count, 4, hipHostMallocDefault));
+    for (int k = 0; k < (blocks ? 4 : 2); ++k) FH_HIP(hipMalloc((void**)&ctx->d_active[k], 4ull * ctx->n_owned));
+    FH_HIP(hipMalloc((void**)&ctx->d_active_blocks, 2ull * 4ull * ((ctx->n_owned + kBlock - 1u) / kBlock + 1u)));
+    if (!ctx->h_active_count) FH_HIP(hipHostMalloc((void**)&ctx->h_active_count, 8, hipHostMallocDefault));
     ctx->active_capacity = ctx->n_owned;
   }
-  if (n_base > ctx->active_capacity) return fail(ctx, FH_E_INVALID, "adaptive_select: base list longer than the owned pixels");
+  if (n_base > ctx->active_capacity || n_sky > ctx->active_capacity) return fail(ctx, FH_E_INVALID, "adaptive_select: base list longer than the owned pixels");
+  if (n_sky && !(blocks && n_sky_active)) return fail(ctx, FH_E_INVALID, "adaptive_select: a sky list is compacted with guard blocks only");
   *n_active = 0;
-  if (n_base == 0) return FH_OK;
+  if (n_sky_active) *n_sky_active = 0;
+  if (n_base == 0 && n_sky == 0) return FH_OK;
+  if (blocks) {
+    if (!ctx->d_block_marks) return fail(ctx, FH_E_INVALID, "adaptive_select: no block marks");
+    if (++ctx->mark_seq == 0u) {  // (the sequence wrapped: words of 2^32 selections ago would read as marked)
+      FH_HIP(hipMemsetAsync(ctx->d_block_marks, 0, 4ull * ctx->marks_capacity, st));
+      ctx->mark_seq = 1u;
+    }
+  }
   const AdaptiveDev ad = adaptive_dev(ctx);
-  const uint32_t n_blocks = (n_base + kBlock - 1u) / kBlock;
-  hipLaunchKernelGGL(k_adaptive_count, dim3(n_blocks), dim3(kBlock), 0, st, ad, base_px, n_base, ctx->d_active_blocks);
-  hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, st, ctx->d_active_blocks, n_blocks);
-  hipLaunchKernelGGL(k_adaptive_select, dim3(n_blocks), dim3(kBlock), 0, st, ad, base_px, base_xy, n_base, ctx->d_active_blocks, ctx->d_active[0], ctx->d_active[1]);
-  FH_HIP(hipMemcpyAsync(ctx->h_active_count, ctx->d_active_blocks + n_blocks, 4, hipMemcpyDeviceToHost, st));
+  if (blocks) hipLaunchKernelGGL(k_adaptive_mark, dim3((ctx->n_owned + kBlock - 1u) / kBlock), dim3(kBlock), 0, st, ad, ctx->d_owned, ctx->d_owned_xy, ctx->n_owned);
+  uint32_t* const scan_sky = ctx->d_active_blocks + ((ctx->active_capacity + kBlock - 1u) / kBlock + 1u);
+  auto compact = [&](const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t* scan, uint32_t* out_px, uint32_t* out_xy, uint32_t* h_count) -> int {
+    const uint32_t n_blocks = (n + kBlock - 1u) / kBlock;
+    hipLaunchKernelGGL(k_adaptive_count, dim3(n_blocks), dim3(kBlock), 0, st, ad, px, n, scan);
+    hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, st, scan, n_blocks);
+    hipLaunchKernelGGL(k_adaptive_select, dim3(n_blocks), dim3(kBlock), 0, st, ad, px, xy, n, scan, out_px, out_xy);
+    FH_HIP(hipMemcpyAsync(h_count, scan + n_blocks, 4, hipMemcpyDeviceToHost, st));
+    return FH_OK;
+  };
+  if (n_base) { const int rc = compact(base_px, base_xy, n_base, ctx->d_active_blocks, ctx->d_active[0], ctx->d_active[1], ctx->h_active_count); if (rc) return rc; }
+  if (n_sky) { const int rc = compact(sky_px, sky_xy, n_sky, scan_sky, ctx->d_active[2], ctx->d_active[3], ctx->h_active_count + 1); if (rc) return rc; }
   FH_HIP(hipStreamSynchronize(st));
-  *n_active = *ctx->h_active_count;
-  if (*n_active > n_base) return fail(ctx, FH_E_HIP, "adaptive_select: count beyond the base list");
+  if (n_base) *n_active = ctx->h_active_count[0];
+  if (n_sky) *n_sky_active = ctx->h_active_count[1];
+  if (*n_active > n_base || (n_sky && *n_sky_active > n_sky)) return fail(ctx, FH_E_HIP, "adaptive_select: count beyond the base list");
   return FH_OK;
 }
 
@@ -2112,6 +2208,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   if (max_depth > 64) return fail(ctx, FH_E_INVALID, "fh_render: max_depth > 64 is not supported");
   if (ctx->n_owned == 0 || n_samples == 0) return FH_OK;
   const bool adaptive = ctx->adaptive;
+  const bool guard_blocks = adaptive && ctx->adapt_block > 1u;  // (the sky pixels then follow their blocks: one k_sky_pixels launch per round, on the round's selection)
   if (adaptive && (ctx->flags & FH_FLAG_REFERENCE_FIRSTHIT) != 0 && n_samples > 1)
     return fail(ctx, FH_E_INVALID, "fh_render: FH_FLAG_REFERENCE_FIRSTHIT with n_samples > 1 does not combine with adaptive sampling (its first-hit state is per launch)");
   ctx->accumulated = true;
@@ -2253,8 +2350,8 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   // (FH_FLAG_SERIAL_PASSES and FH_PIPELINE=0, the measuring modes: in line on the main stream, so that every kernel of the call is alone on the GPU, the spans add up and
   // a serial kernel trace shows the kernel's work instead of the time a starved background kernel was resident)
   hipStream_t sky_st = ((ctx->flags & FH_FLAG_SERIAL_PASSES) != 0 || ctx->n_slots == 1) ? ctx->stream : ctx->sky_stream;
-  if (n_sky) {  // the sky pixels of this call, all samples at once, on a stream of their own next to the passes (they share no pixel with them)
-    if (sky_st != ctx->stream) FH_HIP(hipStreamWaitEvent(sky_st, ctx->ev_enter, 0));
+  if (n_sky && sky_st != ctx->stream) FH_HIP(hipStreamWaitEvent(sky_st, ctx->ev_enter, 0));
+  if (n_sky && !guard_blocks) {  // the sky pixels of this call, all samples at once, on a stream of their own next to the passes (they share no pixel with them)
     Span sp(ctx, sky_st, 4);
     uint32_t sky_grid = grid_for(n_sky);
     if (ctx->tun.sky_blocks_per_cu && sky_grid > ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu) sky_grid = ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu;
@@ -2381,19 +2478,31 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   // Rounds: a plain call is one.  In adaptive mode a round ends where the samples requested since fh_init_render_states are a multiple of `step`, and the pixels
   // still active are selected from the call's base list at the start of every round (a call that starts between two boundaries selects too: that only drops the
   // pixels that stopped before).  The selection waits for the round before it, and its count, read back, sizes the passes of the round.
+  // (fh_set_adaptive_policy: with growth 2 a round runs to the next boundary b0 * 2^k, in as many passes as that takes.)
   const uint32_t* const base_px = px_list;
   const uint32_t* const base_xy = xy_list;
   const uint32_t n_base = n_px;
-  bool ran = false;
+  bool ran = false, sky_ran = false;
   for (uint32_t call_done = 0; call_done < n_samples;) {
-  uint32_t n_round = n_samples - call_done;
+  uint32_t n_round = n_samples - call_done, n_sky_round = 0;
   if (adaptive) {
-    const uint32_t to_boundary = ctx->adapt.step - ctx->adapt_total % ctx->adapt.step;
+    const uint32_t to_boundary = ctx->adapt_growth == 1u ? ctx->adapt.step - ctx->adapt_total % ctx->adapt.step : adaptive_to_boundary(ctx);
     if (n_round > to_boundary) n_round = to_boundary;
     if (ran && last_slot != 0) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
-    const int rc = adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px);
+    if (sky_ran && sky_st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky_st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
+    const int rc = guard_blocks && n_sky ? adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px, ctx->d_split[2], ctx->d_split[3], n_sky, &n_sky_round)
+                                         : adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px);
     if (rc) return rc;
     px_list = ctx->d_active[0]; xy_list = ctx->d_active[1];
+    if (n_sky_round) {  // (the selection has been waited for: nothing else orders this launch)
+      Span sp(ctx, sky_st, 4);
+      uint32_t sky_grid = grid_for(n_sky_round);
+      if (ctx->tun.sky_blocks_per_cu && sky_grid > ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu) sky_grid = ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu;
+      hipLaunchKernelGGL(k_sky_pixels<true>, dim3(sky_grid), dim3(kBlock), 0, sky_st, fr, L, ctx->d_sample_issued, ctx->d_active[2], ctx->d_active[3], n_sky_round, n_round,
+                         (const SkyAdaptive*)ctx->d_sky_adaptive);
+      ctx->sky_taken_pending = true;
+      sky_ran = true;
+    }
   }
   const uint32_t batch = batch_for(n_px, n_round);
   const uint32_t coop_flush = (!tun.coop_flush_fixed && batch >= n_round && !sc.has_alpha && tun.coop_flush > 32u) ? 32u : tun.coop_flush;
@@ -2642,7 +2751,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   }
   call_done += n_round;
   ctx->adapt_total += n_round;
-  if (adaptive && n_px == 0) { ctx->adapt_total += n_samples - call_done; break; }  // (the active set only shrinks: no later round has a pixel)
+  if (adaptive && n_px == 0 && n_sky_round == 0) { ctx->adapt_total += n_samples - call_done; break; }  // (the active set only shrinks: no later round has a pixel)
   }
   // join: later work on the main stream (pack, post-process, copies, the caller's clears) sees every pass of this call
   // (the accumulates form a chain across the streams, so the last one implies all the others)

@@ -111,6 +111,7 @@ EXPORTS = [
     "fh_kat_sobol", "fh_kat_elementary", "fh_kat_warp", "fh_kat_bsdf", "fh_kat_bsdf_lobes", "fh_kat_bsdf_ior", "fh_kat_sky", "fh_kat_hosek_state", "fh_kat_camera",
     "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
     "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued",
+    "fh_set_adaptive_policy", "fh_get_adaptive_policy", "fh_adaptive_next_boundary",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -127,6 +128,9 @@ SIGNATURES = {
     "fh_get_sample_counts": [C.c_void_p, C.c_void_p],
     "fh_get_luminance_moments": [C.c_void_p, C.c_void_p],
     "fh_active_pixel_count": [C.c_void_p, C.POINTER(C.c_uint32)],
+    "fh_set_adaptive_policy": [C.c_void_p, C.c_uint32, C.c_uint32],
+    "fh_get_adaptive_policy": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "fh_adaptive_next_boundary": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_kat_set_issued": [C.c_void_p, C.c_void_p, C.c_uint32],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],

@@ -413,6 +413,23 @@ class Renderer:
     def clear_adaptive_sampling(self):
         self._ck(N.lib().fh_set_adaptive_sampling(self._ctx, None), "fh_set_adaptive_sampling")
 
+    def set_adaptive_policy(self, block=1, growth=1):
+        """how the mode decides: block x block pixel blocks (1, 2, 4, 8) stop together, when all of their pixels are converged; growth 2 tests at b0 * 2^k only
+        (b0: the first multiple of step >= min_samples).  Accepted while the mode is off, and like the mode only before the first sample of a frame."""
+        self._ck(N.lib().fh_set_adaptive_policy(self._ctx, C.c_uint32(int(block)), C.c_uint32(int(growth))), "fh_set_adaptive_policy")
+
+    def adaptive_policy(self):
+        """(block, growth)"""
+        b, g = C.c_uint32(0), C.c_uint32(0)
+        self._ck(N.lib().fh_get_adaptive_policy(self._ctx, C.byref(b), C.byref(g)), "fh_get_adaptive_policy")
+        return b.value, g.value
+
+    def adaptive_next_boundary(self):
+        """samples from those requested since init_render_states to the next boundary: a render() of that many ends a round (the mode must be on)"""
+        out = C.c_uint32(0)
+        self._ck(N.lib().fh_adaptive_next_boundary(self._ctx, C.byref(out)), "fh_adaptive_next_boundary")
+        return out.value
+
     def adaptive_sampling(self):
         """None while off, else the parameters as a dict"""
         on, p = C.c_int(0), N.AdaptiveParamsC()

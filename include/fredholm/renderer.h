@@ -122,6 +122,16 @@ class Renderer
     cwl::check(m_ctx, fh_set_adaptive_sampling(m_ctx, &p), "fh_set_adaptive_sampling");
   }
   void clear_adaptive_sampling() { cwl::check(m_ctx, fh_set_adaptive_sampling(m_ctx, nullptr), "fh_set_adaptive_sampling"); }
+  // how the mode decides (fh_set_adaptive_policy): block x block pixel blocks (1, 2, 4, 8) stop together, when all of their pixels are converged; growth 2 tests at
+  // b0 * 2^k only (b0: the first multiple of step >= min_samples).  Accepted while the mode is off; like the mode itself, before the first render of the frame.
+  void set_adaptive_policy(uint32_t block = 1, uint32_t growth = 1) { cwl::check(m_ctx, fh_set_adaptive_policy(m_ctx, block, growth), "fh_set_adaptive_policy"); }
+  void adaptive_policy(uint32_t& block, uint32_t& growth) { cwl::check(m_ctx, fh_get_adaptive_policy(m_ctx, &block, &growth), "fh_get_adaptive_policy"); }
+  uint32_t adaptive_next_boundary()  // samples from those requested so far to the next boundary: the call that ends a round (the mode must be on)
+  {
+    uint32_t n = 0;
+    cwl::check(m_ctx, fh_adaptive_next_boundary(m_ctx, &n), "fh_adaptive_next_boundary");
+    return n;
+  }
   void get_sample_counts(cwl::CUDABuffer<uint32_t>& counts)  // width * height
   {
     cwl::check(m_ctx, fh_get_sample_counts(m_ctx, counts.get_device_ptr()), "fh_get_sample_counts");

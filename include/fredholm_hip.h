@@ -261,6 +261,22 @@ typedef struct fh_adaptive_params {
  * FH_E_INVALID while it is on. */
 int fh_set_adaptive_sampling(fh_ctx* ctx, const fh_adaptive_params* params);
 int fh_get_adaptive_sampling(fh_ctx* ctx, int* enabled, fh_adaptive_params* params);
+/* how adaptive sampling decides (defaults 1, 1: exactly the per-pixel rule above).
+ * block in {1, 2, 4, 8}: the guard block of pixel (x, y) is the set of frame pixels (x', y') with x' / block = x / block and y' / block = y / block, cut off by the
+ * frame at its right and bottom edges.  A pixel gets no further samples exactly when EVERY pixel of its guard block satisfies the per-pixel predicate above at its
+ * own current state.  So all pixels of a block always hold the same count and stop at the same boundary; a stopped block's states are frozen, so the rule keeps
+ * holding (it is as stateless as the per-pixel rule); a pixel that passes alone keeps sampling and its moments keep updating; and each pixel still holds the bits
+ * of a plain render at its count.  Tile width and height must be multiples of block, so that a block never spans two owners: whichever of this call and
+ * fh_set_tile_shard would break that returns FH_E_INVALID.
+ * growth in {1, 2}: with b0 the smallest multiple of step >= min_samples, growth 1 puts a boundary at every multiple of step >= min_samples (the rule above) and
+ * growth 2 at b0 * 2^k only; a round of fh_render then runs to the next boundary in as many passes as that takes, and the rounds before b0 merge into one.
+ * Values outside the sets are FH_E_INVALID and change nothing.  Changing a value once a sample has been accumulated since fh_init_render_states /
+ * fh_set_resolution is FH_E_INVALID; setting the values it has is FH_OK.  The policy is accepted while the mode is off and survives turning the mode off and on
+ * and fh_set_resolution. */
+int fh_set_adaptive_policy(fh_ctx* ctx, uint32_t block, uint32_t growth);
+int fh_get_adaptive_policy(fh_ctx* ctx, uint32_t* block, uint32_t* growth);
+/* samples from the count requested since fh_init_render_states to the next boundary (>= 1); FH_E_INVALID while the mode is off */
+int fh_adaptive_next_boundary(fh_ctx* ctx, uint32_t* samples);
 /* device buffer of width * height sample counts, copied on the context stream (works with the mode off too) */
 int fh_get_sample_counts(fh_ctx* ctx, uint32_t* counts);
 /* device buffer of width * height float2 (m1, m2), copied on the context stream; FH_E_INVALID while the mode is off */
