@@ -572,6 +572,7 @@ int fh_ctx_create(int device, fh_ctx** out)
     env_off("FH_OVERLAP", t.overlap_secondary);
     env_off("FH_MERGE", t.merge_trace);
     env_uint("FH_SKY_BLOCKS", 0, 64, t.sky_blocks_per_cu);
+    env_uint("FH_SKY_FILLER_GRID", 0, 65535, t.sky_filler_grid);
     if (const char* e = getenv("FH_POISON")) t.poison_pools = e[0] == '1';
     env_off("FH_SKY_SPLIT", t.sky_split);
     env_uint("FH_SKY_SPLIT_MIN_LOG2", 0, 40, t.sky_split_min_log2);
@@ -589,14 +590,15 @@ int fh_ctx_create(int device, fh_ctx** out)
     t.debug_tail = getenv("FH_DEBUG_TAIL") != nullptr;
     if (const char* e = getenv("FH_FORCE_ALPHA")) t.force_alpha = e[0] == '1';
   }
-  {  // the sky-pixel kernel's stream has the lowest priority: its workgroups -- pure arithmetic, 110 registers -- take what the passes leave instead of the wave slots the
-     // traversal launches want (FH_SKY_PRIO=0: default priority; profiles/README.md r4-13)
+  {  // the sky-pixel kernel's stream has the lowest priority: the workgroups of its filler launch -- pure arithmetic, 80 registers -- take what the passes leave instead of the
+     // wave slots the traversal launches want (FH_SKY_PRIO=0: default priority; profiles/README.md r4-13)
     int least = 0, greatest = 0;
     const char* e = getenv("FH_SKY_PRIO");
     const bool low = !(e && e[0] == '0') && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
     if ((low ? hipStreamCreateWithPriority(&ctx->sky_stream, hipStreamNonBlocking, least) : hipStreamCreateWithFlags(&ctx->sky_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate failed");
   }
   (void)hipEventCreateWithFlags(&ctx->ev_sky, hipEventDisableTiming);
+  (void)hipEventCreateWithFlags(&ctx->ev_sky_cursor, hipEventDisableTiming);
   if (hipMalloc((void**)&ctx->d_split_counters, 16) != hipSuccess) return bail("hipMalloc failed");
   (void)hipMemsetAsync(ctx->d_split_counters, 0, 16, ctx->stream);
   (void)hipEventCreate(&ctx->ev_render_begin);
@@ -628,6 +630,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
   if (ctx->h_active_count) (void)hipHostFree(ctx->h_active_count);
   if (ctx->sky_stream) { (void)hipStreamSynchronize(ctx->sky_stream); (void)hipStreamDestroy(ctx->sky_stream); }
   if (ctx->ev_sky) (void)hipEventDestroy(ctx->ev_sky);
+  if (ctx->ev_sky_cursor) (void)hipEventDestroy(ctx->ev_sky_cursor);
   for (auto& s : ctx->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
   for (auto e : ctx->ev_bounce) (void)hipEventDestroy(e);

@@ -110,11 +110,12 @@ struct fh_ctx {
   // pixels that cannot see the scene (render.hip: k_split_pixels / k_sky_pixels): [0] / [1] image indices and x | y << 16 of the pixels the passes render, [2] / [3] of the sky pixels
   uint32_t* d_split[4] = {nullptr, nullptr, nullptr, nullptr};
   uint32_t split_capacity = 0, n_wave_px = 0, n_sky_px = 0;
-  uint32_t* d_split_counters = nullptr;  // wave pixels, sky pixels, bounds-test violations seen by k_sky_pixels, pad
+  uint32_t* d_split_counters = nullptr;  // wave pixels, sky pixels, bounds-test violations seen by k_sky_pixels, k_sky_pixels' cursor over the groups of its list
   bool split_valid = false;
   float split_key[32] = {};              // camera, scene bounds, resolution and ownership the lists were made for
   hipStream_t sky_stream = nullptr;
   hipEvent_t ev_sky = nullptr;
+  hipEvent_t ev_sky_cursor = nullptr;  // the cursor has been cleared on the main stream: the filler launch on the sky stream follows it
   struct ShardList { uint32_t rank, world, width, height, tile_w, tile_h; uint32_t* d_owned; uint32_t n_owned; };
   // fh_unpack_shards: the ownership lists of all ranks of a split one after the other (a permutation of the frame) and where each rank's begins
   struct FrameMap { uint32_t world = 0, width = 0, height = 0, tile_w = 0, tile_h = 0; uint32_t* d_all = nullptr; std::vector<uint32_t> start; };
@@ -202,7 +203,8 @@ struct fh_ctx {
     bool overlap_secondary = true;  // FH_OVERLAP=0: single-pass calls keep every launch on one stream
     bool sky_split = true;          // FH_SKY_SPLIT=0: every pixel goes through the passes (no k_sky_pixels)
     uint32_t sky_split_min_log2 = 27; // FH_SKY_SPLIT_MIN_LOG2: a call splits its pixels from 2^n camera paths on (27: 64 spp of a 1080p frame; tests lower it)
-    uint32_t sky_blocks_per_cu = 0; // FH_SKY_BLOCKS: workgroups per CU k_sky_pixels is launched with (grid-stride over the sky pixels); 0 = one thread per pixel
+    uint32_t sky_blocks_per_cu = 1; // FH_SKY_BLOCKS: workgroups per CU of k_sky_pixels' filler launch, which runs beside the passes (render_submit); 0 = no filler, the drain launch renders everything
+    uint32_t sky_filler_grid = 0;   // FH_SKY_FILLER_GRID: the filler's workgroups in total, whatever the number of CUs (tests: one workgroup, so that the drain does most groups); 0 = per CU, above
     bool poison_pools = false;      // FH_POISON=1: new path pools are filled with 0xa5 before their first use (tests: nothing may read what nobody wrote)
     bool merge_trace = true;        // FH_MERGE=0: single-pass calls trace secondary rays and the next bounce's closest-hit rays in two launches (two streams) instead of one
     uint32_t shade_wgs = 0;         // FH_SHADE_WGS=2|3: workgroups per CU the shade kernels are compiled for (0: three; until r5-12 for textured scenes that stream only)

@@ -49,22 +49,37 @@ inline HosekSky hosek_cook(const float* table, float turbidity, float albedo, fl
 }
 
 // the three channels share every transcendental that does not depend on the coefficients
-FH_HD f3 hosek_radiance(const HosekSky& st, f3 sun_dir, float intensity, f3 v)
+// ROLLED: the channels one after the other in a loop that stays a loop.  Unrolled, the compiler evaluates the three side by side and keeps three sets of
+// intermediates live (k_sky_pixels, whose register budget leaves room for the traversal waves it runs beside).  The same operations in the same order per channel.
+template <bool ROLLED>
+FH_HD f3 hosek_radiance_form(const HosekSky& st, f3 sun_dir, float intensity, f3 v)
 {
   const float theta = fhe_acos(clampf(v.y, -1.0f, 1.0f));
   const float gamma = fhe_acos(dot(sun_dir, v));
   const float cg = fhe_cos(gamma), ct = fhe_cos(theta);
   const float rayM = cg * cg;
   const float zenith = sqrt_cr(ct);
-  float out[3];
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
+  auto channel = [&](int ch) {
     const float* c = st.cfg[ch];
     const float expM = fhe_exp(c[4] * gamma);
     const float mieM = (1.0f + cg * cg) / fhe_pow1p5(1.0f + c[8] * c[8] - 2.0f * c[8] * cg);  // arhosek.cu:109-110: pow(x, 1.5)
-    out[ch] = (1.0f + c[0] * fhe_exp(c[1] / (ct + 0.01f))) * (c[2] + c[3] * expM + c[5] * rayM + c[6] * mieM + c[7] * zenith) * st.rad[ch];
+    return (1.0f + c[0] * fhe_exp(c[1] / (ct + 0.01f))) * (c[2] + c[3] * expM + c[5] * rayM + c[6] * mieM + c[7] * zenith) * st.rad[ch];
+  };
+  if constexpr (ROLLED) {
+    float r = 0.0f, g = 0.0f, b = 0.0f;  // (selects, not an indexed array: that would live in scratch memory)
+#pragma unroll 1
+    for (int ch = 0; ch < 3; ++ch) {
+      const float o = channel(ch);
+      r = ch == 0 ? o : r; g = ch == 1 ? o : g; b = ch == 2 ? o : b;
+    }
+    return intensity * mk3(r, g, b);
+  } else {
+    float out[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out[ch] = channel(ch);
+    return intensity * mk3(out[0], out[1], out[2]);
   }
-  return intensity * mk3(out[0], out[1], out[2]);
 }
+FH_HD f3 hosek_radiance(const HosekSky& st, f3 sun_dir, float intensity, f3 v) { return hosek_radiance_form<false>(st, sun_dir, intensity, v); }
 
 }  // namespace fh

@@ -59,6 +59,9 @@ constexpr uint32_t kMatLds = 32;  // material records staged in LDS by the shade
 #ifndef FH_STREAM_BLOCKS_CLOSEST
 #define FH_STREAM_BLOCKS_CLOSEST FH_STREAM_BLOCKS  // the same for the closest-hit kernel, which needs fewer registers than the secondary-ray kernel
 #endif
+#ifndef FH_STREAM_BLOCKS_FILLER
+#define FH_STREAM_BLOCKS_FILLER 6  // workgroups per CU the streaming kernels are LAUNCHED with while a filler launch of k_sky_pixels is resident (render_submit)
+#endif
 #ifndef FH_SHADE_BLOCKS
 #define FH_SHADE_BLOCKS 2  // resident workgroups per CU the specialised shade kernels are compiled for (register budget = 512 / that per lane): they take 159-182 registers
 #endif                     // since their products go to memory as they are made (PoolSink); the generic seven-lobe kernel keeps one wave per SIMD (350 registers).
@@ -84,6 +87,17 @@ FH_D void load_sobol_rows(SobolRows<N>& rows, const uint32_t* tables, const uint
   __syncthreads();
 }
 
+// Wave priority of the kernels of a pass, raised once at entry.  k_sky_pixels stays at 0: its filler launch shares SIMDs with these kernels for as long as the call's passes
+// run, and the issue arbiter takes priority first and age second -- at equal priority a sky wave, which lives for a whole call, is the oldest on its SIMD and the pass
+// waves get what it leaves.  Among themselves the pass kernels stay equal.
+#ifndef FH_PASS_PRIORITY
+#define FH_PASS_PRIORITY 1
+#endif
+FH_D void pass_priority()
+{
+  if (FH_PASS_PRIORITY) __builtin_amdgcn_s_setprio(FH_PASS_PRIORITY);
+}
+
 // the sky coefficients of the frame, copied to the workgroup's LDS; the caller's next barrier publishes them
 FH_D void stage_sky(FrameDev& fr, HosekSky& lds_sky)
 {
@@ -93,6 +107,8 @@ FH_D void stage_sky(FrameDev& fr, HosekSky& lds_sky)
 }
 
 // environment seen along d: IBL, else Hosek sky, else the constant background (pt.cu:511-517, :536-542)
+// (ROLLED_SKY: fh_sky.h, hosek_radiance_form)
+template <bool ROLLED_SKY = false>
 FH_D f3 env_radiance(const FrameDev& fr, f3 d)
 {
   if (fr.has_ibl) {  // fetch_ibl (pt.cu:344-350) with cartesian_to_spherical (math.cu:111-118)
@@ -103,7 +119,7 @@ FH_D f3 env_radiance(const FrameDev& fr, f3 d)
     fht_tex2d(&fr.ibl, nullptr, phi / (2.0f * kPi), theta / kPi, o);
     return fr.sky_intensity * mk3(o[0], o[1], o[2]);
   }
-  return fr.has_hosek ? hosek_radiance(*fr.hosek, fr.sun_dir, fr.sky_intensity, d) : fr.bg;
+  return fr.has_hosek ? hosek_radiance_form<ROLLED_SKY>(*fr.hosek, fr.sun_dir, fr.sky_intensity, d) : fr.bg;
 }
 
 // sample n_spp of pixel (px, py): CMJ slots 0 / 1 -> thin-lens camera ray (pt.cu:433-454, camera.cu:24-53) and the Russian roulette of bounce 0, which has probability 1 but
@@ -144,6 +160,7 @@ FH_D bool camera_ray(const FrameDev& fr, const uint32_t* sobol_dim1, uint32_t im
 constexpr int kGenChunks = 4;  // (eight measure the same: profiles/README.md r4-20)
 __global__ void __launch_bounds__(kBlock) k_generate(FrameDev fr, PoolDev pool, const uint32_t* issued, const uint32_t* owned, const uint32_t* owned_xy, uint32_t n_owned)
 {
+  pass_priority();
   __shared__ SobolRows<1> rows;
   __shared__ HosekSky s_sky;
   stage_sky(fr, s_sky);
@@ -353,13 +370,26 @@ struct SkyAdaptive {
   uint32_t* violations;
   unsigned long long* taken;
 };
+// Register budget.  The kernel is compiled for kSkyWaves waves per SIMD, i.e. at most 512 / 6 -> 80 registers per lane, so that one of its waves fits beside six waves of
+// the streaming traversal kernels (6 x 72 + 80 = 512): it runs in the issue slots they leave idle (render_submit: filler and drain).  Three things keep it there: the
+// Hosek channels are evaluated one after the other (hosek_radiance_form<true>); the sample loop carries the beauty mean and the moments only; and the five AOV means, which
+// for a sky sample are n times `coef * (fn * a + 0)` -- no input of the sample enters -- are brought up to date AFTER the loop, when the camera and sky state is dead,
+// value for value with the operations the loop applied.  A pixel whose AOV values all hold the bit pattern +0 skips even that: coef * (fn * 0 + 0) is +0 exactly
+// (coef > 0, fn >= 0, both finite).  -0 and NaN take the update.
+//
+// Work distribution.  The list is cut into groups of 64 consecutive entries, one per wave; `cursor` counts the groups handed out.  A wave claims the next group with one
+// atomic of its first lane, renders it, and returns for another until the cursor has passed the end: the only exit, and no wave ever waits for another.  Launches that
+// share a cursor share the list: each group is claimed exactly once, whichever launch's wave comes first.
+constexpr int kSkyWaves = 6;
+constexpr uint32_t kSkyGroup = 64;
 template <bool ADAPTIVE>
-__global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev layers, uint32_t* issued, const uint32_t* sky_px, const uint32_t* sky_xy, uint32_t n_sky, uint32_t n_samples,
-                                                     std::conditional_t<ADAPTIVE, const SkyAdaptive*, uint32_t*> violations_or_adaptive)
+__global__ void __launch_bounds__(kBlock, kSkyWaves) k_sky_pixels(FrameDev fr, LayersDev layers, uint32_t* issued, const uint32_t* sky_px, const uint32_t* sky_xy, uint32_t n_sky, uint32_t n_samples,
+                                                                std::conditional_t<ADAPTIVE, const SkyAdaptive*, uint32_t*> violations_or_adaptive, uint32_t* cursor)
 {
+  static_assert(kSkyGroup == 64u, "a group is one wave's lanes");
   uint32_t* violations;
-  AdaptiveDev ad{};
-  if constexpr (ADAPTIVE) { ad = violations_or_adaptive->ad; violations = violations_or_adaptive->violations; }
+  const AdaptiveDev* adp = nullptr;  // (read where it is used: fourteen more scalars held for the whole kernel cost vector registers, as lanes that scalars spill to)
+  if constexpr (ADAPTIVE) { adp = &violations_or_adaptive->ad; violations = violations_or_adaptive->violations; }
   else violations = violations_or_adaptive;
   unsigned long long n_taken = 0;
   __shared__ SobolRows<1> rows;
@@ -367,28 +397,31 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev la
   stage_sky(fr, s_sky);
   const uint32_t dims[1] = {1u};
   load_sobol_rows<1>(rows, fr.sobol_bytes, dims);
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_sky; i += gridDim.x * blockDim.x) {
+  const uint32_t n_groups = (n_sky + kSkyGroup - 1u) / kSkyGroup;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (;;) {
+    uint32_t group = 0u;
+    if (lane == 0u) group = atomicAdd(cursor, 1u);
+    group = __shfl(group, 0);
+    if (group >= n_groups) break;  // (the same for every lane of the wave)
+    const uint32_t i = group * kSkyGroup + lane;
+    if (i < n_sky) {  // (the last group may be short; its lanes meet again below, before the next claim)
     const uint32_t image_idx = sky_px[i], xy = sky_xy[i];
     const uint32_t first = issued[image_idx];
     uint32_t n_spp = layers.sample_count[image_idx];
-    f3 beauty = mk3(layers.beauty[image_idx]), position = mk3(layers.position[image_idx]), normal = mk3(layers.normal[image_idx]), albedo = mk3(layers.albedo[image_idx]);
-    float depth = layers.depth[image_idx];
-    const float4 tc4 = layers.texcoord[image_idx];
-    float tcx = tc4.x, tcy = tc4.y;
+    f3 beauty = mk3(layers.beauty[image_idx]);
     bool violated = false;
-    uint32_t blk = 0xffffffffu;  // sixteen consecutive samples share most of their two CMJ draws (fh_sampler.h: cmj_block)
-    CmjBlock b0{}, b1{};
+    CmjBlock b0{}, b1{};  // sixteen consecutive samples share most of their two CMJ draws (fh_sampler.h: cmj_block)
     float2 m = make_float2(0.0f, 0.0f);
-    if constexpr (ADAPTIVE) m = ad.moments[image_idx];
-    uint32_t taken = n_samples;
-    for (uint32_t k = 0; k < n_samples; ++k) {
-      if constexpr (ADAPTIVE) { if (!ad.marks && adaptive_converged(ad, n_spp, m.x, m.y)) { taken = k; break; } }
+    if constexpr (ADAPTIVE) m = adp->moments[image_idx];
+    uint32_t taken = 0;
+    for (; taken < n_samples; ++taken) {
+      if constexpr (ADAPTIVE) { if (!adp->marks && adaptive_converged(*adp, n_spp, m.x, m.y)) break; }
       f3 org, dir;
-      const uint32_t n = first + k;
-      if ((n >> 4) != blk) {
-        blk = n >> 4;
-        b0 = cmj_block(blk, image_idx, 0u, fr.seed_hash);
-        b1 = cmj_block(blk, image_idx, 1u, fr.seed_hash);
+      const uint32_t n = first + taken;
+      if (taken == 0u || (n & 15u) == 0u) {
+        b0 = cmj_block(n >> 4, image_idx, 0u, fr.seed_hash);
+        b1 = cmj_block(n >> 4, image_idx, 1u, fr.seed_hash);
       }
       const bool alive = camera_ray(fr, rows.m[0], image_idx, xy & 0xffffu, xy >> 16, n, cmj_draw_in_block(b0, n), cmj_draw_in_block(b1, n), org, dir);
       RayPre rp;
@@ -396,31 +429,50 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(FrameDev fr, LayersDev la
       rp.inv = safe_reciprocal(dir);
       float tn;
       violated = violated || (alive && slab_test(rp, fr.scene_lo.x, fr.scene_lo.y, fr.scene_lo.z, fr.scene_hi.x, fr.scene_hi.y, fr.scene_hi.z, 1e9f, tn));
-      const f3 L = alive ? mk3(0.0f) + mk3(1.0f) * env_radiance(fr, dir) : mk3(0.0f);  // (k_generate: radiance of a path that ends at the scene bounds)
-      const f3 radiance = bad3(L) ? mk3(0.0f) : L;                                      // (k_accumulate: NaN guard, then the running means; a sky sample has no AOVs)
+      const f3 L = alive ? mk3(0.0f) + mk3(1.0f) * env_radiance<true>(fr, dir) : mk3(0.0f);  // (k_generate: radiance of a path that ends at the scene bounds)
+      const f3 radiance = bad3(L) ? mk3(0.0f) : L;                                            // (k_accumulate: NaN guard, then the running means; a sky sample has no AOVs)
       const float coef = 1.0f / (n_spp + 1.0f);
       const float fn = (float)n_spp;
       beauty = coef * (fn * beauty + radiance);
-      position = coef * (fn * position + mk3(0.0f));
-      normal = coef * (fn * normal + mk3(0.0f));
-      depth = coef * (fn * depth + 0.0f);
-      tcx = coef * (fn * tcx + 0.0f);
-      tcy = coef * (fn * tcy + 0.0f);
-      albedo = coef * (fn * albedo + mk3(0.0f));
       if constexpr (ADAPTIVE) moments_update(m.x, m.y, coef, fn, radiance);
       n_spp++;
     }
     if (violated) atomicAdd(violations, 1u);
-    if constexpr (ADAPTIVE) { ad.moments[image_idx] = m; n_taken += taken; issued[image_idx] = first + taken; }
-    else issued[image_idx] = first + n_samples;
+    if constexpr (ADAPTIVE) { adp->moments[image_idx] = m; n_taken += taken; }
+    issued[image_idx] = first + taken;
     layers.sample_count[image_idx] = n_spp;
     layers.beauty[image_idx] = mk4(beauty, 1.0f);
+    // the AOV means: `taken` updates with a sample that carries none
+    f3 position = mk3(layers.position[image_idx]), normal = mk3(layers.normal[image_idx]), albedo = mk3(layers.albedo[image_idx]);
+    float depth = layers.depth[image_idx];
+    const float4 tc4 = layers.texcoord[image_idx];
+    float tcx = tc4.x, tcy = tc4.y;
+    const uint32_t any_bits = __float_as_uint(position.x) | __float_as_uint(position.y) | __float_as_uint(position.z) | __float_as_uint(normal.x) | __float_as_uint(normal.y) |
+                              __float_as_uint(normal.z) | __float_as_uint(albedo.x) | __float_as_uint(albedo.y) | __float_as_uint(albedo.z) | __float_as_uint(depth) |
+                              __float_as_uint(tcx) | __float_as_uint(tcy);
+    if (any_bits != 0u) {
+      uint32_t n_aov = n_spp - taken;
+#pragma unroll 1
+      for (uint32_t k = 0; k < taken; ++k) {
+        const float coef = 1.0f / (n_aov + 1.0f);
+        const float fn = (float)n_aov;
+        position = coef * (fn * position + mk3(0.0f));
+        normal = coef * (fn * normal + mk3(0.0f));
+        depth = coef * (fn * depth + 0.0f);
+        tcx = coef * (fn * tcx + 0.0f);
+        tcy = coef * (fn * tcy + 0.0f);
+        albedo = coef * (fn * albedo + mk3(0.0f));
+        n_aov++;
+      }
+    }
     layers.position[image_idx] = mk4(position, 1.0f);
     layers.normal[image_idx] = mk4(normal, 1.0f);
     layers.depth[image_idx] = depth;
     layers.texcoord[image_idx] = make_float4(tcx, tcy, 0.0f, 1.0f);
     layers.albedo[image_idx] = mk4(albedo, 1.0f);
-  }  if constexpr (ADAPTIVE) {  // (one global atomic per workgroup)
+    }
+  }
+  if constexpr (ADAPTIVE) {  // (one global atomic per workgroup)
     __shared__ unsigned long long s_taken;
     if (threadIdx.x == 0u) s_taken = 0ull;
     __syncthreads();
@@ -516,6 +568,7 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_select(AdaptiveDev ad, cons
 template <bool COUNT, bool WIDE, bool ALPHA>
 __global__ void __launch_bounds__(kBlock) k_trace_closest_static(SceneDev sc, PoolDev pool, uint32_t depth, TraceCounters tc)
 {
+  pass_priority();
   const uint32_t* cnt = pool.counters + depth * kCounterStride;
   const uint32_t count = cnt[CNT_RAD];
   const uint32_t* q = pool.q_rad[depth & 1u];
@@ -546,6 +599,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_closest_static(SceneDev sc, Po
 template <bool COUNT, bool ALPHA>
 __global__ void __launch_bounds__(kBlock) k_trace_closest_coop(SceneDev sc, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush)
 {
+  pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
   __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
   const CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
@@ -668,6 +722,7 @@ template <bool COUNT, bool ALPHA>
 __global__ void __launch_bounds__(kBlock, COUNT ? 1 : FH_STREAM_BLOCKS_CLOSEST) k_trace_closest_stream(SceneDev sc, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays,
                                                                  StackSpill spill)
 {
+  pass_priority();
   __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
   const uint32_t count = pool.counters[depth * kCounterStride + CNT_RAD];
   if (stream_block_idle(count, min_rays)) return;
@@ -697,6 +752,7 @@ __global__ void __launch_bounds__(kBlock, COUNT ? 1 : FH_STREAM_BLOCKS_CLOSEST) 
 constexpr int kRouteChunks = 8;
 __global__ void __launch_bounds__(kBlock) k_route(SceneDev sc, PoolDev pool, uint32_t depth, uint32_t n_classes, unsigned long long* hit_counter)
 {
+  pass_priority();
   // A workgroup takes kRouteChunks x 256 consecutive entries per round and reserves its part of every class queue with ONE returning atomic per class: a class counter is one
   // address, the chip serves ~85 M returning atomics per address and second, and with 256 entries per atomic the 357 M closest hits of a configs[2] frame were 1.4 M atomics per
   // counter -- 16.4 ms of the kernel's 16.6 (profiles/README.md r4-20)
@@ -744,6 +800,7 @@ __global__ void __launch_bounds__(kBlock) k_route(SceneDev sc, PoolDev pool, uin
 // paths that leave the scene at depth 0 see the environment directly (pt.cu:504-523)
 __global__ void __launch_bounds__(kBlock) k_miss_primary(FrameDev fr, PoolDev pool)
 {
+  pass_priority();
   __shared__ HosekSky s_sky;
   stage_sky(fr, s_sky);
   __syncthreads();
@@ -1086,6 +1143,7 @@ FH_D void block_share(uint32_t n, uint32_t& lo, uint32_t& hi)
 
 __global__ void __launch_bounds__(kSortBlock) k_cell_hist(const uint32_t* count_ptr, const uint16_t* keys, uint32_t* hist)
 {
+  pass_priority();
   __shared__ uint32_t h[kCells];
   for (uint32_t b = threadIdx.x; b < kCells; b += kSortBlock) h[b] = 0u;
   __syncthreads();
@@ -1100,6 +1158,7 @@ __global__ void __launch_bounds__(kSortBlock) k_cell_hist(const uint32_t* count_
 // exclusive scan of the histogram into the cursors; the histogram is left zero for the next sort
 __global__ void __launch_bounds__(kSortBlock) k_cell_scan(uint32_t* hist, uint32_t* cursor)
 {
+  pass_priority();
   __shared__ uint32_t part[kSortBlock];
   constexpr uint32_t per = kCells / kSortBlock;
   uint32_t v[per], sum = 0;
@@ -1118,6 +1177,7 @@ __global__ void __launch_bounds__(kSortBlock) k_cell_scan(uint32_t* hist, uint32
 
 __global__ void __launch_bounds__(kSortBlock) k_cell_scatter(const uint32_t* count_ptr, const uint32_t* q_in, const uint16_t* keys, uint32_t* cursor, uint32_t* q_out)
 {
+  pass_priority();
   __shared__ uint32_t h[kCells];     // entries of this block per cell, then the running rank inside the block's range of that cell
   __shared__ uint32_t base[kCells];  // start of this block's range inside the cell's global range
   for (uint32_t b = threadIdx.x; b < kCells; b += kSortBlock) h[b] = 0u;
@@ -1140,6 +1200,7 @@ __global__ void __launch_bounds__(kSortBlock) k_cell_scatter(const uint32_t* cou
 template <uint32_t LOBES, int BLOCKS = FH_SHADE_BLOCKS>
 __global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : BLOCKS)) k_shade(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth)
 {
+  pass_priority();
   // (the grid is sized for every path of the pass; the blocks beyond this class's queue leave before they stage anything)
   if (blockIdx.x * blockDim.x >= pool.counters[depth * kCounterStride + CNT_CLS + cls]) return;
   __shared__ SobolRows<4> rows;
@@ -1242,6 +1303,7 @@ FH_D f3 resolve_light_ray(const SceneDev& sc, const FrameDev& fr, f3 T, float co
 template <bool COUNT, bool WIDE, bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock) k_trace_secondary_static(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc)
 {
+  pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
   __shared__ HosekSky s_sky;  // (light rays that escape see the sky: resolve_light_ray)
   if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
@@ -1291,6 +1353,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_secondary_static(SceneDev sc, 
 template <bool COUNT, bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? 5 : 6)) k_trace_secondary_coop(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush)
 {
+  pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
   __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
   const CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
@@ -1421,6 +1484,7 @@ struct SecondaryStream {
 template <bool COUNT, bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS))) k_trace_secondary_stream(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill)
 {
+  pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
   __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
   const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
@@ -1494,6 +1558,7 @@ struct MergedStream {
 template <bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock, LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS)) k_trace_merged_stream(SceneDev sc, FrameDev fr, PoolDev ps, PoolDev pn, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill)
 {
+  pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];
   __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
   const uint32_t n_sec = ps.counters[depth * kCounterStride + CNT_SEC], n_closest = ps.counters[(depth + 1u) * kCounterStride + CNT_RAD];
@@ -1546,6 +1611,7 @@ struct TailRay { bool has = false; bool any = true; f3 o = mk3(0.0f), d = mk3(0.
 template <uint32_t LOBES>
 __global__ void __launch_bounds__(kBlock, LOBES == L_ALL ? 1 : 2) k_tail(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t first_depth, uint32_t coop_flush)
 {
+  pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // traversal stack of every lane ([entry][thread], as in the streaming kernels): a private array lands in scratch
   __shared__ __attribute__((aligned(16))) unsigned char lds_coop[(kBlock / 64) * kCoopLdsBytesPerWave];
   __shared__ float4 s_in[kBlock / 64][2][64];  // one round of packed rays of a wave: (origin, tmax), (direction, stops at its first hit)
@@ -1705,6 +1771,7 @@ template <bool QUIRK, bool ADAPTIVE = false>
 __global__ void __launch_bounds__(kBlock) k_accumulate(PoolDev pool, LayersDev layers, const uint32_t* owned, uint32_t n_owned, uint32_t n_batch,
                                                      std::conditional_t<ADAPTIVE, float2, float4>* carry)
 {
+  pass_priority();
   static_assert(!(QUIRK && ADAPTIVE), "FH_FLAG_REFERENCE_FIRSTHIT does not combine with adaptive sampling");
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_owned; i += gridDim.x * blockDim.x) {
     const uint32_t image_idx = owned[i];
@@ -2351,16 +2418,44 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   // a serial kernel trace shows the kernel's work instead of the time a starved background kernel was resident)
   hipStream_t sky_st = ((ctx->flags & FH_FLAG_SERIAL_PASSES) != 0 || ctx->n_slots == 1) ? ctx->stream : ctx->sky_stream;
   if (n_sky && sky_st != ctx->stream) FH_HIP(hipStreamWaitEvent(sky_st, ctx->ev_enter, 0));
-  if (n_sky && !guard_blocks) {  // the sky pixels of this call, all samples at once, on a stream of their own next to the passes (they share no pixel with them)
-    Span sp(ctx, sky_st, 4);
-    uint32_t sky_grid = grid_for(n_sky);
-    if (ctx->tun.sky_blocks_per_cu && sky_grid > ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu) sky_grid = ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu;
-    if (adaptive) {  // (the samples it takes are counted on the device: fh_sync adds them to the stats)
-      hipLaunchKernelGGL(k_sky_pixels<true>, dim3(sky_grid), dim3(kBlock), 0, sky_st, fr, L, ctx->d_sample_issued, ctx->d_split[2], ctx->d_split[3], n_sky, n_samples,
-                         (const SkyAdaptive*)ctx->d_sky_adaptive);
-      ctx->sky_taken_pending = true;
-    } else {
-      hipLaunchKernelGGL(k_sky_pixels<false>, dim3(sky_grid), dim3(kBlock), 0, sky_st, fr, L, ctx->d_sample_issued, ctx->d_split[2], ctx->d_split[3], n_sky, n_samples, ctx->d_split_counters + 2);
+  // A list of sky pixels is rendered by two launches of k_sky_pixels that pull groups of 64 pixels from one cursor.  The FILLER, a small fixed grid (FH_SKY_BLOCKS workgroups
+  // per CU) on the sky stream, starts with the passes and runs in the issue slots their kernels leave idle: one wave of 80 registers beside six traversal waves per SIMD, at
+  // wave priority 0 under the pass kernels' 1 (pass_priority).  The DRAIN, a grid that fills the machine, goes to the main stream behind the last pass of the call (or of the
+  // round) and finishes at full rate whatever the filler did not reach -- a call whose passes are short loses nothing to the filler's small grid.  Neither waits for the
+  // other: a group belongs to the wave that claimed it.  In line on the main stream (sky_st == ctx->stream) one launch does it all.
+  struct SkyDrain { const uint32_t* px; const uint32_t* xy; uint32_t n, n_samples; bool pending; } sky_drain{nullptr, nullptr, 0u, 0u, false};
+  uint32_t* const sky_cursor = ctx->d_split_counters + 3;
+  const uint32_t sky_filler_wgs = sky_st == ctx->stream ? 0u : (ctx->tun.sky_filler_grid ? ctx->tun.sky_filler_grid : ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu);
+  auto sky_launch = [&](hipStream_t s, uint32_t wgs, const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t ns) {
+    Span sp(ctx, s, 4);
+    const uint32_t full = (n + kBlock - 1u) / kBlock;  // (one group per wave)
+    const uint32_t grid = wgs < full ? wgs : full;
+    if (adaptive) hipLaunchKernelGGL(k_sky_pixels<true>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, (const SkyAdaptive*)ctx->d_sky_adaptive, sky_cursor);
+    else hipLaunchKernelGGL(k_sky_pixels<false>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, ctx->d_split_counters + 2, sky_cursor);
+  };
+  const uint32_t sky_full_wgs = ctx->tun.n_cus * (uint32_t)kSkyWaves;  // (every workgroup resident: the cursor balances them)
+  // (the caller has ordered the main stream behind every earlier launch that used the cursor)
+  auto sky_begin = [&](const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t ns) -> int {
+    FH_HIP(hipMemsetAsync(sky_cursor, 0, 4, ctx->stream));
+    if (sky_st == ctx->stream) { sky_launch(sky_st, sky_full_wgs, px, xy, n, ns); return FH_OK; }
+    if (sky_filler_wgs) {
+      FH_HIP(hipEventRecord(ctx->ev_sky_cursor, ctx->stream));
+      FH_HIP(hipStreamWaitEvent(sky_st, ctx->ev_sky_cursor, 0));
+      sky_launch(sky_st, sky_filler_wgs, px, xy, n, ns);
+    }
+    sky_drain = SkyDrain{px, xy, n, ns, true};
+    return FH_OK;
+  };
+  auto sky_end = [&]() {  // on the main stream, which the caller has ordered behind the passes the launch is to follow
+    if (!sky_drain.pending) return;
+    sky_launch(ctx->stream, sky_full_wgs, sky_drain.px, sky_drain.xy, sky_drain.n, sky_drain.n_samples);
+    sky_drain.pending = false;
+  };
+  if (n_sky && !guard_blocks) {  // the sky pixels of this call, all samples at once (they share no pixel with the passes)
+    const int rc = sky_begin(ctx->d_split[2], ctx->d_split[3], n_sky, n_samples);
+    if (rc) return rc;
+    if (adaptive) ctx->sky_taken_pending = true;  // (the samples it takes are counted on the device: fh_sync adds them to the stats)
+    else {
       ctx->stats.paths += (uint64_t)n_sky * n_samples;
       ctx->stats.sky_pixel_samples += (uint64_t)n_sky * n_samples;
     }
@@ -2444,8 +2539,13 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
     if (stream && reported && reported < w) w = reported;
     return w;
   };
-  const uint32_t wgs_closest = wgs_for(stream_stack_bytes, static_lds_closest, FH_STREAM_BLOCKS_CLOSEST, ctx->occupancy_blocks);
-  const uint32_t wgs_secondary = wgs_for(stream_stack_bytes_secondary, static_lds_secondary, FH_STREAM_BLOCKS > FH_SECONDARY_BLOCKS_HEAVY ? FH_STREAM_BLOCKS : FH_SECONDARY_BLOCKS_HEAVY, ctx->occupancy_blocks_secondary);
+  // With a filler wave on every SIMD a seventh traversal workgroup per CU has no registers to go to: it would wait for one of the six to end and start as a straggler of a
+  // persistent launch.  The passes of a call that started a filler are launched with six per CU (the compiled budget, FH_STREAM_BLOCKS, stays).
+  const uint32_t wgs_cap = n_sky && sky_filler_wgs ? (uint32_t)FH_STREAM_BLOCKS_FILLER : 0xffffu;
+  uint32_t wgs_closest = wgs_for(stream_stack_bytes, static_lds_closest, FH_STREAM_BLOCKS_CLOSEST, ctx->occupancy_blocks);
+  uint32_t wgs_secondary = wgs_for(stream_stack_bytes_secondary, static_lds_secondary, FH_STREAM_BLOCKS > FH_SECONDARY_BLOCKS_HEAVY ? FH_STREAM_BLOCKS : FH_SECONDARY_BLOCKS_HEAVY, ctx->occupancy_blocks_secondary);
+  if (wgs_closest > wgs_cap) wgs_closest = wgs_cap;
+  if (wgs_secondary > wgs_cap) wgs_secondary = wgs_cap;
   const uint32_t stream_grid = tun.n_cus * wgs_closest;
   const uint32_t stream_grid_secondary = tun.n_cus * wgs_secondary;
   // spill area of the streaming launches: [launch in flight: pass slot x (closest, secondary)][entry beyond the LDS part][thread of the launch]
@@ -2489,17 +2589,15 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
     const uint32_t to_boundary = ctx->adapt_growth == 1u ? ctx->adapt.step - ctx->adapt_total % ctx->adapt.step : adaptive_to_boundary(ctx);
     if (n_round > to_boundary) n_round = to_boundary;
     if (ran && last_slot != 0) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
+    if (guard_blocks) sky_end();  // (the round's own sky launch: the next selection reads what it writes)
     if (sky_ran && sky_st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky_st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
     const int rc = guard_blocks && n_sky ? adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px, ctx->d_split[2], ctx->d_split[3], n_sky, &n_sky_round)
                                          : adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px);
     if (rc) return rc;
     px_list = ctx->d_active[0]; xy_list = ctx->d_active[1];
-    if (n_sky_round) {  // (the selection has been waited for: nothing else orders this launch)
-      Span sp(ctx, sky_st, 4);
-      uint32_t sky_grid = grid_for(n_sky_round);
-      if (ctx->tun.sky_blocks_per_cu && sky_grid > ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu) sky_grid = ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu;
-      hipLaunchKernelGGL(k_sky_pixels<true>, dim3(sky_grid), dim3(kBlock), 0, sky_st, fr, L, ctx->d_sample_issued, ctx->d_active[2], ctx->d_active[3], n_sky_round, n_round,
-                         (const SkyAdaptive*)ctx->d_sky_adaptive);
+    if (n_sky_round) {  // (the selection has been waited for, and with it the drain of the round before)
+      const int rc2 = sky_begin(ctx->d_active[2], ctx->d_active[3], n_sky_round, n_round);
+      if (rc2) return rc2;
       ctx->sky_taken_pending = true;
       sky_ran = true;
     }
@@ -2756,6 +2854,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   // join: later work on the main stream (pack, post-process, copies, the caller's clears) sees every pass of this call
   // (the accumulates form a chain across the streams, so the last one implies all the others)
   if (last_slot != 0 && ran) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
+  sky_end();
   if (n_sky && sky_st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky_st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
   FH_HIP(hipGetLastError());
   return FH_OK;
