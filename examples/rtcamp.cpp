@@ -8,6 +8,8 @@
 //                                                                    until no pixel is active; prints the frame's mean spp)
 //          [--adaptive-block G --adaptive-growth K]   (with --noise-threshold: G x G pixel blocks (1, 2, 4, 8) stop together; K = 2 tests at M, 2M, 4M ... only,
 //                                                       and the frame renders in calls that end on those boundaries)
+//          [--denoiser atrous|guided]   (atrous, the default: fh_denoise; guided: the variance-guided filter on the position and depth layers too, and on the
+//                                         luminance moments and sample counts whenever --noise-threshold is on)
 //          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
 #include <chrono>
 #include <cmath>
@@ -38,6 +40,7 @@ int main(int argc, char** argv)
   bool bloom = false, sun = false, sky = false, reference_launches = false;
   float noise_threshold = -1.0f;  // --noise-threshold T: adaptive sampling, --spp becomes the per-pixel cap
   int min_spp = 64, adaptive_step = 16, adaptive_block = 1, adaptive_growth = 1;
+  std::string denoiser_name = "atrous";  // --denoiser
   std::vector<int> devices;  // --devices: empty = FH_DEVICES, or device 0
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -63,22 +66,25 @@ int main(int argc, char** argv)
     else if (a == "--adaptive-step") adaptive_step = std::atoi(next());
     else if (a == "--adaptive-block") adaptive_block = std::atoi(next());
     else if (a == "--adaptive-growth") adaptive_growth = std::atoi(next());
+    else if (a == "--denoiser") denoiser_name = next();
     else if (a == "--devices") {
       try { devices = cwl::parse_device_list(next(), "--devices"); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--devices 0,1,...]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   if (adaptive_block != 1 && adaptive_block != 2 && adaptive_block != 4 && adaptive_block != 8) { std::fprintf(stderr, "--adaptive-block must be 1, 2, 4 or 8\n"); return 2; }
   if (adaptive_growth != 1 && adaptive_growth != 2) { std::fprintf(stderr, "--adaptive-growth must be 1 or 2\n"); return 2; }
+  if (denoiser_name != "atrous" && denoiser_name != "guided") { std::fprintf(stderr, "--denoiser must be atrous or guided\n"); return 2; }
+  const bool guided = denoiser_name == "guided";
   const float time_step = 1.0f / fps;
   try {
     std::filesystem::create_directories(out_dir);
     if (!devices.empty()) cwl::check(nullptr, cwl::create_context(devices, &cwl::default_context()), "--devices");  // (before anything asks for the process-wide context)
     optwl::Context context;
     fredholm::Renderer renderer(context.get_context());
-    renderer.set_gather_layers(FH_LAYER_BEAUTY | FH_LAYER_NORMAL | FH_LAYER_ALBEDO);  // what the denoise / post / PNG chain below reads (a plain context ignores it)
+    renderer.set_gather_layers(FH_LAYER_BEAUTY | FH_LAYER_NORMAL | FH_LAYER_ALBEDO | (guided ? FH_LAYER_POSITION | FH_LAYER_DEPTH : 0u));  // what the denoise / post / PNG chain below reads (a plain context ignores it)
     if (renderer.group_size() > 1) std::printf("rendering on a group of %u members\n", renderer.group_size());
     renderer.create_module("pt.ptx");
     renderer.create_program_group();
@@ -106,6 +112,12 @@ int main(int argc, char** argv)
     camera.m_F = F;
     camera.m_focus = focus;
     cwl::CUDABuffer<uint32_t> sample_counts(n_px);  // (--noise-threshold: the per-pixel counts a frame ends with)
+    cwl::CUDABuffer<float2> luminance_moments(guided && noise_threshold >= 0.0f ? n_px : 1);  // (and, for the guided denoiser, the moments they go with)
+    if (guided) {
+      denoiser.set_mode(fredholm::Denoiser::Guided);
+      if (noise_threshold >= 0.0f) denoiser.set_guides(layer_position.get_device_ptr(), layer_depth.get_device_ptr(), luminance_moments.get_device_ptr(), sample_counts.get_device_ptr());
+      else denoiser.set_guides(layer_position.get_device_ptr(), layer_depth.get_device_ptr());
+    }
     fredholm::RenderLayer render_layer{layer_beauty.get_device_ptr(), layer_position.get_device_ptr(), layer_depth.get_device_ptr(), layer_normal.get_device_ptr(),
                                        layer_texcoord.get_device_ptr(), layer_albedo.get_device_ptr()};
     if (sun) renderer.set_directional_light(make_float3(20, 20, 20), make_float3(-0.1f, 1, 0.1f), 1.0f);  // rtcamp8.cpp:133-134
@@ -141,6 +153,7 @@ int main(int argc, char** argv)
               if (done < n_spp && renderer.active_pixel_count() == 0) break;
             }
             renderer.get_sample_counts(sample_counts);
+            if (guided) renderer.get_luminance_moments(luminance_moments);
             std::vector<uint32_t> counts;
             sample_counts.copy_from_device_to_host(counts);
             double sum = 0.0;

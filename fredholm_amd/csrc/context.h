@@ -232,6 +232,10 @@ struct fh_ctx {
   // denoiser slot (post.hip): ping-pong buffers of the a-trous filter
   float4* d_denoise_tmp[2] = {nullptr, nullptr};
   size_t denoise_pixels = 0;
+  // variance-guided denoiser (denoise.hip): ping-pong (colour, variance) images and dense variance planes
+  float4* d_guided_cv[2] = {nullptr, nullptr};
+  float* d_guided_var[2] = {nullptr, nullptr};
+  size_t guided_pixels = 0;
 
   // stats
   fh_stats stats{};
@@ -290,4 +294,5 @@ void pool_release(fh_ctx* ctx);
 int kernel_info(fh_ctx* ctx, int which, uint32_t out[6]);   // render.hip
 int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int w, int h, const fh_post_params* pp, float* out);  // post.hip
 int denoise_submit(fh_ctx* ctx, int w, int h, const float* beauty, const float* normal, const float* albedo, float* out, int upscale);  // post.hip
+int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* params, float* out, int upscale);  // denoise.hip (arguments checked by the caller)
 }  // namespace fh

@@ -112,6 +112,7 @@ EXPORTS = [
     "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
     "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued",
     "fh_set_adaptive_policy", "fh_get_adaptive_policy", "fh_adaptive_next_boundary",
+    "fh_denoise_guided",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -119,6 +120,17 @@ EXPORTS = [
 class AdaptiveParamsC(C.Structure):
     """fh_adaptive_params (include/fredholm_hip.h)"""
     _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32), ("step", C.c_uint32)]
+
+
+class DenoiseInputsC(C.Structure):
+    """fh_denoise_inputs (include/fredholm_hip.h): device pointers"""
+    _fields_ = [("beauty", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p), ("moments", C.c_void_p),
+                ("counts", C.c_void_p)]
+
+
+class DenoiseParamsC(C.Structure):
+    """fh_denoise_params (include/fredholm_hip.h); the defaults are the library's (params == NULL)"""
+    _fields_ = [("sigma_l", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("normal_power_log2", C.c_uint32), ("passes", C.c_uint32)]
 
 
 # argument types of the entry points declared with them (the adaptive-sampling ABI); every entry point returns int
@@ -132,6 +144,7 @@ SIGNATURES = {
     "fh_get_adaptive_policy": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "fh_adaptive_next_boundary": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_kat_set_issued": [C.c_void_p, C.c_void_p, C.c_uint32],
+    "fh_denoise_guided": [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputsC), C.POINTER(DenoiseParamsC), C.c_void_p, C.c_int],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_ctx_member": [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)],

@@ -519,6 +519,15 @@ class Renderer:
         self._ck(N.lib().fh_denoise(self._ctx, C.c_uint32(int(width)), C.c_uint32(int(height)), C.c_void_p(beauty_ptr), C.c_void_p(normal_ptr), C.c_void_p(albedo_ptr),
                                     C.c_void_p(denoised_ptr), int(bool(upscale))), "fh_denoise")
 
+    def denoise_guided(self, width, height, beauty_ptr, normal_ptr, albedo_ptr, denoised_ptr, position_ptr=None, depth_ptr=None, moments_ptr=None, counts_ptr=None,
+                       sigma_l=2.0, sigma_z=1.0, sigma_a=0.2, normal_power_log2=7, passes=5, upscale=False):
+        """the variance-guided denoiser (fh_denoise_guided): an a-trous filter whose colour edge stop is each pixel's own standard deviation, from the luminance
+        moments and sample counts of adaptive sampling (moments_ptr, counts_ptr: device copies made with get_luminance_moments / get_sample_counts) or, without
+        them, from a 7x7 spatial estimate.  position_ptr and depth_ptr add the plane edge stop.  All pointers are device pointers; pairs go together."""
+        i = N.DenoiseInputsC(beauty_ptr, normal_ptr, albedo_ptr, position_ptr, depth_ptr, moments_ptr, counts_ptr)
+        p = N.DenoiseParamsC(float(sigma_l), float(sigma_z), float(sigma_a), int(normal_power_log2), int(passes))
+        self._ck(N.lib().fh_denoise_guided(self._ctx, int(width), int(height), C.byref(i), C.byref(p), C.c_void_p(denoised_ptr), int(bool(upscale))), "fh_denoise_guided")
+
     # -- parity-test hooks
     def measure_bandwidth(self, nbytes=1 << 30, iters=8):
         """(read GB/s, copy GB/s) of this GPU's HBM, measured with streaming kernels (fh_measure_bandwidth)"""

@@ -3,8 +3,13 @@
 // constructor / denoise() / wait_for_completion() surface the applications call (app/controller.cpp:70-78,232-236, app/rtcamp8.cpp:120-128,191-196)
 // and runs the library's guided filter in its place: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on albedo-demodulated
 // radiance, steered by the same normal and albedo layers (fh_denoise).  Output size follows the reference: 2 x width by 2 x height when `upscale`.
+// Beyond the reference: set_mode(Denoiser::Guided) runs the variance-guided filter (fh_denoise_guided) on the same layers plus whatever set_guides() was given --
+// position and depth for the plane edge stop, the luminance moments and sample counts of adaptive sampling for the colour edge stop.  An application that is
+// not edited gets it with the environment variable FH_DENOISER=guided (read by the constructor; set_mode wins).
 #pragma once
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 #include "../cwl/util.h"
 #include "types.h"
@@ -17,10 +22,26 @@ class Denoiser
   Denoiser(fh_ctx* context, uint32_t width, uint32_t height, const float4* d_beauty, const float4* d_normal, const float4* d_albedo, const float4* d_denoised, bool upscale = false)
       : m_context(context), m_width(width), m_height(height), m_d_beauty(d_beauty), m_d_normal(d_normal), m_d_albedo(d_albedo), m_d_denoised(const_cast<float4*>(d_denoised)), m_upscale(upscale)
   {
+    const char* env = std::getenv("FH_DENOISER");
+    if (env && std::strcmp(env, "guided") == 0) m_mode = Guided;
+  }
+  enum Mode { Atrous, Guided };
+  void set_mode(Mode mode) { m_mode = mode; }
+  Mode mode() const { return m_mode; }
+  // device pointers of width * height elements; position and depth go together, moments and counts go together, either pair may be null
+  void set_guides(const float4* d_position, const float* d_depth, const float2* d_moments = nullptr, const uint32_t* d_counts = nullptr)
+  {
+    m_d_position = d_position; m_d_depth = d_depth; m_d_moments = d_moments; m_d_counts = d_counts;
   }
   void denoise()
   {
     fh_ctx* ctx = m_context ? m_context : cwl::require_context();
+    if (m_mode == Guided) {
+      const fh_denoise_inputs in = {reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
+                                    reinterpret_cast<const float*>(m_d_position), m_d_depth, reinterpret_cast<const float*>(m_d_moments), m_d_counts};
+      cwl::check(ctx, fh_denoise_guided(ctx, m_width, m_height, &in, nullptr, reinterpret_cast<float*>(m_d_denoised), m_upscale ? 1 : 0), "fh_denoise_guided");
+      return;
+    }
     cwl::check(ctx, fh_denoise(ctx, m_width, m_height, reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
                                reinterpret_cast<float*>(m_d_denoised), m_upscale ? 1 : 0),
                "fh_denoise");
@@ -35,5 +56,10 @@ class Denoiser
   const float4* m_d_albedo;
   float4* m_d_denoised;
   bool m_upscale;
+  Mode m_mode = Atrous;
+  const float4* m_d_position = nullptr;
+  const float* m_d_depth = nullptr;
+  const float2* m_d_moments = nullptr;
+  const uint32_t* m_d_counts = nullptr;
 };
 }  // namespace fredholm

@@ -293,6 +293,42 @@ int fh_post_process(fh_ctx* ctx, const float* beauty_in, float* beauty_high_lumi
  * width x height pixels in, float4 denoised out (2*width x 2*height when upscale2x, by pixel replication).  Asynchronous on the context stream. */
 int fh_denoise(fh_ctx* ctx, uint32_t width, uint32_t height, const float* beauty, const float* normal, const float* albedo, float* denoised, int upscale2x);
 
+/* -- the variance-guided denoiser (an extension beyond the reference; opt-in, fh_denoise keeps its bits): the spatial filter of SVGF (Schied et al. 2017) on
+ * albedo-demodulated radiance.  Its colour edge stop divides the luminance distance by the standard deviation each pixel is measured to have -- from the moments
+ * adaptive sampling keeps, or without them from a 7x7 spatial estimate -- and the variance is filtered along with the colour.
+ * All arithmetic is fp32 without contraction, exp is fhe_exp (fh_elementary.h), sqrt and / are correctly rounded, sums run over dy (outer) and dx (inner) ascending.
+ * lum(r, g, b) = r * 0.2126729 + g * 0.7151522 + b * 0.0721750 (the luminance of the moments); finite(v) = 0 for NaN and |v| > 3e38, else v; B, N, A, P, Z, (m1, m2), n
+ * are the inputs at a pixel; q is the tap position clamped to the frame.
+ *   Preparation, per pixel p: a' = max(A.rgb, 0.01), c = finite(B.rgb) / a', l = lum(c).  Variance v of l
+ *     with moments:    n >= 2: v = max(m2 - m1 * m1, 0) / (n - 1) * (r * r), r = l / max(m1, 1e-3);   n < 2: v = l * l
+ *     without moments: over the 7 x 7 window, wn = max(0, N_p . N_q) squared normal_power_log2 times:  S = max(sum wn, 1e-6), S1 = (sum wn * l_q) / S,
+ *                      S2 = (sum wn * (l_q * l_q)) / S, v = max(S2 - S1 * S1, 0)
+ *   Pass i = 0 .. passes - 1, hole s = 2^i, on (c, v) of the pass before, l = lum(c):
+ *     g = sum over the dense 3 x 3 neighbours of b * v_q, b = (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4);  sd = sigma_l * sqrt(g) + 1e-6
+ *     for (dx, dy) in [-2, 2]^2: q = p + s * (dx, dy), h = k[|dx|] * k[|dy|], k = (3/8, 1/4, 1/16); the centre tap has w = 9/64, every other tap
+ *       w = h * wn * exp(-((e_z + e_a) + e_l)),  e_l = |l_q - l_p| / sd,  e_a = |A_q - A_p|^2 / (sigma_a * sigma_a),
+ *       e_z = |N_p . (P_q - P_p)| / (sigma_z * 0.01 * max(Z_p, 1e-3) * s * sqrt(dx * dx + dy * dy) + 1e-6), or 0 without position
+ *     c' = (sum w * c_q) / (sum w),  v' = (sum (w * w) * v_q) / ((sum w) * (sum w))
+ *   Output: (c * a', 1) after the last pass; 2 * width x 2 * height by pixel replication when upscale2x.
+ * A pixel whose normal is 0 (a miss) takes no neighbour and keeps its beauty up to the rounding of the demodulation; no other pixel takes from it either. */
+typedef struct fh_denoise_inputs { /* device pointers, width * height elements each */
+  const float* beauty;    /* float4, required */
+  const float* normal;    /* float4, required */
+  const float* albedo;    /* float4, required */
+  const float* position;  /* float4, or NULL */
+  const float* depth;     /* float, or NULL; position and depth are given together or not at all */
+  const float* moments;   /* float2 (m1, m2) as fh_get_luminance_moments fills it, or NULL */
+  const uint32_t* counts; /* as fh_get_sample_counts fills it; given together with moments or not at all */
+} fh_denoise_inputs;
+typedef struct fh_denoise_params {
+  float sigma_l, sigma_z, sigma_a;
+  uint32_t normal_power_log2, passes;
+} fh_denoise_params;
+/* params == NULL: sigma_l 2, sigma_z 1, sigma_a 0.2, normal_power_log2 7, passes 5.  FH_E_INVALID, decided from the arguments alone before anything is touched,
+ * for a sigma that is not finite or <= 0, normal_power_log2 > 10, passes outside 1..6, a missing required pointer, or half a pair.  Asynchronous on the
+ * context stream like fh_denoise; on a group it runs on the lead.  The scratch images live in the context and grow on demand. */
+int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* inputs, const fh_denoise_params* params, float* denoised, int upscale2x);
+
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */
 int fh_gl_register_buffer(fh_ctx* ctx, unsigned int gl_buffer, void** resource, void** device_ptr, uint64_t* bytes);
