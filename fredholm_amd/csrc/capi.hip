@@ -13,6 +13,7 @@
 #include "context.h"
 #include "fh_bsdf.h"
 #include "fh_trace.h"
+#include "temporal_host.h"
 
 // generated at build time from fredholm_amd/data/*.{u32,f32} by tools/gen_tables_inc.py
 #include "gen/tables.inc"
@@ -618,7 +619,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
   void* ptrs[] = {ctx->d_sample_issued, ctx->d_sobol, ctx->d_sobol_bytes, ctx->d_alpha_rec, ctx->d_lut_refl, ctx->d_lut_sheen, ctx->d_face_rec, ctx->d_face_cls, ctx->d_materials, ctx->d_lights, ctx->d_bvh2_nodes, ctx->d_bvh2_tris,
                   ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_sample_count, ctx->d_owned, ctx->d_trace_counters, ctx->d_texels, ctx->d_textures, ctx->d_srgb_lut, ctx->d_ibl,
                   ctx->d_bloom_weights, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
-                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
+                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hist_cv[0], ctx->d_hist_cv[1], ctx->d_hist_ph[0], ctx->d_hist_ph[1], ctx->d_hist_n[0], ctx->d_hist_n[1], ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
                   ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active[2], ctx->d_active[3], ctx->d_block_marks, ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1277,21 +1278,47 @@ int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_den
 {
   const fh_denoise_params defaults = {2.0f, 1.0f, 0.2f, 7u, 5u};
   const fh_denoise_params pr = params ? *params : defaults;
-  auto bad_sigma = [](float s) { return !(s > 0.0f) || !std::isfinite(s); };
-  const char* why = nullptr;
-  if (!in || !denoised) why = "null argument";
-  else if (!in->beauty || !in->normal || !in->albedo) why = "the beauty, normal and albedo layers are required";
-  else if ((in->position == nullptr) != (in->depth == nullptr)) why = "position and depth are given together or not at all";
-  else if ((in->moments == nullptr) != (in->counts == nullptr)) why = "moments and counts are given together or not at all";
-  else if (width == 0 || height == 0 || width > 32768 || height > 32768) why = "width and height must be in 1..32768";
-  else if (bad_sigma(pr.sigma_l) || bad_sigma(pr.sigma_z) || bad_sigma(pr.sigma_a)) why = "sigma_l, sigma_z and sigma_a must be finite and > 0";
-  else if (pr.normal_power_log2 > 10) why = "normal_power_log2 must be at most 10";
-  else if (pr.passes < 1 || pr.passes > 6) why = "passes must be in 1..6";
-  else if (!ctx) why = "null context";
+  const char* why = guided_refusal(width, height, in, pr, denoised);
+  if (!why && !ctx) why = "null context";
   if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_guided: ") + why);
   FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   return denoise_guided_submit(ctx, (int)width, (int)height, in, &pr, denoised, upscale2x ? 1 : 0);
+}
+
+// fh_denoise_guided with the temporal stage in front of its passes; refusals as there (temporal_host.h)
+int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const fh_temporal_params* temporal,
+                        const fh_denoise_params* params, float* denoised, int upscale2x)
+{
+  const fh_denoise_params defaults = {2.0f, 1.0f, 0.2f, 7u, 5u};
+  const fh_temporal_params temporal_defaults = {0.2f, 32.0f, 0.5f, 0.02f};
+  const fh_denoise_params pr = params ? *params : defaults;
+  const fh_temporal_params tp = temporal ? *temporal : temporal_defaults;
+  float w2c[12], inv_tan = 0.0f;
+  const char* why = temporal_refusal(width, height, in, camera, tp, pr, denoised, w2c, &inv_tan);
+  if (!why && !ctx) why = "null context";
+  if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_temporal: ") + why);
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
+}
+
+int fh_denoise_history_reset(fh_ctx* ctx)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;  // (the buffers stay: the next call overwrites them without reading)
+  return FH_OK;
+}
+
+int fh_denoise_history_info(fh_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* frames)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (width) *width = ctx->hist_w;
+  if (height) *height = ctx->hist_h;
+  if (frames) *frames = ctx->hist_frames;
+  return FH_OK;
 }
 
 // OpenGL interop (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143: cuGraphicsGLRegisterBuffer + map + mapped pointer, unmapped and

@@ -236,6 +236,17 @@ struct fh_ctx {
   float4* d_guided_cv[2] = {nullptr, nullptr};
   float* d_guided_var[2] = {nullptr, nullptr};
   size_t guided_pixels = 0;
+  // temporal accumulation (denoise.hip: fh_denoise_temporal): the history, double buffered -- per pixel (c_acc.rgb, v_acc), (P, h) and N -- with the camera of the
+  // call that wrote buffer `hist_cur`, that camera's world-to-camera rows and its cam_inv_tan.  hist_frames = 0: there is no history.
+  float4* d_hist_cv[2] = {nullptr, nullptr};
+  float4* d_hist_ph[2] = {nullptr, nullptr};
+  float4* d_hist_n[2] = {nullptr, nullptr};
+  size_t hist_pixels = 0;
+  uint32_t hist_w = 0, hist_h = 0, hist_frames = 0;
+  int hist_cur = 0;
+  fh_camera hist_camera{};
+  float hist_w2c[12] = {};
+  float hist_inv_tan = 0.0f;
 
   // stats
   fh_stats stats{};
@@ -295,4 +306,7 @@ int kernel_info(fh_ctx* ctx, int which, uint32_t out[6]);   // render.hip
 int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int w, int h, const fh_post_params* pp, float* out);  // post.hip
 int denoise_submit(fh_ctx* ctx, int w, int h, const float* beauty, const float* normal, const float* albedo, float* out, int upscale);  // post.hip
 int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* params, float* out, int upscale);  // denoise.hip (arguments checked by the caller)
+// denoise.hip (arguments checked by the caller); w2c, inv_tan: `cam` inverted and its cam_inv_tan, kept with the history this call writes
+int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
+                            const fh_denoise_params* params, float* out, int upscale);
 }  // namespace fh

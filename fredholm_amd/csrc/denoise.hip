@@ -12,9 +12,13 @@
 // float4 per tap from global memory.  A 16-lane group of ds_read_b128 (MI355X: lanes {0-3, 12-15, 20-27} and so on) lies within one 32-pixel row of the tile
 // and reads 16 consecutive float4: all 64 banks once, whatever the row pitch.  The variance also lives in a float plane of its own: the 3x3 prefilter reads
 // DENSE neighbours, which the lattice does not hold.
+//
+// fh_denoise_temporal runs the same preparation and the same passes with one launch between them, k_temporal below: the frame's (c, v) blended with the context's
+// history of the frames before it, found again through the world position and the previous call's camera.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstring>
 
 #include "context.h"
 #include "fh_tonemap.h"
@@ -229,13 +233,105 @@ void launch_pass(const GuidedArgs& a, bool last, dim3 grid, hipStream_t st)
   else hipLaunchKernelGGL((k_guided_pass<POS, false, NP>), grid, dim3(kTW, kTH), 0, st, a);
 }
 
+// ---- the temporal stage of fh_denoise_temporal (include/fredholm_hip.h states it operation by operation): one streaming launch between the preparation and the passes.
+// A pixel reads its own (c, v), N, P, Z, looks its history up -- at itself when the camera stood still, else at the 2 x 2 taps around where the previous camera saw
+// P -- blends, and writes the new history, which is also what the first pass reads.  32 x 8 pixels per workgroup like the passes: a wave is two rows of 32, whose taps
+// after a small camera step are again two or three rows of neighbouring 16-byte elements in each of the three history images.
+struct TemporalArgs {
+  const float4* cv;       // (c.rgb, v) of the preparation
+  const float4* normal;
+  const float4* position;
+  const float* depth;
+  const float4* h_cv;     // the history read (MODE != 0): (c_acc.rgb, v_acc)
+  const float4* h_ph;     // (P, h)
+  const float4* h_n;      // N
+  float4* o_cv;           // the history written; o_cv is the (c, v) image of the first pass
+  float4* o_ph;
+  float4* o_n;
+  float* vplane;          // v_acc, dense, for the first pass
+  int w, h;
+  float m[12];            // world-to-camera rows of the camera the history was written with
+  float f, W, H;          // its cam_inv_tan; width and height as floats
+  float alpha_min, max_history, cos_min, plane_tol;
+};
+
+__device__ __forceinline__ bool td_hit(const float4 n) { return n.x != 0.0f || n.y != 0.0f || n.z != 0.0f; }
+// the two stops of a history tap (its normal nq and position ph.xyz) seen from the pixel (np, pp); lim = plane_tol * max(Z_p, 1e-3)
+__device__ __forceinline__ bool td_valid(const TemporalArgs& A, const float4 np, const float4 pp, float lim, const float4 nq, const float4 ph)
+{
+  const float dn = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+  const float dx = ph.x - pp.x, dy = ph.y - pp.y, dz = ph.z - pp.z;
+  const float dp = fabsf((np.x * dx + np.y * dy) + np.z * dz);
+  return td_hit(nq) && dn >= A.cos_min && dp <= lim;
+}
+
+// MODE 0: there is no history; 1: the camera stood still; 2: it moved (decided on the host: the branch is the same for every pixel)
+template <int MODE>
+__global__ void __launch_bounds__(256) k_temporal(const TemporalArgs A)
+{
+  const int x = blockIdx.x * kTW + threadIdx.x, y = blockIdx.y * kTH + threadIdx.y;
+  if (x >= A.w || y >= A.h) return;
+  const int p = x + A.w * y;
+  const float4 cv = A.cv[p], np = A.normal[p], pp = A.position[p];
+  float cx = cv.x, cy = cv.y, cz = cv.z, v = cv.w, hist = 0.0f;
+  if (td_hit(np)) {
+    hist = 1.0f;
+    bool have = false;
+    float hx = 0.0f, hy = 0.0f, hz = 0.0f, hv = 0.0f, hh = 0.0f;
+    if constexpr (MODE == 1) {
+      const float lim = A.plane_tol * fmaxf(A.depth[p], 1e-3f);
+      const float4 qc = A.h_cv[p], qp = A.h_ph[p], qn = A.h_n[p];
+      have = td_valid(A, np, pp, lim, qn, qp);
+      hx = qc.x; hy = qc.y; hz = qc.z; hv = qc.w; hh = qp.w;
+    }
+    if constexpr (MODE == 2) {
+      const float lim = A.plane_tol * fmaxf(A.depth[p], 1e-3f);
+      const float qx = ((A.m[0] * pp.x + A.m[1] * pp.y) + A.m[2] * pp.z) + A.m[3];
+      const float qy = ((A.m[4] * pp.x + A.m[5] * pp.y) + A.m[6] * pp.z) + A.m[7];
+      const float qz = ((A.m[8] * pp.x + A.m[9] * pp.y) + A.m[10] * pp.z) + A.m[11];
+      const float t = (A.f - qz) / A.f;
+      if (t > 0.0f) {
+        const float xs = (A.W + (A.H * qx) / t) * 0.5f - 0.5f, ys = (A.H - (A.H * qy) / t) * 0.5f - 0.5f;
+        const float ix = floorf(xs), iy = floorf(ys), fx = xs - ix, fy = ys - iy;
+        float S = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const float tx = ix + (float)i, ty = iy + (float)j;
+            const bool inside = tx >= 0.0f && tx <= A.W - 1.0f && ty >= 0.0f && ty <= A.H - 1.0f;  // (false for NaN: the clamps below then give pixel 0)
+            const int q = (int)fminf(fmaxf(tx, 0.0f), A.W - 1.0f) + A.w * (int)fminf(fmaxf(ty, 0.0f), A.H - 1.0f);
+            const float4 qc = A.h_cv[q], qp = A.h_ph[q], qn = A.h_n[q];
+            const float wgt = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+            if (inside && td_valid(A, np, pp, lim, qn, qp)) {
+              S += wgt; hx += wgt * qc.x; hy += wgt * qc.y; hz += wgt * qc.z; hv += wgt * qc.w; hh += wgt * qp.w;
+            }
+          }
+        have = S >= 1e-3f;
+        hx = hx / S; hy = hy / S; hz = hz / S; hv = hv / S; hh = hh / S;
+      }
+    }
+    if (have) {
+      hist = fminf(hh + 1.0f, A.max_history);
+      const float a = fmaxf(1.0f / hist, A.alpha_min), b = 1.0f - a;
+      cx = b * hx + a * cx; cy = b * hy + a * cy; cz = b * hz + a * cz;
+      v = (b * b) * hv + (a * a) * v;
+    }
+  }
+  A.o_cv[p] = make_float4(cx, cy, cz, v);
+  A.o_ph[p] = make_float4(pp.x, pp.y, pp.z, hist);
+  A.o_n[p] = np;
+  A.vplane[p] = v;
+}
+
 }  // namespace
 
-int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* pr, float* out, int upscale)
+namespace {
+
+// two (c, v) images and two variance planes, kept in the context
+int guided_scratch(fh_ctx* ctx, size_t px)
 {
-  hipStream_t st = ctx->stream;
-  const size_t px = (size_t)w * h;
-  if (ctx->guided_pixels < px) {  // two (c, v) images and two variance planes, kept in the context
+  if (ctx->guided_pixels < px) {
     for (int k = 0; k < 2; ++k) {
       if (ctx->d_guided_cv[k]) (void)hipFree(ctx->d_guided_cv[k]);
       if (ctx->d_guided_var[k]) (void)hipFree(ctx->d_guided_var[k]);
@@ -248,6 +344,14 @@ int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in
     }
     ctx->guided_pixels = px;
   }
+  return FH_OK;
+}
+
+// (c, v) into d_guided_cv[0] and v into d_guided_var[0]
+void guided_prepare(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* pr)
+{
+  hipStream_t st = ctx->stream;
+  const size_t px = (size_t)w * h;
   const float4 *beauty = (const float4*)in->beauty, *normal = (const float4*)in->normal, *albedo = (const float4*)in->albedo;
   const dim3 lin((unsigned)((px + 255) / 256));
   if (in->moments) {
@@ -257,13 +361,19 @@ int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in
     hipLaunchKernelGGL(k_guided_spatial_variance, dim3((w + 31) / 32, (h + 7) / 8), dim3(32, 8), 0, st, (const float4*)ctx->d_guided_cv[1], normal, w, h, pr->normal_power_log2,
                        ctx->d_guided_cv[0], ctx->d_guided_var[0]);
   }
+}
+
+// the passes; cv0: the (c, v) image the first one reads (its variance plane is d_guided_var[0])
+int guided_passes(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* pr, const float4* cv0, float* out, int upscale)
+{
+  hipStream_t st = ctx->stream;
   GuidedArgs a{};
-  a.normal = normal; a.albedo = albedo; a.position = (const float4*)in->position; a.depth = in->depth;
+  a.normal = (const float4*)in->normal; a.albedo = (const float4*)in->albedo; a.position = (const float4*)in->position; a.depth = in->depth;
   a.w = w; a.h = h; a.sigma_l = pr->sigma_l; a.sigma_z = pr->sigma_z; a.sa2 = pr->sigma_a * pr->sigma_a; a.power_log2 = pr->normal_power_log2; a.upscale = upscale;
   for (uint32_t it = 0; it < pr->passes; ++it) {
     const bool last = it + 1 == pr->passes;
     const int s = 1 << it;
-    a.cv = ctx->d_guided_cv[it & 1]; a.vplane = ctx->d_guided_var[it & 1];
+    a.cv = it == 0 ? cv0 : ctx->d_guided_cv[it & 1]; a.vplane = ctx->d_guided_var[it & 1];
     a.cv_out = ctx->d_guided_cv[(it + 1) & 1]; a.vplane_out = ctx->d_guided_var[(it + 1) & 1];
     a.image_out = (float4*)out; a.shift = (int)it;
     a.groups_x = (unsigned)(((w + kTW * s - 1) / (kTW * s)) * s); a.groups_y = (unsigned)(((h + kTH * s - 1) / (kTH * s)) * s);
@@ -274,6 +384,52 @@ int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in
   }
   FH_HIP(hipGetLastError());
   return FH_OK;
+}
+
+}  // namespace
+
+int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* pr, float* out, int upscale)
+{
+  if (const int rc = guided_scratch(ctx, (size_t)w * h)) return rc;
+  guided_prepare(ctx, w, h, in, pr);
+  return guided_passes(ctx, w, h, in, pr, ctx->d_guided_cv[0], out, upscale);
+}
+
+int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
+                            const fh_denoise_params* pr, float* out, int upscale)
+{
+  const size_t px = (size_t)w * h;
+  if (const int rc = guided_scratch(ctx, px)) return rc;
+  if (ctx->hist_pixels < px) {  // (growing drops the history; so does any other change of width x height, below)
+    float4** bufs[3] = {ctx->d_hist_cv, ctx->d_hist_ph, ctx->d_hist_n};
+    for (auto b : bufs)
+      for (int k = 0; k < 2; ++k) { if (b[k]) (void)hipFree(b[k]); b[k] = nullptr; }
+    ctx->hist_pixels = 0; ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;
+    for (auto b : bufs)
+      for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&b[k], px * sizeof(float4)));
+    ctx->hist_pixels = px;
+  }
+  if (ctx->hist_w != (uint32_t)w || ctx->hist_h != (uint32_t)h) ctx->hist_frames = 0;
+  guided_prepare(ctx, w, h, in, pr);
+  const int from = ctx->hist_cur, to = from ^ 1;
+  TemporalArgs a{};
+  a.cv = ctx->d_guided_cv[0]; a.normal = (const float4*)in->normal; a.position = (const float4*)in->position; a.depth = in->depth;
+  a.h_cv = ctx->d_hist_cv[from]; a.h_ph = ctx->d_hist_ph[from]; a.h_n = ctx->d_hist_n[from];
+  a.o_cv = ctx->d_hist_cv[to]; a.o_ph = ctx->d_hist_ph[to]; a.o_n = ctx->d_hist_n[to];
+  a.vplane = ctx->d_guided_var[0];
+  a.w = w; a.h = h; a.W = (float)w; a.H = (float)h;
+  for (int k = 0; k < 12; ++k) a.m[k] = ctx->hist_w2c[k];
+  a.f = ctx->hist_inv_tan;
+  a.alpha_min = tp->alpha_min; a.max_history = tp->max_history; a.cos_min = tp->normal_cos_min; a.plane_tol = tp->plane_tol;
+  const dim3 grid((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), block(kTW, kTH);
+  if (ctx->hist_frames == 0) hipLaunchKernelGGL((k_temporal<0>), grid, block, 0, ctx->stream, a);
+  else if (std::memcmp(cam, &ctx->hist_camera, sizeof(fh_camera)) == 0) hipLaunchKernelGGL((k_temporal<1>), grid, block, 0, ctx->stream, a);
+  else hipLaunchKernelGGL((k_temporal<2>), grid, block, 0, ctx->stream, a);
+  ctx->hist_cur = to; ctx->hist_camera = *cam; ctx->hist_inv_tan = inv_tan;
+  for (int k = 0; k < 12; ++k) ctx->hist_w2c[k] = w2c[k];
+  ctx->hist_w = (uint32_t)w; ctx->hist_h = (uint32_t)h;
+  if (ctx->hist_frames != 0xffffffffu) ++ctx->hist_frames;
+  return guided_passes(ctx, w, h, in, pr, ctx->d_hist_cv[to], out, upscale);
 }
 
 }  // namespace fh

@@ -1,0 +1,63 @@
+// temporal_host.h -- the host-only part of fh_denoise_temporal (include/fredholm_hip.h): the refusals, which are decided from the arguments alone, and the
+// inversion of the camera.  Plain C++ without HIP, so that it also compiles into a stand-alone program (tools/temporal_host_check.cpp) for the host sanitizers.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/fredholm_hip.h"
+
+namespace fh {
+
+// why fh_denoise_guided refuses these arguments, or nullptr (the context is not looked at)
+inline const char* guided_refusal(uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_denoise_params& pr, const float* denoised)
+{
+  auto bad_sigma = [](float s) { return !(s > 0.0f) || !std::isfinite(s); };
+  if (!in || !denoised) return "null argument";
+  if (!in->beauty || !in->normal || !in->albedo) return "the beauty, normal and albedo layers are required";
+  if ((in->position == nullptr) != (in->depth == nullptr)) return "position and depth are given together or not at all";
+  if ((in->moments == nullptr) != (in->counts == nullptr)) return "moments and counts are given together or not at all";
+  if (width == 0 || height == 0 || width > 32768 || height > 32768) return "width and height must be in 1..32768";
+  if (bad_sigma(pr.sigma_l) || bad_sigma(pr.sigma_z) || bad_sigma(pr.sigma_a)) return "sigma_l, sigma_z and sigma_a must be finite and > 0";
+  if (pr.normal_power_log2 > 10) return "normal_power_log2 must be at most 10";
+  if (pr.passes < 1 || pr.passes > 6) return "passes must be in 1..6";
+  return nullptr;
+}
+
+// world-to-camera rows of a camera-to-world 3x4, by the cofactor formula of the header: in double, rounded once to float.  False: not invertible.
+inline bool camera_world_to_camera(const float t[12], float out[12])
+{  // (compiled with -ffp-contract=off like everything here: the numpy restatement of the tests reproduces these doubles)
+  const double R00 = t[0], R01 = t[1], R02 = t[2], R10 = t[4], R11 = t[5], R12 = t[6], R20 = t[8], R21 = t[9], R22 = t[10];
+  const double T[3] = {t[3], t[7], t[11]};
+  const double Cf[3][3] = {{R11 * R22 - R12 * R21, R02 * R21 - R01 * R22, R01 * R12 - R02 * R11},
+                           {R12 * R20 - R10 * R22, R00 * R22 - R02 * R20, R02 * R10 - R00 * R12},
+                           {R10 * R21 - R11 * R20, R01 * R20 - R00 * R21, R00 * R11 - R01 * R10}};
+  const double det = (R00 * Cf[0][0] + R01 * Cf[1][0]) + R02 * Cf[2][0];
+  if (!(det != 0.0) || !std::isfinite(det)) return false;
+  for (int i = 0; i < 3; ++i) {
+    const double m0 = Cf[i][0] / det, m1 = Cf[i][1] / det, m2 = Cf[i][2] / det;
+    const double m3 = -((m0 * T[0] + m1 * T[1]) + m2 * T[2]);
+    out[4 * i] = (float)m0; out[4 * i + 1] = (float)m1; out[4 * i + 2] = (float)m2; out[4 * i + 3] = (float)m3;
+    for (int j = 0; j < 4; ++j)
+      if (!std::isfinite(out[4 * i + j])) return false;
+  }
+  return true;
+}
+
+// why fh_denoise_temporal refuses these arguments, or nullptr; on acceptance w2c and *inv_tan hold the inverted camera and its cam_inv_tan
+inline const char* temporal_refusal(uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const fh_temporal_params& tp, const fh_denoise_params& pr,
+                                    const float* denoised, float w2c[12], float* inv_tan)
+{
+  if (const char* why = guided_refusal(width, height, in, pr, denoised)) return why;
+  if (!camera) return "null camera";
+  if (!in->position) return "the position and depth layers are required";
+  if (!(tp.alpha_min >= 0.0f && tp.alpha_min <= 1.0f)) return "alpha_min must be in [0, 1]";
+  if (!(tp.max_history >= 1.0f) || !std::isfinite(tp.max_history)) return "max_history must be finite and >= 1";
+  if (!(tp.normal_cos_min > -1.0f && tp.normal_cos_min <= 1.0f)) return "normal_cos_min must be in (-1, 1]";
+  if (!(tp.plane_tol > 0.0f) || !std::isfinite(tp.plane_tol)) return "plane_tol must be finite and > 0";
+  *inv_tan = 1.0f / tanf(0.5f * camera->fov);  // render.hip: cam_inv_tan
+  if (!(*inv_tan > 0.0f) || !std::isfinite(*inv_tan)) return "the camera's fov gives no finite focal length";
+  if (!camera_world_to_camera(camera->transform, w2c)) return "the camera's transform cannot be inverted";
+  return nullptr;
+}
+
+}  // namespace fh

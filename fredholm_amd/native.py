@@ -112,7 +112,7 @@ EXPORTS = [
     "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
     "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued",
     "fh_set_adaptive_policy", "fh_get_adaptive_policy", "fh_adaptive_next_boundary",
-    "fh_denoise_guided",
+    "fh_denoise_guided", "fh_denoise_temporal", "fh_denoise_history_reset", "fh_denoise_history_info",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -133,6 +133,11 @@ class DenoiseParamsC(C.Structure):
     _fields_ = [("sigma_l", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("normal_power_log2", C.c_uint32), ("passes", C.c_uint32)]
 
 
+class TemporalParamsC(C.Structure):
+    """fh_temporal_params (include/fredholm_hip.h); the defaults are the library's (temporal == NULL)"""
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tol", C.c_float)]
+
+
 # argument types of the entry points declared with them (the adaptive-sampling ABI); every entry point returns int
 SIGNATURES = {
     "fh_set_adaptive_sampling": [C.c_void_p, C.POINTER(AdaptiveParamsC)],
@@ -145,6 +150,9 @@ SIGNATURES = {
     "fh_adaptive_next_boundary": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_kat_set_issued": [C.c_void_p, C.c_void_p, C.c_uint32],
     "fh_denoise_guided": [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputsC), C.POINTER(DenoiseParamsC), C.c_void_p, C.c_int],
+    "fh_denoise_temporal": [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputsC), C.POINTER(CameraC), C.POINTER(TemporalParamsC), C.POINTER(DenoiseParamsC), C.c_void_p, C.c_int],
+    "fh_denoise_history_reset": [C.c_void_p],
+    "fh_denoise_history_info": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_ctx_member": [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)],

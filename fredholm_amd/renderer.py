@@ -528,6 +528,29 @@ class Renderer:
         p = N.DenoiseParamsC(float(sigma_l), float(sigma_z), float(sigma_a), int(normal_power_log2), int(passes))
         self._ck(N.lib().fh_denoise_guided(self._ctx, int(width), int(height), C.byref(i), C.byref(p), C.c_void_p(denoised_ptr), int(bool(upscale))), "fh_denoise_guided")
 
+    def denoise_temporal(self, width, height, beauty_ptr, normal_ptr, albedo_ptr, denoised_ptr, position_ptr, depth_ptr, camera, moments_ptr=None, counts_ptr=None,
+                         alpha_min=0.2, max_history=32.0, normal_cos_min=0.5, plane_tol=0.02, sigma_l=2.0, sigma_z=1.0, sigma_a=0.2, normal_power_log2=7, passes=5, upscale=False):
+        """temporal accumulation in front of the variance-guided denoiser (fh_denoise_temporal): the frame's demodulated radiance and variance are blended with the
+        context's history of the frames before it, reprojected through the world position, and the guided filter's passes run on the result.  `camera` is the Camera
+        the layers were rendered with; give every frame of a sequence samples of its own (Renderer.seed).  The first call after reset_denoise_history or a change of
+        width x height is denoise_guided."""
+        i = N.DenoiseInputsC(beauty_ptr, normal_ptr, albedo_ptr, position_ptr, depth_ptr, moments_ptr, counts_ptr)
+        t = N.TemporalParamsC(float(alpha_min), float(max_history), float(normal_cos_min), float(plane_tol))
+        p = N.DenoiseParamsC(float(sigma_l), float(sigma_z), float(sigma_a), int(normal_power_log2), int(passes))
+        cam = camera.as_c()
+        self._ck(N.lib().fh_denoise_temporal(self._ctx, int(width), int(height), C.byref(i), C.byref(cam), C.byref(t), C.byref(p), C.c_void_p(denoised_ptr), int(bool(upscale))),
+                 "fh_denoise_temporal")
+
+    def reset_denoise_history(self):
+        """drop the history of denoise_temporal (fh_denoise_history_reset)"""
+        self._ck(N.lib().fh_denoise_history_reset(self._ctx), "fh_denoise_history_reset")
+
+    def denoise_history_info(self):
+        """(width, height, frames accumulated since the last reset) of the history of denoise_temporal; (0, 0, 0) when there is none"""
+        w, h, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._ck(N.lib().fh_denoise_history_info(self._ctx, C.byref(w), C.byref(h), C.byref(n)), "fh_denoise_history_info")
+        return w.value, h.value, n.value
+
     # -- parity-test hooks
     def measure_bandwidth(self, nbytes=1 << 30, iters=8):
         """(read GB/s, copy GB/s) of this GPU's HBM, measured with streaming kernels (fh_measure_bandwidth)"""

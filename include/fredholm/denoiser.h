@@ -6,12 +6,18 @@
 // Beyond the reference: set_mode(Denoiser::Guided) runs the variance-guided filter (fh_denoise_guided) on the same layers plus whatever set_guides() was given --
 // position and depth for the plane edge stop, the luminance moments and sample counts of adaptive sampling for the colour edge stop.  An application that is
 // not edited gets it with the environment variable FH_DENOISER=guided (read by the constructor; set_mode wins).
+// set_mode(Denoiser::Temporal) (FH_DENOISER=temporal) puts temporal accumulation in front of that filter (fh_denoise_temporal): it needs the position and depth
+// guides and, before every denoise(), the camera the frame was rendered with (set_camera); the history lives in the context, reset_history() drops it.  Give the
+// frames of a sequence samples of their own (Renderer::set_seed), or a still camera accumulates one image over and over.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 
+#include <stdexcept>
+
 #include "../cwl/util.h"
+#include "camera.h"
 #include "types.h"
 
 namespace fredholm
@@ -24,8 +30,9 @@ class Denoiser
   {
     const char* env = std::getenv("FH_DENOISER");
     if (env && std::strcmp(env, "guided") == 0) m_mode = Guided;
+    if (env && std::strcmp(env, "temporal") == 0) m_mode = Temporal;
   }
-  enum Mode { Atrous, Guided };
+  enum Mode { Atrous, Guided, Temporal };
   void set_mode(Mode mode) { m_mode = mode; }
   Mode mode() const { return m_mode; }
   // device pointers of width * height elements; position and depth go together, moments and counts go together, either pair may be null
@@ -33,9 +40,30 @@ class Denoiser
   {
     m_d_position = d_position; m_d_depth = d_depth; m_d_moments = d_moments; m_d_counts = d_counts;
   }
+  // Temporal mode: the camera the layers were rendered with (what Renderer::render was given; for a scene with a camera of its own, Renderer::camera_params)
+  void set_camera(const Camera& camera) { set_camera(camera.to_c()); }
+  void set_camera(const fh_camera& camera) { m_camera = camera; m_has_camera = true; }
+  void set_temporal_params(float alpha_min, float max_history, float normal_cos_min, float plane_tol)
+  {
+    m_temporal = fh_temporal_params{alpha_min, max_history, normal_cos_min, plane_tol};
+    m_has_temporal = true;
+  }
+  void reset_history()
+  {
+    fh_ctx* ctx = m_context ? m_context : cwl::require_context();
+    cwl::check(ctx, fh_denoise_history_reset(ctx), "fh_denoise_history_reset");
+  }
   void denoise()
   {
     fh_ctx* ctx = m_context ? m_context : cwl::require_context();
+    if (m_mode == Temporal) {
+      if (!m_has_camera) throw std::runtime_error("Denoiser: Temporal mode needs set_camera() before denoise()");
+      const fh_denoise_inputs in = {reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
+                                    reinterpret_cast<const float*>(m_d_position), m_d_depth, reinterpret_cast<const float*>(m_d_moments), m_d_counts};
+      cwl::check(ctx, fh_denoise_temporal(ctx, m_width, m_height, &in, &m_camera, m_has_temporal ? &m_temporal : nullptr, nullptr, reinterpret_cast<float*>(m_d_denoised), m_upscale ? 1 : 0),
+                 "fh_denoise_temporal");
+      return;
+    }
     if (m_mode == Guided) {
       const fh_denoise_inputs in = {reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
                                     reinterpret_cast<const float*>(m_d_position), m_d_depth, reinterpret_cast<const float*>(m_d_moments), m_d_counts};
@@ -61,5 +89,8 @@ class Denoiser
   const float* m_d_depth = nullptr;
   const float2* m_d_moments = nullptr;
   const uint32_t* m_d_counts = nullptr;
+  fh_camera m_camera{};
+  fh_temporal_params m_temporal{};
+  bool m_has_camera = false, m_has_temporal = false;
 };
 }  // namespace fredholm

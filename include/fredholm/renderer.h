@@ -91,8 +91,14 @@ class Renderer
     const float bg[3] = {bg_color.x, bg_color.y, bg_color.z};
     fh_render_layers layers{reinterpret_cast<float*>(render_layer.beauty), reinterpret_cast<float*>(render_layer.position), render_layer.depth,
                             reinterpret_cast<float*>(render_layer.normal), reinterpret_cast<float*>(render_layer.texcoord), reinterpret_cast<float*>(render_layer.albedo)};
-    cwl::check(m_ctx, fh_render(m_ctx, &cam, bg, &layers, n_samples, max_depth, 1u /* params.seed = 1, renderer.h:664 */), "fh_render");
+    cwl::check(m_ctx, fh_render(m_ctx, &cam, bg, &layers, n_samples, max_depth, m_seed), "fh_render");
   }
+  // not in the reference, which always renders with params.seed = 1 (renderer.h:664): the seed of the following render() calls.  The frames of a sequence whose
+  // samples are accumulated over time (Denoiser::Temporal) need different ones; the default 1 keeps every bit.
+  void set_seed(uint32_t seed) { m_seed = seed; }
+  uint32_t seed() const { return m_seed; }
+  // the camera render() hands to the library for `camera`: the scene's own camera transform where it has one (what Denoiser::set_camera wants)
+  fh_camera camera_params(const Camera& camera) const { return m_scene.m_has_camera_transform ? camera_from(m_scene.m_camera_transform, camera) : camera.to_c(); }
   void wait_for_completion() { cwl::check(m_ctx, fh_sync(m_ctx), "fh_sync"); }  // renderer.h:736
 
   // not in the reference: render(n_samples = k) as ONE reference launch of k samples, payload.firsthit quirk included (pt.cu:432-433;
@@ -183,6 +189,7 @@ class Renderer
   }
   fh_ctx* m_ctx = nullptr;
   uint32_t m_width = 0, m_height = 0;
+  uint32_t m_seed = 1;  // params.seed = 1, renderer.h:664
   Scene m_scene;
 };
 

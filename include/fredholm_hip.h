@@ -329,6 +329,51 @@ typedef struct fh_denoise_params {
  * context stream like fh_denoise; on a group it runs on the lead.  The scratch images live in the context and grow on demand. */
 int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* inputs, const fh_denoise_params* params, float* denoised, int upscale2x);
 
+/* -- temporal accumulation in front of the variance-guided denoiser (opt-in; fh_denoise and fh_denoise_guided keep their bits): the reprojection and accumulation
+ * stage of SVGF.  fh_denoise_temporal is fh_denoise_guided with ONE stage between its preparation and its passes, which blends (c, v) of the frame with the
+ * context's history of the frames before it, found again through the world position (there are no motion vectors: a surface that moved fails the plane stop at its
+ * old place and gets no history).  `camera` is the camera the layers were rendered with; position and depth are required; moments and counts stay optional.
+ * The context owns the history (on the lead of a group), double buffered: per pixel (c_acc.rgb, v_acc), (P, h) and N, and the camera of the call that wrote it.
+ * A change of width x height, fh_denoise_history_reset and fh_ctx_destroy drop it; fh_set_resolution does not.  The first call after that gives fh_denoise_guided's bits.
+ *
+ * The stage, per pixel p, in fp32 without contraction, / correctly rounded, sums in the order written; c, v: the preparation's values; N, P, Z: the inputs at p;
+ * primed values: the history; X != 0 for a normal: any of its three components is non-zero.
+ *   N_p = 0 (a miss):      c_acc = c, v_acc = v, h = 0.
+ *   no history (below):    c_acc = c, v_acc = v, h = 1.
+ *   with history c_h, v_h, h_h:  h = min(h_h + 1, max_history),  a = max(1 / h, alpha_min),  b = 1 - a,
+ *                          c_acc = b * c_h + a * c,   v_acc = (b * b) * v_h + (a * a) * v   (the variance of that combination of independent frames; a = 1 gives c, v exactly)
+ *   The passes run on (c_acc, v_acc); the history keeps (c_acc, v_acc), (P_p, h), N_p: values from BEFORE the spatial filter, whose bias must not feed back.
+ *   A tap q of the history is VALID when it lies inside the frame, N'_q != 0, (N_p.x * N'_q.x + N_p.y * N'_q.y) + N_p.z * N'_q.z >= normal_cos_min, and, with
+ *   d = P'_q - P_p,  |(N_p.x * d.x + N_p.y * d.y) + N_p.z * d.z| <= plane_tol * max(Z_p, 1e-3).
+ *   Still camera (all 15 floats of `camera` have the stored camera's bits): the only tap is p itself; valid: c_h, v_h, h_h are its values unchanged; else no history.
+ *   Moved camera: with M' the stored camera's world-to-camera rows and f' = 1 / tanf(0.5 * fov') of it (fp32, as fh_render computes it):
+ *     Q.i = ((M'[4i] * P.x + M'[4i+1] * P.y) + M'[4i+2] * P.z) + M'[4i+3];   t = (f' - Q.z) / f';   no history unless t > 0;
+ *     x = (W + (H * Q.x) / t) * 0.5,  y = (H - (H * Q.y) / t) * 0.5   (W, H: width, height as floats; the inverse of the chief ray of pixel (x, y), pixel centres at + 0.5);
+ *     xs = x - 0.5, ix = floor(xs), fx = xs - ix, likewise ys, iy, fy; taps (ix + i, iy + j) for j = 0, 1 (outer), i = 0, 1 (inner) with weights
+ *     (i ? fx : 1 - fx) * (j ? fy : 1 - fy); over the valid taps in that order S = sum w, then c_h = (sum w * c'_q) / S, v_h = (sum w * v'_q) / S,
+ *     h_h = (sum w * h'_q) / S; no history unless S >= 1e-3.
+ *   M' is computed on the host, in double, and rounded once to float: with R the 3 x 3 of camera.transform (R[i][j] = transform[4i + j]) and T its fourth column,
+ *     C00 = R11 R22 - R12 R21, C01 = R02 R21 - R01 R22, C02 = R01 R12 - R02 R11,   C10 = R12 R20 - R10 R22, C11 = R00 R22 - R02 R20, C12 = R02 R10 - R00 R12,
+ *     C20 = R10 R21 - R11 R20, C21 = R01 R20 - R00 R21, C22 = R00 R11 - R01 R10,   det = (R00 C00 + R01 C10) + R02 C20,
+ *     M'[4i + j] = Cij / det,   M'[4i + 3] = -(((Ci0 / det) * T0 + (Ci1 / det) * T1) + (Ci2 / det) * T2).
+ * Defaults (temporal == NULL): alpha_min 0.2, max_history 32, normal_cos_min 0.5, plane_tol 0.02 -- chosen by the float64 replay of DESIGN.md 4a.  The normal layer
+ * is the mean of the samples' normals, shorter than 1 wherever a pixel straddles an edge, so the usual 0.9 refuses a history to one hit pixel in eight, frame after
+ * frame, on a still camera too; 0.5 still separates walls that meet at a right angle. */
+typedef struct fh_temporal_params {
+  float alpha_min;      /* lower bound of the blend weight of the new frame, in [0, 1] */
+  float max_history;    /* cap of the history length, >= 1 */
+  float normal_cos_min; /* a history tap is valid only if N_p . N'_q >= this, in (-1, 1] */
+  float plane_tol;      /* ... and |N_p . (P'_q - P_p)| <= plane_tol * max(Z_p, 1e-3), > 0 */
+} fh_temporal_params;
+/* FH_E_INVALID, decided from the arguments alone before anything is touched (a refused call leaves history and output alone): a null camera; a camera whose
+ * transform cannot be inverted (det is 0 or not finite) or whose 1 / tanf(0.5 * fov) is not finite and > 0; missing position or depth; a temporal parameter that
+ * is not finite or outside its range; and everything fh_denoise_guided refuses.  Asynchronous on the context stream. */
+int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* inputs, const fh_camera* camera, const fh_temporal_params* temporal,
+                        const fh_denoise_params* params, float* denoised, int upscale2x);
+int fh_denoise_history_reset(fh_ctx* ctx);
+/* width and height of the history and the frames accumulated since the last reset (0, 0, 0 when there is none); any pointer may be NULL */
+int fh_denoise_history_info(fh_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* frames);
+
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */
 int fh_gl_register_buffer(fh_ctx* ctx, unsigned int gl_buffer, void** resource, void** device_ptr, uint64_t* bytes);
