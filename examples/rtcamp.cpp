@@ -8,9 +8,10 @@
 //                                                                    until no pixel is active; prints the frame's mean spp)
 //          [--adaptive-block G --adaptive-growth K]   (with --noise-threshold: G x G pixel blocks (1, 2, 4, 8) stop together; K = 2 tests at M, 2M, 4M ... only,
 //                                                       and the frame renders in calls that end on those boundaries)
-//          [--denoiser atrous|guided|temporal]   (atrous, the default: fh_denoise; guided: the variance-guided filter on the position and depth layers too, and on the
+//          [--denoiser atrous|guided|temporal|temporal-motion]   (atrous, the default: fh_denoise; guided: the variance-guided filter on the position and depth layers too, and on the
 //                                         luminance moments and sample counts whenever --noise-threshold is on; temporal: that filter behind temporal accumulation --
-//                                         frame i renders with seed 1 + i and the denoiser is told the frame's camera; every other mode keeps seed 1)
+//                                         frame i renders with seed 1 + i and the denoiser is told the frame's camera; every other mode keeps seed 1; temporal-motion: temporal with
+//                                         per-instance motion vectors, so that the key-framed objects keep their history too)
 //          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
 #include <chrono>
 #include <cmath>
@@ -73,12 +74,13 @@ int main(int argc, char** argv)
     }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal] [--devices 0,1,...]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   if (adaptive_block != 1 && adaptive_block != 2 && adaptive_block != 4 && adaptive_block != 8) { std::fprintf(stderr, "--adaptive-block must be 1, 2, 4 or 8\n"); return 2; }
   if (adaptive_growth != 1 && adaptive_growth != 2) { std::fprintf(stderr, "--adaptive-growth must be 1 or 2\n"); return 2; }
-  if (denoiser_name != "atrous" && denoiser_name != "guided" && denoiser_name != "temporal") { std::fprintf(stderr, "--denoiser must be atrous, guided or temporal\n"); return 2; }
-  const bool temporal = denoiser_name == "temporal";
+  if (denoiser_name != "atrous" && denoiser_name != "guided" && denoiser_name != "temporal" && denoiser_name != "temporal-motion") { std::fprintf(stderr, "--denoiser must be atrous, guided, temporal or temporal-motion\n"); return 2; }
+  const bool temporal_motion = denoiser_name == "temporal-motion";
+  const bool temporal = denoiser_name == "temporal" || temporal_motion;
   const bool guided = denoiser_name == "guided" || temporal;  // (temporal: the same guides)
   const float time_step = 1.0f / fps;
   try {
@@ -117,6 +119,7 @@ int main(int argc, char** argv)
     cwl::CUDABuffer<float2> luminance_moments(guided && noise_threshold >= 0.0f ? n_px : 1);  // (and, for the guided denoiser, the moments they go with)
     if (guided) {
       denoiser.set_mode(temporal ? fredholm::Denoiser::Temporal : fredholm::Denoiser::Guided);
+      if (temporal_motion) denoiser.set_motion(true);
       if (noise_threshold >= 0.0f) denoiser.set_guides(layer_position.get_device_ptr(), layer_depth.get_device_ptr(), luminance_moments.get_device_ptr(), sample_counts.get_device_ptr());
       else denoiser.set_guides(layer_position.get_device_ptr(), layer_depth.get_device_ptr());
     }

@@ -13,6 +13,7 @@
 #include "context.h"
 #include "fh_bsdf.h"
 #include "fh_trace.h"
+#include "motion_host.h"
 #include "temporal_host.h"
 
 // generated at build time from fredholm_amd/data/*.{u32,f32} by tools/gen_tables_inc.py
@@ -619,7 +620,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
   void* ptrs[] = {ctx->d_sample_issued, ctx->d_sobol, ctx->d_sobol_bytes, ctx->d_alpha_rec, ctx->d_lut_refl, ctx->d_lut_sheen, ctx->d_face_rec, ctx->d_face_cls, ctx->d_materials, ctx->d_lights, ctx->d_bvh2_nodes, ctx->d_bvh2_tris,
                   ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_sample_count, ctx->d_owned, ctx->d_trace_counters, ctx->d_texels, ctx->d_textures, ctx->d_srgb_lut, ctx->d_ibl,
                   ctx->d_bloom_weights, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
-                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hist_cv[0], ctx->d_hist_cv[1], ctx->d_hist_ph[0], ctx->d_hist_ph[1], ctx->d_hist_n[0], ctx->d_hist_n[1], ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
+                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hist_cv[0], ctx->d_hist_cv[1], ctx->d_hist_ph[0], ctx->d_hist_ph[1], ctx->d_hist_n[0], ctx->d_hist_n[1], ctx->d_motion, ctx->d_motion_ids, ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
                   ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active[2], ctx->d_active[3], ctx->d_block_marks, ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -629,6 +630,8 @@ int fh_ctx_destroy(fh_ctx* ctx)
   for (int k = 0; k < 4; ++k) if (ctx->d_split[k]) (void)hipFree(ctx->d_split[k]);
   if (ctx->d_split_counters) (void)hipFree(ctx->d_split_counters);
   if (ctx->h_active_count) (void)hipHostFree(ctx->h_active_count);
+  if (ctx->h_motion) (void)hipHostFree(ctx->h_motion);
+  if (ctx->ev_motion) (void)hipEventDestroy(ctx->ev_motion);
   if (ctx->sky_stream) { (void)hipStreamSynchronize(ctx->sky_stream); (void)hipStreamDestroy(ctx->sky_stream); }
   if (ctx->ev_sky) (void)hipEventDestroy(ctx->ev_sky);
   if (ctx->ev_sky_cursor) (void)hipEventDestroy(ctx->ev_sky_cursor);
@@ -783,6 +786,7 @@ int fh_scene_upload(fh_ctx* ctx, const fh_scene_desc* s)
   const int rc = rebuild_device_scene(ctx);
   if (rc) return rc;
   ctx->scene_loaded = true;
+  ctx->hist_o2w.clear(); ctx->hist_w2o.clear();  // (fh_set_denoise_motion: another scene's instances are not these)
   ctx->builder_choice = 0;  // new geometry: let the next build choose its builder again
   return FH_OK;
 }
@@ -1300,7 +1304,37 @@ int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_d
   if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_temporal: ") + why);
   FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
-  return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
+  if (!ctx->denoise_motion) return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
+  // fh_set_denoise_motion: the history is kept with the instance matrices it was written under; where they differ from the context's, the call carries the moved
+  // instances' pixels itself (motion.hip).  Everything that can fail is decided before the first launch.
+  const size_t nf = ctx->h_o2w.size();
+  const bool alive = ctx->hist_frames != 0 && ctx->hist_w == width && ctx->hist_h == height;
+  const bool moved = alive && nf != 0 && ctx->hist_o2w.size() == nf && ctx->hist_w2o.size() == nf && ctx->h_w2o.size() == nf &&
+                     (std::memcmp(ctx->hist_o2w.data(), ctx->h_o2w.data(), nf * sizeof(float)) != 0 || std::memcmp(ctx->hist_w2o.data(), ctx->h_w2o.data(), nf * sizeof(float)) != 0);
+  int rc;
+  if (!moved) {
+    rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
+  } else {
+    if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_denoise_temporal: instances moved and the BVH has not been built (fh_set_denoise_motion)");
+    const uint32_t ni = (uint32_t)(nf / 12);
+    std::vector<fh_motion> table(ni);
+    for (uint32_t i = 0; i < ni; ++i) {
+      motion_entry(ctx->hist_o2w.data() + 12ull * i, ctx->hist_w2o.data() + 12ull * i, ctx->h_o2w.data() + 12ull * i, ctx->h_w2o.data() + 12ull * i, &table[i]);
+      if (!motion_finite(table[i])) return fail(ctx, FH_E_INVALID, "fh_denoise_temporal: the motion of an instance is not finite (fh_set_denoise_motion)");
+    }
+    const size_t px = (size_t)width * height;
+    if (ctx->motion_ids_pixels < px) {
+      (void)hipStreamSynchronize(ctx->stream);
+      if (ctx->d_motion_ids) (void)hipFree(ctx->d_motion_ids);
+      ctx->d_motion_ids = nullptr; ctx->motion_ids_pixels = 0;
+      FH_HIP(hipMalloc((void**)&ctx->d_motion_ids, px * sizeof(uint32_t)));
+      ctx->motion_ids_pixels = px;
+    }
+    if ((rc = primary_instances_submit(ctx, camera, width, height, ctx->d_motion_ids))) return rc;
+    rc = denoise_temporal_motion_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, ctx->d_motion_ids, ni, table.data(), denoised, upscale2x ? 1 : 0);
+  }
+  if (rc == FH_OK) { ctx->hist_o2w = ctx->h_o2w; ctx->hist_w2o = ctx->h_w2o; }
+  return rc;
 }
 
 int fh_denoise_history_reset(fh_ctx* ctx)
@@ -1308,6 +1342,7 @@ int fh_denoise_history_reset(fh_ctx* ctx)
   FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
   ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;  // (the buffers stay: the next call overwrites them without reading)
+  ctx->hist_o2w.clear(); ctx->hist_w2o.clear();
   return FH_OK;
 }
 

@@ -247,6 +247,17 @@ struct fh_ctx {
   fh_camera hist_camera{};
   float hist_w2c[12] = {};
   float hist_inv_tan = 0.0f;
+  // per-instance motion vectors (motion.hip, denoise.hip: k_temporal_motion).  denoise_motion: fh_set_denoise_motion; hist_o2w / hist_w2o: the instance matrices the
+  // history was written under (empty: no snapshot).  The motion table of a call goes through the pinned h_motion (ev_motion: its copy has been taken) to d_motion;
+  // d_motion_ids is the id plane of the calls the context feeds itself.
+  int denoise_motion = 0;
+  std::vector<float> hist_o2w, hist_w2o;
+  fh_motion* d_motion = nullptr;
+  fh_motion* h_motion = nullptr;
+  uint32_t motion_capacity = 0;
+  hipEvent_t ev_motion = nullptr;
+  uint32_t* d_motion_ids = nullptr;
+  size_t motion_ids_pixels = 0;
 
   // stats
   fh_stats stats{};
@@ -309,4 +320,8 @@ int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in
 // denoise.hip (arguments checked by the caller); w2c, inv_tan: `cam` inverted and its cam_inv_tan, kept with the history this call writes
 int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
                             const fh_denoise_params* params, float* out, int upscale);
+// the same with the motion stage (k_temporal_motion): ids a device pointer, motion a host array of n_instances entries of which at least one has moved
+int denoise_temporal_motion_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
+                                   const fh_denoise_params* params, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale);
+int primary_instances_submit(fh_ctx* ctx, const fh_camera* cam, uint32_t w, uint32_t h, uint32_t* ids);  // motion.hip (arguments checked by the caller)
 }  // namespace fh

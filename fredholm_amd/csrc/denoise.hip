@@ -14,7 +14,8 @@
 // DENSE neighbours, which the lattice does not hold.
 //
 // fh_denoise_temporal runs the same preparation and the same passes with one launch between them, k_temporal below: the frame's (c, v) blended with the context's
-// history of the frames before it, found again through the world position and the previous call's camera.
+// history of the frames before it, found again through the world position and the previous call's camera.  fh_denoise_temporal_motion launches k_temporal_motion in
+// its place where an instance moved: the same stage with the pixels of moved instances carried to where their surface was.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -254,6 +255,13 @@ struct TemporalArgs {
   float f, W, H;          // its cam_inv_tan; width and height as floats
   float alpha_min, max_history, cos_min, plane_tol;
 };
+// what k_temporal_motion takes besides (an argument of its own: the kernels above keep their argument block)
+struct MotionArgs {
+  const uint32_t* ids;     // the instance each pixel's chief ray sees (fh_primary_instances)
+  const fh_motion* motion; // n_instances entries, on the device
+  uint32_t n_instances;
+  int still;               // the camera has the stored camera's bits
+};
 
 __device__ __forceinline__ bool td_hit(const float4 n) { return n.x != 0.0f || n.y != 0.0f || n.z != 0.0f; }
 // the two stops of a history tap (its normal nq and position ph.xyz) seen from the pixel (np, pp); lim = plane_tol * max(Z_p, 1e-3)
@@ -310,6 +318,87 @@ __global__ void __launch_bounds__(256) k_temporal(const TemporalArgs A)
         have = S >= 1e-3f;
         hx = hx / S; hy = hy / S; hz = hz / S; hv = hv / S; hh = hh / S;
       }
+    }
+    if (have) {
+      hist = fminf(hh + 1.0f, A.max_history);
+      const float a = fmaxf(1.0f / hist, A.alpha_min), b = 1.0f - a;
+      cx = b * hx + a * cx; cy = b * hy + a * cy; cz = b * hz + a * cz;
+      v = (b * b) * hv + (a * a) * v;
+    }
+  }
+  A.o_cv[p] = make_float4(cx, cy, cz, v);
+  A.o_ph[p] = make_float4(pp.x, pp.y, pp.z, hist);
+  A.o_n[p] = np;
+  A.vplane[p] = v;
+}
+
+// the moved camera's look-up: where the stored camera saw pp, the 2 x 2 taps around it that pass the two stops seen from (np, pp), renormalised; false: no history
+__device__ __forceinline__ bool td_reproject(const TemporalArgs& A, const float4 np, const float4 pp, float lim, float& hx, float& hy, float& hz, float& hv, float& hh)
+{
+  bool have = false;
+  const float qx = ((A.m[0] * pp.x + A.m[1] * pp.y) + A.m[2] * pp.z) + A.m[3];
+  const float qy = ((A.m[4] * pp.x + A.m[5] * pp.y) + A.m[6] * pp.z) + A.m[7];
+  const float qz = ((A.m[8] * pp.x + A.m[9] * pp.y) + A.m[10] * pp.z) + A.m[11];
+  const float t = (A.f - qz) / A.f;
+  if (t > 0.0f) {
+    const float xs = (A.W + (A.H * qx) / t) * 0.5f - 0.5f, ys = (A.H - (A.H * qy) / t) * 0.5f - 0.5f;
+    const float ix = floorf(xs), iy = floorf(ys), fx = xs - ix, fy = ys - iy;
+    float S = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const float tx = ix + (float)i, ty = iy + (float)j;
+        const bool inside = tx >= 0.0f && tx <= A.W - 1.0f && ty >= 0.0f && ty <= A.H - 1.0f;  // (false for NaN: the clamps below then give pixel 0)
+        const int q = (int)fminf(fmaxf(tx, 0.0f), A.W - 1.0f) + A.w * (int)fminf(fmaxf(ty, 0.0f), A.H - 1.0f);
+        const float4 qc = A.h_cv[q], qp = A.h_ph[q], qn = A.h_n[q];
+        const float wgt = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+        if (inside && td_valid(A, np, pp, lim, qn, qp)) {
+          S += wgt; hx += wgt * qc.x; hy += wgt * qc.y; hz += wgt * qc.z; hv += wgt * qc.w; hh += wgt * qp.w;
+        }
+      }
+    have = S >= 1e-3f;
+    hx = hx / S; hy = hy / S; hz = hz / S; hv = hv / S; hh = hh / S;
+  }
+  return have;
+}
+
+
+// the "motion" form of k_temporal (fh_denoise_temporal_motion; the header states it): a pixel of an instance that moved is CARRIED to where its surface was, by the
+// instance's affine map, and takes the look-up of MODE 2 there whatever the camera did; the other pixels take MODE 1's tap under a still camera (uniform: decided on the
+// host) and MODE 2's look-up otherwise.  It reads 4 more bytes per pixel than MODE 2 and an 88-byte table entry that a wave shares.  A kernel of its own, not a fourth
+// MODE: its arguments would grow the argument block of the three above.
+__global__ void __launch_bounds__(256) k_temporal_motion(const TemporalArgs A, const MotionArgs M)
+{
+  const int x = blockIdx.x * kTW + threadIdx.x, y = blockIdx.y * kTH + threadIdx.y;
+  if (x >= A.w || y >= A.h) return;
+  const int p = x + A.w * y;
+  const float4 cv = A.cv[p], np = A.normal[p], pp = A.position[p];
+  float cx = cv.x, cy = cv.y, cz = cv.z, v = cv.w, hist = 0.0f;
+  if (td_hit(np)) {
+    hist = 1.0f;
+    bool have = false;
+    float hx = 0.0f, hy = 0.0f, hz = 0.0f, hv = 0.0f, hh = 0.0f;
+    const float lim = A.plane_tol * fmaxf(A.depth[p], 1e-3f);
+    const uint32_t inst = M.ids[p];
+    const bool carried = inst < M.n_instances && M.motion[inst < M.n_instances ? inst : 0u].moved != 0u;
+    if (!carried && M.still) {
+      const float4 qc = A.h_cv[p], qp = A.h_ph[p], qn = A.h_n[p];
+      have = td_valid(A, np, pp, lim, qn, qp);
+      hx = qc.x; hy = qc.y; hz = qc.z; hv = qc.w; hh = qp.w;
+    } else {
+      float4 nb = np, pb = pp;
+      if (carried) {
+        const float* a = M.motion[inst].point;
+        const float* g = M.motion[inst].normal;
+        pb.x = ((a[0] * pp.x + a[1] * pp.y) + a[2] * pp.z) + a[3];
+        pb.y = ((a[4] * pp.x + a[5] * pp.y) + a[6] * pp.z) + a[7];
+        pb.z = ((a[8] * pp.x + a[9] * pp.y) + a[10] * pp.z) + a[11];
+        nb.x = (g[0] * np.x + g[1] * np.y) + g[2] * np.z;
+        nb.y = (g[3] * np.x + g[4] * np.y) + g[5] * np.z;
+        nb.z = (g[6] * np.x + g[7] * np.y) + g[8] * np.z;
+      }
+      have = td_reproject(A, nb, pb, lim, hx, hy, hz, hv, hh);
     }
     if (have) {
       hist = fminf(hh + 1.0f, A.max_history);
@@ -395,8 +484,31 @@ int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in
   return guided_passes(ctx, w, h, in, pr, ctx->d_guided_cv[0], out, upscale);
 }
 
-int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
-                            const fh_denoise_params* pr, float* out, int upscale)
+namespace {
+
+// the motion table into the context's device buffer, through pinned memory: the caller's array is free again when the call returns
+int motion_upload(fh_ctx* ctx, uint32_t n, const fh_motion* motion)
+{
+  if (ctx->motion_capacity < n) {
+    (void)hipStreamSynchronize(ctx->stream);  // (a call queued earlier may still read the old table)
+    if (ctx->d_motion) (void)hipFree(ctx->d_motion);
+    if (ctx->h_motion) (void)hipHostFree(ctx->h_motion);
+    ctx->d_motion = nullptr; ctx->h_motion = nullptr; ctx->motion_capacity = 0;
+    FH_HIP(hipMalloc((void**)&ctx->d_motion, (size_t)n * sizeof(fh_motion)));
+    FH_HIP(hipHostMalloc((void**)&ctx->h_motion, (size_t)n * sizeof(fh_motion), hipHostMallocDefault));
+    ctx->motion_capacity = n;
+  }
+  if (!ctx->ev_motion) FH_HIP(hipEventCreateWithFlags(&ctx->ev_motion, hipEventDisableTiming));
+  else FH_HIP(hipEventSynchronize(ctx->ev_motion));  // the copy of the call before has left the pinned buffer
+  std::memcpy(ctx->h_motion, motion, (size_t)n * sizeof(fh_motion));
+  FH_HIP(hipMemcpyAsync(ctx->d_motion, ctx->h_motion, (size_t)n * sizeof(fh_motion), hipMemcpyHostToDevice, ctx->stream));
+  FH_HIP(hipEventRecord(ctx->ev_motion, ctx->stream));
+  return FH_OK;
+}
+
+// ids == nullptr: fh_denoise_temporal
+int temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
+                    const fh_denoise_params* pr, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale)
 {
   const size_t px = (size_t)w * h;
   if (const int rc = guided_scratch(ctx, px)) return rc;
@@ -410,6 +522,9 @@ int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* 
     ctx->hist_pixels = px;
   }
   if (ctx->hist_w != (uint32_t)w || ctx->hist_h != (uint32_t)h) ctx->hist_frames = 0;
+  const bool with_motion = ids && ctx->hist_frames != 0;  // (without a history nothing is looked up: the plain first call)
+  if (with_motion)
+    if (const int rc = motion_upload(ctx, n_instances, motion)) return rc;
   guided_prepare(ctx, w, h, in, pr);
   const int from = ctx->hist_cur, to = from ^ 1;
   TemporalArgs a{};
@@ -422,14 +537,31 @@ int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* 
   a.f = ctx->hist_inv_tan;
   a.alpha_min = tp->alpha_min; a.max_history = tp->max_history; a.cos_min = tp->normal_cos_min; a.plane_tol = tp->plane_tol;
   const dim3 grid((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), block(kTW, kTH);
+  const bool still = std::memcmp(cam, &ctx->hist_camera, sizeof(fh_camera)) == 0;
+  const MotionArgs ma{ids, ctx->d_motion, n_instances, still ? 1 : 0};
   if (ctx->hist_frames == 0) hipLaunchKernelGGL((k_temporal<0>), grid, block, 0, ctx->stream, a);
-  else if (std::memcmp(cam, &ctx->hist_camera, sizeof(fh_camera)) == 0) hipLaunchKernelGGL((k_temporal<1>), grid, block, 0, ctx->stream, a);
+  else if (with_motion) hipLaunchKernelGGL(k_temporal_motion, grid, block, 0, ctx->stream, a, ma);
+  else if (still) hipLaunchKernelGGL((k_temporal<1>), grid, block, 0, ctx->stream, a);
   else hipLaunchKernelGGL((k_temporal<2>), grid, block, 0, ctx->stream, a);
   ctx->hist_cur = to; ctx->hist_camera = *cam; ctx->hist_inv_tan = inv_tan;
   for (int k = 0; k < 12; ++k) ctx->hist_w2c[k] = w2c[k];
   ctx->hist_w = (uint32_t)w; ctx->hist_h = (uint32_t)h;
   if (ctx->hist_frames != 0xffffffffu) ++ctx->hist_frames;
   return guided_passes(ctx, w, h, in, pr, ctx->d_hist_cv[to], out, upscale);
+}
+
+}  // namespace
+
+int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
+                            const fh_denoise_params* pr, float* out, int upscale)
+{
+  return temporal_submit(ctx, w, h, in, cam, w2c, inv_tan, tp, pr, nullptr, 0u, nullptr, out, upscale);
+}
+
+int denoise_temporal_motion_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
+                                   const fh_denoise_params* pr, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale)
+{
+  return temporal_submit(ctx, w, h, in, cam, w2c, inv_tan, tp, pr, ids, n_instances, motion, out, upscale);
 }
 
 }  // namespace fh

@@ -10,8 +10,10 @@
 #include "../../include/fredholm_hip_test.h"
 #include "context.h"
 #include "fh_bsdf.h"
+#include "fh_chief_ray.h"
 #include "fh_tonemap.h"
 #include "fh_trace.h"
+#include "motion_host.h"
 
 namespace fh {
 namespace {
@@ -217,6 +219,16 @@ __global__ void k_camera(m34 xf, float inv_tan, float F, float focus, uint32_t w
   d.z *= -1.0f;
   const f3 dir = xform_dir(xf, d);
   out[6 * i] = org.x; out[6 * i + 1] = org.y; out[6 * i + 2] = org.z; out[6 * i + 3] = dir.x; out[6 * i + 4] = dir.y; out[6 * i + 5] = dir.z;
+}
+
+// the chief rays k_primary_instances (motion.hip) builds, through the same device function
+__global__ void k_chief_rays(ChiefCam cam, float* out)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cam.width * cam.height) return;
+  f3 org, dir;
+  chief_ray(cam, i % cam.width, i / cam.width, org, dir);
+  out[6 * (size_t)i] = org.x; out[6 * (size_t)i + 1] = org.y; out[6 * (size_t)i + 2] = org.z; out[6 * (size_t)i + 3] = dir.x; out[6 * (size_t)i + 4] = dir.y; out[6 * (size_t)i + 5] = dir.z;
 }
 
 __global__ void k_offset(uint32_t n, const float* p, const float* nn, float* out)
@@ -429,6 +441,23 @@ int fh_kat_camera(fh_ctx* ctx, const fh_camera* cam, uint32_t width, uint32_t he
   Tmp<float> o;
   FH_HIP(a.up(pixel_idx, n)); FH_HIP(b.up(n_spp, n)); FH_HIP(o.up(nullptr, 6ull * n));
   hipLaunchKernelGGL(k_camera, dim3(blocks(n)), dim3(256), 0, ctx->stream, xf, 1.0f / tanf(0.5f * cam->fov), cam->F, cam->focus, width, height, xxhash32(seed), n, a.p, b.p, o.p);
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(o.down(out6));
+  return FH_OK;
+}
+int fh_kat_chief_rays(fh_ctx* ctx, const fh_camera* cam, uint32_t width, uint32_t height, float* out6)
+{
+  KCTX(ctx);
+  if (!cam || !out6 || width == 0 || height == 0 || width > 4096 || height > 4096) return fail(ctx, FH_E_INVALID, "fh_kat_chief_rays: bad argument");
+  ChiefCam c{};
+  for (int r = 0; r < 3; ++r) c.xf.r[r] = make_float4(cam->transform[4 * r], cam->transform[4 * r + 1], cam->transform[4 * r + 2], cam->transform[4 * r + 3]);
+  c.inv_tan = 1.0f / tanf(0.5f * cam->fov);
+  c.apb = chief_a_plus_b(c.inv_tan, cam->focus);
+  c.width = width; c.height = height;
+  const uint32_t n = width * height;
+  Tmp<float> o;
+  FH_HIP(o.up(nullptr, 6ull * n));
+  hipLaunchKernelGGL(k_chief_rays, dim3(blocks(n)), dim3(256), 0, ctx->stream, c, o.p);
   FH_HIP(hipStreamSynchronize(ctx->stream));
   FH_HIP(o.down(out6));
   return FH_OK;

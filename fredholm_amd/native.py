@@ -113,6 +113,7 @@ EXPORTS = [
     "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued",
     "fh_set_adaptive_policy", "fh_get_adaptive_policy", "fh_adaptive_next_boundary",
     "fh_denoise_guided", "fh_denoise_temporal", "fh_denoise_history_reset", "fh_denoise_history_info",
+    "fh_primary_instances", "fh_motion_from_transforms", "fh_denoise_temporal_motion", "fh_set_denoise_motion", "fh_get_denoise_motion", "fh_kat_chief_rays",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -138,6 +139,11 @@ class TemporalParamsC(C.Structure):
     _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_float), ("normal_cos_min", C.c_float), ("plane_tol", C.c_float)]
 
 
+class MotionC(C.Structure):
+    """fh_motion (include/fredholm_hip.h): where an instance's points and normals were in the frame before"""
+    _fields_ = [("point", C.c_float * 12), ("normal", C.c_float * 9), ("moved", C.c_uint32)]
+
+
 # argument types of the entry points declared with them (the adaptive-sampling ABI); every entry point returns int
 SIGNATURES = {
     "fh_set_adaptive_sampling": [C.c_void_p, C.POINTER(AdaptiveParamsC)],
@@ -153,6 +159,13 @@ SIGNATURES = {
     "fh_denoise_temporal": [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputsC), C.POINTER(CameraC), C.POINTER(TemporalParamsC), C.POINTER(DenoiseParamsC), C.c_void_p, C.c_int],
     "fh_denoise_history_reset": [C.c_void_p],
     "fh_denoise_history_info": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "fh_primary_instances": [C.c_void_p, C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_void_p],
+    "fh_motion_from_transforms": [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MotionC)],
+    "fh_denoise_temporal_motion": [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputsC), C.POINTER(CameraC), C.POINTER(TemporalParamsC), C.POINTER(DenoiseParamsC), C.c_void_p,
+                                   C.c_uint32, C.POINTER(MotionC), C.c_void_p, C.c_int],
+    "fh_set_denoise_motion": [C.c_void_p, C.c_int],
+    "fh_get_denoise_motion": [C.c_void_p, C.POINTER(C.c_int)],
+    "fh_kat_chief_rays": [C.c_void_p, C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_void_p],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_ctx_member": [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)],
@@ -168,6 +181,18 @@ def group_shard_layout(width, height, n, mask=LAYER_ALL, tile_w=32, tile_h=32):
     rc = lib().fh_group_shard_layout(int(width), int(height), int(tile_w), int(tile_h), int(n), int(mask), out)
     check(None, rc, "fh_group_shard_layout")
     return [int(v) for v in out]
+
+
+def motion_from_transforms(o2w_prev, w2o_prev, o2w_cur, w2o_cur):
+    """fh_motion_from_transforms (host only, no GPU): a ctypes array of MotionC, one per instance, from the previous and the current instance matrices (n x 12 floats each)"""
+    arrs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 12) for a in (o2w_prev, w2o_prev, o2w_cur, w2o_cur)]
+    n = arrs[0].shape[0]
+    if any(a.shape[0] != n for a in arrs):
+        raise ValueError("motion_from_transforms: the four arrays hold one matrix per instance each")
+    out = (MotionC * max(n, 1))()
+    check(None, lib().fh_motion_from_transforms(n, *[ptr(a) for a in arrs], out), "fh_motion_from_transforms")
+    return (MotionC * n).from_buffer(out) if n else (MotionC * 0)()
+
 
 _lib = None
 

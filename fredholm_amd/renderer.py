@@ -541,6 +541,36 @@ class Renderer:
         self._ck(N.lib().fh_denoise_temporal(self._ctx, int(width), int(height), C.byref(i), C.byref(cam), C.byref(t), C.byref(p), C.c_void_p(denoised_ptr), int(bool(upscale))),
                  "fh_denoise_temporal")
 
+    def primary_instances(self, camera, width, height, ids_ptr):
+        """fh_primary_instances: the instance id of the face each pixel's chief ray sees (0xffffffff: a miss), width * height uint32 at the device pointer ids_ptr"""
+        cam = camera.as_c()
+        self._ck(N.lib().fh_primary_instances(self._ctx, C.byref(cam), int(width), int(height), C.c_void_p(ids_ptr)), "fh_primary_instances")
+
+    def denoise_temporal_motion(self, width, height, beauty_ptr, normal_ptr, albedo_ptr, denoised_ptr, position_ptr, depth_ptr, camera, instance_ids_ptr, motion,
+                                moments_ptr=None, counts_ptr=None, alpha_min=0.2, max_history=32.0, normal_cos_min=0.5, plane_tol=0.02, sigma_l=2.0, sigma_z=1.0, sigma_a=0.2,
+                                normal_power_log2=7, passes=5, upscale=False):
+        """denoise_temporal with per-instance motion vectors (fh_denoise_temporal_motion): instance_ids_ptr is the device plane primary_instances fills, `motion` the
+        table native.motion_from_transforms makes from the instance matrices of the frame before and of this frame (a ctypes array of native.MotionC).  Pixels of
+        instances that moved look their history up where the surface was; everything else is denoise_temporal."""
+        i = N.DenoiseInputsC(beauty_ptr, normal_ptr, albedo_ptr, position_ptr, depth_ptr, moments_ptr, counts_ptr)
+        t = N.TemporalParamsC(float(alpha_min), float(max_history), float(normal_cos_min), float(plane_tol))
+        p = N.DenoiseParamsC(float(sigma_l), float(sigma_z), float(sigma_a), int(normal_power_log2), int(passes))
+        cam = camera.as_c()
+        n = 0 if motion is None else len(motion)
+        self._ck(N.lib().fh_denoise_temporal_motion(self._ctx, int(width), int(height), C.byref(i), C.byref(cam), C.byref(t), C.byref(p),
+                                                    None if instance_ids_ptr is None else C.c_void_p(instance_ids_ptr), n, motion if n else None, C.c_void_p(denoised_ptr),
+                                                    int(bool(upscale))), "fh_denoise_temporal_motion")
+
+    def set_denoise_motion(self, on=True):
+        """fh_set_denoise_motion: while on, denoise_temporal keeps the instance matrices with its history and carries the pixels of instances that set_transforms /
+        set_time moved since (the layers must have been rendered with the current transforms)"""
+        self._ck(N.lib().fh_set_denoise_motion(self._ctx, int(bool(on))), "fh_set_denoise_motion")
+
+    def denoise_motion(self):
+        on = C.c_int(0)
+        self._ck(N.lib().fh_get_denoise_motion(self._ctx, C.byref(on)), "fh_get_denoise_motion")
+        return bool(on.value)
+
     def reset_denoise_history(self):
         """drop the history of denoise_temporal (fh_denoise_history_reset)"""
         self._ck(N.lib().fh_denoise_history_reset(self._ctx), "fh_denoise_history_reset")
@@ -557,6 +587,13 @@ class Renderer:
         r, c = C.c_double(0.0), C.c_double(0.0)
         self._ck(N.lib().fh_measure_bandwidth(self._ctx, C.c_uint64(nbytes), C.c_uint32(iters), C.byref(r), C.byref(c)), "fh_measure_bandwidth")
         return r.value, c.value
+
+    def chief_rays(self, camera, width, height):
+        """fh_kat_chief_rays: (height, width, 6) origin and direction of the chief rays primary_instances traces"""
+        out = np.zeros((int(height), int(width), 6), dtype=np.float32)
+        cam = camera.as_c()
+        self._ck(N.lib().fh_kat_chief_rays(self._ctx, C.byref(cam), int(width), int(height), N.ptr(out)), "fh_kat_chief_rays")
+        return out
 
     def trace_rays(self, rays7, any_hit=False):
         r = np.ascontiguousarray(rays7, dtype=np.float32).reshape(-1, 7)

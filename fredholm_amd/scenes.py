@@ -90,6 +90,27 @@ def cornell_box(diffuse_only=False):
     return _finish(tris, mats, m)
 
 
+def cornell_box_instanced(diffuse_only=False):
+    """cornell_box() with the short block as an instance of its own: instance 0 is the room, the light and the tall block, instance 1 the short block (faces 12..23).
+    Both start at the identity, so the vertices are the world positions of cornell_box(); move the block with Renderer.set_transforms(*instanced_transforms(offset))."""
+    sc = cornell_box(diffuse_only)
+    inst = np.zeros(sc["indices"].shape[0], np.uint32)
+    inst[12:24] = 1
+    sc["instance_ids"] = inst
+    sc["object_to_world"], sc["world_to_object"] = instanced_transforms((0.0, 0.0, 0.0))
+    return sc
+
+
+def instanced_transforms(offset):
+    """(object_to_world, world_to_object), 2 x 12 floats each, of cornell_box_instanced() with the short block translated by `offset`"""
+    o2w = np.tile(np.asarray([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32), (2, 1))
+    w2o = o2w.copy()
+    off = np.asarray(offset, np.float32)
+    o2w[1, 3::4] = off
+    w2o[1, 3::4] = -off
+    return o2w, w2o
+
+
 CORNELL_CAMERA = dict(origin=(0.0, 1.0, 1.0), fov=0.5 * np.pi, F=100.0, focus=10000.0)  # GUI defaults, controller.h:89-92
 
 

@@ -9,6 +9,8 @@
 // set_mode(Denoiser::Temporal) (FH_DENOISER=temporal) puts temporal accumulation in front of that filter (fh_denoise_temporal): it needs the position and depth
 // guides and, before every denoise(), the camera the frame was rendered with (set_camera); the history lives in the context, reset_history() drops it.  Give the
 // frames of a sequence samples of their own (Renderer::set_seed), or a still camera accumulates one image over and over.
+// set_motion(true) (FH_DENOISER=temporal-motion: Temporal mode with it) switches the context's per-instance motion vectors on (fh_set_denoise_motion): the history of
+// an instance that Renderer::set_time moved is looked up where the instance was.  The switch belongs to the context and is sent with the next denoise().
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -31,6 +33,7 @@ class Denoiser
     const char* env = std::getenv("FH_DENOISER");
     if (env && std::strcmp(env, "guided") == 0) m_mode = Guided;
     if (env && std::strcmp(env, "temporal") == 0) m_mode = Temporal;
+    if (env && std::strcmp(env, "temporal-motion") == 0) { m_mode = Temporal; set_motion(true); }
   }
   enum Mode { Atrous, Guided, Temporal };
   void set_mode(Mode mode) { m_mode = mode; }
@@ -48,6 +51,9 @@ class Denoiser
     m_temporal = fh_temporal_params{alpha_min, max_history, normal_cos_min, plane_tol};
     m_has_temporal = true;
   }
+  // Temporal mode: carry the history of moved instances (fh_set_denoise_motion); takes effect with the next denoise()
+  void set_motion(bool on) { m_motion = on; m_motion_pending = true; }
+  bool motion() const { return m_motion; }
   void reset_history()
   {
     fh_ctx* ctx = m_context ? m_context : cwl::require_context();
@@ -58,6 +64,10 @@ class Denoiser
     fh_ctx* ctx = m_context ? m_context : cwl::require_context();
     if (m_mode == Temporal) {
       if (!m_has_camera) throw std::runtime_error("Denoiser: Temporal mode needs set_camera() before denoise()");
+      if (m_motion_pending) {
+        cwl::check(ctx, fh_set_denoise_motion(ctx, m_motion ? 1 : 0), "fh_set_denoise_motion");
+        m_motion_pending = false;
+      }
       const fh_denoise_inputs in = {reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
                                     reinterpret_cast<const float*>(m_d_position), m_d_depth, reinterpret_cast<const float*>(m_d_moments), m_d_counts};
       cwl::check(ctx, fh_denoise_temporal(ctx, m_width, m_height, &in, &m_camera, m_has_temporal ? &m_temporal : nullptr, nullptr, reinterpret_cast<float*>(m_d_denoised), m_upscale ? 1 : 0),
@@ -92,5 +102,6 @@ class Denoiser
   fh_camera m_camera{};
   fh_temporal_params m_temporal{};
   bool m_has_camera = false, m_has_temporal = false;
+  bool m_motion = false, m_motion_pending = false;
 };
 }  // namespace fredholm

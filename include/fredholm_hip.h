@@ -331,7 +331,7 @@ int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_den
 
 /* -- temporal accumulation in front of the variance-guided denoiser (opt-in; fh_denoise and fh_denoise_guided keep their bits): the reprojection and accumulation
  * stage of SVGF.  fh_denoise_temporal is fh_denoise_guided with ONE stage between its preparation and its passes, which blends (c, v) of the frame with the
- * context's history of the frames before it, found again through the world position (there are no motion vectors: a surface that moved fails the plane stop at its
+ * context's history of the frames before it, found again through the world position (this call knows no motion vectors -- fh_denoise_temporal_motion and fh_set_denoise_motion below add them --: a surface that moved fails the plane stop at its
  * old place and gets no history).  `camera` is the camera the layers were rendered with; position and depth are required; moments and counts stay optional.
  * The context owns the history (on the lead of a group), double buffered: per pixel (c_acc.rgb, v_acc), (P, h) and N, and the camera of the call that wrote it.
  * A change of width x height, fh_denoise_history_reset and fh_ctx_destroy drop it; fh_set_resolution does not.  The first call after that gives fh_denoise_guided's bits.
@@ -373,6 +373,56 @@ int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_d
 int fh_denoise_history_reset(fh_ctx* ctx);
 /* width and height of the history and the frames accumulated since the last reset (0, 0, 0 when there is none); any pointer may be NULL */
 int fh_denoise_history_info(fh_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* frames);
+
+/* -- per-instance motion vectors for the temporal stage (opt-in; every call above keeps its bits).  Motion here is rigid or affine PER INSTANCE
+ * (fh_set_transforms), so where a pixel's surface was in the frame before is one affine map of the position layer, chosen by the instance the pixel sees.
+ *
+ * fh_primary_instances: per pixel of a width x height frame the instance id of the face the pixel's CHIEF RAY hits first, or 0xffffffff for a miss.  `ids` is a
+ * device pointer to width * height words; asynchronous on the context stream; on a group it runs on the lead.  Needs a scene and a built BVH.
+ *   The chief ray of pixel (px, py) is fh_render's camera ray at the pixel centre through the lens centre, in fp32 without contraction, sums in the order written:
+ *     f = 1 / tanf(0.5 * fov);  a = 1 / ((1 + f) - 1 / focus);  ux = -((2 * (px + 0.5) - W) / H),  uy = (2 * (py + 0.5) - H) / H;
+ *     s = normalize((0, 0, f) - (ux, uy, 0));  o = (ux, uy, 0) + ((a + focus) / s.z) * s;  d = normalize(o - (0, 0, f));  d.z = -d.z;
+ *     origin = T * (0, 0, f, 1),  direction = T * (d, 0)   (T = camera.transform; normalize(v) = v * (1 / sqrt(v . v)); row . vector as ((r0 x + r1 y) + r2 z) + r3 w)
+ *   -- the ray whose inverse the temporal stage above states.  It is traced to 1e9 for its closest hit (smaller t, then lower face id), with the any-hit rule for
+ *   cut-outs that fh_render's primary rays follow. */
+int fh_primary_instances(fh_ctx* ctx, const fh_camera* camera, uint32_t width, uint32_t height, uint32_t* ids);
+/* where instance i's surface points and normals were: P' = point * (P, 1) (3 x 4, row major), N' = normal * N (3 x 3, row major) */
+typedef struct fh_motion {
+  float point[12];
+  float normal[9];
+  uint32_t moved; /* 0: all 24 floats of the instance's previous and current matrices have the same bits; the maps are then never applied */
+} fh_motion;
+/* Host only, no context, no GPU.  All four arrays hold n 3 x 4 row-major matrices (12 floats each) as fh_set_transforms takes them.  With L(M) the 3 x 3 of M:
+ *   point  = o2w_prev * w2o_cur   as affine maps: point[4i + j] = (A[4i] * B[j] + A[4i+1] * B[4+j]) + A[4i+2] * B[8+j]  (+ A[4i+3] for j = 3), A = o2w_prev, B = w2o_cur;
+ *   normal = (L(o2w_cur) * L(w2o_prev))^T: normal[3i + j] = (C[4j] * D[i] + C[4j+1] * D[4+i]) + C[4j+2] * D[8+i], C = o2w_cur, D = w2o_prev
+ *            -- the inverse transpose of point's linear part when the w2o are the inverses of the o2w.
+ * Both products are formed in double from the caller's floats and rounded once.  Normals are NOT renormalised: the normal layer is a mean of sample normals and not
+ * of unit length anyway; under non-uniform scale the carried normal's length changes, so the normal stop (a bound on N_b . N'_q) is approximate there.
+ * FH_E_INVALID for n > 0 with a null pointer. */
+int fh_motion_from_transforms(uint32_t n, const float* o2w_prev, const float* w2o_prev, const float* o2w_cur, const float* w2o_cur, fh_motion* out);
+/* fh_denoise_temporal with motion: instance_ids is a device pointer (width * height words, as fh_primary_instances writes them), motion a host array of n_instances
+ * entries, read during the call (it goes to a context-owned device buffer that grows on demand).  The stage above with these changes, per hit pixel p, i = ids[p]:
+ *   p is CARRIED when i < n_instances and motion[i].moved.  Then, with A = motion[i].point, G = motion[i].normal:
+ *     Pb.k = ((A[4k] * P.x + A[4k+1] * P.y) + A[4k+2] * P.z) + A[4k+3],   Nb.k = (G[3k] * N.x + G[3k+1] * N.y) + G[3k+2] * N.z;   otherwise Pb = P, Nb = N, with their bits.
+ *   Not carried and a still camera: the pixel's own tap with weight 1 (the still-camera rule above).
+ *   Every other case (also a carried pixel under a still camera): Pb is projected with the stored camera's M' and f' as above, and the 2 x 2 taps are valid by the
+ *     two stops with (Nb, Pb) in place of (N_p, P_p) and the limit plane_tol * max(Z_p, 1e-3); renormalised; no history unless S >= 1e-3.
+ *   The blend is unchanged, and the history written is (c_acc, v_acc), (P_p, h), N_p: in the CURRENT frame's world space.
+ * When no entry has `moved` set (and when instance_ids, motion are NULL and n_instances is 0) the call is fh_denoise_temporal launch for launch and bit for bit, and
+ * the id plane is never read.  FH_E_INVALID, from the arguments alone, leaving history and output alone: ids without motion or motion without ids; n_instances 0
+ * with either given; a motion entry with a non-finite float; everything fh_denoise_temporal refuses.
+ * Not covered: motion that is not one affine map per instance (skinning, morphs); the id is the chief ray's, so a pixel most of whose samples see another instance
+ * is carried with the wrong map and the two stops decide whether it keeps a history; the lighting change a moving light or occluder causes still lags. */
+int fh_denoise_temporal_motion(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* inputs, const fh_camera* camera, const fh_temporal_params* temporal,
+                               const fh_denoise_params* params, const uint32_t* instance_ids, uint32_t n_instances, const fh_motion* motion, float* denoised, int upscale2x);
+/* The context does the bookkeeping (default off; on a group the switch is broadcast and the work runs on the lead).  While on, every fh_denoise_temporal call keeps,
+ * on the host, a snapshot of the context's instance matrices with the history it writes.  If a snapshot exists, the history is alive, the instance count is the
+ * snapshot's and any instance's matrices differ from it in bits, the call runs fh_primary_instances, fh_motion_from_transforms (previous: the snapshot, current: the
+ * context's) and fh_denoise_temporal_motion itself -- it then needs a built BVH (FH_E_INVALID otherwise, nothing touched); in every other case (the first call, after
+ * fh_denoise_history_reset, after fh_scene_upload, nothing moved) it is today's call launch for launch.  CONTRACT: the layers were rendered with the context's
+ * current transforms.  Switching off drops the snapshot. */
+int fh_set_denoise_motion(fh_ctx* ctx, int on);
+int fh_get_denoise_motion(fh_ctx* ctx, int* on);
 
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */

@@ -31,6 +31,8 @@ int fh_kat_bsdf_ior(fh_ctx* ctx, const fh_material* material, float eta, uint32_
 int fh_kat_sky(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3);          /* uses the context's Hosek state */
 int fh_kat_hosek_state(fh_ctx* ctx, float* out30);                                  /* cooked cfg[3][9] + rad[3] */
 int fh_kat_camera(fh_ctx* ctx, const fh_camera* cam, uint32_t width, uint32_t height, uint32_t seed, uint32_t n, const uint32_t* pixel_idx, const uint32_t* n_spp, float* out6);
+/* the chief rays fh_primary_instances builds (include/fredholm_hip.h), through the same device function: origin.xyz direction.xyz per pixel, row-major (host memory) */
+int fh_kat_chief_rays(fh_ctx* ctx, const fh_camera* cam, uint32_t width, uint32_t height, float* out6);
 int fh_kat_offset_origin(fh_ctx* ctx, uint32_t n, const float* p3, const float* n3, float* out3);
 /* small math blocks that have a reference-built counterpart (oracle/_ref/libref_lut_math_post.so); floats in / out per item:
    ALBEDO_REFLECTION (w.y, roughness, F0) -> 1  lut.cu:985-992     ALBEDO_SHEEN (w.y, roughness) -> 1  lut.cu:1075-1081

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/denoise_bench.py [--out profiles/denoise_guided_bench.json] [--config 3] [--spp 16] [--calls 20] [--temporal] -- what a call of the denoisers costs.
+"""tools/denoise_bench.py [--out profiles/denoise_guided_bench.json] [--config 3] [--spp 16] [--calls 20] [--temporal | --motion] -- what a call of the denoisers costs.
 
 The layers of a BASELINE.json configs[c] frame at 1920x1080 (`--spp` samples, adaptive sampling on at threshold 0 so that the luminance moments exist), then, in this
 one process, the median of `--calls` calls of fh_denoise and of fh_denoise_guided, each followed by one fh_sync and timed from before the call to after the sync:
@@ -9,10 +9,17 @@ and depth.  Prints one JSON line (and writes it to --out).
 --temporal (-> profiles/denoise_temporal_bench.json): instead, two such frames with seeds 1 and 2 from cameras a small step apart (--step, as a fraction of the camera's
 distance from the origin), and the median of `--calls` calls of fh_denoise_temporal that alternate between the two frames -- every call reprojects the other frame's
 history --, of calls that repeat one frame (the still-camera kernel), and of fh_denoise_guided on the same layers in the same process.  The stage's share is the
-difference of the medians; the kernel's own time comes from running this under `rocprofv3 --kernel-trace --stats` (k_temporal)."""
+difference of the medians; the kernel's own time comes from running this under `rocprofv3 --kernel-trace --stats` (k_temporal).
+
+--motion (-> profiles/denoise_motion_bench.json): one such frame, and the median of `--calls` calls of fh_primary_instances and of fh_denoise_temporal_motion under a still
+camera with a motion table that alternates between two small translations (--step) of the scene's largest instance, so that every call carries that instance's pixels;
+beside them fh_denoise_temporal with the camera alternating as in --temporal, and fh_denoise_guided.  The two new kernels' own times come from a
+`rocprofv3 --kernel-trace --stats` run of this leg (k_primary_instances*, k_temporal_motion): `--merge-kernel-stats STATS.csv --out FILE` (no GPU) writes those rows of the
+profiler's kernel_stats.csv into FILE's record as "kernel_us"."""
 import argparse
 import json
 import os
+import re
 import sys
 import tempfile
 import time
@@ -80,6 +87,82 @@ def temporal(a, bench, F, DeviceBuffer, r, w):
             f.write(line + "\n")
 
 
+def motion(a, bench, F, DeviceBuffer, r, w):
+    from fredholm_amd import native as N
+    W, H = w["width"], w["height"]
+    sc = w["scene"] if isinstance(w["scene"], dict) else None
+    inst = None if sc is None else sc.get("instance_ids")
+    o2w = None if sc is None or sc.get("object_to_world") is None else np.asarray(sc["object_to_world"], np.float32).reshape(-1, 12)
+    n_inst = 1 if o2w is None else o2w.shape[0]
+    ident = np.tile(np.asarray([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32), (n_inst, 1))
+    base_o = ident if o2w is None else o2w
+    base_w = ident if o2w is None else np.asarray(sc["world_to_object"], np.float32).reshape(-1, 12)
+    target = 0 if inst is None else int(np.bincount(np.asarray(inst, np.int64), minlength=n_inst).argmax())
+    o = np.asarray(w["camera"]["origin"], np.float64)
+    step = a.step * max(float(np.linalg.norm(o)), 1.0)
+    tables = []
+    for sign in (1.0, -1.0):  # the instance `step` further along x in world space: o2w' = T o2w, w2o' = w2o T^-1
+        cur_o, cur_w = base_o.copy(), base_w.copy()
+        cur_o[target, 3] += np.float32(sign * step)
+        cur_w[target, 3::4] -= cur_w[target, 0::4][:3] * np.float32(sign * step)
+        tables.append(N.motion_from_transforms(base_o, base_w, cur_o, cur_w))
+    cams = [F.Camera(**w["camera"]), F.Camera(**dict(w["camera"], origin=tuple(o + np.array([step, 0.0, 0.0]))))]
+    L = F.RenderLayer(r, W, H)
+    r.render(cams[0], w["bg"], L, a.spp, w["depth"])
+    m, c, out, ids = DeviceBuffer(r, 8 * W * H), DeviceBuffer(r, 4 * W * H), DeviceBuffer(r, 16 * W * H), DeviceBuffer(r, 4 * W * H)
+    r.get_luminance_moments(m.ptr)
+    r.get_sample_counts(c.ptr)
+    r.primary_instances(cams[0], W, H, ids.ptr)
+    r.wait_for_completion()
+    id_plane = ids.download(np.uint32, (H, W))
+    p = L.ptrs
+    turn = [0]
+
+    def call_motion():
+        turn[0] += 1
+        r.denoise_temporal_motion(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], cams[0], ids.ptr, tables[turn[0] & 1], m.ptr, c.ptr)
+
+    def call_temporal():
+        turn[0] += 1
+        r.denoise_temporal(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], cams[turn[0] & 1], m.ptr, c.ptr)
+
+    def call_guided():
+        r.denoise_guided(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], m.ptr, c.ptr)
+    rec = {"workload": w["name"], "width": W, "height": H, "spp": a.spp, "calls": a.calls, "instance_step": step, "instances": n_inst, "moved_instance": target,
+           "carried_pixel_share": float((id_plane == target).mean()), "missed_pixel_share": float((id_plane == 0xFFFFFFFF).mean()), "source_fingerprint": bench.source_fingerprint(),
+           "fh_denoise_guided_ms": median_ms(r, call_guided, a.calls),
+           "fh_primary_instances_ms": median_ms(r, lambda: r.primary_instances(cams[0], W, H, ids.ptr), a.calls),
+           "fh_denoise_temporal_motion_ms": median_ms(r, call_motion, a.calls),
+           "fh_denoise_temporal_moving_ms": median_ms(r, call_temporal, a.calls),
+           "fh_denoise_guided_again_ms": median_ms(r, call_guided, a.calls)}
+    rec["stage_motion_ms_by_difference"] = rec["fh_denoise_temporal_motion_ms"] - rec["fh_denoise_guided_ms"]
+    rec["stage_moving_ms_by_difference"] = rec["fh_denoise_temporal_moving_ms"] - rec["fh_denoise_guided_ms"]
+    r.close()
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+def merge_kernel_stats(csv_path, json_path):
+    """the k_primary_instances* and k_temporal* rows of a rocprofv3 kernel_stats.csv into the record of json_path: calls, mean, min and max in microseconds"""
+    import csv
+    rec = json.loads(open(json_path).read())
+    rows = {}
+    for row in csv.DictReader(open(csv_path)):
+        name = row["Name"]
+        if "k_primary_instances" in name or "k_temporal" in name:
+            short = re.search(r"k_(primary_instances|temporal)\w*(<[^>]*>)?", name).group(0)
+            rows[short] = {"calls": int(row["Calls"]), "mean": float(row["AverageNs"]) / 1e3, "min": float(row["MinNs"]) / 1e3, "max": float(row["MaxNs"]) / 1e3}
+    rec["kernel_us"] = rows
+    rec["kernel_us_source"] = "rocprofv3 --kernel-trace --stats of a run of this leg of its own (warm-up calls included)"
+    line = json.dumps(rec)
+    print(line)
+    with open(json_path, "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=3)
@@ -87,8 +170,12 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--temporal", action="store_true")
+    ap.add_argument("--motion", action="store_true")
     ap.add_argument("--step", type=float, default=0.002)
+    ap.add_argument("--merge-kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of the --motion leg: add its rows to the record in --out and exit (no GPU)")
     a = ap.parse_args()
+    if a.merge_kernel_stats:
+        return merge_kernel_stats(a.merge_kernel_stats, a.out)
 
     import bench
     import fredholm_amd as F
@@ -104,6 +191,8 @@ def main():
     r.set_adaptive_sampling(0.0)
     if a.temporal:
         return temporal(a, bench, F, DeviceBuffer, r, w)
+    if a.motion:
+        return motion(a, bench, F, DeviceBuffer, r, w)
     L = F.RenderLayer(r, W, H)
     r.render(F.Camera(**w["camera"]), w["bg"], L, a.spp, w["depth"])
     moments, counts, out = DeviceBuffer(r, 8 * W * H), DeviceBuffer(r, 4 * W * H), DeviceBuffer(r, 16 * W * H)

@@ -5,7 +5,13 @@ The sequence of the device's quality test (tests/test_gpu_denoise_temporal.py: Q
 8 frames with seeds 1..8 -- and denoised by that file's float64 restatement of fh_denoise_temporal and of fh_denoise_guided.  The luminance moments are rebuilt
 from the running means the checker leaves after every sample (x_s = s * mean_s - (s - 1) * mean_(s-1)).  Prints, for the last frame with moments against the
 1024-spp truth at the last camera, relMSE of the unfiltered frame, of the guided filter alone and of temporal accumulation, and their ratio R, at 16 spp per frame
-with the moving camera, at 4 spp per frame, and for a still camera; then R of the first sequence for other parameter values.  One JSON line at the end."""
+with the moving camera, at 4 spp per frame, and for a still camera; then R of the first sequence for other parameter values.  One JSON line at the end.
+
+--motion replays the sequence of tests/test_gpu_denoise_motion.py instead (MOTION_QUALITY: a still camera, the short block of cornell_box_instanced() moving 0.05 per
+frame) through that file's float64 restatement of fh_denoise_temporal_motion and through the plain one, and prints relMSE over the pixels whose chief ray sees the block
+in the last frame and over the whole frame: R = relMSE(motion) / relMSE(plain temporal) is what the device test's margin is taken from.  The checker renders the block
+where the instance transform puts it (a translation: the baked vertices are the device's world-space vertices bit for bit); the id plane is the chief rays' closest
+hit, by brute force in float64."""
 import argparse
 import importlib.util
 import json
@@ -68,10 +74,127 @@ def build():
     return T, sequences, ratio
 
 
+def _load(name, filename):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", filename))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def chief_ids(scene, cam, w, h):
+    """instance of the closest triangle along every pixel's chief ray (float64 Moeller-Trumbore over all faces; 0xffffffff: a miss)"""
+    t = np.asarray(cam.params()[:12], np.float64).reshape(3, 4)
+    f = 1.0 / np.tan(0.5 * cam.m_fov)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    d = np.stack([(2.0 * (xx + 0.5) - w) / h, -(2.0 * (yy + 0.5) - h) / h, np.full(xx.shape, -f)], axis=2)  # (ux = -(...), the lens centre minus the sensor point, z flipped)
+    d = (d / np.linalg.norm(d, axis=2, keepdims=True)) @ t[:, :3].T
+    o = t[:, :3] @ np.array([0.0, 0.0, f]) + t[:, 3]
+    v = np.asarray(scene["vertices"], np.float64)[np.asarray(scene["indices"])]
+    best, ids = np.full((h, w), np.inf), np.full((h, w), 0xFFFFFFFF, np.uint32)
+    for k in range(v.shape[0]):
+        e1, e2 = v[k, 1] - v[k, 0], v[k, 2] - v[k, 0]
+        pv = np.cross(d, e2)
+        det = pv @ e1
+        with np.errstate(all="ignore"):
+            inv = 1.0 / det
+            tv = o - v[k, 0]
+            u = (pv @ tv) * inv
+            qv = np.cross(tv, e1)
+            vv = (d @ qv) * inv
+            tt = (qv @ e2) * inv
+        ok = (np.abs(det) > 1e-12) & (u >= 0) & (vv >= 0) & (u + vv <= 1) & (tt > 0) & (tt < best)
+        best = np.where(ok, tt, best)
+        ids = np.where(ok, np.uint32(scene["instance_ids"][k]), ids)
+    return ids
+
+
+def motion_replay(out):
+    """the moving-block sequence: relMSE of plain temporal accumulation and of the motion call, over the block's pixels and over the frame"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    M = _load("test_gpu_denoise_motion", "test_gpu_denoise_motion.py")
+    T = M.T
+    from fredholm_amd import native as N
+    from fredholm_amd import scenes
+    from oracle import pyoracle as O
+    import fredholm_amd as F
+
+    q = M.MOTION_QUALITY
+    w, h, depth, spp = q["w"], q["h"], q["depth"], q["spp"]
+    threads = O.hardware_threads()
+    cam = F.Camera(**scenes.CORNELL_CAMERA)
+
+    def baked(offset):
+        sc = scenes.cornell_box_instanced()
+        v = sc["vertices"].copy()
+        block = np.asarray(sc["indices"])[sc["instance_ids"] == 1].reshape(-1)
+        v[block] = v[block] + np.asarray(offset, np.float32)  # (o2w is the identity plus a translation: 1 * x + t in float32, the device's world-space vertex)
+        sc["vertices"] = v
+        return sc
+
+    def frame(ref, n, seed):
+        lo = ref.new_layers(w, h)
+        s1, s2, prev = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, 3))
+        for s in range(1, n + 1):
+            ref.render(cam.params(), w, h, lo, 1, depth, seed=seed, n_threads=threads)
+            mean = lo["beauty"][..., :3].astype(np.float64)
+            x = s * mean - (s - 1) * prev
+            prev = mean
+            y = x[..., 0] * float(T.LUM[0]) + x[..., 1] * float(T.LUM[1]) + x[..., 2] * float(T.LUM[2])
+            s1 += y
+            s2 += y * y
+        res = {k: lo[k].copy() for k in ("beauty", "normal", "albedo", "position", "depth")}
+        res["moments"] = np.stack([s1 / n, s2 / n], axis=2).astype(np.float32)
+        res["counts"] = np.full((h, w), n, np.uint32)
+        return res
+
+    offsets = [M.motion_quality_offset(k) for k in range(q["frames"])]
+    frames, ids = [], None
+    for k, off in enumerate(offsets):
+        sc = baked(off)
+        plain_scene = {key: val for key, val in sc.items() if key not in ("instance_ids", "object_to_world", "world_to_object")}
+        frames.append(frame(O.Scene(plain_scene), spp, 1 + k))
+        ids = chief_ids(sc, cam, w, h)
+        frames[-1]["ids"] = ids
+        print(f"frame {k}: block at {off}, {int((ids == 1).sum())} pixels see it")
+    ref = O.Scene({key: val for key, val in baked(offsets[-1]).items() if key not in ("instance_ids", "object_to_world", "world_to_object")})
+    lo = ref.new_layers(w, h)
+    for _ in range(q["truth_spp"]):
+        ref.render(cam.params(), w, h, lo, 1, depth, seed=1000, n_threads=threads)
+    truth = lo["beauty"]
+    plain, motion = M.MotionRestatement(np.float64, np.exp), M.MotionRestatement(np.float64, np.exp)
+    for k, layers in enumerate(frames):
+        out_plain = plain.call(layers, cam.params())
+        if k == 0:
+            out_motion = motion.call(layers, cam.params())
+        else:
+            table = N.motion_from_transforms(*scenes.instanced_transforms(offsets[k - 1]), *scenes.instanced_transforms(offsets[k]))
+            out_motion = motion.call_motion(layers, cam.params(), layers["ids"], M.table_arrays(table))
+    guided = T.Restatement(np.float64, np.exp).call(frames[-1], cam.params(), spatial_only=True)
+    box = ids == 1
+
+    def err(x, mask=None):
+        return T._relmse(x, truth) if mask is None else T._relmse(x[mask][None], truth[mask][None])
+    rec = {"replay": True, "motion": True, "quality": q, "defaults": T.TDEF, "block_pixels": int(box.sum()),
+           "block": dict(unfiltered=err(frames[-1]["beauty"], box), guided=err(guided, box), temporal=err(out_plain, box), motion=err(out_motion, box)),
+           "frame": dict(unfiltered=err(frames[-1]["beauty"]), guided=err(guided), temporal=err(out_plain), motion=err(out_motion)),
+           "block_with_history": dict(temporal=float(plain.have[box].mean()), motion=float(motion.have[box].mean())),
+           "block_mean_history": dict(temporal=float(plain.hist["h"][box].mean()), motion=float(motion.hist["h"][box].mean()))}
+    rec["R"] = rec["block"]["motion"] / rec["block"]["temporal"]
+    rec["R_frame"] = rec["frame"]["motion"] / rec["frame"]["temporal"]
+    line = json.dumps(rec)
+    print(line)
+    if out:
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--motion", action="store_true", help="replay the moving-block sequence of tests/test_gpu_denoise_motion.py instead")
     a = ap.parse_args()
+    if a.motion:
+        return motion_replay(a.out)
     T, sequences, ratio = build()
     rec = {"replay": True, "quality": T.QUALITY, "defaults": T.TDEF}
     for name, frames in sequences.items():
