@@ -1346,6 +1346,26 @@ int fh_denoise_history_reset(fh_ctx* ctx)
   return FH_OK;
 }
 
+// the switch of the clipped temporal stage: broadcast on a group like fh_set_denoise_motion (the work it switches on runs on the lead)
+int fh_set_denoise_response(fh_ctx* ctx, const fh_response_params* params)
+{
+  if (const char* why = response_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_response: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_response(m_, params));
+  if (!ctx) return FH_E_INVALID;
+  ctx->denoise_response = params ? 1 : 0;
+  if (params) ctx->response_gamma = params->gamma;
+  return FH_OK;
+}
+
+int fh_get_denoise_response(fh_ctx* ctx, int* on, fh_response_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->denoise_response;
+  if (params) params->gamma = ctx->response_gamma;
+  return FH_OK;
+}
+
 int fh_denoise_history_info(fh_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* frames)
 {
   FH_GROUP_LEAD(ctx);

@@ -258,6 +258,9 @@ struct fh_ctx {
   hipEvent_t ev_motion = nullptr;
   uint32_t* d_motion_ids = nullptr;
   size_t motion_ids_pixels = 0;
+  // fh_set_denoise_response (denoise.hip: k_temporal_response): while on, the temporal stage clips the history it found to the current frame's 5 x 5 colour box
+  int denoise_response = 0;
+  float response_gamma = 1.0f;
 
   // stats
   fh_stats stats{};

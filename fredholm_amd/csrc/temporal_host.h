@@ -60,4 +60,11 @@ inline const char* temporal_refusal(uint32_t width, uint32_t height, const fh_de
   return nullptr;
 }
 
+// why fh_set_denoise_response refuses these parameters, or nullptr (NULL parameters switch the mode off and are never refused)
+inline const char* response_refusal(const fh_response_params* params)
+{
+  if (params && (!(params->gamma > 0.0f) || !std::isfinite(params->gamma))) return "gamma must be finite and > 0";
+  return nullptr;
+}
+
 }  // namespace fh

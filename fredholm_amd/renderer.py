@@ -571,6 +571,21 @@ class Renderer:
         self._ck(N.lib().fh_get_denoise_motion(self._ctx, C.byref(on)), "fh_get_denoise_motion")
         return bool(on.value)
 
+    def set_denoise_response(self, gamma=1.0):
+        """fh_set_denoise_response: while on, denoise_temporal and denoise_temporal_motion clamp the history they found to mean +- gamma standard deviations of the
+        current frame's colour in a 5 x 5 window before blending, and shorten it by how far outside it lay: a change of lighting no longer lags by 1 / alpha_min frames"""
+        p = N.ResponseParamsC(float(gamma))
+        self._ck(N.lib().fh_set_denoise_response(self._ctx, C.byref(p)), "fh_set_denoise_response")
+
+    def clear_denoise_response(self):
+        self._ck(N.lib().fh_set_denoise_response(self._ctx, None), "fh_set_denoise_response")
+
+    def get_denoise_response(self):
+        """(on, gamma): the switch and the gamma last set (1 before any)"""
+        on, p = C.c_int(0), N.ResponseParamsC(0.0)
+        self._ck(N.lib().fh_get_denoise_response(self._ctx, C.byref(on), C.byref(p)), "fh_get_denoise_response")
+        return bool(on.value), float(p.gamma)
+
     def reset_denoise_history(self):
         """drop the history of denoise_temporal (fh_denoise_history_reset)"""
         self._ck(N.lib().fh_denoise_history_reset(self._ctx), "fh_denoise_history_reset")

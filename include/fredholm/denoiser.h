@@ -11,6 +11,8 @@
 // frames of a sequence samples of their own (Renderer::set_seed), or a still camera accumulates one image over and over.
 // set_motion(true) (FH_DENOISER=temporal-motion: Temporal mode with it) switches the context's per-instance motion vectors on (fh_set_denoise_motion): the history of
 // an instance that Renderer::set_time moved is looked up where the instance was.  The switch belongs to the context and is sent with the next denoise().
+// set_response(true, gamma) (FH_DENOISER=temporal-response, temporal-motion-response) switches the context's history clipping on (fh_set_denoise_response): the
+// history is clamped to the current frame's local colour box before the blend, so a change of lighting does not lag.  Sent with the next denoise() likewise.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -34,6 +36,8 @@ class Denoiser
     if (env && std::strcmp(env, "guided") == 0) m_mode = Guided;
     if (env && std::strcmp(env, "temporal") == 0) m_mode = Temporal;
     if (env && std::strcmp(env, "temporal-motion") == 0) { m_mode = Temporal; set_motion(true); }
+    if (env && std::strcmp(env, "temporal-response") == 0) { m_mode = Temporal; set_response(true); }
+    if (env && std::strcmp(env, "temporal-motion-response") == 0) { m_mode = Temporal; set_motion(true); set_response(true); }
   }
   enum Mode { Atrous, Guided, Temporal };
   void set_mode(Mode mode) { m_mode = mode; }
@@ -54,6 +58,10 @@ class Denoiser
   // Temporal mode: carry the history of moved instances (fh_set_denoise_motion); takes effect with the next denoise()
   void set_motion(bool on) { m_motion = on; m_motion_pending = true; }
   bool motion() const { return m_motion; }
+  // Temporal mode: clip the history to the current frame's colour box (fh_set_denoise_response); takes effect with the next denoise()
+  void set_response(bool on, float gamma = 1.0f) { m_response = on; m_response_gamma = gamma; m_response_pending = true; }
+  bool response() const { return m_response; }
+  float response_gamma() const { return m_response_gamma; }
   void reset_history()
   {
     fh_ctx* ctx = m_context ? m_context : cwl::require_context();
@@ -67,6 +75,11 @@ class Denoiser
       if (m_motion_pending) {
         cwl::check(ctx, fh_set_denoise_motion(ctx, m_motion ? 1 : 0), "fh_set_denoise_motion");
         m_motion_pending = false;
+      }
+      if (m_response_pending) {
+        const fh_response_params rp = {m_response_gamma};
+        cwl::check(ctx, fh_set_denoise_response(ctx, m_response ? &rp : nullptr), "fh_set_denoise_response");
+        m_response_pending = false;
       }
       const fh_denoise_inputs in = {reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
                                     reinterpret_cast<const float*>(m_d_position), m_d_depth, reinterpret_cast<const float*>(m_d_moments), m_d_counts};
@@ -103,5 +116,7 @@ class Denoiser
   fh_temporal_params m_temporal{};
   bool m_has_camera = false, m_has_temporal = false;
   bool m_motion = false, m_motion_pending = false;
+  bool m_response = false, m_response_pending = false;
+  float m_response_gamma = 1.0f;
 };
 }  // namespace fredholm

@@ -412,7 +412,8 @@ int fh_motion_from_transforms(uint32_t n, const float* o2w_prev, const float* w2
  * the id plane is never read.  FH_E_INVALID, from the arguments alone, leaving history and output alone: ids without motion or motion without ids; n_instances 0
  * with either given; a motion entry with a non-finite float; everything fh_denoise_temporal refuses.
  * Not covered: motion that is not one affine map per instance (skinning, morphs); the id is the chief ray's, so a pixel most of whose samples see another instance
- * is carried with the wrong map and the two stops decide whether it keeps a history; the lighting change a moving light or occluder causes still lags. */
+ * is carried with the wrong map and the two stops decide whether it keeps a history; the lighting change a moving light or occluder causes lags unless
+ * fh_set_denoise_response (below) is on, which shortens the lag and does not remove it. */
 int fh_denoise_temporal_motion(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* inputs, const fh_camera* camera, const fh_temporal_params* temporal,
                                const fh_denoise_params* params, const uint32_t* instance_ids, uint32_t n_instances, const fh_motion* motion, float* denoised, int upscale2x);
 /* The context does the bookkeeping (default off; on a group the switch is broadcast and the work runs on the lead).  While on, every fh_denoise_temporal call keeps,
@@ -423,6 +424,43 @@ int fh_denoise_temporal_motion(fh_ctx* ctx, uint32_t width, uint32_t height, con
  * current transforms.  Switching off drops the snapshot. */
 int fh_set_denoise_motion(fh_ctx* ctx, int on);
 int fh_get_denoise_motion(fh_ctx* ctx, int* on);
+
+/* -- history clipping for the temporal stage (opt-in, default off; with it off every call above keeps its bits and its launches).  Nothing in the layers tells the
+ * stage that the radiance of an unmoved surface changed: a history that passes the two stops is blended with weight 1 - alpha_min however wrong its colour has become,
+ * so a moving light or occluder lags by 1 / alpha_min frames.  While this switch is on, fh_denoise_temporal and fh_denoise_temporal_motion (also the calls
+ * fh_set_denoise_motion makes itself) clamp the history colour, before the blend, to the box mean +- gamma * standard deviation of the CURRENT frame's colour in a
+ * fixed 5 x 5 window (the variance clipping of temporal anti-aliasing), and shorten the history by how far outside the box it lay.
+ * A call without a history -- the first, after a reset, after a change of size -- is unchanged: fh_denoise_guided's bits.
+ *
+ * The changes to the stage, for a hit pixel p that HAS a history, after (c_h, v_h, h_h) are found exactly as above (the own tap, the 2 x 2 look-up or the carried
+ * look-up); fp32 without contraction, / and sqrt correctly rounded, sums in the order written; c: the preparation's colour of the current frame.
+ *   1 Window: for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = p + (dx, dy).  q COUNTS when it lies inside the frame (taps outside are skipped, not clamped),
+ *     N_q != 0 and (N_p.x * N_q.x + N_p.y * N_q.y) + N_p.z * N_q.z >= normal_cos_min; the centre always counts (a mean normal can be shorter than
+ *     sqrt(normal_cos_min)).  n = the count, as a float; per channel k: S1_k = sum c_q.k, S2_k = sum c_q.k * c_q.k over the counting taps in that order.
+ *   2 Box: mu_k = S1_k / n,  var_k = fmax(S2_k / n - mu_k * mu_k, 0),  sd_k = sqrt(var_k),  lo_k = mu_k - gamma * sd_k,  hi_k = mu_k + gamma * sd_k.
+ *   3 Too few taps: n < 2: cc = c_h, u = 0.
+ *   4 Clip: otherwise cc_k = fmin(fmax(c_h.k, lo_k), hi_k),  u_k = |cc_k - c_h.k| / (gamma * sd_k + 1e-6),  u = fmax(fmax(u_r, u_g), u_b).
+ *   5 Shortened history: k1 = 1 + u,  h_h' = h_h / k1,  v_h' = v_h * k1 (u = 0 gives both with their bits).  The blend is the one above with (cc, v_h', h_h') in
+ *     place of (c_h, v_h, h_h).  What the history stores and what the passes read are as above.
+ *   6 fmax and fmin are C's: a NaN operand loses (numpy's maximum / minimum return it instead).  finite() bounds the beauty, not c * c: for |c_q.k| above
+ *     1.8e19 the square is + infinity and so is S2_k.  While mu_k * mu_k is finite, var_k = sd_k = + infinity, the box is (-inf, +inf), cc_k = c_h.k and
+ *     u_k = 0 / inf = 0: such a window does not clip channel k.  When mu_k * mu_k overflows as well, inf - inf is NaN, fmax drops it, var_k = 0 and the box is
+ *     the point mu_k: cc_k = mu_k, u is of the order 1e6 * |mu_k - c_h.k|, h_h' rounds to 0, so h = 1, a = 1, b = 0 and every pixel whose window counts that tap
+ *     drops its history: c_acc = 0 * mu_k + c = c and v_acc = 0 * (v_h * k1) + v = v, both with their bits, as long as mu_k and v_h * k1 are finite.  They are not
+ *     always: v_h * k1 overflows once u exceeds about 3e38 / v_h (a tap above about 1e32 / v_h), and then v_acc = 0 * inf = NaN; and a tap that is + infinity itself
+ *     (finite() passes a beauty of 3e38, which the division by an albedo of 0.01 takes past FLT_MAX) gives mu_k = cc_k = + infinity and c_acc.k = 0 * inf = NaN.
+ *     In both cases ALL pixels whose window counts the tap (up to 25) get the NaN, where the plain stage has a non-finite value in that one pixel only; the
+ *     passes keep it out of no neighbour.  Not guarded: a frame with radiance above 1e30 is not one this filter is for.
+ * Not covered: where the window straddles an emitter and what surrounds it, its standard deviation is large, the box loose, and a moved emitter still lags
+ * (DESIGN.md 4a gives the figures); window radius is not a parameter. */
+typedef struct fh_response_params {
+  float gamma; /* half-width of the clip box in standard deviations, finite and > 0; default 1 */
+} fh_response_params;
+/* params == NULL: off.  The switch lives on the context like fh_set_denoise_motion: broadcast on a group, the work runs on the lead.  FH_E_INVALID, decided from the
+ * arguments alone, for a gamma that is not finite or <= 0; the switch then stays as it was.  Takes effect with the next call; the history is kept. */
+int fh_set_denoise_response(fh_ctx* ctx, const fh_response_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the gamma last set (1 before any) */
+int fh_get_denoise_response(fh_ctx* ctx, int* on, fh_response_params* params);
 
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/denoise_bench.py [--out profiles/denoise_guided_bench.json] [--config 3] [--spp 16] [--calls 20] [--temporal | --motion] -- what a call of the denoisers costs.
+"""tools/denoise_bench.py [--out profiles/denoise_guided_bench.json] [--config 3] [--spp 16] [--calls 20] [--temporal | --motion | --response] -- what a call of the denoisers costs.
 
 The layers of a BASELINE.json configs[c] frame at 1920x1080 (`--spp` samples, adaptive sampling on at threshold 0 so that the luminance moments exist), then, in this
 one process, the median of `--calls` calls of fh_denoise and of fh_denoise_guided, each followed by one fh_sync and timed from before the call to after the sync:
@@ -15,7 +15,13 @@ difference of the medians; the kernel's own time comes from running this under `
 camera with a motion table that alternates between two small translations (--step) of the scene's largest instance, so that every call carries that instance's pixels;
 beside them fh_denoise_temporal with the camera alternating as in --temporal, and fh_denoise_guided.  The two new kernels' own times come from a
 `rocprofv3 --kernel-trace --stats` run of this leg (k_primary_instances*, k_temporal_motion): `--merge-kernel-stats STATS.csv --out FILE` (no GPU) writes those rows of the
-profiler's kernel_stats.csv into FILE's record as "kernel_us"."""
+profiler's kernel_stats.csv into FILE's record as "kernel_us".
+
+--response (-> profiles/denoise_response_bench.json): the two frames of --temporal and the id plane and alternating tables of --motion, and the median of `--calls` calls of
+fh_denoise_temporal (cameras alternating; one frame repeated) and of fh_denoise_temporal_motion with fh_set_denoise_response off and then on (--gamma), in one process, beside
+fh_denoise_guided.  The kernels' own times come from a `rocprofv3 --kernel-trace --stats` run of this leg, in which k_temporal<1>, k_temporal<2>, k_temporal_motion, the
+three k_temporal_response and the k_guided_pass instances all run: `--merge-kernel-stats STATS.csv --out FILE` adds them (with the passes' rows), and
+`--resource-usage LOG` the registers, LDS, scratch and occupancy hipcc's -Rpass-analysis=kernel-resource-usage printed for those kernels when denoise.hip was built."""
 import argparse
 import json
 import os
@@ -87,9 +93,10 @@ def temporal(a, bench, F, DeviceBuffer, r, w):
             f.write(line + "\n")
 
 
-def motion(a, bench, F, DeviceBuffer, r, w):
+def moving_instance(a, F, w):
+    """what the --motion and --response legs share: the scene's instance with the most faces, `step` (--step x the camera's distance from the origin), the two motion tables
+    that carry that instance by + step and - step along x in world space (o2w' = T o2w, w2o' = w2o T^-1), and the workload's camera with a second one `step` to its side"""
     from fredholm_amd import native as N
-    W, H = w["width"], w["height"]
     sc = w["scene"] if isinstance(w["scene"], dict) else None
     inst = None if sc is None else sc.get("instance_ids")
     o2w = None if sc is None or sc.get("object_to_world") is None else np.asarray(sc["object_to_world"], np.float32).reshape(-1, 12)
@@ -101,12 +108,18 @@ def motion(a, bench, F, DeviceBuffer, r, w):
     o = np.asarray(w["camera"]["origin"], np.float64)
     step = a.step * max(float(np.linalg.norm(o)), 1.0)
     tables = []
-    for sign in (1.0, -1.0):  # the instance `step` further along x in world space: o2w' = T o2w, w2o' = w2o T^-1
+    for sign in (1.0, -1.0):
         cur_o, cur_w = base_o.copy(), base_w.copy()
         cur_o[target, 3] += np.float32(sign * step)
         cur_w[target, 3::4] -= cur_w[target, 0::4][:3] * np.float32(sign * step)
         tables.append(N.motion_from_transforms(base_o, base_w, cur_o, cur_w))
     cams = [F.Camera(**w["camera"]), F.Camera(**dict(w["camera"], origin=tuple(o + np.array([step, 0.0, 0.0]))))]
+    return n_inst, target, step, tables, cams
+
+
+def motion(a, bench, F, DeviceBuffer, r, w):
+    W, H = w["width"], w["height"]
+    n_inst, target, step, tables, cams = moving_instance(a, F, w)
     L = F.RenderLayer(r, W, H)
     r.render(cams[0], w["bg"], L, a.spp, w["depth"])
     m, c, out, ids = DeviceBuffer(r, 8 * W * H), DeviceBuffer(r, 4 * W * H), DeviceBuffer(r, 16 * W * H), DeviceBuffer(r, 4 * W * H)
@@ -145,6 +158,83 @@ def motion(a, bench, F, DeviceBuffer, r, w):
             f.write(line + "\n")
 
 
+def response(a, bench, F, DeviceBuffer, r, w):
+    W, H = w["width"], w["height"]
+    n_inst, target, step, tables, cams = moving_instance(a, F, w)
+    frames = []
+    for k, cam in enumerate(cams):
+        L = F.RenderLayer(r, W, H)
+        r.init_render_states()
+        r.seed = 1 + k
+        r.render(cam, w["bg"], L, a.spp, w["depth"])
+        m, c = DeviceBuffer(r, 8 * W * H), DeviceBuffer(r, 4 * W * H)
+        r.get_luminance_moments(m.ptr)
+        r.get_sample_counts(c.ptr)
+        r.wait_for_completion()
+        frames.append((cam, L.ptrs, m, c))
+    out, ids = DeviceBuffer(r, 16 * W * H), DeviceBuffer(r, 4 * W * H)
+    r.primary_instances(cams[0], W, H, ids.ptr)
+    r.wait_for_completion()
+    turn = [0]
+
+    def call_temporal(alternate):
+        cam, p, m, c = frames[turn[0] & 1 if alternate else 0]
+        turn[0] += 1
+        r.denoise_temporal(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], cam, m.ptr, c.ptr)
+
+    def call_motion():
+        cam, p, m, c = frames[0]
+        turn[0] += 1
+        r.denoise_temporal_motion(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], cam, ids.ptr, tables[turn[0] & 1], m.ptr, c.ptr)
+
+    def call_guided():
+        cam, p, m, c = frames[0]
+        r.denoise_guided(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], m.ptr, c.ptr)
+    rec = {"workload": w["name"], "width": W, "height": H, "spp": a.spp, "calls": a.calls, "camera_step": step, "gamma": a.gamma, "source_fingerprint": bench.source_fingerprint(),
+           "fh_denoise_guided_ms": median_ms(r, call_guided, a.calls)}
+    for name, gamma in (("", None), ("response_", a.gamma)):
+        if gamma is None:
+            r.clear_denoise_response()
+        else:
+            r.set_denoise_response(gamma)
+        rec[f"fh_denoise_temporal_{name}moving_ms"] = median_ms(r, lambda: call_temporal(True), a.calls)
+        rec[f"fh_denoise_temporal_{name}still_ms"] = median_ms(r, lambda: call_temporal(False), a.calls)
+        rec[f"fh_denoise_temporal_motion_{name}ms"] = median_ms(r, call_motion, a.calls)
+    r.clear_denoise_response()
+    rec["fh_denoise_guided_again_ms"] = median_ms(r, call_guided, a.calls)
+    for leg in ("moving", "still"):
+        rec[f"response_{leg}_ms_by_difference"] = rec[f"fh_denoise_temporal_response_{leg}_ms"] - rec[f"fh_denoise_temporal_{leg}_ms"]
+    rec["response_motion_ms_by_difference"] = rec["fh_denoise_temporal_motion_response_ms"] - rec["fh_denoise_temporal_motion_ms"]
+    r.close()
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+def merge_resource_usage(log_path, json_path):
+    """what hipcc -Rpass-analysis=kernel-resource-usage printed for the temporal kernels and the passes, into the record of json_path"""
+    rec = json.loads(open(json_path).read())
+    rows, name = {}, None
+    for line in open(log_path):
+        m = re.search(r"remark: +(Function Name|[A-Za-z ]+(?: \[[^\]]*\])?): +(\S+)", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            name = m.group(2) if ("k_temporal" in m.group(2) or "k_guided_pass" in m.group(2)) else None
+            if name:
+                rows[name] = {}
+        elif name and m.group(1).split(" [")[0] in ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize", "Occupancy", "LDS Size"):
+            rows[name][m.group(1).split(" [")[0]] = int(m.group(2))
+    rec["resource_usage"] = rows
+    rec["resource_usage_source"] = "hipcc -Rpass-analysis=kernel-resource-usage on denoise.hip with the Makefile's flags (mangled names)"
+    line = json.dumps(rec)
+    print(line)
+    with open(json_path, "w") as f:
+        f.write(line + "\n")
+
+
 def merge_kernel_stats(csv_path, json_path):
     """the k_primary_instances* and k_temporal* rows of a rocprofv3 kernel_stats.csv into the record of json_path: calls, mean, min and max in microseconds"""
     import csv
@@ -152,8 +242,8 @@ def merge_kernel_stats(csv_path, json_path):
     rows = {}
     for row in csv.DictReader(open(csv_path)):
         name = row["Name"]
-        if "k_primary_instances" in name or "k_temporal" in name:
-            short = re.search(r"k_(primary_instances|temporal)\w*(<[^>]*>)?", name).group(0)
+        if "k_primary_instances" in name or "k_temporal" in name or ("k_guided_pass" in name and rec.get("gamma") is not None):
+            short = re.search(r"k_(primary_instances|temporal|guided_pass)\w*(<[^>]*>)?", name).group(0)
             rows[short] = {"calls": int(row["Calls"]), "mean": float(row["AverageNs"]) / 1e3, "min": float(row["MinNs"]) / 1e3, "max": float(row["MaxNs"]) / 1e3}
     rec["kernel_us"] = rows
     rec["kernel_us_source"] = "rocprofv3 --kernel-trace --stats of a run of this leg of its own (warm-up calls included)"
@@ -171,11 +261,16 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--motion", action="store_true")
+    ap.add_argument("--response", action="store_true")
+    ap.add_argument("--gamma", type=float, default=1.0, help="--response: the gamma of fh_set_denoise_response")
     ap.add_argument("--step", type=float, default=0.002)
+    ap.add_argument("--resource-usage", default="", help="a log of hipcc -Rpass-analysis=kernel-resource-usage on denoise.hip: add its figures to the record in --out and exit (no GPU)")
     ap.add_argument("--merge-kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of the --motion leg: add its rows to the record in --out and exit (no GPU)")
     a = ap.parse_args()
     if a.merge_kernel_stats:
         return merge_kernel_stats(a.merge_kernel_stats, a.out)
+    if a.resource_usage:
+        return merge_resource_usage(a.resource_usage, a.out)
 
     import bench
     import fredholm_amd as F
@@ -193,6 +288,8 @@ def main():
         return temporal(a, bench, F, DeviceBuffer, r, w)
     if a.motion:
         return motion(a, bench, F, DeviceBuffer, r, w)
+    if a.response:
+        return response(a, bench, F, DeviceBuffer, r, w)
     L = F.RenderLayer(r, W, H)
     r.render(F.Camera(**w["camera"]), w["bg"], L, a.spp, w["depth"])
     moments, counts, out = DeviceBuffer(r, 8 * W * H), DeviceBuffer(r, 4 * W * H), DeviceBuffer(r, 16 * W * H)

@@ -188,13 +188,164 @@ def motion_replay(out):
             f.write(line + "\n")
 
 
+GAMMAS = (0.5, 0.75, 1.0, 1.5, 2.0, 3.0)
+
+
+def response_replay(out, cache):
+    """what fh_set_denoise_response buys and costs: four sequences through the float64 restatement of tests/test_gpu_denoise_response.py, for every gamma of GAMMAS"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    R = _load("test_gpu_denoise_response", "test_gpu_denoise_response.py")
+    M, T = R.M, R.T
+    from fredholm_amd import native as N
+    from fredholm_amd import scenes
+    from oracle import pyoracle as O
+    import fredholm_amd as F
+
+    q = R.RESPONSE_QUALITY
+    w, h, depth, spp, n_before, n_after = q["w"], q["h"], q["depth"], q["spp"], q["frames_before"], q["frames_after"]
+    threads = O.hardware_threads()
+    still = F.Camera(**scenes.CORNELL_CAMERA)
+
+    def frame(ref, cam, seed):
+        lo = ref.new_layers(w, h)
+        s1, s2, prev = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, 3))
+        for s in range(1, spp + 1):
+            ref.render(cam.params(), w, h, lo, 1, depth, seed=seed, n_threads=threads)
+            mean = lo["beauty"][..., :3].astype(np.float64)
+            x = s * mean - (s - 1) * prev
+            prev = mean
+            y = x[..., 0] * float(T.LUM[0]) + x[..., 1] * float(T.LUM[1]) + x[..., 2] * float(T.LUM[2])
+            s1 += y
+            s2 += y * y
+        res = {k: lo[k].copy() for k in ("beauty", "normal", "albedo", "position", "depth")}
+        res["moments"] = np.stack([s1 / spp, s2 / spp], axis=2).astype(np.float32)
+        res["counts"] = np.full((h, w), spp, np.uint32)
+        return res
+
+    def truth(ref, cam):
+        lo = ref.new_layers(w, h)
+        for _ in range(q["truth_spp"]):
+            ref.render(cam.params(), w, h, lo, 1, depth, seed=1000, n_threads=threads)
+        return lo["beauty"].copy()
+
+    def rendered():
+        """every frame and truth of the four sequences, as one flat dict of arrays"""
+        d = {}
+
+        def put(name, layers):
+            for k, v in layers.items():
+                d[f"{name}/{k}"] = v
+        base = O.Scene(scenes.cornell_box())
+        for k in range(n_before):
+            put(f"A{k}", frame(base, still, 1 + k))
+        d["truth/A"] = truth(base, still)
+        for tag in ("L", "S"):
+            ref = O.Scene(R.changed_scene(tag))
+            for k in range(n_before, n_before + n_after):
+                put(f"{tag}{k}", frame(ref, still, 1 + k))
+            d[f"truth/{tag}"] = truth(ref, still)
+            print(f"rendered ({tag})", flush=True)
+        for k in range(T.QUALITY["frames"]):
+            put(f"M{k}", frame(base, T.quality_camera(k), 1 + k))
+        d["truth/M"] = truth(base, T.quality_camera(T.QUALITY["frames"] - 1))
+        print("rendered (M)", flush=True)
+        plain = lambda sc: {key: val for key, val in sc.items() if key not in ("instance_ids", "object_to_world", "world_to_object")}
+        for k in range(M.MOTION_QUALITY["frames"]):
+            sc = scenes.cornell_box_instanced()
+            v = sc["vertices"].copy()
+            block = np.asarray(sc["indices"])[sc["instance_ids"] == 1].reshape(-1)
+            v[block] = v[block] + np.asarray(M.motion_quality_offset(k), np.float32)
+            sc["vertices"] = v
+            ref = O.Scene(plain(sc))
+            put(f"B{k}", dict(frame(ref, still, 1 + k), ids=chief_ids(sc, still, w, h)))
+        d["truth/B"] = truth(ref, still)
+        print("rendered (B)", flush=True)
+        return d
+
+    if cache and os.path.exists(cache):
+        d = dict(np.load(cache))
+    else:
+        d = rendered()
+        if cache:
+            np.savez_compressed(cache, **d)
+    layers_of = lambda name: {k.split("/")[1]: v for k, v in d.items() if k.startswith(name + "/")}
+    assert (T.QUALITY["w"], T.QUALITY["h"], T.QUALITY["spp"]) == (w, h, spp) == (M.MOTION_QUALITY["w"], M.MOTION_QUALITY["h"], M.MOTION_QUALITY["spp"])
+
+    def clipped_share(st):
+        return None if st.u is None else float((st.u[st.have] > 0).mean())
+
+    def run(gamma, frames, first_scored, truth_of, extra=None):
+        """the scored frames of a sequence for one call: gamma None is the plain call, a number the clipped one, "guided" the spatial filter alone on each scored frame.
+        frames: [(camera, layers, motion table or None)]; the frames from `first_scored` on (1-based) are scored against truth_of(frame); extra(output, truth) adds fields"""
+        st = R.ResponseRestatement(np.float64, np.exp)
+        st.gamma = None if gamma == "guided" else gamma
+        res = []
+        for k, (cam, layers, table) in enumerate(frames):
+            scored = k + 1 >= first_scored
+            if gamma == "guided":
+                if not scored:
+                    continue
+                o = T.Restatement(np.float64, np.exp).call(layers, cam.params(), spatial_only=True)
+            else:
+                o = st.call_r(layers, cam.params(), layers.get("ids"), table)
+            if scored:
+                truth_k = truth_of(k + 1)
+                res.append(dict(frame=k + 1, relmse=T._relmse(o, truth_k), clipped=None if gamma == "guided" else clipped_share(st), **(extra(o, truth_k) if extra else {})))
+        return res
+
+    def all_calls(frames, first_scored, truth_of, extra=None):
+        return {"guided": run("guided", frames, first_scored, truth_of, extra), "plain": run(None, frames, first_scored, truth_of, extra),
+                **{f"gamma={g}": run(g, frames, first_scored, truth_of, extra) for g in GAMMAS}}
+
+    rec = {"replay": True, "response": True, "quality": q, "defaults": T.TDEF, "gammas": list(GAMMAS), "sequences": {}}
+    for tag in ("L", "S"):
+        frames = [(still, layers_of(f"A{k}"), None) for k in range(n_before)] + [(still, layers_of(f"{tag}{k}"), None) for k in range(n_before, n_before + n_after)]
+        rec["sequences"][tag] = all_calls(frames, n_before, lambda f, tag=tag: d["truth/A"] if f <= n_before else d[f"truth/{tag}"])
+        print(tag, json.dumps(rec["sequences"][tag]), flush=True)
+    nm = T.QUALITY["frames"]
+    rec["sequences"]["M"] = all_calls([(T.quality_camera(k), layers_of(f"M{k}"), None) for k in range(nm)], nm, lambda f: d["truth/M"])
+    print("M", json.dumps(rec["sequences"]["M"]), flush=True)
+    nb = M.MOTION_QUALITY["frames"]
+    tables = [None] + [M.table_arrays(N.motion_from_transforms(*scenes.instanced_transforms(M.motion_quality_offset(k - 1)), *scenes.instanced_transforms(M.motion_quality_offset(k))))
+                       for k in range(1, nb)]
+    box = d[f"B{nb - 1}/ids"] == 1
+    rec["sequences"]["B"] = all_calls([(still, layers_of(f"B{k}"), tables[k]) for k in range(nb)], nb, lambda f: d["truth/B"],
+                                      lambda o, t: dict(relmse_block=T._relmse(o[box][None], t[box][None])))
+    print("B", json.dumps(rec["sequences"]["B"]), flush=True)
+
+    # the default: the smallest sum of the clipped call's relMSE over the frames after the change on (L) + (S), among the gammas whose steady state costs at most 5 %
+    seq = rec["sequences"]
+    choice = {}
+    for g in GAMMAS:
+        key = f"gamma={g}"
+        steady = {"L frame 8": seq["L"][key][0]["relmse"] / seq["L"]["plain"][0]["relmse"], "M last": seq["M"][key][0]["relmse"] / seq["M"]["plain"][0]["relmse"],
+                  "B frame": seq["B"][key][0]["relmse"] / seq["B"]["plain"][0]["relmse"], "B block": seq["B"][key][0]["relmse_block"] / seq["B"]["plain"][0]["relmse_block"]}
+        after = sum(f["relmse"] for tag in ("L", "S") for f in seq[tag][key][1:])
+        choice[key] = dict(steady=steady, after_change=after, qualifies=max(steady.values()) <= 1.05)
+        print(key, json.dumps(choice[key]))
+    ok = [g for g in GAMMAS if choice[f"gamma={g}"]["qualifies"]]
+    rec["choice"] = choice
+    rec["default_gamma"] = min(ok, key=lambda g: choice[f"gamma={g}"]["after_change"]) if ok else None
+    rec["nearest_gamma"] = min(GAMMAS, key=lambda g: max(choice[f"gamma={g}"]["steady"].values()))
+    print("default gamma:", rec["default_gamma"], "(nearest to the steady-state condition:", rec["nearest_gamma"], ")")
+    line = json.dumps(rec)
+    print(line)
+    if out:
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--motion", action="store_true", help="replay the moving-block sequence of tests/test_gpu_denoise_motion.py instead")
+    ap.add_argument("--response", action="store_true", help="replay the lighting-change and steady-state sequences of tests/test_gpu_denoise_response.py through the clipped stage")
+    ap.add_argument("--cache", default="", help="--response: an .npz the rendered frames are kept in (read when it exists): the rendering is most of the run")
     a = ap.parse_args()
     if a.motion:
         return motion_replay(a.out)
+    if a.response:
+        return response_replay(a.out, a.cache)
     T, sequences, ratio = build()
     rec = {"replay": True, "quality": T.QUALITY, "defaults": T.TDEF}
     for name, frames in sequences.items():
