@@ -1366,6 +1366,26 @@ int fh_get_denoise_response(fh_ctx* ctx, int* on, fh_response_params* params)
   return FH_OK;
 }
 
+// the noise box of the clipped stage: stored and broadcast like the switch above, and read only while that one is on
+int fh_set_denoise_response_noise(fh_ctx* ctx, const fh_response_noise_params* params)
+{
+  if (const char* why = response_noise_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_response_noise: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_response_noise(m_, params));
+  if (!ctx) return FH_E_INVALID;
+  ctx->denoise_response_noise = params ? 1 : 0;
+  if (params) ctx->response_kappa = params->kappa;
+  return FH_OK;
+}
+
+int fh_get_denoise_response_noise(fh_ctx* ctx, int* on, fh_response_noise_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->denoise_response_noise;
+  if (params) params->kappa = ctx->response_kappa;
+  return FH_OK;
+}
+
 int fh_denoise_history_info(fh_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* frames)
 {
   FH_GROUP_LEAD(ctx);

@@ -261,6 +261,9 @@ struct fh_ctx {
   // fh_set_denoise_response (denoise.hip: k_temporal_response): while on, the temporal stage clips the history it found to the current frame's 5 x 5 colour box
   int denoise_response = 0;
   float response_gamma = 1.0f;
+  // fh_set_denoise_response_noise (k_temporal_response_noise): the clipped history is clamped to the pixel's measured noise as well; inert while the switch above is off
+  int denoise_response_noise = 0;
+  float response_kappa = 6.0f;
 
   // stats
   fh_stats stats{};

@@ -16,7 +16,8 @@
 // fh_denoise_temporal runs the same preparation and the same passes with one launch between them, k_temporal below: the frame's (c, v) blended with the context's
 // history of the frames before it, found again through the world position and the previous call's camera.  fh_denoise_temporal_motion launches k_temporal_motion in
 // its place where an instance moved: the same stage with the pixels of moved instances carried to where their surface was.  While fh_set_denoise_response is on, all
-// three are replaced by k_temporal_response, which clamps the history it found to the current frame's local colour statistics before the blend.
+// three are replaced by k_temporal_response, which clamps the history it found to the current frame's local colour statistics before the blend; with
+// fh_set_denoise_response_noise on as well and moments given, by k_temporal_response_noise, which also clamps it to the pixel's own measured noise.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -421,91 +422,25 @@ __global__ void __launch_bounds__(256) k_temporal_motion(const TemporalArgs A, c
 // unrolled window takes do, at 5 waves per SIMD = 5 workgroups per CU.  A tile element outside the
 // frame is staged with N = 0, which is what a miss has: neither counts.  Every thread of a partial tile stages (the loop runs over the tile, not over the live
 // pixels) and only then do the threads without a pixel leave.  A row of 32 pixels reads 32 consecutive float4 of a tile row per tap: every bank once per 16 lanes.
+//
+// NOISE (fh_set_denoise_response_noise, step 4b of the header): the clipped history is clamped once more, to the pixel's own colour +- kappa standard deviations of
+// what it measured -- the preparation's variance v plus the history's v_h, both in registers already -- and shortened by the larger of the two excesses.  No new load,
+// no more LDS.  The body, temporal_response_body.h, is included into both kernel templates: they differ in that step alone, and k_temporal_response, which a
+// function call between it and its body would recompile with other operand orders, keeps its instruction stream.
 template <int KIND>
 __global__ void __launch_bounds__(256) k_temporal_response(const TemporalArgs A, const MotionArgs M, const float gamma)
 {
-  __shared__ float4 s_cv[kGN];  // c.rgb, v of the preparation
-  __shared__ float4 s_n[kGN];   // N; 0 outside the frame
-  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
-  const int tid = threadIdx.y * kTW + threadIdx.x;
-  for (int k = tid; k < kGN; k += 256) {
-    const int qx = x0 + k % kGW - 2, qy = y0 + k / kGW - 2;
-    float4 cq = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nq = cq;
-    if (qx >= 0 && qx < A.w && qy >= 0 && qy < A.h) { cq = A.cv[qx + A.w * qy]; nq = A.normal[qx + A.w * qy]; }
-    s_cv[k] = cq;
-    s_n[k] = nq;
-  }
-  __syncthreads();
-  const int x = x0 + (int)threadIdx.x, y = y0 + (int)threadIdx.y;
-  if (x >= A.w || y >= A.h) return;
-  const int p = x + A.w * y;
-  const int kc = ((int)threadIdx.y + 2) * kGW + (int)threadIdx.x + 2;
-  const float4 cv = s_cv[kc], np = s_n[kc], pp = A.position[p];
-  float cx = cv.x, cy = cv.y, cz = cv.z, v = cv.w, hist = 0.0f;
-  if (td_hit(np)) {
-    hist = 1.0f;
-    bool have = false;
-    float hx = 0.0f, hy = 0.0f, hz = 0.0f, hv = 0.0f, hh = 0.0f;
-    const float lim = A.plane_tol * fmaxf(A.depth[p], 1e-3f);
-    bool own = KIND == 1;
-    float4 nb = np, pb = pp;
-    if constexpr (KIND == 3) {
-      const uint32_t inst = M.ids[p];
-      const bool carried = inst < M.n_instances && M.motion[inst < M.n_instances ? inst : 0u].moved != 0u;
-      own = !carried && M.still;
-      if (carried) {
-        const float* a = M.motion[inst].point;
-        const float* g = M.motion[inst].normal;
-        pb.x = ((a[0] * pp.x + a[1] * pp.y) + a[2] * pp.z) + a[3];
-        pb.y = ((a[4] * pp.x + a[5] * pp.y) + a[6] * pp.z) + a[7];
-        pb.z = ((a[8] * pp.x + a[9] * pp.y) + a[10] * pp.z) + a[11];
-        nb.x = (g[0] * np.x + g[1] * np.y) + g[2] * np.z;
-        nb.y = (g[3] * np.x + g[4] * np.y) + g[5] * np.z;
-        nb.z = (g[6] * np.x + g[7] * np.y) + g[8] * np.z;
-      }
-    }
-    if (own) {
-      const float4 qc = A.h_cv[p], qp = A.h_ph[p], qn = A.h_n[p];
-      have = td_valid(A, np, pp, lim, qn, qp);
-      hx = qc.x; hy = qc.y; hz = qc.z; hv = qc.w; hh = qp.w;
-    } else {
-      have = td_reproject(A, nb, pb, lim, hx, hy, hz, hv, hh);
-    }
-    if (have) {
-      // 1: the window.  A tap that does not count adds + 0, which changes no bit of a sum that started at + 0.
-      float n = 0.0f, s1x = 0.0f, s1y = 0.0f, s1z = 0.0f, s2x = 0.0f, s2y = 0.0f, s2z = 0.0f;
-#pragma unroll
-      for (int dy = -2; dy <= 2; ++dy)
-#pragma unroll
-        for (int dx = -2; dx <= 2; ++dx) {
-          const int k = kc + dy * kGW + dx;
-          const float4 cq = s_cv[k], nq = s_n[k];
-          const bool counts = (dx == 0 && dy == 0) || (td_hit(nq) && (np.x * nq.x + np.y * nq.y) + np.z * nq.z >= A.cos_min);
-          n += counts ? 1.0f : 0.0f;
-          s1x += counts ? cq.x : 0.0f; s1y += counts ? cq.y : 0.0f; s1z += counts ? cq.z : 0.0f;
-          s2x += counts ? cq.x * cq.x : 0.0f; s2y += counts ? cq.y * cq.y : 0.0f; s2z += counts ? cq.z * cq.z : 0.0f;
-        }
-      if (n >= 2.0f) {  // (3: a window of the pixel alone clips nothing)
-        // 2: the box; 4: the clip.  fmaxf and fminf drop a NaN operand.
-        const float mx = s1x / n, my = s1y / n, mz = s1z / n;
-        const float gx = gamma * fhe_sqrt(fmaxf(s2x / n - mx * mx, 0.0f)), gy = gamma * fhe_sqrt(fmaxf(s2y / n - my * my, 0.0f)), gz = gamma * fhe_sqrt(fmaxf(s2z / n - mz * mz, 0.0f));
-        const float ccx = fminf(fmaxf(hx, mx - gx), mx + gx), ccy = fminf(fmaxf(hy, my - gy), my + gy), ccz = fminf(fmaxf(hz, mz - gz), mz + gz);
-        const float ux = fabsf(ccx - hx) / (gx + 1e-6f), uy = fabsf(ccy - hy) / (gy + 1e-6f), uz = fabsf(ccz - hz) / (gz + 1e-6f);
-        const float k1 = 1.0f + fmaxf(fmaxf(ux, uy), uz);
-        // 5: the shortened history
-        hx = ccx; hy = ccy; hz = ccz;
-        hh = hh / k1; hv = hv * k1;
-      }
-      hist = fminf(hh + 1.0f, A.max_history);
-      const float a = fmaxf(1.0f / hist, A.alpha_min), b = 1.0f - a;
-      cx = b * hx + a * cx; cy = b * hy + a * cy; cz = b * hz + a * cz;
-      v = (b * b) * hv + (a * a) * v;
-    }
-  }
-  A.o_cv[p] = make_float4(cx, cy, cz, v);
-  A.o_ph[p] = make_float4(pp.x, pp.y, pp.z, hist);
-  A.o_n[p] = np;
-  A.vplane[p] = v;
+  constexpr bool NOISE = false;
+  constexpr float kappa = 0.0f;
+#include "temporal_response_body.h"
+}
+
+// the same with step 4b; launched only for a call that has moments (without them v is the 7 x 7 spatial estimate, large at exactly the edges this step is for)
+template <int KIND>
+__global__ void __launch_bounds__(256) k_temporal_response_noise(const TemporalArgs A, const MotionArgs M, const float gamma, const float kappa)
+{
+  constexpr bool NOISE = true;
+#include "temporal_response_body.h"
 }
 
 }  // namespace
@@ -636,8 +571,13 @@ int temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, cons
   const MotionArgs ma{ids, ctx->d_motion, n_instances, still ? 1 : 0};
   if (ctx->hist_frames == 0) hipLaunchKernelGGL((k_temporal<0>), grid, block, 0, ctx->stream, a);
   else if (ctx->denoise_response) {  // fh_set_denoise_response: the clipped form of whichever of the three kernels below the call would launch
-    const float gamma = ctx->response_gamma;
-    if (with_motion) hipLaunchKernelGGL((k_temporal_response<3>), grid, block, 0, ctx->stream, a, ma, gamma);
+    const float gamma = ctx->response_gamma, kappa = ctx->response_kappa;
+    if (ctx->denoise_response_noise && in->moments) {  // fh_set_denoise_response_noise: the measured variance exists only with moments
+      if (with_motion) hipLaunchKernelGGL((k_temporal_response_noise<3>), grid, block, 0, ctx->stream, a, ma, gamma, kappa);
+      else if (still) hipLaunchKernelGGL((k_temporal_response_noise<1>), grid, block, 0, ctx->stream, a, ma, gamma, kappa);
+      else hipLaunchKernelGGL((k_temporal_response_noise<2>), grid, block, 0, ctx->stream, a, ma, gamma, kappa);
+    }
+    else if (with_motion) hipLaunchKernelGGL((k_temporal_response<3>), grid, block, 0, ctx->stream, a, ma, gamma);
     else if (still) hipLaunchKernelGGL((k_temporal_response<1>), grid, block, 0, ctx->stream, a, ma, gamma);
     else hipLaunchKernelGGL((k_temporal_response<2>), grid, block, 0, ctx->stream, a, ma, gamma);
   }

@@ -67,4 +67,11 @@ inline const char* response_refusal(const fh_response_params* params)
   return nullptr;
 }
 
+// why fh_set_denoise_response_noise refuses these parameters, or nullptr (NULL parameters switch the step off and are never refused)
+inline const char* response_noise_refusal(const fh_response_noise_params* params)
+{
+  if (params && (!(params->kappa > 0.0f) || !std::isfinite(params->kappa))) return "kappa must be finite and > 0";
+  return nullptr;
+}
+
 }  // namespace fh

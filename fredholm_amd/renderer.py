@@ -586,6 +586,22 @@ class Renderer:
         self._ck(N.lib().fh_get_denoise_response(self._ctx, C.byref(on), C.byref(p)), "fh_get_denoise_response")
         return bool(on.value), float(p.gamma)
 
+    def set_denoise_response_noise(self, kappa=6.0):
+        """fh_set_denoise_response_noise: while set_denoise_response is on and the call is given moments and counts, the clipped history is clamped once more, to the
+        pixel's own colour +- kappa * sqrt(v + v_h) of the luminance variances it measured, and shortened by the larger excess: a moved emitter no longer lags next
+        to where it was.  Stored but without effect while set_denoise_response is off, and in a call without moments (they exist while adaptive sampling is on)"""
+        p = N.ResponseNoiseParamsC(float(kappa))
+        self._ck(N.lib().fh_set_denoise_response_noise(self._ctx, C.byref(p)), "fh_set_denoise_response_noise")
+
+    def clear_denoise_response_noise(self):
+        self._ck(N.lib().fh_set_denoise_response_noise(self._ctx, None), "fh_set_denoise_response_noise")
+
+    def get_denoise_response_noise(self):
+        """(on, kappa): the switch and the kappa last set (6 before any)"""
+        on, p = C.c_int(0), N.ResponseNoiseParamsC(0.0)
+        self._ck(N.lib().fh_get_denoise_response_noise(self._ctx, C.byref(on), C.byref(p)), "fh_get_denoise_response_noise")
+        return bool(on.value), float(p.kappa)
+
     def reset_denoise_history(self):
         """drop the history of denoise_temporal (fh_denoise_history_reset)"""
         self._ck(N.lib().fh_denoise_history_reset(self._ctx), "fh_denoise_history_reset")

@@ -13,6 +13,9 @@
 // an instance that Renderer::set_time moved is looked up where the instance was.  The switch belongs to the context and is sent with the next denoise().
 // set_response(true, gamma) (FH_DENOISER=temporal-response, temporal-motion-response) switches the context's history clipping on (fh_set_denoise_response): the
 // history is clamped to the current frame's local colour box before the blend, so a change of lighting does not lag.  Sent with the next denoise() likewise.
+// set_response_noise(true, kappa) (FH_DENOISER=temporal-response-noise, temporal-motion-response-noise: set_response(true) with it) switches the noise box of that
+// clipping on (fh_set_denoise_response_noise).  It acts only in calls that are given luminance moments and sample counts (set_guides with both: they exist while
+// adaptive sampling keeps them); without them, and without set_response, it does nothing.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -38,6 +41,8 @@ class Denoiser
     if (env && std::strcmp(env, "temporal-motion") == 0) { m_mode = Temporal; set_motion(true); }
     if (env && std::strcmp(env, "temporal-response") == 0) { m_mode = Temporal; set_response(true); }
     if (env && std::strcmp(env, "temporal-motion-response") == 0) { m_mode = Temporal; set_motion(true); set_response(true); }
+    if (env && std::strcmp(env, "temporal-response-noise") == 0) { m_mode = Temporal; set_response(true); set_response_noise(true); }
+    if (env && std::strcmp(env, "temporal-motion-response-noise") == 0) { m_mode = Temporal; set_motion(true); set_response(true); set_response_noise(true); }
   }
   enum Mode { Atrous, Guided, Temporal };
   void set_mode(Mode mode) { m_mode = mode; }
@@ -62,6 +67,10 @@ class Denoiser
   void set_response(bool on, float gamma = 1.0f) { m_response = on; m_response_gamma = gamma; m_response_pending = true; }
   bool response() const { return m_response; }
   float response_gamma() const { return m_response_gamma; }
+  // Temporal mode with set_response: clamp the clipped history to the pixel's measured noise too (fh_set_denoise_response_noise); needs moments; with the next denoise()
+  void set_response_noise(bool on, float kappa = 6.0f) { m_noise = on; m_noise_kappa = kappa; m_noise_pending = true; }
+  bool response_noise() const { return m_noise; }
+  float response_noise_kappa() const { return m_noise_kappa; }
   void reset_history()
   {
     fh_ctx* ctx = m_context ? m_context : cwl::require_context();
@@ -80,6 +89,11 @@ class Denoiser
         const fh_response_params rp = {m_response_gamma};
         cwl::check(ctx, fh_set_denoise_response(ctx, m_response ? &rp : nullptr), "fh_set_denoise_response");
         m_response_pending = false;
+      }
+      if (m_noise_pending) {
+        const fh_response_noise_params np = {m_noise_kappa};
+        cwl::check(ctx, fh_set_denoise_response_noise(ctx, m_noise ? &np : nullptr), "fh_set_denoise_response_noise");
+        m_noise_pending = false;
       }
       const fh_denoise_inputs in = {reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
                                     reinterpret_cast<const float*>(m_d_position), m_d_depth, reinterpret_cast<const float*>(m_d_moments), m_d_counts};
@@ -118,5 +132,7 @@ class Denoiser
   bool m_motion = false, m_motion_pending = false;
   bool m_response = false, m_response_pending = false;
   float m_response_gamma = 1.0f;
+  bool m_noise = false, m_noise_pending = false;
+  float m_noise_kappa = 6.0f;
 };
 }  // namespace fredholm

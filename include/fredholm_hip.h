@@ -451,8 +451,9 @@ int fh_get_denoise_motion(fh_ctx* ctx, int* on);
  *     (finite() passes a beauty of 3e38, which the division by an albedo of 0.01 takes past FLT_MAX) gives mu_k = cc_k = + infinity and c_acc.k = 0 * inf = NaN.
  *     In both cases ALL pixels whose window counts the tap (up to 25) get the NaN, where the plain stage has a non-finite value in that one pixel only; the
  *     passes keep it out of no neighbour.  Not guarded: a frame with radiance above 1e30 is not one this filter is for.
- * Not covered: where the window straddles an emitter and what surrounds it, its standard deviation is large, the box loose, and a moved emitter still lags
- * (DESIGN.md 4a gives the figures); window radius is not a parameter. */
+ * Not covered by these six steps alone: where the window straddles an emitter and what surrounds it, its standard deviation is large, the box loose, and a moved
+ * emitter still lags; fh_set_denoise_response_noise (below) closes most of that where the call has moments, and without moments it stays open (DESIGN.md 4a gives the
+ * figures of both).  Window radius is not a parameter. */
 typedef struct fh_response_params {
   float gamma; /* half-width of the clip box in standard deviations, finite and > 0; default 1 */
 } fh_response_params;
@@ -461,6 +462,33 @@ typedef struct fh_response_params {
 int fh_set_denoise_response(fh_ctx* ctx, const fh_response_params* params);
 /* *on = 0 or 1; params (may be NULL) receives the gamma last set (1 before any) */
 int fh_get_denoise_response(fh_ctx* ctx, int* on, fh_response_params* params);
+
+/* -- the noise box: one more step of the clipped stage (opt-in, default off).  The 5 x 5 box above is loose exactly where a window straddles an emitter and its
+ * surroundings; the pixel's own MEASURED noise is not: a history consistent with the current frame lies within a few standard deviations of the pixel's colour, the
+ * variance being the preparation's v (from the luminance moments) plus the history's v_h.  The step runs only when fh_set_denoise_response is on, this switch is on AND
+ * the call has moments and counts; in every other call -- the response switch off, no moments -- the switch is stored and inert, and the call has the bits and the
+ * launches it has without it.  (Without moments v is the 7 x 7 spatial estimate, which is large at those same edges: the step would gain nothing and cost the steady
+ * state; it is not emulated.)  For a hit pixel p that has a history, fp32 without contraction, / and sqrt correctly rounded, sums in the order written:
+ *   4b Noise box, after step 4 has produced cc and u (call that u_s; step 3's "too few taps" gives cc = c_h, u_s = 0, and this step still runs):
+ *      s = kappa * sqrt(v + v_h),  v the preparation's variance at p, v_h the history variance as looked up (before step 5 scales it);
+ *      per channel k: cd_k = fmin(fmax(cc_k, c.k - s), c.k + s),  w_k = |cd_k - cc_k| / (s + 1e-6);
+ *      u = fmax(u_s, fmax(fmax(w_r, w_g), w_b)).
+ *   5  then uses (cd, u) in place of (cc, u).
+ *   The half-width s is the standard deviation of the LUMINANCE, used for all three channels of the demodulated colour: no per-channel scaling.
+ *   6b fmax and fmin are C's.  A NaN s (a NaN v or v_h; kappa * sqrt cannot make one from finite operands) loses in both clamps, so cd = cc, and w_k = 0 / NaN = NaN
+ *      loses in the fmax: u = u_s, the six steps' result.  An infinite s clips nothing: the box is (-inf, +inf), w_k = 0 / inf = 0 -- this is what v + v_h gives when
+ *      it overflows (both are >= 0 or NaN, so the sum is never inf - inf), what an infinite v or v_h gives, and what kappa * sqrt(v + v_h) gives when the product
+ *      overflows.  With c.k itself infinite and s infinite one bound is NaN and loses: still nothing is clipped.  s = 0 (v = v_h = 0: a pixel whose samples all
+ *      agreed, in both) makes the box the point c: cd = c, and w_k = |c.k - cc_k| * 1e6 drops the history unless it equals the frame.  A NaN cc_k (a NaN history)
+ *      loses against the lower bound and becomes c.k - s, with w_k = NaN, which loses. */
+typedef struct fh_response_noise_params {
+  float kappa; /* half-width of the noise box in standard deviations, finite and > 0; default 6 */
+} fh_response_noise_params;
+/* params == NULL: off.  Lives on the context and is broadcast on a group like fh_set_denoise_response; the work runs on the lead.  FH_E_INVALID, decided from the
+ * arguments alone, for a kappa that is not finite or <= 0; the switch then stays as it was.  Takes effect with the next call; the history is kept. */
+int fh_set_denoise_response_noise(fh_ctx* ctx, const fh_response_noise_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the kappa last set (6 before any) */
+int fh_get_denoise_response_noise(fh_ctx* ctx, int* on, fh_response_noise_params* params);
 
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/denoise_bench.py [--out profiles/denoise_guided_bench.json] [--config 3] [--spp 16] [--calls 20] [--temporal | --motion | --response] -- what a call of the denoisers costs.
+"""tools/denoise_bench.py [--out profiles/denoise_guided_bench.json] [--config 3] [--spp 16] [--calls 20] [--temporal | --motion | --response [--noise]] -- what a call of the denoisers costs.
 
 The layers of a BASELINE.json configs[c] frame at 1920x1080 (`--spp` samples, adaptive sampling on at threshold 0 so that the luminance moments exist), then, in this
 one process, the median of `--calls` calls of fh_denoise and of fh_denoise_guided, each followed by one fh_sync and timed from before the call to after the sync:
@@ -21,7 +21,11 @@ profiler's kernel_stats.csv into FILE's record as "kernel_us".
 fh_denoise_temporal (cameras alternating; one frame repeated) and of fh_denoise_temporal_motion with fh_set_denoise_response off and then on (--gamma), in one process, beside
 fh_denoise_guided.  The kernels' own times come from a `rocprofv3 --kernel-trace --stats` run of this leg, in which k_temporal<1>, k_temporal<2>, k_temporal_motion, the
 three k_temporal_response and the k_guided_pass instances all run: `--merge-kernel-stats STATS.csv --out FILE` adds them (with the passes' rows), and
-`--resource-usage LOG` the registers, LDS, scratch and occupancy hipcc's -Rpass-analysis=kernel-resource-usage printed for those kernels when denoise.hip was built."""
+`--resource-usage LOG` the registers, LDS, scratch and occupancy hipcc's -Rpass-analysis=kernel-resource-usage printed for those kernels when denoise.hip was built.
+
+--response --noise (-> profiles/denoise_noise_box_bench.json): the --response leg (every call has moments) with a third round, fh_set_denoise_response_noise on (--kappa) as well:
+plain, clipped, clipped with the noise box, in one process.  In a `rocprofv3 --kernel-trace --stats` run of this leg the three k_temporal_response and the three
+k_temporal_response_noise run side by side: the former are the reference point for the latter."""
 import argparse
 import json
 import os
@@ -192,15 +196,26 @@ def response(a, bench, F, DeviceBuffer, r, w):
         r.denoise_guided(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], m.ptr, c.ptr)
     rec = {"workload": w["name"], "width": W, "height": H, "spp": a.spp, "calls": a.calls, "camera_step": step, "gamma": a.gamma, "source_fingerprint": bench.source_fingerprint(),
            "fh_denoise_guided_ms": median_ms(r, call_guided, a.calls)}
-    for name, gamma in (("", None), ("response_", a.gamma)):
+    rounds = [("", None, None), ("response_", a.gamma, None)]
+    if a.noise:
+        rec["kappa"] = a.kappa
+        rounds.append(("response_noise_", a.gamma, a.kappa))
+    for name, gamma, kappa in rounds:
         if gamma is None:
             r.clear_denoise_response()
         else:
             r.set_denoise_response(gamma)
+        if kappa is not None:
+            r.set_denoise_response_noise(kappa)
         rec[f"fh_denoise_temporal_{name}moving_ms"] = median_ms(r, lambda: call_temporal(True), a.calls)
         rec[f"fh_denoise_temporal_{name}still_ms"] = median_ms(r, lambda: call_temporal(False), a.calls)
         rec[f"fh_denoise_temporal_motion_{name}ms"] = median_ms(r, call_motion, a.calls)
     r.clear_denoise_response()
+    if a.noise:
+        r.clear_denoise_response_noise()
+        for leg in ("moving", "still"):
+            rec[f"noise_{leg}_ms_by_difference"] = rec[f"fh_denoise_temporal_response_noise_{leg}_ms"] - rec[f"fh_denoise_temporal_response_{leg}_ms"]
+        rec["noise_motion_ms_by_difference"] = rec["fh_denoise_temporal_motion_response_noise_ms"] - rec["fh_denoise_temporal_motion_response_ms"]
     rec["fh_denoise_guided_again_ms"] = median_ms(r, call_guided, a.calls)
     for leg in ("moving", "still"):
         rec[f"response_{leg}_ms_by_difference"] = rec[f"fh_denoise_temporal_response_{leg}_ms"] - rec[f"fh_denoise_temporal_{leg}_ms"]
@@ -263,6 +278,8 @@ def main():
     ap.add_argument("--motion", action="store_true")
     ap.add_argument("--response", action="store_true")
     ap.add_argument("--gamma", type=float, default=1.0, help="--response: the gamma of fh_set_denoise_response")
+    ap.add_argument("--noise", action="store_true", help="--response: a third round with fh_set_denoise_response_noise on")
+    ap.add_argument("--kappa", type=float, default=6.0, help="--response --noise: the kappa of fh_set_denoise_response_noise")
     ap.add_argument("--step", type=float, default=0.002)
     ap.add_argument("--resource-usage", default="", help="a log of hipcc -Rpass-analysis=kernel-resource-usage on denoise.hip: add its figures to the record in --out and exit (no GPU)")
     ap.add_argument("--merge-kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of the --motion leg: add its rows to the record in --out and exit (no GPU)")

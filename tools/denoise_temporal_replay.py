@@ -11,7 +11,12 @@ with the moving camera, at 4 spp per frame, and for a still camera; then R of th
 frame) through that file's float64 restatement of fh_denoise_temporal_motion and through the plain one, and prints relMSE over the pixels whose chief ray sees the block
 in the last frame and over the whole frame: R = relMSE(motion) / relMSE(plain temporal) is what the device test's margin is taken from.  The checker renders the block
 where the instance transform puts it (a translation: the baked vertices are the device's world-space vertices bit for bit); the id plane is the chief rays' closest
-hit, by brute force in float64."""
+hit, by brute force in float64.
+
+--response replays four sequences -- (L) the light's emission x 0.25 after 8 frames, (S) the light quad moved, (M) the moving camera, (B) the moving block -- through the
+float64 restatement of fh_set_denoise_response for several gamma and chooses the default by a stated rule.  --noise-box replays the same four with gamma = 1 fixed
+through the restatement of fh_set_denoise_response_noise (tests/test_denoise_noise_box_host.py) for kappa in KAPPAS, chooses the default kappa by the same rule, and also
+records what the step would do WITHOUT moments (on the 7 x 7 spatial variance), which is why the library leaves that path alone."""
 import argparse
 import importlib.util
 import json
@@ -189,12 +194,15 @@ def motion_replay(out):
 
 
 GAMMAS = (0.5, 0.75, 1.0, 1.5, 2.0, 3.0)
+KAPPAS = (3.0, 4.0, 5.0, 6.0, 8.0)
 
 
-def response_replay(out, cache):
-    """what fh_set_denoise_response buys and costs: four sequences through the float64 restatement of tests/test_gpu_denoise_response.py, for every gamma of GAMMAS"""
+def response_replay(out, cache, noise_box=False):
+    """what fh_set_denoise_response buys and costs: four sequences through the float64 restatement of tests/test_gpu_denoise_response.py, for every gamma of GAMMAS;
+    noise_box: what fh_set_denoise_response_noise adds at gamma = 1, for every kappa of KAPPAS, through the restatement of tests/test_denoise_noise_box_host.py"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     R = _load("test_gpu_denoise_response", "test_gpu_denoise_response.py")
+    H = _load("test_denoise_noise_box_host", "test_denoise_noise_box_host.py") if noise_box else None
     M, T = R.M, R.T
     from fredholm_amd import native as N
     from fredholm_amd import scenes
@@ -274,30 +282,43 @@ def response_replay(out, cache):
     def clipped_share(st):
         return None if st.u is None else float((st.u[st.have] > 0).mean())
 
-    def run(gamma, frames, first_scored, truth_of, extra=None):
+    def run(gamma, frames, first_scored, truth_of, extra=None, kappa=None, use_moments=True):
         """the scored frames of a sequence for one call: gamma None is the plain call, a number the clipped one, "guided" the spatial filter alone on each scored frame.
-        frames: [(camera, layers, motion table or None)]; the frames from `first_scored` on (1-based) are scored against truth_of(frame); extra(output, truth) adds fields"""
-        st = R.ResponseRestatement(np.float64, np.exp)
+        frames: [(camera, layers, motion table or None)]; the frames from `first_scored` on (1-based) are scored against truth_of(frame); extra(output, truth) adds fields.
+        kappa: the noise box on top (use_moments False: on the spatial variance, which the library does not do)"""
+        st = R.ResponseRestatement(np.float64, np.exp) if kappa is None else H.NoiseBoxRestatement(np.float64, np.exp)
         st.gamma = None if gamma == "guided" else gamma
+        if kappa is not None:
+            st.kappa, st.without_moments = kappa, not use_moments
         res = []
         for k, (cam, layers, table) in enumerate(frames):
             scored = k + 1 >= first_scored
             if gamma == "guided":
                 if not scored:
                     continue
-                o = T.Restatement(np.float64, np.exp).call(layers, cam.params(), spatial_only=True)
+                o = T.Restatement(np.float64, np.exp).call(layers, cam.params(), use_moments, spatial_only=True)
             else:
-                o = st.call_r(layers, cam.params(), layers.get("ids"), table)
+                o = st.call_r(layers, cam.params(), layers.get("ids"), table, use_moments)
             if scored:
                 truth_k = truth_of(k + 1)
                 res.append(dict(frame=k + 1, relmse=T._relmse(o, truth_k), clipped=None if gamma == "guided" else clipped_share(st), **(extra(o, truth_k) if extra else {})))
         return res
 
     def all_calls(frames, first_scored, truth_of, extra=None):
+        if noise_box:
+            res = {}
+            for tail, mom in (("", True), (" no moments", False)):
+                res["guided" + tail] = run("guided", frames, first_scored, truth_of, extra, use_moments=mom)
+                res["plain" + tail] = run(None, frames, first_scored, truth_of, extra, use_moments=mom)
+                res["clipped" + tail] = run(1.0, frames, first_scored, truth_of, extra, use_moments=mom)
+                res.update({f"kappa={k}{tail}": run(1.0, frames, first_scored, truth_of, extra, kappa=k, use_moments=mom) for k in KAPPAS})
+            return res
         return {"guided": run("guided", frames, first_scored, truth_of, extra), "plain": run(None, frames, first_scored, truth_of, extra),
                 **{f"gamma={g}": run(g, frames, first_scored, truth_of, extra) for g in GAMMAS}}
 
     rec = {"replay": True, "response": True, "quality": q, "defaults": T.TDEF, "gammas": list(GAMMAS), "sequences": {}}
+    if noise_box:
+        rec = {"replay": True, "noise_box": True, "quality": q, "defaults": T.TDEF, "gamma": 1.0, "kappas": list(KAPPAS), "sequences": {}}
     for tag in ("L", "S"):
         frames = [(still, layers_of(f"A{k}"), None) for k in range(n_before)] + [(still, layers_of(f"{tag}{k}"), None) for k in range(n_before, n_before + n_after)]
         rec["sequences"][tag] = all_calls(frames, n_before, lambda f, tag=tag: d["truth/A"] if f <= n_before else d[f"truth/{tag}"])
@@ -313,8 +334,31 @@ def response_replay(out, cache):
                                       lambda o, t: dict(relmse_block=T._relmse(o[box][None], t[box][None])))
     print("B", json.dumps(rec["sequences"]["B"]), flush=True)
 
-    # the default: the smallest sum of the clipped call's relMSE over the frames after the change on (L) + (S), among the gammas whose steady state costs at most 5 %
     seq = rec["sequences"]
+    if noise_box:
+        # the default, by the rule that chose gamma: the smallest sum of relMSE over the four frames after the change on (L) + (S), among the kappas whose steady state
+        # costs at most 5 % of the plain call; the rows without moments are scored against the plain call without moments
+        for tail in ("", " no moments"):
+            choice = {}
+            for key in ["clipped" + tail] + [f"kappa={k}{tail}" for k in KAPPAS]:
+                plain = "plain" + tail
+                steady = {"L frame 8": seq["L"][key][0]["relmse"] / seq["L"][plain][0]["relmse"], "M last": seq["M"][key][0]["relmse"] / seq["M"][plain][0]["relmse"],
+                          "B frame": seq["B"][key][0]["relmse"] / seq["B"][plain][0]["relmse"], "B block": seq["B"][key][0]["relmse_block"] / seq["B"][plain][0]["relmse_block"]}
+                after = sum(f["relmse"] for tag in ("L", "S") for f in seq[tag][key][1:])
+                choice[key] = dict(steady=steady, after_change=after, qualifies=max(steady.values()) <= 1.05)
+                print(key, json.dumps(choice[key]))
+            rec["choice" + tail.replace(" ", "_")] = choice
+        rec["guided_after_change"] = sum(f["relmse"] for tag in ("L", "S") for f in seq[tag]["guided"][1:])
+        ok = [k for k in KAPPAS if rec["choice"][f"kappa={k}"]["qualifies"]]
+        rec["default_kappa"] = min(ok, key=lambda k: rec["choice"][f"kappa={k}"]["after_change"]) if ok else None
+        print("default kappa:", rec["default_kappa"])
+        line = json.dumps(rec)
+        print(line)
+        if out:
+            with open(out, "w") as f:
+                f.write(line + "\n")
+        return
+    # the default: the smallest sum of the clipped call's relMSE over the frames after the change on (L) + (S), among the gammas whose steady state costs at most 5 %
     choice = {}
     for g in GAMMAS:
         key = f"gamma={g}"
@@ -340,12 +384,13 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--motion", action="store_true", help="replay the moving-block sequence of tests/test_gpu_denoise_motion.py instead")
     ap.add_argument("--response", action="store_true", help="replay the lighting-change and steady-state sequences of tests/test_gpu_denoise_response.py through the clipped stage")
-    ap.add_argument("--cache", default="", help="--response: an .npz the rendered frames are kept in (read when it exists): the rendering is most of the run")
+    ap.add_argument("--noise-box", action="store_true", help="replay the same four sequences at gamma = 1 through the noise box of fh_set_denoise_response_noise, for kappa in KAPPAS")
+    ap.add_argument("--cache", default="", help="--response, --noise-box: an .npz the rendered frames are kept in (read when it exists): the rendering is most of the run")
     a = ap.parse_args()
     if a.motion:
         return motion_replay(a.out)
-    if a.response:
-        return response_replay(a.out, a.cache)
+    if a.response or a.noise_box:
+        return response_replay(a.out, a.cache, a.noise_box)
     T, sequences, ratio = build()
     rec = {"replay": True, "quality": T.QUALITY, "defaults": T.TDEF}
     for name, frames in sequences.items():
