@@ -1280,8 +1280,7 @@ int fh_denoise(fh_ctx* ctx, uint32_t width, uint32_t height, const float* beauty
 // every refusal is decided from the arguments alone, before the context or the device is touched: a refused call changes nothing
 int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_denoise_params* params, float* denoised, int upscale2x)
 {
-  const fh_denoise_params defaults = {2.0f, 1.0f, 0.2f, 7u, 5u};
-  const fh_denoise_params pr = params ? *params : defaults;
+  const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
   const char* why = guided_refusal(width, height, in, pr, denoised);
   if (!why && !ctx) why = "null context";
   if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_guided: ") + why);
@@ -1294,9 +1293,8 @@ int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_den
 int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const fh_temporal_params* temporal,
                         const fh_denoise_params* params, float* denoised, int upscale2x)
 {
-  const fh_denoise_params defaults = {2.0f, 1.0f, 0.2f, 7u, 5u};
   const fh_temporal_params temporal_defaults = {0.2f, 32.0f, 0.5f, 0.02f};
-  const fh_denoise_params pr = params ? *params : defaults;
+  const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
   const fh_temporal_params tp = temporal ? *temporal : temporal_defaults;
   float w2c[12], inv_tan = 0.0f;
   const char* why = temporal_refusal(width, height, in, camera, tp, pr, denoised, w2c, &inv_tan);
@@ -1304,7 +1302,7 @@ int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_d
   if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_temporal: ") + why);
   FH_GROUP_LEAD(ctx);
   CTX_CHECK(ctx);
-  if (!ctx->denoise_motion) return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
+  if (!ctx->denoise_motion) return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, nullptr, 0u, nullptr, denoised, upscale2x ? 1 : 0);
   // fh_set_denoise_motion: the history is kept with the instance matrices it was written under; where they differ from the context's, the call carries the moved
   // instances' pixels itself (motion.hip).  Everything that can fail is decided before the first launch.
   const size_t nf = ctx->h_o2w.size();
@@ -1313,7 +1311,7 @@ int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_d
                      (std::memcmp(ctx->hist_o2w.data(), ctx->h_o2w.data(), nf * sizeof(float)) != 0 || std::memcmp(ctx->hist_w2o.data(), ctx->h_w2o.data(), nf * sizeof(float)) != 0);
   int rc;
   if (!moved) {
-    rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
+    rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, nullptr, 0u, nullptr, denoised, upscale2x ? 1 : 0);
   } else {
     if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_denoise_temporal: instances moved and the BVH has not been built (fh_set_denoise_motion)");
     const uint32_t ni = (uint32_t)(nf / 12);
@@ -1331,7 +1329,7 @@ int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_d
       ctx->motion_ids_pixels = px;
     }
     if ((rc = primary_instances_submit(ctx, camera, width, height, ctx->d_motion_ids))) return rc;
-    rc = denoise_temporal_motion_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, ctx->d_motion_ids, ni, table.data(), denoised, upscale2x ? 1 : 0);
+    rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, ctx->d_motion_ids, ni, table.data(), denoised, upscale2x ? 1 : 0);
   }
   if (rc == FH_OK) { ctx->hist_o2w = ctx->h_o2w; ctx->hist_w2o = ctx->h_w2o; }
   return rc;

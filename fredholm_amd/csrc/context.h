@@ -247,7 +247,7 @@ struct fh_ctx {
   fh_camera hist_camera{};
   float hist_w2c[12] = {};
   float hist_inv_tan = 0.0f;
-  // per-instance motion vectors (motion.hip, denoise.hip: k_temporal_motion).  denoise_motion: fh_set_denoise_motion; hist_o2w / hist_w2o: the instance matrices the
+  // per-instance motion vectors (motion.hip, denoise.hip: k_temporal<kLookMotion, .>).  denoise_motion: fh_set_denoise_motion; hist_o2w / hist_w2o: the instance matrices the
   // history was written under (empty: no snapshot).  The motion table of a call goes through the pinned h_motion (ev_motion: its copy has been taken) to d_motion;
   // d_motion_ids is the id plane of the calls the context feeds itself.
   int denoise_motion = 0;
@@ -258,10 +258,10 @@ struct fh_ctx {
   hipEvent_t ev_motion = nullptr;
   uint32_t* d_motion_ids = nullptr;
   size_t motion_ids_pixels = 0;
-  // fh_set_denoise_response (denoise.hip: k_temporal_response): while on, the temporal stage clips the history it found to the current frame's 5 x 5 colour box
+  // fh_set_denoise_response (denoise.hip: k_temporal<., kClipColour>): while on, the temporal stage clips the history it found to the current frame's 5 x 5 colour box
   int denoise_response = 0;
   float response_gamma = 1.0f;
-  // fh_set_denoise_response_noise (k_temporal_response_noise): the clipped history is clamped to the pixel's measured noise as well; inert while the switch above is off
+  // fh_set_denoise_response_noise (k_temporal<., kClipColourNoise>): the clipped history is clamped to the pixel's measured noise as well; inert while the switch above is off
   int denoise_response_noise = 0;
   float response_kappa = 6.0f;
 
@@ -324,10 +324,8 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
 int denoise_submit(fh_ctx* ctx, int w, int h, const float* beauty, const float* normal, const float* albedo, float* out, int upscale);  // post.hip
 int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* params, float* out, int upscale);  // denoise.hip (arguments checked by the caller)
 // denoise.hip (arguments checked by the caller); w2c, inv_tan: `cam` inverted and its cam_inv_tan, kept with the history this call writes
+// ids == nullptr: no motion stage; else ids a device pointer and motion a host array of n_instances entries of which at least one has moved (k_temporal<kLookMotion, .>)
 int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
-                            const fh_denoise_params* params, float* out, int upscale);
-// the same with the motion stage (k_temporal_motion): ids a device pointer, motion a host array of n_instances entries of which at least one has moved
-int denoise_temporal_motion_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
-                                   const fh_denoise_params* params, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale);
+                            const fh_denoise_params* params, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale);
 int primary_instances_submit(fh_ctx* ctx, const fh_camera* cam, uint32_t w, uint32_t h, uint32_t* ids);  // motion.hip (arguments checked by the caller)
 }  // namespace fh

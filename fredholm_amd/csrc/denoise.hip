@@ -14,10 +14,10 @@
 // DENSE neighbours, which the lattice does not hold.
 //
 // fh_denoise_temporal runs the same preparation and the same passes with one launch between them, k_temporal below: the frame's (c, v) blended with the context's
-// history of the frames before it, found again through the world position and the previous call's camera.  fh_denoise_temporal_motion launches k_temporal_motion in
-// its place where an instance moved: the same stage with the pixels of moved instances carried to where their surface was.  While fh_set_denoise_response is on, all
-// three are replaced by k_temporal_response, which clamps the history it found to the current frame's local colour statistics before the blend; with
-// fh_set_denoise_response_noise on as well and moments given, by k_temporal_response_noise, which also clamps it to the pixel's own measured noise.
+// history of the frames before it, found again through the world position and the previous call's camera.  k_temporal<LOOK, CLIP> is one template.  LOOK is how the
+// history is found: fh_denoise_temporal_motion, where an instance moved, carries the pixels of moved instances to where their surface was.  CLIP is what happens to it
+// before the blend: while fh_set_denoise_response is on it is clamped to the current frame's local colour statistics, and with fh_set_denoise_response_noise on as well
+// and moments given, also to the pixel's own measured noise.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -240,12 +240,18 @@ void launch_pass(const GuidedArgs& a, bool last, dim3 grid, hipStream_t st)
 // A pixel reads its own (c, v), N, P, Z, looks its history up -- at itself when the camera stood still, else at the 2 x 2 taps around where the previous camera saw
 // P -- blends, and writes the new history, which is also what the first pass reads.  32 x 8 pixels per workgroup like the passes: a wave is two rows of 32, whose taps
 // after a small camera step are again two or three rows of neighbouring 16-byte elements in each of the three history images.
+//
+// One kernel template, k_temporal<LOOK, CLIP>, whose parts below are each written once; the host picks the instance (the choice is the same for every pixel).  The build
+// is fp32 without contraction, so a part gives the same bits in every instance it is inlined into, and the GPU suites hold each instance to the restatement's bits.
+enum { kLookNone, kLookOwn, kLookReproject, kLookMotion };  // LOOK: there is no history; the camera stood still; it moved; fh_denoise_temporal_motion with a moved instance
+enum { kClipOff, kClipColour, kClipColourNoise };          // CLIP: fh_set_denoise_response off; on; on with fh_set_denoise_response_noise and moments
+
 struct TemporalArgs {
   const float4* cv;       // (c.rgb, v) of the preparation
   const float4* normal;
   const float4* position;
   const float* depth;
-  const float4* h_cv;     // the history read (MODE != 0): (c_acc.rgb, v_acc)
+  const float4* h_cv;     // the history read (LOOK != kLookNone): (c_acc.rgb, v_acc)
   const float4* h_ph;     // (P, h)
   const float4* h_n;      // N
   float4* o_cv;           // the history written; o_cv is the (c, v) image of the first pass
@@ -256,14 +262,15 @@ struct TemporalArgs {
   float m[12];            // world-to-camera rows of the camera the history was written with
   float f, W, H;          // its cam_inv_tan; width and height as floats
   float alpha_min, max_history, cos_min, plane_tol;
-};
-// what k_temporal_motion takes besides (an argument of its own: the kernels above keep their argument block)
-struct MotionArgs {
+  // kLookMotion
   const uint32_t* ids;     // the instance each pixel's chief ray sees (fh_primary_instances)
   const fh_motion* motion; // n_instances entries, on the device
   uint32_t n_instances;
   int still;               // the camera has the stored camera's bits
+  float gamma, kappa;      // CLIP: fh_set_denoise_response, fh_set_denoise_response_noise
 };
+// what a pixel found of its history: colour, variance, length
+struct History { float x, y, z, v, h; };
 
 __device__ __forceinline__ bool td_hit(const float4 n) { return n.x != 0.0f || n.y != 0.0f || n.z != 0.0f; }
 // the two stops of a history tap (its normal nq and position ph.xyz) seen from the pixel (np, pp); lim = plane_tol * max(Z_p, 1e-3)
@@ -275,67 +282,16 @@ __device__ __forceinline__ bool td_valid(const TemporalArgs& A, const float4 np,
   return td_hit(nq) && dn >= A.cos_min && dp <= lim;
 }
 
-// MODE 0: there is no history; 1: the camera stood still; 2: it moved (decided on the host: the branch is the same for every pixel)
-template <int MODE>
-__global__ void __launch_bounds__(256) k_temporal(const TemporalArgs A)
+// the still camera's look-up: the pixel's own history, if it passes the two stops; false: no history
+__device__ __forceinline__ bool td_own_tap(const TemporalArgs& A, int p, const float4 np, const float4 pp, float lim, History& H)
 {
-  const int x = blockIdx.x * kTW + threadIdx.x, y = blockIdx.y * kTH + threadIdx.y;
-  if (x >= A.w || y >= A.h) return;
-  const int p = x + A.w * y;
-  const float4 cv = A.cv[p], np = A.normal[p], pp = A.position[p];
-  float cx = cv.x, cy = cv.y, cz = cv.z, v = cv.w, hist = 0.0f;
-  if (td_hit(np)) {
-    hist = 1.0f;
-    bool have = false;
-    float hx = 0.0f, hy = 0.0f, hz = 0.0f, hv = 0.0f, hh = 0.0f;
-    if constexpr (MODE == 1) {
-      const float lim = A.plane_tol * fmaxf(A.depth[p], 1e-3f);
-      const float4 qc = A.h_cv[p], qp = A.h_ph[p], qn = A.h_n[p];
-      have = td_valid(A, np, pp, lim, qn, qp);
-      hx = qc.x; hy = qc.y; hz = qc.z; hv = qc.w; hh = qp.w;
-    }
-    if constexpr (MODE == 2) {
-      const float lim = A.plane_tol * fmaxf(A.depth[p], 1e-3f);
-      const float qx = ((A.m[0] * pp.x + A.m[1] * pp.y) + A.m[2] * pp.z) + A.m[3];
-      const float qy = ((A.m[4] * pp.x + A.m[5] * pp.y) + A.m[6] * pp.z) + A.m[7];
-      const float qz = ((A.m[8] * pp.x + A.m[9] * pp.y) + A.m[10] * pp.z) + A.m[11];
-      const float t = (A.f - qz) / A.f;
-      if (t > 0.0f) {
-        const float xs = (A.W + (A.H * qx) / t) * 0.5f - 0.5f, ys = (A.H - (A.H * qy) / t) * 0.5f - 0.5f;
-        const float ix = floorf(xs), iy = floorf(ys), fx = xs - ix, fy = ys - iy;
-        float S = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const float tx = ix + (float)i, ty = iy + (float)j;
-            const bool inside = tx >= 0.0f && tx <= A.W - 1.0f && ty >= 0.0f && ty <= A.H - 1.0f;  // (false for NaN: the clamps below then give pixel 0)
-            const int q = (int)fminf(fmaxf(tx, 0.0f), A.W - 1.0f) + A.w * (int)fminf(fmaxf(ty, 0.0f), A.H - 1.0f);
-            const float4 qc = A.h_cv[q], qp = A.h_ph[q], qn = A.h_n[q];
-            const float wgt = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
-            if (inside && td_valid(A, np, pp, lim, qn, qp)) {
-              S += wgt; hx += wgt * qc.x; hy += wgt * qc.y; hz += wgt * qc.z; hv += wgt * qc.w; hh += wgt * qp.w;
-            }
-          }
-        have = S >= 1e-3f;
-        hx = hx / S; hy = hy / S; hz = hz / S; hv = hv / S; hh = hh / S;
-      }
-    }
-    if (have) {
-      hist = fminf(hh + 1.0f, A.max_history);
-      const float a = fmaxf(1.0f / hist, A.alpha_min), b = 1.0f - a;
-      cx = b * hx + a * cx; cy = b * hy + a * cy; cz = b * hz + a * cz;
-      v = (b * b) * hv + (a * a) * v;
-    }
-  }
-  A.o_cv[p] = make_float4(cx, cy, cz, v);
-  A.o_ph[p] = make_float4(pp.x, pp.y, pp.z, hist);
-  A.o_n[p] = np;
-  A.vplane[p] = v;
+  const float4 qc = A.h_cv[p], qp = A.h_ph[p], qn = A.h_n[p];
+  H = {qc.x, qc.y, qc.z, qc.w, qp.w};
+  return td_valid(A, np, pp, lim, qn, qp);
 }
 
 // the moved camera's look-up: where the stored camera saw pp, the 2 x 2 taps around it that pass the two stops seen from (np, pp), renormalised; false: no history
-__device__ __forceinline__ bool td_reproject(const TemporalArgs& A, const float4 np, const float4 pp, float lim, float& hx, float& hy, float& hz, float& hv, float& hh)
+__device__ __forceinline__ bool td_reproject(const TemporalArgs& A, const float4 np, const float4 pp, float lim, History& H)
 {
   bool have = false;
   const float qx = ((A.m[0] * pp.x + A.m[1] * pp.y) + A.m[2] * pp.z) + A.m[3];
@@ -356,43 +312,34 @@ __device__ __forceinline__ bool td_reproject(const TemporalArgs& A, const float4
         const float4 qc = A.h_cv[q], qp = A.h_ph[q], qn = A.h_n[q];
         const float wgt = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
         if (inside && td_valid(A, np, pp, lim, qn, qp)) {
-          S += wgt; hx += wgt * qc.x; hy += wgt * qc.y; hz += wgt * qc.z; hv += wgt * qc.w; hh += wgt * qp.w;
+          S += wgt; H.x += wgt * qc.x; H.y += wgt * qc.y; H.z += wgt * qc.z; H.v += wgt * qc.w; H.h += wgt * qp.w;
         }
       }
     have = S >= 1e-3f;
-    hx = hx / S; hy = hy / S; hz = hz / S; hv = hv / S; hh = hh / S;
+    H.x = H.x / S; H.y = H.y / S; H.z = H.z / S; H.v = H.v / S; H.h = H.h / S;
   }
   return have;
 }
 
-
-// the "motion" form of k_temporal (fh_denoise_temporal_motion; the header states it): a pixel of an instance that moved is CARRIED to where its surface was, by the
-// instance's affine map, and takes the look-up of MODE 2 there whatever the camera did; the other pixels take MODE 1's tap under a still camera (uniform: decided on the
-// host) and MODE 2's look-up otherwise.  It reads 4 more bytes per pixel than MODE 2 and an 88-byte table entry that a wave shares.  A kernel of its own, not a fourth
-// MODE: its arguments would grow the argument block of the three above.
-__global__ void __launch_bounds__(256) k_temporal_motion(const TemporalArgs A, const MotionArgs M)
+// the look-up of a pixel that hit something (H comes in as zeros).  kLookMotion (the header states it): a pixel of an instance that moved is CARRIED to where its
+// surface was, by the instance's affine map, and is reprojected from there whatever the camera did; the other pixels take their own tap under a still camera and the
+// reprojection otherwise.  It reads 4 more bytes per pixel than kLookReproject and an 88-byte table entry that a wave shares.
+template <int LOOK>
+__device__ __forceinline__ bool td_lookup(const TemporalArgs& A, int p, const float4 np, const float4 pp, History& H)
 {
-  const int x = blockIdx.x * kTW + threadIdx.x, y = blockIdx.y * kTH + threadIdx.y;
-  if (x >= A.w || y >= A.h) return;
-  const int p = x + A.w * y;
-  const float4 cv = A.cv[p], np = A.normal[p], pp = A.position[p];
-  float cx = cv.x, cy = cv.y, cz = cv.z, v = cv.w, hist = 0.0f;
-  if (td_hit(np)) {
-    hist = 1.0f;
-    bool have = false;
-    float hx = 0.0f, hy = 0.0f, hz = 0.0f, hv = 0.0f, hh = 0.0f;
+  if constexpr (LOOK == kLookNone) {
+    return false;
+  } else {
     const float lim = A.plane_tol * fmaxf(A.depth[p], 1e-3f);
-    const uint32_t inst = M.ids[p];
-    const bool carried = inst < M.n_instances && M.motion[inst < M.n_instances ? inst : 0u].moved != 0u;
-    if (!carried && M.still) {
-      const float4 qc = A.h_cv[p], qp = A.h_ph[p], qn = A.h_n[p];
-      have = td_valid(A, np, pp, lim, qn, qp);
-      hx = qc.x; hy = qc.y; hz = qc.z; hv = qc.w; hh = qp.w;
-    } else {
-      float4 nb = np, pb = pp;
+    bool own = LOOK == kLookOwn;
+    float4 nb = np, pb = pp;
+    if constexpr (LOOK == kLookMotion) {
+      const uint32_t inst = A.ids[p];
+      const bool carried = inst < A.n_instances && A.motion[inst < A.n_instances ? inst : 0u].moved != 0u;
+      own = !carried && A.still;
       if (carried) {
-        const float* a = M.motion[inst].point;
-        const float* g = M.motion[inst].normal;
+        const float* a = A.motion[inst].point;
+        const float* g = A.motion[inst].normal;
         pb.x = ((a[0] * pp.x + a[1] * pp.y) + a[2] * pp.z) + a[3];
         pb.y = ((a[4] * pp.x + a[5] * pp.y) + a[6] * pp.z) + a[7];
         pb.z = ((a[8] * pp.x + a[9] * pp.y) + a[10] * pp.z) + a[11];
@@ -400,14 +347,65 @@ __global__ void __launch_bounds__(256) k_temporal_motion(const TemporalArgs A, c
         nb.y = (g[3] * np.x + g[4] * np.y) + g[5] * np.z;
         nb.z = (g[6] * np.x + g[7] * np.y) + g[8] * np.z;
       }
-      have = td_reproject(A, nb, pb, lim, hx, hy, hz, hv, hh);
     }
-    if (have) {
-      hist = fminf(hh + 1.0f, A.max_history);
-      const float a = fmaxf(1.0f / hist, A.alpha_min), b = 1.0f - a;
-      cx = b * hx + a * cx; cy = b * hy + a * cy; cz = b * hz + a * cz;
-      v = (b * b) * hv + (a * a) * v;
+    return own ? td_own_tap(A, p, np, pp, lim, H) : td_reproject(A, nb, pb, lim, H);
+  }
+}
+
+// the clip (fh_set_denoise_response; the header states it step by step): the history a pixel found is clamped, before the blend, to mean +- gamma * standard deviation
+// of the CURRENT frame's colour over the pixel's 5 x 5 window, and shortened by how far outside that box it lay.  The 25 taps come from the staged tile (k_temporal);
+// kc: the pixel's place in it; cv: its own (c, v).  kClipColourNoise (fh_set_denoise_response_noise, step 4b): the clipped history is clamped once more, to the pixel's
+// own colour +- kappa standard deviations of what it measured -- the preparation's variance v plus the history's v_h, both in registers already -- and shortened by the
+// larger of the two excesses.  No new load, no more LDS.
+template <int CLIP>
+__device__ __forceinline__ void td_clip(const TemporalArgs& A, const float4* s_cv, const float4* s_n, int kc, const float4 np, const float4 cv, History& H)
+{
+  // 1: the window.  A tap that does not count adds + 0, which changes no bit of a sum that started at + 0.
+  float n = 0.0f, s1x = 0.0f, s1y = 0.0f, s1z = 0.0f, s2x = 0.0f, s2y = 0.0f, s2z = 0.0f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy)
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      const int k = kc + dy * kGW + dx;
+      const float4 cq = s_cv[k], nq = s_n[k];
+      const bool counts = (dx == 0 && dy == 0) || (td_hit(nq) && (np.x * nq.x + np.y * nq.y) + np.z * nq.z >= A.cos_min);
+      n += counts ? 1.0f : 0.0f;
+      s1x += counts ? cq.x : 0.0f; s1y += counts ? cq.y : 0.0f; s1z += counts ? cq.z : 0.0f;
+      s2x += counts ? cq.x * cq.x : 0.0f; s2y += counts ? cq.y * cq.y : 0.0f; s2z += counts ? cq.z * cq.z : 0.0f;
     }
+  float u = 0.0f;
+  if (n >= 2.0f) {  // (3: a window of the pixel alone clips nothing)
+    // 2: the box; 4: the clip.  fmaxf and fminf drop a NaN operand.
+    const float mx = s1x / n, my = s1y / n, mz = s1z / n;
+    const float gx = A.gamma * fhe_sqrt(fmaxf(s2x / n - mx * mx, 0.0f)), gy = A.gamma * fhe_sqrt(fmaxf(s2y / n - my * my, 0.0f)), gz = A.gamma * fhe_sqrt(fmaxf(s2z / n - mz * mz, 0.0f));
+    const float ccx = fminf(fmaxf(H.x, mx - gx), mx + gx), ccy = fminf(fmaxf(H.y, my - gy), my + gy), ccz = fminf(fmaxf(H.z, mz - gz), mz + gz);
+    const float ux = fabsf(ccx - H.x) / (gx + 1e-6f), uy = fabsf(ccy - H.y) / (gy + 1e-6f), uz = fabsf(ccz - H.z) / (gz + 1e-6f);
+    u = fmaxf(fmaxf(ux, uy), uz);
+    H.x = ccx; H.y = ccy; H.z = ccz;
+  }
+  if constexpr (CLIP == kClipColourNoise) {
+    // 4b: the noise box around the pixel's own colour, also where step 3 left the history alone; v_h as looked up.  A NaN s drops out of every fmaxf and fminf.
+    const float s = A.kappa * fhe_sqrt(cv.w + H.v);
+    const float dx = fminf(fmaxf(H.x, cv.x - s), cv.x + s), dy = fminf(fmaxf(H.y, cv.y - s), cv.y + s), dz = fminf(fmaxf(H.z, cv.z - s), cv.z + s);
+    const float wx = fabsf(dx - H.x) / (s + 1e-6f), wy = fabsf(dy - H.y) / (s + 1e-6f), wz = fabsf(dz - H.z) / (s + 1e-6f);
+    u = fmaxf(u, fmaxf(fmaxf(wx, wy), wz));
+    H.x = dx; H.y = dy; H.z = dz;
+  }
+  if (CLIP == kClipColourNoise || n >= 2.0f) {  // 5: the shortened history (where step 3 left it alone and there is no step 4b, it keeps its length)
+    const float k1 = 1.0f + u;
+    H.h = H.h / k1; H.v = H.v * k1;
+  }
+}
+
+// the blend of the frame's (c, v) with the history, if there is one, and the four stores
+__device__ __forceinline__ void td_blend_store(const TemporalArgs& A, int p, const float4 cv, const float4 np, const float4 pp, bool have, const History& H)
+{
+  float cx = cv.x, cy = cv.y, cz = cv.z, v = cv.w, hist = td_hit(np) ? 1.0f : 0.0f;
+  if (have) {
+    hist = fminf(H.h + 1.0f, A.max_history);
+    const float a = fmaxf(1.0f / hist, A.alpha_min), b = 1.0f - a;
+    cx = b * H.x + a * cx; cy = b * H.y + a * cy; cz = b * H.z + a * cz;
+    v = (b * b) * H.v + (a * a) * v;
   }
   A.o_cv[p] = make_float4(cx, cy, cz, v);
   A.o_ph[p] = make_float4(pp.x, pp.y, pp.z, hist);
@@ -415,33 +413,60 @@ __global__ void __launch_bounds__(256) k_temporal_motion(const TemporalArgs A, c
   A.vplane[p] = v;
 }
 
-// the clipped forms of the three kernels above (fh_set_denoise_response; the header states them step by step): the history a pixel found is clamped, before the
-// blend, to mean +- gamma * standard deviation of the CURRENT frame's colour over the pixel's 5 x 5 window, and shortened by how far outside that box it lay.
-// KIND 1: k_temporal<1>'s tap, 2: k_temporal<2>'s look-up, 3: k_temporal_motion's.  The workgroup's 32 x 8 pixels take their 25 taps from the 36 x 12 tile of
-// (c.rgb, v) and N it stages once: 432 x 32 bytes = 13.5 KiB of LDS.  Neither LDS (eleven workgroups a CU) nor the wave slots (eight) limit residency: the 83 VGPRs the
-// unrolled window takes do, at 5 waves per SIMD = 5 workgroups per CU.  A tile element outside the
-// frame is staged with N = 0, which is what a miss has: neither counts.  Every thread of a partial tile stages (the loop runs over the tile, not over the live
-// pixels) and only then do the threads without a pixel leave.  A row of 32 pixels reads 32 consecutive float4 of a tile row per tap: every bank once per 16 lanes.
-//
-// NOISE (fh_set_denoise_response_noise, step 4b of the header): the clipped history is clamped once more, to the pixel's own colour +- kappa standard deviations of
-// what it measured -- the preparation's variance v plus the history's v_h, both in registers already -- and shortened by the larger of the two excesses.  No new load,
-// no more LDS.  The body, temporal_response_body.h, is included into both kernel templates: they differ in that step alone, and k_temporal_response, which a
-// function call between it and its body would recompile with other operand orders, keeps its instruction stream.
-template <int KIND>
-__global__ void __launch_bounds__(256) k_temporal_response(const TemporalArgs A, const MotionArgs M, const float gamma)
+// With the clip, the workgroup's 32 x 8 pixels take their 25 taps from the 36 x 12 tile of (c.rgb, v) and N it stages once: 432 x 32 bytes = 13.5 KiB of LDS.  Neither LDS
+// (eleven workgroups a CU) nor the wave slots (eight) limit residency: the 83 VGPRs the unrolled window takes do, at 5 waves per SIMD = 5 workgroups per CU.  A tile
+// element outside the frame is staged with N = 0, which is what a miss has: neither counts.  Every thread of a partial tile stages (the loop runs over the tile, not
+// over the live pixels) and only then do the threads without a pixel leave.  A row of 32 pixels reads 32 consecutive float4 of a tile row per tap: every bank once per
+// 16 lanes.  Without the clip the arrays are never referenced: no LDS, and the pixel's (c, v) and N come from global memory.
+template <int LOOK, int CLIP>
+__global__ void __launch_bounds__(256) k_temporal(const TemporalArgs A)
 {
-  constexpr bool NOISE = false;
-  constexpr float kappa = 0.0f;
-#include "temporal_response_body.h"
+  static_assert(LOOK != kLookNone || CLIP == kClipOff, "without a history there is nothing to clip");
+  constexpr bool kTile = CLIP != kClipOff;
+  __shared__ float4 s_cv[kTile ? kGN : 1];  // c.rgb, v of the preparation
+  __shared__ float4 s_n[kTile ? kGN : 1];   // N; 0 outside the frame
+  const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+  if constexpr (kTile) {
+    const int tid = threadIdx.y * kTW + threadIdx.x;
+    for (int k = tid; k < kGN; k += 256) {
+      const int qx = x0 + k % kGW - 2, qy = y0 + k / kGW - 2;
+      float4 cq = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nq = cq;
+      if (qx >= 0 && qx < A.w && qy >= 0 && qy < A.h) { cq = A.cv[qx + A.w * qy]; nq = A.normal[qx + A.w * qy]; }
+      s_cv[k] = cq;
+      s_n[k] = nq;
+    }
+    __syncthreads();
+  }
+  const int x = x0 + (int)threadIdx.x, y = y0 + (int)threadIdx.y;
+  if (x >= A.w || y >= A.h) return;
+  const int p = x + A.w * y;
+  const int kc = ((int)threadIdx.y + 2) * kGW + (int)threadIdx.x + 2;
+  float4 cv, np;
+  if constexpr (kTile) { cv = s_cv[kc]; np = s_n[kc]; } else { cv = A.cv[p]; np = A.normal[p]; }
+  const float4 pp = A.position[p];
+  History H = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool have = false;
+  if (td_hit(np)) {
+    have = td_lookup<LOOK>(A, p, np, pp, H);
+    if constexpr (kTile)
+      if (have) td_clip<CLIP>(A, s_cv, s_n, kc, np, cv, H);
+  }
+  td_blend_store(A, p, cv, np, pp, have, H);
 }
 
-// the same with step 4b; launched only for a call that has moments (without them v is the 7 x 7 spatial estimate, large at exactly the edges this step is for)
-template <int KIND>
-__global__ void __launch_bounds__(256) k_temporal_response_noise(const TemporalArgs A, const MotionArgs M, const float gamma, const float kappa)
+using TemporalLaunch = void (*)(const TemporalArgs&, dim3, hipStream_t);
+template <int LOOK, int CLIP>
+void temporal_launch(const TemporalArgs& a, dim3 grid, hipStream_t st)
 {
-  constexpr bool NOISE = true;
-#include "temporal_response_body.h"
+  hipLaunchKernelGGL((k_temporal<LOOK, CLIP>), grid, dim3(kTW, kTH), 0, st, a);
 }
+// [LOOK][CLIP]: the ten instances in use
+constexpr TemporalLaunch kTemporalLaunch[4][3] = {
+    {temporal_launch<kLookNone, kClipOff>, nullptr, nullptr},
+    {temporal_launch<kLookOwn, kClipOff>, temporal_launch<kLookOwn, kClipColour>, temporal_launch<kLookOwn, kClipColourNoise>},
+    {temporal_launch<kLookReproject, kClipOff>, temporal_launch<kLookReproject, kClipColour>, temporal_launch<kLookReproject, kClipColourNoise>},
+    {temporal_launch<kLookMotion, kClipOff>, temporal_launch<kLookMotion, kClipColour>, temporal_launch<kLookMotion, kClipColourNoise>},
+};
 
 }  // namespace
 
@@ -536,9 +561,11 @@ int motion_upload(fh_ctx* ctx, uint32_t n, const fh_motion* motion)
   return FH_OK;
 }
 
-// ids == nullptr: fh_denoise_temporal
-int temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
-                    const fh_denoise_params* pr, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale)
+}  // namespace
+
+// ids == nullptr: no motion stage (fh_denoise_temporal, or no instance moved)
+int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
+                            const fh_denoise_params* pr, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale)
 {
   const size_t px = (size_t)w * h;
   if (const int rc = guided_scratch(ctx, px)) return rc;
@@ -566,43 +593,18 @@ int temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, cons
   for (int k = 0; k < 12; ++k) a.m[k] = ctx->hist_w2c[k];
   a.f = ctx->hist_inv_tan;
   a.alpha_min = tp->alpha_min; a.max_history = tp->max_history; a.cos_min = tp->normal_cos_min; a.plane_tol = tp->plane_tol;
-  const dim3 grid((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), block(kTW, kTH);
   const bool still = std::memcmp(cam, &ctx->hist_camera, sizeof(fh_camera)) == 0;
-  const MotionArgs ma{ids, ctx->d_motion, n_instances, still ? 1 : 0};
-  if (ctx->hist_frames == 0) hipLaunchKernelGGL((k_temporal<0>), grid, block, 0, ctx->stream, a);
-  else if (ctx->denoise_response) {  // fh_set_denoise_response: the clipped form of whichever of the three kernels below the call would launch
-    const float gamma = ctx->response_gamma, kappa = ctx->response_kappa;
-    if (ctx->denoise_response_noise && in->moments) {  // fh_set_denoise_response_noise: the measured variance exists only with moments
-      if (with_motion) hipLaunchKernelGGL((k_temporal_response_noise<3>), grid, block, 0, ctx->stream, a, ma, gamma, kappa);
-      else if (still) hipLaunchKernelGGL((k_temporal_response_noise<1>), grid, block, 0, ctx->stream, a, ma, gamma, kappa);
-      else hipLaunchKernelGGL((k_temporal_response_noise<2>), grid, block, 0, ctx->stream, a, ma, gamma, kappa);
-    }
-    else if (with_motion) hipLaunchKernelGGL((k_temporal_response<3>), grid, block, 0, ctx->stream, a, ma, gamma);
-    else if (still) hipLaunchKernelGGL((k_temporal_response<1>), grid, block, 0, ctx->stream, a, ma, gamma);
-    else hipLaunchKernelGGL((k_temporal_response<2>), grid, block, 0, ctx->stream, a, ma, gamma);
-  }
-  else if (with_motion) hipLaunchKernelGGL(k_temporal_motion, grid, block, 0, ctx->stream, a, ma);
-  else if (still) hipLaunchKernelGGL((k_temporal<1>), grid, block, 0, ctx->stream, a);
-  else hipLaunchKernelGGL((k_temporal<2>), grid, block, 0, ctx->stream, a);
+  a.ids = ids; a.motion = ctx->d_motion; a.n_instances = n_instances; a.still = still ? 1 : 0;
+  a.gamma = ctx->response_gamma; a.kappa = ctx->response_kappa;
+  const int look = ctx->hist_frames == 0 ? kLookNone : with_motion ? kLookMotion : still ? kLookOwn : kLookReproject;
+  // fh_set_denoise_response clips whatever history the call looks up; fh_set_denoise_response_noise adds its step only with moments (the measured variance exists only then)
+  const int clip = look == kLookNone || !ctx->denoise_response ? kClipOff : ctx->denoise_response_noise && in->moments ? kClipColourNoise : kClipColour;
+  kTemporalLaunch[look][clip](a, dim3((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), ctx->stream);
   ctx->hist_cur = to; ctx->hist_camera = *cam; ctx->hist_inv_tan = inv_tan;
   for (int k = 0; k < 12; ++k) ctx->hist_w2c[k] = w2c[k];
   ctx->hist_w = (uint32_t)w; ctx->hist_h = (uint32_t)h;
   if (ctx->hist_frames != 0xffffffffu) ++ctx->hist_frames;
   return guided_passes(ctx, w, h, in, pr, ctx->d_hist_cv[to], out, upscale);
-}
-
-}  // namespace
-
-int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
-                            const fh_denoise_params* pr, float* out, int upscale)
-{
-  return temporal_submit(ctx, w, h, in, cam, w2c, inv_tan, tp, pr, nullptr, 0u, nullptr, out, upscale);
-}
-
-int denoise_temporal_motion_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
-                                   const fh_denoise_params* pr, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale)
-{
-  return temporal_submit(ctx, w, h, in, cam, w2c, inv_tan, tp, pr, ids, n_instances, motion, out, upscale);
 }
 
 }  // namespace fh

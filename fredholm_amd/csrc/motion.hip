@@ -1,5 +1,5 @@
 // motion.hip -- per-instance motion vectors for the temporal stage (include/fredholm_hip.h): the id plane (fh_primary_instances), the host-side motion table
-// (fh_motion_from_transforms), and the entry points that feed denoise.hip's k_temporal_motion (fh_denoise_temporal_motion, fh_set_denoise_motion).
+// (fh_motion_from_transforms), and the entry points that feed denoise.hip's k_temporal<kLookMotion, .> (fh_denoise_temporal_motion, fh_set_denoise_motion).
 //
 // k_primary_instances: every pixel builds its chief ray (fh_chief_ray.h) and traces it for its closest hit with the traversal code the render kernels run, entered
 // the way fh_trace_rays (kat.hip) enters it: the wave-cooperative traversal with its per-wave LDS on trees small enough for it, `traverse` otherwise.  32 x 8 pixels
@@ -107,9 +107,8 @@ int fh_motion_from_transforms(uint32_t n, const float* o2w_prev, const float* w2
 int fh_denoise_temporal_motion(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const fh_temporal_params* temporal,
                                const fh_denoise_params* params, const uint32_t* instance_ids, uint32_t n_instances, const fh_motion* motion, float* denoised, int upscale2x)
 {
-  const fh_denoise_params defaults = {2.0f, 1.0f, 0.2f, 7u, 5u};
   const fh_temporal_params temporal_defaults = {0.2f, 32.0f, 0.5f, 0.02f};
-  const fh_denoise_params pr = params ? *params : defaults;
+  const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
   const fh_temporal_params tp = temporal ? *temporal : temporal_defaults;
   float w2c[12], inv_tan = 0.0f;
   bool any_moved = false;
@@ -119,8 +118,7 @@ int fh_denoise_temporal_motion(fh_ctx* ctx, uint32_t width, uint32_t height, con
   if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_temporal_motion: ") + why);
   FH_GROUP_LEAD(ctx);
   MCTX_CHECK(ctx);
-  if (!any_moved) return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
-  return denoise_temporal_motion_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, instance_ids, n_instances, motion, denoised, upscale2x ? 1 : 0);
+  return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, any_moved ? instance_ids : nullptr, n_instances, motion, denoised, upscale2x ? 1 : 0);
 }
 
 int fh_set_denoise_motion(fh_ctx* ctx, int on)

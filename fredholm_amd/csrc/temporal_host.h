@@ -8,6 +8,8 @@
 
 namespace fh {
 
+constexpr fh_denoise_params kDenoiseDefaults = {2.0f, 1.0f, 0.2f, 7u, 5u};  // what a null fh_denoise_params means (the header states them)
+
 // why fh_denoise_guided refuses these arguments, or nullptr (the context is not looked at)
 inline const char* guided_refusal(uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_denoise_params& pr, const float* denoised)
 {

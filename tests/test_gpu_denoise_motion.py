@@ -1,5 +1,5 @@
 """Tests of the per-instance motion vectors of temporal accumulation (include/fredholm_hip.h: fh_primary_instances, fh_motion_from_transforms,
-fh_denoise_temporal_motion, fh_set_denoise_motion; fredholm_amd/csrc/motion.hip and denoise.hip: k_temporal_motion).  The restatement of
+fh_denoise_temporal_motion, fh_set_denoise_motion; fredholm_amd/csrc/motion.hip and denoise.hip: k_temporal<kLookMotion, .>).  The restatement of
 test_gpu_denoise_temporal.py is extended by the motion stage as the header states it, in float64 and in float32, and the device is held to that suite's bound:
 4 x the largest float32-versus-float64 difference of the same case.  The tests marked gpu need the device; the host motion function, the chief-ray restatement's
 own consistency and the share of carried pixels that find a history are checked on the CPU.
@@ -554,8 +554,8 @@ def test_an_unmoved_table_gives_the_plain_calls_bits(renderer):
 
 @gpu
 def test_carried_pixels_with_identity_maps_take_the_moved_cameras_look_up_bit_for_bit(renderer):
-    """k_temporal_motion repeats the 2 x 2 look-up of k_temporal<2>: with every pixel carried by maps that are the identity (a table marked moved by hand), Pb and Nb
-    have P's and N's bits, so under a moved camera the whole call must equal the plain one in every pixel -- the two copies of the tap code are held in step here"""
+    """k_temporal<kLookMotion, .> takes the 2 x 2 look-up of k_temporal<kLookReproject, .>: with every pixel carried by maps that are the identity (a table marked moved by
+    hand), Pb and Nb have P's and N's bits, so under a moved camera the whole call must equal the plain one in every pixel"""
     frames = T._abc("37x29", 94)  # cameras A, B, A: the second and third call reproject
     want = _plain_sequence(renderer, frames)
     table = (N.MotionC * 1)()

@@ -1,5 +1,5 @@
 """Tests of the noise box of the clipped temporal stage (include/fredholm_hip.h: fh_set_denoise_response_noise, step 4b; fredholm_amd/csrc/denoise.hip:
-k_temporal_response_noise).  The restatement of test_denoise_noise_box_host.py -- the response suite's with step 4b -- in float64 and in float32; the device is held
+k_temporal<., kClipColourNoise>).  The restatement of test_denoise_noise_box_host.py -- the response suite's with step 4b -- in float64 and in float32; the device is held
 to the suite's bound, 4 x the largest float32-versus-float64 difference of the same case, and to the float32 restatement's bits.  Where the header promises bits the
 comparison is bit for bit.  The tests marked gpu need the device; that every case has pixels the noise box clips and pixels it leaves alone is checked on the CPU too.
 Quality: the sequences of the response suite, with the replay's record (profiles/denoise_noise_box_replay.json) for the margins."""
@@ -186,8 +186,8 @@ def test_first_call_with_both_switches_on_is_the_guided_filter(renderer, upscale
 
 @gpu
 def test_identity_maps_under_a_moved_camera_give_the_plain_table_call(renderer):
-    """the motion form of the noise kernel with every pixel carried by identity maps must equal its moved-camera form: both go through the look-up of td_reproject,
-    which the response suite holds in step with k_temporal<2>'s"""
+    """the motion form of the noise kernel with every pixel carried by identity maps must equal its moved-camera form: both go through the one look-up, td_reproject,
+    with a carried (P, N) that has the pixel's own bits"""
     frames = T._abc("37x29", 441)
     table = (N.MotionC * 1)()
     for k in range(12):

@@ -1,4 +1,4 @@
-"""Tests of the clipped form of the temporal stage (include/fredholm_hip.h: fh_set_denoise_response; fredholm_amd/csrc/denoise.hip: k_temporal_response).  The
+"""Tests of the clipped form of the temporal stage (include/fredholm_hip.h: fh_set_denoise_response; fredholm_amd/csrc/denoise.hip: k_temporal<., kClipColour>).  The
 restatements of test_gpu_denoise_temporal.py and test_gpu_denoise_motion.py are extended by the header's six steps -- the 5 x 5 window of the current frame's colour,
 the box, the clip, the shortened history -- in float64 and in float32, and the device is held to those suites' bound: 4 x the largest float32-versus-float64
 difference of the same case.  Where the header promises bits the comparison is bit for bit.  The tests marked gpu need the device; that the look-up restated here is the

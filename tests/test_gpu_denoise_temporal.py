@@ -1,4 +1,4 @@
-"""Tests of temporal accumulation (fh_denoise_temporal, fredholm_amd/csrc/denoise.hip: k_temporal) against a numpy restatement of the whole call as
+"""Tests of temporal accumulation (fh_denoise_temporal, fredholm_amd/csrc/denoise.hip: k_temporal<LOOK, kClipOff>) against a numpy restatement of the whole call as
 include/fredholm_hip.h states it: the guided filter's preparation, the temporal stage, the passes.  The tests marked gpu need the device (-m gpu); two run on the CPU
 alone: the reprojection formula against the checker's camera, and the with-history share of the moving-camera cases.
 

@@ -14,18 +14,18 @@ difference of the medians; the kernel's own time comes from running this under `
 --motion (-> profiles/denoise_motion_bench.json): one such frame, and the median of `--calls` calls of fh_primary_instances and of fh_denoise_temporal_motion under a still
 camera with a motion table that alternates between two small translations (--step) of the scene's largest instance, so that every call carries that instance's pixels;
 beside them fh_denoise_temporal with the camera alternating as in --temporal, and fh_denoise_guided.  The two new kernels' own times come from a
-`rocprofv3 --kernel-trace --stats` run of this leg (k_primary_instances*, k_temporal_motion): `--merge-kernel-stats STATS.csv --out FILE` (no GPU) writes those rows of the
+`rocprofv3 --kernel-trace --stats` run of this leg (k_primary_instances*, k_temporal<3, 0>: the motion look-up): `--merge-kernel-stats STATS.csv --out FILE` (no GPU) writes those rows of the
 profiler's kernel_stats.csv into FILE's record as "kernel_us".
 
 --response (-> profiles/denoise_response_bench.json): the two frames of --temporal and the id plane and alternating tables of --motion, and the median of `--calls` calls of
 fh_denoise_temporal (cameras alternating; one frame repeated) and of fh_denoise_temporal_motion with fh_set_denoise_response off and then on (--gamma), in one process, beside
-fh_denoise_guided.  The kernels' own times come from a `rocprofv3 --kernel-trace --stats` run of this leg, in which k_temporal<1>, k_temporal<2>, k_temporal_motion, the
-three k_temporal_response and the k_guided_pass instances all run: `--merge-kernel-stats STATS.csv --out FILE` adds them (with the passes' rows), and
+fh_denoise_guided.  The kernels' own times come from a `rocprofv3 --kernel-trace --stats` run of this leg, in which the instances of k_temporal<LOOK, CLIP> -- LOOK 1, 2, 3: own tap,
+reprojection, motion; CLIP 0, 1: plain, colour box -- and the k_guided_pass instances all run: `--merge-kernel-stats STATS.csv --out FILE` adds them (with the passes' rows), and
 `--resource-usage LOG` the registers, LDS, scratch and occupancy hipcc's -Rpass-analysis=kernel-resource-usage printed for those kernels when denoise.hip was built.
 
 --response --noise (-> profiles/denoise_noise_box_bench.json): the --response leg (every call has moments) with a third round, fh_set_denoise_response_noise on (--kappa) as well:
-plain, clipped, clipped with the noise box, in one process.  In a `rocprofv3 --kernel-trace --stats` run of this leg the three k_temporal_response and the three
-k_temporal_response_noise run side by side: the former are the reference point for the latter."""
+plain, clipped, clipped with the noise box, in one process.  In a `rocprofv3 --kernel-trace --stats` run of this leg the three k_temporal<., 1> and the three
+k_temporal<., 2> (colour box + noise box) run side by side: the former are the reference point for the latter."""
 import argparse
 import json
 import os
