@@ -8,13 +8,15 @@
 //                                                                    until no pixel is active; prints the frame's mean spp)
 //          [--adaptive-block G --adaptive-growth K]   (with --noise-threshold: G x G pixel blocks (1, 2, 4, 8) stop together; K = 2 tests at M, 2M, 4M ... only,
 //                                                       and the frame renders in calls that end on those boundaries)
-//          [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K]   (atrous, the default: fh_denoise; guided: the variance-guided filter on the position and depth layers too, and on the
+//          [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]]   (atrous, the default: fh_denoise; guided: the variance-guided filter on the position and depth layers too, and on the
 //                                         luminance moments and sample counts whenever --noise-threshold is on; temporal: that filter behind temporal accumulation --
 //                                         frame i renders with seed 1 + i and the denoiser is told the frame's camera; every other mode keeps seed 1; temporal-motion: temporal with
 //                                         per-instance motion vectors, so that the key-framed objects keep their history too; -response: either of the two with
 //                                         the history clipped to the frame's local colour box of +- G standard deviations (default 1), so that moving lights do not lag;
 //                                         -response-noise: that with the history also clamped to the pixel's own colour +- K measured standard deviations (default 6) --
-//                                         this step needs the luminance moments, so without --noise-threshold it does nothing)
+//                                         this step needs the luminance moments, so without --noise-threshold it does nothing;
+//                                         --denoise-temporal-moments, with every temporal* denoiser: the history also keeps the luminance moments, and a frame without
+//                                         --noise-threshold takes its per-pixel variance from them once a pixel's history is H frames long (default 2))
 //          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
 #include <chrono>
 #include <cmath>
@@ -50,6 +52,9 @@ int main(int argc, char** argv)
   bool gamma_given = false;
   float denoise_kappa = 6.0f;            // --denoise-kappa (with a -response-noise denoiser only)
   bool kappa_given = false;
+  bool temporal_moments = false;         // --denoise-temporal-moments (with a temporal* denoiser only)
+  float denoise_min_history = 2.0f;      // --denoise-min-history (with --denoise-temporal-moments only)
+  bool min_history_given = false;
   std::vector<int> devices;  // --devices: empty = FH_DEVICES, or device 0
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -78,12 +83,14 @@ int main(int argc, char** argv)
     else if (a == "--denoiser") denoiser_name = next();
     else if (a == "--denoise-gamma") { denoise_gamma = float(std::atof(next())); gamma_given = true; }
     else if (a == "--denoise-kappa") { denoise_kappa = float(std::atof(next())); kappa_given = true; }
+    else if (a == "--denoise-temporal-moments") temporal_moments = true;
+    else if (a == "--denoise-min-history") { denoise_min_history = float(std::atof(next())); min_history_given = true; }
     else if (a == "--devices") {
       try { devices = cwl::parse_device_list(next(), "--devices"); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--devices 0,1,...]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   if (adaptive_block != 1 && adaptive_block != 2 && adaptive_block != 4 && adaptive_block != 8) { std::fprintf(stderr, "--adaptive-block must be 1, 2, 4 or 8\n"); return 2; }
   if (adaptive_growth != 1 && adaptive_growth != 2) { std::fprintf(stderr, "--adaptive-growth must be 1 or 2\n"); return 2; }
@@ -96,6 +103,9 @@ int main(int argc, char** argv)
   if (!(denoise_kappa > 0.0f) || !std::isfinite(denoise_kappa)) { std::fprintf(stderr, "--denoise-kappa must be finite and > 0\n"); return 2; }
   if (kappa_given && !temporal_noise) { std::fprintf(stderr, "--denoise-kappa goes with --denoiser temporal-response-noise or temporal-motion-response-noise\n"); return 2; }
   if (gamma_given && !temporal_response) { std::fprintf(stderr, "--denoise-gamma goes with --denoiser temporal-response or temporal-motion-response\n"); return 2; }
+  if (!(denoise_min_history >= 1.0f) || !std::isfinite(denoise_min_history)) { std::fprintf(stderr, "--denoise-min-history must be finite and >= 1\n"); return 2; }
+  if (temporal_moments && !temporal) { std::fprintf(stderr, "--denoise-temporal-moments goes with a temporal --denoiser\n"); return 2; }
+  if (min_history_given && !temporal_moments) { std::fprintf(stderr, "--denoise-min-history goes with --denoise-temporal-moments\n"); return 2; }
   const bool guided = denoiser_name == "guided" || temporal;  // (temporal: the same guides)
   const float time_step = 1.0f / fps;
   try {
@@ -137,6 +147,7 @@ int main(int argc, char** argv)
       if (temporal_motion) denoiser.set_motion(true);
       if (temporal_response) denoiser.set_response(true, denoise_gamma);
       if (temporal_noise) denoiser.set_response_noise(true, denoise_kappa);
+      if (temporal_moments) denoiser.set_temporal_moments(true, denoise_min_history);
       if (noise_threshold >= 0.0f) denoiser.set_guides(layer_position.get_device_ptr(), layer_depth.get_device_ptr(), luminance_moments.get_device_ptr(), sample_counts.get_device_ptr());
       else denoiser.set_guides(layer_position.get_device_ptr(), layer_depth.get_device_ptr());
     }

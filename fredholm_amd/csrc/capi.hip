@@ -620,7 +620,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
   void* ptrs[] = {ctx->d_sample_issued, ctx->d_sobol, ctx->d_sobol_bytes, ctx->d_alpha_rec, ctx->d_lut_refl, ctx->d_lut_sheen, ctx->d_face_rec, ctx->d_face_cls, ctx->d_materials, ctx->d_lights, ctx->d_bvh2_nodes, ctx->d_bvh2_tris,
                   ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_sample_count, ctx->d_owned, ctx->d_trace_counters, ctx->d_texels, ctx->d_textures, ctx->d_srgb_lut, ctx->d_ibl,
                   ctx->d_bloom_weights, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
-                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hist_cv[0], ctx->d_hist_cv[1], ctx->d_hist_ph[0], ctx->d_hist_ph[1], ctx->d_hist_n[0], ctx->d_hist_n[1], ctx->d_motion, ctx->d_motion_ids, ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
+                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hist_cv[0], ctx->d_hist_cv[1], ctx->d_hist_ph[0], ctx->d_hist_ph[1], ctx->d_hist_n[0], ctx->d_hist_n[1], ctx->d_hist_mu[0], ctx->d_hist_mu[1], ctx->d_motion, ctx->d_motion_ids, ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
                   ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active[2], ctx->d_active[3], ctx->d_block_marks, ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -1381,6 +1381,38 @@ int fh_get_denoise_response_noise(fh_ctx* ctx, int* on, fh_response_noise_params
   if (!ctx || !on) return FH_E_INVALID;
   *on = ctx->denoise_response_noise;
   if (params) params->kappa = ctx->response_kappa;
+  return FH_OK;
+}
+
+// the moments of the temporal stage: broadcast like the switches above.  Turning it on or off drops the history (the stored history has, or lacks, the moment image);
+// the image itself is allocated by the next call (denoise.hip) and freed here when the switch goes off
+int fh_set_denoise_temporal_moments(fh_ctx* ctx, const fh_temporal_moments_params* params)
+{
+  if (const char* why = temporal_moments_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_temporal_moments: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_temporal_moments(m_, params));
+  if (!ctx) return FH_E_INVALID;
+  const int on = params ? 1 : 0;
+  if (on != ctx->denoise_temporal_moments) {
+    ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;  // fh_denoise_history_reset
+    ctx->hist_o2w.clear(); ctx->hist_w2o.clear();
+    if (!on && (ctx->d_hist_mu[0] || ctx->d_hist_mu[1])) {
+      if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, FH_E_HIP, "hipSetDevice failed");
+      (void)hipStreamSynchronize(ctx->stream);  // (a call queued earlier may still write them)
+      for (int k = 0; k < 2; ++k) { if (ctx->d_hist_mu[k]) (void)hipFree(ctx->d_hist_mu[k]); ctx->d_hist_mu[k] = nullptr; }
+      ctx->hist_mu_pixels = 0;
+    }
+  }
+  ctx->denoise_temporal_moments = on;
+  if (params) ctx->moments_min_history = params->min_history;
+  return FH_OK;
+}
+
+int fh_get_denoise_temporal_moments(fh_ctx* ctx, int* on, fh_temporal_moments_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->denoise_temporal_moments;
+  if (params) params->min_history = ctx->moments_min_history;
   return FH_OK;
 }
 

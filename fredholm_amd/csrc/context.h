@@ -264,6 +264,12 @@ struct fh_ctx {
   // fh_set_denoise_response_noise (k_temporal<., kClipColourNoise>): the clipped history is clamped to the pixel's measured noise as well; inert while the switch above is off
   int denoise_response_noise = 0;
   float response_kappa = 6.0f;
+  // fh_set_denoise_temporal_moments (k_temporal<., ., true>): while on, the history holds one more double-buffered image, the luminance moments (mu1, mu2), and a call
+  // without sample moments takes its variance from them once a pixel's history is moments_min_history long.  Allocated by the first call with the switch on.
+  int denoise_temporal_moments = 0;
+  float moments_min_history = 2.0f;
+  float2* d_hist_mu[2] = {nullptr, nullptr};
+  size_t hist_mu_pixels = 0;
 
   // stats
   fh_stats stats{};

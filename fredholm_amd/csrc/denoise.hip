@@ -14,10 +14,11 @@
 // DENSE neighbours, which the lattice does not hold.
 //
 // fh_denoise_temporal runs the same preparation and the same passes with one launch between them, k_temporal below: the frame's (c, v) blended with the context's
-// history of the frames before it, found again through the world position and the previous call's camera.  k_temporal<LOOK, CLIP> is one template.  LOOK is how the
+// history of the frames before it, found again through the world position and the previous call's camera.  k_temporal<LOOK, CLIP, MOM> is one template.  LOOK is how the
 // history is found: fh_denoise_temporal_motion, where an instance moved, carries the pixels of moved instances to where their surface was.  CLIP is what happens to it
 // before the blend: while fh_set_denoise_response is on it is clamped to the current frame's local colour statistics, and with fh_set_denoise_response_noise on as well
-// and moments given, also to the pixel's own measured noise.
+// and moments given, also to the pixel's own measured noise.  MOM (fh_set_denoise_temporal_moments): the history also holds the luminance moments (mu1, mu2), looked up and
+// blended like the colour, and a call without sample moments takes its variance from them where the history is long enough.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -241,7 +242,7 @@ void launch_pass(const GuidedArgs& a, bool last, dim3 grid, hipStream_t st)
 // P -- blends, and writes the new history, which is also what the first pass reads.  32 x 8 pixels per workgroup like the passes: a wave is two rows of 32, whose taps
 // after a small camera step are again two or three rows of neighbouring 16-byte elements in each of the three history images.
 //
-// One kernel template, k_temporal<LOOK, CLIP>, whose parts below are each written once; the host picks the instance (the choice is the same for every pixel).  The build
+// One kernel template, k_temporal<LOOK, CLIP, MOM>, whose parts below are each written once; the host picks the instance (the choice is the same for every pixel).  The build
 // is fp32 without contraction, so a part gives the same bits in every instance it is inlined into, and the GPU suites hold each instance to the restatement's bits.
 enum { kLookNone, kLookOwn, kLookReproject, kLookMotion };  // LOOK: there is no history; the camera stood still; it moved; fh_denoise_temporal_motion with a moved instance
 enum { kClipOff, kClipColour, kClipColourNoise };          // CLIP: fh_set_denoise_response off; on; on with fh_set_denoise_response_noise and moments
@@ -268,9 +269,17 @@ struct TemporalArgs {
   uint32_t n_instances;
   int still;               // the camera has the stored camera's bits
   float gamma, kappa;      // CLIP: fh_set_denoise_response, fh_set_denoise_response_noise
+  // MOM (fh_set_denoise_temporal_moments): at the end, so that the instances without it keep their argument offsets
+  const float2* h_mu;      // the history read: the luminance moments (mu1, mu2)
+  float2* o_mu;            // the history written
+  float min_history;       // the history length from which the temporal variance replaces the preparation's
+  int replace_v;           // the call has no sample moments: v may be replaced
 };
 // what a pixel found of its history: colour, variance, length
 struct History { float x, y, z, v, h; };
+// ... and, with MOM, the luminance moments; without it the type is empty, and the instances without moments are the code they were
+template <bool MOM> struct Moments {};
+template <> struct Moments<true> { float x = 0.0f, y = 0.0f; };
 
 __device__ __forceinline__ bool td_hit(const float4 n) { return n.x != 0.0f || n.y != 0.0f || n.z != 0.0f; }
 // the two stops of a history tap (its normal nq and position ph.xyz) seen from the pixel (np, pp); lim = plane_tol * max(Z_p, 1e-3)
@@ -283,15 +292,18 @@ __device__ __forceinline__ bool td_valid(const TemporalArgs& A, const float4 np,
 }
 
 // the still camera's look-up: the pixel's own history, if it passes the two stops; false: no history
-__device__ __forceinline__ bool td_own_tap(const TemporalArgs& A, int p, const float4 np, const float4 pp, float lim, History& H)
+template <bool MOM>
+__device__ __forceinline__ bool td_own_tap(const TemporalArgs& A, int p, const float4 np, const float4 pp, float lim, History& H, Moments<MOM>& mu)
 {
   const float4 qc = A.h_cv[p], qp = A.h_ph[p], qn = A.h_n[p];
   H = {qc.x, qc.y, qc.z, qc.w, qp.w};
+  if constexpr (MOM) { const float2 qm = A.h_mu[p]; mu.x = qm.x; mu.y = qm.y; }
   return td_valid(A, np, pp, lim, qn, qp);
 }
 
 // the moved camera's look-up: where the stored camera saw pp, the 2 x 2 taps around it that pass the two stops seen from (np, pp), renormalised; false: no history
-__device__ __forceinline__ bool td_reproject(const TemporalArgs& A, const float4 np, const float4 pp, float lim, History& H)
+template <bool MOM>
+__device__ __forceinline__ bool td_reproject(const TemporalArgs& A, const float4 np, const float4 pp, float lim, History& H, Moments<MOM>& mu)
 {
   bool have = false;
   const float qx = ((A.m[0] * pp.x + A.m[1] * pp.y) + A.m[2] * pp.z) + A.m[3];
@@ -310,22 +322,26 @@ __device__ __forceinline__ bool td_reproject(const TemporalArgs& A, const float4
         const bool inside = tx >= 0.0f && tx <= A.W - 1.0f && ty >= 0.0f && ty <= A.H - 1.0f;  // (false for NaN: the clamps below then give pixel 0)
         const int q = (int)fminf(fmaxf(tx, 0.0f), A.W - 1.0f) + A.w * (int)fminf(fmaxf(ty, 0.0f), A.H - 1.0f);
         const float4 qc = A.h_cv[q], qp = A.h_ph[q], qn = A.h_n[q];
+        Moments<MOM> qm;
+        if constexpr (MOM) { const float2 t = A.h_mu[q]; qm.x = t.x; qm.y = t.y; }
         const float wgt = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
         if (inside && td_valid(A, np, pp, lim, qn, qp)) {
           S += wgt; H.x += wgt * qc.x; H.y += wgt * qc.y; H.z += wgt * qc.z; H.v += wgt * qc.w; H.h += wgt * qp.w;
+          if constexpr (MOM) { mu.x += wgt * qm.x; mu.y += wgt * qm.y; }
         }
       }
     have = S >= 1e-3f;
     H.x = H.x / S; H.y = H.y / S; H.z = H.z / S; H.v = H.v / S; H.h = H.h / S;
+    if constexpr (MOM) { mu.x = mu.x / S; mu.y = mu.y / S; }
   }
   return have;
 }
 
-// the look-up of a pixel that hit something (H comes in as zeros).  kLookMotion (the header states it): a pixel of an instance that moved is CARRIED to where its
+// the look-up of a pixel that hit something (H and mu come in as zeros).  kLookMotion (the header states it): a pixel of an instance that moved is CARRIED to where its
 // surface was, by the instance's affine map, and is reprojected from there whatever the camera did; the other pixels take their own tap under a still camera and the
 // reprojection otherwise.  It reads 4 more bytes per pixel than kLookReproject and an 88-byte table entry that a wave shares.
-template <int LOOK>
-__device__ __forceinline__ bool td_lookup(const TemporalArgs& A, int p, const float4 np, const float4 pp, History& H)
+template <int LOOK, bool MOM>
+__device__ __forceinline__ bool td_lookup(const TemporalArgs& A, int p, const float4 np, const float4 pp, History& H, Moments<MOM>& mu)
 {
   if constexpr (LOOK == kLookNone) {
     return false;
@@ -348,7 +364,7 @@ __device__ __forceinline__ bool td_lookup(const TemporalArgs& A, int p, const fl
         nb.z = (g[6] * np.x + g[7] * np.y) + g[8] * np.z;
       }
     }
-    return own ? td_own_tap(A, p, np, pp, lim, H) : td_reproject(A, nb, pb, lim, H);
+    return own ? td_own_tap<MOM>(A, p, np, pp, lim, H, mu) : td_reproject<MOM>(A, nb, pb, lim, H, mu);
   }
 }
 
@@ -397,16 +413,29 @@ __device__ __forceinline__ void td_clip(const TemporalArgs& A, const float4* s_c
   }
 }
 
-// the blend of the frame's (c, v) with the history, if there is one, and the four stores
-__device__ __forceinline__ void td_blend_store(const TemporalArgs& A, int p, const float4 cv, const float4 np, const float4 pp, bool have, const History& H)
+// the blend of the frame's (c, v) with the history, if there is one, and the four stores.  MOM: the moments (l, l * l) of the frame's luminance are blended with the
+// history's mu (never clipped) by the same weights and stored as well; where the call has no sample moments and the history is min_history long, their variance takes
+// the place of the preparation's v
+template <bool MOM>
+__device__ __forceinline__ void td_blend_store(const TemporalArgs& A, int p, const float4 cv, const float4 np, const float4 pp, bool have, const History& H, const Moments<MOM>& mu)
 {
   float cx = cv.x, cy = cv.y, cz = cv.z, v = cv.w, hist = td_hit(np) ? 1.0f : 0.0f;
+  Moments<MOM> m;
+  if constexpr (MOM) {
+    const float l = luminance_rgb(cx, cy, cz);
+    m.x = l; m.y = l * l;
+  }
   if (have) {
     hist = fminf(H.h + 1.0f, A.max_history);
     const float a = fmaxf(1.0f / hist, A.alpha_min), b = 1.0f - a;
     cx = b * H.x + a * cx; cy = b * H.y + a * cy; cz = b * H.z + a * cz;
+    if constexpr (MOM) {
+      m.x = b * mu.x + a * m.x; m.y = b * mu.y + a * m.y;
+      if (A.replace_v && hist >= A.min_history) v = fmaxf(m.y - m.x * m.x, 0.0f);
+    }
     v = (b * b) * H.v + (a * a) * v;
   }
+  if constexpr (MOM) A.o_mu[p] = make_float2(m.x, m.y);
   A.o_cv[p] = make_float4(cx, cy, cz, v);
   A.o_ph[p] = make_float4(pp.x, pp.y, pp.z, hist);
   A.o_n[p] = np;
@@ -418,7 +447,7 @@ __device__ __forceinline__ void td_blend_store(const TemporalArgs& A, int p, con
 // element outside the frame is staged with N = 0, which is what a miss has: neither counts.  Every thread of a partial tile stages (the loop runs over the tile, not
 // over the live pixels) and only then do the threads without a pixel leave.  A row of 32 pixels reads 32 consecutive float4 of a tile row per tap: every bank once per
 // 16 lanes.  Without the clip the arrays are never referenced: no LDS, and the pixel's (c, v) and N come from global memory.
-template <int LOOK, int CLIP>
+template <int LOOK, int CLIP, bool MOM>
 __global__ void __launch_bounds__(256) k_temporal(const TemporalArgs A)
 {
   static_assert(LOOK != kLookNone || CLIP == kClipOff, "without a history there is nothing to clip");
@@ -445,20 +474,21 @@ __global__ void __launch_bounds__(256) k_temporal(const TemporalArgs A)
   if constexpr (kTile) { cv = s_cv[kc]; np = s_n[kc]; } else { cv = A.cv[p]; np = A.normal[p]; }
   const float4 pp = A.position[p];
   History H = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  Moments<MOM> mu;
   bool have = false;
   if (td_hit(np)) {
-    have = td_lookup<LOOK>(A, p, np, pp, H);
+    have = td_lookup<LOOK, MOM>(A, p, np, pp, H, mu);
     if constexpr (kTile)
       if (have) td_clip<CLIP>(A, s_cv, s_n, kc, np, cv, H);
   }
-  td_blend_store(A, p, cv, np, pp, have, H);
+  td_blend_store<MOM>(A, p, cv, np, pp, have, H, mu);
 }
 
 using TemporalLaunch = void (*)(const TemporalArgs&, dim3, hipStream_t);
-template <int LOOK, int CLIP>
+template <int LOOK, int CLIP, bool MOM = false>
 void temporal_launch(const TemporalArgs& a, dim3 grid, hipStream_t st)
 {
-  hipLaunchKernelGGL((k_temporal<LOOK, CLIP>), grid, dim3(kTW, kTH), 0, st, a);
+  hipLaunchKernelGGL((k_temporal<LOOK, CLIP, MOM>), grid, dim3(kTW, kTH), 0, st, a);
 }
 // [LOOK][CLIP]: the ten instances in use
 constexpr TemporalLaunch kTemporalLaunch[4][3] = {
@@ -466,6 +496,13 @@ constexpr TemporalLaunch kTemporalLaunch[4][3] = {
     {temporal_launch<kLookOwn, kClipOff>, temporal_launch<kLookOwn, kClipColour>, temporal_launch<kLookOwn, kClipColourNoise>},
     {temporal_launch<kLookReproject, kClipOff>, temporal_launch<kLookReproject, kClipColour>, temporal_launch<kLookReproject, kClipColourNoise>},
     {temporal_launch<kLookMotion, kClipOff>, temporal_launch<kLookMotion, kClipColour>, temporal_launch<kLookMotion, kClipColourNoise>},
+};
+// the same ten with the moments (fh_set_denoise_temporal_moments)
+constexpr TemporalLaunch kTemporalLaunchMoments[4][3] = {
+    {temporal_launch<kLookNone, kClipOff, true>, nullptr, nullptr},
+    {temporal_launch<kLookOwn, kClipOff, true>, temporal_launch<kLookOwn, kClipColour, true>, temporal_launch<kLookOwn, kClipColourNoise, true>},
+    {temporal_launch<kLookReproject, kClipOff, true>, temporal_launch<kLookReproject, kClipColour, true>, temporal_launch<kLookReproject, kClipColourNoise, true>},
+    {temporal_launch<kLookMotion, kClipOff, true>, temporal_launch<kLookMotion, kClipColour, true>, temporal_launch<kLookMotion, kClipColourNoise, true>},
 };
 
 }  // namespace
@@ -578,6 +615,13 @@ int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* 
       for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&b[k], px * sizeof(float4)));
     ctx->hist_pixels = px;
   }
+  const bool mom = ctx->denoise_temporal_moments != 0;
+  if (mom && ctx->hist_mu_pixels < ctx->hist_pixels) {  // (the moment image of fh_set_denoise_temporal_moments: as large as the rest of the history; a new one holds nothing)
+    for (int k = 0; k < 2; ++k) { if (ctx->d_hist_mu[k]) (void)hipFree(ctx->d_hist_mu[k]); ctx->d_hist_mu[k] = nullptr; }
+    ctx->hist_mu_pixels = 0; ctx->hist_frames = 0;
+    for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&ctx->d_hist_mu[k], ctx->hist_pixels * sizeof(float2)));
+    ctx->hist_mu_pixels = ctx->hist_pixels;
+  }
   if (ctx->hist_w != (uint32_t)w || ctx->hist_h != (uint32_t)h) ctx->hist_frames = 0;
   const bool with_motion = ids && ctx->hist_frames != 0;  // (without a history nothing is looked up: the plain first call)
   if (with_motion)
@@ -596,10 +640,11 @@ int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* 
   const bool still = std::memcmp(cam, &ctx->hist_camera, sizeof(fh_camera)) == 0;
   a.ids = ids; a.motion = ctx->d_motion; a.n_instances = n_instances; a.still = still ? 1 : 0;
   a.gamma = ctx->response_gamma; a.kappa = ctx->response_kappa;
+  if (mom) { a.h_mu = ctx->d_hist_mu[from]; a.o_mu = ctx->d_hist_mu[to]; a.min_history = ctx->moments_min_history; a.replace_v = in->moments ? 0 : 1; }
   const int look = ctx->hist_frames == 0 ? kLookNone : with_motion ? kLookMotion : still ? kLookOwn : kLookReproject;
   // fh_set_denoise_response clips whatever history the call looks up; fh_set_denoise_response_noise adds its step only with moments (the measured variance exists only then)
   const int clip = look == kLookNone || !ctx->denoise_response ? kClipOff : ctx->denoise_response_noise && in->moments ? kClipColourNoise : kClipColour;
-  kTemporalLaunch[look][clip](a, dim3((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), ctx->stream);
+  (mom ? kTemporalLaunchMoments : kTemporalLaunch)[look][clip](a, dim3((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), ctx->stream);
   ctx->hist_cur = to; ctx->hist_camera = *cam; ctx->hist_inv_tan = inv_tan;
   for (int k = 0; k < 12; ++k) ctx->hist_w2c[k] = w2c[k];
   ctx->hist_w = (uint32_t)w; ctx->hist_h = (uint32_t)h;

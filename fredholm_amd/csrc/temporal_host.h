@@ -76,4 +76,11 @@ inline const char* response_noise_refusal(const fh_response_noise_params* params
   return nullptr;
 }
 
+// why fh_set_denoise_temporal_moments refuses these parameters, or nullptr (NULL parameters switch it off and are never refused)
+inline const char* temporal_moments_refusal(const fh_temporal_moments_params* params)
+{
+  if (params && (!(params->min_history >= 1.0f) || !std::isfinite(params->min_history))) return "min_history must be finite and >= 1";
+  return nullptr;
+}
+
 }  // namespace fh

@@ -115,6 +115,7 @@ EXPORTS = [
     "fh_denoise_guided", "fh_denoise_temporal", "fh_denoise_history_reset", "fh_denoise_history_info",
     "fh_primary_instances", "fh_motion_from_transforms", "fh_denoise_temporal_motion", "fh_set_denoise_motion", "fh_get_denoise_motion", "fh_kat_chief_rays",
     "fh_set_denoise_response", "fh_get_denoise_response", "fh_set_denoise_response_noise", "fh_get_denoise_response_noise",
+    "fh_set_denoise_temporal_moments", "fh_get_denoise_temporal_moments",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -155,6 +156,11 @@ class ResponseNoiseParamsC(C.Structure):
     _fields_ = [("kappa", C.c_float)]
 
 
+class TemporalMomentsParamsC(C.Structure):
+    """fh_temporal_moments_params (include/fredholm_hip.h)"""
+    _fields_ = [("min_history", C.c_float)]
+
+
 # argument types of the entry points declared with them (the adaptive-sampling ABI); every entry point returns int
 SIGNATURES = {
     "fh_set_adaptive_sampling": [C.c_void_p, C.POINTER(AdaptiveParamsC)],
@@ -180,6 +186,8 @@ SIGNATURES = {
     "fh_get_denoise_response": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(ResponseParamsC)],
     "fh_set_denoise_response_noise": [C.c_void_p, C.POINTER(ResponseNoiseParamsC)],
     "fh_get_denoise_response_noise": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(ResponseNoiseParamsC)],
+    "fh_set_denoise_temporal_moments": [C.c_void_p, C.POINTER(TemporalMomentsParamsC)],
+    "fh_get_denoise_temporal_moments": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(TemporalMomentsParamsC)],
     "fh_kat_chief_rays": [C.c_void_p, C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_void_p],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],

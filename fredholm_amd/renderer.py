@@ -602,6 +602,22 @@ class Renderer:
         self._ck(N.lib().fh_get_denoise_response_noise(self._ctx, C.byref(on), C.byref(p)), "fh_get_denoise_response_noise")
         return bool(on.value), float(p.kappa)
 
+    def set_denoise_temporal_moments(self, min_history=2.0):
+        """fh_set_denoise_temporal_moments: while on, denoise_temporal and denoise_temporal_motion keep the first and second moment of the luminance in the history,
+        looked up and blended like the colour, and a call WITHOUT moments and counts takes its per-pixel variance from them once the pixel's history is min_history
+        long (before that, from the 7 x 7 spatial estimate).  A call with moments keeps its bits.  Turning the switch on or off drops the history"""
+        p = N.TemporalMomentsParamsC(float(min_history))
+        self._ck(N.lib().fh_set_denoise_temporal_moments(self._ctx, C.byref(p)), "fh_set_denoise_temporal_moments")
+
+    def clear_denoise_temporal_moments(self):
+        self._ck(N.lib().fh_set_denoise_temporal_moments(self._ctx, None), "fh_set_denoise_temporal_moments")
+
+    def get_denoise_temporal_moments(self):
+        """(on, min_history): the switch and the min_history last set (the default before any)"""
+        on, p = C.c_int(0), N.TemporalMomentsParamsC(0.0)
+        self._ck(N.lib().fh_get_denoise_temporal_moments(self._ctx, C.byref(on), C.byref(p)), "fh_get_denoise_temporal_moments")
+        return bool(on.value), float(p.min_history)
+
     def reset_denoise_history(self):
         """drop the history of denoise_temporal (fh_denoise_history_reset)"""
         self._ck(N.lib().fh_denoise_history_reset(self._ctx), "fh_denoise_history_reset")

@@ -16,6 +16,10 @@
 // set_response_noise(true, kappa) (FH_DENOISER=temporal-response-noise, temporal-motion-response-noise: set_response(true) with it) switches the noise box of that
 // clipping on (fh_set_denoise_response_noise).  It acts only in calls that are given luminance moments and sample counts (set_guides with both: they exist while
 // adaptive sampling keeps them); without them, and without set_response, it does nothing.
+// set_temporal_moments(true, min_history) switches the context's temporal moments on (fh_set_denoise_temporal_moments): the history also keeps the luminance moments,
+// and a denoise() WITHOUT moments and counts takes its per-pixel variance from them once a pixel's history is min_history long.  The environment variable
+// FH_DENOISE_TEMPORAL_MOMENTS does the same for an application that is not edited (unset or 0: off; 1: on with the default; any other number: on with that
+// min_history); it acts in Temporal mode, whichever FH_DENOISER=temporal... spelling chose it.  Turning it on or off drops the history.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -43,6 +47,11 @@ class Denoiser
     if (env && std::strcmp(env, "temporal-motion-response") == 0) { m_mode = Temporal; set_motion(true); set_response(true); }
     if (env && std::strcmp(env, "temporal-response-noise") == 0) { m_mode = Temporal; set_response(true); set_response_noise(true); }
     if (env && std::strcmp(env, "temporal-motion-response-noise") == 0) { m_mode = Temporal; set_motion(true); set_response(true); set_response_noise(true); }
+    const char* mom = std::getenv("FH_DENOISE_TEMPORAL_MOMENTS");
+    if (mom && *mom && std::strcmp(mom, "0") != 0) {
+      if (std::strcmp(mom, "1") == 0) set_temporal_moments(true);
+      else set_temporal_moments(true, float(std::atof(mom)));
+    }
   }
   enum Mode { Atrous, Guided, Temporal };
   void set_mode(Mode mode) { m_mode = mode; }
@@ -71,6 +80,11 @@ class Denoiser
   void set_response_noise(bool on, float kappa = 6.0f) { m_noise = on; m_noise_kappa = kappa; m_noise_pending = true; }
   bool response_noise() const { return m_noise; }
   float response_noise_kappa() const { return m_noise_kappa; }
+  // Temporal mode: keep the luminance moments in the history and take the variance of a call without sample moments from them (fh_set_denoise_temporal_moments);
+  // takes effect with the next denoise(), and a change of `on` drops the history
+  void set_temporal_moments(bool on, float min_history = 2.0f) { m_moments = on; m_moments_min_history = min_history; m_moments_pending = true; }
+  bool temporal_moments() const { return m_moments; }
+  float temporal_moments_min_history() const { return m_moments_min_history; }
   void reset_history()
   {
     fh_ctx* ctx = m_context ? m_context : cwl::require_context();
@@ -94,6 +108,11 @@ class Denoiser
         const fh_response_noise_params np = {m_noise_kappa};
         cwl::check(ctx, fh_set_denoise_response_noise(ctx, m_noise ? &np : nullptr), "fh_set_denoise_response_noise");
         m_noise_pending = false;
+      }
+      if (m_moments_pending) {
+        const fh_temporal_moments_params mp = {m_moments_min_history};
+        cwl::check(ctx, fh_set_denoise_temporal_moments(ctx, m_moments ? &mp : nullptr), "fh_set_denoise_temporal_moments");
+        m_moments_pending = false;
       }
       const fh_denoise_inputs in = {reinterpret_cast<const float*>(m_d_beauty), reinterpret_cast<const float*>(m_d_normal), reinterpret_cast<const float*>(m_d_albedo),
                                     reinterpret_cast<const float*>(m_d_position), m_d_depth, reinterpret_cast<const float*>(m_d_moments), m_d_counts};
@@ -134,5 +153,7 @@ class Denoiser
   float m_response_gamma = 1.0f;
   bool m_noise = false, m_noise_pending = false;
   float m_noise_kappa = 6.0f;
+  bool m_moments = false, m_moments_pending = false;
+  float m_moments_min_history = 2.0f;
 };
 }  // namespace fredholm

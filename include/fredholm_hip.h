@@ -490,6 +490,42 @@ int fh_set_denoise_response_noise(fh_ctx* ctx, const fh_response_noise_params* p
 /* *on = 0 or 1; params (may be NULL) receives the kappa last set (6 before any) */
 int fh_get_denoise_response_noise(fh_ctx* ctx, int* on, fh_response_noise_params* params);
 
+/* -- temporal moments: the variance of a call WITHOUT luminance moments, from a history of moments (opt-in, default off; with it off every call above keeps its
+ * bits, its launches and its memory).  The colour edge stop of the passes is steered by the per-pixel variance v.  Without sample moments and counts v is the 7 x 7
+ * spatial estimate, which is large exactly at the edges the filter should keep; and at 1 sample per call sample moments cannot exist (n < 2 gives v = l * l).  While
+ * this switch is on, EVERY fh_denoise_temporal and fh_denoise_temporal_motion call (also the calls fh_set_denoise_motion makes itself, and with or without sample
+ * moments) keeps the first and second moment of the luminance, (mu1, mu2), in one more double-buffered history image of two floats per pixel, integrated through the
+ * same look-up and with the same weights as the colour (SVGF's temporal variance); a call without sample moments takes its v from them once the pixel's history is
+ * min_history long, and from the spatial estimate before that.
+ *
+ * The changes to the stage; fp32 without contraction, / correctly rounded, sums in the order written; c: the preparation's colour of the current frame:
+ *   l = lum(c) = (c.r * 0.2126729 + c.g * 0.7151522) + c.b * 0.0721750, the preparation's luminance, for every pixel (a miss too).
+ *   A pixel without a history -- a miss, the first call, a look-up that failed the stops -- stores mu_acc = (l, l * l).
+ *   A pixel WITH a history finds mu_h exactly as it finds (c_h, v_h, h_h): the own tap gives the stored (mu1, mu2) with their bits; the 2 x 2 look-up sums
+ *     wgt * mu'_q.k over the same valid taps in the same order and divides by the same S, per component k; a carried pixel of the motion form is looked up from where
+ *     it is carried to.  The moments are NOT clipped: steps 1 to 5 of fh_set_denoise_response, where on, change (c_h, v_h, h_h) and leave mu_h alone.
+ *   After those steps h = min(h_h + 1, max_history), a = max(1 / h, alpha_min), b = 1 - a as above, and mu_acc.k = b * mu_h.k + a * m.k with m = (l, l * l).
+ *   Only in a call WITHOUT moments and counts: if the pixel has a history and h >= min_history, v := fmax(mu_acc.y - mu_acc.x * mu_acc.x, 0) takes the place of the
+ *     preparation's v in v_acc = (b * b) * v_h + (a * a) * v; otherwise v stays the 7 x 7 estimate.  h is the length after the clip: a history that the clip shortened
+ *     below min_history falls back on the spatial estimate.  fmax is C's: a NaN difference gives 0.
+ *   In a call WITH moments and counts v is untouched: the output has the bits it has with the switch off (the moments are still kept), and step 4b, whose condition
+ *     stays "the call has moments and counts", behaves as it does today.  This switch never enables step 4b.
+ *   The history stores mu_acc next to (c_acc, v_acc), (P_p, h), N_p.  Nothing else changes: the preparation, the 7 x 7 estimate (the fallback needs it) and the passes
+ *   are launched as they are.
+ * Not covered: after a moved emitter a sharper variance blurs the lagging history less, and the call is worse than with the spatial estimate until the history has
+ * caught up (DESIGN.md 4a gives the figures); the noise box is not fed from these moments (measured: it ruins the steady state or never binds). */
+typedef struct fh_temporal_moments_params {
+  float min_history; /* the history length from which the temporal variance replaces the spatial estimate, finite and >= 1; default 2 */
+} fh_temporal_moments_params;
+/* params == NULL: off.  Lives on the context and is broadcast on a group like fh_set_denoise_response; the work runs on the lead.  FH_E_INVALID, decided from the
+ * arguments alone before the context is touched, for a min_history that is not finite or < 1 (any finite value >= 1 is accepted); the switch, the history and the next
+ * output then stay as they were.  A successful call that turns the switch from off to on or from on to off drops the history exactly as fh_denoise_history_reset does
+ * (the next call is fh_denoise_guided's bits); one that only changes min_history keeps it.  The moment images are allocated by the first call with the switch on,
+ * grow and are freed with the rest of the history, and are freed when the switch goes off. */
+int fh_set_denoise_temporal_moments(fh_ctx* ctx, const fh_temporal_moments_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the min_history last set (the default before any) */
+int fh_get_denoise_temporal_moments(fh_ctx* ctx, int* on, fh_temporal_moments_params* params);
+
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */
 int fh_gl_register_buffer(fh_ctx* ctx, unsigned int gl_buffer, void** resource, void** device_ptr, uint64_t* bytes);

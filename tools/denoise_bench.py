@@ -25,7 +25,12 @@ reprojection, motion; CLIP 0, 1: plain, colour box -- and the k_guided_pass inst
 
 --response --noise (-> profiles/denoise_noise_box_bench.json): the --response leg (every call has moments) with a third round, fh_set_denoise_response_noise on (--kappa) as well:
 plain, clipped, clipped with the noise box, in one process.  In a `rocprofv3 --kernel-trace --stats` run of this leg the three k_temporal<., 1> and the three
-k_temporal<., 2> (colour box + noise box) run side by side: the former are the reference point for the latter."""
+k_temporal<., 2> (colour box + noise box) run side by side: the former are the reference point for the latter.
+
+--moments (-> profiles/denoise_temporal_moments_bench.json): the calls of --response WITHOUT sample moments (the 7 x 7 estimate runs in all of them) with
+fh_set_denoise_temporal_moments off and then on (--min-history), each with the clip off and on, in one process.  In a `rocprofv3 --kernel-trace --stats` run of this leg the six
+instances k_temporal<LOOK, CLIP, true> run beside the six k_temporal<LOOK, CLIP, false> they are measured against (LOOK 1, 2, 3; CLIP 0, 1); the record also holds the bytes
+per pixel both move, whose ratio is what the moments may cost."""
 import argparse
 import json
 import os
@@ -228,6 +233,72 @@ def response(a, bench, F, DeviceBuffer, r, w):
             f.write(line + "\n")
 
 
+def temporal_moments(a, bench, F, DeviceBuffer, r, w):
+    """the --response leg's calls WITHOUT sample moments (the calls fh_set_denoise_temporal_moments is for), in four rounds: the moments switch off and on, each with the
+    clip off and on.  Turning the switch drops the history; the warm-up calls of every median build it again"""
+    W, H = w["width"], w["height"]
+    n_inst, target, step, tables, cams = moving_instance(a, F, w)
+    frames = []
+    for k, cam in enumerate(cams):
+        L = F.RenderLayer(r, W, H)
+        r.init_render_states()
+        r.seed = 1 + k
+        r.render(cam, w["bg"], L, a.spp, w["depth"])
+        r.wait_for_completion()
+        frames.append((cam, L.ptrs))
+    out, ids = DeviceBuffer(r, 16 * W * H), DeviceBuffer(r, 4 * W * H)
+    r.primary_instances(cams[0], W, H, ids.ptr)
+    r.wait_for_completion()
+    turn = [0]
+
+    def call_temporal(alternate):
+        cam, p = frames[turn[0] & 1 if alternate else 0]
+        turn[0] += 1
+        r.denoise_temporal(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], cam)
+
+    def call_motion():
+        cam, p = frames[0]
+        turn[0] += 1
+        r.denoise_temporal_motion(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"], cam, ids.ptr, tables[turn[0] & 1])
+
+    def call_guided():
+        cam, p = frames[0]
+        r.denoise_guided(W, H, p["beauty"], p["normal"], p["albedo"], out.ptr, p["position"], p["depth"])
+    rec = {"workload": w["name"], "width": W, "height": H, "spp": a.spp, "calls": a.calls, "camera_step": step, "gamma": a.gamma, "min_history": a.min_history, "sample_moments": False,
+           "source_fingerprint": bench.source_fingerprint(), "fh_denoise_guided_ms": median_ms(r, call_guided, a.calls)}
+    for mom in (False, True):
+        if mom:
+            r.set_denoise_temporal_moments(a.min_history)
+        else:
+            r.clear_denoise_temporal_moments()
+        for gamma in (None, a.gamma):
+            if gamma is None:
+                r.clear_denoise_response()
+            else:
+                r.set_denoise_response(gamma)
+            name = ("moments_" if mom else "") + ("response_" if gamma is not None else "")
+            rec[f"fh_denoise_temporal_{name}moving_ms"] = median_ms(r, lambda: call_temporal(True), a.calls)
+            rec[f"fh_denoise_temporal_{name}still_ms"] = median_ms(r, lambda: call_temporal(False), a.calls)
+            rec[f"fh_denoise_temporal_motion_{name}ms"] = median_ms(r, call_motion, a.calls)
+    r.clear_denoise_response()
+    r.clear_denoise_temporal_moments()
+    rec["fh_denoise_guided_again_ms"] = median_ms(r, call_guided, a.calls)
+    for clip in ("", "response_"):
+        for leg in ("moving", "still"):
+            rec[f"moments_{clip}{leg}_ms_by_difference"] = rec[f"fh_denoise_temporal_moments_{clip}{leg}_ms"] - rec[f"fh_denoise_temporal_{clip}{leg}_ms"]
+        rec[f"moments_{clip}motion_ms_by_difference"] = rec[f"fh_denoise_temporal_motion_moments_{clip}ms"] - rec[f"fh_denoise_temporal_motion_{clip}ms"]
+    # bytes a pixel moves in the stage, as DESIGN.md 4a counts them: (c, v), N, P, Z read, every history element fetched once (48), three images and the plane written (52): 152,
+    # and 4 more for the id with motion.  The moments: 8 per tap fetched (one tap still, four otherwise) and 8 written
+    base = {"still": 152, "moving": 152, "motion": 156}
+    rec["bytes_per_pixel"] = {k: {"plain": v, "moments": v + 8 * (1 if k == "still" else 4) + 8} for k, v in base.items()}
+    r.close()
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def merge_resource_usage(log_path, json_path):
     """what hipcc -Rpass-analysis=kernel-resource-usage printed for the temporal kernels and the passes, into the record of json_path"""
     rec = json.loads(open(json_path).read())
@@ -280,6 +351,8 @@ def main():
     ap.add_argument("--gamma", type=float, default=1.0, help="--response: the gamma of fh_set_denoise_response")
     ap.add_argument("--noise", action="store_true", help="--response: a third round with fh_set_denoise_response_noise on")
     ap.add_argument("--kappa", type=float, default=6.0, help="--response --noise: the kappa of fh_set_denoise_response_noise")
+    ap.add_argument("--moments", action="store_true", help="the --response leg without sample moments, with fh_set_denoise_temporal_moments off and on")
+    ap.add_argument("--min-history", type=float, default=2.0, help="--moments: the min_history of fh_set_denoise_temporal_moments")
     ap.add_argument("--step", type=float, default=0.002)
     ap.add_argument("--resource-usage", default="", help="a log of hipcc -Rpass-analysis=kernel-resource-usage on denoise.hip: add its figures to the record in --out and exit (no GPU)")
     ap.add_argument("--merge-kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of the --motion leg: add its rows to the record in --out and exit (no GPU)")
@@ -305,6 +378,8 @@ def main():
         return temporal(a, bench, F, DeviceBuffer, r, w)
     if a.motion:
         return motion(a, bench, F, DeviceBuffer, r, w)
+    if a.moments:
+        return temporal_moments(a, bench, F, DeviceBuffer, r, w)
     if a.response:
         return response(a, bench, F, DeviceBuffer, r, w)
     L = F.RenderLayer(r, W, H)

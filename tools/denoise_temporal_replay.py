@@ -16,7 +16,12 @@ hit, by brute force in float64.
 --response replays four sequences -- (L) the light's emission x 0.25 after 8 frames, (S) the light quad moved, (M) the moving camera, (B) the moving block -- through the
 float64 restatement of fh_set_denoise_response for several gamma and chooses the default by a stated rule.  --noise-box replays the same four with gamma = 1 fixed
 through the restatement of fh_set_denoise_response_noise (tests/test_denoise_noise_box_host.py) for kappa in KAPPAS, chooses the default kappa by the same rule, and also
-records what the step would do WITHOUT moments (on the 7 x 7 spatial variance), which is why the library leaves that path alone."""
+records what the step would do WITHOUT moments (on the 7 x 7 spatial variance), which is why the library leaves that path alone.
+
+--temporal-moments (-> profiles/denoise_temporal_moments_replay.json) replays calls WITHOUT sample moments through the float64 restatement of
+fh_set_denoise_temporal_moments (tests/test_denoise_temporal_moments_host.py): the QUALITY sequence at 16, 4 and 1 spp, a still camera at 1 spp, and (L), (S), (M) of
+--response (shared with its --cache), for min_history in MIN_HISTORIES, clip off and gamma = 1, beside the spatial-estimate and the sample-moment calls, and chooses the
+default min_history by a stated rule."""
 import argparse
 import importlib.util
 import json
@@ -379,14 +384,131 @@ def response_replay(out, cache, noise_box=False):
             f.write(line + "\n")
 
 
+MIN_HISTORIES = (2.0, 3.0, 4.0, 6.0)
+STEADY = ("moving_16spp", "moving_4spp", "moving_1spp", "still_1spp")
+
+
+def moments_replay(out, cache):
+    """what fh_set_denoise_temporal_moments buys in calls WITHOUT sample moments: the QUALITY sequence at 16, 4 and 1 spp per frame, a still camera at 1 spp, and (L), (S),
+    (M) of --response (read from its --cache where the file holds them, rendered and added to it otherwise), through the float64 restatement of
+    tests/test_denoise_temporal_moments_host.py for min_history in MIN_HISTORIES, clip off and gamma = 1, beside the call with the 7 x 7 spatial estimate (the switch off)
+    and the call WITH sample moments; and the default min_history by the stated rule"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    H = _load("test_denoise_temporal_moments_host", "test_denoise_temporal_moments_host.py")
+    R, T = H.R, H.T
+    from fredholm_amd import scenes
+    from oracle import pyoracle as O
+    import fredholm_amd as F
+
+    q = R.RESPONSE_QUALITY
+    w, h, depth, n_before, n_after, nm = q["w"], q["h"], q["depth"], q["frames_before"], q["frames_after"], T.QUALITY["frames"]
+    assert (T.QUALITY["w"], T.QUALITY["h"], T.QUALITY["spp"], T.QUALITY["depth"]) == (w, h, q["spp"], depth) and q["spp"] == 16
+    threads = O.hardware_threads()
+    still = F.Camera(**scenes.CORNELL_CAMERA)
+    d = dict(np.load(cache)) if cache and os.path.exists(cache) else {}
+    n_cached = len(d)
+
+    def frames_at(ref, cam, seed, names):
+        """one frame rendered sample by sample; names: {spp: name}: the layers after 1, 4 or 16 samples are a frame of that many samples per pixel with the same seed"""
+        if all(f"{n}/beauty" in d for n in names.values()):
+            return
+        lo = ref.new_layers(w, h)
+        s1, s2, prev = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, 3))
+        for s in range(1, max(names) + 1):
+            ref.render(cam.params(), w, h, lo, 1, depth, seed=seed, n_threads=threads)
+            mean = lo["beauty"][..., :3].astype(np.float64)
+            x = s * mean - (s - 1) * prev
+            prev = mean
+            y = x[..., 0] * float(T.LUM[0]) + x[..., 1] * float(T.LUM[1]) + x[..., 2] * float(T.LUM[2])
+            s1 += y
+            s2 += y * y
+            if s in names:
+                for k in ("beauty", "normal", "albedo", "position", "depth"):
+                    d[f"{names[s]}/{k}"] = lo[k].copy()
+                d[f"{names[s]}/moments"] = np.stack([s1 / s, s2 / s], axis=2).astype(np.float32)
+                d[f"{names[s]}/counts"] = np.full((h, w), s, np.uint32)
+
+    def truth(ref, cam, name):
+        if name not in d:
+            lo = ref.new_layers(w, h)
+            for _ in range(q["truth_spp"]):
+                ref.render(cam.params(), w, h, lo, 1, depth, seed=1000, n_threads=threads)
+            d[name] = lo["beauty"].copy()
+
+    base = O.Scene(scenes.cornell_box())
+    for k in range(n_before):
+        frames_at(base, still, 1 + k, {16: f"A{k}", 1: f"A1_{k}"})
+    truth(base, still, "truth/A")
+    for tag in ("L", "S"):
+        ref = O.Scene(R.changed_scene(tag))
+        for k in range(n_before, n_before + n_after):
+            frames_at(ref, still, 1 + k, {16: f"{tag}{k}"})
+        truth(ref, still, f"truth/{tag}")
+    for k in range(nm):
+        frames_at(base, T.quality_camera(k), 1 + k, {16: f"M{k}", 4: f"M4_{k}", 1: f"M1_{k}"})
+    truth(base, T.quality_camera(nm - 1), "truth/M")
+    print("rendered", flush=True)
+    if cache and len(d) != n_cached:
+        np.savez_compressed(cache, **d)
+    layers_of = lambda name: {k.split("/")[1]: v for k, v in d.items() if k.startswith(name + "/")}
+
+    def run(frames, first_scored, truth_of, gamma, min_history, use_moments):
+        """relMSE of the frames from `first_scored` on (1-based): gamma None is the clip off; min_history None the switch off"""
+        st = H.MomentsRestatement(np.float64, np.exp)
+        st.gamma, st.min_history = gamma, min_history
+        res = []
+        for k, (cam, layers) in enumerate(frames):
+            o = st.call_r(layers, cam.params(), use_moments=use_moments)
+            if k + 1 >= first_scored:
+                res.append(T._relmse(o, truth_of(k + 1)))
+        return res
+
+    def rows(frames, first_scored, truth_of, gamma):
+        r = {"spatial": run(frames, first_scored, truth_of, gamma, None, False), "sample moments": run(frames, first_scored, truth_of, gamma, None, True)}
+        r.update({f"min_history={m:g}": run(frames, first_scored, truth_of, gamma, m, False) for m in MIN_HISTORIES})
+        return r
+
+    sequences = {"moving_16spp": [(T.quality_camera(k), layers_of(f"M{k}")) for k in range(nm)], "moving_4spp": [(T.quality_camera(k), layers_of(f"M4_{k}")) for k in range(nm)],
+                 "moving_1spp": [(T.quality_camera(k), layers_of(f"M1_{k}")) for k in range(nm)], "still_1spp": [(still, layers_of(f"A1_{k}")) for k in range(n_before)],
+                 "still_16spp": [(still, layers_of(f"A{k}")) for k in range(n_before)]}
+    rec = {"replay": True, "temporal_moments": True, "quality": q, "defaults": T.TDEF, "min_histories": [f"{m:g}" for m in MIN_HISTORIES], "steady": {}, "steady_clipped": {}, "change": {}}
+    for name, frames in sequences.items():
+        truth_of = (lambda f: d["truth/M"]) if name.startswith("moving") else (lambda f: d["truth/A"])
+        rec["steady"][name] = {k: v[0] for k, v in rows(frames, len(frames), truth_of, None).items()}
+        rec["steady_clipped"][name] = {k: v[0] for k, v in rows(frames, len(frames), truth_of, 1.0).items()}
+        print(name, "clip off", json.dumps(rec["steady"][name]), "gamma 1", json.dumps(rec["steady_clipped"][name]), flush=True)
+    for tag in ("L", "S"):  # the change of lighting after 8 frames: the sum of relMSE over the 4 frames after it (and each of them)
+        frames = [(still, layers_of(f"A{k}")) for k in range(n_before)] + [(still, layers_of(f"{tag}{k}")) for k in range(n_before, n_before + n_after)]
+        rec["change"][tag] = {}
+        for gname, gamma in (("clip off", None), ("gamma=1", 1.0)):
+            r = rows(frames, n_before + 1, lambda f, tag=tag: d[f"truth/{tag}"], gamma)
+            rec["change"][tag][gname] = {k: dict(frames=v, sum=sum(v)) for k, v in r.items()}
+        print(tag, json.dumps(rec["change"][tag]), flush=True)
+    # the default: the smallest sum over the four clip-off steady sequences of relMSE / the spatial-estimate call's relMSE; ties go to the smaller value
+    sums = {f"{m:g}": sum(rec["steady"][n][f"min_history={m:g}"] / rec["steady"][n]["spatial"] for n in STEADY) for m in MIN_HISTORIES}
+    rec["rule_sums"] = sums
+    rec["default_min_history"] = min(MIN_HISTORIES, key=lambda m: (sums[f"{m:g}"], m))
+    key = f"min_history={rec['default_min_history']:g}"
+    rec["R"] = {n: rec["steady"][n][key] / rec["steady"][n]["spatial"] for n in sequences}  # what the device's quality test takes its margin from
+    print("rule sums:", json.dumps(sums), "default min_history:", rec["default_min_history"], "R:", json.dumps(rec["R"]))
+    line = json.dumps(rec)
+    print(line)
+    if out:
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--motion", action="store_true", help="replay the moving-block sequence of tests/test_gpu_denoise_motion.py instead")
     ap.add_argument("--response", action="store_true", help="replay the lighting-change and steady-state sequences of tests/test_gpu_denoise_response.py through the clipped stage")
     ap.add_argument("--noise-box", action="store_true", help="replay the same four sequences at gamma = 1 through the noise box of fh_set_denoise_response_noise, for kappa in KAPPAS")
-    ap.add_argument("--cache", default="", help="--response, --noise-box: an .npz the rendered frames are kept in (read when it exists): the rendering is most of the run")
+    ap.add_argument("--cache", default="", help="--response, --noise-box, --temporal-moments: an .npz the rendered frames are kept in (read when it exists): the rendering is most of the run")
+    ap.add_argument("--temporal-moments", action="store_true", help="replay steady and lighting-change sequences WITHOUT sample moments through fh_set_denoise_temporal_moments, for min_history in MIN_HISTORIES")
     a = ap.parse_args()
+    if a.temporal_moments:
+        return moments_replay(a.out or os.path.join(ROOT, "profiles", "denoise_temporal_moments_replay.json"), a.cache)
     if a.motion:
         return motion_replay(a.out)
     if a.response or a.noise_box:
