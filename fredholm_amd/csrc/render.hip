@@ -37,6 +37,7 @@
 #include "fh_bsdf.h"
 #include "fh_tonemap.h"
 #include "fh_trace.h"
+#include "render_plan_host.h"
 
 namespace fh {
 
@@ -60,7 +61,7 @@ constexpr uint32_t kMatLds = 32;  // material records staged in LDS by the shade
 #define FH_STREAM_BLOCKS_CLOSEST FH_STREAM_BLOCKS  // the same for the closest-hit kernel, which needs fewer registers than the secondary-ray kernel
 #endif
 #ifndef FH_STREAM_BLOCKS_FILLER
-#define FH_STREAM_BLOCKS_FILLER 6  // workgroups per CU the streaming kernels are LAUNCHED with while a filler launch of k_sky_pixels is resident (render_submit)
+#define FH_STREAM_BLOCKS_FILLER 6  // workgroups per CU the streaming kernels are LAUNCHED with while a filler launch of k_sky_pixels is resident (stream_plan)
 #endif
 #ifndef FH_SHADE_BLOCKS
 #define FH_SHADE_BLOCKS 2  // resident workgroups per CU the specialised shade kernels are compiled for (register budget = 512 / that per lane): they take 159-182 registers
@@ -371,7 +372,7 @@ struct SkyAdaptive {
   unsigned long long* taken;
 };
 // Register budget.  The kernel is compiled for kSkyWaves waves per SIMD, i.e. at most 512 / 6 -> 80 registers per lane, so that one of its waves fits beside six waves of
-// the streaming traversal kernels (6 x 72 + 80 = 512): it runs in the issue slots they leave idle (render_submit: filler and drain).  Three things keep it there: the
+// the streaming traversal kernels (6 x 72 + 80 = 512): it runs in the issue slots they leave idle (SkyLaunches: filler and drain).  Three things keep it there: the
 // Hosek channels are evaluated one after the other (hosek_radiance_form<true>); the sample loop carries the beauty mean and the moments only; and the five AOV means, which
 // for a sky sample are n times `coef * (fn * a + 0)` -- no input of the sample enters -- are brought up to date AFTER the loop, when the camera and sky state is dead,
 // value for value with the operations the loop applied.  A pixel whose AOV values all hold the bit pattern +0 skips even that: coef * (fn * 0 + 0) is +0 exactly
@@ -1858,15 +1859,44 @@ void launch_shade(hipStream_t st, uint32_t grid, const SceneDev& sc, const Frame
   else hipLaunchKernelGGL(k_shade<LOBES>, dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth);
 }
 
+// The lobe ladder: of the variants a kernel is compiled in, most specific first, the first that contains every lobe of `lobes`; the last one is taken when none does
+// (L_ALL).  f gets the variant's mask as a std::integral_constant.  (L_METAL | L_SPEC | L_DIFF: glTF metallic-roughness materials; with L_COAT: KHR_materials_clearcoat.)
+template <uint32_t... V>
+struct LobeSet {};
+using ShadeLobes = LobeSet<L_DIFF, L_METAL, L_SPEC | L_DIFF, L_METAL | L_SPEC | L_DIFF, L_COAT | L_METAL | L_SPEC | L_DIFF, L_ALL>;  // k_shade
+using TailLobes = LobeSet<L_DIFF, L_METAL | L_SPEC | L_DIFF, L_COAT | L_METAL | L_SPEC | L_DIFF, L_ALL>;                            // k_tail
+template <typename F, uint32_t V, uint32_t... Rest>
+void with_compiled_lobes(uint32_t lobes, LobeSet<V, Rest...>, F&& f)
+{
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<uint32_t, V>{});
+  else if ((lobes & ~V) == 0) f(std::integral_constant<uint32_t, V>{});
+  else with_compiled_lobes(lobes, LobeSet<Rest...>{}, f);
+}
+
 void dispatch_shade(hipStream_t st, uint32_t grid, uint32_t lobes, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three)
 {
-  // compiled variants, most specific first; a variant is usable when it contains every lobe the class needs
-  if ((lobes & ~(uint32_t)L_DIFF) == 0) return launch_shade<L_DIFF>(st, grid, sc, fr, pool, cls, depth, three);
-  if ((lobes & ~(uint32_t)L_METAL) == 0) return launch_shade<L_METAL>(st, grid, sc, fr, pool, cls, depth, three);
-  if ((lobes & ~(uint32_t)(L_SPEC | L_DIFF)) == 0) return launch_shade<L_SPEC | L_DIFF>(st, grid, sc, fr, pool, cls, depth, three);
-  if ((lobes & ~(uint32_t)(L_METAL | L_SPEC | L_DIFF)) == 0) return launch_shade<L_METAL | L_SPEC | L_DIFF>(st, grid, sc, fr, pool, cls, depth, three);  // glTF metallic-roughness materials
-  if ((lobes & ~(uint32_t)(L_COAT | L_METAL | L_SPEC | L_DIFF)) == 0) return launch_shade<L_COAT | L_METAL | L_SPEC | L_DIFF>(st, grid, sc, fr, pool, cls, depth, three);  // ... with KHR_materials_clearcoat
-  return launch_shade<L_ALL>(st, grid, sc, fr, pool, cls, depth, three);
+  with_compiled_lobes(lobes, ShadeLobes{}, [&](auto V) { launch_shade<decltype(V)::value>(st, grid, sc, fr, pool, cls, depth, three); });
+}
+
+// The streaming trace kernels a scene is traced by, each ladder stated once: a launch takes the typed kernel, the runtime queries (occupancy, fh_kernel_info) its address
+template <typename F>
+void with_closest_stream(bool count, bool alpha, F&& f)
+{
+  with_bool(count, [&](auto C) { with_bool(alpha, [&](auto A) { f(k_trace_closest_stream<decltype(C)::value, decltype(A)::value>); }); });
+}
+template <typename F>
+void with_secondary_stream(bool count, bool lights, bool alpha, F&& f)
+{
+  with_bool(count, [&](auto C) { with_bool(lights, [&](auto Li) { with_bool(alpha, [&](auto A) {
+    f(k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>);
+  }); }); });
+}
+const void* stream_kernel(bool secondary, bool count, bool lights, bool alpha)
+{
+  const void* fn = nullptr;
+  if (!secondary) with_closest_stream(count, alpha, [&](auto kernel) { fn = (const void*)kernel; });
+  else with_secondary_stream(count, lights, alpha, [&](auto kernel) { fn = (const void*)kernel; });
+  return fn;
 }
 
 // registers / LDS / scratch / resident workgroups per CU of the shade kernel a class of `lobes` is shaded by (fh_kernel_info, which >= 2): the same choice as dispatch_shade
@@ -1881,13 +1911,9 @@ hipError_t shade_attributes_of(bool three, hipFuncAttributes& at, int& blocks)
 }
 hipError_t shade_attributes(uint32_t lobes, bool three, hipFuncAttributes& at, int& blocks, uint32_t& compiled_lobes)
 {
-  if ((lobes & ~(uint32_t)L_DIFF) == 0) { compiled_lobes = L_DIFF; return shade_attributes_of<L_DIFF>(three, at, blocks); }
-  if ((lobes & ~(uint32_t)L_METAL) == 0) { compiled_lobes = L_METAL; return shade_attributes_of<L_METAL>(three, at, blocks); }
-  if ((lobes & ~(uint32_t)(L_SPEC | L_DIFF)) == 0) { compiled_lobes = L_SPEC | L_DIFF; return shade_attributes_of<L_SPEC | L_DIFF>(three, at, blocks); }
-  if ((lobes & ~(uint32_t)(L_METAL | L_SPEC | L_DIFF)) == 0) { compiled_lobes = L_METAL | L_SPEC | L_DIFF; return shade_attributes_of<L_METAL | L_SPEC | L_DIFF>(three, at, blocks); }
-  if ((lobes & ~(uint32_t)(L_COAT | L_METAL | L_SPEC | L_DIFF)) == 0) { compiled_lobes = L_COAT | L_METAL | L_SPEC | L_DIFF; return shade_attributes_of<L_COAT | L_METAL | L_SPEC | L_DIFF>(three, at, blocks); }
-  compiled_lobes = L_ALL;
-  return shade_attributes_of<L_ALL>(three, at, blocks);
+  hipError_t e = hipSuccess;
+  with_compiled_lobes(lobes, ShadeLobes{}, [&](auto V) { compiled_lobes = decltype(V)::value; e = shade_attributes_of<decltype(V)::value>(three, at, blocks); });
+  return e;
 }
 
 hipEvent_t take_event(fh_ctx* ctx)
@@ -1938,7 +1964,7 @@ SceneDev scene_dev(const fh_ctx* ctx)
   s.bvh8.depth = stack_entries_for(ctx->bvh8_depth);
   s.use_bvh8 = ctx->use_bvh8 ? 1u : 0u;
   // bottom-up start (fh_trace.h): rays that leave a surface begin at the wide node that holds the face.  Only the streaming kernels climb; they trace trees of 4096 nodes and more
-  // (what the scene CAN do; render_submit switches it per pass: forced by FH_BOTTOM_UP, else by what the first passes of the scene measure)
+  // (what the scene CAN do; submit_pass switches it per pass, start_at_faces: forced by FH_BOTTOM_UP, else by what the first passes of the scene measure)
   const bool bottom_up = ctx->tun.bottom_up != 0 && ctx->use_bvh8 && ctx->d_bvh8_parent && ctx->d_face_node && ctx->tun.coop && ctx->tun.stream && (ctx->tun.stream_forced || ctx->bvh8_n_nodes >= 4096u) &&
                          ctx->bvh8_n_tris < kCoopMaxTris && !((ctx->has_alpha || ctx->tun.force_alpha));
   s.bvh8.parent = bottom_up ? ctx->d_bvh8_parent : nullptr;
@@ -1964,11 +1990,7 @@ int kernel_info(fh_ctx* ctx, int which, uint32_t out[6])
   }
   const bool alpha = ctx->has_alpha || ctx->tun.force_alpha;
   hipFuncAttributes at{};
-  hipError_t e = hipSuccess;
-  with_bool(alpha, [&](auto A) {
-    if (which == 0) e = hipFuncGetAttributes(&at, (const void*)k_trace_closest_stream<false, decltype(A)::value>);
-    else with_bool(ctx->n_lights > 0, [&](auto Li) { e = hipFuncGetAttributes(&at, (const void*)k_trace_secondary_stream<false, decltype(Li)::value, decltype(A)::value>); });
-  });
+  const hipError_t e = hipFuncGetAttributes(&at, stream_kernel(which != 0, false, ctx->n_lights > 0, alpha));
   if (e != hipSuccess) return fail(ctx, FH_E_HIP, std::string("hipFuncGetAttributes: ") + hipGetErrorString(e));
   out[0] = (uint32_t)at.numRegs;
   out[1] = (uint32_t)at.sharedSizeBytes;
@@ -2268,39 +2290,33 @@ int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const 
   return FH_OK;
 }
 
-int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed)
-{
-  if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_render: scene not uploaded or BVH not built");
-  if (ctx->width == 0 || ctx->height == 0 || !ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_render: resolution not set");
-  if (max_depth > 64) return fail(ctx, FH_E_INVALID, "fh_render: max_depth > 64 is not supported");
-  if (ctx->n_owned == 0 || n_samples == 0) return FH_OK;
-  const bool adaptive = ctx->adaptive;
-  const bool guard_blocks = adaptive && ctx->adapt_block > 1u;  // (the sky pixels then follow their blocks: one k_sky_pixels launch per round, on the round's selection)
-  if (adaptive && (ctx->flags & FH_FLAG_REFERENCE_FIRSTHIT) != 0 && n_samples > 1)
-    return fail(ctx, FH_E_INVALID, "fh_render: FH_FLAG_REFERENCE_FIRSTHIT with n_samples > 1 does not combine with adaptive sampling (its first-hit state is per launch)");
-  ctx->accumulated = true;
-  // The default pool size (32 Mi paths per pool) is a wish: whenever a pool has to be allocated -- the first frame, after fh_scene_upload changed what a path record
-  // holds, after a release -- all pools together are kept within A QUARTER of what the device has free at that moment, counting what the pools already hold as free.
-  // (A pool is allocated for the paths a pass really starts -- the pixels that can see the scene x the samples of the pass, pool_ensure -- so the cap is an upper bound.)
-  if (!ctx->pool_target_by_caller) {
-    bool allocating = false;
-    unsigned long long held = 0;
-    for (int k = 0; k < (((ctx->flags & FH_FLAG_SERIAL_PASSES) != 0) ? 1 : ctx->n_slots); ++k) {
-      const fh_ctx::PoolShape& have = ctx->pool_shape[k];
-      if (ctx->pool[k].capacity == 0 || (ctx->has_dir && !have.dir) || (ctx->n_lights > 0 && !have.lights) || have.classes < (ctx->n_classes < 1u ? 1u : ctx->n_classes)) allocating = true;
-      held += (unsigned long long)ctx->pool[k].capacity * pool_bytes_per_path(ctx);
-    }
-    if (allocating) {
-      size_t free_b = 0, total_b = 0;
-      ctx->pool_target = ctx->pool_target_default;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const unsigned long long cap = ((unsigned long long)free_b + held) / (4ull * ctx->pool_share) / ((unsigned long long)ctx->n_slots * pool_bytes_per_path(ctx));  // (pool_share: the members of a group on this device)
-        if (cap < ctx->pool_target) ctx->pool_target = cap > ctx->n_owned ? (uint32_t)cap : ctx->n_owned;
-      }
-      // (pools that exist already keep their size unless they have to be re-made: pool_ensure only grows)
-    }
-  }
+// ---- fh_render's submit path: render_submit (below) is a driver over the steps of this namespace; what they decide from plain values is in render_plan_host.h
+namespace {
 
+// The default pool size (32 Mi paths per pool) is a wish: whenever a pool has to be allocated -- the first frame, after fh_scene_upload changed what a path record
+// holds, after a release -- all pools together are kept within A QUARTER of what the device has free at that moment, counting what the pools already hold as free.
+// (A pool is allocated for the paths a pass really starts -- the pixels that can see the scene x the samples of the pass, pool_ensure -- so the cap is an upper bound.)
+void cap_pool_target(fh_ctx* ctx)
+{
+  if (ctx->pool_target_by_caller) return;
+  bool allocating = false;
+  unsigned long long held = 0;
+  for (int k = 0; k < (((ctx->flags & FH_FLAG_SERIAL_PASSES) != 0) ? 1 : ctx->n_slots); ++k) {
+    const fh_ctx::PoolShape& have = ctx->pool_shape[k];
+    if (ctx->pool[k].capacity == 0 || (ctx->has_dir && !have.dir) || (ctx->n_lights > 0 && !have.lights) || have.classes < (ctx->n_classes < 1u ? 1u : ctx->n_classes)) allocating = true;
+    held += (unsigned long long)ctx->pool[k].capacity * pool_bytes_per_path(ctx);
+  }
+  if (!allocating) return;
+  size_t free_b = 0, total_b = 0;
+  ctx->pool_target = ctx->pool_target_default;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+    ctx->pool_target = pool_target_cap(free_b, held, ctx->pool_share, ctx->n_slots, pool_bytes_per_path(ctx), ctx->pool_target_default, ctx->n_owned);
+  // (pools that exist already keep their size unless they have to be re-made: pool_ensure only grows)
+}
+
+// what the kernels of a call read about the frame: camera, environment, scene bounds, tables
+FrameDev frame_dev(const fh_ctx* ctx, const fh_camera* cam, const float* bg, uint32_t seed, uint32_t max_depth)
+{
   FrameDev fr{};
   fr.width = ctx->width; fr.height = ctx->height;
   fr.seed_hash = xxhash32(seed);
@@ -2315,18 +2331,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   for (int r = 0; r < 3; ++r) fr.cam_xf.r[r] = make_float4(cam->transform[4 * r], cam->transform[4 * r + 1], cam->transform[4 * r + 2], cam->transform[4 * r + 3]);
   fr.cam_inv_tan = 1.0f / tanf(0.5f * cam->fov);
   fr.cam_F = cam->F; fr.cam_focus = cam->focus;
-  {  // camera.cu:33-36, in fp32 like the device code these lines used to be in (volatile: no contraction, no double-precision intermediates)
-    volatile float f = fr.cam_inv_tan, b = cam->focus;
-    volatile float inv_b = 1.0f / b;
-    volatile float den = 1.0f + f;
-    den = den - inv_b;
-    volatile float a = 1.0f / den;
-    volatile float apb = a + b;
-    volatile float two_f = 2.0f * f;
-    volatile float lr = two_f / cam->F;
-    fr.cam_a_plus_b = apb;
-    fr.cam_lens_radius = lr;
-  }
+  lens_values(fr.cam_inv_tan, cam->focus, cam->F, &fr.cam_a_plus_b, &fr.cam_lens_radius);
   fr.bg = mk3(bg[0], bg[1], bg[2]);
   fr.sky_intensity = ctx->sky_intensity;
   fr.sun_dir = mk3(ctx->sun_dir[0], ctx->sun_dir[1], ctx->sun_dir[2]);
@@ -2345,181 +2350,155 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   fr.sobol_bytes = ctx->d_sobol_bytes;
   fr.lut.reflection = ctx->d_lut_refl;
   fr.lut.sheen = ctx->d_lut_sheen;
+  return fr;
+}
 
+LayersDev layers_dev(const fh_ctx* ctx, const fh_render_layers* layers)
+{
   LayersDev L{};
   L.beauty = (float4*)layers->beauty; L.position = (float4*)layers->position; L.depth = layers->depth;
   L.normal = (float4*)layers->normal; L.texcoord = (float4*)layers->texcoord; L.albedo = (float4*)layers->albedo;
   L.sample_count = ctx->d_sample_count;
+  return L;
+}
 
-  // ---- pixels that cannot see the scene are rendered by k_sky_pixels, the others by the passes below (see k_split_pixels).  Worth its fixed cost -- one small launch and a
-  // host synchronisation whenever camera, resolution or scene bounds change -- for calls of many samples only: 2^27 camera paths, 64 spp of a 1080p frame
-  const uint32_t* px_list = ctx->d_owned;
-  const uint32_t* xy_list = ctx->d_owned_xy;
-  uint32_t n_px = ctx->n_owned, n_sky = 0;
-  const bool quirk_call = (ctx->flags & FH_FLAG_REFERENCE_FIRSTHIT) != 0 && n_samples > 1;
-  if (ctx->tun.sky_split && !quirk_call && (unsigned long long)n_samples * ctx->n_owned >= (1ull << ctx->tun.sky_split_min_log2)) {
-    const int rc = split_pixels(ctx, cam, fr);
-    if (rc) return rc;
-    if (ctx->split_valid && ctx->n_sky_px >= ctx->n_owned / 8u) {  // (a handful of sky pixels is not worth a second kernel)
-      px_list = ctx->d_split[0]; xy_list = ctx->d_split[1];
-      n_px = ctx->n_wave_px; n_sky = ctx->n_sky_px;
-    }
+// the pixels a call (in adaptive mode: a round) renders through the passes, as image indices and as x | y << 16; n_sky: the sky pixels beside them
+struct PixelLists { const uint32_t* px; const uint32_t* xy; uint32_t n_px, n_sky; };
+
+// ---- pixels that cannot see the scene are rendered by k_sky_pixels, the others by the passes (see k_split_pixels).  Worth its fixed cost -- one small launch and a
+// host synchronisation whenever camera, resolution or scene bounds change -- for calls of many samples only: 2^27 camera paths, 64 spp of a 1080p frame
+int choose_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr, uint32_t n_samples, bool quirk, PixelLists& out)
+{
+  out = PixelLists{ctx->d_owned, ctx->d_owned_xy, ctx->n_owned, 0u};
+  if (!(ctx->tun.sky_split && !quirk && (unsigned long long)n_samples * ctx->n_owned >= (1ull << ctx->tun.sky_split_min_log2))) return FH_OK;
+  const int rc = split_pixels(ctx, cam, fr);
+  if (rc) return rc;
+  if (ctx->split_valid && ctx->n_sky_px >= ctx->n_owned / 8u)  // (a handful of sky pixels is not worth a second kernel)
+    out = PixelLists{ctx->d_split[0], ctx->d_split[1], ctx->n_wave_px, ctx->n_sky_px};
+  return FH_OK;
+}
+
+// FH_FLAG_REFERENCE_FIRSTHIT with more than one sample per launch: per-pixel state carried through the launch, passes run one after the other
+int quirk_begin(fh_ctx* ctx)
+{
+  const size_t px = (size_t)ctx->width * ctx->height;
+  if (ctx->quirk_pixels != px) {
+    if (ctx->d_quirk_seen) (void)hipFree(ctx->d_quirk_seen);
+    if (ctx->d_quirk_aov) (void)hipFree(ctx->d_quirk_aov);
+    ctx->d_quirk_seen = nullptr; ctx->d_quirk_aov = nullptr; ctx->quirk_pixels = 0;
+    FH_HIP(hipMalloc((void**)&ctx->d_quirk_seen, px * sizeof(uint32_t)));
+    FH_HIP(hipMalloc((void**)&ctx->d_quirk_aov, px * 4 * sizeof(float4)));
+    ctx->quirk_pixels = px;
   }
-  const uint32_t target = ctx->pool_target > ctx->n_owned ? ctx->pool_target : ctx->n_owned;
-  // samples per pass of a run of n_samples samples over n_px pixels (the whole call; in adaptive mode, one round)
-  auto batch_for = [&](uint32_t n_px, uint32_t n_samples) {
-    uint32_t batch = n_px ? target / n_px : n_samples;
-    if (batch > n_samples) batch = n_samples;
-    if (batch > 65535u) batch = 65535u;  // (k_generate's grid has one row per sample of the pass)
-    if (batch < 1) batch = 1;
-    if (batch < n_samples) {  // equal passes, and whole rounds of the passes in flight: a call of 1024 samples with room for 248 per pass runs six passes of 171, not four of
-      // 248 and a runt of 32 -- the last pass of an incomplete round has nothing to overlap with (configs[2]: 3 / 4 / 5 / 6 passes measure 7700 / 7577 / 7578 / 7598 Msamples/s, r5-5)
-      uint32_t passes = (n_samples + batch - 1u) / batch;
-      const uint32_t slots = (uint32_t)ctx->n_slots;
-      if (slots > 1u && passes > slots && passes % slots != 0u && (passes / slots + 1u) * slots <= n_samples) passes = (passes / slots + 1u) * slots;
-      batch = (n_samples + passes - 1u) / passes;
-    }
-    // (the passes of a call overlap, three in flight: a big call that would fit one or two passes is cut into three of the same size -- unless its passes run one after
-    // the other anyway: the bug-compat mode and the measuring mode, where a split is pure overhead)
-    if (!quirk_call && (ctx->flags & FH_FLAG_SERIAL_PASSES) == 0 && (n_samples + batch - 1u) / batch < (uint32_t)ctx->n_slots && n_samples >= (uint32_t)ctx->n_slots && (unsigned long long)n_samples * n_px >= 3ull << 24) batch = (n_samples + (uint32_t)ctx->n_slots - 1u) / (uint32_t)ctx->n_slots;
-    return batch;
-  };
+  FH_HIP(hipMemsetAsync(ctx->d_quirk_seen, 0, px * sizeof(uint32_t), ctx->stream));   // a launch starts with firsthit = true and a zeroed payload
+  FH_HIP(hipMemsetAsync(ctx->d_quirk_aov, 0, px * 4 * sizeof(float4), ctx->stream));
+  return FH_OK;
+}
 
-  const SceneDev sc_all = scene_dev(ctx);
-  const SceneDev& sc = sc_all;  // (the passes below shadow this with their own copy: where rays start is a per-pass choice)
-  const bool count = (ctx->flags & FH_FLAG_COUNT_TRAVERSAL) != 0;
-  const bool clocks = (ctx->flags & FH_FLAG_TIME_KERNELS) != 0;
-  TraceCounters tc_closest{ctx->d_trace_counters, ctx->d_trace_counters + 1, ctx->d_trace_counters + 2, ctx->d_trace_counters + 6, ctx->d_trace_counters + 7, ctx->d_trace_counters + 10,
-                           clocks ? ctx->d_trace_counters + 27 : nullptr};
-  TraceCounters tc_shadow{ctx->d_trace_counters + 3, ctx->d_trace_counters + 4, ctx->d_trace_counters + 5, ctx->d_trace_counters + 8, ctx->d_trace_counters + 9, ctx->d_trace_counters + 18,
-                          clocks ? ctx->d_trace_counters + 29 : nullptr};
-
-  // FH_FLAG_REFERENCE_FIRSTHIT with more than one sample per launch: per-pixel state carried through the launch, passes run one after the other
-  const bool quirk = (ctx->flags & FH_FLAG_REFERENCE_FIRSTHIT) != 0 && n_samples > 1;
-  if (quirk) {
-    const size_t px = (size_t)ctx->width * ctx->height;
-    if (ctx->quirk_pixels != px) {
-      if (ctx->d_quirk_seen) (void)hipFree(ctx->d_quirk_seen);
-      if (ctx->d_quirk_aov) (void)hipFree(ctx->d_quirk_aov);
-      ctx->d_quirk_seen = nullptr; ctx->d_quirk_aov = nullptr; ctx->quirk_pixels = 0;
-      FH_HIP(hipMalloc((void**)&ctx->d_quirk_seen, px * sizeof(uint32_t)));
-      FH_HIP(hipMalloc((void**)&ctx->d_quirk_aov, px * 4 * sizeof(float4)));
-      ctx->quirk_pixels = px;
-    }
-    FH_HIP(hipMemsetAsync(ctx->d_quirk_seen, 0, px * sizeof(uint32_t), ctx->stream));   // a launch starts with firsthit = true and a zeroed payload
-    FH_HIP(hipMemsetAsync(ctx->d_quirk_aov, 0, px * 4 * sizeof(float4), ctx->stream));
-  }
-  if (!ctx->render_pending) { (void)hipEventRecord(ctx->ev_render_begin, ctx->stream); ctx->render_pending = true; }
-  // whatever the caller queued on the main stream before this call (clears, uploads) comes first on the second stream too
-  FH_HIP(hipEventRecord(ctx->ev_enter, ctx->stream));
-  for (int k = 0; k + 1 < ctx->n_slots; ++k) FH_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->ev_enter, 0));
-  int last_slot = 0;
+// A list of sky pixels is rendered by two launches of k_sky_pixels that pull groups of 64 pixels from one cursor.  The FILLER, a small fixed grid (FH_SKY_BLOCKS workgroups
+// per CU) on the sky stream, starts with the passes and runs in the issue slots their kernels leave idle: one wave of 80 registers beside six traversal waves per SIMD, at
+// wave priority 0 under the pass kernels' 1 (pass_priority).  The DRAIN, a grid that fills the machine, goes to the main stream behind the last pass of the call (or of the
+// round) and finishes at full rate whatever the filler did not reach -- a call whose passes are short loses nothing to the filler's small grid.  Neither waits for the
+// other: a group belongs to the wave that claimed it.  In line on the main stream (st == ctx->stream) one launch does it all.
+struct SkyLaunches {
+  fh_ctx* ctx;
+  const FrameDev& fr;
+  const LayersDev& L;
+  bool adaptive;
   // (FH_FLAG_SERIAL_PASSES and FH_PIPELINE=0, the measuring modes: in line on the main stream, so that every kernel of the call is alone on the GPU, the spans add up and
   // a serial kernel trace shows the kernel's work instead of the time a starved background kernel was resident)
-  hipStream_t sky_st = ((ctx->flags & FH_FLAG_SERIAL_PASSES) != 0 || ctx->n_slots == 1) ? ctx->stream : ctx->sky_stream;
-  if (n_sky && sky_st != ctx->stream) FH_HIP(hipStreamWaitEvent(sky_st, ctx->ev_enter, 0));
-  // A list of sky pixels is rendered by two launches of k_sky_pixels that pull groups of 64 pixels from one cursor.  The FILLER, a small fixed grid (FH_SKY_BLOCKS workgroups
-  // per CU) on the sky stream, starts with the passes and runs in the issue slots their kernels leave idle: one wave of 80 registers beside six traversal waves per SIMD, at
-  // wave priority 0 under the pass kernels' 1 (pass_priority).  The DRAIN, a grid that fills the machine, goes to the main stream behind the last pass of the call (or of the
-  // round) and finishes at full rate whatever the filler did not reach -- a call whose passes are short loses nothing to the filler's small grid.  Neither waits for the
-  // other: a group belongs to the wave that claimed it.  In line on the main stream (sky_st == ctx->stream) one launch does it all.
-  struct SkyDrain { const uint32_t* px; const uint32_t* xy; uint32_t n, n_samples; bool pending; } sky_drain{nullptr, nullptr, 0u, 0u, false};
-  uint32_t* const sky_cursor = ctx->d_split_counters + 3;
-  const uint32_t sky_filler_wgs = sky_st == ctx->stream ? 0u : (ctx->tun.sky_filler_grid ? ctx->tun.sky_filler_grid : ctx->tun.n_cus * ctx->tun.sky_blocks_per_cu);
-  auto sky_launch = [&](hipStream_t s, uint32_t wgs, const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t ns) {
+  hipStream_t st;
+  uint32_t* cursor;
+  uint32_t filler_wgs, full_wgs;
+  struct Drain { const uint32_t* px; const uint32_t* xy; uint32_t n, n_samples; bool pending; } drain{nullptr, nullptr, 0u, 0u, false};
+
+  SkyLaunches(fh_ctx* c, const FrameDev& f, const LayersDev& l, bool a)
+      : ctx(c), fr(f), L(l), adaptive(a), st(((c->flags & FH_FLAG_SERIAL_PASSES) != 0 || c->n_slots == 1) ? c->stream : c->sky_stream), cursor(c->d_split_counters + 3),
+        filler_wgs(st == c->stream ? 0u : (c->tun.sky_filler_grid ? c->tun.sky_filler_grid : c->tun.n_cus * c->tun.sky_blocks_per_cu)),
+        full_wgs(c->tun.n_cus * (uint32_t)kSkyWaves)  // (every workgroup resident: the cursor balances them)
+  {
+  }
+  void launch(hipStream_t s, uint32_t wgs, const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t ns)
+  {
     Span sp(ctx, s, 4);
     const uint32_t full = (n + kBlock - 1u) / kBlock;  // (one group per wave)
     const uint32_t grid = wgs < full ? wgs : full;
-    if (adaptive) hipLaunchKernelGGL(k_sky_pixels<true>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, (const SkyAdaptive*)ctx->d_sky_adaptive, sky_cursor);
-    else hipLaunchKernelGGL(k_sky_pixels<false>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, ctx->d_split_counters + 2, sky_cursor);
-  };
-  const uint32_t sky_full_wgs = ctx->tun.n_cus * (uint32_t)kSkyWaves;  // (every workgroup resident: the cursor balances them)
-  // (the caller has ordered the main stream behind every earlier launch that used the cursor)
-  auto sky_begin = [&](const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t ns) -> int {
-    FH_HIP(hipMemsetAsync(sky_cursor, 0, 4, ctx->stream));
-    if (sky_st == ctx->stream) { sky_launch(sky_st, sky_full_wgs, px, xy, n, ns); return FH_OK; }
-    if (sky_filler_wgs) {
-      FH_HIP(hipEventRecord(ctx->ev_sky_cursor, ctx->stream));
-      FH_HIP(hipStreamWaitEvent(sky_st, ctx->ev_sky_cursor, 0));
-      sky_launch(sky_st, sky_filler_wgs, px, xy, n, ns);
-    }
-    sky_drain = SkyDrain{px, xy, n, ns, true};
-    return FH_OK;
-  };
-  auto sky_end = [&]() {  // on the main stream, which the caller has ordered behind the passes the launch is to follow
-    if (!sky_drain.pending) return;
-    sky_launch(ctx->stream, sky_full_wgs, sky_drain.px, sky_drain.xy, sky_drain.n, sky_drain.n_samples);
-    sky_drain.pending = false;
-  };
-  if (n_sky && !guard_blocks) {  // the sky pixels of this call, all samples at once (they share no pixel with the passes)
-    const int rc = sky_begin(ctx->d_split[2], ctx->d_split[3], n_sky, n_samples);
-    if (rc) return rc;
-    if (adaptive) ctx->sky_taken_pending = true;  // (the samples it takes are counted on the device: fh_sync adds them to the stats)
-    else {
-      ctx->stats.paths += (uint64_t)n_sky * n_samples;
-      ctx->stats.sky_pixel_samples += (uint64_t)n_sky * n_samples;
-    }
+    if (adaptive) hipLaunchKernelGGL(k_sky_pixels<true>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, (const SkyAdaptive*)ctx->d_sky_adaptive, cursor);
+    else hipLaunchKernelGGL(k_sky_pixels<false>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, ctx->d_split_counters + 2, cursor);
   }
+  // (the caller has ordered the main stream behind every earlier launch that used the cursor)
+  int begin(const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t ns)
+  {
+    FH_HIP(hipMemsetAsync(cursor, 0, 4, ctx->stream));
+    if (st == ctx->stream) { launch(st, full_wgs, px, xy, n, ns); return FH_OK; }
+    if (filler_wgs) {
+      FH_HIP(hipEventRecord(ctx->ev_sky_cursor, ctx->stream));
+      FH_HIP(hipStreamWaitEvent(st, ctx->ev_sky_cursor, 0));
+      launch(st, filler_wgs, px, xy, n, ns);
+    }
+    drain = Drain{px, xy, n, ns, true};
+    return FH_OK;
+  }
+  void end()  // on the main stream, which the caller has ordered behind the passes the launch is to follow
+  {
+    if (!drain.pending) return;
+    launch(ctx->stream, full_wgs, drain.px, drain.xy, drain.n, drain.n_samples);
+    drain.pending = false;
+  }
+};
 
+// how the traversal kernels of a call are launched; of the streaming launches [0] is the closest-hit one, [1] the secondary-ray one (and the merged one)
+struct StreamPlan {
+  bool coop, stream, sort_queues, shade_three;
+  uint32_t stack_bytes;                      // dynamic LDS of the fixed-batch kernels and of the fused tail: the whole stack
+  uint32_t entries[2], lds_bytes[2];         // stack levels a streaming kernel keeps in LDS, and their bytes
+  uint32_t grid[2];                          // workgroups of a streaming launch: all resident
+  uint32_t spill_entries[2];                 // stack levels beyond the LDS part
+  size_t spill_region;                       // uint2 per launch in flight of ctx->d_stack_spill
+  uint32_t chunk[2];                         // packed chunk words (render_plan_host.h: stream_chunk_word)
+};
+
+// `filler`: a filler launch of k_sky_pixels runs beside the passes of this call
+int stream_plan(fh_ctx* ctx, const SceneDev& sc, bool count, bool filler, StreamPlan& p)
+{
   // device facts and developer switches were read once at fh_ctx_create (context.h: Tunables)
   const fh_ctx::Tunables& tun = ctx->tun;
-  // wave-cooperative triangle tests (default for the wide BVH): queued candidates that trigger a round.  48 (r5-12) -- but ONE-PASS calls of scenes without cut-outs keep 32
-  // (r5-13, profiles/r05_latency_defaults.log: the soup's fh_render(1 / 4 / 16) take 2.02 / 3.37 / 7.02 ms with 32 and 2.21 / 3.62 / 7.32 with 48 -- a launch of few rays
-  // waits longer for 48 candidates; the interior with cut-outs is 1 % faster with 48 there too).  FH_COOP_T fixes it for every call.
-  const bool coop = sc.use_bvh8 != 0 && sc.bvh8.n_tris < kCoopMaxTris && tun.coop;
+  // wave-cooperative triangle tests (default for the wide BVH)
+  p.coop = sc.use_bvh8 != 0 && sc.bvh8.n_tris < kCoopMaxTris && tun.coop;
   // streaming form (FH_STREAM=0: one fixed batch per wave).  Through a small tree every ray takes the same few steps: nothing to rebalance, and the fixed
   // batches run without the refill machinery (1000-triangle soup: closest 7.4 -> 4.6 ms, secondary 2.6 -> 1.0 ms per 256 spp; even at ~2 K nodes; behind at 20 K)
-  const bool stream = coop && tun.stream && (tun.stream_forced || ctx->bvh8_n_nodes >= 4096u);
+  p.stream = p.coop && tun.stream && (tun.stream_forced || ctx->bvh8_n_nodes >= 4096u);
   // the traversal stack of every lane lives in LDS, one entry per level of the BVH (bvh_build.hip records the depth); the streaming kernels may spill deep levels (below)
-  const uint32_t stack_bytes = lds_stack_bytes(stack_entries_for(ctx->bvh8_depth));
-  const uint32_t cfg_bytes = lds_stack_bytes(stack_entries_for(ctx->bvh8_depth) + 1u);  // (+ 1: the anchor entry of rays that start below the root, fh_trace.h)
+  const uint32_t stack_entries = stack_entries_for(ctx->bvh8_depth);
+  p.stack_bytes = lds_stack_bytes(stack_entries);
+  const uint32_t cfg_bytes = lds_stack_bytes(stack_entries + 1u);  // (+ 1: the anchor entry of rays that start below the root, fh_trace.h)
   if (sc.use_bvh8 && ctx->lds_configured_bytes != cfg_bytes) {  // kernels that may need more than the default 64 KB of LDS are told so once per BVH depth
     const int rc = configure_traversal_lds(ctx, cfg_bytes);
     if (rc) return rc;
   }
-  if (sc.use_bvh8 && stack_bytes + ctx->lds_static_max > tun.lds_per_block) return fail(ctx, FH_E_UNSUPPORTED, "fh_render: BVH too deep for the LDS traversal stack");
+  if (sc.use_bvh8 && p.stack_bytes + ctx->lds_static_max > tun.lds_per_block) return fail(ctx, FH_E_UNSUPPORTED, "fh_render: BVH too deep for the LDS traversal stack");
   // all workgroups of a streaming launch are resident: as many per CU as its LDS (160 KB on gfx950) holds (at most 6: the kernels' register budget)
-  const uint32_t stack_entries = stack_entries_for(ctx->bvh8_depth);
   // the streaming kernels' rays may start below the root: entry 0 of such a ray's stack is its anchor, the groups come on top (fh_trace.h: bottom-up start)
   const uint32_t stream_need = stack_entries + (sc.bvh8.parent ? 1u : 0u);
   // static LDS of a streaming kernel's workgroup: the cooperative-test records and, where candidates are parked for their any-hit test (AlphaDefer), the ring
-  const uint32_t static_lds_closest = kCoopLdsBytesPerBlock + (sc.has_alpha && AlphaDefer<false, true>::value ? kAlphaLdsBytesPerBlock : 0u);
-  const uint32_t static_lds_secondary = kCoopLdsBytesPerBlock + kTopLdsBytes + (sc.has_alpha && AlphaDefer<true, true>::value ? kAlphaLdsBytesPerBlock : 0u);
-  if (stream) {  // what the runtime says really fits (LDS granularity, registers of the variant in use): a grid above it would leave blocks queued behind the resident ones
-    const uint32_t key = stack_bytes | (count ? 1u : 0u) | (sc.has_alpha ? 2u : 0u) | (sc.n_lights > 0 ? 4u : 0u) | (sc.bvh8.parent ? 8u : 0u) | (tun.stack_lds_entries << 20);
+  const uint32_t static_lds[2] = {kCoopLdsBytesPerBlock + (sc.has_alpha && AlphaDefer<false, true>::value ? kAlphaLdsBytesPerBlock : 0u),
+                                  kCoopLdsBytesPerBlock + kTopLdsBytes + (sc.has_alpha && AlphaDefer<true, true>::value ? kAlphaLdsBytesPerBlock : 0u)};
+  if (p.stream) {  // what the runtime says really fits (LDS granularity, registers of the variant in use): a grid above it would leave blocks queued behind the resident ones
+    const uint32_t key = p.stack_bytes | (count ? 1u : 0u) | (sc.has_alpha ? 2u : 0u) | (sc.n_lights > 0 ? 4u : 0u) | (sc.bvh8.parent ? 8u : 0u) | (tun.stack_lds_entries << 20);
     if (ctx->occupancy_key != key) {
-      auto occupancy = [&](bool secondary, uint32_t entries) {
-        const uint32_t bytes = lds_stack_bytes(entries);
-        int r = 0;
-        with_bool(count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
-          if (!secondary) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, k_trace_closest_stream<decltype(C)::value, decltype(A)::value>, kBlock, bytes);
-          else with_bool(sc.n_lights > 0, [&](auto Li) {
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>, kBlock, bytes);
-          });
-        }); });
-        return r;
+      auto occupancy = [&](bool secondary) {
+        return [&, secondary](uint32_t entries) {
+          int r = 0;
+          (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, stream_kernel(secondary, count, sc.n_lights > 0, sc.has_alpha != 0), kBlock, lds_stack_bytes(entries));
+          return r;
+        };
       };
-      // The stack costs LDS, and LDS costs resident workgroups.  Each of the two kernels keeps as many stack levels in LDS as still give it the workgroups per CU it is compiled
-      // for (FH_STREAM_BLOCKS_CLOSEST / FH_STREAM_BLOCKS: at n workgroups per CU one has lds_per_cu / n bytes, and what the cooperative-test records leave is the stack's) and spills
-      // the deeper levels, which are rarely reached, to global memory (GroupStack<true>).  FH_STACK_LDS=n fixes the number for both, FH_STACK_LDS=99 keeps everything in LDS.
-      auto pick = [&](bool secondary, uint32_t blocks_wanted, uint32_t& entries_out, uint32_t& blocks_out) {
-        const uint32_t lds_share = tun.lds_per_cu / blocks_wanted;
-        const uint32_t static_lds = secondary ? static_lds_secondary : static_lds_closest;
-        const uint32_t fit = lds_share > static_lds + 1280u ? (lds_share - static_lds) / 1280u : 1u;
-        const uint32_t floor_entries = fit < 8u ? fit : 8u;
-        uint32_t entries = stream_need;
-        int got = occupancy(secondary, entries);
-        if (tun.stack_lds_entries) entries = tun.stack_lds_entries < stream_need ? tun.stack_lds_entries : stream_need;
-        else if (stream_need > floor_entries) {
-          const int best = occupancy(secondary, floor_entries);
-          while (entries > floor_entries && got < best) { --entries; got = occupancy(secondary, entries); }
-        }
-        if (entries != stream_need) got = occupancy(secondary, entries);
-        entries_out = entries;
-        blocks_out = got > 0 ? (uint32_t)got : 0u;
-      };
-      pick(false, FH_STREAM_BLOCKS_CLOSEST, ctx->stream_lds_entries, ctx->occupancy_blocks);
-      pick(true, sc.n_lights > 0 ? FH_SECONDARY_BLOCKS_HEAVY : (sc.has_alpha ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS), ctx->stream_lds_entries_secondary, ctx->occupancy_blocks_secondary);
+      // how many stack levels each of the two kernels keeps in LDS (render_plan_host.h: stream_lds_entries; FH_STREAM_BLOCKS_CLOSEST / FH_STREAM_BLOCKS: what they are compiled for)
+      const StreamLds closest = stream_lds_entries(tun.lds_per_cu, FH_STREAM_BLOCKS_CLOSEST, static_lds[0], stream_need, tun.stack_lds_entries, occupancy(false));
+      const StreamLds secondary = stream_lds_entries(tun.lds_per_cu, sc.n_lights > 0 ? FH_SECONDARY_BLOCKS_HEAVY : (sc.has_alpha ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS), static_lds[1],
+                                                     stream_need, tun.stack_lds_entries, occupancy(true));
+      ctx->stream_lds_entries = closest.entries; ctx->occupancy_blocks = closest.blocks;
+      ctx->stream_lds_entries_secondary = secondary.entries; ctx->occupancy_blocks_secondary = secondary.blocks;
       ctx->occupancy_key = key;
       if (!count) {  // (what fh_kernel_info reports: the plan of the kernels that render, not of the instrumented variants a counting call has just been launched with)
         ctx->info_blocks[0] = ctx->occupancy_blocks; ctx->info_blocks[1] = ctx->occupancy_blocks_secondary;
@@ -2527,335 +2506,437 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
       }
       if (getenv("FH_DEBUG_BVH"))
         fprintf(stderr, "[trace] stack of %u entries (%s); in LDS: closest %u (%u B + %u B per workgroup, %u resident workgroups per CU), secondary %u (%u B + %u B, %u workgroups)\n", stream_need, sc.bvh8.parent ? "rays start at the node of the face they leave" : "rays start at the root",
-                ctx->stream_lds_entries, lds_stack_bytes(ctx->stream_lds_entries), static_lds_closest, ctx->occupancy_blocks, ctx->stream_lds_entries_secondary,
-                lds_stack_bytes(ctx->stream_lds_entries_secondary), static_lds_secondary, ctx->occupancy_blocks_secondary);
+                ctx->stream_lds_entries, lds_stack_bytes(ctx->stream_lds_entries), static_lds[0], ctx->occupancy_blocks, ctx->stream_lds_entries_secondary,
+                lds_stack_bytes(ctx->stream_lds_entries_secondary), static_lds[1], ctx->occupancy_blocks_secondary);
     }
   }
-  const uint32_t stream_entries = stream ? ctx->stream_lds_entries : stream_need, stream_entries_secondary = stream ? ctx->stream_lds_entries_secondary : stream_need;
-  const uint32_t stream_stack_bytes = lds_stack_bytes(stream_entries), stream_stack_bytes_secondary = lds_stack_bytes(stream_entries_secondary);
-  auto wgs_for = [&](uint32_t bytes, uint32_t static_lds, uint32_t compiled_for, uint32_t reported) {
-    uint32_t w = tun.lds_per_cu / (bytes + static_lds);
-    w = w > compiled_for ? compiled_for : (w < 1u ? 1u : w);
-    if (stream && reported && reported < w) w = reported;
-    return w;
-  };
   // With a filler wave on every SIMD a seventh traversal workgroup per CU has no registers to go to: it would wait for one of the six to end and start as a straggler of a
   // persistent launch.  The passes of a call that started a filler are launched with six per CU (the compiled budget, FH_STREAM_BLOCKS, stays).
-  const uint32_t wgs_cap = n_sky && sky_filler_wgs ? (uint32_t)FH_STREAM_BLOCKS_FILLER : 0xffffu;
-  uint32_t wgs_closest = wgs_for(stream_stack_bytes, static_lds_closest, FH_STREAM_BLOCKS_CLOSEST, ctx->occupancy_blocks);
-  uint32_t wgs_secondary = wgs_for(stream_stack_bytes_secondary, static_lds_secondary, FH_STREAM_BLOCKS > FH_SECONDARY_BLOCKS_HEAVY ? FH_STREAM_BLOCKS : FH_SECONDARY_BLOCKS_HEAVY, ctx->occupancy_blocks_secondary);
-  if (wgs_closest > wgs_cap) wgs_closest = wgs_cap;
-  if (wgs_secondary > wgs_cap) wgs_secondary = wgs_cap;
-  const uint32_t stream_grid = tun.n_cus * wgs_closest;
-  const uint32_t stream_grid_secondary = tun.n_cus * wgs_secondary;
+  const uint32_t wgs_cap = filler ? (uint32_t)FH_STREAM_BLOCKS_FILLER : 0xffffu;
+  const uint32_t in_lds[2] = {ctx->stream_lds_entries, ctx->stream_lds_entries_secondary}, reported[2] = {ctx->occupancy_blocks, ctx->occupancy_blocks_secondary};
+  const uint32_t compiled_for[2] = {FH_STREAM_BLOCKS_CLOSEST, FH_STREAM_BLOCKS > FH_SECONDARY_BLOCKS_HEAVY ? FH_STREAM_BLOCKS : FH_SECONDARY_BLOCKS_HEAVY};
+  for (int k = 0; k < 2; ++k) {
+    p.entries[k] = p.stream ? in_lds[k] : stream_need;
+    p.lds_bytes[k] = lds_stack_bytes(p.entries[k]);
+    p.grid[k] = tun.n_cus * stream_wgs(tun.lds_per_cu, p.lds_bytes[k], static_lds[k], compiled_for[k], p.stream ? reported[k] : 0u, wgs_cap);
+    p.spill_entries[k] = p.entries[k] < stream_need ? stream_need - p.entries[k] : 0u;
+  }
   // spill area of the streaming launches: [launch in flight: pass slot x (closest, secondary)][entry beyond the LDS part][thread of the launch]
-  const uint32_t spill_entries = stream_entries < stream_need ? stream_need - stream_entries : 0u;
-  const uint32_t spill_entries_secondary = stream_entries_secondary < stream_need ? stream_need - stream_entries_secondary : 0u;
-  const size_t spill_threads = (size_t)(stream_grid > stream_grid_secondary ? stream_grid : stream_grid_secondary) * kBlock;
-  const size_t spill_region = (size_t)(spill_entries > spill_entries_secondary ? spill_entries : spill_entries_secondary) * spill_threads;  // uint2 each
-  if (spill_region * 6u > ctx->stack_spill_capacity) {
+  const size_t spill_threads = (size_t)(p.grid[0] > p.grid[1] ? p.grid[0] : p.grid[1]) * kBlock;
+  p.spill_region = (size_t)(p.spill_entries[0] > p.spill_entries[1] ? p.spill_entries[0] : p.spill_entries[1]) * spill_threads;  // uint2 each
+  if (p.spill_region * 6u > ctx->stack_spill_capacity) {
     FH_HIP(hipDeviceSynchronize());  // (launches of earlier calls may still use the old area)
     if (ctx->d_stack_spill) FH_HIP(hipFree(ctx->d_stack_spill));
     ctx->d_stack_spill = nullptr;
     ctx->stack_spill_capacity = 0;
-    FH_HIP(hipMalloc((void**)&ctx->d_stack_spill, sizeof(uint2) * spill_region * 6u));
-    ctx->stack_spill_capacity = spill_region * 6u;
+    FH_HIP(hipMalloc((void**)&ctx->d_stack_spill, sizeof(uint2) * p.spill_region * 6u));
+    ctx->stack_spill_capacity = p.spill_region * 6u;
   }
-  // (rays through a small tree are cheap enough to run into the atomic rate of the work cursor: allow larger chunks there, stream_chunk_for)
-  const uint32_t chunk_max = tun.stream_chunk_fixed ? tun.stream_chunk : (ctx->bvh8_n_nodes < 512u ? 256u : (ctx->bvh8_n_nodes < 4096u ? 128u : tun.stream_chunk));
-  const uint32_t stream_refill = tun.stream_refill, stream_chunk = (tun.stream_chunk & 0xffffu) | ((chunk_max > tun.stream_chunk ? chunk_max : 0u) << 16);
+  const uint32_t chunk_max = stream_chunk_max(tun.stream_chunk_fixed, tun.stream_chunk, ctx->bvh8_n_nodes);
+  p.chunk[1] = stream_chunk_word(tun.stream_chunk, chunk_max);
   // (the closest-hit launch takes its own chunk size, FH_STREAM_CHUNK_CLOSEST)
-  const uint32_t chunk_closest = tun.stream_chunk_closest ? tun.stream_chunk_closest : tun.stream_chunk;
-  const uint32_t stream_chunk_closest = (chunk_closest & 0xffffu) | ((chunk_max > chunk_closest ? chunk_max : 0u) << 16);
-  const uint32_t env_tail_depth = tun.tail_depth;
+  p.chunk[0] = stream_chunk_word(tun.stream_chunk_closest ? tun.stream_chunk_closest : tun.stream_chunk, chunk_max);
   // cell-ordered queues pay where rays of one cell share the nodes they fetch; a tree the fixed-batch kernels trace (under 4096 nodes) sits in the caches whatever
   // the order, and there the six sort launches per bounce are what a small frame waits for (Cornell box, 1 spp: 0.33 of 2.15 ms)
-  const bool sort_queues = tun.sort_queues && (stream || tun.sort_small);
-  const bool shade_three = tun.shade_wgs ? tun.shade_wgs == 3u : true;  // (above, FH_SHADE_BLOCKS)
+  p.sort_queues = tun.sort_queues && (p.stream || tun.sort_small);
+  p.shade_three = tun.shade_wgs ? tun.shade_wgs == 3u : true;  // (above, FH_SHADE_BLOCKS)
+  return FH_OK;
+}
+
+// what every pass of one fh_render call shares
+struct Call {
+  fh_ctx* ctx;
+  FrameDev fr;
+  LayersDev L;
+  SceneDev sc;  // what the scene CAN do (where rays start is a per-pass choice: Pass::sc)
+  TraceCounters tc_closest, tc_shadow;
+  uint32_t max_depth;
+  bool adaptive, quirk, count;
+  StreamPlan plan;
+};
+
+// one pass: its pool slot and streams, and what was chosen for it
+struct Pass {
+  SceneDev sc;         // the call's scene with this pass's choice of where first-hit rays start
+  int slot, probe;     // probe: while the scene's ray start is being probed, what this pass tries (0: the root, 1: the node of the face; -1: not a probing pass)
+  hipStream_t st, sb;  // the pass's stream; the stream of its secondary launches (the same, but for the overlap form of a one-pass call)
+  uint32_t grid, coop_flush, wave_depth;
+  bool single_pass, merge, overlap;
+};
+
+// the counter snapshots of earlier passes that have arrived: the share of a pass's paths alive at each depth (context.h: survival) and, while the scene's ray start is
+// being probed, what the secondary launches cost (no host/device synchronisation: a snapshot is looked at when its event has passed)
+void harvest_counters(fh_ctx* ctx)
+{
+  for (int k = 0; k < 3; ++k) {
+    if (!(ctx->counters_in_flight[k] && hipEventQuery(ctx->ev_counters[k]) == hipSuccess)) continue;
+    ctx->counters_in_flight[k] = false;
+    const uint32_t wd = ctx->counters_wave_depth[k];
+    const uint32_t* hc = ctx->h_counters[k];
+    if (ctx->counters_paths[k]) {  // the share of the pass's paths alive at each depth it ran as a wavefront (context.h: survival)
+      const uint32_t n = wd < 65u ? wd : 65u;
+      for (uint32_t d = 0; d <= n; ++d) ctx->survival[d] = (double)hc[d * kCounterStride + CNT_RAD] / (double)ctx->counters_paths[k];
+      if (ctx->survival_n < n + 1u) ctx->survival_n = n + 1u;  // (a pass the tail took over early says nothing about the deeper shares: what an earlier pass of this scene measured stays)
+    }
+    if (ctx->counters_bu[k] >= 0 && ctx->bu_choice == 0) {  // (a pass of the scene's probing phase: what its secondary launches cost, by the issue model's weights)
+      double cost = 0.0, items = 0.0;
+      for (uint32_t d = 0; d < wd; ++d) { cost += 510.0 * hc[d * kCounterStride + CNT_COST_NODE] + 175.0 * hc[d * kCounterStride + CNT_COST_TRI]; items += hc[d * kCounterStride + CNT_SEC]; }
+      ctx->bu_cost[ctx->counters_bu[k]] += cost; ctx->bu_items[ctx->counters_bu[k]] += items;
+      const int verdict = bottom_up_verdict(ctx->bu_cost, ctx->bu_items);
+      if (verdict) {
+        ctx->bu_choice = verdict;
+        if (getenv("FH_DEBUG_BVH"))
+          fprintf(stderr, "[trace] rays that leave a surface start at %s: %.0f against %.0f SIMD cycles of tests per shaded path (from the root / from the face)\n", ctx->bu_choice == 2 ? "the node of their face" : "the root",
+                  ctx->bu_cost[0] / ctx->bu_items[0], ctx->bu_cost[1] / ctx->bu_items[1]);
+      }
+    }
+    ctx->counters_bu[k] = -1;
+    if (ctx->tun.debug_tail) { fprintf(stderr, "[tail] slot %d wd %u paths %u survivors:", k, wd, ctx->counters_paths[k]); for (uint32_t d = 0; d <= wd; ++d) fprintf(stderr, " %u", ctx->h_counters[k][d * kCounterStride + CNT_RAD]); fprintf(stderr, "\n"); }
+  }
+}
+
+// ---- where a pass's first-hit rays start their traversal (fh_trace.h: bottom-up start): forced by FH_BOTTOM_UP=0 / 1; else the first passes after a build alternate and
+// the device's own count of test rounds per shaded path decides (harvest_counters): a dense scene gains (1M-triangle soup: -12 %), an interior of long rays does not (-0.4 %)
+bool start_at_faces(const Call& c, bool merge, int& probe)
+{
+  fh_ctx* const ctx = c.ctx;
+  probe = -1;
+  if (!(c.sc.bvh8.parent && c.plan.stream && (ctx->flags & FH_FLAG_ROOT_START) == 0u)) return false;
+  if (ctx->tun.bottom_up == 1u) return true;
+  if (ctx->tun.bottom_up != 2u) return false;
+  // (only a pass whose secondary launch can climb is a probe: the merged launch of a one-pass call walks from the root whatever the pass says and counts no test
+  // rounds, so counting it would fill one side of the comparison with cost 0 and fix the choice at "root" -- the reference's 1- and 16-sample calls come first in a GUI)
+  if (ctx->bu_choice == 0 && !c.count && !merge && !c.sc.has_alpha) {
+    probe = (ctx->bu_toggle++ & 1u) != 0u ? 1 : 0;
+    return probe == 1;
+  }
+  return ctx->bu_choice == 2;
+}
+
+StackSpill stack_spill(const Call& c, const Pass& p, int k, uint32_t probe_flag)
+{
+  return StackSpill{c.plan.spill_entries[k] ? c.ctx->d_stack_spill + (size_t)(2 * p.slot + k) * c.plan.spill_region : nullptr, c.plan.entries[k], probe_flag};
+}
+
+void launch_closest(const Call& c, const Pass& p, const PoolDev& pd, uint32_t depth)
+{
+  fh_ctx* const ctx = c.ctx;
+  const StreamPlan& pl = c.plan;
+  const SceneDev& sc = p.sc;
+  Span sp(ctx, p.st, 0);
+  if (pl.stream) {
+    with_closest_stream(c.count, sc.has_alpha != 0, [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(p.grid < pl.grid[0] ? p.grid : pl.grid[0]), dim3(kBlock), pl.lds_bytes[0], p.st, sc, pd, depth, c.tc_closest, p.coop_flush, ctx->tun.stream_refill, pl.chunk[0],
+                         ctx->tun.stream_min_rays, stack_spill(c, p, 0, 0u));
+    });
+  } else if (pl.coop) {
+    with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
+      hipLaunchKernelGGL((k_trace_closest_coop<decltype(C)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.st, sc, pd, depth, c.tc_closest, p.coop_flush);
+    }); });
+  } else {
+    with_bool(c.count, [&](auto C) { with_bool(sc.use_bvh8 != 0, [&](auto W) { with_bool(sc.has_alpha != 0, [&](auto A) {
+      hipLaunchKernelGGL((k_trace_closest_static<decltype(C)::value, decltype(W)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), 0, p.st, sc, pd, depth, c.tc_closest);
+    }); }); });
+  }
+  ctx->stats.n_closest_launches++;
+}
+
+void launch_secondary(const Call& c, const Pass& p, const PoolDev& ps, uint32_t depth)
+{
+  fh_ctx* const ctx = c.ctx;
+  const StreamPlan& pl = c.plan;
+  const SceneDev& sc = p.sc;
+  Span sp(ctx, p.sb, 1);
+  if (pl.stream) {
+    with_secondary_stream(c.count, sc.n_lights > 0, sc.has_alpha != 0, [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.sb, sc, c.fr, ps, depth, c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1],
+                         ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u));
+    });
+  } else if (pl.coop) {
+    with_bool(c.count, [&](auto C) { with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
+      hipLaunchKernelGGL((k_trace_secondary_coop<decltype(C)::value, decltype(Li)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps, depth, c.tc_shadow,
+                         p.coop_flush);
+    }); }); });
+  } else {
+    with_bool(c.count, [&](auto C) { with_bool(sc.use_bvh8 != 0, [&](auto W) { with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
+      hipLaunchKernelGGL((k_trace_secondary_static<decltype(C)::value, decltype(W)::value, decltype(Li)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps,
+                         depth, c.tc_shadow);
+    }); }); }); });
+  }
+  ctx->stats.n_shadow_launches++;
+}
+
+// one-pass calls where the streaming kernels trace the scene: the secondary rays of bounce `depth` and the closest-hit rays of bounce depth + 1 in ONE launch
+void launch_merged(const Call& c, const Pass& p, const PoolDev& ps, const PoolDev& pd, uint32_t depth)
+{
+  fh_ctx* const ctx = c.ctx;
+  const StreamPlan& pl = c.plan;
+  const SceneDev& sc = p.sc;
+  Span sp(ctx, p.st, 1);
+  with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
+    hipLaunchKernelGGL((k_trace_merged_stream<decltype(Li)::value, decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.st, sc, c.fr, ps, pd, depth,
+                       c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u));
+  }); });
+  ctx->stats.n_shadow_launches++;
+  ctx->stats.n_closest_launches++;
+}
+
+// the fused tail finishes the survivors of the wavefront bounces: every class in one kernel, so it is compiled for every lobe a material of the scene can have
+void launch_tail(const Call& c, const Pass& p, const PoolDev& pd, uint32_t n_paths)
+{
+  fh_ctx* const ctx = c.ctx;
+  Span sp(ctx, p.st, 3);
+  uint32_t lobes = 0;
+  for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) lobes |= ctx->class_lobes[cls];
+  const dim3 tg(grid_for(n_paths / 16 + 1)), tb(kBlock);
+  const uint32_t tl = p.sc.use_bvh8 ? c.plan.stack_bytes : 0u, tf = c.plan.coop ? p.coop_flush : 0u;
+  with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_tail<decltype(V)::value>, tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf); });
+  ctx->stats.n_tail_launches++;
+}
+
+// secondary rays of this bounce and the radiance rays of the next one, each into cell order.  ONE-PASS calls (r6-7): the order buys their launches nothing -- every
+// line they touch is touched for the first time whatever the order -- and the six sort launches per bounce are pure chain: 4- and 16-sample calls of configs[3] are
+// 3 % / 2 % faster without them; only the queue the fused tail takes over keeps its order (FH_SORT_ONEPASS=1: all, =0: none)
+// pd, ps: the per-bounce views of the pool -- pd rotates the radiance queues through the sorted buffers, ps reads the sorted secondary queue
+void sort_bounce_queues(const Call& c, const Pass& p, const PoolDev& pool, uint32_t depth, uint32_t sort_blocks, PoolDev& pd, PoolDev& ps, uint32_t*& q_spare)
+{
+  const fh_ctx::Tunables& tun = c.ctx->tun;
+  Span sp(c.ctx, p.st, 6);
+  const bool tail_next = depth + 1u == p.wave_depth && p.wave_depth < c.max_depth;
+  const bool sort_sec = c.plan.sort_queues && (!p.single_pass || tun.sort_onepass == 1u);
+  const bool sort_rad = c.plan.sort_queues && (!p.single_pass || tun.sort_onepass == 1u || (tun.sort_onepass == 2u && tail_next));
+  ps = pd;
+  if (sort_sec) {
+    sort_queue_by_cell(p.st, sort_blocks, pool.counters + depth * kCounterStride + CNT_SEC, pool.q_sec, pool.key_sec, pool.bins, pool.q_sec_sorted);
+    ps.q_sec = pool.q_sec_sorted;
+  }
+  if (sort_rad) {
+    const uint32_t nxt = (depth + 1u) & 1u;
+    sort_queue_by_cell(p.st, sort_blocks, pool.counters + (depth + 1u) * kCounterStride + CNT_RAD, pd.q_rad[nxt], pool.key_rad, pool.bins, q_spare);
+    uint32_t* const unsorted = pd.q_rad[nxt];
+    pd.q_rad[nxt] = q_spare;  // the next bounce reads the sorted queue ...
+    q_spare = unsorted;       // ... and the buffer it came from is the next scratch target
+  }
+}
+
+// One pass of nb samples over the pixels of `px`, of a call (round) of n_round samples in passes of `batch`.
+// n_slots passes in flight (three by default, FH_PIPELINE): pass j lives in pool j % n_slots on the stream of that slot.  Only two things order consecutive passes: the sample
+// indices (k_generate reads what k_bump_issued of the pass before wrote) and the running means (k_accumulate of pass j
+// follows k_accumulate of pass j - 1, so the floating-point result is that of a serial run)
+// (the bug-compat mode keeps every pass on the main stream: a pass needs the first-hit state the pass before it left)
+// FH_FLAG_SERIAL_PASSES does the same for measurements: kernels then run alone on the GPU and their HIP-event spans are kernel times
+int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint32_t n_round, uint32_t coop_flush, int& last_slot)
+{
+  fh_ctx* const ctx = c.ctx;
+  const fh_ctx::Tunables& tun = ctx->tun;
+  const uint32_t n_px = px.n_px, n_paths = n_px * nb, max_depth = c.max_depth;
+  const bool serial = c.quirk || (ctx->flags & FH_FLAG_SERIAL_PASSES) != 0;
+  const int n_slots = serial ? 1 : ctx->n_slots;
+  Pass p{};
+  p.grid = grid_for(n_paths);
+  p.coop_flush = coop_flush;
+  p.slot = serial ? 0 : (int)(ctx->pass_seq % (unsigned long long)n_slots);
+  const int slot = p.slot, prev = serial ? ctx->last_slot_used : (slot + n_slots - 1) % n_slots;
+  ctx->pass_seq++;
+  ctx->stats.n_passes++;
+  ctx->last_slot_used = slot;
+  const hipStream_t st = p.st = slot ? ctx->aux_stream[slot - 1] : ctx->stream;
+  last_slot = slot;
+  // A call that is ONE pass (the reference's callers: 1 or 16 samples per call) has no other pass to share the GPU with, and its bounces are chains of launches that
+  // each end in a few long rays.  The secondary rays of bounce b and the closest-hit launch of bounce b + 1 do not depend on each other -- the secondary launch reads the
+  // secondary-ray records and adds to the radiance, the closest-hit launch and the routing read rays and write hits -- so the secondary launch goes to a second stream;
+  // the shade kernels of bounce b + 1, which overwrite the records it reads, wait for it.  (Calls of several passes overlap whole passes instead.)
+  p.single_pass = !serial && batch >= n_round && n_round == nb;
+  // ... or, where the streaming kernels trace the scene, both in ONE launch (k_trace_merged_stream): one end instead of two, no second stream (FH_MERGE=0: the two-stream form)
+  p.merge = p.single_pass && c.plan.stream && !c.count && tun.merge_trace;
+  p.overlap = p.single_pass && tun.overlap_secondary && !p.merge;
+  p.sb = st;
+  if (p.overlap) {
+    p.sb = (st == ctx->aux_stream[0]) ? ctx->aux_stream[1] : ctx->aux_stream[0];
+    while (ctx->ev_bounce.size() < 2u * (max_depth + 1u)) {
+      hipEvent_t e = nullptr;
+      FH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      ctx->ev_bounce.push_back(e);
+    }
+  }
+  // (The shade side of every bounce -- routing, shade kernels, queue sorts -- on a stream of its own, optionally of high priority, with the pass streams kept off some CUs,
+  // was measured in round 4 and is slower: r4-6, tools/patches/r6_pruned_switches.patch.)
+  { const int rc = pool_ensure(ctx, slot, n_px * batch); if (rc) return rc; }
+  const PoolDev& pool = ctx->pool[slot];
+  FH_HIP(hipMemsetAsync(pool.counters, 0, sizeof(uint32_t) * kCounterStride * (max_depth + 1), st));
+  p.sc = c.sc;
+  if (!start_at_faces(c, p.merge, p.probe)) { p.sc.bvh8.parent = nullptr; p.sc.face_node = nullptr; }
+  if (prev != slot && ctx->gen_valid[prev]) FH_HIP(hipStreamWaitEvent(st, ctx->ev_gen[prev], 0));
+  {
+    Span sp(ctx, st, 4);
+    hipLaunchKernelGGL(k_generate, dim3(grid_for((n_px + kGenChunks - 1) / kGenChunks), nb), dim3(kBlock), 0, st, c.fr, pool, ctx->d_sample_issued, px.px, px.xy, n_px);
+    hipLaunchKernelGGL(k_bump_issued, dim3((n_px + kBlock - 1) / kBlock), dim3(kBlock), 0, st, ctx->d_sample_issued, px.px, n_px, nb);
+    ctx->stats.n_generate_launches++;
+  }
+  FH_HIP(hipEventRecord(ctx->ev_gen[slot], st));
+  ctx->gen_valid[slot] = true;
+  ctx->stats.paths += n_paths;
+  // bounces run as bounce-synchronous wavefront kernels; the survivors are finished by k_tail.  Adaptive mode picks the
+  // first depth at which an earlier pass had at most tail_paths survivors (counts come from an asynchronous snapshot of
+  // the device counters: no host/device synchronisation)
+  // (a wavefront bounce costs two traversal launches, each as long as its longest ray whatever the number of rays, and a dozen small launches: 0.5 ms on the
+  // 1 M-triangle scene against 0.14 ms for a bounce inside the fused tail, so in a small pass the tail takes over earlier -- 1-spp 1080p frames: configs[2] 3.02 -> 2.73 ms
+  // at 128 Ki, configs[1] 1.90 -> 1.77 ms at 256 Ki; in a big pass the tail runs next to the streaming launches of the passes in flight, two waves per SIMD
+  // against their six, and more paths in it cost 0-1 %)
+  const uint32_t tail_paths = tun.tail_paths ? tun.tail_paths : (n_paths <= (1u << 22) ? 262144u : 65536u);
+  harvest_counters(ctx);
+  p.wave_depth = tail_wave_depth(ctx->survival, ctx->survival_n, n_paths, tail_paths, max_depth, ctx->tail_depth, tun.tail_depth, &ctx->auto_wave_depth);
+  PoolDev pd = pool, ps = pool;  // per-bounce views: pd rotates the radiance queues through the sorted buffers, ps reads the sorted secondary queue
+  uint32_t* q_spare = pool.q_tmp;
+  const uint32_t sort_blocks = n_paths / 16384u < 1u ? 1u : (n_paths / 16384u > 512u ? 512u : n_paths / 16384u);
+  for (uint32_t depth = 0; depth < p.wave_depth; ++depth) {
+    if (!(p.merge && depth > 0)) launch_closest(c, p, pd, depth);  // (merged launches: the closest-hit rays of this bounce were traced next to the secondary rays of the bounce before)
+    if (c.quirk && depth == 0) hipLaunchKernelGGL(k_firsthit_scan, dim3(grid_for(n_px)), dim3(kBlock), 0, st, pd, px.px, n_px, nb, ctx->d_quirk_seen);
+    {
+      Span sp(ctx, st, 6);
+      hipLaunchKernelGGL(k_route, dim3(p.grid), dim3(kBlock), 0, st, p.sc, pd, depth, ctx->n_classes, c.count ? ctx->d_trace_counters + 26 : nullptr);
+    }
+    if (p.overlap && depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (depth - 1u) + 1u], 0));  // the secondary launch of the bounce before reads what the shade kernels and the sorts below overwrite
+    {
+      Span sp(ctx, st, 2);
+      for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) dispatch_shade(st, p.grid, ctx->class_lobes[cls], p.sc, c.fr, pd, cls, depth, c.plan.shade_three);
+      if (depth == 0) hipLaunchKernelGGL(k_miss_primary, dim3(p.grid), dim3(kBlock), 0, st, c.fr, pd);
+      ctx->stats.n_shade_launches += ctx->n_classes;
+    }
+    sort_bounce_queues(c, p, pool, depth, sort_blocks, pd, ps, q_spare);
+    if (p.merge && depth + 1u < p.wave_depth) launch_merged(c, p, ps, pd, depth);
+    else {
+      if (p.overlap) { FH_HIP(hipEventRecord(ctx->ev_bounce[2u * depth], st)); FH_HIP(hipStreamWaitEvent(p.sb, ctx->ev_bounce[2u * depth], 0)); }
+      launch_secondary(c, p, ps, depth);
+    }
+    if (p.overlap) FH_HIP(hipEventRecord(ctx->ev_bounce[2u * depth + 1u], p.sb));
+  }
+  if (p.overlap && p.wave_depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (p.wave_depth - 1u) + 1u], 0));  // the tail and the accumulate read the radiance the last secondary launch completes
+  if (p.wave_depth < max_depth) launch_tail(c, p, pd, n_paths);
+  if (prev != slot && ctx->acc_valid[prev]) FH_HIP(hipStreamWaitEvent(st, ctx->ev_acc[prev], 0));
+  {
+    Span sp(ctx, st, 5);
+    if (c.quirk) hipLaunchKernelGGL((k_accumulate<true>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, c.L, px.px, n_px, nb, ctx->d_quirk_aov);
+    else if (c.adaptive) hipLaunchKernelGGL((k_accumulate<false, true>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, c.L, px.px, n_px, nb, ctx->d_moments);
+    else hipLaunchKernelGGL((k_accumulate<false>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, c.L, px.px, n_px, nb, (float4*)nullptr);
+    ctx->stats.n_accumulate_launches++;
+  }
+  FH_HIP(hipEventRecord(ctx->ev_acc[slot], st));
+  ctx->acc_valid[slot] = true;
+  if (!ctx->counters_in_flight[slot] && ctx->h_counters[slot]) {
+    FH_HIP(hipMemcpyAsync(ctx->h_counters[slot], pool.counters, sizeof(uint32_t) * kCounterStride * (max_depth + 1), hipMemcpyDeviceToHost, st));
+    FH_HIP(hipEventRecord(ctx->ev_counters[slot], st));
+    ctx->counters_in_flight[slot] = true;
+    ctx->counters_wave_depth[slot] = p.wave_depth;
+    ctx->counters_paths[slot] = n_paths;
+    ctx->counters_bu[slot] = p.probe;
+  }
+  return FH_OK;
+}
+
+// Adaptive mode, the start of a round of n_round samples: the pixels still active are selected from the call's base list.  The selection waits for the round before it
+// (wait_slot: the slot of its last pass, 0: the main stream itself or none), and its count, read back, sizes the passes of the round.
+int select_round(const Call& c, SkyLaunches& sky, const PixelLists& base, bool guard_blocks, int wait_slot, uint32_t n_round, PixelLists& act, bool& sky_ran)
+{
+  fh_ctx* const ctx = c.ctx;
+  if (wait_slot != 0) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[wait_slot], 0));
+  if (guard_blocks) sky.end();  // (the round's own sky launch: the next selection reads what it writes)
+  if (sky_ran && sky.st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky.st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
+  act.n_sky = 0;
+  const int rc = guard_blocks && base.n_sky ? adaptive_select(ctx, ctx->stream, base.px, base.xy, base.n_px, &act.n_px, ctx->d_split[2], ctx->d_split[3], base.n_sky, &act.n_sky)
+                                            : adaptive_select(ctx, ctx->stream, base.px, base.xy, base.n_px, &act.n_px);
+  if (rc) return rc;
+  act.px = ctx->d_active[0]; act.xy = ctx->d_active[1];
+  if (act.n_sky) {  // (the selection has been waited for, and with it the drain of the round before)
+    const int rc2 = sky.begin(ctx->d_active[2], ctx->d_active[3], act.n_sky, n_round);
+    if (rc2) return rc2;
+    ctx->sky_taken_pending = true;
+    sky_ran = true;
+  }
+  return FH_OK;
+}
+
+}  // namespace
+
+int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed)
+{
+  if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_render: scene not uploaded or BVH not built");
+  if (ctx->width == 0 || ctx->height == 0 || !ctx->d_sample_count) return fail(ctx, FH_E_INVALID, "fh_render: resolution not set");
+  if (max_depth > 64) return fail(ctx, FH_E_INVALID, "fh_render: max_depth > 64 is not supported");
+  if (ctx->n_owned == 0 || n_samples == 0) return FH_OK;
+  const bool adaptive = ctx->adaptive;
+  const bool guard_blocks = adaptive && ctx->adapt_block > 1u;  // (the sky pixels then follow their blocks: one k_sky_pixels launch per round, on the round's selection)
+  const bool quirk = (ctx->flags & FH_FLAG_REFERENCE_FIRSTHIT) != 0 && n_samples > 1;
+  if (adaptive && quirk)
+    return fail(ctx, FH_E_INVALID, "fh_render: FH_FLAG_REFERENCE_FIRSTHIT with n_samples > 1 does not combine with adaptive sampling (its first-hit state is per launch)");
+  ctx->accumulated = true;
+  cap_pool_target(ctx);
+
+  const bool count = (ctx->flags & FH_FLAG_COUNT_TRAVERSAL) != 0;
+  unsigned long long* const tc = ctx->d_trace_counters;
+  const bool clocks = (ctx->flags & FH_FLAG_TIME_KERNELS) != 0;
+  Call c{ctx, frame_dev(ctx, cam, bg, seed, max_depth), layers_dev(ctx, layers), SceneDev{},
+         TraceCounters{tc, tc + 1, tc + 2, tc + 6, tc + 7, tc + 10, clocks ? tc + 27 : nullptr}, TraceCounters{tc + 3, tc + 4, tc + 5, tc + 8, tc + 9, tc + 18, clocks ? tc + 29 : nullptr},
+         max_depth, adaptive, quirk, count, StreamPlan{}};
+  PixelLists base;  // the pixels of the call
+  { const int rc = choose_pixels(ctx, cam, c.fr, n_samples, quirk, base); if (rc) return rc; }
+  const uint32_t target = ctx->pool_target > ctx->n_owned ? ctx->pool_target : ctx->n_owned;
+  c.sc = scene_dev(ctx);
+  if (quirk) { const int rc = quirk_begin(ctx); if (rc) return rc; }
+  if (!ctx->render_pending) { (void)hipEventRecord(ctx->ev_render_begin, ctx->stream); ctx->render_pending = true; }
+  // whatever the caller queued on the main stream before this call (clears, uploads) comes first on the second stream too
+  FH_HIP(hipEventRecord(ctx->ev_enter, ctx->stream));
+  for (int k = 0; k + 1 < ctx->n_slots; ++k) FH_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->ev_enter, 0));
+  SkyLaunches sky(ctx, c.fr, c.L, adaptive);
+  if (base.n_sky && sky.st != ctx->stream) FH_HIP(hipStreamWaitEvent(sky.st, ctx->ev_enter, 0));
+  if (base.n_sky && !guard_blocks) {  // the sky pixels of this call, all samples at once (they share no pixel with the passes)
+    const int rc = sky.begin(ctx->d_split[2], ctx->d_split[3], base.n_sky, n_samples);
+    if (rc) return rc;
+    if (adaptive) ctx->sky_taken_pending = true;  // (the samples it takes are counted on the device: fh_sync adds them to the stats)
+    else {
+      ctx->stats.paths += (uint64_t)base.n_sky * n_samples;
+      ctx->stats.sky_pixel_samples += (uint64_t)base.n_sky * n_samples;
+    }
+  }
+  { const int rc = stream_plan(ctx, c.sc, count, base.n_sky && sky.filler_wgs, c.plan); if (rc) return rc; }
 
   // (Small calls -- the reference's callers: 1 sample per call in the GUI, controller.cpp:224, 16 in rtcamp8, rtcamp8.cpp:183-189 -- cut into PIXEL sub-passes, each a pass of
   // its own in its own pool on its own stream, were built and measured in round 5: slower, configs[3] 1 spp 6.45 -> 8.24 ms.  tools/patches/r6_pruned_switches.patch, r5-4.)
   // Rounds: a plain call is one.  In adaptive mode a round ends where the samples requested since fh_init_render_states are a multiple of `step`, and the pixels
   // still active are selected from the call's base list at the start of every round (a call that starts between two boundaries selects too: that only drops the
-  // pixels that stopped before).  The selection waits for the round before it, and its count, read back, sizes the passes of the round.
+  // pixels that stopped before; select_round).
   // (fh_set_adaptive_policy: with growth 2 a round runs to the next boundary b0 * 2^k, in as many passes as that takes.)
-  const uint32_t* const base_px = px_list;
-  const uint32_t* const base_xy = xy_list;
-  const uint32_t n_base = n_px;
+  PixelLists act = base;  // the pixels of the round; n_sky: the sky pixels the round's own selection left (guard blocks only)
+  act.n_sky = 0;
   bool ran = false, sky_ran = false;
+  int last_slot = 0;
   for (uint32_t call_done = 0; call_done < n_samples;) {
-  uint32_t n_round = n_samples - call_done, n_sky_round = 0;
-  if (adaptive) {
-    const uint32_t to_boundary = ctx->adapt_growth == 1u ? ctx->adapt.step - ctx->adapt_total % ctx->adapt.step : adaptive_to_boundary(ctx);
-    if (n_round > to_boundary) n_round = to_boundary;
-    if (ran && last_slot != 0) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
-    if (guard_blocks) sky_end();  // (the round's own sky launch: the next selection reads what it writes)
-    if (sky_ran && sky_st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky_st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
-    const int rc = guard_blocks && n_sky ? adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px, ctx->d_split[2], ctx->d_split[3], n_sky, &n_sky_round)
-                                         : adaptive_select(ctx, ctx->stream, base_px, base_xy, n_base, &n_px);
-    if (rc) return rc;
-    px_list = ctx->d_active[0]; xy_list = ctx->d_active[1];
-    if (n_sky_round) {  // (the selection has been waited for, and with it the drain of the round before)
-      const int rc2 = sky_begin(ctx->d_active[2], ctx->d_active[3], n_sky_round, n_round);
-      if (rc2) return rc2;
-      ctx->sky_taken_pending = true;
-      sky_ran = true;
+    uint32_t n_round = n_samples - call_done;
+    if (adaptive) {
+      const uint32_t to_boundary = ctx->adapt_growth == 1u ? ctx->adapt.step - ctx->adapt_total % ctx->adapt.step : adaptive_to_boundary(ctx);
+      if (n_round > to_boundary) n_round = to_boundary;
+      const int rc = select_round(c, sky, base, guard_blocks, ran ? last_slot : 0, n_round, act, sky_ran);
+      if (rc) return rc;
     }
-  }
-  const uint32_t batch = batch_for(n_px, n_round);
-  const uint32_t coop_flush = (!tun.coop_flush_fixed && batch >= n_round && !sc.has_alpha && tun.coop_flush > 32u) ? 32u : tun.coop_flush;
-  for (uint32_t done = 0; done < n_round && n_px; done += batch) {
-    const uint32_t nb = (n_round - done) < batch ? (n_round - done) : batch;
-    ran = true;
-    const uint32_t n_paths = n_px * nb;
-    const uint32_t grid = grid_for(n_paths);
-    // n_slots passes in flight (three by default, FH_PIPELINE): pass j lives in pool j % n_slots on the stream of that slot.  Only two things order consecutive passes: the sample
-    // indices (k_generate reads what k_bump_issued of the pass before wrote) and the running means (k_accumulate of pass j
-    // follows k_accumulate of pass j - 1, so the floating-point result is that of a serial run)
-    // (the bug-compat mode keeps every pass on the main stream: a pass needs the first-hit state the pass before it left)
-    // FH_FLAG_SERIAL_PASSES does the same for measurements: kernels then run alone on the GPU and their HIP-event spans are kernel times
-    const bool serial = quirk || (ctx->flags & FH_FLAG_SERIAL_PASSES) != 0;
-    const int n_slots = serial ? 1 : ctx->n_slots;
-    const int slot = serial ? 0 : (int)(ctx->pass_seq % (unsigned long long)n_slots), prev = serial ? ctx->last_slot_used : (slot + n_slots - 1) % n_slots;
-    ctx->pass_seq++;
-    ctx->stats.n_passes++;
-    ctx->last_slot_used = slot;
-    hipStream_t st = slot ? ctx->aux_stream[slot - 1] : ctx->stream;
-    last_slot = slot;
-    // A call that is ONE pass (the reference's callers: 1 or 16 samples per call) has no other pass to share the GPU with, and its bounces are chains of launches that
-    // each end in a few long rays.  The secondary rays of bounce b and the closest-hit launch of bounce b + 1 do not depend on each other -- the secondary launch reads the
-    // secondary-ray records and adds to the radiance, the closest-hit launch and the routing read rays and write hits -- so the secondary launch goes to a second stream;
-    // the shade kernels of bounce b + 1, which overwrite the records it reads, wait for it.  (Calls of several passes overlap whole passes instead.)
-    const bool single_pass = !serial && batch >= n_round && n_round == nb;
-    // ... or, where the streaming kernels trace the scene, both in ONE launch (k_trace_merged_stream): one end instead of two, no second stream (FH_MERGE=0: the two-stream form)
-    const bool merge = single_pass && stream && !count && tun.merge_trace;
-    const bool overlap = single_pass && tun.overlap_secondary && !merge;
-    hipStream_t sb = st;
-    if (overlap) {
-      sb = (st == ctx->aux_stream[0]) ? ctx->aux_stream[1] : ctx->aux_stream[0];
-      while (ctx->ev_bounce.size() < 2u * (max_depth + 1u)) {
-        hipEvent_t e = nullptr;
-        FH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->ev_bounce.push_back(e);
-      }
+    const uint32_t batch = samples_per_pass(target, act.n_px, n_round, (uint32_t)ctx->n_slots, quirk, (ctx->flags & FH_FLAG_SERIAL_PASSES) != 0);
+    // cooperative triangle tests: queued candidates that trigger a round.  48 (r5-12) -- but ONE-PASS calls of scenes without cut-outs keep 32
+    // (r5-13, profiles/r05_latency_defaults.log: the soup's fh_render(1 / 4 / 16) take 2.02 / 3.37 / 7.02 ms with 32 and 2.21 / 3.62 / 7.32 with 48 -- a launch of few rays
+    // waits longer for 48 candidates; the interior with cut-outs is 1 % faster with 48 there too).  FH_COOP_T fixes it for every call.
+    const uint32_t coop_flush = (!ctx->tun.coop_flush_fixed && batch >= n_round && !c.sc.has_alpha && ctx->tun.coop_flush > 32u) ? 32u : ctx->tun.coop_flush;
+    for (uint32_t done = 0; done < n_round && act.n_px; done += batch) {
+      ran = true;
+      const int rc = submit_pass(c, act, (n_round - done) < batch ? (n_round - done) : batch, batch, n_round, coop_flush, last_slot);
+      if (rc) return rc;
     }
-    // (The shade side of every bounce -- routing, shade kernels, queue sorts -- on a stream of its own, optionally of high priority, with the pass streams kept off some CUs,
-    // was measured in round 4 and is slower: r4-6, tools/patches/r6_pruned_switches.patch.)
-    hipStream_t sh = st;
-    { const int rc = pool_ensure(ctx, slot, n_px * batch); if (rc) return rc; }
-    const PoolDev& pool = ctx->pool[slot];
-    FH_HIP(hipMemsetAsync(pool.counters, 0, sizeof(uint32_t) * kCounterStride * (max_depth + 1), st));
-    // ---- where this pass's first-hit rays start their traversal (fh_trace.h: bottom-up start): forced by FH_BOTTOM_UP=0 / 1; else the first passes after a build alternate and
-    // the device's own count of test rounds per shaded path decides (above): a dense scene gains (1M-triangle soup: -12 %), an interior of long rays does not (-0.4 %)
-    int pass_bu = -1;  // -1: not a probing pass
-    bool use_bu = false;
-    if (sc_all.bvh8.parent && stream && (ctx->flags & FH_FLAG_ROOT_START) == 0u) {
-      if (tun.bottom_up == 1u) use_bu = true;
-      else if (tun.bottom_up == 2u) {
-        // (only a pass whose secondary launch can climb is a probe: the merged launch of a one-pass call walks from the root whatever the pass says and counts no test
-        // rounds, so counting it would fill one side of the comparison with cost 0 and fix the choice at "root" -- the reference's 1- and 16-sample calls come first in a GUI)
-        if (ctx->bu_choice == 0 && !count && !merge && !sc_all.has_alpha) { use_bu = (ctx->bu_toggle++ & 1u) != 0u; pass_bu = use_bu ? 1 : 0; }
-        else use_bu = ctx->bu_choice == 2;
-      }
-    }
-    SceneDev sc = sc_all;
-    if (!use_bu) { sc.bvh8.parent = nullptr; sc.face_node = nullptr; }
-    if (prev != slot && ctx->gen_valid[prev]) FH_HIP(hipStreamWaitEvent(st, ctx->ev_gen[prev], 0));
-    {
-      Span sp(ctx, st, 4);
-      hipLaunchKernelGGL(k_generate, dim3(grid_for((n_px + kGenChunks - 1) / kGenChunks), nb), dim3(kBlock), 0, st, fr, pool, ctx->d_sample_issued, px_list, xy_list, n_px);
-      hipLaunchKernelGGL(k_bump_issued, dim3((n_px + kBlock - 1) / kBlock), dim3(kBlock), 0, st, ctx->d_sample_issued, px_list, n_px, nb);
-      ctx->stats.n_generate_launches++;
-    }
-    FH_HIP(hipEventRecord(ctx->ev_gen[slot], st));
-    ctx->gen_valid[slot] = true;
-    ctx->stats.paths += n_paths;
-    // bounces run as bounce-synchronous wavefront kernels; the survivors are finished by k_tail.  Adaptive mode picks the
-    // first depth at which an earlier pass had at most kTailPaths survivors (counts come from an asynchronous snapshot of
-    // the device counters: no host/device synchronisation)
-    // (a wavefront bounce costs two traversal launches, each as long as its longest ray whatever the number of rays, and a dozen small launches: 0.5 ms on the
-    // 1 M-triangle scene against 0.14 ms for a bounce inside the fused tail, so in a small pass the tail takes over earlier -- 1-spp 1080p frames: configs[2] 3.02 -> 2.73 ms
-    // at 128 Ki, configs[1] 1.90 -> 1.77 ms at 256 Ki; in a big pass the tail runs next to the streaming launches of the passes in flight, two waves per SIMD
-    // against their six, and more paths in it cost 0-1 %)
-    const uint32_t kTailPaths = tun.tail_paths ? tun.tail_paths : (n_paths <= (1u << 22) ? 262144u : 65536u);
-    for (int k = 0; k < 3; ++k) {
-      if (!(ctx->counters_in_flight[k] && hipEventQuery(ctx->ev_counters[k]) == hipSuccess)) continue;
-      ctx->counters_in_flight[k] = false;
-      const uint32_t wd = ctx->counters_wave_depth[k];
-      const uint32_t* hc = ctx->h_counters[k];
-      if (ctx->counters_paths[k]) {  // the share of the pass's paths alive at each depth it ran as a wavefront (context.h: survival)
-        const uint32_t n = wd < 65u ? wd : 65u;
-        for (uint32_t d = 0; d <= n; ++d) ctx->survival[d] = (double)hc[d * kCounterStride + CNT_RAD] / (double)ctx->counters_paths[k];
-        if (ctx->survival_n < n + 1u) ctx->survival_n = n + 1u;  // (a pass the tail took over early says nothing about the deeper shares: what an earlier pass of this scene measured stays)
-      }
-      if (ctx->counters_bu[k] >= 0 && ctx->bu_choice == 0) {  // (a pass of the scene's probing phase: what its secondary launches cost, by the issue model's weights)
-        double cost = 0.0, items = 0.0;
-        for (uint32_t d = 0; d < wd; ++d) { cost += 510.0 * hc[d * kCounterStride + CNT_COST_NODE] + 175.0 * hc[d * kCounterStride + CNT_COST_TRI]; items += hc[d * kCounterStride + CNT_SEC]; }
-        ctx->bu_cost[ctx->counters_bu[k]] += cost; ctx->bu_items[ctx->counters_bu[k]] += items;
-        if (ctx->bu_items[0] >= 65536.0 && ctx->bu_items[1] >= 65536.0) {
-          const double off = ctx->bu_cost[0] / ctx->bu_items[0], on = ctx->bu_cost[1] / ctx->bu_items[1];
-          ctx->bu_choice = on < 0.95 * off ? 2 : 1;
-          if (getenv("FH_DEBUG_BVH")) fprintf(stderr, "[trace] rays that leave a surface start at %s: %.0f against %.0f SIMD cycles of tests per shaded path (from the root / from the face)\n", ctx->bu_choice == 2 ? "the node of their face" : "the root", off, on);
-        }
-      }
-      ctx->counters_bu[k] = -1;
-      if (tun.debug_tail) { fprintf(stderr, "[tail] slot %d wd %u paths %u survivors:", k, wd, ctx->counters_paths[k]); for (uint32_t d = 0; d <= wd; ++d) fprintf(stderr, " %u", ctx->h_counters[k][d * kCounterStride + CNT_RAD]); fprintf(stderr, "\n"); }
-    }
-    // the first depth at which THIS pass is expected to have at most kTailPaths survivors
-    {
-      uint32_t pick = 0;
-      if (!ctx->survival_n) pick = n_paths > (1u << 22) ? max_depth : 2u;  // (nothing known: a big pass runs without the tail -- a wavefront bounce of few paths costs it 0.5 ms, a tail of millions of paths seconds)
-      else {
-        const uint32_t known = ctx->survival_n - 1u;
-        for (uint32_t d = 1; d <= known && !pick; ++d)
-          if ((double)n_paths * ctx->survival[d] <= (double)kTailPaths) pick = d;
-        if (!pick) {
-          // too many survivors even at the last depth counted: extrapolate with the survival ratio of the last bounce.  (Snapshots only
-          // arrive when the host happens to be behind the GPU -- after a synchronisation -- so the depth has to be right in one step.)
-          const double last = (double)n_paths * ctx->survival[known], prev = known ? (double)n_paths * ctx->survival[known - 1u] : 0.0;
-          uint32_t more = 1;
-          if (last > 0.0 && prev > last) {
-            const double steps = ceil(log((double)kTailPaths / last) / log(last / prev));
-            more = steps < 1.0 ? 1u : (steps > 16.0 ? 16u : (uint32_t)steps);
-          }
-          pick = known + more;
-        }
-      }
-      ctx->auto_wave_depth = pick;
-    }
-    uint32_t wave_depth = ctx->tail_depth ? ctx->tail_depth : ctx->auto_wave_depth;
-    if (env_tail_depth) wave_depth = env_tail_depth;
-    if (wave_depth < 1u) wave_depth = 1u;
-    if (wave_depth > max_depth) wave_depth = max_depth;
-    PoolDev pd = pool, ps = pool;  // per-bounce views: pd rotates the radiance queues through the sorted buffers, ps reads the sorted secondary queue
-    uint32_t* q_spare = pool.q_tmp;
-    const uint32_t sort_blocks = n_paths / 16384u < 1u ? 1u : (n_paths / 16384u > 512u ? 512u : n_paths / 16384u);
-    for (uint32_t depth = 0; depth < wave_depth; ++depth) {
-      if (!(merge && depth > 0)) {  // (merged launches: the closest-hit rays of this bounce were traced next to the secondary rays of the bounce before)
-        Span sp(ctx, st, 0);
-        if (stream) {
-          with_bool(count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_trace_closest_stream<decltype(C)::value, decltype(A)::value>), dim3(grid < stream_grid ? grid : stream_grid), dim3(kBlock), stream_stack_bytes, st, sc, pd, depth, tc_closest,
-                               coop_flush, stream_refill, stream_chunk_closest, tun.stream_min_rays, StackSpill{spill_entries ? ctx->d_stack_spill + (size_t)(2 * slot) * spill_region : nullptr, stream_entries});
-          }); });
-        } else if (coop) {
-          with_bool(count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_trace_closest_coop<decltype(C)::value, decltype(A)::value>), dim3(grid), dim3(kBlock), stack_bytes, st, sc, pd, depth, tc_closest, coop_flush);
-          }); });
-        } else {
-          with_bool(count, [&](auto C) { with_bool(sc.use_bvh8 != 0, [&](auto W) { with_bool(sc.has_alpha != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_trace_closest_static<decltype(C)::value, decltype(W)::value, decltype(A)::value>), dim3(grid), dim3(kBlock), 0, st, sc, pd, depth, tc_closest);
-          }); }); });
-        }
-        ctx->stats.n_closest_launches++;
-      }
-      if (quirk && depth == 0) hipLaunchKernelGGL(k_firsthit_scan, dim3(grid_for(n_px)), dim3(kBlock), 0, st, pd, px_list, n_px, nb, ctx->d_quirk_seen);
-      {
-        Span sp(ctx, sh, 6);
-        hipLaunchKernelGGL(k_route, dim3(grid), dim3(kBlock), 0, sh, sc, pd, depth, ctx->n_classes, count ? ctx->d_trace_counters + 26 : nullptr);
-      }
-      if (overlap && depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (depth - 1u) + 1u], 0));  // the secondary launch of the bounce before reads what the shade kernels and the sorts below overwrite
-      {
-        Span sp(ctx, sh, 2);
-        for (uint32_t c = 0; c < ctx->n_classes; ++c) dispatch_shade(sh, grid, ctx->class_lobes[c], sc, fr, pd, c, depth, shade_three);
-        if (depth == 0) hipLaunchKernelGGL(k_miss_primary, dim3(grid), dim3(kBlock), 0, sh, fr, pd);
-        ctx->stats.n_shade_launches += ctx->n_classes;
-      }
-      {
-        Span sp(ctx, sh, 6);
-        // secondary rays of this bounce and the radiance rays of the next one, each into cell order.  ONE-PASS calls (r6-7): the order buys their launches nothing -- every
-        // line they touch is touched for the first time whatever the order -- and the six sort launches per bounce are pure chain: 4- and 16-sample calls of configs[3] are
-        // 3 % / 2 % faster without them; only the queue the fused tail takes over keeps its order (FH_SORT_ONEPASS=1: all, =0: none)
-        const bool tail_next = depth + 1u == wave_depth && wave_depth < max_depth;
-        const bool sort_sec = sort_queues && (!single_pass || tun.sort_onepass == 1u);
-        const bool sort_rad = sort_queues && (!single_pass || tun.sort_onepass == 1u || (tun.sort_onepass == 2u && tail_next));
-        ps = pd;
-        if (sort_sec) {
-          sort_queue_by_cell(sh, sort_blocks, pool.counters + depth * kCounterStride + CNT_SEC, pool.q_sec, pool.key_sec, pool.bins, pool.q_sec_sorted);
-          ps.q_sec = pool.q_sec_sorted;
-        }
-        if (sort_rad) {
-          const uint32_t nxt = (depth + 1u) & 1u;
-          sort_queue_by_cell(sh, sort_blocks, pool.counters + (depth + 1u) * kCounterStride + CNT_RAD, pd.q_rad[nxt], pool.key_rad, pool.bins, q_spare);
-          uint32_t* const unsorted = pd.q_rad[nxt];
-          pd.q_rad[nxt] = q_spare;  // the next bounce reads the sorted queue ...
-          q_spare = unsorted;       // ... and the buffer it came from is the next scratch target
-        }
-      }
-      if (merge && depth + 1u < wave_depth) {
-        Span sp(ctx, st, 1);
-        with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
-          hipLaunchKernelGGL((k_trace_merged_stream<decltype(Li)::value, decltype(A)::value>), dim3(grid < stream_grid_secondary ? grid : stream_grid_secondary), dim3(kBlock), stream_stack_bytes_secondary, st, sc,
-                             fr, ps, pd, depth, tc_shadow, coop_flush, stream_refill, stream_chunk, tun.stream_min_rays,
-                             StackSpill{spill_entries_secondary ? ctx->d_stack_spill + (size_t)(2 * slot + 1) * spill_region : nullptr, stream_entries_secondary, pass_bu >= 0 ? 1u : 0u});
-        }); });
-        ctx->stats.n_shadow_launches++;
-        ctx->stats.n_closest_launches++;
-      } else {
-        if (overlap) { FH_HIP(hipEventRecord(ctx->ev_bounce[2u * depth], st)); FH_HIP(hipStreamWaitEvent(sb, ctx->ev_bounce[2u * depth], 0)); }
-        Span sp(ctx, sb, 1);
-        if (stream) {
-          with_bool(count, [&](auto C) { with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>), dim3(grid < stream_grid_secondary ? grid : stream_grid_secondary), dim3(kBlock), stream_stack_bytes_secondary, sb, sc,
-                               fr, ps, depth, tc_shadow, coop_flush, stream_refill, stream_chunk, tun.stream_min_rays,
-                               StackSpill{spill_entries_secondary ? ctx->d_stack_spill + (size_t)(2 * slot + 1) * spill_region : nullptr, stream_entries_secondary, pass_bu >= 0 ? 1u : 0u});
-          }); }); });
-        } else if (coop) {
-          with_bool(count, [&](auto C) { with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_trace_secondary_coop<decltype(C)::value, decltype(Li)::value, decltype(A)::value>), dim3(grid), dim3(kBlock), stack_bytes, sb, sc, fr, ps, depth, tc_shadow,
-                               coop_flush);
-          }); }); });
-        } else {
-          with_bool(count, [&](auto C) { with_bool(sc.use_bvh8 != 0, [&](auto W) { with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
-            hipLaunchKernelGGL((k_trace_secondary_static<decltype(C)::value, decltype(W)::value, decltype(Li)::value, decltype(A)::value>), dim3(grid), dim3(kBlock), stack_bytes, sb, sc, fr, ps,
-                               depth, tc_shadow);
-          }); }); }); });
-        }
-        ctx->stats.n_shadow_launches++;
-      }
-      if (overlap) FH_HIP(hipEventRecord(ctx->ev_bounce[2u * depth + 1u], sb));
-    }
-    if (overlap && wave_depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (wave_depth - 1u) + 1u], 0));  // the tail and the accumulate read the radiance the last secondary launch completes
-    if (wave_depth < max_depth) {
-      Span sp(ctx, st, 3);
-      uint32_t lobes = 0;  // every lobe a material of the scene can have: the tail shades all classes in one kernel
-      for (uint32_t c = 0; c < ctx->n_classes; ++c) lobes |= ctx->class_lobes[c];
-      const dim3 tg(grid_for(n_paths / 16 + 1)), tb(kBlock);
-      const uint32_t tl = sc.use_bvh8 ? stack_bytes : 0u, tf = coop ? coop_flush : 0u;
-      if ((lobes & ~(uint32_t)L_DIFF) == 0) hipLaunchKernelGGL(k_tail<L_DIFF>, tg, tb, tl, st, sc, fr, pd, wave_depth, tf);
-      else if ((lobes & ~(uint32_t)(L_METAL | L_SPEC | L_DIFF)) == 0) hipLaunchKernelGGL((k_tail<L_METAL | L_SPEC | L_DIFF>), tg, tb, tl, st, sc, fr, pd, wave_depth, tf);
-      else if ((lobes & ~(uint32_t)(L_COAT | L_METAL | L_SPEC | L_DIFF)) == 0) hipLaunchKernelGGL((k_tail<L_COAT | L_METAL | L_SPEC | L_DIFF>), tg, tb, tl, st, sc, fr, pd, wave_depth, tf);
-      else hipLaunchKernelGGL(k_tail<L_ALL>, tg, tb, tl, st, sc, fr, pd, wave_depth, tf);
-      ctx->stats.n_tail_launches++;
-    }
-    if (prev != slot && ctx->acc_valid[prev]) FH_HIP(hipStreamWaitEvent(st, ctx->ev_acc[prev], 0));
-    {
-      Span sp(ctx, st, 5);
-      if (quirk) hipLaunchKernelGGL((k_accumulate<true>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, ctx->d_quirk_aov);
-      else if (adaptive) hipLaunchKernelGGL((k_accumulate<false, true>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, ctx->d_moments);
-      else hipLaunchKernelGGL((k_accumulate<false>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, L, px_list, n_px, nb, (float4*)nullptr);
-      ctx->stats.n_accumulate_launches++;
-    }
-    FH_HIP(hipEventRecord(ctx->ev_acc[slot], st));
-    ctx->acc_valid[slot] = true;
-    if (!ctx->counters_in_flight[slot] && ctx->h_counters[slot]) {
-      FH_HIP(hipMemcpyAsync(ctx->h_counters[slot], pool.counters, sizeof(uint32_t) * kCounterStride * (max_depth + 1), hipMemcpyDeviceToHost, st));
-      FH_HIP(hipEventRecord(ctx->ev_counters[slot], st));
-      ctx->counters_in_flight[slot] = true;
-      ctx->counters_wave_depth[slot] = wave_depth;
-      ctx->counters_paths[slot] = n_paths;
-      ctx->counters_bu[slot] = pass_bu;
-    }
-  }
-  call_done += n_round;
-  ctx->adapt_total += n_round;
-  if (adaptive && n_px == 0 && n_sky_round == 0) { ctx->adapt_total += n_samples - call_done; break; }  // (the active set only shrinks: no later round has a pixel)
+    call_done += n_round;
+    ctx->adapt_total += n_round;
+    if (adaptive && act.n_px == 0 && act.n_sky == 0) { ctx->adapt_total += n_samples - call_done; break; }  // (the active set only shrinks: no later round has a pixel)
   }
   // join: later work on the main stream (pack, post-process, copies, the caller's clears) sees every pass of this call
   // (the accumulates form a chain across the streams, so the last one implies all the others)
   if (last_slot != 0 && ran) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
-  sky_end();
-  if (n_sky && sky_st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky_st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
+  sky.end();
+  if (base.n_sky && sky.st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky.st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
   FH_HIP(hipGetLastError());
   return FH_OK;
 }

@@ -620,6 +620,54 @@ def test_large_one_pass_calls_of_the_bug_compat_and_measuring_modes_are_not_spli
     assert not _same(frames["plain"], frames["quirk"])
 
 
+def test_launch_bookkeeping_of_the_dispatch_paths(request, monkeypatch):
+    """What a pass launches, by fh_stats, on every path the submit code takes (render.hip: submit_pass and its launch steps): a call of ONE pass (the merged launch where the
+    streaming kernels trace the scene, else the secondary launch on a second stream), a call of three passes in flight, and the same three one after the other
+    (FH_FLAG_SERIAL_PASSES).  The Cornell box is a small tree -- the fixed-batch kernels; the soup under FH_STREAM=1 takes the streaming kernels (the file's two runs of
+    every test choose the scene).  With a fixed tail depth of 2 of max_depth 4 nothing depends on when a counter snapshot arrives; per pass: one generate, one accumulate,
+    one fused tail, two closest-hit and two secondary launches (merged, the second closest-hit launch rides with the first secondary one and is still counted) and two shade
+    launches per shading class.  How a call is cut never changes a bit of the frame."""
+    w, h, depth = 64, 48, 4
+    for k in ("FH_PIPELINE", "FH_MERGE", "FH_OVERLAP", "FH_TAIL_DEPTH", "FH_SKY_SPLIT_MIN_LOG2"):  # (developer switches that change what a pass launches)
+        monkeypatch.delenv(k, raising=False)
+    if request.node.callspec.params["traversal_kernels"] == "stream":
+        sc, cam = scenes.triangle_soup(24000, 0.06), F.Camera(**scenes.SOUP_CAMERA)
+        assert os.environ.get("FH_STREAM") == "1"
+    else:
+        sc, cam = scenes.cornell_box(), F.Camera(**scenes.CORNELL_CAMERA)
+    frames = {}
+    for mode, flags, pool, spp, passes in (("one_pass", 0, None, 1, 1), ("in_flight", 0, w * h * 2, 6, 3), ("serial", N.FLAG_SERIAL_PASSES, w * h * 2, 6, 3)):
+        r = F.Renderer(0)
+        if pool:
+            r.set_path_pool(pool)
+        r.load_scene(sc)
+        r.build_ias()
+        r.set_resolution(w, h)
+        r.set_tail_depth(2)
+        L = F.RenderLayer(r, w, h)
+        r.set_flags(flags)
+        n_classes = 0
+        while n_classes < 64:
+            try:
+                r.kernel_info(2 + n_classes)
+            except F.FredholmError:
+                break
+            n_classes += 1
+        assert n_classes >= 1
+        r.reset_stats()
+        r.render(cam, (0.1, 0.2, 0.4), L, spp, depth)
+        r.wait_for_completion()
+        st = r.stats()
+        frames[mode] = L.download("beauty")
+        r.close()
+        got = {k: st[k] for k in ("n_passes", "n_generate_launches", "n_accumulate_launches", "n_tail_launches", "n_closest_launches", "n_shadow_launches", "n_shade_launches", "paths")}
+        want = {"n_passes": passes, "n_generate_launches": passes, "n_accumulate_launches": passes, "n_tail_launches": passes, "n_closest_launches": 2 * passes,
+                "n_shadow_launches": 2 * passes, "n_shade_launches": 2 * n_classes * passes, "paths": w * h * spp}
+        assert got == want, (mode, got, want)
+    assert _same(frames["in_flight"], frames["serial"])
+    assert not _same(frames["one_pass"], frames["serial"])  # (1 sample against 6: the calls did render)
+
+
 @pytest.mark.parametrize("start", ["auto", "face"])
 def test_moving_instances_refit_the_tree_and_match_checker_and_rebuild(oracle, monkeypatch, start):
     """(start = "face": the streaming kernels forced, first-hit rays forced to start at the node of the face they leave -- the start node rides in the face records, which
