@@ -17,6 +17,9 @@
 //                                         this step needs the luminance moments, so without --noise-threshold it does nothing;
 //                                         --denoise-temporal-moments, with every temporal* denoiser: the history also keeps the luminance moments, and a frame without
 //                                         --noise-threshold takes its per-pixel variance from them once a pixel's history is H frames long (default 2))
+//          [--auto-exposure [--exposure-key K] [--exposure-comp EV] [--exposure-speed UP DOWN] [--bloom-relative]]   (the tone map's exposure is metered from every frame's
+//                                         luminance histogram in place of ISO: the mean log2 luminance of the middle ranks is mapped to K (default 0.18), shifted by EV stops, and
+//                                         followed at UP / DOWN per second (default 3 / 1) with a frame time of 1 / fps; --bloom-relative: the bloom threshold compares exposed luminance)
 //          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
 #include <chrono>
 #include <cmath>
@@ -55,6 +58,9 @@ int main(int argc, char** argv)
   bool temporal_moments = false;         // --denoise-temporal-moments (with a temporal* denoiser only)
   float denoise_min_history = 2.0f;      // --denoise-min-history (with --denoise-temporal-moments only)
   bool min_history_given = false;
+  bool auto_exposure = false, bloom_relative = false;  // --auto-exposure, --bloom-relative
+  AutoExposureParams exposure;                         // --exposure-key, --exposure-comp, --exposure-speed (with --auto-exposure only)
+  const char* exposure_flag = nullptr;                 // the first of those flags that was given
   std::vector<int> devices;  // --devices: empty = FH_DEVICES, or device 0
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -85,12 +91,17 @@ int main(int argc, char** argv)
     else if (a == "--denoise-kappa") { denoise_kappa = float(std::atof(next())); kappa_given = true; }
     else if (a == "--denoise-temporal-moments") temporal_moments = true;
     else if (a == "--denoise-min-history") { denoise_min_history = float(std::atof(next())); min_history_given = true; }
+    else if (a == "--auto-exposure") auto_exposure = true;
+    else if (a == "--exposure-key") { exposure.key = float(std::atof(next())); if (!exposure_flag) exposure_flag = "--exposure-key"; }
+    else if (a == "--exposure-comp") { exposure.compensation_ev = float(std::atof(next())); if (!exposure_flag) exposure_flag = "--exposure-comp"; }
+    else if (a == "--exposure-speed") { exposure.speed_up = float(std::atof(next())); exposure.speed_down = float(std::atof(next())); if (!exposure_flag) exposure_flag = "--exposure-speed"; }
+    else if (a == "--bloom-relative") { bloom_relative = true; if (!exposure_flag) exposure_flag = "--bloom-relative"; }
     else if (a == "--devices") {
       try { devices = cwl::parse_device_list(next(), "--devices"); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]] [--devices 0,1,...]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]] [--auto-exposure [--exposure-key K] [--exposure-comp EV] [--exposure-speed UP DOWN] [--bloom-relative]] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   if (adaptive_block != 1 && adaptive_block != 2 && adaptive_block != 4 && adaptive_block != 8) { std::fprintf(stderr, "--adaptive-block must be 1, 2, 4 or 8\n"); return 2; }
   if (adaptive_growth != 1 && adaptive_growth != 2) { std::fprintf(stderr, "--adaptive-growth must be 1 or 2\n"); return 2; }
@@ -106,6 +117,11 @@ int main(int argc, char** argv)
   if (!(denoise_min_history >= 1.0f) || !std::isfinite(denoise_min_history)) { std::fprintf(stderr, "--denoise-min-history must be finite and >= 1\n"); return 2; }
   if (temporal_moments && !temporal) { std::fprintf(stderr, "--denoise-temporal-moments goes with a temporal --denoiser\n"); return 2; }
   if (min_history_given && !temporal_moments) { std::fprintf(stderr, "--denoise-min-history goes with --denoise-temporal-moments\n"); return 2; }
+  if (exposure_flag && !auto_exposure) { std::fprintf(stderr, "%s goes with --auto-exposure\n", exposure_flag); return 2; }
+  if (!(exposure.key > 0.0f) || !std::isfinite(exposure.key)) { std::fprintf(stderr, "--exposure-key must be finite and > 0\n"); return 2; }
+  if (!std::isfinite(exposure.compensation_ev)) { std::fprintf(stderr, "--exposure-comp must be finite\n"); return 2; }
+  if (!(exposure.speed_up >= 0.0f) || !std::isfinite(exposure.speed_up) || !(exposure.speed_down >= 0.0f) || !std::isfinite(exposure.speed_down)) { std::fprintf(stderr, "--exposure-speed takes two finite rates >= 0\n"); return 2; }
+  if (auto_exposure && !(fps > 0.0f)) { std::fprintf(stderr, "--auto-exposure needs --fps > 0\n"); return 2; }
   const bool guided = denoiser_name == "guided" || temporal;  // (temporal: the same guides)
   const float time_step = 1.0f / fps;
   try {
@@ -153,6 +169,11 @@ int main(int argc, char** argv)
     }
     fredholm::RenderLayer render_layer{layer_beauty.get_device_ptr(), layer_position.get_device_ptr(), layer_depth.get_device_ptr(), layer_normal.get_device_ptr(),
                                        layer_texcoord.get_device_ptr(), layer_albedo.get_device_ptr()};
+    if (auto_exposure) {
+      exposure.frame_time = time_step;
+      exposure.bloom_relative = bloom_relative;
+      set_auto_exposure(&exposure);
+    }
     if (sun) renderer.set_directional_light(make_float3(20, 20, 20), make_float3(-0.1f, 1, 0.1f), 1.0f);  // rtcamp8.cpp:133-134
     if (sky) renderer.load_arhosek_sky(3.0f, 0.3f);                                                       // rtcamp8.cpp:137
     if (!ibl.empty()) renderer.load_ibl(ibl);

@@ -12,6 +12,7 @@
 
 #include "context.h"
 #include "fh_bsdf.h"
+#include "fh_meter.h"
 #include "fh_trace.h"
 #include "motion_host.h"
 #include "temporal_host.h"
@@ -619,7 +620,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
   pool_release(ctx);
   void* ptrs[] = {ctx->d_sample_issued, ctx->d_sobol, ctx->d_sobol_bytes, ctx->d_alpha_rec, ctx->d_lut_refl, ctx->d_lut_sheen, ctx->d_face_rec, ctx->d_face_cls, ctx->d_materials, ctx->d_lights, ctx->d_bvh2_nodes, ctx->d_bvh2_tris,
                   ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_sample_count, ctx->d_owned, ctx->d_trace_counters, ctx->d_texels, ctx->d_textures, ctx->d_srgb_lut, ctx->d_ibl,
-                  ctx->d_bloom_weights, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
+                  ctx->d_bloom_weights, ctx->d_meter, ctx->d_meter_slabs, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
                   ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hist_cv[0], ctx->d_hist_cv[1], ctx->d_hist_ph[0], ctx->d_hist_ph[1], ctx->d_hist_n[0], ctx->d_hist_n[1], ctx->d_hist_mu[0], ctx->d_hist_mu[1], ctx->d_motion, ctx->d_motion_ids, ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
                   ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active[2], ctx->d_active[3], ctx->d_block_marks, ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
   for (void* p : ptrs)
@@ -1267,6 +1268,60 @@ int fh_post_process(fh_ctx* ctx, const float* in, float* hi, float* tmp, int w, 
   CTX_CHECK(ctx);
   if (!in || !hi || !tmp || !out || !pp || w <= 0 || h <= 0) return fail(ctx, FH_E_INVALID, "fh_post_process: bad argument");
   return post_process_submit(ctx, in, hi, tmp, w, h, pp, out);
+}
+
+// auto-exposure of the post chain (post.hip, fh_meter.h).  Every refusal of the parameters is decided before the context is looked at; on a group all of it lives
+// and runs on the lead, as fh_post_process does
+int fh_set_auto_exposure(fh_ctx* ctx, const fh_auto_exposure_params* params)
+{
+  if (const char* why = auto_exposure_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_auto_exposure: ") + why);
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  return auto_exposure_set(ctx, params);
+}
+
+int fh_get_auto_exposure(fh_ctx* ctx, int* on, fh_auto_exposure_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->auto_exposure;
+  if (params) *params = ctx->ae_params;
+  return FH_OK;
+}
+
+int fh_auto_exposure_reset(fh_ctx* ctx)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!ctx->auto_exposure) return fail(ctx, FH_E_INVALID, "fh_auto_exposure_reset: auto-exposure is off (fh_set_auto_exposure)");
+  return auto_exposure_reset(ctx);
+}
+
+int fh_meter_exposure(fh_ctx* ctx, const float* image_rgba, uint32_t width, uint32_t height)
+{
+  if (!image_rgba || width == 0 || height == 0 || width > 32768 || height > 32768) return fail(ctx, FH_E_INVALID, "fh_meter_exposure: needs an image of 1 .. 32768 pixels each way");
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!ctx->auto_exposure) return fail(ctx, FH_E_INVALID, "fh_meter_exposure: auto-exposure is off (fh_set_auto_exposure)");
+  return meter_submit(ctx, image_rgba, width, height);
+}
+
+int fh_get_auto_exposure_state(fh_ctx* ctx, fh_auto_exposure_state* state)
+{
+  if (!state) return fail(ctx, FH_E_INVALID, "fh_get_auto_exposure_state: null argument");
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!ctx->auto_exposure) return fail(ctx, FH_E_INVALID, "fh_get_auto_exposure_state: auto-exposure is off (fh_set_auto_exposure)");
+  return auto_exposure_read(ctx, state, nullptr);
+}
+
+int fh_get_luminance_histogram(fh_ctx* ctx, uint32_t hist[257])
+{
+  if (!hist) return fail(ctx, FH_E_INVALID, "fh_get_luminance_histogram: null argument");
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!ctx->auto_exposure) return fail(ctx, FH_E_INVALID, "fh_get_luminance_histogram: auto-exposure is off (fh_set_auto_exposure)");
+  return auto_exposure_read(ctx, nullptr, hist);
 }
 
 int fh_denoise(fh_ctx* ctx, uint32_t width, uint32_t height, const float* beauty, const float* normal, const float* albedo, float* denoised, int upscale2x)

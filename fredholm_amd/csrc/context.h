@@ -229,6 +229,14 @@ struct fh_ctx {
   float* d_bloom_weights = nullptr;
   float bloom_sigma_cached = -1.0f, bloom_wsum = 0.0f;
 
+  // fh_set_auto_exposure (post.hip: k_meter_histogram, k_meter_resolve, k_tone_map_metered).  d_meter: the state, the exposure word and the summed histogram
+  // (post.hip: MeterDev), allocated when the switch first goes on; d_meter_slabs: 257 words per workgroup of the metering launch, grown on demand
+  int auto_exposure = 0;
+  fh_auto_exposure_params ae_params = {0.18f, 0.0f, -16.0f, 16.0f, 0.10f, 0.90f, 3.0f, 1.0f, 1.0f / 30.0f, -16.0f, 16.0f, 0u};
+  void* d_meter = nullptr;
+  uint32_t* d_meter_slabs = nullptr;
+  uint32_t meter_slab_blocks = 0;
+
   // denoiser slot (post.hip): ping-pong buffers of the a-trous filter
   float4* d_denoise_tmp[2] = {nullptr, nullptr};
   size_t denoise_pixels = 0;
@@ -327,6 +335,11 @@ uint64_t pool_bytes_per_path(const fh_ctx* ctx);            // capi.hip
 void pool_release(fh_ctx* ctx);
 int kernel_info(fh_ctx* ctx, int which, uint32_t out[6]);   // render.hip
 int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int w, int h, const fh_post_params* pp, float* out);  // post.hip
+// post.hip, auto-exposure (arguments checked by the caller): the switch with its device state; metering + resolve of one image; frames = 0; synchronising read-backs
+int auto_exposure_set(fh_ctx* ctx, const fh_auto_exposure_params* params);
+int meter_submit(fh_ctx* ctx, const float* image, uint32_t w, uint32_t h);
+int auto_exposure_reset(fh_ctx* ctx);
+int auto_exposure_read(fh_ctx* ctx, fh_auto_exposure_state* state, uint32_t* hist);
 int denoise_submit(fh_ctx* ctx, int w, int h, const float* beauty, const float* normal, const float* albedo, float* out, int upscale);  // post.hip
 int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* params, float* out, int upscale);  // denoise.hip (arguments checked by the caller)
 // denoise.hip (arguments checked by the caller); w2c, inv_tan: `cam` inverted and its cam_inv_tan, kept with the history this call writes

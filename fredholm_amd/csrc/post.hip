@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "context.h"
+#include "fh_meter.h"
 #include "fh_tonemap.h"
 
 namespace fh {
@@ -85,6 +86,156 @@ __global__ void __launch_bounds__(256) k_tone_map(const float4* in, int w, int h
 
 
 // ------------------------------------------------------------------------------------------------
+// Auto-exposure (fh_set_auto_exposure; the arithmetic is fh_meter.h's and stated in include/fredholm_hip.h).  No counterpart in the reference.
+// k_meter_histogram counts every pixel of the input in one of 256 log2-luminance bins (word 256: unmetered) and leaves one 257-word slab per workgroup;
+// k_meter_resolve sums the slabs, runs the serial resolve in one lane and writes the state and the exposure word; the metered forms of the threshold and the tone
+// map read that word from device memory, so nothing comes back to the host between the metering and the chain.
+constexpr int kMeterThreads = 256, kMeterWaves = kMeterThreads / 64, kMeterMaxBlocks = 512, kMeterLoads = 4, kResolveThreads = 1024;
+
+struct MeterDev {
+  fh_auto_exposure_state st;
+  float exposure;              // fhe_pow(2, st.ev); valid while st.frames != 0
+  uint32_t hist[kMeterWords];  // of the last metering call
+};
+
+// one count per valid lane into the wave's own histogram.  A wave's 64 pixels are neighbours and mostly share a bin (sky, a black background, a wall): in up to two
+// rounds the lanes that agree with the first pending lane are counted by that lane with one plain add; what is left after that goes through LDS atomics.
+// Called by whole waves (`valid` carries the image bound).
+__device__ __forceinline__ void meter_count(uint32_t* h, int bin, bool valid)
+{
+  const int lane = (int)(threadIdx.x & 63u);
+  for (int k = 0; k < 2; ++k) {
+    const unsigned long long todo = __ballot(valid);
+    if (todo == 0ull) return;
+    const int leader = __ffsll((long long)todo) - 1;
+    const int b0 = __shfl(bin, leader);
+    const bool same = valid && bin == b0;
+    const unsigned long long m = __ballot(same);
+    if (lane == leader) h[b0] += (uint32_t)__popcll(m);
+    if (same) valid = false;
+  }
+  if (valid) atomicAdd(&h[bin], 1u);
+}
+
+__global__ void __launch_bounds__(kMeterThreads) k_meter_histogram(const float4* in, uint32_t n, float log2_lo, float scale, uint32_t* slabs)
+{
+  __shared__ uint32_t s_h[kMeterWaves * kMeterWords];
+  for (int k = threadIdx.x; k < kMeterWaves * kMeterWords; k += kMeterThreads) s_h[k] = 0u;
+  __syncthreads();
+  uint32_t* h = s_h + (threadIdx.x >> 6) * kMeterWords;
+  const uint32_t stride = gridDim.x * (uint32_t)kMeterThreads;  // n <= 2^30 and kMeterLoads * stride <= 2^19: no index below wraps
+  for (uint32_t base = blockIdx.x * (uint32_t)kMeterThreads; base < n; base += (uint32_t)kMeterLoads * stride) {  // (the trip count is the workgroup's: meter_count sees whole waves)
+    float4 p[kMeterLoads];
+    bool v[kMeterLoads];
+#pragma unroll
+    for (int k = 0; k < kMeterLoads; ++k) {  // all loads are issued before the first is used
+      const uint32_t i = base + (uint32_t)k * stride + threadIdx.x;
+      v[k] = i < n;
+      p[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (v[k]) p[k] = in[i];
+    }
+#pragma unroll
+    for (int k = 0; k < kMeterLoads; ++k) meter_count(h, meter_bin(p[k].x, p[k].y, p[k].z, log2_lo, scale), v[k]);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < kMeterWords; k += kMeterThreads) {
+    uint32_t c = 0u;
+    for (int wv = 0; wv < kMeterWaves; ++wv) c += s_h[wv * kMeterWords + k];
+    slabs[(size_t)blockIdx.x * kMeterWords + k] = c;
+  }
+}
+
+// one workgroup.  The slabs are summed by all lanes (integers: any order); the count before each bin comes from a scan, so the bins' terms of S are formed one per
+// lane; what has to be serial -- the sum of the 256 doubles in bin order, and the state -- is left to one lane
+__global__ void __launch_bounds__(kResolveThreads) k_meter_resolve(const uint32_t* slabs, uint32_t n_slabs, MeterConsts mc, MeterDev* md)
+{
+  constexpr int kParts = kResolveThreads / kMeterBins, kInFlight = 16;
+  __shared__ uint32_t s_part[kParts * kMeterBins];
+  __shared__ uint32_t s_scan[2][kMeterBins];
+  __shared__ double s_term[kMeterBins];
+  __shared__ uint32_t s_unmetered;
+  const int t = threadIdx.x & (kMeterBins - 1), q = threadIdx.x / kMeterBins;
+  if (threadIdx.x == 0) s_unmetered = 0u;
+  __syncthreads();
+  // lane (q, t) sums bin t of the slabs q, q + kParts, ...: kInFlight independent loads at a time (one workgroup reads all slabs, so this loop is bound by latency)
+  uint32_t acc = 0u;
+  for (uint32_t b = q; b < n_slabs; b += (uint32_t)(kInFlight * kParts)) {
+    uint32_t x[kInFlight];
+#pragma unroll
+    for (int k = 0; k < kInFlight; ++k) {
+      const uint32_t c = b + (uint32_t)(k * kParts);
+      x[k] = c < n_slabs ? slabs[(size_t)c * kMeterWords + t] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < kInFlight; ++k) acc += x[k];
+  }
+  s_part[q * kMeterBins + t] = acc;
+  uint32_t u = 0u;  // word 256 of every slab: one slab per lane and round
+  for (uint32_t c = threadIdx.x; c < n_slabs; c += (uint32_t)kResolveThreads) u += slabs[(size_t)c * kMeterWords + kMeterBins];
+  if (u != 0u) atomicAdd(&s_unmetered, u);
+  __syncthreads();
+  if (q == 0) {
+    uint32_t c = 0u;
+    for (int r = 0; r < kParts; ++r) c += s_part[r * kMeterBins + t];
+    s_part[t] = c;
+    s_scan[0][t] = c;
+    md->hist[t] = c;
+    if (t == 0) md->hist[kMeterBins] = s_unmetered;
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int d = 1; d < kMeterBins; d <<= 1) {  // inclusive scan of the 256 counts
+    if (q == 0) s_scan[cur ^ 1][t] = s_scan[cur][t] + (t >= d ? s_scan[cur][t - d] : 0u);
+    cur ^= 1;
+    __syncthreads();
+  }
+  const uint32_t n = s_scan[cur][kMeterBins - 1];
+  if (n == 0u) return;  // nothing metered: the state is left alone (uniform: no barrier follows for some lanes only)
+  uint32_t cut, end;
+  meter_cuts(n, mc.low, mc.high, &cut, &end);
+  if (q == 0) s_term[t] = meter_term(meter_kept(s_scan[cur][t] - s_part[t], s_part[t], cut, end), t, mc.log2_lo, mc.scale);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < kMeterBins; ++k) s += s_term[k];
+    fh_auto_exposure_state st = md->st;
+    meter_update(n, s_unmetered, s, cut, end, mc, &st);
+    md->st = st;
+    md->exposure = meter_exposure(st.ev);
+  }
+}
+
+// k_bloom_threshold with the pixel's luminance scaled by the metered exposure (FH_AE_BLOOM_RELATIVE); iso_exposure: what it uses until a frame has been metered
+__global__ void __launch_bounds__(256) k_bloom_threshold_metered(const float4* in, int w, int gw, int gh, float threshold, const MeterDev* md, float iso_exposure, float4* out)
+{
+  const int i = blockIdx.x * kT + threadIdx.x, j = blockIdx.y * kT + threadIdx.y;
+  if (i >= gw || j >= gh) return;
+  const float exposure = md->st.frames != 0u ? md->exposure : iso_exposure;
+  const float4 b = in[i + w * j];
+  const float l = b.x * 0.2126729f + b.y * 0.7151522f + b.z * 0.0721750f;
+  out[i + w * j] = l * exposure > threshold ? b : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// k_tone_map with the exposure word read from device memory
+__global__ void __launch_bounds__(256) k_tone_map_metered(const float4* in, int w, int h, int gw, int gh, const MeterDev* md, float iso_exposure, float ca, float4* out)
+{
+  const int i = blockIdx.x * kT + threadIdx.x, j = blockIdx.y * kT + threadIdx.y;
+  if (i >= gw || j >= gh) return;
+  const float exposure = md->st.frames != 0u ? md->exposure : iso_exposure;
+  const float uvx = (float)i / w, uvy = (float)j / h;
+  const float inv = 1.0f / (float)(w * h);
+  const float dx = (uvx - 0.5f) * inv * ca, dy = (uvy - 0.5f) * inv * ca;
+  const float rx = clamp01f(uvx - 0.0f * dx), ry = clamp01f(uvy - 0.0f * dy);
+  const float gx = clamp01f(uvx - 1.0f * dx), gy = clamp01f(uvy - 1.0f * dy);
+  const float bx = clamp01f(uvx - 2.0f * dx), by = clamp01f(uvy - 2.0f * dy);
+  const int ir = (int)(rx * w + w * (ry * h)), ig = (int)(gx * w + w * (gy * h)), ib = (int)(bx * w + w * (by * h));
+  float r = in[ir].x, g = in[ig].y, b = in[ib].z;
+  r *= exposure; g *= exposure; b *= exposure;
+  r = srgb1(uchimura1(r)); g = srgb1(uchimura1(g)); b = srgb1(uchimura1(b));
+  out[i + w * j] = make_float4(r, g, b, 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Denoiser slot.  The reference calls NVIDIA's OptiX AI denoiser (fredholm/include/fredholm/denoiser.h:14-146: HDR model, albedo + normal
 // guides, optional 2x upscale) -- a proprietary network with no counterpart here and nothing to be bit-compatible with.  What fills the slot is
 // the classic guided filter it replaced in many renderers: the edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010)
@@ -151,8 +302,17 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
   const int bx = w / kT > 1 ? w / kT : 1, by = h / kT > 1 ? h / kT : 1;  // floor division, post-process.cu:9-11
   const int gw = bx * kT < w ? bx * kT : w, gh = by * kT < h ? by * kT : h;
   const dim3 grid(bx, by), block(kT, kT);
+  // fh_set_auto_exposure: metering -> resolve -> the chain, all on the stream; the chain's metered kernels read what the resolve wrote
+  const bool metered = ctx->auto_exposure != 0;
+  const MeterDev* md = (const MeterDev*)ctx->d_meter;
+  const float exposure = exposure_from_ev100(ev100_of(1.0f, 1.0f, pp->ISO));
+  if (pp->use_bloom && (w < kT || h < kT)) return fail(ctx, FH_E_UNSUPPORTED, "bloom needs an image of at least 16x16 pixels");
+  if (metered) {
+    if (w > 32768 || h > 32768) return fail(ctx, FH_E_INVALID, "fh_post_process: auto-exposure meters images of at most 32768 x 32768 pixels");
+    const int rc = meter_submit(ctx, in, (uint32_t)w, (uint32_t)h);
+    if (rc != FH_OK) return rc;
+  }
   if (pp->use_bloom) {
-    if (w < kT || h < kT) return fail(ctx, FH_E_UNSUPPORTED, "bloom needs an image of at least 16x16 pixels");
     // the 1089 weights depend on bloom_sigma only: computed and uploaded when sigma changes, kept in the context otherwise
     // (no allocation, copy or host synchronisation per frame)
     if (!ctx->d_bloom_weights) FH_HIP(hipMalloc((void**)&ctx->d_bloom_weights, 33 * 33 * sizeof(float)));
@@ -171,15 +331,68 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
       ctx->bloom_sigma_cached = pp->bloom_sigma;
       ctx->bloom_wsum = wsum;
     }
-    hipLaunchKernelGGL(k_bloom_threshold, grid, block, 0, st, (const float4*)in, w, gw, gh, pp->bloom_threshold, (float4*)hi);
+    if (metered && (ctx->ae_params.flags & FH_AE_BLOOM_RELATIVE)) hipLaunchKernelGGL(k_bloom_threshold_metered, grid, block, 0, st, (const float4*)in, w, gw, gh, pp->bloom_threshold, md, exposure, (float4*)hi);
+    else hipLaunchKernelGGL(k_bloom_threshold, grid, block, 0, st, (const float4*)in, w, gw, gh, pp->bloom_threshold, (float4*)hi);
     hipLaunchKernelGGL(k_bloom_blur, grid, block, 0, st, (const float4*)in, (const float4*)hi, w, h, ctx->d_bloom_weights, ctx->bloom_wsum, (float4*)tmp);
   } else {
     hipLaunchKernelGGL(k_copy, grid, block, 0, st, (const float4*)in, w, gw, gh, (float4*)tmp);
   }
-  const float exposure = exposure_from_ev100(ev100_of(1.0f, 1.0f, pp->ISO));
-  hipLaunchKernelGGL(k_tone_map, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, exposure, pp->chromatic_aberration, (float4*)out);
+  if (metered) hipLaunchKernelGGL(k_tone_map_metered, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, md, exposure, pp->chromatic_aberration, (float4*)out);
+  else hipLaunchKernelGGL(k_tone_map, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, exposure, pp->chromatic_aberration, (float4*)out);
   if (timed) { (void)hipEventRecord(ev_b, st); ctx->spans.push_back({ev_a, ev_b, 7}); ctx->stats.n_post_launches++; }
   FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// ---- auto-exposure, host side
+int auto_exposure_set(fh_ctx* ctx, const fh_auto_exposure_params* params)
+{
+  if (!params) {
+    if (ctx->d_meter) FH_HIP(hipMemsetAsync(ctx->d_meter, 0, sizeof(MeterDev), ctx->stream));  // the state is dropped; the allocation is kept for the next switch-on
+    ctx->auto_exposure = 0;
+    return FH_OK;
+  }
+  if (!ctx->d_meter) FH_HIP(hipMalloc(&ctx->d_meter, sizeof(MeterDev)));
+  if (!ctx->auto_exposure) FH_HIP(hipMemsetAsync(ctx->d_meter, 0, sizeof(MeterDev), ctx->stream));  // off -> on: frames = 0; on -> on keeps the state
+  ctx->auto_exposure = 1;
+  ctx->ae_params = *params;
+  return FH_OK;
+}
+
+int meter_submit(fh_ctx* ctx, const float* image, uint32_t w, uint32_t h)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t n = w * h;  // w, h <= 32768
+  const uint32_t per_block = (uint32_t)(kMeterLoads * kMeterThreads);
+  uint32_t blocks = (n + per_block - 1u) / per_block;
+  blocks = blocks < 1u ? 1u : (blocks > (uint32_t)kMeterMaxBlocks ? (uint32_t)kMeterMaxBlocks : blocks);
+  if (ctx->meter_slab_blocks < blocks) {  // grows on demand, never per frame
+    FH_HIP(hipStreamSynchronize(st));     // an earlier call may still use the old slabs
+    if (ctx->d_meter_slabs) (void)hipFree(ctx->d_meter_slabs);
+    ctx->d_meter_slabs = nullptr; ctx->meter_slab_blocks = 0;
+    FH_HIP(hipMalloc((void**)&ctx->d_meter_slabs, (size_t)blocks * kMeterWords * sizeof(uint32_t)));
+    ctx->meter_slab_blocks = blocks;
+  }
+  const MeterConsts mc = meter_consts(ctx->ae_params);
+  hipLaunchKernelGGL(k_meter_histogram, dim3(blocks), dim3(kMeterThreads), 0, st, (const float4*)image, n, mc.log2_lo, mc.scale, ctx->d_meter_slabs);
+  hipLaunchKernelGGL(k_meter_resolve, dim3(1), dim3(kResolveThreads), 0, st, (const uint32_t*)ctx->d_meter_slabs, blocks, mc, (MeterDev*)ctx->d_meter);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int auto_exposure_reset(fh_ctx* ctx)
+{
+  FH_HIP(hipMemsetAsync(&((MeterDev*)ctx->d_meter)->st.frames, 0, sizeof(uint32_t), ctx->stream));
+  return FH_OK;
+}
+
+int auto_exposure_read(fh_ctx* ctx, fh_auto_exposure_state* state, uint32_t* hist)
+{
+  MeterDev host;
+  FH_HIP(hipMemcpyAsync(&host, ctx->d_meter, sizeof(MeterDev), hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  if (state) *state = host.st;
+  if (hist) for (int k = 0; k < kMeterWords; ++k) hist[k] = host.hist[k];
   return FH_OK;
 }
 

@@ -116,6 +116,7 @@ EXPORTS = [
     "fh_primary_instances", "fh_motion_from_transforms", "fh_denoise_temporal_motion", "fh_set_denoise_motion", "fh_get_denoise_motion", "fh_kat_chief_rays",
     "fh_set_denoise_response", "fh_get_denoise_response", "fh_set_denoise_response_noise", "fh_get_denoise_response_noise",
     "fh_set_denoise_temporal_moments", "fh_get_denoise_temporal_moments",
+    "fh_set_auto_exposure", "fh_get_auto_exposure", "fh_auto_exposure_reset", "fh_meter_exposure", "fh_get_auto_exposure_state", "fh_get_luminance_histogram",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -161,6 +162,20 @@ class TemporalMomentsParamsC(C.Structure):
     _fields_ = [("min_history", C.c_float)]
 
 
+AE_BLOOM_RELATIVE = 1  # FH_AE_BLOOM_RELATIVE
+
+
+class AutoExposureParamsC(C.Structure):
+    """fh_auto_exposure_params (include/fredholm_hip.h)"""
+    _fields_ = [("key", C.c_float), ("compensation_ev", C.c_float), ("min_ev", C.c_float), ("max_ev", C.c_float), ("low", C.c_float), ("high", C.c_float),
+                ("speed_up", C.c_float), ("speed_down", C.c_float), ("frame_time", C.c_float), ("log2_lo", C.c_float), ("log2_hi", C.c_float), ("flags", C.c_uint32)]
+
+
+class AutoExposureStateC(C.Structure):
+    """fh_auto_exposure_state (include/fredholm_hip.h)"""
+    _fields_ = [("ev", C.c_float), ("target_ev", C.c_float), ("mean_log2", C.c_float), ("metered", C.c_uint32), ("unmetered", C.c_uint32), ("frames", C.c_uint32)]
+
+
 # argument types of the entry points declared with them (the adaptive-sampling ABI); every entry point returns int
 SIGNATURES = {
     "fh_set_adaptive_sampling": [C.c_void_p, C.POINTER(AdaptiveParamsC)],
@@ -188,6 +203,12 @@ SIGNATURES = {
     "fh_get_denoise_response_noise": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(ResponseNoiseParamsC)],
     "fh_set_denoise_temporal_moments": [C.c_void_p, C.POINTER(TemporalMomentsParamsC)],
     "fh_get_denoise_temporal_moments": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(TemporalMomentsParamsC)],
+    "fh_set_auto_exposure": [C.c_void_p, C.POINTER(AutoExposureParamsC)],
+    "fh_get_auto_exposure": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(AutoExposureParamsC)],
+    "fh_auto_exposure_reset": [C.c_void_p],
+    "fh_meter_exposure": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
+    "fh_get_auto_exposure_state": [C.c_void_p, C.POINTER(AutoExposureStateC)],
+    "fh_get_luminance_histogram": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_kat_chief_rays": [C.c_void_p, C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_void_p],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],

@@ -514,6 +514,46 @@ class Renderer:
         self._ck(N.lib().fh_post_process(self._ctx, C.c_void_p(beauty_in_ptr), C.c_void_p(high_ptr), C.c_void_p(temp_ptr), int(width), int(height), C.byref(pp), C.c_void_p(beauty_out_ptr)),
                  "fh_post_process")
 
+    # -- auto-exposure of the post chain (fh_set_auto_exposure)
+    def set_auto_exposure(self, key=0.18, compensation_ev=0.0, min_ev=-16.0, max_ev=16.0, low=0.10, high=0.90, speed_up=3.0, speed_down=1.0, frame_time=1.0 / 30.0,
+                          log2_lo=-16.0, log2_hi=16.0, bloom_relative=False):
+        """fh_set_auto_exposure: while on, post_process meters its input into a 256-bin log2-luminance histogram, maps the mean of the ranks between `low` and `high`
+        to `key`, moves ev = log2(exposure) towards that target at speed_up / speed_down per second (frame_time seconds per call; inf: no adaptation) and tone-maps
+        with 2^ev in place of the ISO exposure.  bloom_relative: the bloom threshold compares exposed luminance.  Turning it on starts from frames = 0"""
+        p = N.AutoExposureParamsC(float(key), float(compensation_ev), float(min_ev), float(max_ev), float(low), float(high), float(speed_up), float(speed_down), float(frame_time),
+                                  float(log2_lo), float(log2_hi), N.AE_BLOOM_RELATIVE if bloom_relative else 0)
+        self._ck(N.lib().fh_set_auto_exposure(self._ctx, C.byref(p)), "fh_set_auto_exposure")
+
+    def clear_auto_exposure(self):
+        """off; the state is dropped"""
+        self._ck(N.lib().fh_set_auto_exposure(self._ctx, None), "fh_set_auto_exposure")
+
+    def get_auto_exposure(self):
+        """(on, parameters as a dict): the switch and the parameters last set (the defaults before any)"""
+        on, p = C.c_int(0), N.AutoExposureParamsC()
+        self._ck(N.lib().fh_get_auto_exposure(self._ctx, C.byref(on), C.byref(p)), "fh_get_auto_exposure")
+        return bool(on.value), {k: getattr(p, k) for k, _ in p._fields_}
+
+    def auto_exposure_state(self):
+        """the state after everything queued so far (synchronising): ev, target_ev, mean_log2, metered, unmetered, frames"""
+        s = N.AutoExposureStateC()
+        self._ck(N.lib().fh_get_auto_exposure_state(self._ctx, C.byref(s)), "fh_get_auto_exposure_state")
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def auto_exposure_reset(self):
+        """frames = 0: the next metered frame sets ev = target"""
+        self._ck(N.lib().fh_auto_exposure_reset(self._ctx), "fh_auto_exposure_reset")
+
+    def meter_exposure(self, image_ptr, width, height):
+        """fh_meter_exposure: meter a device image of width * height float4 and update the state (asynchronous); what post_process does first while the switch is on"""
+        self._ck(N.lib().fh_meter_exposure(self._ctx, C.c_void_p(image_ptr), C.c_uint32(int(width)), C.c_uint32(int(height))), "fh_meter_exposure")
+
+    def luminance_histogram(self):
+        """the 257 counts of the last metering call (synchronising); [256] = unmetered pixels"""
+        h = (C.c_uint32 * 257)()
+        self._ck(N.lib().fh_get_luminance_histogram(self._ctx, h), "fh_get_luminance_histogram")
+        return np.frombuffer(h, dtype=np.uint32).copy()
+
     def denoise(self, width, height, beauty_ptr, normal_ptr, albedo_ptr, denoised_ptr, upscale=False):
         """the denoiser slot (Denoiser::denoise, denoiser.h:87-95): edge-avoiding a-trous filter guided by the normal and albedo layers"""
         self._ck(N.lib().fh_denoise(self._ctx, C.c_uint32(int(width)), C.c_uint32(int(height)), C.c_void_p(beauty_ptr), C.c_void_p(normal_ptr), C.c_void_p(albedo_ptr),

@@ -526,6 +526,60 @@ int fh_set_denoise_temporal_moments(fh_ctx* ctx, const fh_temporal_moments_param
 /* *on = 0 or 1; params (may be NULL) receives the min_history last set (the default before any) */
 int fh_get_denoise_temporal_moments(fh_ctx* ctx, int* on, fh_temporal_moments_params* params);
 
+/* -- auto-exposure of the post chain: histogram metering and adaptation (opt-in, default off; with it off fh_post_process keeps its bits and its launches).
+ * fh_post_params stays as it is: the feature is a switch on the context.  While it is on, every fh_post_process call first meters its input (fh_meter_exposure), and
+ * its tone map multiplies by exposure = fhe_pow(2, ev) of the context's state in place of the exposure ISO gives; until a frame has been metered (frames == 0: an
+ * input with no pixel of positive luminance) the ISO exposure is used.  Everything is queued on the context stream: no host synchronisation.
+ * All of it is fp32 without contraction, / correctly rounded, sums in the order written, unless noted; finite() and lum() are fh_denoise_inputs' (above);
+ * fhe_log2, fhe_exp, fhe_pow: include/fh_elementary.h.  On the host: scale = 256.0f / (log2_hi - log2_lo), log2key = fhe_log2(key),
+ * a_up = 1 - fhe_exp(-frame_time * speed_up), a_down likewise with speed_down; both are exactly 1 for an infinite frame_time.
+ *   Metering, over ALL width * height pixels of the input (not the floor-division grid of the tone map: the metering describes the scene):
+ *     l = lum(finite(r), finite(g), finite(b)).  The pixel is UNMETERED when !(l > 0) and counts in word [256]; otherwise it counts in
+ *     bin = clamp((int)floorf((fhe_log2(l) - log2_lo) * scale), 0, 255)  (the clamp is applied to the float, so every finite log2_lo is defined).
+ *     The counts are integers: the histogram does not depend on the order the pixels are visited in.
+ *   Resolve, once per metering call:
+ *     N = sum of hist[0 .. 255].  N == 0: the state is left alone, whole.
+ *     cut = (uint32)((double)N * (double)low),  end = (uint32)((double)N * (double)high);  if end <= cut: end = min(cut + 1, N), cut = end - 1.
+ *     For b = 0 .. 255 in ascending order, c0 the count in the bins before b, h = hist[b]:  kept = max(0, min(c0 + h, end) - max(c0, cut)),
+ *       centre_b = ((float)b + 0.5f) / scale + log2_lo,  S += (double)kept * (double)centre_b   (S a double, summed serially; the product and the sum rounded separately).
+ *     mean_log2 = (float)(S / (double)(end - cut)).
+ *     target = fmaxf(min_ev, fminf((log2key - mean_log2) + compensation_ev, max_ev)).
+ *     frames == 0: ev = target.  Otherwise a = target > ev ? a_up : a_down and ev = ev + (target - ev) * a.
+ *     target_ev = target, metered = N, unmetered = hist[256], frames += 1.
+ *   Chain: the tone map is fh_post_process's with r, g, b multiplied by fhe_pow(2.0f, ev).  With FH_AE_BLOOM_RELATIVE the bloom threshold passes a pixel when
+ *     l * exposure > bloom_threshold (l = r * 0.2126729 + g * 0.7151522 + b * 0.0721750 as that kernel computes it), with the ISO exposure while frames == 0;
+ *     without the flag the threshold compares scene luminance as it always did.
+ * Not covered: metering of tile shards before a gather (the input is a whole frame on one device), spatial (centre-weighted) metering, local tone mapping. */
+#define FH_AE_BLOOM_RELATIVE 1u
+typedef struct fh_auto_exposure_params {
+  float key;               /* 0.18: the value the metered mean luminance is mapped to */
+  float compensation_ev;   /* 0 */
+  float min_ev, max_ev;    /* -16, 16: clamp of ev = log2(exposure) */
+  float low, high;         /* 0.10, 0.90: share of metered pixels below / up to which ranks are kept */
+  float speed_up, speed_down; /* 3, 1 (1/s): rate while the exposure rises / falls */
+  float frame_time;        /* 1/30 s per metering call; +inf = no adaptation (ev = target) */
+  float log2_lo, log2_hi;  /* -16, 16: range of the 256 bins */
+  uint32_t flags;          /* FH_AE_BLOOM_RELATIVE = 1 */
+} fh_auto_exposure_params;
+typedef struct fh_auto_exposure_state { float ev, target_ev, mean_log2; uint32_t metered, unmetered, frames; } fh_auto_exposure_state;
+/* params == NULL: off, and the state is dropped.  A call that turns the switch on starts from frames = 0; one that changes the parameters of a switch that is on keeps
+ * the state.  On a group the switch lives on the lead, where fh_post_process runs.  FH_E_INVALID, decided from the arguments alone before the context is looked at and
+ * each with its own message: a key that is not finite or <= 0; a non-finite compensation_ev, min_ev, max_ev, log2_lo or log2_hi; min_ev > max_ev;
+ * log2_hi - log2_lo not in (0, 64]; low or high outside [0, 1], or low >= high; a speed that is not finite or < 0; a frame_time that is NaN or < 0; unknown flag
+ * bits.  A refused call leaves the switch, the parameters and the state alone. */
+int fh_set_auto_exposure(fh_ctx* ctx, const fh_auto_exposure_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the parameters last set (the defaults above before any) */
+int fh_get_auto_exposure(fh_ctx* ctx, int* on, fh_auto_exposure_params* params);
+/* frames = 0: the next metered frame sets ev = target.  Asynchronous, on the context stream.  FH_E_INVALID while the switch is off */
+int fh_auto_exposure_reset(fh_ctx* ctx);
+/* meters image_rgba (a device pointer, width * height float4) and resolves: asynchronous, on the context stream; what fh_post_process runs first while the switch
+ * is on.  FH_E_INVALID, from the arguments alone: a null image, width or height 0 or above 32768; and while the switch is off */
+int fh_meter_exposure(fh_ctx* ctx, const float* image_rgba, uint32_t width, uint32_t height);
+/* synchronising: the state after everything queued so far.  FH_E_INVALID while the switch is off */
+int fh_get_auto_exposure_state(fh_ctx* ctx, fh_auto_exposure_state* state);
+/* synchronising: the histogram of the last metering call (all zero before any); hist[256] = unmetered pixels.  FH_E_INVALID while the switch is off */
+int fh_get_luminance_histogram(fh_ctx* ctx, uint32_t hist[257]);
+
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */
 int fh_gl_register_buffer(fh_ctx* ctx, unsigned int gl_buffer, void** resource, void** device_ptr, uint64_t* bytes);

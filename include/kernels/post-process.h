@@ -1,6 +1,12 @@
 // kernels/post-process.h -- PostProcessParams + post_process_kernel_launch with the reference's signature
 // (fredholm/kernels/include/kernels/post-process.h:4-10, :126-128), forwarding to fh_post_process.
+// Beyond the reference: auto-exposure (fh_set_auto_exposure), a switch on the process-wide context, so post_process_kernel_launch keeps its signature.
 #pragma once
+#include <cstdlib>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
 #include "../cwl/util.h"
 #include "../fredholm/types.h"
 
@@ -12,11 +18,71 @@ struct PostProcessParams {
   float chromatic_aberration;
 };
 
+// fh_auto_exposure_params with the library's defaults
+struct AutoExposureParams {
+  float key = 0.18f;
+  float compensation_ev = 0.0f;
+  float min_ev = -16.0f, max_ev = 16.0f;
+  float low = 0.10f, high = 0.90f;
+  float speed_up = 3.0f, speed_down = 1.0f;
+  float frame_time = 1.0f / 30.0f;  // seconds per post_process_kernel_launch; infinity: no adaptation
+  float log2_lo = -16.0f, log2_hi = 16.0f;
+  bool bloom_relative = false;      // FH_AE_BLOOM_RELATIVE
+};
+
+namespace fh_post_detail
+{
+// the environment variable FH_AUTO_EXPOSURE has been looked at, or the application has set the switch itself (which wins)
+inline bool& auto_exposure_decided()
+{
+  static bool decided = false;
+  return decided;
+}
+}  // namespace fh_post_detail
+
+// nullptr: off.  Throws what fh_set_auto_exposure refuses
+inline void set_auto_exposure(const AutoExposureParams* params)
+{
+  fh_post_detail::auto_exposure_decided() = true;
+  fh_ctx* ctx = cwl::require_context();
+  if (!params) { cwl::check(ctx, fh_set_auto_exposure(ctx, nullptr), "fh_set_auto_exposure"); return; }
+  const fh_auto_exposure_params p{params->key, params->compensation_ev, params->min_ev, params->max_ev, params->low, params->high, params->speed_up, params->speed_down,
+                                  params->frame_time, params->log2_lo, params->log2_hi, params->bloom_relative ? FH_AE_BLOOM_RELATIVE : 0u};
+  cwl::check(ctx, fh_set_auto_exposure(ctx, &p), "fh_set_auto_exposure");
+}
+inline fh_auto_exposure_state get_auto_exposure_state()
+{
+  fh_ctx* ctx = cwl::require_context();
+  fh_auto_exposure_state s{};
+  cwl::check(ctx, fh_get_auto_exposure_state(ctx, &s), "fh_get_auto_exposure_state");
+  return s;
+}
+inline void reset_auto_exposure()
+{
+  fh_ctx* ctx = cwl::require_context();
+  cwl::check(ctx, fh_auto_exposure_reset(ctx), "fh_auto_exposure_reset");
+}
+
 inline void post_process_kernel_launch(const float4* beauty_in, float4* beauty_high_luminance, float4* beauty_temp, int width, int height, const PostProcessParams& params,
                                        float4* beauty_out)
 {
   fh_post_params p{params.use_bloom ? 1 : 0, params.bloom_threshold, params.bloom_sigma, params.ISO, params.chromatic_aberration};
   fh_ctx* ctx = cwl::require_context();
+  // FH_AUTO_EXPOSURE, read once, gives applications that know nothing of the switch the feature (as FH_DENOISER does for the denoiser): "1" = the defaults,
+  // any other number = that key, "0" or unset = off
+  if (!fh_post_detail::auto_exposure_decided()) {
+    fh_post_detail::auto_exposure_decided() = true;
+    if (const char* e = std::getenv("FH_AUTO_EXPOSURE")) {
+      char* end = nullptr;
+      const float v = std::strtof(e, &end);
+      if (end == e || *end != '\0') throw std::runtime_error(std::string("FH_AUTO_EXPOSURE: \"") + e + "\" is neither 1 (the defaults) nor a key such as 0.18");
+      if (v != 0.0f) {
+        AutoExposureParams ae;
+        if (std::strcmp(e, "1") != 0) ae.key = v;
+        set_auto_exposure(&ae);
+      }
+    }
+  }
   cwl::check(ctx, fh_post_process(ctx, reinterpret_cast<const float*>(beauty_in), reinterpret_cast<float*>(beauty_high_luminance), reinterpret_cast<float*>(beauty_temp), width, height, &p,
                                   reinterpret_cast<float*>(beauty_out)),
              "fh_post_process");
