@@ -837,13 +837,6 @@ __global__ void k_box_area_sum(uint32_t n, const float4* box, double* sum)
   if ((threadIdx.x & 63) == 0 && a != 0.0) atomicAdd(sum, a);
 }
 
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
-};
-
 }  // namespace
 
 // boxes of all levels bottom up (requantise = 0: only the full-precision boxes of a freshly built tree), then the sum of the node areas
@@ -855,11 +848,11 @@ static int refit_levels(fh_ctx* ctx, float pad, int requantise, double* area)
     const uint32_t begin = ls[l], end = ls[l + 1];
     if (end > begin) hipLaunchKernelGGL(k_refit8_level, dim3((end - begin + 127) / 128), dim3(128), 0, st, ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_bvh8_box, begin, end, pad, requantise);
   }
-  DevBuf<double> sum;
+  DeviceBuffer<double> sum;
   FH_HIP(sum.alloc(1));
-  FH_HIP(hipMemsetAsync(sum.p, 0, 8, st));
-  hipLaunchKernelGGL(k_box_area_sum, dim3((ctx->bvh8_n_nodes + 255) / 256), dim3(256), 0, st, ctx->bvh8_n_nodes, ctx->d_bvh8_box, sum.p);
-  FH_HIP(hipMemcpyAsync(area, sum.p, 8, hipMemcpyDeviceToHost, st));
+  FH_HIP(hipMemsetAsync(sum.get(), 0, 8, st));
+  hipLaunchKernelGGL(k_box_area_sum, dim3((ctx->bvh8_n_nodes + 255) / 256), dim3(256), 0, st, ctx->bvh8_n_nodes, ctx->d_bvh8_box, sum.get());
+  FH_HIP(hipMemcpyAsync(area, sum.get(), 8, hipMemcpyDeviceToHost, st));
   FH_HIP(hipGetLastError());
   FH_HIP(hipStreamSynchronize(st));
   return FH_OK;
@@ -873,15 +866,15 @@ int bvh_build_device(fh_ctx* ctx)
   // ---- instance transforms changed, topology did not: refit (FH_REFIT=0 forces the full rebuild).  A refit whose boxes have grown to
   // more than 1.5x the area the tree had when it was built is discarded for a rebuild: the instances have moved too far for the old topology.
   if (ctx->refit_ok && ctx->use_bvh8 && ctx->d_bvh8_box && n && ctx->bvh8_n_tris == n && !(getenv("FH_REFIT") && getenv("FH_REFIT")[0] == '0')) {
-    DevBuf<float4> face_lo, face_hi;
-    DevBuf<int> bounds;
+    DeviceBuffer<float4> face_lo, face_hi;
+    DeviceBuffer<int> bounds;
     FH_HIP(face_lo.alloc(n)); FH_HIP(face_hi.alloc(n)); FH_HIP(bounds.alloc(6));
     const int init_bounds[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-    FH_HIP(hipMemcpyAsync(bounds.p, init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_face_bounds, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, n, face_lo.p, face_hi.p, bounds.p);
+    FH_HIP(hipMemcpyAsync(bounds.get(), init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_face_bounds, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, n, face_lo.get(), face_hi.get(), bounds.get());
     hipLaunchKernelGGL(k_refresh_tris8, dim3((8u * ctx->bvh8_n_nodes + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, 8u * ctx->bvh8_n_nodes, ctx->d_bvh8_tris);
     int hb[6];
-    FH_HIP(hipMemcpyAsync(hb, bounds.p, sizeof hb, hipMemcpyDeviceToHost, st));
+    FH_HIP(hipMemcpyAsync(hb, bounds.get(), sizeof hb, hipMemcpyDeviceToHost, st));
     FH_HIP(hipStreamSynchronize(st));
     float maxabs = 0.0f;
     for (int k = 0; k < 6; ++k) maxabs = fmaxf(maxabs, fabsf(order_float(hb[k])));
@@ -903,33 +896,29 @@ int bvh_build_device(fh_ctx* ctx)
   ctx->refit_ok = false;
   ctx->bu_choice = 0; ctx->bu_toggle = 0; ctx->bu_cost[0] = ctx->bu_cost[1] = ctx->bu_items[0] = ctx->bu_items[1] = 0.0;  // a new tree: where its rays should start is measured again (render.hip)
   ctx->survival_n = 0;  // ... and how long its paths live is not known yet (context.h: survival)
-  if (ctx->d_bvh8_box) { (void)hipFree(ctx->d_bvh8_box); ctx->d_bvh8_box = nullptr; }
+  ctx->d_bvh8_box.reset();
   ctx->bvh8_level_start.clear();
-  if (ctx->d_bvh2_nodes) { (void)hipFree(ctx->d_bvh2_nodes); ctx->d_bvh2_nodes = nullptr; }
-  if (ctx->d_bvh2_tris) { (void)hipFree(ctx->d_bvh2_tris); ctx->d_bvh2_tris = nullptr; }
-  if (ctx->d_bvh8_nodes) { (void)hipFree(ctx->d_bvh8_nodes); ctx->d_bvh8_nodes = nullptr; }
-  if (ctx->d_bvh8_tris) { (void)hipFree(ctx->d_bvh8_tris); ctx->d_bvh8_tris = nullptr; }
-  if (ctx->d_bvh8_parent) { (void)hipFree(ctx->d_bvh8_parent); ctx->d_bvh8_parent = nullptr; }
-  if (ctx->d_face_node) { (void)hipFree(ctx->d_face_node); ctx->d_face_node = nullptr; }
+  ctx->d_bvh2_nodes.reset(); ctx->d_bvh2_tris.reset();
+  ctx->d_bvh8_nodes.reset(); ctx->d_bvh8_tris.reset(); ctx->d_bvh8_parent.reset(); ctx->d_face_node.reset();
   ctx->bvh2_n_nodes = ctx->bvh2_n_tris = ctx->bvh8_n_nodes = ctx->bvh8_n_tris = 0;
   ctx->use_bvh8 = false;
   ctx->bvh_valid = false;
   if (n == 0) { ctx->bvh_valid = true; return FH_OK; }
 
-  DevBuf<float4> face_lo, face_hi, node_lo, node_hi, leaf_lo, leaf_hi;
-  DevBuf<int> bounds, node_parent, leaf_parent;
-  DevBuf<unsigned long long> keys_a, keys_b;
-  DevBuf<uint32_t> vals_a, vals_b;
-  DevBuf<int2> children, ranges;
-  DevBuf<unsigned int> arrive;
+  DeviceBuffer<float4> face_lo, face_hi, node_lo, node_hi, leaf_lo, leaf_hi;
+  DeviceBuffer<int> bounds, node_parent, leaf_parent;
+  DeviceBuffer<unsigned long long> keys_a, keys_b;
+  DeviceBuffer<uint32_t> vals_a, vals_b;
+  DeviceBuffer<int2> children, ranges;
+  DeviceBuffer<unsigned int> arrive;
   FH_HIP(face_lo.alloc(n)); FH_HIP(face_hi.alloc(n));
   FH_HIP(bounds.alloc(6));
   const int init_bounds[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-  FH_HIP(hipMemcpyAsync(bounds.p, init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, st));
+  FH_HIP(hipMemcpyAsync(bounds.get(), init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, st));
   const uint32_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(k_face_bounds, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, n, face_lo.p, face_hi.p, bounds.p);
+  hipLaunchKernelGGL(k_face_bounds, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, n, face_lo.get(), face_hi.get(), bounds.get());
   int hb[6];
-  FH_HIP(hipMemcpyAsync(hb, bounds.p, sizeof hb, hipMemcpyDeviceToHost, st));
+  FH_HIP(hipMemcpyAsync(hb, bounds.get(), sizeof hb, hipMemcpyDeviceToHost, st));
   FH_HIP(hipStreamSynchronize(st));
   float maxabs = 0.0f;
   for (int k = 0; k < 6; ++k) maxabs = fmaxf(maxabs, fabsf(order_float(hb[k])));
@@ -937,25 +926,25 @@ int bvh_build_device(fh_ctx* ctx)
   for (int k = 0; k < 3; ++k) { ctx->scene_lo[k] = order_float(hb[k]) - 2.0f * pad; ctx->scene_hi[k] = order_float(hb[3 + k]) + 2.0f * pad; }
 
   if (n <= kLeafMax2) {
-    FH_HIP(hipMalloc((void**)&ctx->d_bvh2_tris, sizeof(float4) * 3ull * n));
+    FH_HIP(ctx->d_bvh2_tris.alloc(3ull * n));
     ctx->bvh2_n_tris = n;
-    FH_HIP(hipMalloc((void**)&ctx->d_bvh2_nodes, sizeof(float4) * 4));
+    FH_HIP(ctx->d_bvh2_nodes.alloc(4));
     FH_HIP(vals_a.alloc(n));
     std::vector<uint32_t> ident(n);
     for (uint32_t i = 0; i < n; ++i) ident[i] = i;
-    FH_HIP(hipMemcpyAsync(vals_a.p, ident.data(), 4ull * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_emit2_tiny, dim3(1), dim3(1), 0, st, (int)n, face_lo.p, face_hi.p, pad, ctx->d_bvh2_nodes);
-    hipLaunchKernelGGL(k_emit_tris, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_a.p, n, ctx->d_bvh2_tris, (const uint32_t*)nullptr);
+    FH_HIP(hipMemcpyAsync(vals_a.get(), ident.data(), 4ull * n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_emit2_tiny, dim3(1), dim3(1), 0, st, (int)n, face_lo.get(), face_hi.get(), pad, ctx->d_bvh2_nodes);
+    hipLaunchKernelGGL(k_emit_tris, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_a.get(), n, ctx->d_bvh2_tris, (const uint32_t*)nullptr);
     FH_HIP(hipStreamSynchronize(st));
     ctx->bvh2_n_nodes = 1;
     if (n <= kLeafMax8) {
-      DevBuf<uint32_t> tri_slot;
+      DeviceBuffer<uint32_t> tri_slot;
       FH_HIP(tri_slot.alloc(n));
-      FH_HIP(hipMalloc((void**)&ctx->d_bvh8_nodes, sizeof(uint4) * kBvh8NodeVec));
-      FH_HIP(hipMalloc((void**)&ctx->d_bvh8_tris, sizeof(float4) * 3ull * 8ull));
+      FH_HIP(ctx->d_bvh8_nodes.alloc(kBvh8NodeVec));
+      FH_HIP(ctx->d_bvh8_tris.alloc(3ull * 8ull));
       hipLaunchKernelGGL(k_clear_tris8, dim3(1), dim3(64), 0, st, ctx->d_bvh8_tris, 8u);
-      hipLaunchKernelGGL(k_collapse8_tiny, dim3(1), dim3(1), 0, st, (int)n, face_lo.p, face_hi.p, pad, ctx->d_bvh8_nodes, tri_slot.p);
-      hipLaunchKernelGGL(k_emit_tris8, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_a.p, tri_slot.p, n, ctx->d_bvh8_tris, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr);
+      hipLaunchKernelGGL(k_collapse8_tiny, dim3(1), dim3(1), 0, st, (int)n, face_lo.get(), face_hi.get(), pad, ctx->d_bvh8_nodes, tri_slot.get());
+      hipLaunchKernelGGL(k_emit_tris8, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_a.get(), tri_slot.get(), n, ctx->d_bvh8_tris, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr);
       FH_HIP(hipStreamSynchronize(st));
       ctx->bvh8_n_nodes = 1;
       ctx->bvh8_n_tris = n;
@@ -964,10 +953,10 @@ int bvh_build_device(fh_ctx* ctx)
   } else {
     // ---- references: large triangles enter the build as several clipped boxes (early split clipping, kernels above)
     uint32_t nr = n;
-    DevBuf<uint32_t> ref_face_buf, split_count, split_offset;
-    DevBuf<float4> ref_lo, ref_hi;
-    const float4* box_lo = face_lo.p;
-    const float4* box_hi = face_hi.p;
+    DeviceBuffer<uint32_t> ref_face_buf, split_count, split_offset;
+    DeviceBuffer<float4> ref_lo, ref_hi;
+    const float4* box_lo = face_lo.get();
+    const float4* box_hi = face_hi.get();
     const uint32_t* ref_face = nullptr;
     bool splitting = n >= 256;
     if (const char* e = getenv("FH_SPLIT")) splitting = splitting && e[0] != '0';
@@ -977,17 +966,17 @@ int bvh_build_device(fh_ctx* ctx)
       const float eps = extent * 1e-6f;
       FH_HIP(split_count.alloc(n)); FH_HIP(split_offset.alloc(n));
       size_t scan_bytes = 0;
-      FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, split_count.p, split_offset.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-      DevBuf<char> scan_tmp;
+      FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, split_count.get(), split_offset.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+      DeviceBuffer<char> scan_tmp;
       FH_HIP(scan_tmp.alloc(scan_bytes));
       uint32_t total = n;
       const double split_budget = 1.5;  // references per face the split may produce at most
       for (int attempt = 0; attempt < 6; ++attempt, thr *= 2.0f) {  // a scene made of large triangles only: coarser cells until the references fit
-        hipLaunchKernelGGL(k_split_count, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, face_lo.p, face_hi.p, n, thr, eps, split_count.p);
-        FH_HIP(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, split_count.p, split_offset.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        hipLaunchKernelGGL(k_split_count, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, face_lo.get(), face_hi.get(), n, thr, eps, split_count.get());
+        FH_HIP(rocprim::exclusive_scan(scan_tmp.get(), scan_bytes, split_count.get(), split_offset.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
         uint32_t tail[2];
-        FH_HIP(hipMemcpyAsync(&tail[0], split_offset.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        FH_HIP(hipMemcpyAsync(&tail[1], split_count.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        FH_HIP(hipMemcpyAsync(&tail[0], split_offset.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        FH_HIP(hipMemcpyAsync(&tail[1], split_count.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
         FH_HIP(hipStreamSynchronize(st));
         total = tail[0] + tail[1];
         if ((unsigned long long)total <= (unsigned long long)((double)n * split_budget) + 4096ull) break;
@@ -996,33 +985,33 @@ int bvh_build_device(fh_ctx* ctx)
       if (total > n) {
         nr = total;
         FH_HIP(ref_face_buf.alloc(nr)); FH_HIP(ref_lo.alloc(nr)); FH_HIP(ref_hi.alloc(nr));
-        hipLaunchKernelGGL(k_split_emit, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, face_lo.p, face_hi.p, n, thr, eps, split_count.p, split_offset.p, ref_face_buf.p, ref_lo.p,
-                           ref_hi.p);
-        box_lo = ref_lo.p; box_hi = ref_hi.p; ref_face = ref_face_buf.p;
+        hipLaunchKernelGGL(k_split_emit, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, face_lo.get(), face_hi.get(), n, thr, eps, split_count.get(), split_offset.get(), ref_face_buf.get(), ref_lo.get(),
+                           ref_hi.get());
+        box_lo = ref_lo.get(); box_hi = ref_hi.get(); ref_face = ref_face_buf.get();
       }
     }
     const uint32_t rblocks = (nr + 255) / 256;
-    FH_HIP(hipMalloc((void**)&ctx->d_bvh2_tris, sizeof(float4) * 3ull * nr));
+    FH_HIP(ctx->d_bvh2_tris.alloc(3ull * nr));
     ctx->bvh2_n_tris = nr;
     FH_HIP(keys_a.alloc(nr)); FH_HIP(keys_b.alloc(nr)); FH_HIP(vals_a.alloc(nr)); FH_HIP(vals_b.alloc(nr));
-    hipLaunchKernelGGL(k_morton, dim3(rblocks), dim3(256), 0, st, box_lo, box_hi, nr, bounds.p, keys_a.p, vals_a.p);
+    hipLaunchKernelGGL(k_morton, dim3(rblocks), dim3(256), 0, st, box_lo, box_hi, nr, bounds.get(), keys_a.get(), vals_a.get());
     size_t temp_bytes = 0;
-    FH_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (size_t)nr, 0u, 63u, st));
-    DevBuf<char> temp;
+    FH_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_a.get(), keys_b.get(), vals_a.get(), vals_b.get(), (size_t)nr, 0u, 63u, st));
+    DeviceBuffer<char> temp;
     FH_HIP(temp.alloc(temp_bytes));
-    FH_HIP(rocprim::radix_sort_pairs(temp.p, temp_bytes, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (size_t)nr, 0u, 63u, st));
+    FH_HIP(rocprim::radix_sort_pairs(temp.get(), temp_bytes, keys_a.get(), keys_b.get(), vals_a.get(), vals_b.get(), (size_t)nr, 0u, 63u, st));
     const uint32_t n_inner = nr - 1;
     FH_HIP(children.alloc(n_inner)); FH_HIP(ranges.alloc(n_inner)); FH_HIP(node_parent.alloc(n_inner)); FH_HIP(leaf_parent.alloc(nr));
     FH_HIP(node_lo.alloc(n_inner)); FH_HIP(node_hi.alloc(n_inner)); FH_HIP(leaf_lo.alloc(nr)); FH_HIP(leaf_hi.alloc(nr));
     FH_HIP(arrive.alloc(n_inner));
-    FH_HIP(hipMemsetAsync(arrive.p, 0, 4ull * n_inner, st));
+    FH_HIP(hipMemsetAsync(arrive.get(), 0, 4ull * n_inner, st));
     const uint32_t iblocks = (n_inner + 255) / 256;
-    hipLaunchKernelGGL(k_hierarchy, dim3(iblocks), dim3(256), 0, st, keys_b.p, (int)nr, children.p, ranges.p, node_parent.p, leaf_parent.p);
-    hipLaunchKernelGGL(k_refit, dim3(rblocks), dim3(256), 0, st, vals_b.p, box_lo, box_hi, (int)nr, children.p, node_parent.p, leaf_parent.p, node_lo.p, node_hi.p, leaf_lo.p,
-                       leaf_hi.p, arrive.p);
-    FH_HIP(hipMalloc((void**)&ctx->d_bvh2_nodes, sizeof(float4) * 4ull * n_inner));
-    hipLaunchKernelGGL(k_emit2, dim3(iblocks), dim3(256), 0, st, (int)n_inner, children.p, ranges.p, node_lo.p, node_hi.p, leaf_lo.p, leaf_hi.p, pad, ctx->d_bvh2_nodes);
-    hipLaunchKernelGGL(k_emit_tris, dim3(rblocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_b.p, nr, ctx->d_bvh2_tris, ref_face);
+    hipLaunchKernelGGL(k_hierarchy, dim3(iblocks), dim3(256), 0, st, keys_b.get(), (int)nr, children.get(), ranges.get(), node_parent.get(), leaf_parent.get());
+    hipLaunchKernelGGL(k_refit, dim3(rblocks), dim3(256), 0, st, vals_b.get(), box_lo, box_hi, (int)nr, children.get(), node_parent.get(), leaf_parent.get(), node_lo.get(), node_hi.get(), leaf_lo.get(),
+                       leaf_hi.get(), arrive.get());
+    FH_HIP(ctx->d_bvh2_nodes.alloc(4ull * n_inner));
+    hipLaunchKernelGGL(k_emit2, dim3(iblocks), dim3(256), 0, st, (int)n_inner, children.get(), ranges.get(), node_lo.get(), node_hi.get(), leaf_lo.get(), leaf_hi.get(), pad, ctx->d_bvh2_nodes);
+    hipLaunchKernelGGL(k_emit_tris, dim3(rblocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_b.get(), nr, ctx->d_bvh2_tris, ref_face);
     FH_HIP(hipGetLastError());
     FH_HIP(hipStreamSynchronize(st));
     ctx->bvh2_n_nodes = n_inner;
@@ -1039,34 +1028,34 @@ int bvh_build_device(fh_ctx* ctx)
     const bool deciding = mode == 0;
     bool ploc = mode == 2 || deciding;
     bool ploc_failed = false;
-    DevBuf<int2> p_children, p_ranges;
-    DevBuf<float4> p_node_lo, p_node_hi;
+    DeviceBuffer<int2> p_children, p_ranges;
+    DeviceBuffer<float4> p_node_lo, p_node_hi;
     if (ploc) {
-      DevBuf<int> cid_a, cid_b, nn;
-      DevBuf<float4> clo_a, chi_a, clo_b, chi_b;
-      DevBuf<uint32_t> valid, offset, node_counter;
+      DeviceBuffer<int> cid_a, cid_b, nn;
+      DeviceBuffer<float4> clo_a, chi_a, clo_b, chi_b;
+      DeviceBuffer<uint32_t> valid, offset, node_counter;
       FH_HIP(cid_a.alloc(nr)); FH_HIP(cid_b.alloc(nr)); FH_HIP(nn.alloc(nr)); FH_HIP(clo_a.alloc(nr)); FH_HIP(chi_a.alloc(nr)); FH_HIP(clo_b.alloc(nr)); FH_HIP(chi_b.alloc(nr));
       FH_HIP(valid.alloc(nr)); FH_HIP(offset.alloc(nr)); FH_HIP(node_counter.alloc(1));
       FH_HIP(p_children.alloc(n_inner)); FH_HIP(p_ranges.alloc(n_inner)); FH_HIP(p_node_lo.alloc(n_inner)); FH_HIP(p_node_hi.alloc(n_inner));
-      FH_HIP(hipMemsetAsync(node_counter.p, 0, 4, st));
-      hipLaunchKernelGGL(k_ploc_init, dim3(rblocks), dim3(256), 0, st, (int)nr, leaf_lo.p, leaf_hi.p, cid_a.p, clo_a.p, chi_a.p);
+      FH_HIP(hipMemsetAsync(node_counter.get(), 0, 4, st));
+      hipLaunchKernelGGL(k_ploc_init, dim3(rblocks), dim3(256), 0, st, (int)nr, leaf_lo.get(), leaf_hi.get(), cid_a.get(), clo_a.get(), chi_a.get());
       size_t scan_bytes = 0;
-      FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, valid.p, offset.p, 0u, (size_t)nr, rocprim::plus<uint32_t>(), st));
-      DevBuf<char> scan_tmp;
+      FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, valid.get(), offset.get(), 0u, (size_t)nr, rocprim::plus<uint32_t>(), st));
+      DeviceBuffer<char> scan_tmp;
       FH_HIP(scan_tmp.alloc(scan_bytes));
       const int ploc_radius = kPlocRadius;  // neighbours searched to either side
-      int* cid = cid_a.p; int* cid_o = cid_b.p;
-      float4 *clo = clo_a.p, *chi = chi_a.p, *clo_o = clo_b.p, *chi_o = chi_b.p;
+      int* cid = cid_a.get(); int* cid_o = cid_b.get();
+      float4 *clo = clo_a.get(), *chi = chi_a.get(), *clo_o = clo_b.get(), *chi_o = chi_b.get();
       uint32_t count = nr;
       for (int round = 0; count > 1 && round < 4096; ++round) {
         const uint32_t b = (count + 255) / 256;
-        hipLaunchKernelGGL(k_ploc_nearest, dim3(b), dim3(256), 0, st, (int)count, clo, chi, nn.p, ploc_radius);
-        hipLaunchKernelGGL(k_ploc_merge, dim3(b), dim3(256), 0, st, (int)count, nn.p, cid, clo, chi, valid.p, p_children.p, p_ranges.p, p_node_lo.p, p_node_hi.p, node_counter.p);
-        FH_HIP(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, valid.p, offset.p, 0u, (size_t)count, rocprim::plus<uint32_t>(), st));
-        hipLaunchKernelGGL(k_ploc_compact, dim3(b), dim3(256), 0, st, (int)count, valid.p, offset.p, cid, clo, chi, cid_o, clo_o, chi_o);
+        hipLaunchKernelGGL(k_ploc_nearest, dim3(b), dim3(256), 0, st, (int)count, clo, chi, nn.get(), ploc_radius);
+        hipLaunchKernelGGL(k_ploc_merge, dim3(b), dim3(256), 0, st, (int)count, nn.get(), cid, clo, chi, valid.get(), p_children.get(), p_ranges.get(), p_node_lo.get(), p_node_hi.get(), node_counter.get());
+        FH_HIP(rocprim::exclusive_scan(scan_tmp.get(), scan_bytes, valid.get(), offset.get(), 0u, (size_t)count, rocprim::plus<uint32_t>(), st));
+        hipLaunchKernelGGL(k_ploc_compact, dim3(b), dim3(256), 0, st, (int)count, valid.get(), offset.get(), cid, clo, chi, cid_o, clo_o, chi_o);
         uint32_t tail[2] = {0, 0};  // offset and flag of the last cluster -> new count
-        FH_HIP(hipMemcpyAsync(&tail[0], offset.p + (count - 1), 4, hipMemcpyDeviceToHost, st));
-        FH_HIP(hipMemcpyAsync(&tail[1], valid.p + (count - 1), 4, hipMemcpyDeviceToHost, st));
+        FH_HIP(hipMemcpyAsync(&tail[0], offset.get() + (count - 1), 4, hipMemcpyDeviceToHost, st));
+        FH_HIP(hipMemcpyAsync(&tail[1], valid.get() + (count - 1), 4, hipMemcpyDeviceToHost, st));
         FH_HIP(hipStreamSynchronize(st));
         const uint32_t next = tail[0] + tail[1];
         if (next >= count) {  // no mutual pair found (non-finite boxes): in auto mode the radix tree built above is still valid
@@ -1090,13 +1079,13 @@ int bvh_build_device(fh_ctx* ctx)
       if (ploc_failed) { ploc = false; ctx->builder_choice = 1; }  // auto mode falls back to the radix tree; an explicit FH_BVH_BUILDER=ploc reported the error above
     }
     if (deciding || getenv("FH_DEBUG_BVH")) {
-      DevBuf<double> sums;
+      DeviceBuffer<double> sums;
       FH_HIP(sums.alloc(2));
-      FH_HIP(hipMemsetAsync(sums.p, 0, 16, st));
-      hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, node_lo.p, node_hi.p, sums.p);
-      if (ploc) hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, p_node_lo.p, p_node_hi.p, sums.p + 1);
+      FH_HIP(hipMemsetAsync(sums.get(), 0, 16, st));
+      hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, node_lo.get(), node_hi.get(), sums.get());
+      if (ploc) hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, p_node_lo.get(), p_node_hi.get(), sums.get() + 1);
       double h[2];
-      FH_HIP(hipMemcpyAsync(h, sums.p, 16, hipMemcpyDeviceToHost, st));
+      FH_HIP(hipMemcpyAsync(h, sums.get(), 16, hipMemcpyDeviceToHost, st));
       FH_HIP(hipStreamSynchronize(st));
       if (deciding && !ploc_failed) {
         ploc = h[1] < 0.93 * h[0];
@@ -1105,21 +1094,21 @@ int bvh_build_device(fh_ctx* ctx)
       if (getenv("FH_DEBUG_BVH")) fprintf(stderr, "[bvh] sum of inner-node areas: radix tree %.4f, PLOC %.4f -> %s\n", h[0], h[1], ploc ? "PLOC" : "radix tree");
     }
     if (!ploc) root_node = 0;  // the radix tree's root is node 0
-    const int2* c_children = ploc ? p_children.p : children.p;
-    const int2* c_ranges = ploc ? p_ranges.p : ranges.p;
-    const float4* c_node_lo = ploc ? p_node_lo.p : node_lo.p;
-    const float4* c_node_hi = ploc ? p_node_hi.p : node_hi.p;
+    const int2* c_children = ploc ? p_children.get() : children.get();
+    const int2* c_ranges = ploc ? p_ranges.get() : ranges.get();
+    const float4* c_node_lo = ploc ? p_node_lo.get() : node_lo.get();
+    const float4* c_node_hi = ploc ? p_node_hi.get() : node_hi.get();
 
     // (SAH refinement of the chosen binary tree by parallel reinsertion, Meister & Bittner 2018, was built in round 5: the summed inner-node area falls by 2-7 %, the node visits per
     // ray do not -- 15.28 -> 15.12 on configs[2], 11.73 -> 11.81 on configs[3].  profiles/README.md r5-1, tools/patches/r6_pruned_switches.patch)
 
     // ---- collapse to BVH8, breadth first
-    DevBuf<Work8> work_a, work_b;
-    DevBuf<uint32_t> counters, tri_slot;  // [0] node counter, [1] triangle counter, [2] next-level item count; triangle slot of every sorted leaf
+    DeviceBuffer<Work8> work_a, work_b;
+    DeviceBuffer<uint32_t> counters, tri_slot;  // [0] node counter, [1] triangle counter, [2] next-level item count; triangle slot of every sorted leaf
     FH_HIP(work_a.alloc(n_inner)); FH_HIP(work_b.alloc(n_inner)); FH_HIP(counters.alloc(3)); FH_HIP(tri_slot.alloc(nr));
-    FH_HIP(hipMalloc((void**)&ctx->d_bvh8_nodes, sizeof(uint4) * (size_t)kBvh8NodeVec * n_inner));
-    FH_HIP(hipMalloc((void**)&ctx->d_bvh8_parent, 4ull * n_inner));
-    FH_HIP(hipMalloc((void**)&ctx->d_face_node, 4ull * n));
+    FH_HIP(ctx->d_bvh8_nodes.alloc((size_t)kBvh8NodeVec * n_inner));
+    FH_HIP(ctx->d_bvh8_parent.alloc(n_inner));
+    FH_HIP(ctx->d_face_node.alloc(n));
     FH_HIP(hipMemsetAsync(ctx->d_bvh8_parent, 0xff, 4ull * n_inner, st));  // (the root keeps 0xffffffff: no way up)
     FH_HIP(hipMemsetAsync(ctx->d_face_node, 0xff, 4ull * n, st));
     const uint32_t leaf_max8 = 1;  // one triangle per leaf child (the node layout has one triangle slot per child slot): box tests are ~4x cheaper than triangle tests (profiles/README.md)
@@ -1128,45 +1117,45 @@ int bvh_build_device(fh_ctx* ctx)
     // the cut of least summed wide-node area (k_cut_tables); FH_COLLAPSE=greedy: the largest-child-first rule above
     bool optimal_cut = leaf_max8 == 1;
     if (const char* e = getenv("FH_COLLAPSE")) optimal_cut = optimal_cut && std::strcmp(e, "greedy") != 0;
-    DevBuf<float> cut_cost_tab;
-    DevBuf<uint2> cut_decision;
+    DeviceBuffer<float> cut_cost_tab;
+    DeviceBuffer<uint2> cut_decision;
     if (optimal_cut) {
-      DevBuf<int> c_node_parent, c_leaf_parent;
+      DeviceBuffer<int> c_node_parent, c_leaf_parent;
       FH_HIP(c_node_parent.alloc(n_inner)); FH_HIP(c_leaf_parent.alloc(nr)); FH_HIP(cut_cost_tab.alloc(7ull * n_inner)); FH_HIP(cut_decision.alloc(n_inner));
-      FH_HIP(hipMemsetAsync(c_node_parent.p, 0xff, 4ull * n_inner, st));  // the root keeps -1
-      FH_HIP(hipMemsetAsync(arrive.p, 0, 4ull * n_inner, st));
-      hipLaunchKernelGGL(k_tree_parents, dim3(iblocks), dim3(256), 0, st, (int)n_inner, c_children, c_node_parent.p, c_leaf_parent.p);
-      hipLaunchKernelGGL(k_cut_tables, dim3(rblocks), dim3(256), 0, st, (int)nr, c_children, c_node_parent.p, c_leaf_parent.p, c_node_lo, c_node_hi, arrive.p, cut_cost_tab.p,
-                         cut_decision.p);
+      FH_HIP(hipMemsetAsync(c_node_parent.get(), 0xff, 4ull * n_inner, st));  // the root keeps -1
+      FH_HIP(hipMemsetAsync(arrive.get(), 0, 4ull * n_inner, st));
+      hipLaunchKernelGGL(k_tree_parents, dim3(iblocks), dim3(256), 0, st, (int)n_inner, c_children, c_node_parent.get(), c_leaf_parent.get());
+      hipLaunchKernelGGL(k_cut_tables, dim3(rblocks), dim3(256), 0, st, (int)nr, c_children, c_node_parent.get(), c_leaf_parent.get(), c_node_lo, c_node_hi, arrive.get(), cut_cost_tab.get(),
+                         cut_decision.get());
       FH_HIP(hipGetLastError());
       FH_HIP(hipStreamSynchronize(st));  // (the parent arrays go out of scope here)
       if (getenv("FH_DEBUG_BVH")) {
         float c_root = 0.0f;
-        FH_HIP(hipMemcpy(&c_root, cut_cost_tab.p + 7ull * (size_t)root_node, 4, hipMemcpyDeviceToHost));
+        FH_HIP(hipMemcpy(&c_root, cut_cost_tab.get() + 7ull * (size_t)root_node, 4, hipMemcpyDeviceToHost));
         fprintf(stderr, "[bvh] least summed area of the wide nodes (cut tables, root): %.4f\n", c_root);
       }
     }
     const Work8 root{root_node, 0u};
     const uint32_t init_counters[3] = {1u, 0u, 0u};
-    FH_HIP(hipMemcpyAsync(work_a.p, &root, sizeof root, hipMemcpyHostToDevice, st));
-    FH_HIP(hipMemcpyAsync(counters.p, init_counters, sizeof init_counters, hipMemcpyHostToDevice, st));
+    FH_HIP(hipMemcpyAsync(work_a.get(), &root, sizeof root, hipMemcpyHostToDevice, st));
+    FH_HIP(hipMemcpyAsync(counters.get(), init_counters, sizeof init_counters, hipMemcpyHostToDevice, st));
     uint32_t level_count = 1;
-    Work8* cur = work_a.p;
-    Work8* nxt = work_b.p;
+    Work8* cur = work_a.get();
+    Work8* nxt = work_b.get();
     uint32_t levels = 0;
     std::vector<uint32_t> level_start{0u};
     for (int level = 0; level < 64 && level_count > 0; ++level) {
       ++levels;
       level_start.push_back(level_start.back() + level_count);
-      FH_HIP(hipMemsetAsync(counters.p + 2, 0, 4, st));
-      hipLaunchKernelGGL(k_collapse8, dim3((level_count + 63) / 64), dim3(64), 0, st, cur, level_count, c_children, c_ranges, c_node_lo, c_node_hi, leaf_lo.p, leaf_hi.p, pad,
-                         leaf_max8, absorb8, ctx->d_bvh8_nodes, counters.p, counters.p + 1, tri_slot.p, nxt, counters.p + 2, optimal_cut ? cut_decision.p : (const uint2*)nullptr, ctx->d_bvh8_parent);
-      FH_HIP(hipMemcpyAsync(&level_count, counters.p + 2, 4, hipMemcpyDeviceToHost, st));
+      FH_HIP(hipMemsetAsync(counters.get() + 2, 0, 4, st));
+      hipLaunchKernelGGL(k_collapse8, dim3((level_count + 63) / 64), dim3(64), 0, st, cur, level_count, c_children, c_ranges, c_node_lo, c_node_hi, leaf_lo.get(), leaf_hi.get(), pad,
+                         leaf_max8, absorb8, ctx->d_bvh8_nodes, counters.get(), counters.get() + 1, tri_slot.get(), nxt, counters.get() + 2, optimal_cut ? cut_decision.get() : (const uint2*)nullptr, ctx->d_bvh8_parent);
+      FH_HIP(hipMemcpyAsync(&level_count, counters.get() + 2, 4, hipMemcpyDeviceToHost, st));
       FH_HIP(hipStreamSynchronize(st));
       Work8* t = cur; cur = nxt; nxt = t;
     }
     uint32_t final_counters[2] = {0, 0};
-    FH_HIP(hipMemcpyAsync(final_counters, counters.p, 8, hipMemcpyDeviceToHost, st));
+    FH_HIP(hipMemcpyAsync(final_counters, counters.get(), 8, hipMemcpyDeviceToHost, st));
     FH_HIP(hipStreamSynchronize(st));
     if (final_counters[1] != nr) return fail(ctx, FH_E_INVALID, "BVH8 collapse lost triangles");
     if (levels > (uint32_t)kBvh8Stack) return fail(ctx, FH_E_UNSUPPORTED, "BVH8 deeper than the traversal stack (48 levels)");
@@ -1174,9 +1163,9 @@ int bvh_build_device(fh_ctx* ctx)
     if (final_counters[0] >= kCoopMaxTris / 8u) return fail(ctx, FH_E_UNSUPPORTED, "BVH8 with 2^23 or more nodes (the cooperative triangle queue keeps triangle slots in 26 bits)");
     ctx->bvh8_depth = levels;
     const uint32_t n_slots = 8u * final_counters[0];  // one triangle slot per child slot
-    FH_HIP(hipMalloc((void**)&ctx->d_bvh8_tris, sizeof(float4) * 3ull * n_slots));
+    FH_HIP(ctx->d_bvh8_tris.alloc(3ull * n_slots));
     hipLaunchKernelGGL(k_clear_tris8, dim3((n_slots + 255) / 256), dim3(256), 0, st, ctx->d_bvh8_tris, n_slots);
-    hipLaunchKernelGGL(k_emit_tris8, dim3(rblocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_b.p, tri_slot.p, nr, ctx->d_bvh8_tris, ref_face, ctx->d_face_node, ref_face ? split_count.p : (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_emit_tris8, dim3(rblocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_b.get(), tri_slot.get(), nr, ctx->d_bvh8_tris, ref_face, ctx->d_face_node, ref_face ? split_count.get() : (const uint32_t*)nullptr);
     hipLaunchKernelGGL(k_face_node_to_rec, dim3(blocks), dim3(256), 0, st, ctx->d_face_node, n, ctx->d_face_rec);
     FH_HIP(hipGetLastError());
     FH_HIP(hipStreamSynchronize(st));
@@ -1187,7 +1176,7 @@ int bvh_build_device(fh_ctx* ctx)
     // clipped boxes that a moved triangle no longer has, so scenes that use them are rebuilt instead.
     if (nr == n && level_start.back() == final_counters[0]) {
       ctx->bvh8_level_start = level_start;
-      FH_HIP(hipMalloc((void**)&ctx->d_bvh8_box, sizeof(float4) * 2ull * final_counters[0]));
+      FH_HIP(ctx->d_bvh8_box.alloc(2ull * final_counters[0]));
       const int rc = refit_levels(ctx, pad, 0, &ctx->bvh8_area_built);
       if (rc) return rc;
       ctx->refit_ok = true;

@@ -108,14 +108,8 @@ __global__ void __launch_bounds__(256) k_face_records(uint32_t nf, const float* 
 int transform_faces(fh_ctx* ctx)
 {
   const uint32_t ni = (uint32_t)ctx->h_o2w.size() / 12;
-  if (ctx->n_xf_alloc < ni) {
-    if (ctx->d_o2w) (void)hipFree(ctx->d_o2w);
-    if (ctx->d_w2o) (void)hipFree(ctx->d_w2o);
-    ctx->d_o2w = ctx->d_w2o = nullptr; ctx->n_xf_alloc = 0;
-    FH_HIP(hipMalloc((void**)&ctx->d_o2w, 48ull * ni));
-    FH_HIP(hipMalloc((void**)&ctx->d_w2o, 48ull * ni));
-    ctx->n_xf_alloc = ni;
-  }
+  FH_HIP(ctx->d_o2w.ensure(3ull * ni));  // (three rows per instance)
+  FH_HIP(ctx->d_w2o.ensure(3ull * ni));
   FH_HIP(hipMemcpyAsync(ctx->d_o2w, ctx->h_o2w.data(), 48ull * ni, hipMemcpyHostToDevice, ctx->stream));
   FH_HIP(hipMemcpyAsync(ctx->d_w2o, ctx->h_w2o.data(), 48ull * ni, hipMemcpyHostToDevice, ctx->stream));
   if (ctx->n_faces)
@@ -251,19 +245,15 @@ int rebuild_device_scene(fh_ctx* ctx)
     if (alpha) any_alpha = true;
     if (mats[mid].emissive) lights.push_back({f, mid});  // renderer.h:388-402, face order
   }
-  auto re_alloc = [&](auto*& ptr, size_t bytes) -> hipError_t {
-    if (ptr) { (void)hipFree(ptr); ptr = nullptr; }
-    return hipMalloc((void**)&ptr, bytes ? bytes : 16);
-  };
-  FH_HIP(re_alloc(ctx->d_face_rec, (unsigned long long)kFaceRec * nf * sizeof(float4)));
-  FH_HIP(re_alloc(ctx->d_face_cls, cls.size()));
-  FH_HIP(re_alloc(ctx->d_materials, mats.size() * sizeof(MaterialDev)));
-  FH_HIP(re_alloc(ctx->d_lights, lights.size() * sizeof(AreaLightDev)));
-  FH_HIP(re_alloc(ctx->d_obj_vertices, ctx->h_vertices.size() * sizeof(float)));
-  FH_HIP(re_alloc(ctx->d_obj_normals, ctx->h_normals.size() * sizeof(float)));
-  FH_HIP(re_alloc(ctx->d_obj_texcoords, ctx->h_texcoords.size() * sizeof(float)));
-  FH_HIP(re_alloc(ctx->d_obj_indices, ctx->h_indices.size() * sizeof(uint32_t)));
-  FH_HIP(re_alloc(ctx->d_face_meta, meta.size() * sizeof(uint2)));
+  FH_HIP(ctx->d_face_rec.alloc((size_t)kFaceRec * nf));
+  FH_HIP(ctx->d_face_cls.alloc(cls.size()));
+  FH_HIP(ctx->d_materials.alloc(mats.size()));
+  FH_HIP(ctx->d_lights.alloc(lights.size()));
+  FH_HIP(ctx->d_obj_vertices.alloc(ctx->h_vertices.size()));
+  FH_HIP(ctx->d_obj_normals.alloc(ctx->h_normals.size()));
+  FH_HIP(ctx->d_obj_texcoords.alloc(ctx->h_texcoords.size()));
+  FH_HIP(ctx->d_obj_indices.alloc(ctx->h_indices.size()));
+  FH_HIP(ctx->d_face_meta.alloc(meta.size()));
   FH_HIP(hipMemcpy(ctx->d_face_cls, cls.data(), cls.size(), hipMemcpyHostToDevice));
   FH_HIP(hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(MaterialDev), hipMemcpyHostToDevice));
   if (!lights.empty()) FH_HIP(hipMemcpy(ctx->d_lights, lights.data(), lights.size() * sizeof(AreaLightDev), hipMemcpyHostToDevice));
@@ -280,7 +270,7 @@ int rebuild_device_scene(fh_ctx* ctx)
   if (getenv("FH_DEBUG_BVH") && ctx->alpha_face_counts[0])
     fprintf(stderr, "[alpha] %u faces whose textures can cut: %u always pass, %u never pass, %u keep their any-hit test\n", ctx->alpha_face_counts[0], ctx->alpha_face_counts[1], ctx->alpha_face_counts[2],
             ctx->alpha_face_counts[3]);
-  if (ctx->d_alpha_rec) { (void)hipFree(ctx->d_alpha_rec); ctx->d_alpha_rec = nullptr; }
+  ctx->d_alpha_rec.reset();
   if (any_alpha) {
     // everything the any-hit test of a face reads, in one 64-byte line: the three texture coordinates and the two textures it may have to look at
     // ... and, behind them (second 64-byte line), the face's OPACITY MICROMAP: the face cut into 16 x 16 cells of its barycentrics (cell = (floor(16 u), floor(16 v)), the
@@ -337,7 +327,7 @@ int rebuild_device_scene(fh_ctx* ctx)
     ctx->alpha_cell_counts[0] = cells_total; ctx->alpha_cell_counts[1] = cells_pass; ctx->alpha_cell_counts[2] = cells_never;
     if (getenv("FH_DEBUG_BVH") && cells_total)
       fprintf(stderr, "[alpha] micromap: %llu cells of the faces that keep their test: %.1f %% always pass, %.1f %% never pass\n", cells_total, 100.0 * cells_pass / cells_total, 100.0 * cells_never / cells_total);
-    FH_HIP(hipMalloc((void**)&ctx->d_alpha_rec, rec.size() * sizeof(uint4)));
+    FH_HIP(ctx->d_alpha_rec.alloc(rec.size()));
     FH_HIP(hipMemcpy(ctx->d_alpha_rec, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice));
   }
   // (the host copies of the textures that can cut were needed for the classes and the micromaps above only: every upload brings its textures again)
@@ -349,13 +339,13 @@ int rebuild_device_scene(fh_ctx* ctx)
 // texels of all textures in one device blob + descriptors + the 256-entry sRGB table (cwl/texture.h:13-75 per texture)
 int upload_textures(fh_ctx* ctx, uint32_t n, const fh_texture_desc* descs)
 {
-  if (ctx->d_texels) { (void)hipFree(ctx->d_texels); ctx->d_texels = nullptr; }
-  if (ctx->d_textures) { (void)hipFree(ctx->d_textures); ctx->d_textures = nullptr; }
+  ctx->d_texels.reset();
+  ctx->d_textures.reset();
   ctx->n_textures = n;
   if (!ctx->d_srgb_lut) {
     float lut[256];
     for (int i = 0; i < 256; ++i) lut[i] = fht_srgb_to_linear((float)i * (1.0f / 255.0f));
-    FH_HIP(hipMalloc((void**)&ctx->d_srgb_lut, sizeof lut));
+    FH_HIP(ctx->d_srgb_lut.alloc(256));
     FH_HIP(hipMemcpy(ctx->d_srgb_lut, lut, sizeof lut, hipMemcpyHostToDevice));
   }
   ctx->h_tex_alpha_cuts.assign(n, 0);
@@ -385,7 +375,7 @@ int upload_textures(fh_ctx* ctx, uint32_t n, const fh_texture_desc* descs)
     t.width = descs[i].width; t.height = descs[i].height; t.srgb = descs[i].srgb ? 1u : 0u;
     if (ctx->h_tex_alpha_cuts[i] || ctx->h_tex_red_cuts[i]) t.rgba8.assign(descs[i].rgba8, descs[i].rgba8 + (size_t)descs[i].width * descs[i].height * 4);
   }
-  FH_HIP(hipMalloc((void**)&ctx->d_texels, total));
+  FH_HIP(ctx->d_texels.alloc(total));
   std::vector<fht_texture> t(n);
   size_t off = 0;
   for (uint32_t i = 0; i < n; ++i) {
@@ -394,7 +384,7 @@ int upload_textures(fh_ctx* ctx, uint32_t n, const fh_texture_desc* descs)
     t[i] = fht_texture{ctx->d_texels + off, nullptr, descs[i].width, descs[i].height, descs[i].srgb ? 1u : 0u};
     off += bytes;
   }
-  FH_HIP(hipMalloc((void**)&ctx->d_textures, n * sizeof(fht_texture)));
+  FH_HIP(ctx->d_textures.alloc(n));
   FH_HIP(hipMemcpy(ctx->d_textures, t.data(), n * sizeof(fht_texture), hipMemcpyHostToDevice));
   ctx->h_tex_desc = t;
   return FH_OK;
@@ -418,20 +408,32 @@ static void owned_list(uint32_t width, uint32_t height, uint32_t tw, uint32_t th
   }
 }
 
+// the ownership list of (rank, world) at the context's resolution and tile size, on the device; xy: its x | y << 16 form as well, for who wants it.
+// *n: its length; *e: what failed (the buffers are then empty).  A context without a resolution has no list.
+DeviceBuffer<uint32_t> upload_owned(const fh_ctx* ctx, uint32_t rank, uint32_t world, uint32_t* n, hipError_t* e, DeviceBuffer<uint32_t>* xy = nullptr)
+{
+  DeviceBuffer<uint32_t> list;
+  *n = 0; *e = hipSuccess;
+  if (ctx->width == 0 || ctx->height == 0) return list;
+  std::vector<uint32_t> owned, owned_xy;
+  owned_list(ctx->width, ctx->height, ctx->tile_w, ctx->tile_h, rank, world, owned, xy ? &owned_xy : nullptr);
+  const size_t bytes = owned.size() * 4;
+  if ((*e = list.alloc(owned.size())) == hipSuccess && bytes) *e = hipMemcpy(list, owned.data(), bytes, hipMemcpyHostToDevice);
+  if (xy && *e == hipSuccess && (*e = xy->alloc(owned.size())) == hipSuccess && bytes) *e = hipMemcpy(*xy, owned_xy.data(), bytes, hipMemcpyHostToDevice);
+  if (*e != hipSuccess) { list.reset(); if (xy) xy->reset(); return list; }
+  *n = (uint32_t)owned.size();
+  return list;
+}
+
 int rebuild_ownership(fh_ctx* ctx)
 {
-  if (ctx->d_owned) { (void)hipFree(ctx->d_owned); ctx->d_owned = nullptr; }
-  if (ctx->d_owned_xy) { (void)hipFree(ctx->d_owned_xy); ctx->d_owned_xy = nullptr; }
+  ctx->d_owned.reset();
+  ctx->d_owned_xy.reset();
   ctx->n_owned = 0;
-  if (ctx->width == 0 || ctx->height == 0) return FH_OK;
   if (ctx->width > 65535u || ctx->height > 65535u) return fail(ctx, FH_E_UNSUPPORTED, "frames wider or higher than 65535 pixels are not supported");
-  std::vector<uint32_t> owned, owned_xy;
-  owned_list(ctx->width, ctx->height, ctx->tile_w, ctx->tile_h, ctx->shard_rank, ctx->shard_world, owned, &owned_xy);
-  ctx->n_owned = (uint32_t)owned.size();
-  FH_HIP(hipMalloc((void**)&ctx->d_owned, owned.empty() ? 16 : owned.size() * 4));
-  FH_HIP(hipMalloc((void**)&ctx->d_owned_xy, owned.empty() ? 16 : owned.size() * 4));
-  if (!owned.empty()) FH_HIP(hipMemcpy(ctx->d_owned, owned.data(), owned.size() * 4, hipMemcpyHostToDevice));
-  if (!owned.empty()) FH_HIP(hipMemcpy(ctx->d_owned_xy, owned_xy.data(), owned_xy.size() * 4, hipMemcpyHostToDevice));
+  hipError_t e = hipSuccess;
+  ctx->d_owned = upload_owned(ctx, ctx->shard_rank, ctx->shard_world, &ctx->n_owned, &e, std::addressof(ctx->d_owned_xy));
+  FH_HIP(e);
   return FH_OK;
 }
 
@@ -442,14 +444,13 @@ int frame_map_ensure(fh_ctx* ctx, uint32_t world)
 {
   // built once per (world, resolution, tile size) and kept, so a presented frame is ONE asynchronous launch
   fh_ctx::FrameMap& fm = ctx->frame_map;
-  if (!(fm.d_all && fm.world == world && fm.width == ctx->width && fm.height == ctx->height && fm.tile_w == ctx->tile_w && fm.tile_h == ctx->tile_h)) {
+  if (!(fm.d_all.get() && fm.world == world && fm.width == ctx->width && fm.height == ctx->height && fm.tile_w == ctx->tile_w && fm.tile_h == ctx->tile_h)) {
     (void)hipStreamSynchronize(ctx->stream);
-    if (fm.d_all) (void)hipFree(fm.d_all);
     fm = fh_ctx::FrameMap{};
     std::vector<uint32_t> all;
     fm.start.assign(world + 1u, 0u);
     for (uint32_t r = 0; r < world; ++r) { owned_list(ctx->width, ctx->height, ctx->tile_w, ctx->tile_h, r, world, all, nullptr); fm.start[r + 1u] = (uint32_t)all.size(); }
-    FH_HIP(hipMalloc((void**)&fm.d_all, all.empty() ? 16 : all.size() * 4));
+    FH_HIP(fm.d_all.alloc(all.size()));
     if (!all.empty()) FH_HIP(hipMemcpy(fm.d_all, all.data(), all.size() * 4, hipMemcpyHostToDevice));
     fm.world = world; fm.width = ctx->width; fm.height = ctx->height; fm.tile_w = ctx->tile_w; fm.tile_h = ctx->tile_h;
   }
@@ -518,14 +519,13 @@ int fh_ctx_create(int device, fh_ctx** out)
   if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return FH_E_HIP; }
   fh_ctx* ctx = new fh_ctx;
   ctx->device = device;
-  auto bail = [&](const char* what) { g_create_error = what; delete ctx; return FH_E_HIP; };
-  auto make_stream = [&](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); };
-  if (make_stream(&ctx->stream) != hipSuccess) return bail("hipStreamCreate failed");
-  if (hipMalloc((void**)&ctx->d_sobol, kSobolMatricesBytes) != hipSuccess) return bail("hipMalloc failed");
-  if (hipMalloc((void**)&ctx->d_lut_refl, kLutReflectionBytes) != hipSuccess) return bail("hipMalloc failed");
-  if (hipMalloc((void**)&ctx->d_lut_sheen, kLutSheenBytes) != hipSuccess) return bail("hipMalloc failed");
-  if (hipMalloc((void**)&ctx->d_trace_counters, 32 * sizeof(unsigned long long)) != hipSuccess) return bail("hipMalloc failed");
-  if (hipMalloc((void**)&ctx->d_hosek, sizeof(fh::HosekSky)) != hipSuccess || hipMemsetAsync(ctx->d_hosek, 0, sizeof(fh::HosekSky), ctx->stream) != hipSuccess) return bail("hipMalloc failed");
+  auto bail = [&](const char* what) { g_create_error = what; delete ctx; return FH_E_HIP; };  // (the context releases what it has made so far)
+  if (ctx->stream.create(hipStreamNonBlocking) != hipSuccess) return bail("stream creation failed");
+  if (ctx->d_sobol.alloc(kSobolMatricesBytes / sizeof(uint32_t)) != hipSuccess) return bail("device allocation failed");
+  if (ctx->d_lut_refl.alloc(kLutReflectionBytes / sizeof(float)) != hipSuccess) return bail("device allocation failed");
+  if (ctx->d_lut_sheen.alloc(kLutSheenBytes / sizeof(float)) != hipSuccess) return bail("device allocation failed");
+  if (ctx->d_trace_counters.alloc(32) != hipSuccess) return bail("device allocation failed");
+  if (ctx->d_hosek.alloc(1) != hipSuccess || hipMemsetAsync(ctx->d_hosek, 0, sizeof(fh::HosekSky), ctx->stream) != hipSuccess) return bail("device allocation failed");
   if (hipMemcpy(ctx->d_sobol, kSobolMatrices, kSobolMatricesBytes, hipMemcpyHostToDevice) != hipSuccess) return bail("table upload failed");
   {
     // byte-indexed form of the generator matrices: entry [dim][k][b] = XOR of the columns 8k + j selected by the bits j of b, so that the XOR over the 32 index
@@ -538,21 +538,19 @@ int fh_ctx_create(int device, fh_ctx** out)
         t[0] = 0u;
         for (uint32_t b = 1; b < 256u; ++b) t[b] = t[b & (b - 1u)] ^ mat[dim * 52u + 8u * k + (uint32_t)__builtin_ctz(b)];
       }
-    if (hipMalloc((void**)&ctx->d_sobol_bytes, bytes.size() * sizeof(uint32_t)) != hipSuccess) return bail("hipMalloc failed");
+    if (ctx->d_sobol_bytes.alloc(bytes.size()) != hipSuccess) return bail("device allocation failed");
     if (hipMemcpy(ctx->d_sobol_bytes, bytes.data(), bytes.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return bail("table upload failed");
   }
   if (hipMemcpy(ctx->d_lut_refl, kLutReflection, kLutReflectionBytes, hipMemcpyHostToDevice) != hipSuccess) return bail("table upload failed");
   if (hipMemcpy(ctx->d_lut_sheen, kLutSheen, kLutSheenBytes, hipMemcpyHostToDevice) != hipSuccess) return bail("table upload failed");
   (void)hipMemsetAsync(ctx->d_trace_counters, 0, 32 * sizeof(unsigned long long), ctx->stream);  // (never hipMemset: it is asynchronous and ordered with nothing on a non-blocking stream)
   for (int k = 0; k < 2; ++k)
-    if (make_stream(&ctx->aux_stream[k]) != hipSuccess) return bail("hipStreamCreate failed");
+    if (ctx->aux_stream[k].create(hipStreamNonBlocking) != hipSuccess) return bail("stream creation failed");
   for (int k = 0; k < 3; ++k) {
-    (void)hipHostMalloc((void**)&ctx->h_counters[k], sizeof(uint32_t) * fh::kCounterStride * 66);
-    (void)hipEventCreate(&ctx->ev_counters[k]);
-    (void)hipEventCreateWithFlags(&ctx->ev_gen[k], hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&ctx->ev_acc[k], hipEventDisableTiming);
+    if (ctx->h_counters[k].alloc((size_t)fh::kCounterStride * 66) != hipSuccess) return bail("pinned allocation failed");
+    if (ctx->ev_counters[k].create() != hipSuccess || ctx->ev_gen[k].create(hipEventDisableTiming) != hipSuccess || ctx->ev_acc[k].create(hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
   }
-  (void)hipEventCreateWithFlags(&ctx->ev_enter, hipEventDisableTiming);
+  if (ctx->ev_enter.create(hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
   if (const char* e = getenv("FH_PIPELINE")) ctx->n_slots = e[0] == '0' ? 1 : (e[0] == '2' ? 2 : 3);
   {
     fh_ctx::Tunables& t = ctx->tun;
@@ -598,14 +596,12 @@ int fh_ctx_create(int device, fh_ctx** out)
     int least = 0, greatest = 0;
     const char* e = getenv("FH_SKY_PRIO");
     const bool low = !(e && e[0] == '0') && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-    if ((low ? hipStreamCreateWithPriority(&ctx->sky_stream, hipStreamNonBlocking, least) : hipStreamCreateWithFlags(&ctx->sky_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate failed");
+    if (ctx->sky_stream.create(hipStreamNonBlocking, low ? least : 0) != hipSuccess) return bail("stream creation failed");
   }
-  (void)hipEventCreateWithFlags(&ctx->ev_sky, hipEventDisableTiming);
-  (void)hipEventCreateWithFlags(&ctx->ev_sky_cursor, hipEventDisableTiming);
-  if (hipMalloc((void**)&ctx->d_split_counters, 16) != hipSuccess) return bail("hipMalloc failed");
+  if (ctx->ev_sky.create(hipEventDisableTiming) != hipSuccess || ctx->ev_sky_cursor.create(hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
+  if (ctx->d_split_counters.alloc(4) != hipSuccess) return bail("device allocation failed");
   (void)hipMemsetAsync(ctx->d_split_counters, 0, 16, ctx->stream);
-  (void)hipEventCreate(&ctx->ev_render_begin);
-  (void)hipEventCreate(&ctx->ev_render_end);
+  if (ctx->ev_render_begin.create() != hipSuccess || ctx->ev_render_end.create() != hipSuccess) return bail("event creation failed");
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail("hipStreamSynchronize failed");  // the fills above are done before any upload (synchronous copies, ordered with no stream) touches what they cleared
   *out = ctx;
   return FH_OK;
@@ -616,43 +612,8 @@ int fh_ctx_destroy(fh_ctx* ctx)
   FH_GROUP(ctx, group_destroy(ctx));
   if (!ctx) return FH_E_INVALID;
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  pool_release(ctx);
-  void* ptrs[] = {ctx->d_sample_issued, ctx->d_sobol, ctx->d_sobol_bytes, ctx->d_alpha_rec, ctx->d_lut_refl, ctx->d_lut_sheen, ctx->d_face_rec, ctx->d_face_cls, ctx->d_materials, ctx->d_lights, ctx->d_bvh2_nodes, ctx->d_bvh2_tris,
-                  ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_sample_count, ctx->d_owned, ctx->d_trace_counters, ctx->d_texels, ctx->d_textures, ctx->d_srgb_lut, ctx->d_ibl,
-                  ctx->d_bloom_weights, ctx->d_meter, ctx->d_meter_slabs, ctx->d_quirk_seen, ctx->d_quirk_aov, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices, ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o,
-                  ctx->d_bvh8_box, ctx->d_denoise_tmp[0], ctx->d_denoise_tmp[1], ctx->d_guided_cv[0], ctx->d_guided_cv[1], ctx->d_guided_var[0], ctx->d_guided_var[1], ctx->d_hist_cv[0], ctx->d_hist_cv[1], ctx->d_hist_ph[0], ctx->d_hist_ph[1], ctx->d_hist_n[0], ctx->d_hist_n[1], ctx->d_hist_mu[0], ctx->d_hist_mu[1], ctx->d_motion, ctx->d_motion_ids, ctx->d_hosek, ctx->d_owned_xy, ctx->d_stack_spill, ctx->d_bvh8_parent, ctx->d_face_node,
-                  ctx->d_moments, ctx->d_active[0], ctx->d_active[1], ctx->d_active[2], ctx->d_active[3], ctx->d_block_marks, ctx->d_active_blocks, ctx->d_sky_taken, ctx->d_sky_adaptive};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (fh_ctx::ShardList& c : ctx->shard_lists)
-    if (c.d_owned) (void)hipFree(c.d_owned);
-  if (ctx->frame_map.d_all) (void)hipFree(ctx->frame_map.d_all);
-  for (int k = 0; k < 4; ++k) if (ctx->d_split[k]) (void)hipFree(ctx->d_split[k]);
-  if (ctx->d_split_counters) (void)hipFree(ctx->d_split_counters);
-  if (ctx->h_active_count) (void)hipHostFree(ctx->h_active_count);
-  if (ctx->h_motion) (void)hipHostFree(ctx->h_motion);
-  if (ctx->ev_motion) (void)hipEventDestroy(ctx->ev_motion);
-  if (ctx->sky_stream) { (void)hipStreamSynchronize(ctx->sky_stream); (void)hipStreamDestroy(ctx->sky_stream); }
-  if (ctx->ev_sky) (void)hipEventDestroy(ctx->ev_sky);
-  if (ctx->ev_sky_cursor) (void)hipEventDestroy(ctx->ev_sky_cursor);
-  for (auto& s : ctx->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
-  for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-  for (auto e : ctx->ev_bounce) (void)hipEventDestroy(e);
-  for (int k = 0; k < 3; ++k) {
-  }
-  for (int k = 0; k < 3; ++k) {
-    if (ctx->h_counters[k]) (void)hipHostFree(ctx->h_counters[k]);
-    (void)hipEventDestroy(ctx->ev_counters[k]);
-    (void)hipEventDestroy(ctx->ev_gen[k]);
-    (void)hipEventDestroy(ctx->ev_acc[k]);
-  }
-  (void)hipEventDestroy(ctx->ev_enter);
-  for (int k = 0; k < 2; ++k) (void)hipStreamDestroy(ctx->aux_stream[k]);
-  (void)hipEventDestroy(ctx->ev_render_begin);
-  (void)hipEventDestroy(ctx->ev_render_end);
-  (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  for (const Stream* st : {std::addressof(ctx->stream), std::addressof(ctx->aux_stream[0]), std::addressof(ctx->aux_stream[1]), std::addressof(ctx->sky_stream)}) (void)hipStreamSynchronize(*st);
+  delete ctx;  // (the members release themselves, the streams last: context.h)
   return FH_OK;
 }
 
@@ -882,8 +843,7 @@ int fh_load_ibl(fh_ctx* ctx, const float* rgba, uint32_t w, uint32_t h)
   CTX_CHECK(ctx);
   if (!rgba || w == 0 || h == 0) return fail(ctx, FH_E_INVALID, "fh_load_ibl: empty image");
   (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->d_ibl) { (void)hipFree(ctx->d_ibl); ctx->d_ibl = nullptr; }
-  FH_HIP(hipMalloc((void**)&ctx->d_ibl, sizeof(float) * 4ull * w * h));
+  FH_HIP(ctx->d_ibl.alloc(4ull * w * h));
   FH_HIP(hipMemcpy(ctx->d_ibl, rgba, sizeof(float) * 4ull * w * h, hipMemcpyHostToDevice));
   ctx->ibl_w = w;
   ctx->ibl_h = h;
@@ -894,7 +854,7 @@ int fh_clear_ibl(fh_ctx* ctx)
   FH_GROUP_EACH(ctx, kGroupCallScene, fh_clear_ibl(m_));
   CTX_CHECK(ctx);
   (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->d_ibl) { (void)hipFree(ctx->d_ibl); ctx->d_ibl = nullptr; }
+  ctx->d_ibl.reset();
   return FH_OK;
 }
 
@@ -905,9 +865,9 @@ static int adaptive_reset(fh_ctx* ctx)
   ctx->adapt_total = 0;
   if (!ctx->adaptive) return FH_OK;
   const size_t px = (size_t)ctx->width * ctx->height;
-  if (!ctx->d_moments) FH_HIP(hipMalloc((void**)&ctx->d_moments, 8ull * px));
+  if (!ctx->d_moments) FH_HIP(ctx->d_moments.alloc(px));
   if (!ctx->d_sky_taken) {
-    FH_HIP(hipMalloc((void**)&ctx->d_sky_taken, sizeof(unsigned long long)));
+    FH_HIP(ctx->d_sky_taken.alloc(1));
     FH_HIP(hipMemsetAsync(ctx->d_sky_taken, 0, sizeof(unsigned long long), ctx->stream));
   }
   FH_HIP(hipMemsetAsync(ctx->d_moments, 0, 8ull * px, ctx->stream));
@@ -1061,12 +1021,12 @@ int fh_set_resolution(fh_ctx* ctx, uint32_t w, uint32_t h)
   if (w == 0 || h == 0) return fail(ctx, FH_E_INVALID, "zero resolution");
   if (w > 65535u || h > 65535u) return fail(ctx, FH_E_UNSUPPORTED, "frames wider or higher than 65535 pixels are not supported");  // (before anything is changed: the context keeps its resolution)
   (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->d_sample_count) { (void)hipFree(ctx->d_sample_count); ctx->d_sample_count = nullptr; }
-  if (ctx->d_sample_issued) { (void)hipFree(ctx->d_sample_issued); ctx->d_sample_issued = nullptr; }
-  if (ctx->d_moments) { (void)hipFree(ctx->d_moments); ctx->d_moments = nullptr; }  // (fh_init_render_states below makes it again at the new size if the mode is on)
+  ctx->d_sample_count.reset();
+  ctx->d_sample_issued.reset();
+  ctx->d_moments.reset();  // (fh_init_render_states below makes it again at the new size if the mode is on)
   ctx->width = w; ctx->height = h;
-  FH_HIP(hipMalloc((void**)&ctx->d_sample_count, 4ull * w * h));
-  FH_HIP(hipMalloc((void**)&ctx->d_sample_issued, 4ull * w * h));
+  FH_HIP(ctx->d_sample_count.alloc((size_t)w * h));
+  FH_HIP(ctx->d_sample_issued.alloc((size_t)w * h));
   const int rc = rebuild_ownership(ctx);
   if (rc) return rc;
   return fh_init_render_states(ctx);
@@ -1114,17 +1074,15 @@ int fh_unpack_shard(fh_ctx* ctx, uint32_t rank, uint32_t world, const float* pac
   for (fh_ctx::ShardList& c : ctx->shard_lists)
     if (c.rank == rank && c.world == world && c.width == ctx->width && c.height == ctx->height && c.tile_w == ctx->tile_w && c.tile_h == ctx->tile_h) sl = &c;
   if (!sl) {
-    fh_ctx tmp;
-    tmp.device = ctx->device; tmp.width = ctx->width; tmp.height = ctx->height; tmp.tile_w = ctx->tile_w; tmp.tile_h = ctx->tile_h; tmp.shard_rank = rank; tmp.shard_world = world;
-    const int rc = rebuild_ownership(&tmp);
-    if (rc) { ctx->err = tmp.err; return rc; }
-    if (tmp.d_owned_xy) (void)hipFree(tmp.d_owned_xy);
+    uint32_t n = 0;
+    hipError_t e = hipSuccess;
+    DeviceBuffer<uint32_t> list = upload_owned(ctx, rank, world, &n, &e);
+    FH_HIP(e);
     if (ctx->shard_lists.size() >= 64u) {  // (a caller cycling through many splits: drop the oldest)
       (void)hipStreamSynchronize(ctx->stream);
-      if (ctx->shard_lists.front().d_owned) (void)hipFree(ctx->shard_lists.front().d_owned);
       ctx->shard_lists.erase(ctx->shard_lists.begin());
     }
-    ctx->shard_lists.push_back(fh_ctx::ShardList{rank, world, ctx->width, ctx->height, ctx->tile_w, ctx->tile_h, tmp.d_owned, tmp.n_owned});
+    ctx->shard_lists.push_back(fh_ctx::ShardList{rank, world, ctx->width, ctx->height, ctx->tile_w, ctx->tile_h, std::move(list), n});
     sl = &ctx->shard_lists.back();
   }
   if (sl->n_owned) hipLaunchKernelGGL(k_unpack, dim3((sl->n_owned * fpp + 255) / 256), dim3(256), 0, ctx->stream, packed, sl->d_owned, sl->n_owned, fpp, layer);
@@ -1189,8 +1147,8 @@ int fh_sync(fh_ctx* ctx)
       else if (s.kind == 7) ctx->stats.post_ms += ms;
       else ctx->stats.shade_ms += ms;
     }
-    ctx->event_pool.push_back(s.a);
-    ctx->event_pool.push_back(s.b);
+    ctx->event_pool.push_back(std::move(s.a));
+    ctx->event_pool.push_back(std::move(s.b));
   }
   ctx->spans.clear();
   if (ctx->sky_taken_pending) {  // samples the adaptive k_sky_pixels took (it stops pixels on the device)
@@ -1376,12 +1334,9 @@ int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_d
       if (!motion_finite(table[i])) return fail(ctx, FH_E_INVALID, "fh_denoise_temporal: the motion of an instance is not finite (fh_set_denoise_motion)");
     }
     const size_t px = (size_t)width * height;
-    if (ctx->motion_ids_pixels < px) {
+    if (ctx->d_motion_ids.size() < px) {
       (void)hipStreamSynchronize(ctx->stream);
-      if (ctx->d_motion_ids) (void)hipFree(ctx->d_motion_ids);
-      ctx->d_motion_ids = nullptr; ctx->motion_ids_pixels = 0;
-      FH_HIP(hipMalloc((void**)&ctx->d_motion_ids, px * sizeof(uint32_t)));
-      ctx->motion_ids_pixels = px;
+      FH_HIP(ctx->d_motion_ids.alloc(px));
     }
     if ((rc = primary_instances_submit(ctx, camera, width, height, ctx->d_motion_ids))) return rc;
     rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, ctx->d_motion_ids, ni, table.data(), denoised, upscale2x ? 1 : 0);
@@ -1453,8 +1408,7 @@ int fh_set_denoise_temporal_moments(fh_ctx* ctx, const fh_temporal_moments_param
     if (!on && (ctx->d_hist_mu[0] || ctx->d_hist_mu[1])) {
       if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, FH_E_HIP, "hipSetDevice failed");
       (void)hipStreamSynchronize(ctx->stream);  // (a call queued earlier may still write them)
-      for (int k = 0; k < 2; ++k) { if (ctx->d_hist_mu[k]) (void)hipFree(ctx->d_hist_mu[k]); ctx->d_hist_mu[k] = nullptr; }
-      ctx->hist_mu_pixels = 0;
+      for (int k = 0; k < 2; ++k) ctx->d_hist_mu[k].reset();
     }
   }
   ctx->denoise_temporal_moments = on;

@@ -10,6 +10,7 @@
 
 #include "../../include/fredholm_hip.h"
 #include "fh_device.h"
+#include "fh_memory.h"
 
 struct fh_group;  // group.hip
 
@@ -19,16 +20,18 @@ struct fh_ctx {
   fh_ctx* owner = nullptr;
   uint32_t member_index = 0;
   int device = 0;
-  hipStream_t stream = nullptr;   // main stream: everything the caller can observe is ordered on it
-  hipStream_t aux_stream[2] = {nullptr, nullptr};  // passes j % n_slots != 0 of fh_render run here, overlapping the latency-bound ends of the passes before
+  // the streams come first: members are destroyed in reverse order, so whatever may be in flight on a stream is released before the stream itself
+  fh::Stream stream;   // main stream: everything the caller can observe is ordered on it
+  fh::Stream aux_stream[2];  // passes j % n_slots != 0 of fh_render run here, overlapping the latency-bound ends of the passes before
+  fh::Stream sky_stream;
   std::string err;
   uint32_t flags = 0;
 
   // constant tables
-  uint32_t* d_sobol = nullptr;
-  uint32_t* d_sobol_bytes = nullptr;  // [1024 dims][4 index bytes][256]: byte-indexed generator matrices (capi.hip: fh_ctx_create)
-  float* d_lut_refl = nullptr;
-  float* d_lut_sheen = nullptr;
+  fh::DeviceBuffer<uint32_t> d_sobol;
+  fh::DeviceBuffer<uint32_t> d_sobol_bytes;  // [1024 dims][4 index bytes][256]: byte-indexed generator matrices (capi.hip: fh_ctx_create)
+  fh::DeviceBuffer<float> d_lut_refl;
+  fh::DeviceBuffer<float> d_lut_sheen;
 
   // host copy of the flat scene (transforms can change: Renderer::set_time)
   std::vector<float> h_vertices, h_normals, h_texcoords;
@@ -38,19 +41,18 @@ struct fh_ctx {
   bool scene_loaded = false, bvh_valid = false;
 
   // device scene
-  float4* d_face_rec = nullptr;
-  uint8_t* d_face_cls = nullptr;
-  fh::MaterialDev* d_materials = nullptr;
-  fh::AreaLightDev* d_lights = nullptr;
+  fh::DeviceBuffer<float4> d_face_rec;
+  fh::DeviceBuffer<uint8_t> d_face_cls;
+  fh::DeviceBuffer<fh::MaterialDev> d_materials;
+  fh::DeviceBuffer<fh::AreaLightDev> d_lights;
   // object-space geometry resident on the device: the face records above are recomputed from it when the instance transforms change
-  float* d_obj_vertices = nullptr;
-  float* d_obj_normals = nullptr;
-  float* d_obj_texcoords = nullptr;
-  uint32_t* d_obj_indices = nullptr;
-  uint2* d_face_meta = nullptr;  // (material id, instance id) per face
-  float4* d_o2w = nullptr;       // 3 rows per instance
-  float4* d_w2o = nullptr;
-  uint32_t n_xf_alloc = 0;
+  fh::DeviceBuffer<float> d_obj_vertices;
+  fh::DeviceBuffer<float> d_obj_normals;
+  fh::DeviceBuffer<float> d_obj_texcoords;
+  fh::DeviceBuffer<uint32_t> d_obj_indices;
+  fh::DeviceBuffer<uint2> d_face_meta;  // (material id, instance id) per face
+  fh::DeviceBuffer<float4> d_o2w;       // 3 rows per instance
+  fh::DeviceBuffer<float4> d_w2o;
   // textures (renderer.h:372-386): one device blob of texels + descriptors + the sRGB table
   // per texture: can a filtered fetch of its alpha channel / of its red channel come out below the any-hit threshold 0.5 (upload_textures)?
   std::vector<uint8_t> h_tex_alpha_cuts, h_tex_red_cuts;
@@ -59,29 +61,29 @@ struct fh_ctx {
   std::vector<HostTexture> h_tex_host;  // texels of the textures that can cut, kept on the host: per-face opacity classes (capi.hip: footprint_class)
   unsigned long long alpha_cell_counts[3] = {0, 0, 0};  // micromap cells of the faces that keep their test; of them: always pass, never pass (fh_alpha_cell_counts)
   uint32_t alpha_face_counts[4] = {0, 0, 0, 0};  // faces whose textures can cut; of them: always pass, never pass, still tested (fh_alpha_face_counts)
-  uint4* d_alpha_rec = nullptr;         // 8 x 16 bytes per face when the scene has cut-outs: what the any-hit test of that face reads (4) and the face's opacity micromap (4) (fh_trace.h: alpha_pass)
-  uint8_t* d_texels = nullptr;
-  fht_texture* d_textures = nullptr;
-  float* d_srgb_lut = nullptr;
+  fh::DeviceBuffer<uint4> d_alpha_rec;         // 8 x 16 bytes per face when the scene has cut-outs: what the any-hit test of that face reads (4) and the face's opacity micromap (4) (fh_trace.h: alpha_pass)
+  fh::DeviceBuffer<uint8_t> d_texels;
+  fh::DeviceBuffer<fht_texture> d_textures;
+  fh::DeviceBuffer<float> d_srgb_lut;
   uint32_t n_textures = 0;
   bool has_alpha = false;
-  float* d_ibl = nullptr;
+  fh::DeviceBuffer<float> d_ibl;
   uint32_t ibl_w = 0, ibl_h = 0;
   uint32_t n_faces = 0, n_lights = 0, n_materials = 0;
   uint32_t n_classes = 0;
   uint32_t class_lobes[fh::kMaxClasses] = {};
 
   // BVH
-  float4* d_bvh2_nodes = nullptr;
-  float4* d_bvh2_tris = nullptr;
+  fh::DeviceBuffer<float4> d_bvh2_nodes;
+  fh::DeviceBuffer<float4> d_bvh2_tris;
   uint32_t bvh2_n_nodes = 0, bvh2_n_tris = 0;
-  uint4* d_bvh8_nodes = nullptr;
-  float4* d_bvh8_tris = nullptr;
+  fh::DeviceBuffer<uint4> d_bvh8_nodes;
+  fh::DeviceBuffer<float4> d_bvh8_tris;
   uint32_t bvh8_n_nodes = 0, bvh8_n_tris = 0;
-  uint32_t* d_bvh8_parent = nullptr;  // per wide node: parent << 3 | child slot in the parent (root: 0xffffffff)
-  uint32_t* d_face_node = nullptr;    // per face: the wide node that holds it (bottom-up start of the rays that leave it, fh_trace.h)
+  fh::DeviceBuffer<uint32_t> d_bvh8_parent;  // per wide node: parent << 3 | child slot in the parent (root: 0xffffffff)
+  fh::DeviceBuffer<uint32_t> d_face_node;    // per face: the wide node that holds it (bottom-up start of the rays that leave it, fh_trace.h)
   // kept after a full build so that a change of instance transforms refits the wide tree instead of rebuilding it (bvh_build.hip)
-  float4* d_bvh8_box = nullptr;             // full-precision (lo, hi) of every wide node
+  fh::DeviceBuffer<float4> d_bvh8_box;             // full-precision (lo, hi) of every wide node
   std::vector<uint32_t> bvh8_level_start;   // node index range of every level (levels are contiguous: the collapse is breadth first)
   bool refit_ok = false;                    // topology unchanged since the last full build, no split references
   double bvh8_area_built = 0.0;             // sum of the node areas right after the full build (quality reference for refits)
@@ -91,8 +93,7 @@ struct fh_ctx {
   uint32_t info_blocks[2] = {0, 0}, info_entries[2] = {0, 0};  // the same two facts for the uninstrumented closest-hit / secondary kernels as last launched (fh_kernel_info)
   uint32_t lds_configured_bytes = 0;  // dynamic-LDS size the traversal kernels were last configured for (render.hip)
   uint32_t stream_lds_entries = 0, stream_lds_entries_secondary = 0;    // stack levels the closest-hit / secondary streaming kernel keeps in LDS (the rest spills to d_stack_spill)
-  uint2* d_stack_spill = nullptr;     // [6 launches in flight][entry beyond the LDS part][thread of the launch]
-  size_t stack_spill_capacity = 0;    // in uint2
+  fh::DeviceBuffer<uint2> d_stack_spill;  // [6 launches in flight][entry beyond the LDS part][thread of the launch]
   uint32_t lds_static_max = 0;        // largest static LDS of a kernel that keeps its traversal stack in dynamic LDS (hipFuncGetAttributes; render.hip: configure_traversal_lds)
   bool use_bvh8 = false;
   int builder_choice = 0;  // 0 = not decided for this scene, 1 = radix tree (LBVH), 2 = PLOC; decided at the first build after an upload
@@ -101,44 +102,41 @@ struct fh_ctx {
 
   // frame state
   uint32_t width = 0, height = 0;
-  uint32_t* d_sample_count = nullptr;   // samples accumulated per pixel (written by k_accumulate)
-  uint32_t* d_sample_issued = nullptr;  // samples started per pixel (written after k_generate): the next pass does not wait for the accumulate
+  fh::DeviceBuffer<uint32_t> d_sample_count;   // samples accumulated per pixel (written by k_accumulate)
+  fh::DeviceBuffer<uint32_t> d_sample_issued;  // samples started per pixel (written after k_generate): the next pass does not wait for the accumulate
   uint32_t shard_rank = 0, shard_world = 1, tile_w = 32, tile_h = 32;
-  uint32_t* d_owned = nullptr;  // image indices of owned pixels, in tile order
-  uint32_t* d_owned_xy = nullptr;  // the same pixels as x | y << 16
+  fh::DeviceBuffer<uint32_t> d_owned;  // image indices of owned pixels, in tile order
+  fh::DeviceBuffer<uint32_t> d_owned_xy;  // the same pixels as x | y << 16
   uint32_t n_owned = 0;
   // pixels that cannot see the scene (render.hip: k_split_pixels / k_sky_pixels): [0] / [1] image indices and x | y << 16 of the pixels the passes render, [2] / [3] of the sky pixels
-  uint32_t* d_split[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint32_t split_capacity = 0, n_wave_px = 0, n_sky_px = 0;
-  uint32_t* d_split_counters = nullptr;  // wave pixels, sky pixels, bounds-test violations seen by k_sky_pixels, k_sky_pixels' cursor over the groups of its list
+  fh::DeviceBuffer<uint32_t> d_split[4];
+  uint32_t n_wave_px = 0, n_sky_px = 0;
+  fh::DeviceBuffer<uint32_t> d_split_counters;  // wave pixels, sky pixels, bounds-test violations seen by k_sky_pixels, k_sky_pixels' cursor over the groups of its list
   bool split_valid = false;
   float split_key[32] = {};              // camera, scene bounds, resolution and ownership the lists were made for
-  hipStream_t sky_stream = nullptr;
-  hipEvent_t ev_sky = nullptr;
-  hipEvent_t ev_sky_cursor = nullptr;  // the cursor has been cleared on the main stream: the filler launch on the sky stream follows it
-  struct ShardList { uint32_t rank, world, width, height, tile_w, tile_h; uint32_t* d_owned; uint32_t n_owned; };
+  fh::Event ev_sky;
+  fh::Event ev_sky_cursor;  // the cursor has been cleared on the main stream: the filler launch on the sky stream follows it
+  struct ShardList { uint32_t rank, world, width, height, tile_w, tile_h; fh::DeviceBuffer<uint32_t> d_owned; uint32_t n_owned; };
   // fh_unpack_shards: the ownership lists of all ranks of a split one after the other (a permutation of the frame) and where each rank's begins
-  struct FrameMap { uint32_t world = 0, width = 0, height = 0, tile_w = 0, tile_h = 0; uint32_t* d_all = nullptr; std::vector<uint32_t> start; };
+  struct FrameMap { uint32_t world = 0, width = 0, height = 0, tile_w = 0, tile_h = 0; fh::DeviceBuffer<uint32_t> d_all; std::vector<uint32_t> start; };
   FrameMap frame_map;
   std::vector<ShardList> shard_lists;  // ownership lists of other ranks' shards, built on first use by fh_unpack_shard and kept (freed with the context)
   // adaptive sampling (fh_set_adaptive_sampling; render.hip: k_adaptive_select and the round loop of render_submit)
   bool adaptive = false;
   fh_adaptive_params adapt{};
-  float2* d_moments = nullptr;         // (m1, m2) per pixel of the frame, cleared by fh_init_render_states
+  fh::DeviceBuffer<float2> d_moments;         // (m1, m2) per pixel of the frame, cleared by fh_init_render_states
   bool accumulated = false;            // a call has submitted samples since fh_init_render_states / fh_set_resolution
   uint32_t adapt_total = 0;            // samples requested since then: the count every pixel still active shares (rounds end where it is a multiple of step)
-  uint32_t* d_active[4] = {nullptr, nullptr, nullptr, nullptr};  // the active pixels of the round: image indices, x | y << 16 (a stable compaction of the call's base list); [2] / [3]: of its sky list (guard blocks only)
-  uint32_t* d_active_blocks = nullptr; // per-workgroup counts, then their exclusive scan; word [capacity blocks] = the active count (twice: the base list, the sky list)
-  uint32_t active_capacity = 0;
-  uint32_t* h_active_count = nullptr;  // pinned: the counts read back at every boundary (base list, sky list)
+  fh::DeviceBuffer<uint32_t> d_active[4];  // the active pixels of the round: image indices, x | y << 16 (a stable compaction of the call's base list); [2] / [3]: of its sky list (guard blocks only)
+  fh::DeviceBuffer<uint32_t> d_active_blocks; // per-workgroup counts, then their exclusive scan; word [capacity blocks] = the active count (twice: the base list, the sky list)
+  fh::PinnedBuffer<uint32_t> h_active_count;  // pinned: the counts read back at every boundary (base list, sky list)
   // fh_set_adaptive_policy: guard blocks of adapt_block x adapt_block pixels stop together, boundaries grow by adapt_growth (render.hip: k_adaptive_mark, adaptive_to_boundary)
   uint32_t adapt_block = 1, adapt_growth = 1;
-  uint32_t* d_block_marks = nullptr;   // one word per guard block of the frame: the sequence number of the last selection that found an unconverged pixel in it
-  size_t marks_capacity = 0;
+  fh::DeviceBuffer<uint32_t> d_block_marks;   // one word per guard block of the frame: the sequence number of the last selection that found an unconverged pixel in it
   uint32_t mark_seq = 0;
-  unsigned long long* d_sky_taken = nullptr;  // samples the adaptive k_sky_pixels took since the last fh_sync (fh_stats.paths)
+  fh::DeviceBuffer<unsigned long long> d_sky_taken;  // samples the adaptive k_sky_pixels took since the last fh_sync (fh_stats.paths)
   bool sky_taken_pending = false;
-  void* d_sky_adaptive = nullptr;      // the adaptive k_sky_pixels' arguments beyond the plain form's (render.hip: SkyAdaptive)
+  fh::DeviceBuffer<uint8_t> d_sky_adaptive;      // the adaptive k_sky_pixels' arguments beyond the plain form's (render.hip: SkyAdaptive)
 
   // environment (renderer.h:819-827)
   bool has_dir = false;
@@ -147,13 +145,13 @@ struct fh_ctx {
   float sun_dir[3] = {0.0f, 1.0f, 0.0f};
   bool has_hosek = false;
   fh::HosekSky hosek{};
-  fh::HosekSky* d_hosek = nullptr;  // device copy (FrameDev::hosek)
+  fh::DeviceBuffer<fh::HosekSky> d_hosek;  // device copy (FrameDev::hosek)
 
   // path pools: one per pass in flight (pass j uses slot j % n_slots and the stream of that slot); allocated on first use
   fh::PoolDev pool[3] = {};
   struct PoolShape { bool dir = false, lights = false; uint32_t classes = 0; };  // what the records of a pool have room for (render.hip: pool_ensure)
   PoolShape pool_shape[3];
-  std::vector<void*> pool_allocs[3];
+  std::vector<fh::DeviceBuffer<uint8_t>> pool_allocs[3];
   unsigned long long pool_alloc_bytes[3] = {0, 0, 0};  // device memory the allocations of each pool hold (fh_path_pool_allocated)
   // 32 Mi path slots per pool: 16 samples per pixel per pass at 1080p.  Three pools (one per pass in flight) of 284-436 bytes per path are 27-42 GB when a call brings enough
   // samples to fill them; unless the caller chose the size (fh_set_path_pool), fh_render keeps all pools together within half of the device memory that is free when the first one is made
@@ -169,8 +167,8 @@ struct fh_ctx {
   // snapshot's wavefront bounces are an earlier pass's.
   double survival[66] = {};
   uint32_t survival_n = 0;
-  uint32_t* h_counters[3] = {nullptr, nullptr, nullptr};  // pinned snapshots of the per-bounce counters of a finished pass
-  hipEvent_t ev_counters[3] = {nullptr, nullptr, nullptr};
+  fh::PinnedBuffer<uint32_t> h_counters[3];  // pinned snapshots of the per-bounce counters of a finished pass
+  fh::Event ev_counters[3];
   bool counters_in_flight[3] = {false, false, false};
   uint32_t counters_wave_depth[3] = {0, 0, 0};  // wave depth used by the pass the snapshot comes from
   uint32_t counters_paths[3] = {0, 0, 0};       // ... and the paths it started
@@ -179,15 +177,14 @@ struct fh_ctx {
   uint32_t bu_toggle = 0;
   double bu_cost[2] = {0.0, 0.0}, bu_items[2] = {0.0, 0.0};
   unsigned long long pass_seq = 0;           // passes submitted so far
-  hipEvent_t ev_gen[3] = {nullptr, nullptr, nullptr}, ev_acc[3] = {nullptr, nullptr, nullptr}, ev_enter = nullptr;
+  fh::Event ev_gen[3], ev_acc[3], ev_enter;
   bool gen_valid[3] = {false, false, false}, acc_valid[3] = {false, false, false};
   int n_slots = 3;  // passes in flight (FH_PIPELINE=0: 1, every pass on the main stream; =2: two).  Three against two: +2.3 % on configs[2], +0.3-0.9 % on the others, one more path pool
   int last_slot_used = 0;  // slot of the pass submitted last (what the next pass orders itself after)
-  std::vector<hipEvent_t> ev_bounce;  // single-pass calls: (shade done, secondary done) per bounce, for the secondary launch on a second stream (render.hip)
+  std::vector<fh::Event> ev_bounce;  // single-pass calls: (shade done, secondary done) per bounce, for the secondary launch on a second stream (render.hip)
   // FH_FLAG_REFERENCE_FIRSTHIT (render.hip: k_firsthit_scan): per-pixel "a sample of this launch has hit something" + the AOVs of that hit
-  uint32_t* d_quirk_seen = nullptr;
-  float4* d_quirk_aov = nullptr;
-  size_t quirk_pixels = 0;
+  fh::DeviceBuffer<uint32_t> d_quirk_seen;
+  fh::DeviceBuffer<float4> d_quirk_aov;
 
   // device facts and developer switches, read ONCE at fh_ctx_create (fh_render does no getenv / hipGetDeviceProperties)
   struct Tunables {
@@ -226,30 +223,26 @@ struct fh_ctx {
   } tun;
 
   // bloom weights of the last sigma used (post.hip): no allocation, upload or host synchronisation per frame
-  float* d_bloom_weights = nullptr;
+  fh::DeviceBuffer<float> d_bloom_weights;
   float bloom_sigma_cached = -1.0f, bloom_wsum = 0.0f;
 
   // fh_set_auto_exposure (post.hip: k_meter_histogram, k_meter_resolve, k_tone_map_metered).  d_meter: the state, the exposure word and the summed histogram
   // (post.hip: MeterDev), allocated when the switch first goes on; d_meter_slabs: 257 words per workgroup of the metering launch, grown on demand
   int auto_exposure = 0;
   fh_auto_exposure_params ae_params = {0.18f, 0.0f, -16.0f, 16.0f, 0.10f, 0.90f, 3.0f, 1.0f, 1.0f / 30.0f, -16.0f, 16.0f, 0u};
-  void* d_meter = nullptr;
-  uint32_t* d_meter_slabs = nullptr;
-  uint32_t meter_slab_blocks = 0;
+  fh::DeviceBuffer<uint8_t> d_meter;
+  fh::DeviceBuffer<uint32_t> d_meter_slabs;
 
   // denoiser slot (post.hip): ping-pong buffers of the a-trous filter
-  float4* d_denoise_tmp[2] = {nullptr, nullptr};
-  size_t denoise_pixels = 0;
+  fh::DeviceBuffer<float4> d_denoise_tmp[2];
   // variance-guided denoiser (denoise.hip): ping-pong (colour, variance) images and dense variance planes
-  float4* d_guided_cv[2] = {nullptr, nullptr};
-  float* d_guided_var[2] = {nullptr, nullptr};
-  size_t guided_pixels = 0;
+  fh::DeviceBuffer<float4> d_guided_cv[2];
+  fh::DeviceBuffer<float> d_guided_var[2];
   // temporal accumulation (denoise.hip: fh_denoise_temporal): the history, double buffered -- per pixel (c_acc.rgb, v_acc), (P, h) and N -- with the camera of the
   // call that wrote buffer `hist_cur`, that camera's world-to-camera rows and its cam_inv_tan.  hist_frames = 0: there is no history.
-  float4* d_hist_cv[2] = {nullptr, nullptr};
-  float4* d_hist_ph[2] = {nullptr, nullptr};
-  float4* d_hist_n[2] = {nullptr, nullptr};
-  size_t hist_pixels = 0;
+  fh::DeviceBuffer<float4> d_hist_cv[2];
+  fh::DeviceBuffer<float4> d_hist_ph[2];
+  fh::DeviceBuffer<float4> d_hist_n[2];
   uint32_t hist_w = 0, hist_h = 0, hist_frames = 0;
   int hist_cur = 0;
   fh_camera hist_camera{};
@@ -260,12 +253,10 @@ struct fh_ctx {
   // d_motion_ids is the id plane of the calls the context feeds itself.
   int denoise_motion = 0;
   std::vector<float> hist_o2w, hist_w2o;
-  fh_motion* d_motion = nullptr;
-  fh_motion* h_motion = nullptr;
-  uint32_t motion_capacity = 0;
-  hipEvent_t ev_motion = nullptr;
-  uint32_t* d_motion_ids = nullptr;
-  size_t motion_ids_pixels = 0;
+  fh::DeviceBuffer<fh_motion> d_motion;
+  fh::PinnedBuffer<fh_motion> h_motion;
+  fh::Event ev_motion;
+  fh::DeviceBuffer<uint32_t> d_motion_ids;
   // fh_set_denoise_response (denoise.hip: k_temporal<., kClipColour>): while on, the temporal stage clips the history it found to the current frame's 5 x 5 colour box
   int denoise_response = 0;
   float response_gamma = 1.0f;
@@ -276,16 +267,15 @@ struct fh_ctx {
   // without sample moments takes its variance from them once a pixel's history is moments_min_history long.  Allocated by the first call with the switch on.
   int denoise_temporal_moments = 0;
   float moments_min_history = 2.0f;
-  float2* d_hist_mu[2] = {nullptr, nullptr};
-  size_t hist_mu_pixels = 0;
+  fh::DeviceBuffer<float2> d_hist_mu[2];
 
   // stats
   fh_stats stats{};
-  unsigned long long* d_trace_counters = nullptr;  // nodes, tris, rays of the closest-hit kernel, then of the secondary kernel
-  struct TimedSpan { hipEvent_t a, b; int kind; };
+  fh::DeviceBuffer<unsigned long long> d_trace_counters;  // nodes, tris, rays of the closest-hit kernel, then of the secondary kernel
+  struct TimedSpan { fh::Event a, b; int kind; };
   std::vector<TimedSpan> spans;
-  std::vector<hipEvent_t> event_pool;
-  hipEvent_t ev_render_begin = nullptr, ev_render_end = nullptr;
+  std::vector<fh::Event> event_pool;
+  fh::Event ev_render_begin, ev_render_end;
   bool render_pending = false;
 };
 
@@ -323,6 +313,7 @@ int group_path_pool_allocated(fh_ctx* g, uint64_t* bytes, uint64_t* paths);
 int frame_map_ensure(fh_ctx* ctx, uint32_t world);  // capi.hip: ctx->frame_map for `world` ranks at the context's resolution and tile size
 uint32_t owned_count(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, uint32_t rank, uint32_t world);  // capi.hip
 
+Event take_event(fh_ctx* ctx);  // render.hip: a timing event from ctx->event_pool, or a new one
 SceneDev scene_dev(const fh_ctx* ctx);
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);  // render.hip

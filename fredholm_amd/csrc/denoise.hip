@@ -512,18 +512,12 @@ namespace {
 // two (c, v) images and two variance planes, kept in the context
 int guided_scratch(fh_ctx* ctx, size_t px)
 {
-  if (ctx->guided_pixels < px) {
+  if (ctx->d_guided_var[1].size() < px) {  // (the last of the four: all were made)
+    for (int k = 0; k < 2; ++k) { ctx->d_guided_cv[k].reset(); ctx->d_guided_var[k].reset(); }
     for (int k = 0; k < 2; ++k) {
-      if (ctx->d_guided_cv[k]) (void)hipFree(ctx->d_guided_cv[k]);
-      if (ctx->d_guided_var[k]) (void)hipFree(ctx->d_guided_var[k]);
-      ctx->d_guided_cv[k] = nullptr; ctx->d_guided_var[k] = nullptr;
+      FH_HIP(ctx->d_guided_cv[k].alloc(px));
+      FH_HIP(ctx->d_guided_var[k].alloc(px));
     }
-    ctx->guided_pixels = 0;
-    for (int k = 0; k < 2; ++k) {
-      FH_HIP(hipMalloc((void**)&ctx->d_guided_cv[k], px * sizeof(float4)));
-      FH_HIP(hipMalloc((void**)&ctx->d_guided_var[k], px * sizeof(float)));
-    }
-    ctx->guided_pixels = px;
   }
   return FH_OK;
 }
@@ -581,16 +575,13 @@ namespace {
 // the motion table into the context's device buffer, through pinned memory: the caller's array is free again when the call returns
 int motion_upload(fh_ctx* ctx, uint32_t n, const fh_motion* motion)
 {
-  if (ctx->motion_capacity < n) {
+  if (ctx->h_motion.size() < n) {  // (the second of the two: both were made)
     (void)hipStreamSynchronize(ctx->stream);  // (a call queued earlier may still read the old table)
-    if (ctx->d_motion) (void)hipFree(ctx->d_motion);
-    if (ctx->h_motion) (void)hipHostFree(ctx->h_motion);
-    ctx->d_motion = nullptr; ctx->h_motion = nullptr; ctx->motion_capacity = 0;
-    FH_HIP(hipMalloc((void**)&ctx->d_motion, (size_t)n * sizeof(fh_motion)));
-    FH_HIP(hipHostMalloc((void**)&ctx->h_motion, (size_t)n * sizeof(fh_motion), hipHostMallocDefault));
-    ctx->motion_capacity = n;
+    ctx->d_motion.reset(); ctx->h_motion.reset();
+    FH_HIP(ctx->d_motion.alloc(n));
+    FH_HIP(ctx->h_motion.alloc(n));
   }
-  if (!ctx->ev_motion) FH_HIP(hipEventCreateWithFlags(&ctx->ev_motion, hipEventDisableTiming));
+  if (!ctx->ev_motion) FH_HIP(ctx->ev_motion.create(hipEventDisableTiming));
   else FH_HIP(hipEventSynchronize(ctx->ev_motion));  // the copy of the call before has left the pinned buffer
   std::memcpy(ctx->h_motion, motion, (size_t)n * sizeof(fh_motion));
   FH_HIP(hipMemcpyAsync(ctx->d_motion, ctx->h_motion, (size_t)n * sizeof(fh_motion), hipMemcpyHostToDevice, ctx->stream));
@@ -606,21 +597,20 @@ int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* 
 {
   const size_t px = (size_t)w * h;
   if (const int rc = guided_scratch(ctx, px)) return rc;
-  if (ctx->hist_pixels < px) {  // (growing drops the history; so does any other change of width x height, below)
-    float4** bufs[3] = {ctx->d_hist_cv, ctx->d_hist_ph, ctx->d_hist_n};
+  if (ctx->d_hist_n[1].size() < px) {  // (the last of the six, so all were made.  Growing drops the history; so does any other change of width x height, below)
+    DeviceBuffer<float4>* const bufs[3] = {ctx->d_hist_cv, ctx->d_hist_ph, ctx->d_hist_n};
     for (auto b : bufs)
-      for (int k = 0; k < 2; ++k) { if (b[k]) (void)hipFree(b[k]); b[k] = nullptr; }
-    ctx->hist_pixels = 0; ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;
+      for (int k = 0; k < 2; ++k) b[k].reset();
+    ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;
     for (auto b : bufs)
-      for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&b[k], px * sizeof(float4)));
-    ctx->hist_pixels = px;
+      for (int k = 0; k < 2; ++k) FH_HIP(b[k].alloc(px));
   }
   const bool mom = ctx->denoise_temporal_moments != 0;
-  if (mom && ctx->hist_mu_pixels < ctx->hist_pixels) {  // (the moment image of fh_set_denoise_temporal_moments: as large as the rest of the history; a new one holds nothing)
-    for (int k = 0; k < 2; ++k) { if (ctx->d_hist_mu[k]) (void)hipFree(ctx->d_hist_mu[k]); ctx->d_hist_mu[k] = nullptr; }
-    ctx->hist_mu_pixels = 0; ctx->hist_frames = 0;
-    for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&ctx->d_hist_mu[k], ctx->hist_pixels * sizeof(float2)));
-    ctx->hist_mu_pixels = ctx->hist_pixels;
+  const size_t hist_pixels = ctx->d_hist_n[1].size();
+  if (mom && ctx->d_hist_mu[1].size() < hist_pixels) {  // (the moment image of fh_set_denoise_temporal_moments: as large as the rest of the history; a new one holds nothing)
+    for (int k = 0; k < 2; ++k) ctx->d_hist_mu[k].reset();
+    ctx->hist_frames = 0;
+    for (int k = 0; k < 2; ++k) FH_HIP(ctx->d_hist_mu[k].alloc(hist_pixels));
   }
   if (ctx->hist_w != (uint32_t)w || ctx->hist_h != (uint32_t)h) ctx->hist_frames = 0;
   const bool with_motion = ids && ctx->hist_frames != 0;  // (without a history nothing is looked up: the plain first call)

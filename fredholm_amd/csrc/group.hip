@@ -17,17 +17,18 @@ struct fh_group {
   bool scene_in_doubt = false, frame_in_doubt = false;  // a broadcast failed half way: fh_render refuses until fh_scene_upload / fh_set_resolution succeeded again
   bool sized = false;
   struct Member {
-    float* layers[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // full-size, on the member's device: its running means live here
-    uint8_t* staging = nullptr;                                                 // packed shard, on the member's device
-    size_t lead_offset = 0;                                                     // where the shard goes in the lead's staging area
-    hipEvent_t ev_pack_begin = nullptr, ev_packed = nullptr;                    // member's device
-    hipEvent_t ev_copy_begin = nullptr, ev_copied = nullptr;                    // lead's device
+    // (what lives on the member's device is released with that device current: free_frame_buffers, group_destroy)
+    fh::DeviceBuffer<float> layers[6];      // full-size, on the member's device: its running means live here
+    fh::DeviceBuffer<uint8_t> staging;      // packed shard, on the member's device
+    size_t lead_offset = 0;                 // where the shard goes in the lead's staging area
+    fh::Event ev_pack_begin, ev_packed;     // member's device
+    fh::Event ev_copy_begin, ev_copied;     // lead's device
     bool copy_recorded = false, timed = false;
   };
   std::vector<Member> mem;
-  uint8_t* lead_staging = nullptr;
-  hipStream_t copy_stream = nullptr;                           // lead's device
-  hipEvent_t ev_unpack_begin = nullptr, ev_unpacked = nullptr;  // lead's device
+  fh::Stream copy_stream;                  // lead's device
+  fh::DeviceBuffer<uint8_t> lead_staging;
+  fh::Event ev_unpack_begin, ev_unpacked;  // lead's device
   bool unpack_recorded = false, unpack_timed = false;
 };
 
@@ -118,14 +119,14 @@ void free_frame_buffers(fh_group* G)
     fh_group::Member& M = G->mem[i];
     (void)hipSetDevice(G->m[i]->device);
     (void)hipStreamSynchronize(G->m[i]->stream);
-    for (float*& p : M.layers) { if (p) (void)hipFree(p); p = nullptr; }
-    if (M.staging) { (void)hipFree(M.staging); M.staging = nullptr; }
+    for (auto& l : M.layers) l.reset();
+    M.staging.reset();
     M.copy_recorded = false;
   }
   (void)hipSetDevice(G->m[0]->device);
   if (G->copy_stream) (void)hipStreamSynchronize(G->copy_stream);
   (void)hipStreamSynchronize(G->m[0]->stream);
-  if (G->lead_staging) { (void)hipFree(G->lead_staging); G->lead_staging = nullptr; }
+  G->lead_staging.reset();
   G->unpack_recorded = false;
   G->sized = false;
 }
@@ -145,14 +146,12 @@ int size_frame_buffers(fh_ctx* g, bool with_layers)
     GROUP_HIP(g, hipStreamSynchronize(c->stream));
     if (with_layers) {
       for (uint32_t k = 0; k < 6u; ++k) {
-        if (M.layers[k]) { (void)hipFree(M.layers[k]); M.layers[k] = nullptr; }
-        GROUP_HIP(g, hipMalloc((void**)&M.layers[k], px * kLayerBytes[k]));
+        GROUP_HIP(g, M.layers[k].alloc(px * kLayerBytes[k] / sizeof(float)));
         GROUP_HIP(g, hipMemsetAsync(M.layers[k], 0, px * kLayerBytes[k], c->stream));
       }
     }
-    if (M.staging) { (void)hipFree(M.staging); M.staging = nullptr; }
     const size_t bytes = shard_bytes(all, c->n_owned);
-    GROUP_HIP(g, hipMalloc((void**)&M.staging, bytes ? bytes : 16));
+    GROUP_HIP(g, M.staging.alloc(bytes));
     M.lead_offset = lead_bytes;
     M.copy_recorded = false;
     lead_bytes += bytes;
@@ -160,8 +159,7 @@ int size_frame_buffers(fh_ctx* g, bool with_layers)
   GROUP_HIP(g, hipSetDevice(lead->device));
   GROUP_HIP(g, hipStreamSynchronize(G->copy_stream));
   GROUP_HIP(g, hipStreamSynchronize(lead->stream));
-  if (G->lead_staging) { (void)hipFree(G->lead_staging); G->lead_staging = nullptr; }
-  GROUP_HIP(g, hipMalloc((void**)&G->lead_staging, lead_bytes ? lead_bytes : 16));
+  GROUP_HIP(g, G->lead_staging.alloc(lead_bytes));
   G->unpack_recorded = false;
   const int rc = frame_map_ensure(lead, G->n);
   if (rc) return rc;
@@ -263,16 +261,13 @@ int group_destroy(fh_ctx* g)
     free_frame_buffers(G);
     for (uint32_t i = 1; i < (uint32_t)G->m.size(); ++i) {
       (void)hipSetDevice(G->m[i]->device);
-      if (G->mem[i].ev_pack_begin) (void)hipEventDestroy(G->mem[i].ev_pack_begin);
-      if (G->mem[i].ev_packed) (void)hipEventDestroy(G->mem[i].ev_packed);
+      G->mem[i].ev_pack_begin.reset(); G->mem[i].ev_packed.reset();
       (void)hipSetDevice(G->m[0]->device);
-      if (G->mem[i].ev_copy_begin) (void)hipEventDestroy(G->mem[i].ev_copy_begin);
-      if (G->mem[i].ev_copied) (void)hipEventDestroy(G->mem[i].ev_copied);
+      G->mem[i].ev_copy_begin.reset(); G->mem[i].ev_copied.reset();
     }
     (void)hipSetDevice(G->m[0]->device);
-    if (G->ev_unpack_begin) (void)hipEventDestroy(G->ev_unpack_begin);
-    if (G->ev_unpacked) (void)hipEventDestroy(G->ev_unpacked);
-    if (G->copy_stream) (void)hipStreamDestroy(G->copy_stream);
+    G->ev_unpack_begin.reset(); G->ev_unpacked.reset();
+    G->copy_stream.reset();
   }
   int rc = FH_OK;
   for (fh_ctx* c : G->m) {
@@ -486,12 +481,12 @@ int fh_ctx_create_group(const int* devices, uint32_t n, fh_ctx** out)
     if (hipSetDevice(b) == hipSuccess && hipDeviceCanAccessPeer(&can, b, a) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(a, 0);
     (void)hipGetLastError();  // (hipErrorPeerAccessAlreadyEnabled: a second group on the same devices)
   }
-  bool ok = hipSetDevice(devices[0]) == hipSuccess && hipStreamCreateWithFlags(&G->copy_stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreate(&G->ev_unpack_begin) == hipSuccess && hipEventCreate(&G->ev_unpacked) == hipSuccess;
+  bool ok = hipSetDevice(devices[0]) == hipSuccess && G->copy_stream.create(hipStreamNonBlocking) == hipSuccess;
+  ok = ok && G->ev_unpack_begin.create() == hipSuccess && G->ev_unpacked.create() == hipSuccess;
   for (uint32_t i = 1; i < n && ok; ++i) {
     fh_group::Member& M = G->mem[i];
-    ok = hipSetDevice(devices[i]) == hipSuccess && hipEventCreate(&M.ev_pack_begin) == hipSuccess && hipEventCreate(&M.ev_packed) == hipSuccess;
-    ok = ok && hipSetDevice(devices[0]) == hipSuccess && hipEventCreate(&M.ev_copy_begin) == hipSuccess && hipEventCreate(&M.ev_copied) == hipSuccess;
+    ok = hipSetDevice(devices[i]) == hipSuccess && M.ev_pack_begin.create() == hipSuccess && M.ev_packed.create() == hipSuccess;
+    ok = ok && hipSetDevice(devices[0]) == hipSuccess && M.ev_copy_begin.create() == hipSuccess && M.ev_copied.create() == hipSuccess;
   }
   if (!ok) return bail(FH_E_HIP, "fh_ctx_create_group: stream / event creation failed");
   *out = g;

@@ -18,21 +18,15 @@
 namespace fh {
 namespace {
 
+// a buffer of `count` elements, filled from `host` where there is one; and its contents back
 template <typename T>
-struct Tmp {
-  T* p = nullptr;
-  size_t n = 0;
-  ~Tmp() { if (p) (void)hipFree(p); }
-  hipError_t up(const T* host, size_t count)
-  {
-    n = count;
-    hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (host && count) e = hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-  }
-  hipError_t down(T* host) { return hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost); }
-};
+hipError_t up(DeviceBuffer<T>& d, const std::common_type_t<T>* host, size_t count)  // (T comes from the buffer: host may be nullptr)
+{
+  const hipError_t e = d.alloc(count);
+  return e == hipSuccess && host && count ? hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice) : e;
+}
+template <typename T>
+hipError_t down(const DeviceBuffer<T>& d, T* host) { return hipMemcpy(host, d, d.size() * sizeof(T), hipMemcpyDeviceToHost); }
 
 __global__ void k_hash(int kind, uint32_t n, const uint32_t* in, uint32_t* out)
 {
@@ -308,77 +302,77 @@ int fh_trace_rays(fh_ctx* ctx, uint32_t n, const float* rays7, int any_hit, floa
   KCTX(ctx);
   if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_trace_rays: scene/BVH missing");
   if (n == 0) return FH_OK;
-  Tmp<float> r, t;
-  Tmp<uint32_t> p;
-  FH_HIP(r.up(rays7, 7ull * n)); FH_HIP(t.up(nullptr, 3ull * n)); FH_HIP(p.up(nullptr, n));
+  DeviceBuffer<float> r, t;
+  DeviceBuffer<uint32_t> p;
+  FH_HIP(up(r, rays7, 7ull * n)); FH_HIP(up(t, nullptr, 3ull * n)); FH_HIP(up(p, nullptr, n));
   const SceneDev sd = scene_dev(ctx);
   uint32_t flush = 32u;
   flush = ctx->tun.coop_flush;
   if (sd.use_bvh8 && sd.bvh8.n_tris < kCoopMaxTris && ctx->tun.coop) {
     const dim3 g(blocks(n)), b(256);
-    if (any_hit && sd.has_alpha) hipLaunchKernelGGL((k_trace_batch_coop<true, true>), g, b, 0, ctx->stream, sd, n, r.p, t.p, p.p, flush);
-    else if (any_hit) hipLaunchKernelGGL((k_trace_batch_coop<true, false>), g, b, 0, ctx->stream, sd, n, r.p, t.p, p.p, flush);
-    else if (sd.has_alpha) hipLaunchKernelGGL((k_trace_batch_coop<false, true>), g, b, 0, ctx->stream, sd, n, r.p, t.p, p.p, flush);
-    else hipLaunchKernelGGL((k_trace_batch_coop<false, false>), g, b, 0, ctx->stream, sd, n, r.p, t.p, p.p, flush);
+    if (any_hit && sd.has_alpha) hipLaunchKernelGGL((k_trace_batch_coop<true, true>), g, b, 0, ctx->stream, sd, n, r.get(), t.get(), p.get(), flush);
+    else if (any_hit) hipLaunchKernelGGL((k_trace_batch_coop<true, false>), g, b, 0, ctx->stream, sd, n, r.get(), t.get(), p.get(), flush);
+    else if (sd.has_alpha) hipLaunchKernelGGL((k_trace_batch_coop<false, true>), g, b, 0, ctx->stream, sd, n, r.get(), t.get(), p.get(), flush);
+    else hipLaunchKernelGGL((k_trace_batch_coop<false, false>), g, b, 0, ctx->stream, sd, n, r.get(), t.get(), p.get(), flush);
   } else {
-    hipLaunchKernelGGL(k_trace_batch, dim3(blocks(n)), dim3(256), 0, ctx->stream, sd, n, r.p, any_hit, t.p, p.p);
+    hipLaunchKernelGGL(k_trace_batch, dim3(blocks(n)), dim3(256), 0, ctx->stream, sd, n, r.get(), any_hit, t.get(), p.get());
   }
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(t.down(tuv)); FH_HIP(p.down(prim));
+  FH_HIP(down(t, tuv)); FH_HIP(down(p, prim));
   return FH_OK;
 }
 
 int fh_kat_hash(fh_ctx* ctx, int kind, uint32_t n, const uint32_t* in4, uint32_t* out)
 {
   KCTX(ctx);
-  Tmp<uint32_t> a, o;
-  FH_HIP(a.up(in4, 4ull * n)); FH_HIP(o.up(nullptr, n));
-  hipLaunchKernelGGL(k_hash, dim3(blocks(n)), dim3(256), 0, ctx->stream, kind, n, a.p, o.p);
+  DeviceBuffer<uint32_t> a, o;
+  FH_HIP(up(a, in4, 4ull * n)); FH_HIP(up(o, nullptr, n));
+  hipLaunchKernelGGL(k_hash, dim3(blocks(n)), dim3(256), 0, ctx->stream, kind, n, a.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out));
+  FH_HIP(down(o, out));
   return FH_OK;
 }
 int fh_kat_cmj(fh_ctx* ctx, uint32_t n, const uint32_t* in4, float* out2)
 {
   KCTX(ctx);
-  Tmp<uint32_t> a;
-  Tmp<float> o;
-  FH_HIP(a.up(in4, 4ull * n)); FH_HIP(o.up(nullptr, 2ull * n));
-  hipLaunchKernelGGL(k_cmj, dim3(blocks(n)), dim3(256), 0, ctx->stream, n, a.p, o.p);
+  DeviceBuffer<uint32_t> a;
+  DeviceBuffer<float> o;
+  FH_HIP(up(a, in4, 4ull * n)); FH_HIP(up(o, nullptr, 2ull * n));
+  hipLaunchKernelGGL(k_cmj, dim3(blocks(n)), dim3(256), 0, ctx->stream, n, a.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out2));
+  FH_HIP(down(o, out2));
   return FH_OK;
 }
 int fh_kat_sobol(fh_ctx* ctx, uint32_t n, const uint32_t* in4, float* out)
 {
   KCTX(ctx);
-  Tmp<uint32_t> a;
-  Tmp<float> o;
-  FH_HIP(a.up(in4, 4ull * n)); FH_HIP(o.up(nullptr, n));
-  hipLaunchKernelGGL(k_sobol, dim3(blocks(n)), dim3(256), 0, ctx->stream, n, a.p, ctx->d_sobol, o.p);
+  DeviceBuffer<uint32_t> a;
+  DeviceBuffer<float> o;
+  FH_HIP(up(a, in4, 4ull * n)); FH_HIP(up(o, nullptr, n));
+  hipLaunchKernelGGL(k_sobol, dim3(blocks(n)), dim3(256), 0, ctx->stream, n, a.get(), ctx->d_sobol, o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out));
+  FH_HIP(down(o, out));
   return FH_OK;
 }
 int fh_kat_elementary(fh_ctx* ctx, int fn, uint32_t n, const float* x, const float* y, float* out)
 {
   KCTX(ctx);
-  Tmp<float> a, b, o;
-  FH_HIP(a.up(x, n)); FH_HIP(b.up(y ? y : x, n)); FH_HIP(o.up(nullptr, n));
-  hipLaunchKernelGGL(k_elementary, dim3(blocks(n)), dim3(256), 0, ctx->stream, fn, n, a.p, b.p, o.p);
+  DeviceBuffer<float> a, b, o;
+  FH_HIP(up(a, x, n)); FH_HIP(up(b, y ? y : x, n)); FH_HIP(up(o, nullptr, n));
+  hipLaunchKernelGGL(k_elementary, dim3(blocks(n)), dim3(256), 0, ctx->stream, fn, n, a.get(), b.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out));
+  FH_HIP(down(o, out));
   return FH_OK;
 }
 int fh_kat_warp(fh_ctx* ctx, int kind, uint32_t n, const float* u2, const float* wo3, const float* alpha2, float* out)
 {
   KCTX(ctx);
   const uint32_t width = (kind == 1 || kind == 3) ? 3u : 2u;
-  Tmp<float> u, w, o;
-  FH_HIP(u.up(u2, 2ull * n)); FH_HIP(w.up(wo3, wo3 ? 3ull * n : 0)); FH_HIP(o.up(nullptr, (size_t)width * n));
-  hipLaunchKernelGGL(k_warp, dim3(blocks(n)), dim3(256), 0, ctx->stream, kind, n, u.p, w.p, alpha2 ? alpha2[0] : 1.0f, alpha2 ? alpha2[1] : 1.0f, o.p);
+  DeviceBuffer<float> u, w, o;
+  FH_HIP(up(u, u2, 2ull * n)); FH_HIP(up(w, wo3, wo3 ? 3ull * n : 0)); FH_HIP(up(o, nullptr, (size_t)width * n));
+  hipLaunchKernelGGL(k_warp, dim3(blocks(n)), dim3(256), 0, ctx->stream, kind, n, u.get(), w.get(), alpha2 ? alpha2[0] : 1.0f, alpha2 ? alpha2[1] : 1.0f, o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out));
+  FH_HIP(down(o, out));
   return FH_OK;
 }
 static int kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, float eta_given, uint32_t lobes_mask, uint32_t only, uint32_t n, const float* wo3, const float* wi3, const float* u1, const float* u2, float* out18)
@@ -388,18 +382,18 @@ static int kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, floa
   MaterialDev m{};
   std::memcpy(m.w, material, 180);
   const BsdfTables lut{ctx->d_lut_refl, ctx->d_lut_sheen};
-  Tmp<float> a, b, c, d, o;
-  FH_HIP(a.up(wo3, 3ull * n)); FH_HIP(b.up(wi3, 3ull * n)); FH_HIP(c.up(u1, n)); FH_HIP(d.up(u2, 2ull * n)); FH_HIP(o.up(nullptr, 18ull * n));
+  DeviceBuffer<float> a, b, c, d, o;
+  FH_HIP(up(a, wo3, 3ull * n)); FH_HIP(up(b, wi3, 3ull * n)); FH_HIP(up(c, u1, n)); FH_HIP(up(d, u2, 2ull * n)); FH_HIP(up(o, nullptr, 18ull * n));
   const dim3 g(blocks(n)), t(256);
   switch (lobes_mask) {
-    case L_DIFF: hipLaunchKernelGGL(k_bsdf<L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    case L_METAL: hipLaunchKernelGGL(k_bsdf<L_METAL>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    case L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    case L_METAL | L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_METAL | L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
-    default: hipLaunchKernelGGL(k_bsdf<L_ALL>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.p, b.p, c.p, d.p, o.p); break;
+    case L_DIFF: hipLaunchKernelGGL(k_bsdf<L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.get(), b.get(), c.get(), d.get(), o.get()); break;
+    case L_METAL: hipLaunchKernelGGL(k_bsdf<L_METAL>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.get(), b.get(), c.get(), d.get(), o.get()); break;
+    case L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.get(), b.get(), c.get(), d.get(), o.get()); break;
+    case L_METAL | L_SPEC | L_DIFF: hipLaunchKernelGGL(k_bsdf<L_METAL | L_SPEC | L_DIFF>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.get(), b.get(), c.get(), d.get(), o.get()); break;
+    default: hipLaunchKernelGGL(k_bsdf<L_ALL>, g, t, 0, ctx->stream, m, entering, eta_given, only, lut, n, a.get(), b.get(), c.get(), d.get(), o.get()); break;
   }
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out18));
+  FH_HIP(down(o, out18));
   return FH_OK;
 }
 int fh_kat_bsdf(fh_ctx* ctx, const fh_material* material, int entering, uint32_t lobes_mask, uint32_t n, const float* wo3, const float* wi3, const float* u1, const float* u2, float* out18)
@@ -419,11 +413,11 @@ int fh_kat_bsdf_ior(fh_ctx* ctx, const fh_material* material, float eta, uint32_
 int fh_kat_sky(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3)
 {
   KCTX(ctx);
-  Tmp<float> a, o;
-  FH_HIP(a.up(dirs3, 3ull * n)); FH_HIP(o.up(nullptr, 3ull * n));
-  hipLaunchKernelGGL(k_sky, dim3(blocks(n)), dim3(256), 0, ctx->stream, ctx->hosek, mk3(ctx->sun_dir[0], ctx->sun_dir[1], ctx->sun_dir[2]), ctx->sky_intensity, n, a.p, o.p);
+  DeviceBuffer<float> a, o;
+  FH_HIP(up(a, dirs3, 3ull * n)); FH_HIP(up(o, nullptr, 3ull * n));
+  hipLaunchKernelGGL(k_sky, dim3(blocks(n)), dim3(256), 0, ctx->stream, ctx->hosek, mk3(ctx->sun_dir[0], ctx->sun_dir[1], ctx->sun_dir[2]), ctx->sky_intensity, n, a.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out3));
+  FH_HIP(down(o, out3));
   return FH_OK;
 }
 int fh_kat_hosek_state(fh_ctx* ctx, float* out30)
@@ -437,12 +431,18 @@ int fh_kat_camera(fh_ctx* ctx, const fh_camera* cam, uint32_t width, uint32_t he
   KCTX(ctx);
   m34 xf;
   for (int r = 0; r < 3; ++r) xf.r[r] = make_float4(cam->transform[4 * r], cam->transform[4 * r + 1], cam->transform[4 * r + 2], cam->transform[4 * r + 3]);
-  Tmp<uint32_t> a, b;
-  Tmp<float> o;
-  FH_HIP(a.up(pixel_idx, n)); FH_HIP(b.up(n_spp, n)); FH_HIP(o.up(nullptr, 6ull * n));
-  hipLaunchKernelGGL(k_camera, dim3(blocks(n)), dim3(256), 0, ctx->stream, xf, 1.0f / tanf(0.5f * cam->fov), cam->F, cam->focus, width, height, xxhash32(seed), n, a.p, b.p, o.p);
+  DeviceBuffer<uint32_t> a, b;
+  DeviceBuffer<float> o;
+  FH_HIP(up(a, pixel_idx, n)); FH_HIP(up(b, n_spp, n)); FH_HIP(up(o, nullptr, 6ull * n));
+  hipLaunchKernelGGL(k_camera, dim3(blocks(n)), dim3(256), 0, ctx->stream, xf, 1.0f / tanf(0.5f * cam->fov), cam->F, cam->focus, width, height, xxhash32(seed), n, a.get(), b.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out6));
+  FH_HIP(down(o, out6));
+  return FH_OK;
+}
+int fh_kat_live_allocations(uint64_t* count, uint64_t* bytes)
+{
+  if (count) *count = seam::live_count.load(std::memory_order_relaxed);
+  if (bytes) *bytes = seam::live_bytes.load(std::memory_order_relaxed);
   return FH_OK;
 }
 int fh_kat_chief_rays(fh_ctx* ctx, const fh_camera* cam, uint32_t width, uint32_t height, float* out6)
@@ -455,39 +455,39 @@ int fh_kat_chief_rays(fh_ctx* ctx, const fh_camera* cam, uint32_t width, uint32_
   c.apb = chief_a_plus_b(c.inv_tan, cam->focus);
   c.width = width; c.height = height;
   const uint32_t n = width * height;
-  Tmp<float> o;
-  FH_HIP(o.up(nullptr, 6ull * n));
-  hipLaunchKernelGGL(k_chief_rays, dim3(blocks(n)), dim3(256), 0, ctx->stream, c, o.p);
+  DeviceBuffer<float> o;
+  FH_HIP(up(o, nullptr, 6ull * n));
+  hipLaunchKernelGGL(k_chief_rays, dim3(blocks(n)), dim3(256), 0, ctx->stream, c, o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out6));
+  FH_HIP(down(o, out6));
   return FH_OK;
 }
 int fh_kat_offset_origin(fh_ctx* ctx, uint32_t n, const float* p3, const float* n3, float* out3)
 {
   KCTX(ctx);
-  Tmp<float> a, b, o;
-  FH_HIP(a.up(p3, 3ull * n)); FH_HIP(b.up(n3, 3ull * n)); FH_HIP(o.up(nullptr, 3ull * n));
-  hipLaunchKernelGGL(k_offset, dim3(blocks(n)), dim3(256), 0, ctx->stream, n, a.p, b.p, o.p);
+  DeviceBuffer<float> a, b, o;
+  FH_HIP(up(a, p3, 3ull * n)); FH_HIP(up(b, n3, 3ull * n)); FH_HIP(up(o, nullptr, 3ull * n));
+  hipLaunchKernelGGL(k_offset, dim3(blocks(n)), dim3(256), 0, ctx->stream, n, a.get(), b.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out3));
+  FH_HIP(down(o, out3));
   return FH_OK;
 }
 int fh_kat_sqrt(fh_ctx* ctx, unsigned long long* mismatches_over_all_inputs, uint32_t n_sample, const float* sample_in, float* sample_out)
 {
   KCTX(ctx);
   if (!mismatches_over_all_inputs || (n_sample && (!sample_in || !sample_out))) return fail(ctx, FH_E_INVALID, "fh_kat_sqrt: null argument");
-  Tmp<unsigned long long> bad;
+  DeviceBuffer<unsigned long long> bad;
   const unsigned long long zero = 0;
-  FH_HIP(bad.up(&zero, 1));
-  hipLaunchKernelGGL(k_sqrt_all, dim3(1u << 14), dim3(256), 0, ctx->stream, bad.p);
-  Tmp<float> a, o;
+  FH_HIP(up(bad, &zero, 1));
+  hipLaunchKernelGGL(k_sqrt_all, dim3(1u << 14), dim3(256), 0, ctx->stream, bad.get());
+  DeviceBuffer<float> a, o;
   if (n_sample) {
-    FH_HIP(a.up(sample_in, n_sample)); FH_HIP(o.up(nullptr, n_sample));
-    hipLaunchKernelGGL(k_sqrt_some, dim3(blocks(n_sample)), dim3(256), 0, ctx->stream, n_sample, a.p, o.p);
+    FH_HIP(up(a, sample_in, n_sample)); FH_HIP(up(o, nullptr, n_sample));
+    hipLaunchKernelGGL(k_sqrt_some, dim3(blocks(n_sample)), dim3(256), 0, ctx->stream, n_sample, a.get(), o.get());
   }
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(bad.down(mismatches_over_all_inputs));
-  if (n_sample) FH_HIP(o.down(sample_out));
+  FH_HIP(down(bad, mismatches_over_all_inputs));
+  if (n_sample) FH_HIP(down(o, sample_out));
   return FH_OK;
 }
 int fh_kat_math(fh_ctx* ctx, int kind, uint32_t n, const float* in, float* out)
@@ -496,14 +496,14 @@ int fh_kat_math(fh_ctx* ctx, int kind, uint32_t n, const float* in, float* out)
   static const uint32_t widths[FH_MATH_COUNT][2] = {{3, 1}, {2, 1}, {3, 6}, {12, 3}, {12, 3}, {3, 2}, {3, 1}, {3, 3}, {3, 3}, {3, 2}, {4, 3}, {3, 1}};
   if (kind < 0 || kind >= FH_MATH_COUNT) return fail(ctx, FH_E_INVALID, "fh_kat_math: unknown kind");
   const uint32_t si = widths[kind][0], so = widths[kind][1];
-  Tmp<float> a, o;
-  FH_HIP(a.up(in, (size_t)si * n)); FH_HIP(o.up(nullptr, (size_t)so * n));
+  DeviceBuffer<float> a, o;
+  FH_HIP(up(a, in, (size_t)si * n)); FH_HIP(up(o, nullptr, (size_t)so * n));
   BsdfTables lut;
   lut.reflection = ctx->d_lut_refl;
   lut.sheen = ctx->d_lut_sheen;
-  hipLaunchKernelGGL(k_math, dim3(blocks(n)), dim3(256), 0, ctx->stream, kind, lut, n, a.p, si, o.p, so);
+  hipLaunchKernelGGL(k_math, dim3(blocks(n)), dim3(256), 0, ctx->stream, kind, lut, n, a.get(), si, o.get(), so);
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out));
+  FH_HIP(down(o, out));
   return FH_OK;
 }
 int fh_measure_bandwidth(fh_ctx* ctx, uint64_t bytes, uint32_t iters, double* read_gbs, double* copy_gbs)
@@ -512,43 +512,41 @@ int fh_measure_bandwidth(fh_ctx* ctx, uint64_t bytes, uint32_t iters, double* re
   KCTX(ctx);
   if (!read_gbs || !copy_gbs || bytes < (1ull << 20) || iters == 0) return fail(ctx, FH_E_INVALID, "fh_measure_bandwidth: bad argument");
   const size_t n = (size_t)(bytes / 16);
-  Tmp<float4> a, b;
-  Tmp<float> sink;
-  FH_HIP(a.up(nullptr, n)); FH_HIP(b.up(nullptr, n)); FH_HIP(sink.up(nullptr, 1));
-  FH_HIP(hipMemsetAsync(a.p, 0, n * 16, ctx->stream));
-  FH_HIP(hipMemsetAsync(b.p, 0, n * 16, ctx->stream));
+  DeviceBuffer<float4> a, b;
+  DeviceBuffer<float> sink;
+  FH_HIP(up(a, nullptr, n)); FH_HIP(up(b, nullptr, n)); FH_HIP(up(sink, nullptr, 1));
+  FH_HIP(hipMemsetAsync(a.get(), 0, n * 16, ctx->stream));
+  FH_HIP(hipMemsetAsync(b.get(), 0, n * 16, ctx->stream));
   const dim3 block(256);
   *read_gbs = *copy_gbs = 0.0;
   for (uint32_t per_cu : {8u, 16u, 32u, 64u}) {  // the best of a few grid sizes: the right number of workgroups in flight is a property of the GPU, not of the renderer
     const dim3 grid(ctx->tun.n_cus * per_cu);
-    hipEvent_t e0, e1, e2;
-    FH_HIP(hipEventCreate(&e0)); FH_HIP(hipEventCreate(&e1)); FH_HIP(hipEventCreate(&e2));
-    hipLaunchKernelGGL(k_bw_read, grid, block, 0, ctx->stream, (const float4*)a.p, n, sink.p);  // warm-up (page tables, clocks)
-    hipLaunchKernelGGL(k_bw_copy, grid, block, 0, ctx->stream, (const float4*)a.p, b.p, n);
+    Event e0, e1, e2;
+    FH_HIP(e0.create()); FH_HIP(e1.create()); FH_HIP(e2.create());
+    hipLaunchKernelGGL(k_bw_read, grid, block, 0, ctx->stream, (const float4*)a.get(), n, sink.get());  // warm-up (page tables, clocks)
+    hipLaunchKernelGGL(k_bw_copy, grid, block, 0, ctx->stream, (const float4*)a.get(), b.get(), n);
     FH_HIP(hipEventRecord(e0, ctx->stream));
-    for (uint32_t k = 0; k < iters; ++k) hipLaunchKernelGGL(k_bw_read, grid, block, 0, ctx->stream, (const float4*)((k & 1u) ? b.p : a.p), n, sink.p);
+    for (uint32_t k = 0; k < iters; ++k) hipLaunchKernelGGL(k_bw_read, grid, block, 0, ctx->stream, (const float4*)((k & 1u) ? b.get() : a.get()), n, sink.get());
     FH_HIP(hipEventRecord(e1, ctx->stream));
-    for (uint32_t k = 0; k < iters; ++k) hipLaunchKernelGGL(k_bw_copy, grid, block, 0, ctx->stream, (const float4*)((k & 1u) ? b.p : a.p), (k & 1u) ? a.p : b.p, n);
+    for (uint32_t k = 0; k < iters; ++k) hipLaunchKernelGGL(k_bw_copy, grid, block, 0, ctx->stream, (const float4*)((k & 1u) ? b.get() : a.get()), (k & 1u) ? a.get() : b.get(), n);
     FH_HIP(hipEventRecord(e2, ctx->stream));
     FH_HIP(hipStreamSynchronize(ctx->stream));
     float ms_r = 0.0f, ms_c = 0.0f;
     FH_HIP(hipEventElapsedTime(&ms_r, e0, e1));
     FH_HIP(hipEventElapsedTime(&ms_c, e1, e2));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
     const double r = (double)n * 16.0 * iters / (ms_r * 1e-3) / 1e9, c = 2.0 * (double)n * 16.0 * iters / (ms_c * 1e-3) / 1e9;  // copy: bytes read + bytes written
     if (r > *read_gbs) *read_gbs = r;
     if (c > *copy_gbs) *copy_gbs = c;
   }
   // the runtime's own device-to-device copy of the same buffers: the better of the two is reported as the copy bandwidth
-  hipEvent_t m0, m1;
-  FH_HIP(hipEventCreate(&m0)); FH_HIP(hipEventCreate(&m1));
+  Event m0, m1;
+  FH_HIP(m0.create()); FH_HIP(m1.create());
   FH_HIP(hipEventRecord(m0, ctx->stream));
-  for (uint32_t k = 0; k < iters; ++k) FH_HIP(hipMemcpyAsync((k & 1u) ? (void*)a.p : (void*)b.p, (k & 1u) ? (const void*)b.p : (const void*)a.p, n * 16, hipMemcpyDeviceToDevice, ctx->stream));
+  for (uint32_t k = 0; k < iters; ++k) FH_HIP(hipMemcpyAsync((k & 1u) ? (void*)a.get() : (void*)b.get(), (k & 1u) ? (const void*)b.get() : (const void*)a.get(), n * 16, hipMemcpyDeviceToDevice, ctx->stream));
   FH_HIP(hipEventRecord(m1, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
   float ms_m = 0.0f;
   FH_HIP(hipEventElapsedTime(&ms_m, m0, m1));
-  (void)hipEventDestroy(m0); (void)hipEventDestroy(m1);
   const double memcpy_gbs = 2.0 * (double)n * 16.0 * iters / (ms_m * 1e-3) / 1e9;
   if (memcpy_gbs > *copy_gbs) *copy_gbs = memcpy_gbs;
   return FH_OK;
@@ -557,17 +555,17 @@ int fh_kat_tex2d(fh_ctx* ctx, const uint8_t* rgba8, const float* rgba32f, uint32
 {
   KCTX(ctx);
   if ((!rgba8 && !rgba32f) || !uv2 || !out4 || width == 0 || height == 0) return fail(ctx, FH_E_INVALID, "fh_kat_tex2d: bad argument");
-  Tmp<uint8_t> t8;
-  Tmp<float> t32, lut, uv, o;
+  DeviceBuffer<uint8_t> t8;
+  DeviceBuffer<float> t32, lut, uv, o;
   const size_t texels = (size_t)width * height * 4;
-  if (rgba8) FH_HIP(t8.up(rgba8, texels)); else FH_HIP(t32.up(rgba32f, texels));
+  if (rgba8) FH_HIP(up(t8, rgba8, texels)); else FH_HIP(up(t32, rgba32f, texels));
   float h_lut[256];
   for (int i = 0; i < 256; ++i) h_lut[i] = fht_srgb_to_linear((float)i * (1.0f / 255.0f));
-  FH_HIP(lut.up(h_lut, 256)); FH_HIP(uv.up(uv2, 2ull * n)); FH_HIP(o.up(nullptr, 4ull * n));
-  const fht_texture tex{rgba8 ? t8.p : nullptr, rgba8 ? nullptr : t32.p, width, height, srgb ? 1u : 0u};
-  hipLaunchKernelGGL(k_tex2d, dim3(blocks(n)), dim3(256), 0, ctx->stream, tex, lut.p, n, uv.p, o.p);
+  FH_HIP(up(lut, h_lut, 256)); FH_HIP(up(uv, uv2, 2ull * n)); FH_HIP(up(o, nullptr, 4ull * n));
+  const fht_texture tex{rgba8 ? t8.get() : nullptr, rgba8 ? nullptr : t32.get(), width, height, srgb ? 1u : 0u};
+  hipLaunchKernelGGL(k_tex2d, dim3(blocks(n)), dim3(256), 0, ctx->stream, tex, lut.get(), n, uv.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  FH_HIP(o.down(out4));
+  FH_HIP(down(o, out4));
   return FH_OK;
 }
 

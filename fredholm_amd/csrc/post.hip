@@ -295,16 +295,15 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
 {
   hipStream_t st = ctx->stream;
   // FH_FLAG_TIME_KERNELS: HIP events around the whole chain (fh_stats.post_ms, reduced at fh_sync like the render spans: kind 7)
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  Event ev_a, ev_b;
   const bool timed = (ctx->flags & FH_FLAG_TIME_KERNELS) != 0;
-  auto take = [&]() { hipEvent_t e = nullptr; if (!ctx->event_pool.empty()) { e = ctx->event_pool.back(); ctx->event_pool.pop_back(); } else (void)hipEventCreate(&e); return e; };
-  if (timed) { ev_a = take(); ev_b = take(); (void)hipEventRecord(ev_a, st); }
+  if (timed) { ev_a = take_event(ctx); ev_b = take_event(ctx); (void)hipEventRecord(ev_a, st); }
   const int bx = w / kT > 1 ? w / kT : 1, by = h / kT > 1 ? h / kT : 1;  // floor division, post-process.cu:9-11
   const int gw = bx * kT < w ? bx * kT : w, gh = by * kT < h ? by * kT : h;
   const dim3 grid(bx, by), block(kT, kT);
   // fh_set_auto_exposure: metering -> resolve -> the chain, all on the stream; the chain's metered kernels read what the resolve wrote
   const bool metered = ctx->auto_exposure != 0;
-  const MeterDev* md = (const MeterDev*)ctx->d_meter;
+  const MeterDev* md = (const MeterDev*)ctx->d_meter.get();
   const float exposure = exposure_from_ev100(ev100_of(1.0f, 1.0f, pp->ISO));
   if (pp->use_bloom && (w < kT || h < kT)) return fail(ctx, FH_E_UNSUPPORTED, "bloom needs an image of at least 16x16 pixels");
   if (metered) {
@@ -315,7 +314,7 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
   if (pp->use_bloom) {
     // the 1089 weights depend on bloom_sigma only: computed and uploaded when sigma changes, kept in the context otherwise
     // (no allocation, copy or host synchronisation per frame)
-    if (!ctx->d_bloom_weights) FH_HIP(hipMalloc((void**)&ctx->d_bloom_weights, 33 * 33 * sizeof(float)));
+    FH_HIP(ctx->d_bloom_weights.ensure(33 * 33));
     if (ctx->bloom_sigma_cached != pp->bloom_sigma) {
       std::vector<float> wt(33 * 33);
       float wsum = 0.0f;
@@ -339,7 +338,7 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
   }
   if (metered) hipLaunchKernelGGL(k_tone_map_metered, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, md, exposure, pp->chromatic_aberration, (float4*)out);
   else hipLaunchKernelGGL(k_tone_map, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, exposure, pp->chromatic_aberration, (float4*)out);
-  if (timed) { (void)hipEventRecord(ev_b, st); ctx->spans.push_back({ev_a, ev_b, 7}); ctx->stats.n_post_launches++; }
+  if (timed) { (void)hipEventRecord(ev_b, st); ctx->spans.push_back({std::move(ev_a), std::move(ev_b), 7}); ctx->stats.n_post_launches++; }
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
@@ -352,7 +351,7 @@ int auto_exposure_set(fh_ctx* ctx, const fh_auto_exposure_params* params)
     ctx->auto_exposure = 0;
     return FH_OK;
   }
-  if (!ctx->d_meter) FH_HIP(hipMalloc(&ctx->d_meter, sizeof(MeterDev)));
+  FH_HIP(ctx->d_meter.ensure(sizeof(MeterDev)));
   if (!ctx->auto_exposure) FH_HIP(hipMemsetAsync(ctx->d_meter, 0, sizeof(MeterDev), ctx->stream));  // off -> on: frames = 0; on -> on keeps the state
   ctx->auto_exposure = 1;
   ctx->ae_params = *params;
@@ -366,23 +365,20 @@ int meter_submit(fh_ctx* ctx, const float* image, uint32_t w, uint32_t h)
   const uint32_t per_block = (uint32_t)(kMeterLoads * kMeterThreads);
   uint32_t blocks = (n + per_block - 1u) / per_block;
   blocks = blocks < 1u ? 1u : (blocks > (uint32_t)kMeterMaxBlocks ? (uint32_t)kMeterMaxBlocks : blocks);
-  if (ctx->meter_slab_blocks < blocks) {  // grows on demand, never per frame
-    FH_HIP(hipStreamSynchronize(st));     // an earlier call may still use the old slabs
-    if (ctx->d_meter_slabs) (void)hipFree(ctx->d_meter_slabs);
-    ctx->d_meter_slabs = nullptr; ctx->meter_slab_blocks = 0;
-    FH_HIP(hipMalloc((void**)&ctx->d_meter_slabs, (size_t)blocks * kMeterWords * sizeof(uint32_t)));
-    ctx->meter_slab_blocks = blocks;
+  if (ctx->d_meter_slabs.size() < (size_t)blocks * kMeterWords) {  // grows on demand, never per frame
+    FH_HIP(hipStreamSynchronize(st));                              // an earlier call may still use the old slabs
+    FH_HIP(ctx->d_meter_slabs.alloc((size_t)blocks * kMeterWords));
   }
   const MeterConsts mc = meter_consts(ctx->ae_params);
   hipLaunchKernelGGL(k_meter_histogram, dim3(blocks), dim3(kMeterThreads), 0, st, (const float4*)image, n, mc.log2_lo, mc.scale, ctx->d_meter_slabs);
-  hipLaunchKernelGGL(k_meter_resolve, dim3(1), dim3(kResolveThreads), 0, st, (const uint32_t*)ctx->d_meter_slabs, blocks, mc, (MeterDev*)ctx->d_meter);
+  hipLaunchKernelGGL(k_meter_resolve, dim3(1), dim3(kResolveThreads), 0, st, (const uint32_t*)ctx->d_meter_slabs.get(), blocks, mc, (MeterDev*)ctx->d_meter.get());
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
 
 int auto_exposure_reset(fh_ctx* ctx)
 {
-  FH_HIP(hipMemsetAsync(&((MeterDev*)ctx->d_meter)->st.frames, 0, sizeof(uint32_t), ctx->stream));
+  FH_HIP(hipMemsetAsync(&((MeterDev*)ctx->d_meter.get())->st.frames, 0, sizeof(uint32_t), ctx->stream));
   return FH_OK;
 }
 
@@ -400,12 +396,7 @@ int denoise_submit(fh_ctx* ctx, int w, int h, const float* beauty, const float* 
 {
   hipStream_t st = ctx->stream;
   const size_t px = (size_t)w * h;
-  if (ctx->denoise_pixels < px) {  // two ping-pong irradiance buffers, kept in the context
-    for (int k = 0; k < 2; ++k) { if (ctx->d_denoise_tmp[k]) (void)hipFree(ctx->d_denoise_tmp[k]); ctx->d_denoise_tmp[k] = nullptr; }
-    ctx->denoise_pixels = 0;
-    for (int k = 0; k < 2; ++k) FH_HIP(hipMalloc((void**)&ctx->d_denoise_tmp[k], px * sizeof(float4)));
-    ctx->denoise_pixels = px;
-  }
+  for (int k = 0; k < 2; ++k) FH_HIP(ctx->d_denoise_tmp[k].ensure(px));  // two ping-pong irradiance buffers, kept in the context
   const dim3 grid((w + 15) / 16, (h + 15) / 16), block(16, 16);
   const float4* src = nullptr;
   for (int it = 0; it < kDnPasses; ++it) {

@@ -1916,27 +1916,27 @@ hipError_t shade_attributes(uint32_t lobes, bool three, hipFuncAttributes& at, i
   return e;
 }
 
-hipEvent_t take_event(fh_ctx* ctx)
-{
-  if (!ctx->event_pool.empty()) { hipEvent_t e = ctx->event_pool.back(); ctx->event_pool.pop_back(); return e; }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-
 struct Span {
-  fh_ctx* ctx; hipStream_t st; int kind; hipEvent_t a = nullptr, b = nullptr; bool on;
+  fh_ctx* ctx; hipStream_t st; int kind; Event a, b; bool on;
   Span(fh_ctx* c, hipStream_t s, int k) : ctx(c), st(s), kind(k), on((c->flags & FH_FLAG_TIME_KERNELS) != 0)
   {
     if (on) { a = take_event(ctx); b = take_event(ctx); (void)hipEventRecord(a, st); }
   }
   ~Span()
   {
-    if (on) { (void)hipEventRecord(b, st); ctx->spans.push_back({a, b, kind}); }
+    if (on) { (void)hipEventRecord(b, st); ctx->spans.push_back({std::move(a), std::move(b), kind}); }
   }
 };
 
 }  // namespace
+
+Event take_event(fh_ctx* ctx)
+{
+  Event e;
+  if (!ctx->event_pool.empty()) { e = std::move(ctx->event_pool.back()); ctx->event_pool.pop_back(); }
+  else (void)e.create();
+  return e;
+}
 
 SceneDev scene_dev(const fh_ctx* ctx)
 {
@@ -2007,7 +2007,6 @@ void pool_release(fh_ctx* ctx)
   for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(ctx->aux_stream[k]);
   if (ctx->sky_stream) (void)hipStreamSynchronize(ctx->sky_stream);
   for (int k = 0; k < 3; ++k) {
-    for (void* p : ctx->pool_allocs[k]) (void)hipFree(p);
     ctx->pool_allocs[k].clear();
     ctx->pool_alloc_bytes[k] = 0;
     ctx->pool[k] = PoolDev{};
@@ -2029,7 +2028,6 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
   if (ctx->pool[slot].capacity) {  // growing: nothing may still be running out of the old buffers
     FH_HIP(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 2; ++k) FH_HIP(hipStreamSynchronize(ctx->aux_stream[k]));
-    for (void* p : ctx->pool_allocs[slot]) (void)hipFree(p);
     ctx->pool_allocs[slot].clear();
     ctx->pool_alloc_bytes[slot] = 0;
     if (ctx->pool_target_by_caller && ctx->pool[slot].capacity > capacity) capacity = ctx->pool[slot].capacity;  // (a default-sized pool is re-made at the size the memory cap of this call allows)
@@ -2040,9 +2038,10 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
   }
   PoolDev& P = ctx->pool[slot];
   auto alloc = [&](auto*& ptr, size_t count) -> hipError_t {
-    void* raw = nullptr;
-    hipError_t e = hipMalloc(&raw, count * sizeof(*ptr));
-    if (e == hipSuccess) { ctx->pool_allocs[slot].push_back(raw); ctx->pool_alloc_bytes[slot] += count * sizeof(*ptr); ptr = (decltype(ptr))raw; }
+    DeviceBuffer<uint8_t> buf;
+    hipError_t e = buf.alloc(count * sizeof(*ptr));
+    void* const raw = buf.get();
+    if (e == hipSuccess) { ctx->pool_allocs[slot].push_back(std::move(buf)); ctx->pool_alloc_bytes[slot] += count * sizeof(*ptr); ptr = (decltype(ptr))raw; }
     // FH_POISON=1 (tests): a new pool starts out full of 0xa5 instead of whatever the allocation held, so a kernel that reads a record or a queue entry nobody wrote shows at once
     if (e == hipSuccess && ctx->tun.poison_pools) e = hipMemsetAsync(raw, 0xa5, count * sizeof(*ptr), slot ? ctx->aux_stream[slot - 1] : ctx->stream);
     return e;
@@ -2076,7 +2075,6 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
   };
   const hipError_t e = all();
   if (e != hipSuccess) {  // leave the slot empty rather than half allocated: the next call starts from scratch
-    for (void* p : ctx->pool_allocs[slot]) (void)hipFree(p);
     ctx->pool_allocs[slot].clear();
     ctx->pool_alloc_bytes[slot] = 0;
     P = PoolDev{};
@@ -2148,12 +2146,10 @@ static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
   std::memcpy(ctx->split_key, key, sizeof key);
   ctx->n_wave_px = ctx->n_owned; ctx->n_sky_px = 0;
   if (!(dev < 1e-4f)) { ctx->split_valid = true; return FH_OK; }  // (valid: "no sky pixels" for this key)
-  if (ctx->split_capacity < ctx->n_owned) {
+  if (ctx->d_split[3].size() < ctx->n_owned) {  // (the last of the four: all were made)
     FH_HIP(hipDeviceSynchronize());
-    for (int k = 0; k < 4; ++k) { if (ctx->d_split[k]) (void)hipFree(ctx->d_split[k]); ctx->d_split[k] = nullptr; }
-    ctx->split_capacity = 0;
-    for (int k = 0; k < 4; ++k) FH_HIP(hipMalloc((void**)&ctx->d_split[k], 4ull * ctx->n_owned));
-    ctx->split_capacity = ctx->n_owned;
+    for (int k = 0; k < 4; ++k) ctx->d_split[k].reset();
+    for (int k = 0; k < 4; ++k) FH_HIP(ctx->d_split[k].alloc(ctx->n_owned));
   }
   // no launch of an earlier call may still read the lists that are rewritten here
   FH_HIP(hipStreamSynchronize(ctx->stream));
@@ -2222,18 +2218,12 @@ uint32_t adaptive_to_boundary(const fh_ctx* ctx)
 // launch reads it; with guard blocks also their marks (cleared, sequence 0: no block is marked)
 int adaptive_upload(fh_ctx* ctx)
 {
-  if (!ctx->d_sky_adaptive) FH_HIP(hipMalloc(&ctx->d_sky_adaptive, sizeof(SkyAdaptive)));
+  FH_HIP(ctx->d_sky_adaptive.ensure(sizeof(SkyAdaptive)));
   FH_HIP(hipStreamSynchronize(ctx->stream));  // (earlier calls have joined the main stream)
   if (ctx->adapt_block > 1u) {
     const size_t b = ctx->adapt_block, words = (size_t)((ctx->width + b - 1u) / b) * ((ctx->height + b - 1u) / b);
-    if (words > ctx->marks_capacity) {
-      if (ctx->d_block_marks) (void)hipFree(ctx->d_block_marks);
-      ctx->d_block_marks = nullptr;
-      ctx->marks_capacity = 0;
-      FH_HIP(hipMalloc((void**)&ctx->d_block_marks, 4ull * words));
-      ctx->marks_capacity = words;
-    }
-    FH_HIP(hipMemsetAsync(ctx->d_block_marks, 0, 4ull * ctx->marks_capacity, ctx->stream));  // (the selections run on this stream)
+    FH_HIP(ctx->d_block_marks.ensure(words));
+    FH_HIP(hipMemsetAsync(ctx->d_block_marks, 0, 4ull * ctx->d_block_marks.size(), ctx->stream));  // (the selections run on this stream)
     ctx->mark_seq = 0;
   }
   const SkyAdaptive h{adaptive_dev(ctx), ctx->d_split_counters + 2, ctx->d_sky_taken};
@@ -2247,18 +2237,17 @@ int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const 
                     uint32_t n_sky, uint32_t* n_sky_active)
 {
   const bool blocks = ctx->adapt_block > 1u;
-  if (ctx->active_capacity < ctx->n_owned || !ctx->h_active_count || (blocks && !ctx->d_active[2])) {
+  // (d_active_blocks is made last: without it, an attempt failed half way)
+  if (ctx->d_active[0].size() < ctx->n_owned || !ctx->d_active_blocks || !ctx->h_active_count || (blocks && !ctx->d_active[2])) {
     FH_HIP(hipDeviceSynchronize());  // (launches of earlier calls may still read the old lists)
-    for (int k = 0; k < 4; ++k) { if (ctx->d_active[k]) (void)hipFree(ctx->d_active[k]); ctx->d_active[k] = nullptr; }
-    if (ctx->d_active_blocks) (void)hipFree(ctx->d_active_blocks);
-    ctx->d_active_blocks = nullptr;
-    ctx->active_capacity = 0;
-    for (int k = 0; k < (blocks ? 4 : 2); ++k) FH_HIP(hipMalloc((void**)&ctx->d_active[k], 4ull * ctx->n_owned));
-    FH_HIP(hipMalloc((void**)&ctx->d_active_blocks, 2ull * 4ull * ((ctx->n_owned + kBlock - 1u) / kBlock + 1u)));
-    if (!ctx->h_active_count) FH_HIP(hipHostMalloc((void**)&ctx->h_active_count, 8, hipHostMallocDefault));
-    ctx->active_capacity = ctx->n_owned;
+    for (int k = 0; k < 4; ++k) ctx->d_active[k].reset();
+    ctx->d_active_blocks.reset();
+    FH_HIP(ctx->h_active_count.ensure(2));
+    for (int k = 0; k < (blocks ? 4 : 2); ++k) FH_HIP(ctx->d_active[k].alloc(ctx->n_owned));
+    FH_HIP(ctx->d_active_blocks.alloc(2ull * ((ctx->n_owned + kBlock - 1u) / kBlock + 1u)));
   }
-  if (n_base > ctx->active_capacity || n_sky > ctx->active_capacity) return fail(ctx, FH_E_INVALID, "adaptive_select: base list longer than the owned pixels");
+  const size_t active_capacity = ctx->d_active[0].size();  // the owned pixels when the lists were made
+  if (n_base > active_capacity || n_sky > active_capacity) return fail(ctx, FH_E_INVALID, "adaptive_select: base list longer than the owned pixels");
   if (n_sky && !(blocks && n_sky_active)) return fail(ctx, FH_E_INVALID, "adaptive_select: a sky list is compacted with guard blocks only");
   *n_active = 0;
   if (n_sky_active) *n_sky_active = 0;
@@ -2266,13 +2255,13 @@ int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const 
   if (blocks) {
     if (!ctx->d_block_marks) return fail(ctx, FH_E_INVALID, "adaptive_select: no block marks");
     if (++ctx->mark_seq == 0u) {  // (the sequence wrapped: words of 2^32 selections ago would read as marked)
-      FH_HIP(hipMemsetAsync(ctx->d_block_marks, 0, 4ull * ctx->marks_capacity, st));
+      FH_HIP(hipMemsetAsync(ctx->d_block_marks, 0, 4ull * ctx->d_block_marks.size(), st));
       ctx->mark_seq = 1u;
     }
   }
   const AdaptiveDev ad = adaptive_dev(ctx);
   if (blocks) hipLaunchKernelGGL(k_adaptive_mark, dim3((ctx->n_owned + kBlock - 1u) / kBlock), dim3(kBlock), 0, st, ad, ctx->d_owned, ctx->d_owned_xy, ctx->n_owned);
-  uint32_t* const scan_sky = ctx->d_active_blocks + ((ctx->active_capacity + kBlock - 1u) / kBlock + 1u);
+  uint32_t* const scan_sky = ctx->d_active_blocks + ((active_capacity + kBlock - 1u) / kBlock + 1u);
   auto compact = [&](const uint32_t* px, const uint32_t* xy, uint32_t n, uint32_t* scan, uint32_t* out_px, uint32_t* out_xy, uint32_t* h_count) -> int {
     const uint32_t n_blocks = (n + kBlock - 1u) / kBlock;
     hipLaunchKernelGGL(k_adaptive_count, dim3(n_blocks), dim3(kBlock), 0, st, ad, px, n, scan);
@@ -2382,13 +2371,10 @@ int choose_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr, uint32_
 int quirk_begin(fh_ctx* ctx)
 {
   const size_t px = (size_t)ctx->width * ctx->height;
-  if (ctx->quirk_pixels != px) {
-    if (ctx->d_quirk_seen) (void)hipFree(ctx->d_quirk_seen);
-    if (ctx->d_quirk_aov) (void)hipFree(ctx->d_quirk_aov);
-    ctx->d_quirk_seen = nullptr; ctx->d_quirk_aov = nullptr; ctx->quirk_pixels = 0;
-    FH_HIP(hipMalloc((void**)&ctx->d_quirk_seen, px * sizeof(uint32_t)));
-    FH_HIP(hipMalloc((void**)&ctx->d_quirk_aov, px * 4 * sizeof(float4)));
-    ctx->quirk_pixels = px;
+  if (ctx->d_quirk_aov.size() != px * 4) {  // (the second of the two: both were made)
+    ctx->d_quirk_seen.reset(); ctx->d_quirk_aov.reset();
+    FH_HIP(ctx->d_quirk_seen.alloc(px));
+    FH_HIP(ctx->d_quirk_aov.alloc(px * 4));
   }
   FH_HIP(hipMemsetAsync(ctx->d_quirk_seen, 0, px * sizeof(uint32_t), ctx->stream));   // a launch starts with firsthit = true and a zeroed payload
   FH_HIP(hipMemsetAsync(ctx->d_quirk_aov, 0, px * 4 * sizeof(float4), ctx->stream));
@@ -2423,7 +2409,7 @@ struct SkyLaunches {
     Span sp(ctx, s, 4);
     const uint32_t full = (n + kBlock - 1u) / kBlock;  // (one group per wave)
     const uint32_t grid = wgs < full ? wgs : full;
-    if (adaptive) hipLaunchKernelGGL(k_sky_pixels<true>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, (const SkyAdaptive*)ctx->d_sky_adaptive, cursor);
+    if (adaptive) hipLaunchKernelGGL(k_sky_pixels<true>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, (const SkyAdaptive*)ctx->d_sky_adaptive.get(), cursor);
     else hipLaunchKernelGGL(k_sky_pixels<false>, dim3(grid), dim3(kBlock), 0, s, fr, L, ctx->d_sample_issued, px, xy, n, ns, ctx->d_split_counters + 2, cursor);
   }
   // (the caller has ordered the main stream behind every earlier launch that used the cursor)
@@ -2524,13 +2510,9 @@ int stream_plan(fh_ctx* ctx, const SceneDev& sc, bool count, bool filler, Stream
   // spill area of the streaming launches: [launch in flight: pass slot x (closest, secondary)][entry beyond the LDS part][thread of the launch]
   const size_t spill_threads = (size_t)(p.grid[0] > p.grid[1] ? p.grid[0] : p.grid[1]) * kBlock;
   p.spill_region = (size_t)(p.spill_entries[0] > p.spill_entries[1] ? p.spill_entries[0] : p.spill_entries[1]) * spill_threads;  // uint2 each
-  if (p.spill_region * 6u > ctx->stack_spill_capacity) {
+  if (p.spill_region * 6u > ctx->d_stack_spill.size()) {
     FH_HIP(hipDeviceSynchronize());  // (launches of earlier calls may still use the old area)
-    if (ctx->d_stack_spill) FH_HIP(hipFree(ctx->d_stack_spill));
-    ctx->d_stack_spill = nullptr;
-    ctx->stack_spill_capacity = 0;
-    FH_HIP(hipMalloc((void**)&ctx->d_stack_spill, sizeof(uint2) * p.spill_region * 6u));
-    ctx->stack_spill_capacity = p.spill_region * 6u;
+    FH_HIP(ctx->d_stack_spill.alloc(p.spill_region * 6u));
   }
   const uint32_t chunk_max = stream_chunk_max(tun.stream_chunk_fixed, tun.stream_chunk, ctx->bvh8_n_nodes);
   p.chunk[1] = stream_chunk_word(tun.stream_chunk, chunk_max);
@@ -2754,9 +2736,9 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
   if (p.overlap) {
     p.sb = (st == ctx->aux_stream[0]) ? ctx->aux_stream[1] : ctx->aux_stream[0];
     while (ctx->ev_bounce.size() < 2u * (max_depth + 1u)) {
-      hipEvent_t e = nullptr;
-      FH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ctx->ev_bounce.push_back(e);
+      Event e;
+      FH_HIP(e.create(hipEventDisableTiming));
+      ctx->ev_bounce.push_back(std::move(e));
     }
   }
   // (The shade side of every bounce -- routing, shade kernels, queue sorts -- on a stream of its own, optionally of high priority, with the pass streams kept off some CUs,

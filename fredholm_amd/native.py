@@ -110,7 +110,7 @@ EXPORTS = [
     "fh_free", "fh_memset", "fh_copy_to_device", "fh_copy_to_host", "fh_copy_on_device", "fh_image_load_rgba8", "fh_image_free", "fh_stream", "fh_trace_rays", "fh_kernel_info", "fh_kat_hash", "fh_kat_cmj",
     "fh_kat_sobol", "fh_kat_elementary", "fh_kat_warp", "fh_kat_bsdf", "fh_kat_bsdf_lobes", "fh_kat_bsdf_ior", "fh_kat_sky", "fh_kat_hosek_state", "fh_kat_camera",
     "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
-    "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued",
+    "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued", "fh_kat_live_allocations",
     "fh_set_adaptive_policy", "fh_get_adaptive_policy", "fh_adaptive_next_boundary",
     "fh_denoise_guided", "fh_denoise_temporal", "fh_denoise_history_reset", "fh_denoise_history_info",
     "fh_primary_instances", "fh_motion_from_transforms", "fh_denoise_temporal_motion", "fh_set_denoise_motion", "fh_get_denoise_motion", "fh_kat_chief_rays",
@@ -187,6 +187,7 @@ SIGNATURES = {
     "fh_get_adaptive_policy": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "fh_adaptive_next_boundary": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_kat_set_issued": [C.c_void_p, C.c_void_p, C.c_uint32],
+    "fh_kat_live_allocations": [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "fh_denoise_guided": [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputsC), C.POINTER(DenoiseParamsC), C.c_void_p, C.c_int],
     "fh_denoise_temporal": [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputsC), C.POINTER(CameraC), C.POINTER(TemporalParamsC), C.POINTER(DenoiseParamsC), C.c_void_p, C.c_int],
     "fh_denoise_history_reset": [C.c_void_p],

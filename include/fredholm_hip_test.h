@@ -71,6 +71,11 @@ int fh_kat_sample_counts(fh_ctx* ctx, uint32_t* sample_count, uint32_t* issued, 
    one-sample render then leaves exactly sample issued[i]'s NaN-guarded radiance in pixel i's beauty (the adaptive-sampling tests replay the moments from it) */
 int fh_kat_set_issued(fh_ctx* ctx, const uint32_t* issued, uint32_t n_pixels);
 
+/* device buffers, pinned buffers, events and streams the library's contexts and groups hold in this process right now, and the bytes of the buffers among them
+   (csrc/fh_memory.h; memory from fh_malloc is the caller's and is not counted).  Takes no context; either pointer may be NULL.  A context that has been destroyed
+   leaves both where they were before it was created */
+int fh_kat_live_allocations(uint64_t* count, uint64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif
