@@ -18,6 +18,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
@@ -25,6 +26,7 @@
 #include <chrono>
 #include <cstdlib>
 
+#include "bvh_plan_host.h"
 #include "context.h"
 #include "fh_trace.h"
 
@@ -837,361 +839,492 @@ __global__ void k_box_area_sum(uint32_t n, const float4* box, double* sum)
   if ((threadIdx.x & 63) == 0 && a != 0.0) atomicAdd(sum, a);
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------------------
+// The build on the host.  bvh_build_device, at the bottom, is a sequence of the steps below; what they decide is decided by the pure functions of bvh_plan_host.h.
+// A build assembles its tree in a NewTree; the context's tree fields are written by clear_tree and by the three commits (tiny, full, refit) only, so a failed
+// build leaves the cleared state behind bvh_valid == false.
+typedef std::chrono::steady_clock::time_point TimePoint;
+
+BuildSwitches read_build_switches()  // (the only getenv calls of this file: at the top of every build, not at fh_ctx_create)
+{
+  return build_switches(getenv("FH_REFIT"), getenv("FH_SPLIT"), getenv("FH_BVH_BUILDER"), getenv("FH_ABSORB"), getenv("FH_COLLAPSE"), getenv("FH_BVH2"), getenv("FH_DEBUG_BVH"));
+}
+
+struct FaceBounds {  // per-face boxes, the scene's bounds as ordered ints (k_morton reads them), and the padding and scene box they give
+  DeviceBuffer<float4> lo, hi;
+  DeviceBuffer<int> bounds;
+  ScenePad sp;
+};
+struct References {  // what the trees are built over: the faces' own boxes, or the clipped boxes of early split clipping (ref_face == nullptr: reference i is face i)
+  uint32_t nr = 0;
+  const float4 *box_lo = nullptr, *box_hi = nullptr;
+  const uint32_t* ref_face = nullptr;
+  DeviceBuffer<uint32_t> ref_face_buf, split_count, split_offset;  // (split_count: k_emit_tris8 finds a face's first reference with it)
+  DeviceBuffer<float4> ref_lo, ref_hi;
+};
+struct SortedLeaves {  // the references in Morton order: order[i] is the reference of leaf i; the arrival counters are scratch of the bottom-up kernels
+  DeviceBuffer<uint32_t> order;
+  DeviceBuffer<float4> lo, hi;
+  DeviceBuffer<unsigned int> arrive;
+  // what the sort and the hierarchy worked in.  Kept with the leaves to the end of the build: a hipFree synchronises the device, and these are released after
+  // the build has taken its time (fh_stats::bvh_build_ms), not inside it
+  DeviceBuffer<unsigned long long> keys_a, keys_b;
+  DeviceBuffer<uint32_t> vals_a;
+  DeviceBuffer<int> node_parent, leaf_parent;
+};
+struct BinaryTree {  // nr - 1 inner nodes over the sorted leaves: the radix tree or the PLOC tree
+  DeviceBuffer<int2> children, ranges;
+  DeviceBuffer<float4> node_lo, node_hi;
+  int root = 0;
+};
+struct NewTree {  // what a successful build hands to the context
+  DeviceBuffer<float4> bvh2_nodes, bvh2_tris, bvh8_tris, bvh8_box;
+  DeviceBuffer<uint4> bvh8_nodes;
+  DeviceBuffer<uint32_t> bvh8_parent, face_node;
+  uint32_t bvh2_n_nodes = 0, bvh2_n_tris = 0, bvh8_n_nodes = 0, bvh8_n_tris = 0, levels = 0;
+  bool use_bvh8 = false, refit_ok = false;
+  std::vector<uint32_t> level_start{0u};
+  double area_built = 0.0;
+};
+
+// offset + count of the last element of an exclusive scan: the total
+int scan_total(fh_ctx* ctx, const uint32_t* offset, const uint32_t* count, uint32_t n, uint32_t* total)
+{
+  uint32_t tail[2] = {0, 0};
+  FH_HIP(hipMemcpyAsync(&tail[0], offset + (n - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipMemcpyAsync(&tail[1], count + (n - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  *total = tail[0] + tail[1];
+  return FH_OK;
+}
 
 // boxes of all levels bottom up (requantise = 0: only the full-precision boxes of a freshly built tree), then the sum of the node areas
-static int refit_levels(fh_ctx* ctx, float pad, int requantise, double* area)
+int refit_levels(fh_ctx* ctx, uint4* nodes, const float4* tris, float4* box, const std::vector<uint32_t>& ls, uint32_t n_nodes, float pad, int requantise, double* area)
 {
   hipStream_t st = ctx->stream;
-  const std::vector<uint32_t>& ls = ctx->bvh8_level_start;
   for (size_t l = ls.size() - 1; l-- > 0;) {
     const uint32_t begin = ls[l], end = ls[l + 1];
-    if (end > begin) hipLaunchKernelGGL(k_refit8_level, dim3((end - begin + 127) / 128), dim3(128), 0, st, ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_bvh8_box, begin, end, pad, requantise);
+    if (end > begin) hipLaunchKernelGGL(k_refit8_level, dim3((end - begin + 127) / 128), dim3(128), 0, st, nodes, tris, box, begin, end, pad, requantise);
   }
   DeviceBuffer<double> sum;
   FH_HIP(sum.alloc(1));
   FH_HIP(hipMemsetAsync(sum.get(), 0, 8, st));
-  hipLaunchKernelGGL(k_box_area_sum, dim3((ctx->bvh8_n_nodes + 255) / 256), dim3(256), 0, st, ctx->bvh8_n_nodes, ctx->d_bvh8_box, sum.get());
+  hipLaunchKernelGGL(k_box_area_sum, dim3((n_nodes + 255) / 256), dim3(256), 0, st, n_nodes, box, sum.get());
   FH_HIP(hipMemcpyAsync(area, sum.get(), 8, hipMemcpyDeviceToHost, st));
   FH_HIP(hipGetLastError());
   FH_HIP(hipStreamSynchronize(st));
   return FH_OK;
 }
 
-int bvh_build_device(fh_ctx* ctx)
+void publish_build_time(fh_ctx* ctx, TimePoint t_begin)
 {
-  const auto t_begin = std::chrono::steady_clock::now();
-  hipStream_t st = ctx->stream;
-  const uint32_t n = ctx->n_faces;
-  // ---- instance transforms changed, topology did not: refit (FH_REFIT=0 forces the full rebuild).  A refit whose boxes have grown to
-  // more than 1.5x the area the tree had when it was built is discarded for a rebuild: the instances have moved too far for the old topology.
-  if (ctx->refit_ok && ctx->use_bvh8 && ctx->d_bvh8_box && n && ctx->bvh8_n_tris == n && !(getenv("FH_REFIT") && getenv("FH_REFIT")[0] == '0')) {
-    DeviceBuffer<float4> face_lo, face_hi;
-    DeviceBuffer<int> bounds;
-    FH_HIP(face_lo.alloc(n)); FH_HIP(face_hi.alloc(n)); FH_HIP(bounds.alloc(6));
-    const int init_bounds[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-    FH_HIP(hipMemcpyAsync(bounds.get(), init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_face_bounds, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, n, face_lo.get(), face_hi.get(), bounds.get());
-    hipLaunchKernelGGL(k_refresh_tris8, dim3((8u * ctx->bvh8_n_nodes + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, 8u * ctx->bvh8_n_nodes, ctx->d_bvh8_tris);
-    int hb[6];
-    FH_HIP(hipMemcpyAsync(hb, bounds.get(), sizeof hb, hipMemcpyDeviceToHost, st));
-    FH_HIP(hipStreamSynchronize(st));
-    float maxabs = 0.0f;
-    for (int k = 0; k < 6; ++k) maxabs = fmaxf(maxabs, fabsf(order_float(hb[k])));
-    const float pad = fmaxf(maxabs, 1e-3f) * (1.0f / 65536.0f);
-    double area = 0.0;
-    { const int rc = refit_levels(ctx, pad, 1, &area); if (rc) return rc; }
-    if (area <= 1.5 * ctx->bvh8_area_built) {
-      if (ctx->d_face_node) hipLaunchKernelGGL(k_face_node_to_rec, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_face_node, n, ctx->d_face_rec);  // (k_face_records has just rewritten the records)
-      for (int k = 0; k < 3; ++k) { ctx->scene_lo[k] = order_float(hb[k]) - 2.0f * pad; ctx->scene_hi[k] = order_float(hb[3 + k]) + 2.0f * pad; }
-      ctx->bvh_valid = true;
-      ctx->n_refits++;
-      ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-      ctx->stats.bvh_build_ms = ctx->bvh_build_ms;
-      if (getenv("FH_DEBUG_BVH")) fprintf(stderr, "[bvh] refit %u: node area %.4f (built %.4f), %.3f ms\n", ctx->n_refits, area, ctx->bvh8_area_built, ctx->bvh_build_ms);
-      return FH_OK;
-    }
-    if (getenv("FH_DEBUG_BVH")) fprintf(stderr, "[bvh] refit discarded: node area %.4f > 1.5 x %.4f, rebuilding\n", area, ctx->bvh8_area_built);
-  }
+  ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  ctx->stats.bvh_build_ms = ctx->bvh_build_ms;
+}
+
+void clear_tree(fh_ctx* ctx, uint32_t n)
+{
   ctx->refit_ok = false;
-  ctx->bu_choice = 0; ctx->bu_toggle = 0; ctx->bu_cost[0] = ctx->bu_cost[1] = ctx->bu_items[0] = ctx->bu_items[1] = 0.0;  // a new tree: where its rays should start is measured again (render.hip)
-  ctx->survival_n = 0;  // ... and how long its paths live is not known yet (context.h: survival)
   ctx->d_bvh8_box.reset();
   ctx->bvh8_level_start.clear();
   ctx->d_bvh2_nodes.reset(); ctx->d_bvh2_tris.reset();
   ctx->d_bvh8_nodes.reset(); ctx->d_bvh8_tris.reset(); ctx->d_bvh8_parent.reset(); ctx->d_face_node.reset();
   ctx->bvh2_n_nodes = ctx->bvh2_n_tris = ctx->bvh8_n_nodes = ctx->bvh8_n_tris = 0;
   ctx->use_bvh8 = false;
-  ctx->bvh_valid = false;
-  if (n == 0) { ctx->bvh_valid = true; return FH_OK; }
+  ctx->bvh_valid = n == 0;  // (a scene without faces: the cleared state is its tree)
+}
 
-  DeviceBuffer<float4> face_lo, face_hi, node_lo, node_hi, leaf_lo, leaf_hi;
-  DeviceBuffer<int> bounds, node_parent, leaf_parent;
-  DeviceBuffer<unsigned long long> keys_a, keys_b;
-  DeviceBuffer<uint32_t> vals_a, vals_b;
-  DeviceBuffer<int2> children, ranges;
-  DeviceBuffer<unsigned int> arrive;
-  FH_HIP(face_lo.alloc(n)); FH_HIP(face_hi.alloc(n));
-  FH_HIP(bounds.alloc(6));
-  const int init_bounds[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-  FH_HIP(hipMemcpyAsync(bounds.get(), init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, st));
-  const uint32_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(k_face_bounds, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, n, face_lo.get(), face_hi.get(), bounds.get());
-  int hb[6];
-  FH_HIP(hipMemcpyAsync(hb, bounds.get(), sizeof hb, hipMemcpyDeviceToHost, st));
-  FH_HIP(hipStreamSynchronize(st));
-  float maxabs = 0.0f;
-  for (int k = 0; k < 6; ++k) maxabs = fmaxf(maxabs, fabsf(order_float(hb[k])));
-  const float pad = fmaxf(maxabs, 1e-3f) * (1.0f / 65536.0f);
-  for (int k = 0; k < 3; ++k) { ctx->scene_lo[k] = order_float(hb[k]) - 2.0f * pad; ctx->scene_hi[k] = order_float(hb[3 + k]) + 2.0f * pad; }
-
-  if (n <= kLeafMax2) {
-    FH_HIP(ctx->d_bvh2_tris.alloc(3ull * n));
-    ctx->bvh2_n_tris = n;
-    FH_HIP(ctx->d_bvh2_nodes.alloc(4));
-    FH_HIP(vals_a.alloc(n));
-    std::vector<uint32_t> ident(n);
-    for (uint32_t i = 0; i < n; ++i) ident[i] = i;
-    FH_HIP(hipMemcpyAsync(vals_a.get(), ident.data(), 4ull * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_emit2_tiny, dim3(1), dim3(1), 0, st, (int)n, face_lo.get(), face_hi.get(), pad, ctx->d_bvh2_nodes);
-    hipLaunchKernelGGL(k_emit_tris, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_a.get(), n, ctx->d_bvh2_tris, (const uint32_t*)nullptr);
-    FH_HIP(hipStreamSynchronize(st));
-    ctx->bvh2_n_nodes = 1;
-    if (n <= kLeafMax8) {
-      DeviceBuffer<uint32_t> tri_slot;
-      FH_HIP(tri_slot.alloc(n));
-      FH_HIP(ctx->d_bvh8_nodes.alloc(kBvh8NodeVec));
-      FH_HIP(ctx->d_bvh8_tris.alloc(3ull * 8ull));
-      hipLaunchKernelGGL(k_clear_tris8, dim3(1), dim3(64), 0, st, ctx->d_bvh8_tris, 8u);
-      hipLaunchKernelGGL(k_collapse8_tiny, dim3(1), dim3(1), 0, st, (int)n, face_lo.get(), face_hi.get(), pad, ctx->d_bvh8_nodes, tri_slot.get());
-      hipLaunchKernelGGL(k_emit_tris8, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_a.get(), tri_slot.get(), n, ctx->d_bvh8_tris, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr);
-      FH_HIP(hipStreamSynchronize(st));
-      ctx->bvh8_n_nodes = 1;
-      ctx->bvh8_n_tris = n;
-      ctx->use_bvh8 = true;
-    }
-  } else {
-    // ---- references: large triangles enter the build as several clipped boxes (early split clipping, kernels above)
-    uint32_t nr = n;
-    DeviceBuffer<uint32_t> ref_face_buf, split_count, split_offset;
-    DeviceBuffer<float4> ref_lo, ref_hi;
-    const float4* box_lo = face_lo.get();
-    const float4* box_hi = face_hi.get();
-    const uint32_t* ref_face = nullptr;
-    bool splitting = n >= 256;
-    if (const char* e = getenv("FH_SPLIT")) splitting = splitting && e[0] != '0';
-    if (splitting) {
-      const float extent = fmaxf(fmaxf(ctx->scene_hi[0] - ctx->scene_lo[0], ctx->scene_hi[1] - ctx->scene_lo[1]), ctx->scene_hi[2] - ctx->scene_lo[2]);
-      float thr = extent / 32.0f;
-      const float eps = extent * 1e-6f;
-      FH_HIP(split_count.alloc(n)); FH_HIP(split_offset.alloc(n));
-      size_t scan_bytes = 0;
-      FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, split_count.get(), split_offset.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-      DeviceBuffer<char> scan_tmp;
-      FH_HIP(scan_tmp.alloc(scan_bytes));
-      uint32_t total = n;
-      const double split_budget = 1.5;  // references per face the split may produce at most
-      for (int attempt = 0; attempt < 6; ++attempt, thr *= 2.0f) {  // a scene made of large triangles only: coarser cells until the references fit
-        hipLaunchKernelGGL(k_split_count, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, face_lo.get(), face_hi.get(), n, thr, eps, split_count.get());
-        FH_HIP(rocprim::exclusive_scan(scan_tmp.get(), scan_bytes, split_count.get(), split_offset.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-        uint32_t tail[2];
-        FH_HIP(hipMemcpyAsync(&tail[0], split_offset.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        FH_HIP(hipMemcpyAsync(&tail[1], split_count.get() + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        FH_HIP(hipStreamSynchronize(st));
-        total = tail[0] + tail[1];
-        if ((unsigned long long)total <= (unsigned long long)((double)n * split_budget) + 4096ull) break;
-        total = n;
-      }
-      if (total > n) {
-        nr = total;
-        FH_HIP(ref_face_buf.alloc(nr)); FH_HIP(ref_lo.alloc(nr)); FH_HIP(ref_hi.alloc(nr));
-        hipLaunchKernelGGL(k_split_emit, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, face_lo.get(), face_hi.get(), n, thr, eps, split_count.get(), split_offset.get(), ref_face_buf.get(), ref_lo.get(),
-                           ref_hi.get());
-        box_lo = ref_lo.get(); box_hi = ref_hi.get(); ref_face = ref_face_buf.get();
-      }
-    }
-    const uint32_t rblocks = (nr + 255) / 256;
-    FH_HIP(ctx->d_bvh2_tris.alloc(3ull * nr));
-    ctx->bvh2_n_tris = nr;
-    FH_HIP(keys_a.alloc(nr)); FH_HIP(keys_b.alloc(nr)); FH_HIP(vals_a.alloc(nr)); FH_HIP(vals_b.alloc(nr));
-    hipLaunchKernelGGL(k_morton, dim3(rblocks), dim3(256), 0, st, box_lo, box_hi, nr, bounds.get(), keys_a.get(), vals_a.get());
-    size_t temp_bytes = 0;
-    FH_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_a.get(), keys_b.get(), vals_a.get(), vals_b.get(), (size_t)nr, 0u, 63u, st));
-    DeviceBuffer<char> temp;
-    FH_HIP(temp.alloc(temp_bytes));
-    FH_HIP(rocprim::radix_sort_pairs(temp.get(), temp_bytes, keys_a.get(), keys_b.get(), vals_a.get(), vals_b.get(), (size_t)nr, 0u, 63u, st));
-    const uint32_t n_inner = nr - 1;
-    FH_HIP(children.alloc(n_inner)); FH_HIP(ranges.alloc(n_inner)); FH_HIP(node_parent.alloc(n_inner)); FH_HIP(leaf_parent.alloc(nr));
-    FH_HIP(node_lo.alloc(n_inner)); FH_HIP(node_hi.alloc(n_inner)); FH_HIP(leaf_lo.alloc(nr)); FH_HIP(leaf_hi.alloc(nr));
-    FH_HIP(arrive.alloc(n_inner));
-    FH_HIP(hipMemsetAsync(arrive.get(), 0, 4ull * n_inner, st));
-    const uint32_t iblocks = (n_inner + 255) / 256;
-    hipLaunchKernelGGL(k_hierarchy, dim3(iblocks), dim3(256), 0, st, keys_b.get(), (int)nr, children.get(), ranges.get(), node_parent.get(), leaf_parent.get());
-    hipLaunchKernelGGL(k_refit, dim3(rblocks), dim3(256), 0, st, vals_b.get(), box_lo, box_hi, (int)nr, children.get(), node_parent.get(), leaf_parent.get(), node_lo.get(), node_hi.get(), leaf_lo.get(),
-                       leaf_hi.get(), arrive.get());
-    FH_HIP(ctx->d_bvh2_nodes.alloc(4ull * n_inner));
-    hipLaunchKernelGGL(k_emit2, dim3(iblocks), dim3(256), 0, st, (int)n_inner, children.get(), ranges.get(), node_lo.get(), node_hi.get(), leaf_lo.get(), leaf_hi.get(), pad, ctx->d_bvh2_nodes);
-    hipLaunchKernelGGL(k_emit_tris, dim3(rblocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_b.get(), nr, ctx->d_bvh2_tris, ref_face);
-    FH_HIP(hipGetLastError());
-    FH_HIP(hipStreamSynchronize(st));
-    ctx->bvh2_n_nodes = n_inner;
-
-    // ---- optional: replace the radix tree by a PLOC tree as the input of the collapse (the binary fallback above keeps the radix tree)
-    int root_node = 0;
-    // FH_BVH_BUILDER = lbvh | ploc | auto (default).  auto: the first build after an upload makes both trees and keeps PLOC when the
-    // sum of its inner-node areas is at least 7 % below the radix tree's (non-uniform scenes: -29 % on tools' `city`, 9 % faster
-    // frames; -9 % on the Sponza-class glTF, 5 % faster frames); on a uniform soup the two are within 3 % and the radix tree traverses
-    // faster (closest-hit rays need the well separated children of a Morton split for the octant order to work), so it stays.  Later builds of the same
-    // scene (animation) reuse the choice.
-    int mode = ctx->builder_choice;
-    if (const char* e = getenv("FH_BVH_BUILDER")) { if (std::strcmp(e, "ploc") == 0) mode = 2; else if (std::strcmp(e, "lbvh") == 0) mode = 1; }
-    const bool deciding = mode == 0;
-    bool ploc = mode == 2 || deciding;
-    bool ploc_failed = false;
-    DeviceBuffer<int2> p_children, p_ranges;
-    DeviceBuffer<float4> p_node_lo, p_node_hi;
-    if (ploc) {
-      DeviceBuffer<int> cid_a, cid_b, nn;
-      DeviceBuffer<float4> clo_a, chi_a, clo_b, chi_b;
-      DeviceBuffer<uint32_t> valid, offset, node_counter;
-      FH_HIP(cid_a.alloc(nr)); FH_HIP(cid_b.alloc(nr)); FH_HIP(nn.alloc(nr)); FH_HIP(clo_a.alloc(nr)); FH_HIP(chi_a.alloc(nr)); FH_HIP(clo_b.alloc(nr)); FH_HIP(chi_b.alloc(nr));
-      FH_HIP(valid.alloc(nr)); FH_HIP(offset.alloc(nr)); FH_HIP(node_counter.alloc(1));
-      FH_HIP(p_children.alloc(n_inner)); FH_HIP(p_ranges.alloc(n_inner)); FH_HIP(p_node_lo.alloc(n_inner)); FH_HIP(p_node_hi.alloc(n_inner));
-      FH_HIP(hipMemsetAsync(node_counter.get(), 0, 4, st));
-      hipLaunchKernelGGL(k_ploc_init, dim3(rblocks), dim3(256), 0, st, (int)nr, leaf_lo.get(), leaf_hi.get(), cid_a.get(), clo_a.get(), chi_a.get());
-      size_t scan_bytes = 0;
-      FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, valid.get(), offset.get(), 0u, (size_t)nr, rocprim::plus<uint32_t>(), st));
-      DeviceBuffer<char> scan_tmp;
-      FH_HIP(scan_tmp.alloc(scan_bytes));
-      const int ploc_radius = kPlocRadius;  // neighbours searched to either side
-      int* cid = cid_a.get(); int* cid_o = cid_b.get();
-      float4 *clo = clo_a.get(), *chi = chi_a.get(), *clo_o = clo_b.get(), *chi_o = chi_b.get();
-      uint32_t count = nr;
-      for (int round = 0; count > 1 && round < 4096; ++round) {
-        const uint32_t b = (count + 255) / 256;
-        hipLaunchKernelGGL(k_ploc_nearest, dim3(b), dim3(256), 0, st, (int)count, clo, chi, nn.get(), ploc_radius);
-        hipLaunchKernelGGL(k_ploc_merge, dim3(b), dim3(256), 0, st, (int)count, nn.get(), cid, clo, chi, valid.get(), p_children.get(), p_ranges.get(), p_node_lo.get(), p_node_hi.get(), node_counter.get());
-        FH_HIP(rocprim::exclusive_scan(scan_tmp.get(), scan_bytes, valid.get(), offset.get(), 0u, (size_t)count, rocprim::plus<uint32_t>(), st));
-        hipLaunchKernelGGL(k_ploc_compact, dim3(b), dim3(256), 0, st, (int)count, valid.get(), offset.get(), cid, clo, chi, cid_o, clo_o, chi_o);
-        uint32_t tail[2] = {0, 0};  // offset and flag of the last cluster -> new count
-        FH_HIP(hipMemcpyAsync(&tail[0], offset.get() + (count - 1), 4, hipMemcpyDeviceToHost, st));
-        FH_HIP(hipMemcpyAsync(&tail[1], valid.get() + (count - 1), 4, hipMemcpyDeviceToHost, st));
-        FH_HIP(hipStreamSynchronize(st));
-        const uint32_t next = tail[0] + tail[1];
-        if (next >= count) {  // no mutual pair found (non-finite boxes): in auto mode the radix tree built above is still valid
-          if (!deciding) return fail(ctx, FH_E_INVALID, "PLOC made no progress");
-          ploc_failed = true;
-          break;
-        }
-        count = next;
-        int* t = cid; cid = cid_o; cid_o = t;
-        float4* tl = clo; clo = clo_o; clo_o = tl;
-        float4* th = chi; chi = chi_o; chi_o = th;
-      }
-      if (!ploc_failed) {
-        FH_HIP(hipMemcpyAsync(&root_node, cid, 4, hipMemcpyDeviceToHost, st));
-        FH_HIP(hipStreamSynchronize(st));
-        if (root_node < 0 || (uint32_t)root_node >= n_inner) {
-          if (!deciding) return fail(ctx, FH_E_INVALID, "PLOC did not end in one inner node");
-          ploc_failed = true;
-        }
-      }
-      if (ploc_failed) { ploc = false; ctx->builder_choice = 1; }  // auto mode falls back to the radix tree; an explicit FH_BVH_BUILDER=ploc reported the error above
-    }
-    if (deciding || getenv("FH_DEBUG_BVH")) {
-      DeviceBuffer<double> sums;
-      FH_HIP(sums.alloc(2));
-      FH_HIP(hipMemsetAsync(sums.get(), 0, 16, st));
-      hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, node_lo.get(), node_hi.get(), sums.get());
-      if (ploc) hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, p_node_lo.get(), p_node_hi.get(), sums.get() + 1);
-      double h[2];
-      FH_HIP(hipMemcpyAsync(h, sums.get(), 16, hipMemcpyDeviceToHost, st));
-      FH_HIP(hipStreamSynchronize(st));
-      if (deciding && !ploc_failed) {
-        ploc = h[1] < 0.93 * h[0];
-        ctx->builder_choice = ploc ? 2 : 1;
-      }
-      if (getenv("FH_DEBUG_BVH")) fprintf(stderr, "[bvh] sum of inner-node areas: radix tree %.4f, PLOC %.4f -> %s\n", h[0], h[1], ploc ? "PLOC" : "radix tree");
-    }
-    if (!ploc) root_node = 0;  // the radix tree's root is node 0
-    const int2* c_children = ploc ? p_children.get() : children.get();
-    const int2* c_ranges = ploc ? p_ranges.get() : ranges.get();
-    const float4* c_node_lo = ploc ? p_node_lo.get() : node_lo.get();
-    const float4* c_node_hi = ploc ? p_node_hi.get() : node_hi.get();
-
-    // (SAH refinement of the chosen binary tree by parallel reinsertion, Meister & Bittner 2018, was built in round 5: the summed inner-node area falls by 2-7 %, the node visits per
-    // ray do not -- 15.28 -> 15.12 on configs[2], 11.73 -> 11.81 on configs[3].  profiles/README.md r5-1, tools/patches/r6_pruned_switches.patch)
-
-    // ---- collapse to BVH8, breadth first
-    DeviceBuffer<Work8> work_a, work_b;
-    DeviceBuffer<uint32_t> counters, tri_slot;  // [0] node counter, [1] triangle counter, [2] next-level item count; triangle slot of every sorted leaf
-    FH_HIP(work_a.alloc(n_inner)); FH_HIP(work_b.alloc(n_inner)); FH_HIP(counters.alloc(3)); FH_HIP(tri_slot.alloc(nr));
-    FH_HIP(ctx->d_bvh8_nodes.alloc((size_t)kBvh8NodeVec * n_inner));
-    FH_HIP(ctx->d_bvh8_parent.alloc(n_inner));
-    FH_HIP(ctx->d_face_node.alloc(n));
-    FH_HIP(hipMemsetAsync(ctx->d_bvh8_parent, 0xff, 4ull * n_inner, st));  // (the root keeps 0xffffffff: no way up)
-    FH_HIP(hipMemsetAsync(ctx->d_face_node, 0xff, 4ull * n, st));
-    const uint32_t leaf_max8 = 1;  // one triangle per leaf child (the node layout has one triangle slot per child slot): box tests are ~4x cheaper than triangle tests (profiles/README.md)
-    uint32_t absorb8 = 1u;  // FH_ABSORB=0: plain largest-child-first collapse
-    if (const char* e = getenv("FH_ABSORB")) absorb8 = e[0] != '0' ? 1u : 0u;
-    // the cut of least summed wide-node area (k_cut_tables); FH_COLLAPSE=greedy: the largest-child-first rule above
-    bool optimal_cut = leaf_max8 == 1;
-    if (const char* e = getenv("FH_COLLAPSE")) optimal_cut = optimal_cut && std::strcmp(e, "greedy") != 0;
-    DeviceBuffer<float> cut_cost_tab;
-    DeviceBuffer<uint2> cut_decision;
-    if (optimal_cut) {
-      DeviceBuffer<int> c_node_parent, c_leaf_parent;
-      FH_HIP(c_node_parent.alloc(n_inner)); FH_HIP(c_leaf_parent.alloc(nr)); FH_HIP(cut_cost_tab.alloc(7ull * n_inner)); FH_HIP(cut_decision.alloc(n_inner));
-      FH_HIP(hipMemsetAsync(c_node_parent.get(), 0xff, 4ull * n_inner, st));  // the root keeps -1
-      FH_HIP(hipMemsetAsync(arrive.get(), 0, 4ull * n_inner, st));
-      hipLaunchKernelGGL(k_tree_parents, dim3(iblocks), dim3(256), 0, st, (int)n_inner, c_children, c_node_parent.get(), c_leaf_parent.get());
-      hipLaunchKernelGGL(k_cut_tables, dim3(rblocks), dim3(256), 0, st, (int)nr, c_children, c_node_parent.get(), c_leaf_parent.get(), c_node_lo, c_node_hi, arrive.get(), cut_cost_tab.get(),
-                         cut_decision.get());
-      FH_HIP(hipGetLastError());
-      FH_HIP(hipStreamSynchronize(st));  // (the parent arrays go out of scope here)
-      if (getenv("FH_DEBUG_BVH")) {
-        float c_root = 0.0f;
-        FH_HIP(hipMemcpy(&c_root, cut_cost_tab.get() + 7ull * (size_t)root_node, 4, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[bvh] least summed area of the wide nodes (cut tables, root): %.4f\n", c_root);
-      }
-    }
-    const Work8 root{root_node, 0u};
-    const uint32_t init_counters[3] = {1u, 0u, 0u};
-    FH_HIP(hipMemcpyAsync(work_a.get(), &root, sizeof root, hipMemcpyHostToDevice, st));
-    FH_HIP(hipMemcpyAsync(counters.get(), init_counters, sizeof init_counters, hipMemcpyHostToDevice, st));
-    uint32_t level_count = 1;
-    Work8* cur = work_a.get();
-    Work8* nxt = work_b.get();
-    uint32_t levels = 0;
-    std::vector<uint32_t> level_start{0u};
-    for (int level = 0; level < 64 && level_count > 0; ++level) {
-      ++levels;
-      level_start.push_back(level_start.back() + level_count);
-      FH_HIP(hipMemsetAsync(counters.get() + 2, 0, 4, st));
-      hipLaunchKernelGGL(k_collapse8, dim3((level_count + 63) / 64), dim3(64), 0, st, cur, level_count, c_children, c_ranges, c_node_lo, c_node_hi, leaf_lo.get(), leaf_hi.get(), pad,
-                         leaf_max8, absorb8, ctx->d_bvh8_nodes, counters.get(), counters.get() + 1, tri_slot.get(), nxt, counters.get() + 2, optimal_cut ? cut_decision.get() : (const uint2*)nullptr, ctx->d_bvh8_parent);
-      FH_HIP(hipMemcpyAsync(&level_count, counters.get() + 2, 4, hipMemcpyDeviceToHost, st));
-      FH_HIP(hipStreamSynchronize(st));
-      Work8* t = cur; cur = nxt; nxt = t;
-    }
-    uint32_t final_counters[2] = {0, 0};
-    FH_HIP(hipMemcpyAsync(final_counters, counters.get(), 8, hipMemcpyDeviceToHost, st));
-    FH_HIP(hipStreamSynchronize(st));
-    if (final_counters[1] != nr) return fail(ctx, FH_E_INVALID, "BVH8 collapse lost triangles");
-    if (levels > (uint32_t)kBvh8Stack) return fail(ctx, FH_E_UNSUPPORTED, "BVH8 deeper than the traversal stack (48 levels)");
-    if (final_counters[0] >= (1u << 24)) return fail(ctx, FH_E_UNSUPPORTED, "BVH8 with 2^24 or more nodes (the traversal stack keeps node indices in 24 bits)");
-    if (final_counters[0] >= kCoopMaxTris / 8u) return fail(ctx, FH_E_UNSUPPORTED, "BVH8 with 2^23 or more nodes (the cooperative triangle queue keeps triangle slots in 26 bits)");
-    ctx->bvh8_depth = levels;
-    const uint32_t n_slots = 8u * final_counters[0];  // one triangle slot per child slot
-    FH_HIP(ctx->d_bvh8_tris.alloc(3ull * n_slots));
-    hipLaunchKernelGGL(k_clear_tris8, dim3((n_slots + 255) / 256), dim3(256), 0, st, ctx->d_bvh8_tris, n_slots);
-    hipLaunchKernelGGL(k_emit_tris8, dim3(rblocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, vals_b.get(), tri_slot.get(), nr, ctx->d_bvh8_tris, ref_face, ctx->d_face_node, ref_face ? split_count.get() : (const uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_face_node_to_rec, dim3(blocks), dim3(256), 0, st, ctx->d_face_node, n, ctx->d_face_rec);
-    FH_HIP(hipGetLastError());
-    FH_HIP(hipStreamSynchronize(st));
-    ctx->bvh8_n_nodes = final_counters[0];
-    ctx->bvh8_n_tris = nr;
-    ctx->use_bvh8 = true;
-    // what a later refit needs: the level ranges, the full-precision node boxes and the area the tree has now.  Split references carry
-    // clipped boxes that a moved triangle no longer has, so scenes that use them are rebuilt instead.
-    if (nr == n && level_start.back() == final_counters[0]) {
-      ctx->bvh8_level_start = level_start;
-      FH_HIP(ctx->d_bvh8_box.alloc(2ull * final_counters[0]));
-      const int rc = refit_levels(ctx, pad, 0, &ctx->bvh8_area_built);
-      if (rc) return rc;
-      ctx->refit_ok = true;
-      ctx->n_refits = 0;
-    }
-  }
+void commit_scene_box(fh_ctx* ctx, const ScenePad& sp)
+{
+  for (int k = 0; k < 3; ++k) { ctx->scene_lo[k] = sp.lo[k]; ctx->scene_hi[k] = sp.hi[k]; }
   ctx->bvh_valid = true;
-  ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  ctx->stats.bvh_build_ms = ctx->bvh_build_ms;
-  if (getenv("FH_BVH2")) ctx->use_bvh8 = false;  // developer switch: traverse the binary layout instead of the wide one
-  ctx->stats.bvh_nodes = ctx->use_bvh8 ? ctx->bvh8_n_nodes : ctx->bvh2_n_nodes;
-  ctx->stats.bvh_node_bytes = ctx->use_bvh8 ? 16ull * kBvh8NodeVec * ctx->bvh8_n_nodes : 64ull * ctx->bvh2_n_nodes;
-  ctx->stats.bvh_tri_bytes = ctx->use_bvh8 ? 48ull * 8ull * ctx->bvh8_n_nodes : 48ull * ctx->bvh2_n_tris;  // (wide tree: eight triangle slots per node)
-  ctx->stats.bvh_depth = ctx->use_bvh8 ? ctx->bvh8_depth : 0;
+}
+void commit_refit(fh_ctx* ctx, const ScenePad& sp)
+{
+  commit_scene_box(ctx, sp);
+  ctx->n_refits++;
+}
+// the binary root of up to kLeafMax2 faces and, up to kLeafMax8, the single wide node beside it (bvh8_depth keeps what the last full build left)
+void commit_tiny(fh_ctx* ctx, const BuildSwitches& sw, const ScenePad& sp, NewTree& t)
+{
+  commit_scene_box(ctx, sp);
+  ctx->d_bvh2_nodes = std::move(t.bvh2_nodes); ctx->d_bvh2_tris = std::move(t.bvh2_tris);
+  ctx->d_bvh8_nodes = std::move(t.bvh8_nodes); ctx->d_bvh8_tris = std::move(t.bvh8_tris);
+  ctx->bvh2_n_nodes = t.bvh2_n_nodes; ctx->bvh2_n_tris = t.bvh2_n_tris; ctx->bvh8_n_nodes = t.bvh8_n_nodes; ctx->bvh8_n_tris = t.bvh8_n_tris;
+  ctx->use_bvh8 = traverse_wide(t.use_bvh8, sw);
+}
+void commit_full(fh_ctx* ctx, const BuildSwitches& sw, const ScenePad& sp, NewTree& t)
+{
+  commit_tiny(ctx, sw, sp, t);
+  ctx->d_bvh8_parent = std::move(t.bvh8_parent); ctx->d_face_node = std::move(t.face_node);
+  ctx->bvh8_depth = t.levels;
+  if (!t.refit_ok) return;
+  ctx->bvh8_level_start = std::move(t.level_start);
+  ctx->d_bvh8_box = std::move(t.bvh8_box);
+  ctx->bvh8_area_built = t.area_built;
+  ctx->refit_ok = true;
+  ctx->n_refits = 0;
+}
+
+void publish_stats(fh_ctx* ctx, TimePoint t_begin)
+{
+  publish_build_time(ctx, t_begin);
+  const TreeStats s = tree_stats(ctx->use_bvh8, ctx->bvh8_n_nodes, ctx->bvh8_depth, ctx->bvh2_n_nodes, ctx->bvh2_n_tris, kBvh8NodeVec);
+  ctx->stats.bvh_nodes = s.nodes;
+  ctx->stats.bvh_node_bytes = s.node_bytes;
+  ctx->stats.bvh_tri_bytes = s.tri_bytes;
+  ctx->stats.bvh_depth = s.depth;
+}
+
+// Boxes of the faces, and the scene's bounds with the padding they give.  refit: the triangle copies of the wide tree are refreshed from the moved face records
+// in the same submission.
+int scene_bounds(fh_ctx* ctx, uint32_t n, bool refit, FaceBounds& fb)
+{
+  hipStream_t st = ctx->stream;
+  FH_HIP(fb.lo.alloc(n)); FH_HIP(fb.hi.alloc(n)); FH_HIP(fb.bounds.alloc(6));
+  const int init_bounds[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
+  FH_HIP(hipMemcpyAsync(fb.bounds.get(), init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_face_bounds, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, n, fb.lo.get(), fb.hi.get(), fb.bounds.get());
+  if (refit) hipLaunchKernelGGL(k_refresh_tris8, dim3((8u * ctx->bvh8_n_nodes + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, 8u * ctx->bvh8_n_nodes, ctx->d_bvh8_tris);
+  int hb[6];
+  FH_HIP(hipMemcpyAsync(hb, fb.bounds.get(), sizeof hb, hipMemcpyDeviceToHost, st));
+  FH_HIP(hipStreamSynchronize(st));
+  const float b[6] = {order_float(hb[0]), order_float(hb[1]), order_float(hb[2]), order_float(hb[3]), order_float(hb[4]), order_float(hb[5])};
+  fb.sp = scene_padding(b);
+  return FH_OK;
+}
+
+// Instance transforms changed, topology did not: the wide tree is refitted in place.  *kept == false: not eligible, or the boxes have grown too far for the old
+// topology and the caller rebuilds.
+int try_refit(fh_ctx* ctx, uint32_t n, const BuildSwitches& sw, TimePoint t_begin, bool* kept)
+{
+  *kept = false;
+  if (!refit_eligible(ctx->refit_ok, ctx->use_bvh8, ctx->d_bvh8_box.get() != nullptr, n, ctx->bvh8_n_tris, sw)) return FH_OK;
+  FaceBounds fb;
+  if (const int rc = scene_bounds(ctx, n, true, fb)) return rc;
+  double area = 0.0;
+  if (const int rc = refit_levels(ctx, ctx->d_bvh8_nodes, ctx->d_bvh8_tris, ctx->d_bvh8_box, ctx->bvh8_level_start, ctx->bvh8_n_nodes, fb.sp.pad, 1, &area)) return rc;
+  if (!refit_accepted(area, ctx->bvh8_area_built)) {
+    if (sw.debug) fprintf(stderr, "[bvh] refit discarded: node area %.4f > 1.5 x %.4f, rebuilding\n", area, ctx->bvh8_area_built);
+    return FH_OK;
+  }
+  if (ctx->d_face_node) hipLaunchKernelGGL(k_face_node_to_rec, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_face_node, n, ctx->d_face_rec);  // (k_face_records has just rewritten the records)
+  commit_refit(ctx, fb.sp);
+  publish_build_time(ctx, t_begin);
+  if (sw.debug) fprintf(stderr, "[bvh] refit %u: node area %.4f (built %.4f), %.3f ms\n", ctx->n_refits, area, ctx->bvh8_area_built, ctx->bvh_build_ms);
+  *kept = true;
+  return FH_OK;
+}
+
+// up to kLeafMax2 faces: the binary root with its one leaf; up to kLeafMax8 also a wide root with one leaf child per face
+int build_tiny(fh_ctx* ctx, uint32_t n, bool wide, const FaceBounds& fb, NewTree& t)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t blocks = (n + 255) / 256;
+  const float pad = fb.sp.pad;
+  DeviceBuffer<uint32_t> order, tri_slot;
+  FH_HIP(t.bvh2_tris.alloc(3ull * n));
+  FH_HIP(t.bvh2_nodes.alloc(4));
+  FH_HIP(order.alloc(n));
+  std::vector<uint32_t> ident(n);
+  for (uint32_t i = 0; i < n; ++i) ident[i] = i;
+  FH_HIP(hipMemcpyAsync(order.get(), ident.data(), 4ull * n, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_emit2_tiny, dim3(1), dim3(1), 0, st, (int)n, fb.lo.get(), fb.hi.get(), pad, t.bvh2_nodes.get());
+  hipLaunchKernelGGL(k_emit_tris, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, order.get(), n, t.bvh2_tris.get(), (const uint32_t*)nullptr);
+  FH_HIP(hipStreamSynchronize(st));
+  t.bvh2_n_tris = n;
+  t.bvh2_n_nodes = 1;
+  if (!wide) return FH_OK;
+  FH_HIP(tri_slot.alloc(n));
+  FH_HIP(t.bvh8_nodes.alloc(kBvh8NodeVec));
+  FH_HIP(t.bvh8_tris.alloc(3ull * 8ull));
+  hipLaunchKernelGGL(k_clear_tris8, dim3(1), dim3(64), 0, st, t.bvh8_tris.get(), 8u);
+  hipLaunchKernelGGL(k_collapse8_tiny, dim3(1), dim3(1), 0, st, (int)n, fb.lo.get(), fb.hi.get(), pad, t.bvh8_nodes.get(), tri_slot.get());
+  hipLaunchKernelGGL(k_emit_tris8, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, order.get(), tri_slot.get(), n, t.bvh8_tris.get(), (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr);
+  FH_HIP(hipStreamSynchronize(st));
+  t.bvh8_n_nodes = 1;
+  t.bvh8_n_tris = n;
+  t.use_bvh8 = true;
+  return FH_OK;
+}
+
+// references: large triangles enter the build as several clipped boxes (early split clipping, kernels above)
+int split_references(fh_ctx* ctx, uint32_t n, const BuildSwitches& sw, const FaceBounds& fb, References& r)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t blocks = (n + 255) / 256;
+  r.nr = n;
+  r.box_lo = fb.lo.get();
+  r.box_hi = fb.hi.get();
+  if (!split_enabled(n, sw)) return FH_OK;
+  const SplitCells cells = split_cells(fb.sp.lo, fb.sp.hi);
+  float thr = cells.thr;
+  FH_HIP(r.split_count.alloc(n)); FH_HIP(r.split_offset.alloc(n));
+  size_t scan_bytes = 0;
+  FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, r.split_count.get(), r.split_offset.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+  DeviceBuffer<char> scan_tmp;
+  FH_HIP(scan_tmp.alloc(scan_bytes));
+  uint32_t total = n;
+  const int rc = split_search(n, &thr, &total, [&](float cell, uint32_t* found) {
+    hipLaunchKernelGGL(k_split_count, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, fb.lo.get(), fb.hi.get(), n, cell, cells.eps, r.split_count.get());
+    FH_HIP(rocprim::exclusive_scan(scan_tmp.get(), scan_bytes, r.split_count.get(), r.split_offset.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+    return scan_total(ctx, r.split_offset.get(), r.split_count.get(), n, found);
+  });
+  if (rc || total <= n) return rc;
+  r.nr = total;
+  FH_HIP(r.ref_face_buf.alloc(r.nr)); FH_HIP(r.ref_lo.alloc(r.nr)); FH_HIP(r.ref_hi.alloc(r.nr));
+  hipLaunchKernelGGL(k_split_emit, dim3(blocks), dim3(256), 0, st, ctx->d_face_rec, fb.lo.get(), fb.hi.get(), n, thr, cells.eps, r.split_count.get(), r.split_offset.get(), r.ref_face_buf.get(), r.ref_lo.get(),
+                     r.ref_hi.get());
+  r.box_lo = r.ref_lo.get(); r.box_hi = r.ref_hi.get(); r.ref_face = r.ref_face_buf.get();
+  return FH_OK;
+}
+
+// Morton codes, sort, Karras hierarchy, bottom-up boxes; and the binary traversal layout (the fallback, which keeps the radix tree whatever the collapse takes)
+int build_radix_tree(fh_ctx* ctx, const References& r, const FaceBounds& fb, SortedLeaves& leaves, BinaryTree& radix, NewTree& t)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t nr = r.nr, n_inner = nr - 1, rblocks = (nr + 255) / 256, iblocks = (n_inner + 255) / 256;
+  FH_HIP(t.bvh2_tris.alloc(3ull * nr));
+  FH_HIP(leaves.keys_a.alloc(nr)); FH_HIP(leaves.keys_b.alloc(nr)); FH_HIP(leaves.vals_a.alloc(nr)); FH_HIP(leaves.order.alloc(nr));
+  hipLaunchKernelGGL(k_morton, dim3(rblocks), dim3(256), 0, st, r.box_lo, r.box_hi, nr, fb.bounds.get(), leaves.keys_a.get(), leaves.vals_a.get());
+  size_t temp_bytes = 0;
+  FH_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, leaves.keys_a.get(), leaves.keys_b.get(), leaves.vals_a.get(), leaves.order.get(), (size_t)nr, 0u, 63u, st));
+  DeviceBuffer<char> temp;
+  FH_HIP(temp.alloc(temp_bytes));
+  FH_HIP(rocprim::radix_sort_pairs(temp.get(), temp_bytes, leaves.keys_a.get(), leaves.keys_b.get(), leaves.vals_a.get(), leaves.order.get(), (size_t)nr, 0u, 63u, st));
+  FH_HIP(radix.children.alloc(n_inner)); FH_HIP(radix.ranges.alloc(n_inner)); FH_HIP(leaves.node_parent.alloc(n_inner)); FH_HIP(leaves.leaf_parent.alloc(nr));
+  FH_HIP(radix.node_lo.alloc(n_inner)); FH_HIP(radix.node_hi.alloc(n_inner)); FH_HIP(leaves.lo.alloc(nr)); FH_HIP(leaves.hi.alloc(nr));
+  FH_HIP(leaves.arrive.alloc(n_inner));
+  FH_HIP(hipMemsetAsync(leaves.arrive.get(), 0, 4ull * n_inner, st));
+  hipLaunchKernelGGL(k_hierarchy, dim3(iblocks), dim3(256), 0, st, leaves.keys_b.get(), (int)nr, radix.children.get(), radix.ranges.get(), leaves.node_parent.get(), leaves.leaf_parent.get());
+  hipLaunchKernelGGL(k_refit, dim3(rblocks), dim3(256), 0, st, leaves.order.get(), r.box_lo, r.box_hi, (int)nr, radix.children.get(), leaves.node_parent.get(), leaves.leaf_parent.get(), radix.node_lo.get(), radix.node_hi.get(),
+                     leaves.lo.get(), leaves.hi.get(), leaves.arrive.get());
+  FH_HIP(t.bvh2_nodes.alloc(4ull * n_inner));
+  hipLaunchKernelGGL(k_emit2, dim3(iblocks), dim3(256), 0, st, (int)n_inner, radix.children.get(), radix.ranges.get(), radix.node_lo.get(), radix.node_hi.get(), leaves.lo.get(), leaves.hi.get(), fb.sp.pad, t.bvh2_nodes.get());
+  hipLaunchKernelGGL(k_emit_tris, dim3(rblocks), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, leaves.order.get(), nr, t.bvh2_tris.get(), r.ref_face);
+  FH_HIP(hipGetLastError());
+  FH_HIP(hipStreamSynchronize(st));
+  t.bvh2_n_tris = nr;
+  t.bvh2_n_nodes = n_inner;
+  radix.root = 0;  // the radix tree's root is node 0
+  return FH_OK;
+}
+
+// PLOC over the sorted leaves: rounds of nearest-neighbour search, merge of the mutual pairs and compaction until one cluster is left.  *failed (auto mode
+// only; an explicit FH_BVH_BUILDER=ploc reports the error): no mutual pair found (non-finite boxes), or the last cluster is no inner node.
+int build_ploc_tree(fh_ctx* ctx, uint32_t nr, const BuilderPlan& plan, const SortedLeaves& leaves, BinaryTree& tree, bool* failed)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t n_inner = nr - 1, rblocks = (nr + 255) / 256;
+  DeviceBuffer<int> cid_a, cid_b, nn;
+  DeviceBuffer<float4> clo_a, chi_a, clo_b, chi_b;
+  DeviceBuffer<uint32_t> valid, offset, node_counter;
+  FH_HIP(cid_a.alloc(nr)); FH_HIP(cid_b.alloc(nr)); FH_HIP(nn.alloc(nr)); FH_HIP(clo_a.alloc(nr)); FH_HIP(chi_a.alloc(nr)); FH_HIP(clo_b.alloc(nr)); FH_HIP(chi_b.alloc(nr));
+  FH_HIP(valid.alloc(nr)); FH_HIP(offset.alloc(nr)); FH_HIP(node_counter.alloc(1));
+  FH_HIP(tree.children.alloc(n_inner)); FH_HIP(tree.ranges.alloc(n_inner)); FH_HIP(tree.node_lo.alloc(n_inner)); FH_HIP(tree.node_hi.alloc(n_inner));
+  FH_HIP(hipMemsetAsync(node_counter.get(), 0, 4, st));
+  hipLaunchKernelGGL(k_ploc_init, dim3(rblocks), dim3(256), 0, st, (int)nr, leaves.lo.get(), leaves.hi.get(), cid_a.get(), clo_a.get(), chi_a.get());
+  size_t scan_bytes = 0;
+  FH_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, valid.get(), offset.get(), 0u, (size_t)nr, rocprim::plus<uint32_t>(), st));
+  DeviceBuffer<char> scan_tmp;
+  FH_HIP(scan_tmp.alloc(scan_bytes));
+  const int ploc_radius = kPlocRadius;  // neighbours searched to either side
+  int* cid = cid_a.get(); int* cid_o = cid_b.get();
+  float4 *clo = clo_a.get(), *chi = chi_a.get(), *clo_o = clo_b.get(), *chi_o = chi_b.get();
+  uint32_t count = nr;
+  for (int round = 0; count > 1 && round < 4096; ++round) {
+    const uint32_t b = (count + 255) / 256;
+    hipLaunchKernelGGL(k_ploc_nearest, dim3(b), dim3(256), 0, st, (int)count, clo, chi, nn.get(), ploc_radius);
+    hipLaunchKernelGGL(k_ploc_merge, dim3(b), dim3(256), 0, st, (int)count, nn.get(), cid, clo, chi, valid.get(), tree.children.get(), tree.ranges.get(), tree.node_lo.get(), tree.node_hi.get(), node_counter.get());
+    FH_HIP(rocprim::exclusive_scan(scan_tmp.get(), scan_bytes, valid.get(), offset.get(), 0u, (size_t)count, rocprim::plus<uint32_t>(), st));
+    hipLaunchKernelGGL(k_ploc_compact, dim3(b), dim3(256), 0, st, (int)count, valid.get(), offset.get(), cid, clo, chi, cid_o, clo_o, chi_o);
+    uint32_t next = 0;  // offset and flag of the last cluster -> new count
+    if (const int rc = scan_total(ctx, offset.get(), valid.get(), count, &next)) return rc;
+    if (next >= count) {
+      if (ploc_failure_is_error(plan)) return fail(ctx, FH_E_INVALID, "PLOC made no progress");
+      *failed = true;
+      return FH_OK;
+    }
+    count = next;
+    std::swap(cid, cid_o); std::swap(clo, clo_o); std::swap(chi, chi_o);
+  }
+  FH_HIP(hipMemcpyAsync(&tree.root, cid, 4, hipMemcpyDeviceToHost, st));
+  FH_HIP(hipStreamSynchronize(st));
+  if (tree.root < 0 || (uint32_t)tree.root >= n_inner) {
+    if (ploc_failure_is_error(plan)) return fail(ctx, FH_E_INVALID, "PLOC did not end in one inner node");
+    *failed = true;
+  }
+  return FH_OK;
+}
+
+// The binary tree the collapse takes.  While deciding (and for the debug line) the sums of the inner-node areas of both trees are measured: -29 % for PLOC on
+// tools' `city`, 9 % faster frames; -9 % on the Sponza-class glTF, 5 % faster frames; on a uniform soup the two are within 3 % and the radix tree traverses faster
+// (closest-hit rays need the well separated children of a Morton split for the octant order to work), so it stays.
+int choose_builder(fh_ctx* ctx, uint32_t n_inner, const BuildSwitches& sw, const BuilderPlan& plan, bool ploc_failed, const BinaryTree& radix, const BinaryTree& ploc, const BinaryTree** chosen)
+{
+  hipStream_t st = ctx->stream;
+  double h[2] = {0.0, 0.0};
+  if (plan.deciding || sw.debug) {
+    const uint32_t iblocks = (n_inner + 255) / 256;
+    DeviceBuffer<double> sums;
+    FH_HIP(sums.alloc(2));
+    FH_HIP(hipMemsetAsync(sums.get(), 0, 16, st));
+    hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, radix.node_lo.get(), radix.node_hi.get(), sums.get());
+    if (plan.ploc && !ploc_failed) hipLaunchKernelGGL(k_sah_sum, dim3(iblocks), dim3(256), 0, st, (int)n_inner, ploc.node_lo.get(), ploc.node_hi.get(), sums.get() + 1);
+    FH_HIP(hipMemcpyAsync(h, sums.get(), 16, hipMemcpyDeviceToHost, st));
+    FH_HIP(hipStreamSynchronize(st));
+  }
+  const BuilderVerdict v = builder_verdict(plan, ploc_failed, h);
+  if (v.choice) ctx->builder_choice = v.choice;
+  if (sw.debug) fprintf(stderr, "[bvh] sum of inner-node areas: radix tree %.4f, PLOC %.4f -> %s\n", h[0], h[1], v.ploc ? "PLOC" : "radix tree");
+  *chosen = v.ploc ? &ploc : &radix;
+  return FH_OK;
+}
+
+// the cut of least summed wide-node area below every node of the binary tree (k_cut_tables), bottom up with the tree's parents
+int fill_cut_tables(fh_ctx* ctx, uint32_t nr, const BuildSwitches& sw, const BinaryTree& tree, const SortedLeaves& leaves, DeviceBuffer<float>& cost_tab, DeviceBuffer<uint2>& decision)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t n_inner = nr - 1;
+  DeviceBuffer<int> node_parent, leaf_parent;
+  FH_HIP(node_parent.alloc(n_inner)); FH_HIP(leaf_parent.alloc(nr)); FH_HIP(cost_tab.alloc(7ull * n_inner)); FH_HIP(decision.alloc(n_inner));
+  FH_HIP(hipMemsetAsync(node_parent.get(), 0xff, 4ull * n_inner, st));  // the root keeps -1
+  FH_HIP(hipMemsetAsync(leaves.arrive.get(), 0, 4ull * n_inner, st));
+  hipLaunchKernelGGL(k_tree_parents, dim3((n_inner + 255) / 256), dim3(256), 0, st, (int)n_inner, tree.children.get(), node_parent.get(), leaf_parent.get());
+  hipLaunchKernelGGL(k_cut_tables, dim3((nr + 255) / 256), dim3(256), 0, st, (int)nr, tree.children.get(), node_parent.get(), leaf_parent.get(), tree.node_lo.get(), tree.node_hi.get(), leaves.arrive.get(), cost_tab.get(),
+                     decision.get());
+  FH_HIP(hipGetLastError());
+  FH_HIP(hipStreamSynchronize(st));  // (the parent arrays go out of scope here)
+  if (sw.debug) {
+    float c_root = 0.0f;
+    FH_HIP(hipMemcpy(&c_root, cost_tab.get() + 7ull * (size_t)tree.root, 4, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[bvh] least summed area of the wide nodes (cut tables, root): %.4f\n", c_root);
+  }
+  return FH_OK;
+}
+
+// Collapse of the chosen binary tree to BVH8, breadth first, one launch per level; then the limits the traversal sets.  tri_slot: triangle slot of every sorted leaf.
+// (SAH refinement of the binary tree by parallel reinsertion, Meister & Bittner 2018, was built in round 5: the summed inner-node area falls by 2-7 %, the node visits per
+// ray do not -- 15.28 -> 15.12 on configs[2], 11.73 -> 11.81 on configs[3].  profiles/README.md r5-1, tools/patches/r6_pruned_switches.patch)
+int collapse_wide(fh_ctx* ctx, uint32_t n, uint32_t nr, const BuildSwitches& sw, float pad, const BinaryTree& tree, const SortedLeaves& leaves, DeviceBuffer<uint32_t>& tri_slot, NewTree& t)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t n_inner = nr - 1;
+  const CollapsePlan plan = collapse_plan(sw);
+  DeviceBuffer<Work8> work_a, work_b;
+  DeviceBuffer<uint32_t> counters;  // [0] node counter, [1] triangle counter, [2] next-level item count
+  FH_HIP(work_a.alloc(n_inner)); FH_HIP(work_b.alloc(n_inner)); FH_HIP(counters.alloc(3)); FH_HIP(tri_slot.alloc(nr));
+  FH_HIP(t.bvh8_nodes.alloc((size_t)kBvh8NodeVec * n_inner));
+  FH_HIP(t.bvh8_parent.alloc(n_inner));
+  FH_HIP(t.face_node.alloc(n));
+  FH_HIP(hipMemsetAsync(t.bvh8_parent.get(), 0xff, 4ull * n_inner, st));  // (the root keeps 0xffffffff: no way up)
+  FH_HIP(hipMemsetAsync(t.face_node.get(), 0xff, 4ull * n, st));
+  DeviceBuffer<float> cut_cost_tab;
+  DeviceBuffer<uint2> cut_decision;
+  if (plan.optimal_cut)
+    if (const int rc = fill_cut_tables(ctx, nr, sw, tree, leaves, cut_cost_tab, cut_decision)) return rc;
+  const Work8 root{tree.root, 0u};
+  const uint32_t init_counters[3] = {1u, 0u, 0u};
+  FH_HIP(hipMemcpyAsync(work_a.get(), &root, sizeof root, hipMemcpyHostToDevice, st));
+  FH_HIP(hipMemcpyAsync(counters.get(), init_counters, sizeof init_counters, hipMemcpyHostToDevice, st));
+  uint32_t level_count = 1;
+  Work8* cur = work_a.get();
+  Work8* nxt = work_b.get();
+  for (int level = 0; level < 64 && level_count > 0; ++level) {
+    ++t.levels;
+    t.level_start.push_back(t.level_start.back() + level_count);
+    FH_HIP(hipMemsetAsync(counters.get() + 2, 0, 4, st));
+    hipLaunchKernelGGL(k_collapse8, dim3((level_count + 63) / 64), dim3(64), 0, st, cur, level_count, tree.children.get(), tree.ranges.get(), tree.node_lo.get(), tree.node_hi.get(), leaves.lo.get(), leaves.hi.get(), pad,
+                       plan.leaf_max8, plan.absorb8, t.bvh8_nodes.get(), counters.get(), counters.get() + 1, tri_slot.get(), nxt, counters.get() + 2, plan.optimal_cut ? cut_decision.get() : (const uint2*)nullptr, t.bvh8_parent.get());
+    FH_HIP(hipMemcpyAsync(&level_count, counters.get() + 2, 4, hipMemcpyDeviceToHost, st));
+    FH_HIP(hipStreamSynchronize(st));
+    std::swap(cur, nxt);
+  }
+  uint32_t final_counters[2] = {0, 0};
+  FH_HIP(hipMemcpyAsync(final_counters, counters.get(), 8, hipMemcpyDeviceToHost, st));
+  FH_HIP(hipStreamSynchronize(st));
+  const BuildError e = collapse_limits(final_counters[1], nr, t.levels, final_counters[0], (uint32_t)kBvh8Stack, kCoopMaxTris, FH_E_INVALID, FH_E_UNSUPPORTED);
+  if (e.code) return fail(ctx, e.code, e.msg);
+  t.bvh8_n_nodes = final_counters[0];
+  return FH_OK;
+}
+
+// the triangle copies of the wide tree, one slot per child slot; the wide node of every face, also into the face's record
+int emit_wide_triangles(fh_ctx* ctx, uint32_t n, const References& r, const SortedLeaves& leaves, const DeviceBuffer<uint32_t>& tri_slot, NewTree& t)
+{
+  hipStream_t st = ctx->stream;
+  const uint32_t n_slots = 8u * t.bvh8_n_nodes;
+  FH_HIP(t.bvh8_tris.alloc(3ull * n_slots));
+  hipLaunchKernelGGL(k_clear_tris8, dim3((n_slots + 255) / 256), dim3(256), 0, st, t.bvh8_tris.get(), n_slots);
+  hipLaunchKernelGGL(k_emit_tris8, dim3((r.nr + 255) / 256), dim3(256), 0, st, ctx->d_face_rec, ctx->d_face_cls, leaves.order.get(), tri_slot.get(), r.nr, t.bvh8_tris.get(), r.ref_face, t.face_node.get(),
+                     r.ref_face ? r.split_count.get() : (const uint32_t*)nullptr);
+  hipLaunchKernelGGL(k_face_node_to_rec, dim3((n + 255) / 256), dim3(256), 0, st, t.face_node.get(), n, ctx->d_face_rec);
+  FH_HIP(hipGetLastError());
+  FH_HIP(hipStreamSynchronize(st));
+  t.bvh8_n_tris = r.nr;
+  t.use_bvh8 = true;
+  return FH_OK;
+}
+
+// what a later refit needs: the level ranges, the full-precision node boxes and the area the tree has now
+int keep_for_refit(fh_ctx* ctx, uint32_t n, uint32_t nr, float pad, NewTree& t)
+{
+  if (!tree_refittable(nr, n, t.level_start.back(), t.bvh8_n_nodes)) return FH_OK;
+  FH_HIP(t.bvh8_box.alloc(2ull * t.bvh8_n_nodes));
+  if (const int rc = refit_levels(ctx, t.bvh8_nodes.get(), t.bvh8_tris.get(), t.bvh8_box.get(), t.level_start, t.bvh8_n_nodes, pad, 0, &t.area_built)) return rc;
+  t.refit_ok = true;
+  return FH_OK;
+}
+
+}  // namespace
+
+void reset_tree_measurements(fh_ctx* ctx)
+{
+  ctx->bu_choice = 0; ctx->bu_toggle = 0; ctx->bu_cost[0] = ctx->bu_cost[1] = ctx->bu_items[0] = ctx->bu_items[1] = 0.0;  // a new tree: where its rays should start is measured again (render.hip)
+  ctx->survival_n = 0;  // ... and how long its paths live is not known yet (context.h: survival)
+}
+
+int bvh_build_device(fh_ctx* ctx)
+{
+  const TimePoint t_begin = std::chrono::steady_clock::now();
+  const uint32_t n = ctx->n_faces;
+  const BuildSwitches sw = read_build_switches();
+  bool refitted = false;
+  if (const int rc = try_refit(ctx, n, sw, t_begin, &refitted)) return rc;
+  if (refitted) return FH_OK;
+  reset_tree_measurements(ctx);
+  clear_tree(ctx, n);
+  const TreeShape shape = tree_shape(n, kLeafMax8, kLeafMax2);
+  if (shape == TreeShape::Empty) return FH_OK;
+
+  FaceBounds fb;
+  SortedLeaves leaves;  // (these three outlive the timed part of the build, like the boxes of the faces)
+  BinaryTree radix;
+  NewTree tree;
+  if (const int rc = scene_bounds(ctx, n, false, fb)) return rc;
+  if (shape != TreeShape::Full) {
+    if (const int rc = build_tiny(ctx, n, shape == TreeShape::WideRoot, fb, tree)) return rc;
+    commit_tiny(ctx, sw, fb.sp, tree);
+  } else {
+    References refs;
+    BinaryTree ploc;
+    const BinaryTree* chosen = nullptr;
+    DeviceBuffer<uint32_t> tri_slot;
+    bool ploc_failed = false;
+    if (const int rc = split_references(ctx, n, sw, fb, refs)) return rc;
+    if (const int rc = build_radix_tree(ctx, refs, fb, leaves, radix, tree)) return rc;
+    const BuilderPlan plan = builder_plan(ctx->builder_choice, sw);
+    if (plan.ploc)
+      if (const int rc = build_ploc_tree(ctx, refs.nr, plan, leaves, ploc, &ploc_failed)) return rc;
+    if (const int rc = choose_builder(ctx, refs.nr - 1, sw, plan, ploc_failed, radix, ploc, &chosen)) return rc;
+    if (const int rc = collapse_wide(ctx, n, refs.nr, sw, fb.sp.pad, *chosen, leaves, tri_slot, tree)) return rc;
+    if (const int rc = emit_wide_triangles(ctx, n, refs, leaves, tri_slot, tree)) return rc;
+    if (const int rc = keep_for_refit(ctx, n, refs.nr, fb.sp.pad, tree)) return rc;
+    commit_full(ctx, sw, fb.sp, tree);
+  }
+  publish_stats(ctx, t_begin);
   return FH_OK;
 }
 
 }  // namespace fh
+

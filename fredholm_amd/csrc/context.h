@@ -316,6 +316,7 @@ uint32_t owned_count(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, 
 Event take_event(fh_ctx* ctx);  // render.hip: a timing event from ctx->event_pool, or a new one
 SceneDev scene_dev(const fh_ctx* ctx);
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip
+void reset_tree_measurements(fh_ctx* ctx);         // bvh_build.hip: a new tree; what the render path has measured on the old one (bu_*, survival) starts again
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);  // render.hip
 int adaptive_upload(fh_ctx* ctx);  // render.hip
 int adaptive_select(fh_ctx* ctx, hipStream_t st, const uint32_t* base_px, const uint32_t* base_xy, uint32_t n_base, uint32_t* n_active, const uint32_t* sky_px = nullptr,

@@ -272,6 +272,62 @@ def test_closest_and_any_hit_match_checker(oracle, n_tris, edge):
     r.close()
 
 
+def _small_scene(n):
+    """n well-formed triangles inside the unit box [0,1]^3: every edge at least 0.1 long, every height at least 0.05, nothing degenerate, displaced or scaled.
+    The triangles span up to half the box for the scenes of a few faces and a quarter of it for the 255/256 ones, so that rays both hit and miss."""
+    rng = np.random.default_rng(20240 + n)
+    span = np.float32(0.5 if n <= 5 else 0.125)
+    tris = []
+    while len(tris) < n:
+        c = rng.uniform(0.0, 1.0, 3).astype(np.float32)
+        v = (c + rng.uniform(-1.0, 1.0, (3, 3)).astype(np.float32) * span).astype(np.float32)
+        e = np.linalg.norm(v - np.roll(v, 1, axis=0), axis=1)
+        area2 = np.linalg.norm(np.cross(v[1] - v[0], v[2] - v[0]))
+        if v.min() < 0.0 or v.max() > 1.0 or e.min() < 0.1 or area2 / e.max() < 0.05:
+            continue
+        tris.append(v)
+    return scenes._finish(np.concatenate(tris), np.zeros(n, np.uint32), default_materials(1))
+
+
+def _small_scene_rays(sc, n_rays=2000):
+    """a quarter of the rays in random directions from around the box, half aimed at a point of a triangle, a quarter aimed likewise but ending short of it"""
+    n = sc["indices"].shape[0]
+    rng = np.random.default_rng(977 + n)
+    rays = _rays(rng, n_rays, -0.5, 1.5)
+    k = n_rays // 4
+    v = sc["vertices"].reshape(-1, 3, 3)
+    b = rng.dirichlet((1.0, 1.0, 1.0), n_rays - k).astype(np.float32)
+    to = (v[rng.integers(0, n, n_rays - k)] * b[:, :, None]).sum(axis=1) - rays[k:, 0:3]
+    dist = np.linalg.norm(to, axis=1, keepdims=True)
+    rays[k:, 3:6] = to / dist
+    rays[3 * k:, 6] = dist[2 * k:, 0] * rng.uniform(0.1, 0.9, n_rays - 3 * k).astype(np.float32)
+    return np.ascontiguousarray(rays, dtype=np.float32)
+
+
+@pytest.mark.parametrize("n_tris", [1, 3, 4, 5, 255, 256])
+def test_small_scenes_take_each_build_path(oracle, n_tris):
+    """The builder's paths for small scenes: up to 3 faces a single wide node, 4 faces the binary fallback, 5 the smallest tree that is collapsed, 255 / 256 either
+    side of where split clipping starts.  Closest hits and any-hits equal the checker's to the last bit, and at least a tenth of the rays hit and a tenth miss."""
+    sc = _small_scene(n_tris)
+    rays = _small_scene_rays(sc)
+    tuv_o, prim_o = oracle.Scene(sc).trace(rays)
+    hit_share = (prim_o != 0xFFFFFFFF).mean()
+    assert 0.1 <= hit_share <= 0.9, hit_share
+    r = F.Renderer(0)
+    r.load_scene(sc)
+    r.build_ias()
+    st = r.stats()
+    tuv_g, prim_g = r.trace_rays(rays)
+    assert np.array_equal(prim_g, prim_o)
+    assert np.array_equal(_bits(tuv_g), _bits(tuv_o))
+    assert np.array_equal(r.trace_rays(rays, any_hit=True)[1] != 0xFFFFFFFF, prim_o != 0xFFFFFFFF)
+    if n_tris <= 4:
+        assert st["bvh_nodes"] == 1
+    if n_tris == 4:
+        assert st["bvh_depth"] == 0  # (the binary layout: four faces are one leaf of it, and more than the single wide node takes)
+    r.close()
+
+
 @pytest.mark.parametrize("n_tris,edge,n", [(5000, 0.02, 40000), (200000, 0.01, 2500)])
 def test_rays_from_far_outside_the_scene_match_checker(oracle, n_tris, edge, n):
     """A ray that starts 10^3 .. 10^6 scene sizes away: the slab distances (p - o) * inv then carry a rounding error that grows with |p - o| and passes the
