@@ -14,8 +14,9 @@ Each test compares the frame's mean residual (pixel - E) with its empirical stan
 The model's lobes (f_i, pmf_i * pdf_i) come from the checker's orc_bsdf_lobes, which the GPU parity suite pins bit for bit to the
 device's.  Large surfaces are built from tiles of <= 20 units: on triangles of 1e3-1e4 units the error of the watertight test exceeds
 ray_origin_offset's epsilon (pt.cu:405-416), the floor's own shadow, light and continuation rays hit it again, and a Lambertian
-floor under a constant background renders 0.79 rho (depth 1) / 1.12 rho (depth 8) instead of rho, on both sides alike.  Whether
-the offset should scale with the triangle is left for a follow-up.
+floor under a constant background renders 0.79 rho (depth 1) / 1.12 rho (depth 8) instead of rho, on both sides alike.  Where
+that starts is measured by test_where_surfaces_start_to_shadow_themselves (test_trace_exact_host.py, test_gpu_trace_exact.py): no
+leaving ray hits its own surface again up to a half-extent of 20 units, 0.4 % do at 100 (tilted), 11-23 % at 1e3, 28-34 % at 1e4.
 """
 from statistics import NormalDist
 
