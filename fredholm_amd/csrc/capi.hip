@@ -828,6 +828,7 @@ int fh_load_arhosek_sky(fh_ctx* ctx, float turbidity, float albedo)
   ctx->has_hosek = true;
   FH_HIP(hipMemcpyAsync(ctx->d_hosek, &ctx->hosek, sizeof ctx->hosek, hipMemcpyHostToDevice, ctx->stream));  // (ordered after the frames already submitted)
   FH_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->env_stale = true;
   return FH_OK;
 }
 int fh_clear_arhosek_sky(fh_ctx* ctx)
@@ -835,6 +836,7 @@ int fh_clear_arhosek_sky(fh_ctx* ctx)
   FH_GROUP_EACH(ctx, kGroupCallScene, fh_clear_arhosek_sky(m_));
   CTX_CHECK(ctx);
   ctx->has_hosek = false;
+  ctx->env_stale = true;
   return FH_OK;
 }
 int fh_load_ibl(fh_ctx* ctx, const float* rgba, uint32_t w, uint32_t h)
@@ -843,6 +845,7 @@ int fh_load_ibl(fh_ctx* ctx, const float* rgba, uint32_t w, uint32_t h)
   CTX_CHECK(ctx);
   if (!rgba || w == 0 || h == 0) return fail(ctx, FH_E_INVALID, "fh_load_ibl: empty image");
   (void)hipStreamSynchronize(ctx->stream);
+  ctx->env_stale = true;
   FH_HIP(ctx->d_ibl.alloc(4ull * w * h));
   FH_HIP(hipMemcpy(ctx->d_ibl, rgba, sizeof(float) * 4ull * w * h, hipMemcpyHostToDevice));
   ctx->ibl_w = w;
@@ -855,6 +858,24 @@ int fh_clear_ibl(fh_ctx* ctx)
   CTX_CHECK(ctx);
   (void)hipStreamSynchronize(ctx->stream);
   ctx->d_ibl.reset();
+  ctx->env_stale = true;
+  return FH_OK;
+}
+
+// importance sampling of the environment (envmap.hip, fh_envmap.h).  The refusal is decided before the context is looked at; a scene call, so every member of a group gets it
+int fh_set_env_sampling(fh_ctx* ctx, const fh_env_sampling_params* params)
+{
+  if (const char* why = env_sampling_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_env_sampling: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_env_sampling(m_, params));
+  CTX_CHECK(ctx);
+  return env_sampling_set(ctx, params);
+}
+int fh_get_env_sampling(fh_ctx* ctx, int* on, fh_env_sampling_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->env_sampling;
+  if (params) params->cosine_fraction = ctx->env_cosine_fraction;
   return FH_OK;
 }
 

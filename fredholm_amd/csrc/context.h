@@ -10,6 +10,7 @@
 
 #include "../../include/fredholm_hip.h"
 #include "fh_device.h"
+#include "fh_envmap.h"
 #include "fh_memory.h"
 
 struct fh_group;  // group.hip
@@ -146,6 +147,15 @@ struct fh_ctx {
   bool has_hosek = false;
   fh::HosekSky hosek{};
   fh::DeviceBuffer<fh::HosekSky> d_hosek;  // device copy (FrameDev::hosek)
+  // fh_set_env_sampling (envmap.hip, fh_envmap.h): the table of the environment's luminance the sky rays are drawn from.  Allocated when the switch first goes on;
+  // env_stale: the environment changed since it was built (the next fh_render rebuilds it on the context stream)
+  int env_sampling = 0;
+  float env_cosine_fraction = FH_ENV_COSINE_FRACTION_DEFAULT;
+  bool env_stale = true;
+  fh::DeviceBuffer<float> d_env_w;         // cell means, then one word: the bits of their maximum
+  fh::DeviceBuffer<uint32_t> d_env_q;      // integer weights, then the 256 row sums
+  fh::DeviceBuffer<unsigned long long> d_env_total;
+  fh::DeviceBuffer<float> d_env_cdf_row, d_env_cdf_m, d_env_cell_p;
 
   // path pools: one per pass in flight (pass j uses slot j % n_slots and the stream of that slot); allocated on first use
   fh::PoolDev pool[3] = {};
@@ -315,6 +325,7 @@ uint32_t owned_count(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, 
 
 Event take_event(fh_ctx* ctx);  // render.hip: a timing event from ctx->event_pool, or a new one
 SceneDev scene_dev(const fh_ctx* ctx);
+inline EnvTable env_table_dev(const fh_ctx* ctx) { return EnvTable{ctx->d_env_cdf_row, ctx->d_env_cdf_m, ctx->d_env_cell_p, ctx->env_cosine_fraction}; }
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip
 void reset_tree_measurements(fh_ctx* ctx);         // bvh_build.hip: a new tree; what the render path has measured on the old one (bu_*, survival) starts again
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);  // render.hip
@@ -338,5 +349,9 @@ int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in
 // ids == nullptr: no motion stage; else ids a device pointer and motion a host array of n_instances entries of which at least one has moved (k_temporal<kLookMotion, .>)
 int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
                             const fh_denoise_params* params, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale);
+// envmap.hip: the switch with its device memory (arguments checked by the caller); the rebuild of a stale table, queued on the context stream
+int env_sampling_set(fh_ctx* ctx, const fh_env_sampling_params* params);
+int env_table_ensure(fh_ctx* ctx);
+FrameDev env_frame(const fh_ctx* ctx);  // the environment as the table weighs it: sky intensity 1, a white background
 int primary_instances_submit(fh_ctx* ctx, const fh_camera* cam, uint32_t w, uint32_t h, uint32_t* ids);  // motion.hip (arguments checked by the caller)
 }  // namespace fh

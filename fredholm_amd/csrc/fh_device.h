@@ -98,6 +98,22 @@ struct FrameDev {
   BsdfTables lut;
 };
 
+// environment seen along d: IBL, else Hosek sky, else the constant background (pt.cu:511-517, :536-542)
+// (ROLLED_SKY: fh_sky.h, hosek_radiance_form)
+template <bool ROLLED_SKY = false>
+FH_D f3 env_radiance(const FrameDev& fr, f3 d)
+{
+  if (fr.has_ibl) {  // fetch_ibl (pt.cu:344-350) with cartesian_to_spherical (math.cu:111-118)
+    const float theta = fhe_acos(clampf(d.y, -1.0f, 1.0f));
+    float phi = fhe_atan2(d.z, d.x);
+    if (phi < 0) phi += 2.0f * kPi;
+    float o[4];
+    fht_tex2d(&fr.ibl, nullptr, phi / (2.0f * kPi), theta / kPi, o);
+    return fr.sky_intensity * mk3(o[0], o[1], o[2]);
+  }
+  return fr.has_hosek ? hosek_radiance_form<ROLLED_SKY>(*fr.hosek, fr.sun_dir, fr.sky_intensity, d) : fr.bg;
+}
+
 // A path's state is kept in records, not in one array per field: after the first bounce the queues hold path slots in spatial order, so every access to
 // slot p is a random one and a kernel that touches n fields of a path touched n cache lines.  With records the closest-hit kernel reads a ray and writes its
 // hit in ONE 64-byte line, the shade kernel finds ray, throughput and hit in that same line, and the up to four secondary rays of a path are contiguous.

@@ -282,6 +282,31 @@ __global__ void k_sqrt_some(uint32_t n, const float* in, float* out)
   if (i < n) out[i] = fhe_sqrt(in[i]);
 }
 
+// fh_set_env_sampling: the draw of the sky slot, the evaluator, and the environment as the table weighs it.  The frame is the one shade_hit builds round a normal
+__global__ void k_env_sample(EnvTable t, uint32_t n, const float* u2, const float* n3, float* dir3, float* pdf, uint32_t* cell)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const f3 ns = mk3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]);
+  f3 tangent, bitangent;
+  onb(ns, tangent, bitangent);
+  const f3 d = env_sample(t, mk2(u2[2 * i], u2[2 * i + 1]), tangent, ns, bitangent, pdf[i], cell[i]);
+  dir3[3 * i] = d.x; dir3[3 * i + 1] = d.y; dir3[3 * i + 2] = d.z;
+}
+__global__ void k_env_pdf(EnvTable t, uint32_t n, const float* d3, const float* n3, float* pdf, uint32_t* cell)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  pdf[i] = env_pdf(t, EnvDir{d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]}, EnvDir{n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]}, &cell[i]);
+}
+__global__ void k_env_radiance(FrameDev fr, uint32_t n, const float* d3, float* out)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const f3 r = env_radiance(fr, mk3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]));
+  out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+
 uint32_t blocks(uint32_t n) { return (n + 255) / 256; }
 
 }  // namespace
@@ -416,6 +441,61 @@ int fh_kat_sky(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3)
   DeviceBuffer<float> a, o;
   FH_HIP(up(a, dirs3, 3ull * n)); FH_HIP(up(o, nullptr, 3ull * n));
   hipLaunchKernelGGL(k_sky, dim3(blocks(n)), dim3(256), 0, ctx->stream, ctx->hosek, mk3(ctx->sun_dir[0], ctx->sun_dir[1], ctx->sun_dir[2]), ctx->sky_intensity, n, a.get(), o.get());
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(down(o, out3));
+  return FH_OK;
+}
+// the hooks of fh_set_env_sampling work on the CURRENT table: a stale one is rebuilt first, as fh_render would
+static int kat_env_table(fh_ctx* ctx, const char* who)
+{
+  if (!ctx->env_sampling) return fail(ctx, FH_E_INVALID, std::string(who) + ": environment sampling is off (fh_set_env_sampling)");
+  return env_table_ensure(ctx);
+}
+int fh_kat_env_table(fh_ctx* ctx, uint32_t* weights, float* cdf_row, float* cdf_marginal, float* cell_p)
+{
+  KCTX(ctx);
+  if (!weights || !cdf_row || !cdf_marginal || !cell_p) return fail(ctx, FH_E_INVALID, "fh_kat_env_table: null argument");
+  if (const int rc = kat_env_table(ctx, "fh_kat_env_table")) return rc;
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(hipMemcpy(weights, ctx->d_env_q, sizeof(uint32_t) * kEnvCells, hipMemcpyDeviceToHost));
+  FH_HIP(hipMemcpy(cdf_row, ctx->d_env_cdf_row, sizeof(float) * kEnvH * kEnvRowCdf, hipMemcpyDeviceToHost));
+  FH_HIP(hipMemcpy(cdf_marginal, ctx->d_env_cdf_m, sizeof(float) * (kEnvH + 1), hipMemcpyDeviceToHost));
+  FH_HIP(hipMemcpy(cell_p, ctx->d_env_cell_p, sizeof(float) * kEnvCells, hipMemcpyDeviceToHost));
+  return FH_OK;
+}
+int fh_kat_env_sample(fh_ctx* ctx, uint32_t n, const float* u2, const float* normal3, float* dir3, float* pdf, uint32_t* cell)
+{
+  KCTX(ctx);
+  if (!u2 || !normal3 || !dir3 || !pdf || !cell) return fail(ctx, FH_E_INVALID, "fh_kat_env_sample: null argument");
+  if (const int rc = kat_env_table(ctx, "fh_kat_env_sample")) return rc;
+  DeviceBuffer<float> a, b, d, p;
+  DeviceBuffer<uint32_t> c;
+  FH_HIP(up(a, u2, 2ull * n)); FH_HIP(up(b, normal3, 3ull * n)); FH_HIP(up(d, nullptr, 3ull * n)); FH_HIP(up(p, nullptr, n)); FH_HIP(up(c, nullptr, n));
+  hipLaunchKernelGGL(k_env_sample, dim3(blocks(n)), dim3(256), 0, ctx->stream, env_table_dev(ctx), n, a.get(), b.get(), d.get(), p.get(), c.get());
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(down(d, dir3)); FH_HIP(down(p, pdf)); FH_HIP(down(c, cell));
+  return FH_OK;
+}
+int fh_kat_env_pdf(fh_ctx* ctx, uint32_t n, const float* dirs3, const float* normal3, float* pdf, uint32_t* cell)
+{
+  KCTX(ctx);
+  if (!dirs3 || !normal3 || !pdf || !cell) return fail(ctx, FH_E_INVALID, "fh_kat_env_pdf: null argument");
+  if (const int rc = kat_env_table(ctx, "fh_kat_env_pdf")) return rc;
+  DeviceBuffer<float> a, b, p;
+  DeviceBuffer<uint32_t> c;
+  FH_HIP(up(a, dirs3, 3ull * n)); FH_HIP(up(b, normal3, 3ull * n)); FH_HIP(up(p, nullptr, n)); FH_HIP(up(c, nullptr, n));
+  hipLaunchKernelGGL(k_env_pdf, dim3(blocks(n)), dim3(256), 0, ctx->stream, env_table_dev(ctx), n, a.get(), b.get(), p.get(), c.get());
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(down(p, pdf)); FH_HIP(down(c, cell));
+  return FH_OK;
+}
+int fh_kat_env_radiance(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3)
+{
+  KCTX(ctx);
+  if (!dirs3 || !out3) return fail(ctx, FH_E_INVALID, "fh_kat_env_radiance: null argument");
+  DeviceBuffer<float> a, o;
+  FH_HIP(up(a, dirs3, 3ull * n)); FH_HIP(up(o, nullptr, 3ull * n));
+  hipLaunchKernelGGL(k_env_radiance, dim3(blocks(n)), dim3(256), 0, ctx->stream, env_frame(ctx), n, a.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
   FH_HIP(down(o, out3));
   return FH_OK;

@@ -35,6 +35,7 @@
 
 #include "context.h"
 #include "fh_bsdf.h"
+#include "fh_envmap.h"
 #include "fh_tonemap.h"
 #include "fh_trace.h"
 #include "render_plan_host.h"
@@ -105,22 +106,6 @@ FH_D void stage_sky(FrameDev& fr, HosekSky& lds_sky)
   if (!fr.has_hosek) return;
   if (threadIdx.x < sizeof(HosekSky) / 4u) reinterpret_cast<float*>(&lds_sky)[threadIdx.x] = reinterpret_cast<const float*>(fr.hosek)[threadIdx.x];
   fr.hosek = &lds_sky;
-}
-
-// environment seen along d: IBL, else Hosek sky, else the constant background (pt.cu:511-517, :536-542)
-// (ROLLED_SKY: fh_sky.h, hosek_radiance_form)
-template <bool ROLLED_SKY = false>
-FH_D f3 env_radiance(const FrameDev& fr, f3 d)
-{
-  if (fr.has_ibl) {  // fetch_ibl (pt.cu:344-350) with cartesian_to_spherical (math.cu:111-118)
-    const float theta = fhe_acos(clampf(d.y, -1.0f, 1.0f));
-    float phi = fhe_atan2(d.z, d.x);
-    if (phi < 0) phi += 2.0f * kPi;
-    float o[4];
-    fht_tex2d(&fr.ibl, nullptr, phi / (2.0f * kPi), theta / kPi, o);
-    return fr.sky_intensity * mk3(o[0], o[1], o[2]);
-  }
-  return fr.has_hosek ? hosek_radiance_form<ROLLED_SKY>(*fr.hosek, fr.sun_dir, fr.sky_intensity, d) : fr.bg;
 }
 
 // sample n_spp of pixel (px, py): CMJ slots 0 / 1 -> thin-lens camera ray (pt.cu:433-454, camera.cu:24-53) and the Russian roulette of bounce 0, which has probability 1 but
@@ -966,9 +951,11 @@ struct PoolSink {      // memory sink (k_shade): path slot p of the pool
   }
 };
 
-template <uint32_t LOBES, class Sink>
+// ENV (fh_set_env_sampling): the sky ray is drawn from the mixture of fh_envmap.h and the two light-ray weights that stand against it use that density; `env` is read
+// by these variants only, and nothing else of the hit differs
+template <uint32_t LOBES, bool ENV = false, class Sink>
 FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& rows, const BounceSlots& bs, uint32_t depth, float4 hit, f3 rd, f3 T, f3 L, uint32_t image_idx, uint32_t n_spp,
-                    Sink& out, bool first = true)
+                    Sink& out, bool first = true, const EnvTable* env = nullptr)
 {
   const uint32_t has_lights = bs.has_lights;
   const uint32_t prim = __float_as_uint(hit.w);
@@ -1040,7 +1027,27 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
     out.secondary(SEC_DIR, so, 1e9f - 0.001f, sd, contributes(c), c);
   }
   // sky / constant background (pt.cu:817-857)
-  {
+  if constexpr (ENV) {
+    float pdf;
+    uint32_t cell;
+    const f3 sd = env_sample(*env, cmj_draw(n_spp, image_idx, bs.slot_sky, fr.seed_hash), tangent, ns, bitangent, pdf, cell);
+    const f3 wi = to_local(sd, tangent, ns, bitangent);
+    // A direction at or below the shading horizon adds nothing.  The table draws over the whole sphere, and the BSDF's evaluation is not meant for down there: today's
+    // draw never asks it, and what it answers is the upper side's value with |cos| (rho / pi for the diffuse lobe), so a surface that faces the sun with its geometry
+    // and not with its shading normal would be lit through its back.  (The ray starts on the outer side whatever its direction, so below the geometric horizon the
+    // surface itself stops it, as it does a transmissive floor's today.)
+    // Nor does a weight that is not finite.  Every hit on the back side of an opaque surface has one: all lobe weights are 0 there, the lobe pmf is 0 / 0 and eval_pdf
+    // NaN.  regularize_weight would make it 1, and the expectation of 1 * L(d) is the integral of p * L -- a glow under the cosine draw, the sun's radiance times its
+    // share of the table under this one (measured on the textured interior, whose curtains and cards are seen from both sides: a frame mean of 42 against 0.08).
+    f3 c = mk3(0.0f);
+    if (wi.y > 0.0f) {
+      const f3 f = bsdf.eval(wo, wi);
+      const float w = pdf / (pdf + bsdf.eval_pdf(wo, wi));
+      const f3 weight = T * w * f * abs_cos(wi) / pdf;
+      if (!bad3(weight)) c = clamp01(weight) * env_radiance(fr, sd);
+    }
+    out.secondary(SEC_SKY, so, 1e9f - 0.001f, sd, contributes(c), c);
+  } else {
     const f3 wi = cosine_hemisphere(cmj_draw(n_spp, image_idx, bs.slot_sky, fr.seed_hash));
     const f3 sd = to_world(wi, tangent, ns, bitangent);
     const f3 f = bsdf.eval(wo, wi);
@@ -1088,11 +1095,19 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
     const f3 lo = offset_origin(x, transmitted ? -ng : ng);
     if (has_lights) {
       // the MIS weight needs the hit (emitter or sky): finished once the closest hit is known
-      out.light_pending(T, abs_cos(wi), f, pdf);
+      if constexpr (ENV) {
+        // resolve_light_ray takes pdf_light = cos' / pi on a miss and T * w * f * cos' / pdf in both branches: with cos' = pi * p(ld) the miss density is the
+        // mixture's p(ld), and f' = f * |cos| / cos' keeps the product T * w * f * |cos| / pdf where the ray escapes and where it finds an emitter
+        const float cosp = kPi * env_pdf(*env, env_dir(ld), env_dir(ns), nullptr);
+        out.light_pending(T, cosp, f * (abs_cos(wi) / cosp), pdf);
+      } else {
+        out.light_pending(T, abs_cos(wi), f, pdf);
+      }
       out.secondary(SEC_LIGHT, lo, 1e9f, ld, true, mk3(0.0f));
     } else {
-      // no emitters: the ray contributes only if it escapes, with the sky's cosine pdf (pt.cu:917-919)
-      const float pdf_light = abs_cos(wi) / kPi;
+      // no emitters: the ray contributes only if it escapes, with the sky's cosine pdf (pt.cu:917-919), or the mixture's
+      float pdf_light = abs_cos(wi) / kPi;
+      if constexpr (ENV) pdf_light = env_pdf(*env, env_dir(ld), env_dir(ns), nullptr);
       const float w = pdf / (pdf + pdf_light);
       const f3 c = clamp01(T * w * f * abs_cos(wi) / pdf) * env_radiance(fr, ld);
       out.secondary(SEC_LIGHT, lo, 1e9f, ld, contributes(c), c);
@@ -1198,71 +1213,23 @@ __global__ void __launch_bounds__(kSortBlock) k_cell_scatter(const uint32_t* cou
   }
 }
 
+// k_shade and k_shade_env, its twin that takes the environment table (fh_set_env_sampling), share ONE body text, render_shade_body.inc, included into both: a device
+// function called by both was tried first and changed the plain kernels' instruction streams (registers allocated differently in 15 of them), and the plain kernels
+// must stay what they are.  The body reads ENV and env.
 template <uint32_t LOBES, int BLOCKS = FH_SHADE_BLOCKS>
 __global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : BLOCKS)) k_shade(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth)
 {
-  pass_priority();
-  // (the grid is sized for every path of the pass; the blocks beyond this class's queue leave before they stage anything)
-  if (blockIdx.x * blockDim.x >= pool.counters[depth * kCounterStride + CNT_CLS + cls]) return;
-  __shared__ SobolRows<4> rows;
-  // the shade kernels run one wave per SIMD (512 registers per lane), so nothing hides a dependent global load: the small tables every
-  // hit reads -- the two albedo LUTs and, when there are few of them, the material records -- are staged in LDS once per workgroup
-  __shared__ float s_lut[kLutReflFloats + kLutSheenFloats];
-  __shared__ MaterialDev s_mat[kMatLds];
-  for (uint32_t i = threadIdx.x; i < kLutReflFloats; i += blockDim.x) s_lut[i] = fr.lut.reflection[i];
-  for (uint32_t i = threadIdx.x; i < kLutSheenFloats; i += blockDim.x) s_lut[kLutReflFloats + i] = fr.lut.sheen[i];
-  fr.lut.reflection = s_lut;
-  fr.lut.sheen = s_lut + kLutReflFloats;
-  if (sc.n_materials <= kMatLds) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(sc.materials);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(s_mat);
-    for (uint32_t i = threadIdx.x; i < sc.n_materials * (uint32_t)(sizeof(MaterialDev) / 4); i += blockDim.x) dst[i] = src[i];
-    sc.materials = s_mat;
-  }
-  __shared__ float s_srgb[256];  // the sRGB decode table: twelve lookups per fetch of a colour texture
-  if (sc.n_textures) {
-    s_srgb[threadIdx.x] = sc.srgb_lut[threadIdx.x];
-    sc.srgb_lut = s_srgb;
-  }
-  __shared__ HosekSky s_sky;
-  stage_sky(fr, s_sky);
-  BounceSlots bs;
-  bs.set(fr, sc.n_lights, depth);
-  bs.load_rows(rows, fr.sobol_bytes);  // (ends with the workgroup barrier that also publishes the tables above)
-
-  uint32_t* cnt = pool.counters + depth * kCounterStride;
-  uint32_t* cnt_next = cnt + kCounterStride;
-  const uint32_t count = cnt[CNT_CLS + cls];
-  const uint32_t* q = pool.q_cls + (size_t)cls * pool.capacity;
-  const uint32_t qnext = (depth + 1u) & 1u;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  __shared__ uint32_t s_reserve[2][10];  // (two areas, used alternately: block_queue_reserve)
-  uint32_t iter = 0;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < count; base += stride) {
-    const uint32_t i = base + threadIdx.x;
-    const bool valid = i < count;
-    bool shaded = false, cont = false;
-    uint32_t p = 0, cell = 0;
-    if (valid) {
-      p = q[i];
-      const float4 hit = pool.hit[p];
-      PoolSink o(pool, p, hit.x);
-      const bool first = depth != 0 || (pool.flags[p] & 4u) == 0u;
-      const f3 L = depth == 0u ? mk3(pool.rad[p]) : mk3(0.0f);  // the radiance so far only enters at a directly visible emitter (first hit): later bounces skip the load
-      shade_hit<LOBES>(sc, fr, rows, bs, depth, hit, mk3(pool.ray_d[p]), mk3(pool.thr[p]), L, pool.pixel[p], pool.nspp[p], o, first);
-      shaded = o.shaded;
-      cont = o.cont;
-      if (shaded || cont) cell = cell_of(fr, o.origin);
-    }
-    // queue positions of both appends: one returning atomic per workgroup and queue (fh_device.h: block_queue_reserve)
-    uint32_t* const counters2[2] = {&cnt[CNT_SEC], &cnt_next[CNT_RAD]};
-    const bool act[2] = {shaded, cont};
-    uint32_t pos[2];
-    block_queue_reserve<2>(counters2, act, pos, s_reserve[iter & 1u]);
-    ++iter;
-    if (shaded) { pool.q_sec[pos[0]] = p; pool.key_sec[pos[0]] = (uint16_t)cell; }
-    if (cont) { pool.q_rad[qnext][pos[1]] = p; pool.key_rad[pos[1]] = (uint16_t)cell; }
-  }
+  constexpr bool ENV = false;
+  const EnvTable* const env = nullptr;
+#include "render_shade_body.inc"
+}
+// compiled for the lobe sets of the fused tail (TailLobes), two workgroups per CU
+template <uint32_t LOBES>
+__global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : FH_SHADE_BLOCKS)) k_shade_env(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth, EnvTable env_table)
+{
+  constexpr bool ENV = true;
+  const EnvTable* const env = &env_table;
+#include "render_shade_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1609,135 +1576,20 @@ __device__ __attribute__((noinline)) bool tail_trace_lane(const SceneDev& sc, ui
 }
 struct TailRay { bool has = false; bool any = true; f3 o = mk3(0.0f), d = mk3(0.0f, 0.0f, 1.0f); float tmax = 0.0f; HitRec h = HitRec{0.0f, 0.0f, 0.0f, 0xffffffffu}; bool hit = false; };  // (no indeterminate field: r6-13)
 
+// (k_tail and k_tail_env share render_tail_body.inc the way the shade kernels share theirs)
 template <uint32_t LOBES>
 __global__ void __launch_bounds__(kBlock, LOBES == L_ALL ? 1 : 2) k_tail(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t first_depth, uint32_t coop_flush)
 {
-  pass_priority();
-  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // traversal stack of every lane ([entry][thread], as in the streaming kernels): a private array lands in scratch
-  __shared__ __attribute__((aligned(16))) unsigned char lds_coop[(kBlock / 64) * kCoopLdsBytesPerWave];
-  __shared__ float4 s_in[kBlock / 64][2][64];  // one round of packed rays of a wave: (origin, tmax), (direction, stops at its first hit)
-  __shared__ float4 s_out[kBlock / 64][64];    // and their hits: t, u, v, face id bits
-  if (blockIdx.x * blockDim.x >= pool.counters[first_depth * kCounterStride + CNT_RAD]) return;  // (the grid is sized for the pass, the survivors are few: most blocks have nothing to do, and leave before the tables are staged)
-  const CoopLds cl = coop_lds(lds_coop, threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const bool coop = sc.use_bvh8 && coop_flush != 0u;
-  // all rays of the wave (called by its 64 lanes together)
-  auto trace_all = [&](TailRay (&rays)[kTailRays]) {
-    if (!coop) {  // one ray per lane, per-lane loops: tiny scenes (binary tree) and FH_COOP=0 (an out-of-line call per ray: five inlined copies of every traversal would be most of the kernel)
-      HitRec t;  // (only this one has its address taken: the rays themselves stay in registers)
-      if (rays[0].has) { rays[0].hit = tail_trace_lane(sc, lds_stack, rays[0].any, rays[0].o, rays[0].d, rays[0].tmax, t); rays[0].h = t; }
-      if (rays[1].has) { rays[1].hit = tail_trace_lane(sc, lds_stack, rays[1].any, rays[1].o, rays[1].d, rays[1].tmax, t); rays[1].h = t; }
-      if (rays[2].has) { rays[2].hit = tail_trace_lane(sc, lds_stack, rays[2].any, rays[2].o, rays[2].d, rays[2].tmax, t); rays[2].h = t; }
-      if (rays[3].has) { rays[3].hit = tail_trace_lane(sc, lds_stack, rays[3].any, rays[3].o, rays[3].d, rays[3].tmax, t); rays[3].h = t; }
-      if (rays[4].has) { rays[4].hit = tail_trace_lane(sc, lds_stack, rays[4].any, rays[4].o, rays[4].d, rays[4].tmax, t); rays[4].h = t; }
-      return;
-    }
-    uint32_t idx[kTailRays], total = 0;  // position of this lane's ray of kind k among the wave's rays; total: wave-uniform
-#pragma unroll
-    for (uint32_t k = 0; k < kTailRays; ++k) {
-      const unsigned long long m = __ballot(rays[k].has);
-      idx[k] = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      total += (uint32_t)__popcll(m);
-    }
-    for (uint32_t lo = 0; lo < total; lo += 64u) {
-#pragma unroll
-      for (uint32_t k = 0; k < kTailRays; ++k)
-        if (rays[k].has && idx[k] - lo < 64u) {
-          s_in[wave][0][idx[k] - lo] = mk4(rays[k].o, rays[k].tmax);
-          s_in[wave][1][idx[k] - lo] = mk4(rays[k].d, rays[k].any ? 1.0f : 0.0f);
-        }
-      const bool valid = lo + lane < total;
-      const float4 a = valid ? s_in[wave][0][lane] : make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = valid ? s_in[wave][1][lane] : make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-      HitRec h;
-      uint32_t na = 0, nb = 0;
-      if (sc.has_alpha) traverse_bvh8_coop_mode<2, false, true, true>(sc.bvh8, valid, b.w != 0.0f, mk3(a), mk3(b), a.w, h, na, nb, nullptr, cl, coop_flush, lds_stack, (int)sc.bvh8.depth, &sc);
-      else traverse_bvh8_coop_mode<2, false, true, false>(sc.bvh8, valid, b.w != 0.0f, mk3(a), mk3(b), a.w, h, na, nb, nullptr, cl, coop_flush, lds_stack, (int)sc.bvh8.depth, &sc);
-      if (valid) s_out[wave][lane] = make_float4(h.t, h.u, h.v, __uint_as_float(h.prim));
-#pragma unroll
-      for (uint32_t k = 0; k < kTailRays; ++k)
-        if (rays[k].has && idx[k] - lo < 64u) {
-          const float4 r = s_out[wave][idx[k] - lo];
-          rays[k].h.t = r.x; rays[k].h.u = r.y; rays[k].h.v = r.z; rays[k].h.prim = __float_as_uint(r.w);
-          rays[k].hit = rays[k].h.prim != 0xffffffffu;
-        }
-    }
-  };
-  __shared__ SobolRows<4> rows;
-  __shared__ float s_lut[kLutReflFloats + kLutSheenFloats];  // as in k_shade: small tables every hit reads live in LDS
-  __shared__ MaterialDev s_mat[kMatLds];
-  for (uint32_t i = threadIdx.x; i < kLutReflFloats; i += blockDim.x) s_lut[i] = fr.lut.reflection[i];
-  for (uint32_t i = threadIdx.x; i < kLutSheenFloats; i += blockDim.x) s_lut[kLutReflFloats + i] = fr.lut.sheen[i];
-  fr.lut.reflection = s_lut;
-  fr.lut.sheen = s_lut + kLutReflFloats;
-  if (sc.n_materials <= kMatLds) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(sc.materials);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(s_mat);
-    for (uint32_t i = threadIdx.x; i < sc.n_materials * (uint32_t)(sizeof(MaterialDev) / 4); i += blockDim.x) dst[i] = src[i];
-    sc.materials = s_mat;
-  }
-  __shared__ HosekSky s_sky;
-  stage_sky(fr, s_sky);
-  __syncthreads();
-  const uint32_t count = pool.counters[first_depth * kCounterStride + CNT_RAD];
-  const uint32_t* q = pool.q_rad[first_depth & 1u];
-  const bool has_lights = sc.n_lights > 0;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < count; base += stride) {  // (block-uniform bound: the bounce loop holds workgroup barriers)
-    const uint32_t i = base + threadIdx.x;
-    bool alive = i < count;
-    uint32_t p = 0, image_idx = 0, n_spp = 0;
-    f3 ro = mk3(0.0f), rd = mk3(0.0f, 0.0f, 1.0f), T = mk3(0.0f), L = mk3(0.0f);
-    if (alive) {
-      p = q[i];
-      const float4 o = pool.ray_o[p];
-      ro = mk3(o); rd = mk3(pool.ray_d[p]); T = mk3(pool.thr[p]); L = mk3(pool.rad[p]);
-      image_idx = pool.pixel[p]; n_spp = pool.nspp[p];
-    }
-    // the closest hit of the first bounce; every later one comes back with the rays of the bounce before it
-    HitRec h;
-    bool hit = false;
-    {
-      TailRay rays[kTailRays];
-      rays[SEC_COUNT].has = alive; rays[SEC_COUNT].any = false; rays[SEC_COUNT].o = ro; rays[SEC_COUNT].d = rd; rays[SEC_COUNT].tmax = 1e9f;
-      trace_all(rays);
-      h = rays[SEC_COUNT].h; hit = rays[SEC_COUNT].hit;
-    }
-    for (uint32_t depth = first_depth; depth < fr.max_depth; ++depth) {
-      BounceSlots bs;
-      bs.set(fr, sc.n_lights, depth);
-      __syncthreads();  // rows of the previous bounce are no longer read
-      bs.load_rows(rows, fr.sobol_bytes);
-      if (__ballot(alive) == 0ull) continue;  // (wave-uniform; the barriers above are still met)
-      ShadeOut o;
-      if (alive) {
-        if (!hit) alive = false;  // pt.cu:504-523 with firsthit == false: nothing added
-        else shade_hit<LOBES>(sc, fr, rows, bs, depth, make_float4(h.t, h.u, h.v, __uint_as_float(h.prim)), rd, T, L, image_idx, n_spp, o);
-      }
-      TailRay rays[kTailRays];
-#pragma unroll
-      for (uint32_t slot = SEC_DIR; slot <= SEC_LIGHT; ++slot) {
-        if (slot == SEC_DIR && !fr.has_dir) continue;
-        if (slot == SEC_AREA && !has_lights) continue;
-        rays[slot].has = alive && o.sec[slot].active;
-        rays[slot].any = !(slot == SEC_LIGHT && has_lights);
-        rays[slot].o = o.sec[slot].o; rays[slot].d = o.sec[slot].d; rays[slot].tmax = o.sec[slot].tmax;
-      }
-      rays[SEC_COUNT].has = alive && o.cont; rays[SEC_COUNT].any = false; rays[SEC_COUNT].o = o.next_o; rays[SEC_COUNT].d = o.next_d; rays[SEC_COUNT].tmax = 1e9f;
-      trace_all(rays);
-      // secondary rays in the reference's order
-#pragma unroll
-      for (uint32_t slot = SEC_DIR; slot <= SEC_LIGHT; ++slot) {
-        if (!rays[slot].has) continue;
-        if (slot == SEC_LIGHT && has_lights) L += resolve_light_ray(sc, fr, o.lp_T, o.lp_cos, o.lp_f, o.lp_pdf, o.sec[slot].o, o.sec[slot].d, rays[slot].hit, rays[slot].h);
-        else if (!rays[slot].hit) L += o.sec[slot].c;
-      }
-      if (alive) {
-        if (o.cont) { rd = o.next_d; T = o.T; h = rays[SEC_COUNT].h; hit = rays[SEC_COUNT].hit; }
-        else alive = false;
-      }
-    }
-    if (i < count) pool.rad[p] = mk4(L, 0.0f);
-  }
+  constexpr bool ENV = false;
+  const EnvTable* const env = nullptr;
+#include "render_tail_body.inc"
+}
+template <uint32_t LOBES>
+__global__ void __launch_bounds__(kBlock, LOBES == L_ALL ? 1 : 2) k_tail_env(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t first_depth, uint32_t coop_flush, EnvTable env_table)
+{
+  constexpr bool ENV = true;
+  const EnvTable* const env = &env_table;
+#include "render_tail_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1873,8 +1725,12 @@ void with_compiled_lobes(uint32_t lobes, LobeSet<V, Rest...>, F&& f)
   else with_compiled_lobes(lobes, LobeSet<Rest...>{}, f);
 }
 
-void dispatch_shade(hipStream_t st, uint32_t grid, uint32_t lobes, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three)
+void dispatch_shade(hipStream_t st, uint32_t grid, uint32_t lobes, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three, const EnvTable* env)
 {
+  if (env) {
+    with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_shade_env<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, *env); });
+    return;
+  }
   with_compiled_lobes(lobes, ShadeLobes{}, [&](auto V) { launch_shade<decltype(V)::value>(st, grid, sc, fr, pool, cls, depth, three); });
 }
 
@@ -2118,6 +1974,10 @@ int configure_traversal_lds(fh_ctx* ctx, uint32_t stack_bytes)
   set((const void*)k_tail<L_METAL | L_SPEC | L_DIFF>);
   set((const void*)k_tail<L_COAT | L_METAL | L_SPEC | L_DIFF>);
   set((const void*)k_tail<L_ALL>);
+  set((const void*)k_tail_env<L_DIFF>);
+  set((const void*)k_tail_env<L_METAL | L_SPEC | L_DIFF>);
+  set((const void*)k_tail_env<L_COAT | L_METAL | L_SPEC | L_DIFF>);
+  set((const void*)k_tail_env<L_ALL>);
   if (err != hipSuccess) return fail(ctx, FH_E_HIP, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(err));
   ctx->lds_configured_bytes = stack_bytes;
   ctx->lds_static_max = max_static;
@@ -2535,6 +2395,8 @@ struct Call {
   uint32_t max_depth;
   bool adaptive, quirk, count;
   StreamPlan plan;
+  EnvTable env;  // fh_set_env_sampling; env_on: the shade kernels and the fused tail of this call are the ENV variants
+  bool env_on;
 };
 
 // one pass: its pool slot and streams, and what was chosen for it
@@ -2672,7 +2534,8 @@ void launch_tail(const Call& c, const Pass& p, const PoolDev& pd, uint32_t n_pat
   for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) lobes |= ctx->class_lobes[cls];
   const dim3 tg(grid_for(n_paths / 16 + 1)), tb(kBlock);
   const uint32_t tl = p.sc.use_bvh8 ? c.plan.stack_bytes : 0u, tf = c.plan.coop ? p.coop_flush : 0u;
-  with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_tail<decltype(V)::value>, tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf); });
+  if (c.env_on) with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_tail_env<decltype(V)::value>, tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf, c.env); });
+  else with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_tail<decltype(V)::value>, tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf); });
   ctx->stats.n_tail_launches++;
 }
 
@@ -2781,7 +2644,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
     if (p.overlap && depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (depth - 1u) + 1u], 0));  // the secondary launch of the bounce before reads what the shade kernels and the sorts below overwrite
     {
       Span sp(ctx, st, 2);
-      for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) dispatch_shade(st, p.grid, ctx->class_lobes[cls], p.sc, c.fr, pd, cls, depth, c.plan.shade_three);
+      for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) dispatch_shade(st, p.grid, ctx->class_lobes[cls], p.sc, c.fr, pd, cls, depth, c.plan.shade_three, c.env_on ? &c.env : nullptr);
       if (depth == 0) hipLaunchKernelGGL(k_miss_primary, dim3(p.grid), dim3(kBlock), 0, st, c.fr, pd);
       ctx->stats.n_shade_launches += ctx->n_classes;
     }
@@ -2859,7 +2722,8 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   const bool clocks = (ctx->flags & FH_FLAG_TIME_KERNELS) != 0;
   Call c{ctx, frame_dev(ctx, cam, bg, seed, max_depth), layers_dev(ctx, layers), SceneDev{},
          TraceCounters{tc, tc + 1, tc + 2, tc + 6, tc + 7, tc + 10, clocks ? tc + 27 : nullptr}, TraceCounters{tc + 3, tc + 4, tc + 5, tc + 8, tc + 9, tc + 18, clocks ? tc + 29 : nullptr},
-         max_depth, adaptive, quirk, count, StreamPlan{}};
+         max_depth, adaptive, quirk, count, StreamPlan{}, env_table_dev(ctx), ctx->env_sampling != 0};
+  if (c.env_on) { const int rc = env_table_ensure(ctx); if (rc) return rc; }  // (a stale table is rebuilt on the main stream, ahead of everything this call queues)
   PixelLists base;  // the pixels of the call
   { const int rc = choose_pixels(ctx, cam, c.fr, n_samples, quirk, base); if (rc) return rc; }
   const uint32_t target = ctx->pool_target > ctx->n_owned ? ctx->pool_target : ctx->n_owned;

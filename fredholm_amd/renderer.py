@@ -514,6 +514,24 @@ class Renderer:
         self._ck(N.lib().fh_post_process(self._ctx, C.c_void_p(beauty_in_ptr), C.c_void_p(high_ptr), C.c_void_p(temp_ptr), int(width), int(height), C.byref(pp), C.c_void_p(beauty_out_ptr)),
                  "fh_post_process")
 
+    # -- importance sampling of the environment (fh_set_env_sampling)
+    def set_env_sampling(self, cosine_fraction=N.ENV_COSINE_FRACTION_DEFAULT):
+        """fh_set_env_sampling: while on, the sky next-event ray of every shaded hit is drawn from a mixture of the cosine lobe (share `cosine_fraction`, in [0, 1)) and a
+        512 x 256 table of the environment's luminance (image, Hosek dome or constant), and the BSDF-sampled light ray is weighed against that density.  The table is
+        rebuilt by the next render after the environment changes.  Nothing else of a frame changes; off (the default) keeps every bit"""
+        p = N.EnvSamplingParamsC(float(cosine_fraction))
+        self._ck(N.lib().fh_set_env_sampling(self._ctx, C.byref(p)), "fh_set_env_sampling")
+
+    def clear_env_sampling(self):
+        """off: the cosine-distributed sky ray of the reference"""
+        self._ck(N.lib().fh_set_env_sampling(self._ctx, None), "fh_set_env_sampling")
+
+    def get_env_sampling(self):
+        """(on, cosine_fraction): the switch and the fraction last set (the default before any)"""
+        on, p = C.c_int(0), N.EnvSamplingParamsC()
+        self._ck(N.lib().fh_get_env_sampling(self._ctx, C.byref(on), C.byref(p)), "fh_get_env_sampling")
+        return bool(on.value), float(p.cosine_fraction)
+
     # -- auto-exposure of the post chain (fh_set_auto_exposure)
     def set_auto_exposure(self, key=0.18, compensation_ev=0.0, min_ev=-16.0, max_ev=16.0, low=0.10, high=0.90, speed_up=3.0, speed_down=1.0, frame_time=1.0 / 30.0,
                           log2_lo=-16.0, log2_hi=16.0, bloom_relative=False):

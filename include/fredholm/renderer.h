@@ -5,6 +5,7 @@
 // (app/controller.cpp:60-68, app/rtcamp8.cpp:75-146) compiles unchanged.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <filesystem>
 #include <stdexcept>
 
@@ -28,7 +29,18 @@ namespace fredholm
 class Renderer
 {
  public:
-  explicit Renderer(const OptixDeviceContext& context) : m_ctx(context) {}
+  // FH_ENV_SAMPLING gives an application that is not edited importance sampling of the environment (fh_set_env_sampling): unset or 0: off; 1: on with the
+  // library's cosine fraction; any other number: on with that fraction (one the library refuses throws here).  set_env_sampling / clear_env_sampling win.
+  explicit Renderer(const OptixDeviceContext& context) : m_ctx(context)
+  {
+    if (const char* e = std::getenv("FH_ENV_SAMPLING")) {
+      char* end = nullptr;
+      const float v = std::strtof(e, &end);
+      if (end == e || *end != '\0') throw std::runtime_error("FH_ENV_SAMPLING: not a number");
+      if (v == 1.0f) set_env_sampling();
+      else if (v != 0.0f) set_env_sampling(v);
+    }
+  }
   ~Renderer() noexcept(false) {}
 
   // OptiX plumbing of the reference (renderer.h:124-352): nothing to build, the kernels live in the library
@@ -67,6 +79,14 @@ class Renderer
   void clear_ibl() { cwl::check(m_ctx, fh_clear_ibl(m_ctx), "fh_clear_ibl"); }  // renderer.h:583-586
   void load_arhosek_sky(float turbidity, float albedo) { cwl::check(m_ctx, fh_load_arhosek_sky(m_ctx, turbidity, albedo), "fh_load_arhosek_sky"); }
   void clear_arhosek_sky() { cwl::check(m_ctx, fh_clear_arhosek_sky(m_ctx), "fh_clear_arhosek_sky"); }
+  // importance sampling of the environment for the sky rays (no counterpart in the reference, pt.cu:796-815); without an argument: the library's cosine fraction
+  void set_env_sampling() { set_env_sampling(FH_ENV_COSINE_FRACTION_DEFAULT); }
+  void set_env_sampling(float cosine_fraction)
+  {
+    const fh_env_sampling_params p = {cosine_fraction};
+    cwl::check(m_ctx, fh_set_env_sampling(m_ctx, &p), "fh_set_env_sampling");
+  }
+  void clear_env_sampling() { cwl::check(m_ctx, fh_set_env_sampling(m_ctx, nullptr), "fh_set_env_sampling"); }
 
   void set_time(float time)  // renderer.h:614-640: animation update, transform re-upload, acceleration-structure rebuild
   {

@@ -580,6 +580,63 @@ int fh_get_auto_exposure_state(fh_ctx* ctx, fh_auto_exposure_state* state);
 /* synchronising: the histogram of the last metering call (all zero before any); hist[256] = unmetered pixels.  FH_E_INVALID while the switch is off */
 int fh_get_luminance_histogram(fh_ctx* ctx, uint32_t hist[257]);
 
+/* -- importance sampling of the environment for sky lighting (opt-in, default off; with it off every render keeps its bits, its launches and its kernels).
+ * The sky next-event ray of a shaded hit is drawn cosine-distributed round the shading normal whatever the environment is (pt.cu:796-815: "TODO: implement IBL
+ * importance sampling").  While this switch is on it is drawn from a mixture of that cosine lobe (fraction cosine_fraction = B) and a table of the environment's
+ * luminance, and the two BSDF-sampled light-ray weights that stand against it use the same density.  Nothing else of a frame changes: the draw is the 2-D draw of the
+ * same sampler slot, and every other slot, dimension, kernel and layer is as it is with the switch off.
+ * All of it is fp32 without contraction, / and sqrt correctly rounded, sums in the order written; fhe_sincos, fhe_acos, fhe_atan2: include/fh_elementary.h;
+ * PI = 3.14159265358979323846f, TWO_PI = 2.0f * PI; fmax / fmin are C's (a NaN operand loses).
+ *   The table: W x H = 512 x 256 cells over (phi, theta), cell (i, j) covering u = phi / TWO_PI in [i, i + 1) / 512 and v = theta / PI in [j, j + 1) / 256 --
+ *     the mapping of the environment look-up: theta = fhe_acos(clamp(d.y, -1, 1)), phi = fhe_atan2(d.z, d.x), + TWO_PI when negative.
+ *   Sub-samples: K = clamp(ceil(ibl_width / 512), 2, 16) with an image loaded, else 2.  For b = 0 .. K - 1 (outer), a = 0 .. K - 1 (inner):
+ *     u = ((float)i + ((float)a + 0.5f) / (float)K) / 512,  v = ((float)j + ((float)b + 0.5f) / (float)K) / 256;
+ *     (st, ct) = fhe_sincos(v * PI), (sp, cp) = fhe_sincos(u * TWO_PI), d = (st * cp, ct, st * sp);
+ *     (r, g, b) = what the context shows along d at sky intensity 1: the image (its bilinear fetch at (phi / TWO_PI, theta / PI) of d), else the Hosek dome;
+ *     l = (finite(r) * 0.2126729f + finite(g) * 0.7151522f) + finite(b) * 0.0721750f, finite(x) = 0 for a NaN or |x| > 3e38, else x; with neither image nor dome
+ *       l = 1: a constant background weighs every direction alike, whatever its colour, so neither fh_set_sky_intensity nor the background changes the table;
+ *     S += fmin(fmax(l, 0), 3e38) * fmax(st, 0)   (serially).   w = fmin(S / (float)(K * K), 3e38).
+ *   Quantisation: w_max = the largest w of the table;  q = max(1, (uint32)((w / w_max) * 1048576.0f)), and q = 1 for every cell when w_max == 0.
+ *     So a black image, NaN or infinite texels and texels below 2^-20 of the maximum all leave their cells the weight 1, never 0: every direction keeps a positive
+ *     probability.  Row sums R_j = sum_i q (32 bits, at most 2^29), total T = sum_j R_j (64 bits): exact, independent of the order of summation.
+ *   Stored: q;  cdf_row[j][i] = (float)((double)(q[j][0] + .. + q[j][i - 1]) / (double)R_j), i = 0 .. 512 (first 0, last 1);
+ *     cdf_m[j] = (float)((double)(R_0 + .. + R_(j - 1)) / (double)T), j = 0 .. 256;  cell_p[j][i] = (float)((double)q[j][i] / (double)T).
+ *   Search: the interval of u in a CDF of n + 1 entries is lo after  lo = 0, hi = n; while (hi - lo > 1) { mid = (lo + hi) >> 1; if (cdf[mid] <= u) lo = mid; else hi = mid; }
+ *     and the position inside it is r = fmin((u - cdf[lo]) / (cdf[lo + 1] - cdf[lo]), 0.99999994f).
+ *   The draw, from the sky slot's (ux, uy):  ux < B: the cosine branch with ux := ux / B: today's cosine_hemisphere(ux, uy) round the shading normal;
+ *     otherwise ux := fmin((ux - B) / (1 - B), 0.99999994f): row j by cdf_m from ux, column i by cdf_row[j] from uy,
+ *     v = ((float)j + r_j) / 256, u = ((float)i + r_i) / 512, d as for a sub-sample.  The drawn cell is (i, j).
+ *   The density of a world direction d in cell c, for a shading normal n:
+ *     st = fmax(sqrt(d.x * d.x + d.z * d.z), 2^-20),  cos = (d.x * n.x + d.y * n.y) + d.z * n.z,
+ *     p = (1 - B) * ((cell_p[c] * 131072.0f) / ((2.0f * (PI * PI)) * st)) + B * (fmax(cos, 0) / PI).
+ *     The table branch reports p with c = the drawn cell; the cosine branch and the BSDF-sampled rays take c from d: i = (int)((phi / TWO_PI) * 512), j = (int)((theta / PI)
+ *     * 256), each held to its range.  This is the true mixture density: the cosine term lives on the upper hemisphere only (the reference's |cos| / pi on both is
+ *     not carried into this mode).  A direction drawn from the table maps back to a neighbouring cell in well under 1e-3 of the draws (the position inside a cell is
+ *     continuous, and u and v round); the reported density is then the drawn cell's.  Below 2^-24 a probability cannot be hit by a 24-bit draw: a row or cell whose
+ *     CDF interval rounds to nothing is never drawn although its density is positive -- the same granularity every fp32 sampler here has.
+ *   The three sites of the closest-hit program (pt.cu:817-857, :893-925), T the throughput, f the BSDF value, pdf_b the BSDF's density:
+ *     sky ray: (d, p) from the draw; w = p / (p + pdf_b(d)); contribution clamp01(T * w * f * |cos| / p) * environment(d) -- and nothing when d lies at or below the
+ *       shading horizon (d in the shading frame has y <= 0): the BSDF evaluation is not meant for there (today's draw never asks it; it answers the upper side's value
+ *       with |cos|, which would light a surface through its back), and the ray leaves from the outer side of the surface, which stops it below the geometric horizon anyway.  Nor when T * w * f * |cos| / p has a
+ *       NaN or infinite channel -- every hit on the back side of an opaque surface has one (all lobe weights 0, the lobe pmf 0 / 0, the BSDF's density NaN) --: clamp01
+ *       would make it 1 (the reference's regularize_weight), and a draw weighed 1 has the expectation integral of p * L, which
+ *       depends on the density -- under the table it is the sun's radiance times the sun's share.  The BSDF-sampled rays keep the clamp as it is.
+ *     BSDF-sampled light ray, no emitters: pdf_light = p(d) in place of |cos| / pi.
+ *     BSDF-sampled light ray, emitters: the secondary-ray kernels finish it with pdf_light = cos' / pi on a miss and T * w * f * cos' / pdf; they are handed
+ *       cos' = PI * p(d) and f' = f * |cos| / cos', which makes the miss density p(d) and leaves the product T * w * f * |cos| / pdf in both branches.
+ * The table is rebuilt, on the context stream and without a host synchronisation, by the first fh_render after fh_load_ibl, fh_clear_ibl, fh_load_arhosek_sky,
+ * fh_clear_arhosek_sky or a call of this function that turns the switch on; a change of cosine_fraction alone keeps it.
+ * Not covered: sampling the product of BSDF and environment, a table resolution parameter, sampling area lights by power. */
+#define FH_ENV_COSINE_FRACTION_DEFAULT 0.5f
+typedef struct fh_env_sampling_params {
+  float cosine_fraction; /* B: share of sky rays drawn cosine-distributed, in [0, 1); default FH_ENV_COSINE_FRACTION_DEFAULT (DESIGN.md 4 has the rule that chose it) */
+} fh_env_sampling_params;
+/* params == NULL: off.  A scene call: on a group it reaches every member.  FH_E_INVALID, decided from the arguments alone before the context is looked at, for a
+ * cosine_fraction outside [0, 1) or NaN; the switch then stays as it was. */
+int fh_set_env_sampling(fh_ctx* ctx, const fh_env_sampling_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the fraction last set (the default before any) */
+int fh_get_env_sampling(fh_ctx* ctx, int* on, fh_env_sampling_params* params);
+
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */
 int fh_gl_register_buffer(fh_ctx* ctx, unsigned int gl_buffer, void** resource, void** device_ptr, uint64_t* bytes);

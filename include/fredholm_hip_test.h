@@ -75,6 +75,15 @@ int fh_kat_set_issued(fh_ctx* ctx, const uint32_t* issued, uint32_t n_pixels);
    (csrc/fh_memory.h; memory from fh_malloc is the caller's and is not counted).  Takes no context; either pointer may be NULL.  A context that has been destroyed
    leaves both where they were before it was created */
 int fh_kat_live_allocations(uint64_t* count, uint64_t* bytes);
+/* fh_set_env_sampling (include/fredholm_hip.h), on the context's CURRENT table (a stale one is rebuilt first, as fh_render does); FH_E_INVALID while the switch is off.
+ * fh_kat_env_table: the 512 x 256 integer weights, cdf_row [256][513], cdf_marginal [257], cell_p [256][512].
+ * fh_kat_env_sample: n draws of the sky slot, (ux, uy) and a unit shading normal each -> world direction, mixture density, the cell the density was taken from.
+ * fh_kat_env_pdf: the evaluator: n (world direction, shading normal) -> mixture density and the direction's cell. */
+int fh_kat_env_table(fh_ctx* ctx, uint32_t* weights, float* cdf_row, float* cdf_marginal, float* cell_p);
+int fh_kat_env_sample(fh_ctx* ctx, uint32_t n, const float* u2, const float* normal3, float* dir3, float* pdf, uint32_t* cell);
+int fh_kat_env_pdf(fh_ctx* ctx, uint32_t n, const float* dirs3, const float* normal3, float* pdf, uint32_t* cell);
+/* the environment along n directions as the table weighs it -- the image, else the Hosek dome, else white, at sky intensity 1; works with the switch off */
+int fh_kat_env_radiance(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3);
 
 #ifdef __cplusplus
 }

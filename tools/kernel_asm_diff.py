@@ -4,7 +4,7 @@
 Make the listings with the Makefile's flags, e.g. in fredholm_amd/csrc of each of the two trees:
     hipcc $(FLAGS) -S --cuda-device-only render.hip -o render.s
 Every function (kernel or device function) is cut out at its label and compared line by line, comments stripped and the function-local label numbers
-(.LBB<function>_<block>, jump tables, .Ltmp) normalised: a function added in front of another renumbers that one's labels and changes nothing else.
+(.LBB<function>_<block>, jump tables, .Ltmp, .Lpost_getpc) normalised: a function added in front of another renumbers that one's labels and changes nothing else.
 Prints the functions that differ, are new or are gone, and the counts; exit status 0 always (it reports, the reader judges)."""
 import re
 import sys
@@ -21,7 +21,7 @@ def functions(path):
             if line.startswith(".Lfunc_end"):
                 out[name], name = body, None
                 continue
-            t = re.sub(r"\.L(BB|JTI|func_begin|func_end|tmp)\d+(_\d+)?", lambda m: ".L" + m.group(1) + (m.group(2) or ""), line.split(";")[0].rstrip())
+            t = re.sub(r"\.L(BB|JTI|func_begin|func_end|tmp|post_getpc)\d+(_\d+)?", lambda m: ".L" + m.group(1) + (m.group(2) or ""), line.split(";")[0].rstrip())
             if t.strip():
                 body.append(t)
     return out
