@@ -20,6 +20,9 @@
 //          [--auto-exposure [--exposure-key K] [--exposure-comp EV] [--exposure-speed UP DOWN] [--bloom-relative]]   (the tone map's exposure is metered from every frame's
 //                                         luminance histogram in place of ISO: the mean log2 luminance of the middle ranks is mapped to K (default 0.18), shifted by EV stops, and
 //                                         followed at UP / DOWN per second (default 3 / 1) with a frame time of 1 / fps; --bloom-relative: the bloom threshold compares exposed luminance)
+//          [--local-exposure [--local-highlights H] [--local-shadows S] [--local-sigma R] [--local-passes P]]   (the tone map's exposure varies over the frame: an
+//                                         edge-aware base layer of log-luminance loses the share H of its distance above and S below mid-grey (default 0.5 / 0.5); R: the range
+//                                         sigma of the edge stop in stops (default 1); P: a-trous passes on the quarter-resolution image, 1 .. 6 (default 4))
 //          [--env-sampling [--env-cosine-fraction B]]   (the sky rays are drawn from a table of the environment's luminance -- the --ibl image, the --sky dome -- mixed with
 //                                         the cosine lobe at share B in [0, 1) (default: the library's); without it they are cosine-distributed as in the reference)
 //          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
@@ -63,6 +66,9 @@ int main(int argc, char** argv)
   bool auto_exposure = false, bloom_relative = false;  // --auto-exposure, --bloom-relative
   AutoExposureParams exposure;                         // --exposure-key, --exposure-comp, --exposure-speed (with --auto-exposure only)
   const char* exposure_flag = nullptr;                 // the first of those flags that was given
+  bool local_exposure = false;                         // --local-exposure
+  LocalExposureParams local;                           // --local-highlights, --local-shadows, --local-sigma, --local-passes (with --local-exposure only)
+  const char* local_flag = nullptr;                    // the first of those flags that was given
   bool env_sampling = false, env_fraction_given = false;  // --env-sampling, --env-cosine-fraction (with --env-sampling only)
   float env_fraction = FH_ENV_COSINE_FRACTION_DEFAULT;
   std::vector<int> devices;  // --devices: empty = FH_DEVICES, or device 0
@@ -96,6 +102,11 @@ int main(int argc, char** argv)
     else if (a == "--denoise-temporal-moments") temporal_moments = true;
     else if (a == "--denoise-min-history") { denoise_min_history = float(std::atof(next())); min_history_given = true; }
     else if (a == "--auto-exposure") auto_exposure = true;
+    else if (a == "--local-exposure") local_exposure = true;
+    else if (a == "--local-highlights") { local.highlights = float(std::atof(next())); if (!local_flag) local_flag = "--local-highlights"; }
+    else if (a == "--local-shadows") { local.shadows = float(std::atof(next())); if (!local_flag) local_flag = "--local-shadows"; }
+    else if (a == "--local-sigma") { local.sigma_range = float(std::atof(next())); if (!local_flag) local_flag = "--local-sigma"; }
+    else if (a == "--local-passes") { local.passes = uint32_t(std::atoi(next())); if (!local_flag) local_flag = "--local-passes"; }
     else if (a == "--env-sampling") env_sampling = true;
     else if (a == "--env-cosine-fraction") { env_fraction = float(std::atof(next())); env_fraction_given = true; }
     else if (a == "--exposure-key") { exposure.key = float(std::atof(next())); if (!exposure_flag) exposure_flag = "--exposure-key"; }
@@ -107,7 +118,7 @@ int main(int argc, char** argv)
     }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]] [--auto-exposure [--exposure-key K] [--exposure-comp EV] [--exposure-speed UP DOWN] [--bloom-relative]] [--env-sampling [--env-cosine-fraction B]] [--devices 0,1,...]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]] [--auto-exposure [--exposure-key K] [--exposure-comp EV] [--exposure-speed UP DOWN] [--bloom-relative]] [--local-exposure [--local-highlights H] [--local-shadows S] [--local-sigma R] [--local-passes P]] [--env-sampling [--env-cosine-fraction B]] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   if (adaptive_block != 1 && adaptive_block != 2 && adaptive_block != 4 && adaptive_block != 8) { std::fprintf(stderr, "--adaptive-block must be 1, 2, 4 or 8\n"); return 2; }
   if (adaptive_growth != 1 && adaptive_growth != 2) { std::fprintf(stderr, "--adaptive-growth must be 1 or 2\n"); return 2; }
@@ -127,6 +138,11 @@ int main(int argc, char** argv)
   if (!(exposure.key > 0.0f) || !std::isfinite(exposure.key)) { std::fprintf(stderr, "--exposure-key must be finite and > 0\n"); return 2; }
   if (!std::isfinite(exposure.compensation_ev)) { std::fprintf(stderr, "--exposure-comp must be finite\n"); return 2; }
   if (!(exposure.speed_up >= 0.0f) || !std::isfinite(exposure.speed_up) || !(exposure.speed_down >= 0.0f) || !std::isfinite(exposure.speed_down)) { std::fprintf(stderr, "--exposure-speed takes two finite rates >= 0\n"); return 2; }
+  if (local_flag && !local_exposure) { std::fprintf(stderr, "%s goes with --local-exposure\n", local_flag); return 2; }
+  if (!(local.highlights >= 0.0f && local.highlights <= 1.0f)) { std::fprintf(stderr, "--local-highlights must be in [0, 1]\n"); return 2; }
+  if (!(local.shadows >= 0.0f && local.shadows <= 1.0f)) { std::fprintf(stderr, "--local-shadows must be in [0, 1]\n"); return 2; }
+  if (!(local.sigma_range > 0.0f) || !std::isfinite(local.sigma_range)) { std::fprintf(stderr, "--local-sigma must be finite and > 0\n"); return 2; }
+  if (local.passes < 1u || local.passes > 6u) { std::fprintf(stderr, "--local-passes must be 1 .. 6\n"); return 2; }
   if (env_fraction_given && !env_sampling) { std::fprintf(stderr, "--env-cosine-fraction goes with --env-sampling\n"); return 2; }
   if (!(env_fraction >= 0.0f && env_fraction < 1.0f)) { std::fprintf(stderr, "--env-cosine-fraction must be in [0, 1)\n"); return 2; }
   if (auto_exposure && !(fps > 0.0f)) { std::fprintf(stderr, "--auto-exposure needs --fps > 0\n"); return 2; }
@@ -183,6 +199,7 @@ int main(int argc, char** argv)
       exposure.bloom_relative = bloom_relative;
       set_auto_exposure(&exposure);
     }
+    if (local_exposure) set_local_exposure(&local);
     if (sun) renderer.set_directional_light(make_float3(20, 20, 20), make_float3(-0.1f, 1, 0.1f), 1.0f);  // rtcamp8.cpp:133-134
     if (sky) renderer.load_arhosek_sky(3.0f, 0.3f);                                                       // rtcamp8.cpp:137
     if (!ibl.empty()) renderer.load_ibl(ibl);

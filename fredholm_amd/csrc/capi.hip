@@ -12,6 +12,7 @@
 
 #include "context.h"
 #include "fh_bsdf.h"
+#include "fh_local_exposure.h"
 #include "fh_meter.h"
 #include "fh_trace.h"
 #include "motion_host.h"
@@ -1301,6 +1302,42 @@ int fh_get_luminance_histogram(fh_ctx* ctx, uint32_t hist[257])
   CTX_CHECK(ctx);
   if (!ctx->auto_exposure) return fail(ctx, FH_E_INVALID, "fh_get_luminance_histogram: auto-exposure is off (fh_set_auto_exposure)");
   return auto_exposure_read(ctx, nullptr, hist);
+}
+
+// local exposure of the post chain (post.hip, fh_local_exposure.h): the same rules as auto-exposure above
+int fh_set_local_exposure(fh_ctx* ctx, const fh_local_exposure_params* params)
+{
+  if (const char* why = local_exposure_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_local_exposure: ") + why);
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  return local_exposure_set(ctx, params);
+}
+
+int fh_get_local_exposure(fh_ctx* ctx, int* on, fh_local_exposure_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->local_exposure;
+  if (params) *params = ctx->lx_params;
+  return FH_OK;
+}
+
+int fh_local_exposure_analyse(fh_ctx* ctx, const float* image_rgba, uint32_t width, uint32_t height)
+{
+  if (!image_rgba || width == 0 || height == 0 || width > 32768 || height > 32768) return fail(ctx, FH_E_INVALID, "fh_local_exposure_analyse: needs an image of 1 .. 32768 pixels each way");
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!ctx->local_exposure) return fail(ctx, FH_E_INVALID, "fh_local_exposure_analyse: local exposure is off (fh_set_local_exposure)");
+  return local_exposure_submit(ctx, image_rgba, width, height);
+}
+
+int fh_get_local_exposure_base(fh_ctx* ctx, float* base, uint32_t* w4, uint32_t* h4)
+{
+  if (!w4 || !h4) return fail(ctx, FH_E_INVALID, "fh_get_local_exposure_base: null argument");
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!ctx->local_exposure) return fail(ctx, FH_E_INVALID, "fh_get_local_exposure_base: local exposure is off (fh_set_local_exposure)");
+  return local_exposure_read_base(ctx, base, w4, h4);
 }
 
 int fh_denoise(fh_ctx* ctx, uint32_t width, uint32_t height, const float* beauty, const float* normal, const float* albedo, float* denoised, int upscale2x)

@@ -243,6 +243,14 @@ struct fh_ctx {
   fh::DeviceBuffer<uint8_t> d_meter;
   fh::DeviceBuffer<uint32_t> d_meter_slabs;
 
+  // fh_set_local_exposure (post.hip: k_lx_down, k_lx_atrous, k_tone_map_local).  d_lx_log: the log image of the last analysis, one float per pixel; d_lx_q: the two
+  // quarter-resolution images the a-trous passes go back and forth between -- the base is d_lx_q[lx_passes_run & 1].  All three grow on demand and are kept
+  int local_exposure = 0;
+  fh_local_exposure_params lx_params = {0.5f, 0.5f, 0.18f, 4.0f, 1.0f, 4u};
+  fh::DeviceBuffer<float> d_lx_log;
+  fh::DeviceBuffer<float> d_lx_q[2];
+  uint32_t lx_w4 = 0, lx_h4 = 0, lx_passes_run = 0;  // of the last analysis; 0 x 0: none since the switch went on
+
   // denoiser slot (post.hip): ping-pong buffers of the a-trous filter
   fh::DeviceBuffer<float4> d_denoise_tmp[2];
   // variance-guided denoiser (denoise.hip): ping-pong (colour, variance) images and dense variance planes
@@ -343,6 +351,10 @@ int auto_exposure_set(fh_ctx* ctx, const fh_auto_exposure_params* params);
 int meter_submit(fh_ctx* ctx, const float* image, uint32_t w, uint32_t h);
 int auto_exposure_reset(fh_ctx* ctx);
 int auto_exposure_read(fh_ctx* ctx, fh_auto_exposure_state* state, uint32_t* hist);
+// post.hip, local exposure (arguments checked by the caller): the switch; log image, quarter image and a-trous passes of one image; the synchronising read-back
+int local_exposure_set(fh_ctx* ctx, const fh_local_exposure_params* params);
+int local_exposure_submit(fh_ctx* ctx, const float* image, uint32_t w, uint32_t h);
+int local_exposure_read_base(fh_ctx* ctx, float* base, uint32_t* w4, uint32_t* h4);
 int denoise_submit(fh_ctx* ctx, int w, int h, const float* beauty, const float* normal, const float* albedo, float* out, int upscale);  // post.hip
 int denoise_guided_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_denoise_params* params, float* out, int upscale);  // denoise.hip (arguments checked by the caller)
 // denoise.hip (arguments checked by the caller); w2c, inv_tan: `cam` inverted and its cam_inv_tan, kept with the history this call writes

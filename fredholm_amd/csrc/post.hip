@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "context.h"
+#include "fh_local_exposure.h"
 #include "fh_meter.h"
 #include "fh_tonemap.h"
 
@@ -236,6 +237,68 @@ __global__ void __launch_bounds__(256) k_tone_map_metered(const float4* in, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Local exposure (fh_set_local_exposure; the arithmetic is fh_local_exposure.h's and stated in include/fredholm_hip.h).  No counterpart in the reference.
+// k_lx_down reads the input once and leaves the log image and its 4 x 4 means; k_lx_atrous runs one edge-stopping pass on that quarter image; k_tone_map_local
+// upsamples the base against each output pixel's own log-luminance, turns it into a gain and runs the tone map with it.
+constexpr int kLxDownW = 64, kLxDownWaves = 4;  // a workgroup of k_lx_down: 64 columns x (4 waves x 4 rows)
+
+// One wave per row of 4 x 4 blocks: lane x loads its column's pixel of each of the four rows -- a wave reads 1 KiB of consecutive float4 per row, all four loads
+// issued before the first is used -- and the three lanes to the right of every fourth lane hand it their values, so the row sums are formed left to right in one
+// lane, which then adds them top to bottom.  No LDS.
+__global__ void __launch_bounds__(kLxDownW * kLxDownWaves) k_lx_down(const float4* in, int w, int h, int w4, float* logi, float* q0)
+{
+  const int x = blockIdx.x * kLxDownW + threadIdx.x;
+  const int y0 = (blockIdx.y * kLxDownWaves + threadIdx.y) * kLxFactor;
+  if (y0 >= h) return;  // (the whole wave: threadIdx.y is the wave)
+  const bool col = x < w;
+  const int n_rows = h - y0 < kLxFactor ? h - y0 : kLxFactor;
+  const int n_cols = w - (x & ~3) < kLxFactor ? w - (x & ~3) : kLxFactor;  // of the block this lane lies in
+  float4 p[kLxFactor];
+#pragma unroll
+  for (int k = 0; k < kLxFactor; ++k) {
+    p[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (col && k < n_rows) p[k] = in[(size_t)x + (size_t)w * (size_t)(y0 + k)];
+  }
+  float row[kLxFactor];
+#pragma unroll
+  for (int k = 0; k < kLxFactor; ++k) {
+    const float l = lx_log(p[k].x, p[k].y, p[k].z);
+    if (col && k < n_rows) logi[(size_t)x + (size_t)w * (size_t)(y0 + k)] = l;
+    const float l1 = __shfl_down(l, 1), l2 = __shfl_down(l, 2), l3 = __shfl_down(l, 3);  // by every lane of the wave
+    row[k] = lx_row_sum(l, l1, l2, l3, n_cols);
+  }
+  if ((threadIdx.x & 3) == 0 && col) q0[(x >> 2) + w4 * (y0 >> 2)] = lx_block_mean(row[0], row[1], row[2], row[3], n_rows, n_cols);
+}
+
+__global__ void __launch_bounds__(256) k_lx_atrous(const float* src, int w4, int h4, int step, float inv_sr, float* dst)
+{
+  const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
+  if (x >= w4 || y >= h4) return;
+  dst[x + w4 * y] = lx_atrous(src, w4, h4, x, y, step, inv_sr);
+}
+
+// k_tone_map / k_tone_map_metered (md != nullptr) with the exposure multiplied by the output pixel's local gain
+__global__ void __launch_bounds__(256) k_tone_map_local(const float4* in, const float* logi, const float* base, int w, int h, int gw, int gh, int w4, int h4, const MeterDev* md,
+                                                        float iso_exposure, float ca, LxConsts lx, float4* out)
+{
+  const int i = blockIdx.x * kT + threadIdx.x, j = blockIdx.y * kT + threadIdx.y;
+  if (i >= gw || j >= gh) return;
+  const float exposure = (md && md->st.frames != 0u) ? md->exposure : iso_exposure;
+  const float gain = lx_gain(lx_upsample(base, w4, h4, i, j, logi[i + w * j], lx.inv_sr), exposure, lx);
+  const float uvx = (float)i / w, uvy = (float)j / h;
+  const float inv = 1.0f / (float)(w * h);
+  const float dx = (uvx - 0.5f) * inv * ca, dy = (uvy - 0.5f) * inv * ca;
+  const float rx = clamp01f(uvx - 0.0f * dx), ry = clamp01f(uvy - 0.0f * dy);
+  const float gx = clamp01f(uvx - 1.0f * dx), gy = clamp01f(uvy - 1.0f * dy);
+  const float bx = clamp01f(uvx - 2.0f * dx), by = clamp01f(uvy - 2.0f * dy);
+  const int ir = (int)(rx * w + w * (ry * h)), ig = (int)(gx * w + w * (gy * h)), ib = (int)(bx * w + w * (by * h));
+  float r = in[ir].x, g = in[ig].y, b = in[ib].z;
+  r *= gain; g *= gain; b *= gain;
+  r = srgb1(uchimura1(r)); g = srgb1(uchimura1(g)); b = srgb1(uchimura1(b));
+  out[i + w * j] = make_float4(r, g, b, 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Denoiser slot.  The reference calls NVIDIA's OptiX AI denoiser (fredholm/include/fredholm/denoiser.h:14-146: HDR model, albedo + normal
 // guides, optional 2x upscale) -- a proprietary network with no counterpart here and nothing to be bit-compatible with.  What fills the slot is
 // the classic guided filter it replaced in many renderers: the edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010)
@@ -311,6 +374,13 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
     const int rc = meter_submit(ctx, in, (uint32_t)w, (uint32_t)h);
     if (rc != FH_OK) return rc;
   }
+  // fh_set_local_exposure: the analysis of the input goes first; the tone map at the end reads the log image and the base it left
+  const bool local = ctx->local_exposure != 0;
+  if (local) {
+    if (w > 32768 || h > 32768) return fail(ctx, FH_E_INVALID, "fh_post_process: local exposure analyses images of at most 32768 x 32768 pixels");
+    const int rc = local_exposure_submit(ctx, in, (uint32_t)w, (uint32_t)h);
+    if (rc != FH_OK) return rc;
+  }
   if (pp->use_bloom) {
     // the 1089 weights depend on bloom_sigma only: computed and uploaded when sigma changes, kept in the context otherwise
     // (no allocation, copy or host synchronisation per frame)
@@ -336,7 +406,9 @@ int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int
   } else {
     hipLaunchKernelGGL(k_copy, grid, block, 0, st, (const float4*)in, w, gw, gh, (float4*)tmp);
   }
-  if (metered) hipLaunchKernelGGL(k_tone_map_metered, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, md, exposure, pp->chromatic_aberration, (float4*)out);
+  if (local) hipLaunchKernelGGL(k_tone_map_local, grid, block, 0, st, (const float4*)tmp, (const float*)ctx->d_lx_log.get(), (const float*)ctx->d_lx_q[ctx->lx_passes_run & 1u].get(), w, h, gw, gh,
+                                (int)ctx->lx_w4, (int)ctx->lx_h4, metered ? md : nullptr, exposure, pp->chromatic_aberration, lx_consts(ctx->lx_params), (float4*)out);
+  else if (metered) hipLaunchKernelGGL(k_tone_map_metered, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, md, exposure, pp->chromatic_aberration, (float4*)out);
   else hipLaunchKernelGGL(k_tone_map, grid, block, 0, st, (const float4*)tmp, w, h, gw, gh, exposure, pp->chromatic_aberration, (float4*)out);
   if (timed) { (void)hipEventRecord(ev_b, st); ctx->spans.push_back({std::move(ev_a), std::move(ev_b), 7}); ctx->stats.n_post_launches++; }
   FH_HIP(hipGetLastError());
@@ -389,6 +461,46 @@ int auto_exposure_read(fh_ctx* ctx, fh_auto_exposure_state* state, uint32_t* his
   FH_HIP(hipStreamSynchronize(ctx->stream));
   if (state) *state = host.st;
   if (hist) for (int k = 0; k < kMeterWords; ++k) hist[k] = host.hist[k];
+  return FH_OK;
+}
+
+// ---- local exposure, host side
+int local_exposure_set(fh_ctx* ctx, const fh_local_exposure_params* params)
+{
+  if (!params || !ctx->local_exposure) ctx->lx_w4 = ctx->lx_h4 = ctx->lx_passes_run = 0;  // off, or off -> on: no analysis to read back; the allocations are kept
+  ctx->local_exposure = params ? 1 : 0;
+  if (params) ctx->lx_params = *params;
+  return FH_OK;
+}
+
+int local_exposure_submit(fh_ctx* ctx, const float* image, uint32_t w, uint32_t h)
+{
+  hipStream_t st = ctx->stream;
+  const int w4 = lx_quarter((int)w), h4 = lx_quarter((int)h);  // w, h <= 32768
+  const size_t n = (size_t)w * h, n4 = (size_t)w4 * h4;
+  if (ctx->d_lx_log.size() < n || ctx->d_lx_q[0].size() < n4 || ctx->d_lx_q[1].size() < n4) {  // grow on demand, never per frame
+    FH_HIP(hipStreamSynchronize(st));                                                       // an earlier call may still use the old images
+    FH_HIP(ctx->d_lx_log.ensure(n));
+    for (int k = 0; k < 2; ++k) FH_HIP(ctx->d_lx_q[k].ensure(n4));
+  }
+  const LxConsts lx = lx_consts(ctx->lx_params);
+  hipLaunchKernelGGL(k_lx_down, dim3((w + kLxDownW - 1) / kLxDownW, (h + kLxDownWaves * kLxFactor - 1) / (kLxDownWaves * kLxFactor)), dim3(kLxDownW, kLxDownWaves), 0, st,
+                     (const float4*)image, (int)w, (int)h, w4, ctx->d_lx_log.get(), ctx->d_lx_q[0].get());
+  const dim3 grid((w4 + 15) / 16, (h4 + 15) / 16), block(16, 16);
+  for (uint32_t it = 0; it < ctx->lx_params.passes; ++it)
+    hipLaunchKernelGGL(k_lx_atrous, grid, block, 0, st, (const float*)ctx->d_lx_q[it & 1u].get(), w4, h4, 1 << it, lx.inv_sr, ctx->d_lx_q[(it + 1u) & 1u].get());
+  ctx->lx_w4 = (uint32_t)w4; ctx->lx_h4 = (uint32_t)h4; ctx->lx_passes_run = ctx->lx_params.passes;
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int local_exposure_read_base(fh_ctx* ctx, float* base, uint32_t* w4, uint32_t* h4)
+{
+  *w4 = ctx->lx_w4; *h4 = ctx->lx_h4;
+  const size_t n4 = (size_t)ctx->lx_w4 * ctx->lx_h4;
+  if (!base || n4 == 0) return FH_OK;
+  FH_HIP(hipMemcpyAsync(base, ctx->d_lx_q[ctx->lx_passes_run & 1u].get(), n4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipStreamSynchronize(ctx->stream));
   return FH_OK;
 }
 

@@ -117,6 +117,7 @@ EXPORTS = [
     "fh_set_denoise_response", "fh_get_denoise_response", "fh_set_denoise_response_noise", "fh_get_denoise_response_noise",
     "fh_set_denoise_temporal_moments", "fh_get_denoise_temporal_moments",
     "fh_set_auto_exposure", "fh_get_auto_exposure", "fh_auto_exposure_reset", "fh_meter_exposure", "fh_get_auto_exposure_state", "fh_get_luminance_histogram",
+    "fh_set_local_exposure", "fh_get_local_exposure", "fh_local_exposure_analyse", "fh_get_local_exposure_base",
     "fh_set_env_sampling", "fh_get_env_sampling", "fh_kat_env_table", "fh_kat_env_sample", "fh_kat_env_pdf", "fh_kat_env_radiance",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
@@ -172,6 +173,11 @@ class AutoExposureParamsC(C.Structure):
                 ("speed_up", C.c_float), ("speed_down", C.c_float), ("frame_time", C.c_float), ("log2_lo", C.c_float), ("log2_hi", C.c_float), ("flags", C.c_uint32)]
 
 
+class LocalExposureParamsC(C.Structure):
+    """fh_local_exposure_params (include/fredholm_hip.h)"""
+    _fields_ = [("highlights", C.c_float), ("shadows", C.c_float), ("pivot", C.c_float), ("max_stops", C.c_float), ("sigma_range", C.c_float), ("passes", C.c_uint32)]
+
+
 class EnvSamplingParamsC(C.Structure):
     """fh_env_sampling_params (include/fredholm_hip.h)"""
     _fields_ = [("cosine_fraction", C.c_float)]
@@ -219,6 +225,10 @@ SIGNATURES = {
     "fh_meter_exposure": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
     "fh_get_auto_exposure_state": [C.c_void_p, C.POINTER(AutoExposureStateC)],
     "fh_get_luminance_histogram": [C.c_void_p, C.POINTER(C.c_uint32)],
+    "fh_set_local_exposure": [C.c_void_p, C.POINTER(LocalExposureParamsC)],
+    "fh_get_local_exposure": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(LocalExposureParamsC)],
+    "fh_local_exposure_analyse": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32],
+    "fh_get_local_exposure_base": [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "fh_set_env_sampling": [C.c_void_p, C.POINTER(EnvSamplingParamsC)],
     "fh_get_env_sampling": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(EnvSamplingParamsC)],
     "fh_kat_env_table": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],

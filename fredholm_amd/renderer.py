@@ -572,6 +572,37 @@ class Renderer:
         self._ck(N.lib().fh_get_luminance_histogram(self._ctx, h), "fh_get_luminance_histogram")
         return np.frombuffer(h, dtype=np.uint32).copy()
 
+    # -- local exposure of the post chain (fh_set_local_exposure)
+    def set_local_exposure(self, highlights=0.5, shadows=0.5, pivot=0.18, max_stops=4.0, sigma_range=1.0, passes=4):
+        """fh_set_local_exposure: while on, post_process builds an edge-aware base layer of its input's log2-luminance (4 x 4 means, `passes` a-trous passes with a
+        range sigma of `sigma_range` stops, upsampled against each pixel's own value) and its tone map multiplies each pixel by a gain that removes the share
+        `highlights` (above) or `shadows` (below) of the base's distance from `pivot`, by at most `max_stops` stops.  The detail on top of the base is left alone"""
+        p = N.LocalExposureParamsC(float(highlights), float(shadows), float(pivot), float(max_stops), float(sigma_range), int(passes))
+        self._ck(N.lib().fh_set_local_exposure(self._ctx, C.byref(p)), "fh_set_local_exposure")
+
+    def clear_local_exposure(self):
+        """off: one exposure for the frame"""
+        self._ck(N.lib().fh_set_local_exposure(self._ctx, None), "fh_set_local_exposure")
+
+    def get_local_exposure(self):
+        """(on, parameters as a dict): the switch and the parameters last set (the defaults before any)"""
+        on, p = C.c_int(0), N.LocalExposureParamsC()
+        self._ck(N.lib().fh_get_local_exposure(self._ctx, C.byref(on), C.byref(p)), "fh_get_local_exposure")
+        return bool(on.value), {k: getattr(p, k) for k, _ in p._fields_}
+
+    def local_exposure_analyse(self, image_ptr, width, height):
+        """fh_local_exposure_analyse: the base stage alone on a device image of width * height float4 (asynchronous); what post_process does first while the switch is on"""
+        self._ck(N.lib().fh_local_exposure_analyse(self._ctx, C.c_void_p(image_ptr), C.c_uint32(int(width)), C.c_uint32(int(height))), "fh_local_exposure_analyse")
+
+    def local_exposure_base(self):
+        """the quarter-resolution base of the last analysis (synchronising): a float32 array of ceil(h / 4) x ceil(w / 4), empty before any"""
+        w4, h4 = C.c_uint32(0), C.c_uint32(0)
+        self._ck(N.lib().fh_get_local_exposure_base(self._ctx, None, C.byref(w4), C.byref(h4)), "fh_get_local_exposure_base")
+        base = np.zeros((h4.value, w4.value), dtype=np.float32)
+        if base.size:
+            self._ck(N.lib().fh_get_local_exposure_base(self._ctx, base.ctypes.data_as(C.c_void_p), C.byref(w4), C.byref(h4)), "fh_get_local_exposure_base")
+        return base
+
     def denoise(self, width, height, beauty_ptr, normal_ptr, albedo_ptr, denoised_ptr, upscale=False):
         """the denoiser slot (Denoiser::denoise, denoiser.h:87-95): edge-avoiding a-trous filter guided by the normal and albedo layers"""
         self._ck(N.lib().fh_denoise(self._ctx, C.c_uint32(int(width)), C.c_uint32(int(height)), C.c_void_p(beauty_ptr), C.c_void_p(normal_ptr), C.c_void_p(albedo_ptr),

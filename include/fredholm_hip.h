@@ -549,7 +549,8 @@ int fh_get_denoise_temporal_moments(fh_ctx* ctx, int* on, fh_temporal_moments_pa
  *   Chain: the tone map is fh_post_process's with r, g, b multiplied by fhe_pow(2.0f, ev).  With FH_AE_BLOOM_RELATIVE the bloom threshold passes a pixel when
  *     l * exposure > bloom_threshold (l = r * 0.2126729 + g * 0.7151522 + b * 0.0721750 as that kernel computes it), with the ISO exposure while frames == 0;
  *     without the flag the threshold compares scene luminance as it always did.
- * Not covered: metering of tile shards before a gather (the input is a whole frame on one device), spatial (centre-weighted) metering, local tone mapping. */
+ * Not covered: metering of tile shards before a gather (the input is a whole frame on one device), spatial (centre-weighted) metering.  Local tone mapping is
+ * fh_set_local_exposure's, below. */
 #define FH_AE_BLOOM_RELATIVE 1u
 typedef struct fh_auto_exposure_params {
   float key;               /* 0.18: the value the metered mean luminance is mapped to */
@@ -579,6 +580,53 @@ int fh_meter_exposure(fh_ctx* ctx, const float* image_rgba, uint32_t width, uint
 int fh_get_auto_exposure_state(fh_ctx* ctx, fh_auto_exposure_state* state);
 /* synchronising: the histogram of the last metering call (all zero before any); hist[256] = unmetered pixels.  FH_E_INVALID while the switch is off */
 int fh_get_luminance_histogram(fh_ctx* ctx, uint32_t hist[257]);
+
+/* -- local exposure of the post chain: an edge-aware base layer of log-luminance whose contrast is reduced, the detail on top of it left alone (opt-in, default off;
+ * with it off fh_post_process keeps its bits, its launches and its kernels).  fh_post_params stays as it is: the feature is a switch on the context.  While it is on,
+ * every fh_post_process call first analyses its input (fh_local_exposure_analyse: steps 1 - 3) and its tone map multiplies each output pixel by a gain of its own
+ * (steps 4 - 5).  Everything is queued on the context stream: no host synchronisation.
+ * All of it is fp32 without contraction, / correctly rounded, sums in the order written and starting from 0.0f unless noted; finite() and lum() are the metering's
+ * (above); fhe_log2, fhe_exp, fhe_pow: include/fh_elementary.h; fmaxf / fminf are C's.  On the host: inv_sr = 1.0f / sigma_range, log2pivot = fhe_log2(pivot).
+ *   1. Log image, per pixel of the input -- the image handed in as beauty_in, over ALL width * height pixels (not the floor-division grid of the tone map, and not
+ *      beauty_temp, whose border is never written):  l = fhe_log2(fmaxf(lum(finite(r), finite(g), finite(b)), 0x1p-24f)).
+ *   2. Quarter image, w4 = ceil(w / 4), h4 = ceil(h / 4):  for each in-frame row of the 4 x 4 block (X, Y) its in-frame l are added left to right (the first starts
+ *      the sum), the row sums are added top to bottom (likewise), and D0[Y, X] = that sum / (float)(the number of pixels added).
+ *   3. Base: `passes` a-trous passes, pass i = 0 .. passes - 1 with hole s = 2^i on the image of the pass before.  For pixel p = (X, Y), with dy = -2 .. 2 the outer
+ *      and dx = -2 .. 2 the inner loop:  q = p + s * (dx, dy), each coordinate clamped to the quarter frame;  t = (D_q - D_p) * inv_sr;
+ *      wt = (k[|dx|] * k[|dy|]) * fhe_exp(-(t * t)) with k = (3/8, 1/4, 1/16);  num += wt * D_q;  den += wt.  Then D'_p = num / den.
+ *   4. Joint upsampling, per output pixel (i, j) with l_p its own value of the log image:  fx = ((float)i + 0.5f) * 0.25f - 0.5f, x0 = floorf(fx), tx = fx - x0, and
+ *      the same for fy, y0, ty from j.  The taps (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) in this order, each index clamped to the quarter frame, with
+ *      wx = 1.0f - tx for x0 and tx for x0 + 1 (wy likewise), Q the base there:  t = (Q - l_p) * inv_sr;  wt = (wy * wx) * fhe_exp(-(t * t));  num += wt * Q;
+ *      den += wt.  B = den > 1e-6f ? num / den : l_p.
+ *   5. Gain: `exposure` is what the tone map would multiply by -- the ISO exposure, or fhe_pow(2, ev) once a frame has been metered while auto-exposure is on.
+ *      d = (B + fhe_log2(exposure)) - log2pivot;  g = -(d > 0 ? highlights : shadows) * d;  g = fmaxf(-max_stops, fminf(g, max_stops));
+ *      x = exposure * fhe_pow(2.0f, g).  The tone map is fh_post_process's with r, g, b multiplied by x in place of exposure: chromatic aberration still fetches the
+ *      three channels where it did, and the gain is the output pixel's.  Bloom and its threshold are untouched.  highlights = shadows = 0, or max_stops = 0, give
+ *      g = +-0, fhe_pow(2, +-0) = 1 and so the bits of the call with the switch off.
+ * The defaults are this library's own choice, made from a float64 prototype of the filter: at sigma_range = 1 and 4 passes an edge of 3 stops or more between two
+ * noisy plateaus stays in the base (no halo), and 0.3 stops of noise stay out of it.  An edge of less than about 2 sigma_range is smoothed by design.
+ * Not covered: analysis of tile shards before a gather (the input is a whole frame on one device), a resolution factor other than 4, per-channel gains, temporal
+ * smoothing of the base (every frame is analysed anew), any change to bloom. */
+typedef struct fh_local_exposure_params {
+  float highlights;   /* 0.5: share of the base layer's distance ABOVE the pivot that is removed; [0, 1] */
+  float shadows;      /* 0.5: the same BELOW the pivot; [0, 1] */
+  float pivot;        /* 0.18: the exposed luminance that is left alone; finite, > 0 */
+  float max_stops;    /* 4: clamp of the per-pixel correction, in stops; finite, >= 0 */
+  float sigma_range;  /* 1.0: range sigma of the edge stop, in stops; finite, > 0 */
+  uint32_t passes;    /* 4: a-trous passes on the quarter-resolution image; 1..6 */
+} fh_local_exposure_params;
+/* params == NULL: off.  On a group the switch lives on the lead, where fh_post_process runs.  FH_E_INVALID, decided from the arguments alone before the context is
+ * looked at and each with its own message: highlights or shadows outside [0, 1]; a pivot that is not finite or <= 0; a max_stops that is not finite or < 0; a
+ * sigma_range that is not finite or <= 0; passes outside 1 .. 6.  A refused call leaves the switch and the parameters alone. */
+int fh_set_local_exposure(fh_ctx* ctx, const fh_local_exposure_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the parameters last set (the defaults above before any) */
+int fh_get_local_exposure(fh_ctx* ctx, int* on, fh_local_exposure_params* params);
+/* steps 1 - 3 on image_rgba (a device pointer, width * height float4): asynchronous, on the context stream; what fh_post_process runs first while the switch is
+ * on.  FH_E_INVALID, from the arguments alone: a null image, width or height 0 or above 32768; and while the switch is off */
+int fh_local_exposure_analyse(fh_ctx* ctx, const float* image_rgba, uint32_t width, uint32_t height);
+/* synchronising: *w4 x *h4 and, when base is not NULL, the w4 * h4 floats (row-major) of the quarter-resolution base of the last analysis; 0 x 0 and nothing before
+ * any.  FH_E_INVALID for a null w4 or h4, and while the switch is off */
+int fh_get_local_exposure_base(fh_ctx* ctx, float* base, uint32_t* w4, uint32_t* h4);
 
 /* -- importance sampling of the environment for sky lighting (opt-in, default off; with it off every render keeps its bits, its launches and its kernels).
  * The sky next-event ray of a shaded hit is drawn cosine-distributed round the shading normal whatever the environment is (pt.cu:796-815: "TODO: implement IBL

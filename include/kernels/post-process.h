@@ -1,6 +1,7 @@
 // kernels/post-process.h -- PostProcessParams + post_process_kernel_launch with the reference's signature
 // (fredholm/kernels/include/kernels/post-process.h:4-10, :126-128), forwarding to fh_post_process.
-// Beyond the reference: auto-exposure (fh_set_auto_exposure), a switch on the process-wide context, so post_process_kernel_launch keeps its signature.
+// Beyond the reference: auto-exposure (fh_set_auto_exposure) and local exposure (fh_set_local_exposure), switches on the process-wide context, so
+// post_process_kernel_launch keeps its signature.
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -30,8 +31,23 @@ struct AutoExposureParams {
   bool bloom_relative = false;      // FH_AE_BLOOM_RELATIVE
 };
 
+// fh_local_exposure_params with the library's defaults
+struct LocalExposureParams {
+  float highlights = 0.5f, shadows = 0.5f;  // share of the base layer's distance above / below the pivot that is removed
+  float pivot = 0.18f;
+  float max_stops = 4.0f;
+  float sigma_range = 1.0f;
+  uint32_t passes = 4;
+};
+
 namespace fh_post_detail
 {
+// the same for FH_LOCAL_EXPOSURE
+inline bool& local_exposure_decided()
+{
+  static bool decided = false;
+  return decided;
+}
 // the environment variable FH_AUTO_EXPOSURE has been looked at, or the application has set the switch itself (which wins)
 inline bool& auto_exposure_decided()
 {
@@ -63,6 +79,20 @@ inline void reset_auto_exposure()
   cwl::check(ctx, fh_auto_exposure_reset(ctx), "fh_auto_exposure_reset");
 }
 
+// A weak reference: a program that brings entry points of its own from before this switch (stubs under a test) still links, and asking for the switch there throws
+extern "C" int fh_set_local_exposure(fh_ctx* ctx, const fh_local_exposure_params* params) __attribute__((weak));
+
+// nullptr: off.  Throws what fh_set_local_exposure refuses
+inline void set_local_exposure(const LocalExposureParams* params)
+{
+  fh_post_detail::local_exposure_decided() = true;
+  if (!fh_set_local_exposure) throw std::runtime_error("fh_set_local_exposure: not in the library this program is linked with");
+  fh_ctx* ctx = cwl::require_context();
+  if (!params) { cwl::check(ctx, fh_set_local_exposure(ctx, nullptr), "fh_set_local_exposure"); return; }
+  const fh_local_exposure_params p{params->highlights, params->shadows, params->pivot, params->max_stops, params->sigma_range, params->passes};
+  cwl::check(ctx, fh_set_local_exposure(ctx, &p), "fh_set_local_exposure");
+}
+
 inline void post_process_kernel_launch(const float4* beauty_in, float4* beauty_high_luminance, float4* beauty_temp, int width, int height, const PostProcessParams& params,
                                        float4* beauty_out)
 {
@@ -80,6 +110,20 @@ inline void post_process_kernel_launch(const float4* beauty_in, float4* beauty_h
         AutoExposureParams ae;
         if (std::strcmp(e, "1") != 0) ae.key = v;
         set_auto_exposure(&ae);
+      }
+    }
+  }
+  // FH_LOCAL_EXPOSURE likewise: "1" = the defaults, any other number = that share for both highlights and shadows, "0" or unset = off
+  if (!fh_post_detail::local_exposure_decided()) {
+    fh_post_detail::local_exposure_decided() = true;
+    if (const char* e = std::getenv("FH_LOCAL_EXPOSURE")) {
+      char* end = nullptr;
+      const float v = std::strtof(e, &end);
+      if (end == e || *end != '\0') throw std::runtime_error(std::string("FH_LOCAL_EXPOSURE: \"") + e + "\" is neither 1 (the defaults) nor a share such as 0.5");
+      if (v != 0.0f) {
+        LocalExposureParams lx;
+        if (std::strcmp(e, "1") != 0) lx.highlights = lx.shadows = v;
+        set_local_exposure(&lx);
       }
     }
   }
