@@ -341,7 +341,7 @@ __global__ void k_emit_tris(const float4* face_rec, const uint8_t* face_cls, con
   if (i >= n) return;
   uint32_t f = sorted_face[i];
   if (ref_face) f = ref_face[f];  // split faces: the leaf is a reference
-  if (face_cls[f] & 0x20u) {  // a cut-out face whose any-hit test can never pass (capi.hip: footprint_class): a triangle no ray hits
+  if (face_cls[f] & 0x20u) {  // a cut-out face whose any-hit test can never pass (scene_plan_host.h: footprint_class): a triangle no ray hits
     tris[3 * i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
     tris[3 * i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     tris[3 * i + 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);

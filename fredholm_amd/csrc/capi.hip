@@ -1,5 +1,5 @@
-// capi.hip -- implementation of the C ABI declared in include/fredholm_hip.h (context, scene
-// upload, environment, frame state, stats, device-memory helpers, tile pack/unpack).
+// capi.hip -- implementation of the C ABI declared in include/fredholm_hip.h (context, environment,
+// frame state, stats, device-memory helpers, tile pack/unpack; the scene upload is scene.hip).
 // Mirrors the host duties of fredholm::Renderer (fredholm/include/fredholm/renderer.h).
 #include <hip/hip_runtime.h>
 
@@ -36,360 +36,6 @@ int fail(fh_ctx* ctx, int code, const std::string& msg)
 }
 
 namespace {
-
-m34 load_m34(const float* m)
-{
-  m34 r;
-  for (int k = 0; k < 3; ++k) r.r[k] = make_float4(m[4 * k], m[4 * k + 1], m[4 * k + 2], m[4 * k + 3]);
-  return r;
-}
-const float kIdentity12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-
-bool material_emissive(const fh_material& m) { return m.emission_color[0] > 0 || m.emission_color[1] > 0 || m.emission_color[2] > 0 || m.emission_texture_id != -1; }
-bool material_textured(const fh_material& m)
-{
-  return m.base_color_texture_id != -1 || m.specular_color_texture_id != -1 || m.specular_roughness_texture_id != -1 || m.metalness_texture_id != -1 ||
-         m.metallic_roughness_texture_id != -1 || m.coat_texture_id != -1 || m.coat_roughness_texture_id != -1 || m.emission_texture_id != -1 || m.heightmap_texture_id != -1 ||
-         m.normalmap_texture_id != -1 || m.alpha_texture_id != -1;
-}
-
-// lobes a material can ever enable (see fh_bsdf.h).  Seen from the FRONT, metalness == 1 zeroes the weight and the layering
-// multiplier of every lobe after the metal one.  Seen from BEHIND the reference resets metalness, specular, sheen and diffuse to 0
-// (bsdf.cu:56-62), so transmission and diffuse transmission get their full weight back (weights[3], weights[5], bsdf.cu:74-84): those
-// two stay whenever their own parameters enable them.  specular / sheen / diffuse are zero on both sides of a full metal and are dropped.
-uint32_t material_lobes(const fh_material& m)
-{
-  // A texture on metalness (or the glTF metallic-roughness texture) makes metalness unknowable on the host: the metal lobe AND the lobes
-  // a non-metal needs are kept.  Lobes whose OWN switch is a constant zero stay dropped whatever the textures say: transmission, sheen and
-  // subsurface have no texture slot (shared.h:100-142), so a glTF material (scene.cpp:487-549 sets none of them) shades with
-  // coat? + metal + specular + diffuse instead of the generic seven-lobe kernel.
-  const bool metal_unknown = m.metalness_texture_id >= 0 || m.metallic_roughness_texture_id >= 0;
-  uint32_t l = 0;
-  const float coat = clampf(m.coat, 0.0f, 1.0f);
-  if (coat > 0.0f || m.coat_texture_id >= 0) l |= L_COAT;
-  if (m.metalness > 0.0f || metal_unknown) l |= L_METAL;
-  const bool metal_full = m.metalness == 1.0f && !metal_unknown;
-  if (m.transmission > 0.0f) l |= L_TRANS;
-  if (m.subsurface * m.thin_walled > 0.0f) l |= L_DT;
-  if (!metal_full) {
-    if (m.specular_color_texture_id >= 0 || m.specular * lum(mk3(m.specular_color[0], m.specular_color[1], m.specular_color[2])) > 0.0f) l |= L_SPEC;
-    if (m.sheen * lum(mk3(m.sheen_color[0], m.sheen_color[1], m.sheen_color[2])) != 0.0f) l |= L_SHEEN;
-    if (m.diffuse > 0.0f) l |= L_DIFF;
-  }
-  return l;
-}
-
-// world-space face record of every face (layout: fh_device.h) from the object-space arrays and the instance transforms:
-// positions by object_to_world, normals by the transpose of world_to_object (shared.h:42-50), as pt.cu:141-179 does per hit
-__global__ void __launch_bounds__(256) k_face_records(uint32_t nf, const float* vertices, const float* normals, const float* texcoords, const uint32_t* indices, const uint2* meta,
-                                                      const float4* o2w, const float4* w2o, float4* rec)
-{
-  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= nf) return;
-  const uint2 mi = meta[f];
-  m34 a, b;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { a.r[k] = o2w[3 * (size_t)mi.y + k]; b.r[k] = w2o[3 * (size_t)mi.y + k]; }
-  f3 p[3], n[3];
-  float uv[3][2];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const size_t v = indices[3 * (size_t)f + k];
-    p[k] = xform_point(a, mk3(vertices[3 * v], vertices[3 * v + 1], vertices[3 * v + 2]));
-    n[k] = xform_normal(b, mk3(normals[3 * v], normals[3 * v + 1], normals[3 * v + 2]));
-    uv[k][0] = texcoords[2 * v];
-    uv[k][1] = texcoords[2 * v + 1];
-  }
-  float4* r = rec + kFaceRec * (size_t)f;
-  r[0] = mk4(p[0], uv[0][0]); r[1] = mk4(p[1], uv[0][1]); r[2] = mk4(p[2], uv[1][0]);
-  r[3] = mk4(n[0], uv[1][1]); r[4] = mk4(n[1], uv[2][0]); r[5] = mk4(n[2], uv[2][1]);
-  r[6] = make_float4(__uint_as_float(mi.x), __uint_as_float(mi.y), 0.0f, 0.0f);
-}
-
-int transform_faces(fh_ctx* ctx)
-{
-  const uint32_t ni = (uint32_t)ctx->h_o2w.size() / 12;
-  FH_HIP(ctx->d_o2w.ensure(3ull * ni));  // (three rows per instance)
-  FH_HIP(ctx->d_w2o.ensure(3ull * ni));
-  FH_HIP(hipMemcpyAsync(ctx->d_o2w, ctx->h_o2w.data(), 48ull * ni, hipMemcpyHostToDevice, ctx->stream));
-  FH_HIP(hipMemcpyAsync(ctx->d_w2o, ctx->h_w2o.data(), 48ull * ni, hipMemcpyHostToDevice, ctx->stream));
-  if (ctx->n_faces)
-    hipLaunchKernelGGL(k_face_records, dim3((ctx->n_faces + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_faces, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices,
-                       ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o, ctx->d_face_rec);
-  FH_HIP(hipGetLastError());
-  FH_HIP(hipStreamSynchronize(ctx->stream));  // the host copies of the transforms may change right after this call
-  ctx->bvh_valid = false;
-  return FH_OK;
-}
-
-// ---- Opacity classes of cut-out faces (round 5).  The any-hit programs (pt.cu:545-678) discard a candidate hit when the filtered alpha of the base-colour texture or the
-// filtered red of the alpha texture is below 0.5 at the hit's texture coordinate.  A filtered value is a convex combination of the four texels around the coordinate (weights
-// are products of 1.8 fixed-point fractions and sum to exactly 1, include/fh_texture_unit.h), so over the part of a texture a FACE can ever address the outcome is known in
-// advance when all of those texels agree: every byte >= 128 (0.50196) -- the test always passes, the face needs no test at all -- or every byte <= 127 (0.49804) -- it never
-// passes, the face can never be hit.  The footprint is the rectangle of texels the face's three texture coordinates span, one texel wider on every side for the bilinear taps
-// and a sixteenth more for the rounding of the interpolated coordinate, wrapped like the texture unit wraps; faces with a footprint of more than 2^18 texels are left to the
-// test.  0 = test as before, 1 = always passes, 2 = never passes.  FH_OPACITY_CLASSES=0 (read at upload): everything 0.
-static int texel_span(float lo, float hi, uint32_t n, int& first, int& count)
-{
-  // texel columns (rows) a fetch at normalised coordinates in [lo, hi] can read: floor(u * n - 0.5) and its successor, before wrapping
-  const double a = (double)lo * n - 0.5, b = (double)hi * n - 0.5;
-  const double slack = 0.0625 + 1e-5 * (std::fabs(a) > std::fabs(b) ? std::fabs(a) : std::fabs(b));
-  const double f0 = std::floor(a - slack), f1 = std::floor(b + slack) + 1.0;
-  if (!(f1 - f0 < (double)n)) { first = 0; count = (int)n; return 1; }
-  first = (int)(((long long)f0 % (long long)n + (long long)n) % (long long)n);
-  count = (int)(f1 - f0) + 1;
-  return 1;
-}
-// 1: every texel of the footprint passes the 0.5 threshold, 2: none does, 0: mixed (or not decided).  uv: n_pts texture coordinates whose bounding rectangle is the footprint
-static uint32_t footprint_class(const uint8_t* rgba8, uint32_t w, uint32_t h, uint32_t channel, const float* decode, const float* uv, int n_pts = 3)
-{
-  if (!rgba8 || w == 0 || h == 0) return 0u;
-  float ulo = uv[0], uhi = uv[0], vlo = uv[1], vhi = uv[1];
-  for (int k = 1; k < n_pts; ++k) { ulo = std::fmin(ulo, uv[2 * k]); uhi = std::fmax(uhi, uv[2 * k]); vlo = std::fmin(vlo, uv[2 * k + 1]); vhi = std::fmax(vhi, uv[2 * k + 1]); }
-  if (!(std::fabs(ulo) < 1e6f) || !(std::fabs(uhi) < 1e6f) || !(std::fabs(vlo) < 1e6f) || !(std::fabs(vhi) < 1e6f)) return 0u;  // (huge or non-finite coordinates: left to the test)
-  int x0, nx, y0, ny;
-  texel_span(ulo, uhi, w, x0, nx);
-  texel_span(vlo, vhi, h, y0, ny);
-  if ((long long)nx * ny > (1ll << 18)) return 0u;
-  bool all_pass = true, none_pass = true;
-  for (int j = 0; j < ny && (all_pass || none_pass); ++j) {
-    const size_t row = (size_t)((y0 + j) % (int)h) * w;
-    for (int i = 0; i < nx; ++i) {
-      const uint8_t b = rgba8[(row + (size_t)((x0 + i) % (int)w)) * 4u + channel];
-      const float v = decode ? decode[b] : (float)b * (1.0f / 255.0f);
-      if (v >= 0.50196f) none_pass = false;       // (byte 128 of a linear channel)
-      else if (v <= 0.49804f) all_pass = false;   // (byte 127)
-      else { all_pass = none_pass = false; }      // an sRGB-decoded value between the two: not decided
-    }
-  }
-  return all_pass ? 1u : (none_pass ? 2u : 0u);
-}
-
-// Rebuild everything derived from the flat scene + transforms: face records, classes, lights.
-int rebuild_device_scene(fh_ctx* ctx)
-{
-  const uint32_t nf = (uint32_t)ctx->h_indices.size() / 3;
-  const uint32_t nv = (uint32_t)ctx->h_vertices.size() / 3;
-  const uint32_t nm = (uint32_t)ctx->h_materials.size();
-  const uint32_t ni = (uint32_t)ctx->h_o2w.size() / 12;
-  // classes
-  std::vector<MaterialDev> mats(nm);
-  ctx->n_classes = 0;
-  for (uint32_t i = 0; i < nm; ++i) {
-    static_assert(sizeof(fh_material) == 180, "fh_material must match the reference Material (shared.h:100-142)");
-    std::memcpy(mats[i].w, &ctx->h_materials[i], 180);
-    const uint32_t lobes = material_lobes(ctx->h_materials[i]);
-    mats[i].lobes = lobes;
-    mats[i].emissive = material_emissive(ctx->h_materials[i]) ? 1u : 0u;
-    {  // alpha: 1 = some fetch of the material's textures can fail the any-hit test; 2 = only a non-finite texture coordinate can (the texture unit returns 0 for it)
-      const int32_t bt = ctx->h_materials[i].base_color_texture_id, at = ctx->h_materials[i].alpha_texture_id;
-      const bool cuts = (bt >= 0 && ctx->h_tex_alpha_cuts[(size_t)bt]) || (at >= 0 && ctx->h_tex_red_cuts[(size_t)at]);
-      mats[i].alpha = cuts ? 1u : ((bt >= 0 || at >= 0) ? 2u : 0u);
-    }
-    uint32_t c = 0;
-    for (; c < ctx->n_classes; ++c)
-      if (ctx->class_lobes[c] == lobes) break;
-    if (c == ctx->n_classes) {
-      if (ctx->n_classes < kMaxClasses) ctx->class_lobes[ctx->n_classes++] = lobes;
-      else { c = kMaxClasses - 1; ctx->class_lobes[c] = L_ALL; }  // overflow: fold into one generic class
-    }
-    mats[i].cls = c;
-  }
-  if (ctx->n_classes == kMaxClasses)  // materials folded into the generic class must see the generic mask
-    for (uint32_t i = 0; i < nm; ++i)
-      if (mats[i].cls == kMaxClasses - 1) ctx->class_lobes[kMaxClasses - 1] |= mats[i].lobes;
-
-  // per-face class bytes, the light list and index validation on the host (cheap integer work); the world-space face records -- the
-  // transform of 3 positions and 3 normals per face -- on the device from the object-space arrays resident there, so that a frame of an
-  // animation (fh_set_transforms) uploads 96 bytes per instance instead of recomputing and re-uploading 112 bytes per face
-  std::vector<uint8_t> cls(nf);
-  std::vector<uint2> meta(nf);
-  std::vector<AreaLightDev> lights;
-  std::vector<uint8_t> alpha_bits(nf, 0);  // bit 0: test the base-colour texture's alpha, bit 1: test the alpha texture's red
-  bool any_alpha = false;
-  bool opacity_classes = true;
-  if (const char* e = getenv("FH_OPACITY_CLASSES")) opacity_classes = e[0] != '0';
-  for (int k = 0; k < 4; ++k) ctx->alpha_face_counts[k] = 0;
-  for (int k = 0; k < 3; ++k) ctx->alpha_cell_counts[k] = 0;
-  float srgb_table[256];
-  for (int i = 0; i < 256; ++i) srgb_table[i] = fht_srgb_to_linear((float)i * (1.0f / 255.0f));
-  for (uint32_t f = 0; f < nf; ++f) {
-    const uint32_t inst = ctx->h_instance_ids.empty() ? 0u : ctx->h_instance_ids[f];
-    if (inst >= ni) return fail(ctx, FH_E_INVALID, "instance id out of range");
-    const uint32_t mid = ctx->h_material_ids[f];
-    if (mid >= nm) return fail(ctx, FH_E_INVALID, "material id out of range");
-    for (int k = 0; k < 3; ++k)
-      if (ctx->h_indices[3ull * f + k] >= nv) return fail(ctx, FH_E_INVALID, "vertex index out of range");
-    meta[f] = make_uint2(mid, inst);
-    bool alpha = mats[mid].alpha == 1u, never = false;
-    if (mats[mid].alpha) {
-      bool wild = false;  // opaque textures: the test can only fail where the interpolated coordinate is NaN or overflows
-      for (int k = 0; k < 3; ++k) {
-        const size_t v = ctx->h_indices[3ull * f + k];
-        if (!(std::fabs(ctx->h_texcoords[2 * v]) < 1e30f) || !(std::fabs(ctx->h_texcoords[2 * v + 1]) < 1e30f)) wild = true;
-      }
-      alpha = alpha || wild;
-      const int32_t bt = ctx->h_materials[mid].base_color_texture_id, at = ctx->h_materials[mid].alpha_texture_id;
-      alpha_bits[f] = (uint8_t)(((bt >= 0 && (wild || ctx->h_tex_alpha_cuts[(size_t)bt])) ? 1u : 0u) | ((at >= 0 && (wild || ctx->h_tex_red_cuts[(size_t)at])) ? 2u : 0u));
-      if (alpha) ctx->alpha_face_counts[0]++;
-      if (alpha && !wild && opacity_classes && !ctx->h_tex_host.empty()) {  // what the face's own footprint says (above)
-        float uv[6];
-        for (int k = 0; k < 3; ++k) { const size_t v = ctx->h_indices[3ull * f + k]; uv[2 * k] = ctx->h_texcoords[2 * v]; uv[2 * k + 1] = ctx->h_texcoords[2 * v + 1]; }
-        uint32_t cb = 1u, ca = 1u;  // a texture the face does not test passes by itself
-        if (alpha_bits[f] & 1u) { const fh_ctx::HostTexture& t = ctx->h_tex_host[(size_t)bt]; cb = footprint_class(t.rgba8.data(), t.width, t.height, 3u, nullptr, uv); }
-        if (alpha_bits[f] & 2u) { const fh_ctx::HostTexture& t = ctx->h_tex_host[(size_t)at]; ca = footprint_class(t.rgba8.data(), t.width, t.height, 0u, t.srgb ? srgb_table : nullptr, uv); }
-        if (cb == 1u && ca == 1u) { alpha = false; alpha_bits[f] = 0; ctx->alpha_face_counts[1]++; }          // always passes: an ordinary opaque face
-        else if (cb == 2u || ca == 2u) { never = true; alpha = false; alpha_bits[f] = 0; ctx->alpha_face_counts[2]++; }  // never passes: no ray can hit it
-      }
-    }
-    cls[f] = (uint8_t)(mats[mid].cls | (mats[mid].emissive ? 0x80u : 0u) | (alpha ? 0x40u : 0u) | (never ? 0x20u : 0u));
-    if (alpha) any_alpha = true;
-    if (mats[mid].emissive) lights.push_back({f, mid});  // renderer.h:388-402, face order
-  }
-  FH_HIP(ctx->d_face_rec.alloc((size_t)kFaceRec * nf));
-  FH_HIP(ctx->d_face_cls.alloc(cls.size()));
-  FH_HIP(ctx->d_materials.alloc(mats.size()));
-  FH_HIP(ctx->d_lights.alloc(lights.size()));
-  FH_HIP(ctx->d_obj_vertices.alloc(ctx->h_vertices.size()));
-  FH_HIP(ctx->d_obj_normals.alloc(ctx->h_normals.size()));
-  FH_HIP(ctx->d_obj_texcoords.alloc(ctx->h_texcoords.size()));
-  FH_HIP(ctx->d_obj_indices.alloc(ctx->h_indices.size()));
-  FH_HIP(ctx->d_face_meta.alloc(meta.size()));
-  FH_HIP(hipMemcpy(ctx->d_face_cls, cls.data(), cls.size(), hipMemcpyHostToDevice));
-  FH_HIP(hipMemcpy(ctx->d_materials, mats.data(), mats.size() * sizeof(MaterialDev), hipMemcpyHostToDevice));
-  if (!lights.empty()) FH_HIP(hipMemcpy(ctx->d_lights, lights.data(), lights.size() * sizeof(AreaLightDev), hipMemcpyHostToDevice));
-  FH_HIP(hipMemcpy(ctx->d_obj_vertices, ctx->h_vertices.data(), ctx->h_vertices.size() * sizeof(float), hipMemcpyHostToDevice));
-  FH_HIP(hipMemcpy(ctx->d_obj_normals, ctx->h_normals.data(), ctx->h_normals.size() * sizeof(float), hipMemcpyHostToDevice));
-  FH_HIP(hipMemcpy(ctx->d_obj_texcoords, ctx->h_texcoords.data(), ctx->h_texcoords.size() * sizeof(float), hipMemcpyHostToDevice));
-  FH_HIP(hipMemcpy(ctx->d_obj_indices, ctx->h_indices.data(), ctx->h_indices.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  FH_HIP(hipMemcpy(ctx->d_face_meta, meta.data(), meta.size() * sizeof(uint2), hipMemcpyHostToDevice));
-  ctx->n_faces = nf;
-  ctx->n_lights = (uint32_t)lights.size();
-  ctx->n_materials = nm;
-  ctx->has_alpha = any_alpha;
-  ctx->alpha_face_counts[3] = ctx->alpha_face_counts[0] - ctx->alpha_face_counts[1] - ctx->alpha_face_counts[2];
-  if (getenv("FH_DEBUG_BVH") && ctx->alpha_face_counts[0])
-    fprintf(stderr, "[alpha] %u faces whose textures can cut: %u always pass, %u never pass, %u keep their any-hit test\n", ctx->alpha_face_counts[0], ctx->alpha_face_counts[1], ctx->alpha_face_counts[2],
-            ctx->alpha_face_counts[3]);
-  ctx->d_alpha_rec.reset();
-  if (any_alpha) {
-    // everything the any-hit test of a face reads, in one 64-byte line: the three texture coordinates and the two textures it may have to look at
-    // ... and, behind them (second 64-byte line), the face's OPACITY MICROMAP: the face cut into 16 x 16 cells of its barycentrics (cell = (floor(16 u), floor(16 v)), the
-    // v1 / v2 weights of a hit), two bits per cell -- 0: test, 1: the test passes everywhere in the cell, 2: nowhere -- decided like the per-face classes above from the texels
-    // the cell can address (the cell's four corners, moved out by 10^-4 for the rounding of the barycentrics and of the cell index).  alpha_pass looks the cell of a candidate up
-    // before anything else (one dword).  Exact: same hits, same images.  FH_OPACITY_MICROMAP=0 (read at upload): all cells 0.
-    bool micromap = opacity_classes;
-    if (const char* e = getenv("FH_OPACITY_MICROMAP")) micromap = micromap && e[0] != '0';
-    unsigned long long cells_total = 0, cells_pass = 0, cells_never = 0;
-    std::vector<uint4> rec(8ull * nf, make_uint4(0u, 0u, 0u, 0u));
-    auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
-    for (uint32_t f = 0; f < nf; ++f) {
-      if (!alpha_bits[f]) continue;
-      const fh_material& m = ctx->h_materials[ctx->h_material_ids[f]];
-      const float* tc = ctx->h_texcoords.data();
-      const size_t v0 = ctx->h_indices[3ull * f], v1 = ctx->h_indices[3ull * f + 1], v2 = ctx->h_indices[3ull * f + 2];
-      rec[8ull * f] = make_uint4(bits(tc[2 * v0]), bits(tc[2 * v0 + 1]), bits(tc[2 * v1]), bits(tc[2 * v1 + 1]));
-      uint32_t flags = alpha_bits[f];
-      if ((flags & 2u) && ctx->h_tex_desc[(size_t)m.alpha_texture_id].srgb) flags |= 4u;
-      rec[8ull * f + 1] = make_uint4(bits(tc[2 * v2]), bits(tc[2 * v2 + 1]), flags, 0u);
-      if (flags & 1u) {
-        const fht_texture& t = ctx->h_tex_desc[(size_t)m.base_color_texture_id];
-        const unsigned long long p = (unsigned long long)(uintptr_t)t.rgba8;
-        rec[8ull * f + 2] = make_uint4((uint32_t)p, (uint32_t)(p >> 32), t.width, t.height);
-      }
-      if (flags & 2u) {
-        const fht_texture& t = ctx->h_tex_desc[(size_t)m.alpha_texture_id];
-        const unsigned long long p = (unsigned long long)(uintptr_t)t.rgba8;
-        rec[8ull * f + 3] = make_uint4((uint32_t)p, (uint32_t)(p >> 32), t.width, t.height);
-      }
-      const bool finite_uv = std::fabs(tc[2 * v0]) < 1e6f && std::fabs(tc[2 * v0 + 1]) < 1e6f && std::fabs(tc[2 * v1]) < 1e6f && std::fabs(tc[2 * v1 + 1]) < 1e6f && std::fabs(tc[2 * v2]) < 1e6f &&
-                             std::fabs(tc[2 * v2 + 1]) < 1e6f;
-      if (micromap && finite_uv && !ctx->h_tex_host.empty()) {
-        uint32_t words[16] = {};
-        const double u0 = tc[2 * v0], w0 = tc[2 * v0 + 1], du1 = (double)tc[2 * v1] - u0, dw1 = (double)tc[2 * v1 + 1] - w0, du2 = (double)tc[2 * v2] - u0, dw2 = (double)tc[2 * v2 + 1] - w0;
-        for (int cj = 0; cj < 16; ++cj)
-          for (int ci = 0; ci + cj <= 16 && ci < 16; ++ci) {  // (cells beyond the hypotenuse are never addressed: they stay 0)
-            // barycentric range of the cell, widened: the last cell of a row / column also takes weights of 1 (and a hair more), the first a hair below 0
-            const double a0 = ci / 16.0 - 1e-4, a1 = (ci == 15 ? 1.0 : (ci + 1) / 16.0) + 1e-4, b0 = cj / 16.0 - 1e-4, b1 = (cj == 15 ? 1.0 : (cj + 1) / 16.0) + 1e-4;
-            const double cb[4][2] = {{a0, b0}, {a1, b0}, {a0, b1}, {a1, b1}};
-            float uv[8];
-            for (int k = 0; k < 4; ++k) { uv[2 * k] = (float)(u0 + cb[k][0] * du1 + cb[k][1] * du2); uv[2 * k + 1] = (float)(w0 + cb[k][0] * dw1 + cb[k][1] * dw2); }
-            uint32_t cb_ = 1u, ca_ = 1u;
-            if (flags & 1u) { const fh_ctx::HostTexture& t = ctx->h_tex_host[(size_t)m.base_color_texture_id]; cb_ = footprint_class(t.rgba8.data(), t.width, t.height, 3u, nullptr, uv, 4); }
-            if (flags & 2u) { const fh_ctx::HostTexture& t = ctx->h_tex_host[(size_t)m.alpha_texture_id]; ca_ = footprint_class(t.rgba8.data(), t.width, t.height, 0u, t.srgb ? srgb_table : nullptr, uv, 4); }
-            const uint32_t st = (cb_ == 1u && ca_ == 1u) ? 1u : ((cb_ == 2u || ca_ == 2u) ? 2u : 0u);
-            const int cell = cj * 16 + ci;
-            words[cell >> 4] |= st << (2 * (cell & 15));
-            ++cells_total; cells_pass += st == 1u; cells_never += st == 2u;
-          }
-        for (int k = 0; k < 4; ++k) rec[8ull * f + 4 + k] = make_uint4(words[4 * k], words[4 * k + 1], words[4 * k + 2], words[4 * k + 3]);
-      }
-    }
-    ctx->alpha_cell_counts[0] = cells_total; ctx->alpha_cell_counts[1] = cells_pass; ctx->alpha_cell_counts[2] = cells_never;
-    if (getenv("FH_DEBUG_BVH") && cells_total)
-      fprintf(stderr, "[alpha] micromap: %llu cells of the faces that keep their test: %.1f %% always pass, %.1f %% never pass\n", cells_total, 100.0 * cells_pass / cells_total, 100.0 * cells_never / cells_total);
-    FH_HIP(ctx->d_alpha_rec.alloc(rec.size()));
-    FH_HIP(hipMemcpy(ctx->d_alpha_rec, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice));
-  }
-  // (the host copies of the textures that can cut were needed for the classes and the micromaps above only: every upload brings its textures again)
-  for (fh_ctx::HostTexture& t : ctx->h_tex_host) std::vector<uint8_t>().swap(t.rgba8);
-  ctx->refit_ok = false;  // new topology: the next build is a full one
-  return transform_faces(ctx);
-}
-
-// texels of all textures in one device blob + descriptors + the 256-entry sRGB table (cwl/texture.h:13-75 per texture)
-int upload_textures(fh_ctx* ctx, uint32_t n, const fh_texture_desc* descs)
-{
-  ctx->d_texels.reset();
-  ctx->d_textures.reset();
-  ctx->n_textures = n;
-  if (!ctx->d_srgb_lut) {
-    float lut[256];
-    for (int i = 0; i < 256; ++i) lut[i] = fht_srgb_to_linear((float)i * (1.0f / 255.0f));
-    FH_HIP(ctx->d_srgb_lut.alloc(256));
-    FH_HIP(hipMemcpy(ctx->d_srgb_lut, lut, sizeof lut, hipMemcpyHostToDevice));
-  }
-  ctx->h_tex_alpha_cuts.assign(n, 0);
-  ctx->h_tex_red_cuts.assign(n, 0);
-  ctx->h_tex_desc.clear();
-  ctx->h_tex_host.clear();
-  if (n == 0) return FH_OK;
-  size_t total = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!descs[i].rgba8 || descs[i].width == 0 || descs[i].height == 0) return fail(ctx, FH_E_INVALID, "fh_scene_upload: empty texture");
-    total += (size_t)descs[i].width * descs[i].height * 4;
-    // The any-hit programs discard a hit when the filtered alpha (base-colour texture) or red (alpha texture) is below 0.5 (pt.cu:545-678).  A filtered
-    // value is a convex combination of texel values (weights are multiples of 2^-16 that sum to exactly 1), so a texture whose every texel decodes to
-    // >= 0.501 can never discard a hit: faces that only reference such textures need no any-hit test at all (most base-colour maps are opaque).
-    const uint8_t* px = descs[i].rgba8;
-    const size_t n_px = (size_t)descs[i].width * descs[i].height;
-    uint8_t min_a = 255, min_r = 255;
-    for (size_t k = 0; k < n_px; ++k) { min_r = px[4 * k] < min_r ? px[4 * k] : min_r; min_a = px[4 * k + 3] < min_a ? px[4 * k + 3] : min_a; }
-    const float red = descs[i].srgb ? fht_srgb_to_linear((float)min_r * (1.0f / 255.0f)) : (float)min_r * (1.0f / 255.0f);
-    ctx->h_tex_alpha_cuts[i] = (float)min_a * (1.0f / 255.0f) < 0.501f ? 1 : 0;
-    ctx->h_tex_red_cuts[i] = red < 0.501f ? 1 : 0;
-  }
-  // host copies of the textures that can cut: what the per-face opacity classes are decided from (rebuild_device_scene)
-  ctx->h_tex_host.resize(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    fh_ctx::HostTexture& t = ctx->h_tex_host[i];
-    t.width = descs[i].width; t.height = descs[i].height; t.srgb = descs[i].srgb ? 1u : 0u;
-    if (ctx->h_tex_alpha_cuts[i] || ctx->h_tex_red_cuts[i]) t.rgba8.assign(descs[i].rgba8, descs[i].rgba8 + (size_t)descs[i].width * descs[i].height * 4);
-  }
-  FH_HIP(ctx->d_texels.alloc(total));
-  std::vector<fht_texture> t(n);
-  size_t off = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const size_t bytes = (size_t)descs[i].width * descs[i].height * 4;
-    FH_HIP(hipMemcpy(ctx->d_texels + off, descs[i].rgba8, bytes, hipMemcpyHostToDevice));
-    t[i] = fht_texture{ctx->d_texels + off, nullptr, descs[i].width, descs[i].height, descs[i].srgb ? 1u : 0u};
-    off += bytes;
-  }
-  FH_HIP(ctx->d_textures.alloc(n));
-  FH_HIP(hipMemcpy(ctx->d_textures, t.data(), n * sizeof(fht_texture), hipMemcpyHostToDevice));
-  ctx->h_tex_desc = t;
-  return FH_OK;
-}
 
 // the pixels of rank `rank` of `world` in the order the library packs them: tiles t with t % world == rank, row-major tile order; inside a tile 8 x 8 blocks, row-major,
 // and row-major inside a block -- so the 64 lanes of a wave of k_generate (64 consecutive list entries) hold a compact 8 x 8 patch of the image instead of two rows of 32:
@@ -492,10 +138,6 @@ __global__ void k_unpack_all(ShardSources src, const uint32_t* all_owned, uint32
 }  // namespace fh
 
 using namespace fh;
-
-#define CTX_CHECK(ctx)                      \
-  if (!(ctx)) return FH_E_INVALID;          \
-  if (hipSetDevice((ctx)->device) != hipSuccess) return fh::fail(ctx, FH_E_HIP, "hipSetDevice failed")
 
 namespace fh {
 // render.hip: pool_ensure -- path record 64, radiance 16, identity 8, flags 4, first-hit AOVs 64, a 48-byte place per kind of secondary ray, the pending
@@ -711,67 +353,6 @@ int fh_set_tail_depth(fh_ctx* ctx, uint32_t depth)
   CTX_CHECK(ctx);
   ctx->tail_depth = depth;  // 0 = adaptive; bounce 0 always runs as wavefront kernels (it writes the first-hit AOVs)
   return FH_OK;
-}
-
-int fh_scene_upload(fh_ctx* ctx, const fh_scene_desc* s)
-{
-  FH_GROUP_EACH(ctx, kGroupCallUpload, fh_scene_upload(m_, s));
-  CTX_CHECK(ctx);
-  if (!s || !s->vertices || !s->normals || !s->texcoords || !s->indices || !s->material_ids || !s->materials || s->n_materials == 0)
-    return fail(ctx, FH_E_INVALID, "fh_scene_upload: missing arrays");
-  for (uint32_t i = 0; i < s->n_materials; ++i) {
-    const fh_material& m = s->materials[i];
-    const int32_t ids[11] = {m.base_color_texture_id, m.specular_color_texture_id, m.specular_roughness_texture_id, m.metalness_texture_id, m.metallic_roughness_texture_id, m.coat_texture_id,
-                             m.coat_roughness_texture_id, m.emission_texture_id, m.heightmap_texture_id, m.normalmap_texture_id, m.alpha_texture_id};
-    for (int32_t id : ids)
-      if (id < -1 || id >= (int32_t)s->n_textures) return fail(ctx, FH_E_INVALID, "fh_scene_upload: material references a texture id outside [0, n_textures)");
-  }
-  if (s->n_textures && !s->textures) return fail(ctx, FH_E_INVALID, "fh_scene_upload: n_textures > 0 but textures == NULL");
-  {
-    const int rc = upload_textures(ctx, s->n_textures, s->textures);
-    if (rc) return rc;
-  }
-  ctx->h_vertices.assign(s->vertices, s->vertices + 3ull * s->n_vertices);
-  ctx->h_normals.assign(s->normals, s->normals + 3ull * s->n_vertices);
-  ctx->h_texcoords.assign(s->texcoords, s->texcoords + 2ull * s->n_vertices);
-  ctx->h_indices.assign(s->indices, s->indices + 3ull * s->n_faces);
-  ctx->h_material_ids.assign(s->material_ids, s->material_ids + s->n_faces);
-  if (s->instance_ids) ctx->h_instance_ids.assign(s->instance_ids, s->instance_ids + s->n_faces);
-  else ctx->h_instance_ids.clear();
-  ctx->h_materials.assign(s->materials, s->materials + s->n_materials);
-  if (s->n_instances && s->object_to_world && s->world_to_object) {
-    ctx->h_o2w.assign(s->object_to_world, s->object_to_world + 12ull * s->n_instances);
-    ctx->h_w2o.assign(s->world_to_object, s->world_to_object + 12ull * s->n_instances);
-  } else {
-    ctx->h_o2w.assign(kIdentity12, kIdentity12 + 12);
-    ctx->h_w2o.assign(kIdentity12, kIdentity12 + 12);
-  }
-  const int rc = rebuild_device_scene(ctx);
-  if (rc) return rc;
-  ctx->scene_loaded = true;
-  ctx->hist_o2w.clear(); ctx->hist_w2o.clear();  // (fh_set_denoise_motion: another scene's instances are not these)
-  ctx->builder_choice = 0;  // new geometry: let the next build choose its builder again
-  return FH_OK;
-}
-
-int fh_set_transforms(fh_ctx* ctx, uint32_t n, const float* o2w, const float* w2o)
-{
-  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_transforms(m_, n, o2w, w2o));
-  CTX_CHECK(ctx);
-  if (!ctx->scene_loaded || !o2w || !w2o || n == 0) return fail(ctx, FH_E_INVALID, "fh_set_transforms: no scene / null arrays");
-  // a frame of an animation that only moves the camera (rtcamp8's scene) leaves every instance where it was: keep the world-space
-  // geometry and the acceleration structure (fh_bvh_build returns at once while bvh_valid holds)
-  if (ctx->h_o2w.size() == 12ull * n && ctx->h_w2o.size() == 12ull * n && std::memcmp(ctx->h_o2w.data(), o2w, 48ull * n) == 0 &&
-      std::memcmp(ctx->h_w2o.data(), w2o, 48ull * n) == 0)
-    return FH_OK;
-  (void)hipStreamSynchronize(ctx->stream);
-  for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(ctx->aux_stream[k]);  // no pass may still be reading the face records
-  uint32_t max_inst = 0;
-  for (uint32_t i : ctx->h_instance_ids) max_inst = i > max_inst ? i : max_inst;
-  if (max_inst >= n) return fail(ctx, FH_E_INVALID, "fh_set_transforms: fewer transforms than the scene has instances");
-  ctx->h_o2w.assign(o2w, o2w + 12ull * n);
-  ctx->h_w2o.assign(w2o, w2o + 12ull * n);
-  return transform_faces(ctx);  // topology, classes and lights are unchanged: only the world-space records move (and the BVH is refitted)
 }
 
 int fh_bvh_build(fh_ctx* ctx)

@@ -55,11 +55,7 @@ struct fh_ctx {
   fh::DeviceBuffer<float4> d_o2w;       // 3 rows per instance
   fh::DeviceBuffer<float4> d_w2o;
   // textures (renderer.h:372-386): one device blob of texels + descriptors + the sRGB table
-  // per texture: can a filtered fetch of its alpha channel / of its red channel come out below the any-hit threshold 0.5 (upload_textures)?
-  std::vector<uint8_t> h_tex_alpha_cuts, h_tex_red_cuts;
-  std::vector<fht_texture> h_tex_desc;  // the descriptors as uploaded (device pointers)
-  struct HostTexture { uint32_t width = 0, height = 0, srgb = 0; std::vector<uint8_t> rgba8; };
-  std::vector<HostTexture> h_tex_host;  // texels of the textures that can cut, kept on the host: per-face opacity classes (capi.hip: footprint_class)
+  // (which textures can cut, and the opacity classes and micromaps decided from their texels, are the upload's plan: scene_plan_host.h)
   unsigned long long alpha_cell_counts[3] = {0, 0, 0};  // micromap cells of the faces that keep their test; of them: always pass, never pass (fh_alpha_cell_counts)
   uint32_t alpha_face_counts[4] = {0, 0, 0, 0};  // faces whose textures can cut; of them: always pass, never pass, still tested (fh_alpha_face_counts)
   fh::DeviceBuffer<uint4> d_alpha_rec;         // 8 x 16 bytes per face when the scene has cut-outs: what the any-hit test of that face reads (4) and the face's opacity micromap (4) (fh_trace.h: alpha_pass)
@@ -304,6 +300,10 @@ int fail(fh_ctx* ctx, int code, const std::string& msg);
     hipError_t e_ = (call);                                                                                            \
     if (e_ != hipSuccess) return fh::fail(ctx, FH_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
   } while (0)
+// the top of an entry point that takes a context: the context's device is the current one from here on
+#define CTX_CHECK(ctx)                      \
+  if (!(ctx)) return FH_E_INVALID;          \
+  if (hipSetDevice((ctx)->device) != hipSuccess) return fh::fail(ctx, FH_E_HIP, "hipSetDevice failed")
 
 // group dispatch at the top of the entry points (group.hip).  A plain context pays the one branch.
 #define FH_GROUP(ctx, call) \

@@ -14,10 +14,9 @@
 #pragma once
 #include "fh_device.h"
 #include "fh_sampler.h"
+#include "scene_plan_host.h"  // the lobe masks L_COAT .. L_ALL: the host decides which lobes a material can enable (material_lobes)
 
 namespace fh {
-
-enum : uint32_t { L_COAT = 1, L_METAL = 2, L_SPEC = 4, L_TRANS = 8, L_SHEEN = 16, L_DT = 32, L_DIFF = 64, L_ALL = 127 };
 
 struct MatParams {  // the reference's ShadingParams (shared.h:173-199) after fill_shading_params
   float diffuse; f3 base_color; float diffuse_roughness;

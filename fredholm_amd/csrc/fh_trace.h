@@ -114,10 +114,10 @@ FH_D float4 tex_rgba(const SceneDev& sc, int id, float u, float v)
 }
 __device__ __attribute__((noinline)) bool alpha_pass(const SceneDev& sc, uint32_t prim, float bu, float bv)
 {
-  // one 64-byte record per face (capi.hip: rebuild_device_scene): texture coordinates of the three vertices + the textures that can actually cut
+  // one 64-byte record per face (scene_plan_host.h: plan_alpha_records): texture coordinates of the three vertices + the textures that can actually cut
   // (a texture whose every texel is opaque is not listed: a filtered fetch of it cannot come out below 0.5)
   const uint4* r = sc.alpha_rec + 8 * (size_t)prim;
-  {  // the face's opacity micromap (capi.hip: rebuild_device_scene): 16 x 16 cells of the hit's barycentrics, two bits each -- decided at upload for every point of the cell
+  {  // the face's opacity micromap (scene_plan_host.h: micromap_words): 16 x 16 cells of the hit's barycentrics, two bits each -- decided at upload for every point of the cell
     const uint32_t ci = (uint32_t)fminf(fmaxf(bu, 0.0f) * 16.0f, 15.0f), cj = (uint32_t)fminf(fmaxf(bv, 0.0f) * 16.0f, 15.0f);
     const uint32_t cell = cj * 16u + ci;
     const uint32_t st = (((const uint32_t*)(r + 4))[cell >> 4] >> (2u * (cell & 15u))) & 3u;

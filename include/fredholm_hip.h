@@ -206,7 +206,9 @@ int fh_path_pool_allocated(fh_ctx* ctx, uint64_t* bytes, uint64_t* paths);
  * paths survived in earlier passes; a value >= max_depth disables the fused tail. */
 int fh_set_tail_depth(fh_ctx* ctx, uint32_t depth);
 
-/* -- scene: Renderer::load_scene upload + AreaLight extraction (renderer.h:354-432) */
+/* -- scene: Renderer::load_scene upload + AreaLight extraction (renderer.h:354-432).  FH_E_INVALID (missing arrays, a texture id outside the
+ * textures, an empty texture, an instance id, material id or vertex index out of range) is found from the arguments alone, before anything is
+ * changed: the context keeps the scene, the tree and the counters it had.  After FH_E_HIP the context has no scene until an upload succeeds. */
 int fh_scene_upload(fh_ctx* ctx, const fh_scene_desc* scene);
 /* Renderer::build_gas + build_ias (renderer.h:434-552): on-device LBVH build + wide-BVH collapse */
 int fh_bvh_build(fh_ctx* ctx);

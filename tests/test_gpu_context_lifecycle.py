@@ -82,6 +82,7 @@ def test_a_context_with_everything_on_gives_back_all_it_took():
         r.set_auto_exposure()
         r.post_process(p["beauty"], hi.ptr, tmp.ptr, w, h, F.PostProcessParams(use_bloom=True), out.ptr)
         packed = DeviceBuffer(r, 16 * px)
+        packed.clear()  # (fh_malloc does not: without this the frame below is whatever a freed buffer held, 0xffffffff words included)
         for rank in (0, 1):
             r.unpack_shard(rank, 2, packed.ptr, 4, out.ptr)
         r.wait_for_completion()

@@ -520,7 +520,7 @@ def test_exotic_lobes_render_matches_checker(oracle):
 
 def test_full_metal_seen_from_behind_still_transmits(oracle):
     """bsdf.cu:56-62 zeroes metalness / specular / sheen / diffuse on a back-face hit, so an open metalness = 1 surface with transmission
-    (or thin-walled subsurface) refracts when seen from behind: the host-side lobe mask must keep those two lobes (capi.hip: material_lobes)"""
+    (or thin-walled subsurface) refracts when seen from behind: the host-side lobe mask must keep those two lobes (scene_plan_host.h: material_lobes)"""
     base = scenes.cornell_box()
     nm = base["materials"].shape[0]
     mats = default_materials(nm + 2)
@@ -818,7 +818,7 @@ def test_moving_instances_refit_the_tree_and_match_checker_and_rebuild(oracle, m
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_random_materials_textures_and_lights_match_checker(oracle, seed):
     """fuzz over what the hand-made scenes fix: every material parameter drawn at random -- each lobe switch at 0, at 1 and in between, so that
-    the host-side lobe masks (capi.hip: material_lobes) meet combinations nobody wrote a scene for (the round-1 advisor found one: a full metal
+    the host-side lobe masks (scene_plan_host.h: material_lobes) meet combinations nobody wrote a scene for (the round-1 advisor found one: a full metal
     seen from behind) --, random textures on random slots, open geometry seen from both sides, instances with random transforms, a random
     environment (constant / Hosek / image) and light set.  All six AOVs bit-identical to the checker."""
     rng = np.random.default_rng(1000 + seed)
@@ -1514,6 +1514,123 @@ def test_wild_texture_coordinates_on_opaque_textures_still_take_the_any_hit_test
     with np.errstate(all="ignore"):  # texcoord AOVs carry the wild values
         for name in F.RenderLayer.NAMES:
             _assert_image_parity(gpu[name], ref[name])
+
+
+def _nine_masks_scene():
+    """twelve quads in a row (24 faces), ten materials: nine distinct lobe masks -- one more than the library has shading classes, so the ninth folds into the generic
+    class -- and an emitter"""
+    m = default_materials(10)
+    m["specular"][0] = 0.0                              # diffuse
+    m["coat"][2] = 1.0                                  # coat + specular + diffuse
+    m["metalness"][3] = 0.5                             # metal + specular + diffuse
+    m["metalness"][4] = 1.0                             # a full metal: metal alone
+    m["transmission"][5] = 1.0
+    m["sheen"][6] = 1.0
+    m["subsurface"][7] = 1.0; m["thin_walled"][7] = 1.0
+    m["coat"][8] = 1.0; m["transmission"][8] = 1.0      # the ninth mask
+    m["emission"][9] = 1.0; m["emission_color"][9] = (5.0, 5.0, 5.0)
+    v, tri = [], []
+    for q in range(12):
+        x0, b = -1.2 + 0.2 * q, 4 * q
+        v.extend([[x0, 0.0, 0.0], [x0 + 0.18, 0.0, 0.0], [x0 + 0.18, 0.5, 0.0], [x0, 0.5, 0.0]])
+        tri.extend([[b, b + 1, b + 2], [b, b + 2, b + 3]])
+    return {"vertices": np.asarray(v, np.float32), "normals": np.tile(np.array([[0.0, 0.0, 1.0]], np.float32), (48, 1)),
+            "texcoords": np.tile(np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32), (12, 1)), "indices": np.asarray(tri, np.uint32),
+            "material_ids": (np.arange(24, dtype=np.uint32) // 2) % 10, "materials": m}
+
+
+def _scene_readbacks(r, nf):
+    """what fh_scene_upload left in the context and on the device, through the read-back entry points; the two pointer words of each texture slot of the any-hit
+    records (fh_kat_alpha_records: words 8, 9 and 12, 13 of a face whose flags, word 6, name the slot) as the offset from the lowest pointer in the table"""
+    rec = _alpha_records(r, nf).astype(np.uint64)
+    named = np.stack([(rec[:, 6] & 1) != 0, (rec[:, 6] & 2) != 0], axis=1)
+    ptr = np.stack([rec[:, 8] | (rec[:, 9] << np.uint64(32)), rec[:, 12] | (rec[:, 13] << np.uint64(32))], axis=1)
+    if named.any():
+        ptr = np.where(named, ptr - ptr[named].min(), ptr)
+    for slot in (0, 1):
+        rec[:, 8 + 4 * slot], rec[:, 9 + 4 * slot] = ptr[:, slot] & np.uint64(0xFFFFFFFF), ptr[:, slot] >> np.uint64(32)
+    return {"face_classes": _face_classes(r, nf), "alpha_records": rec.astype(np.uint32), "alpha_face_counts": np.asarray(r.alpha_face_counts(), np.uint32),
+            "alpha_cell_counts": np.asarray(r.alpha_cell_counts(), np.uint64), "n_lights": np.asarray([r.n_lights()], np.uint32)}
+
+
+UPLOAD_SCENES = {"fence": _fence_scene, "nine_masks": _nine_masks_scene}
+
+
+@pytest.mark.parametrize("name", sorted(UPLOAD_SCENES))
+def test_scene_upload_leaves_what_the_unsplit_upload_left(name, monkeypatch):
+    """fh_scene_upload as a host-only plan (csrc/scene_plan_host.h) and upload steps (csrc/scene.hip) leaves the same class bytes, any-hit records with their micromaps,
+    counters and lights as the one function it was split from: tests/golden/scene_upload_parent.npz holds these read-backs as the library of the commit before the
+    split gave them on the GPU"""
+    monkeypatch.delenv("FH_OPACITY_CLASSES", raising=False)
+    monkeypatch.delenv("FH_OPACITY_MICROMAP", raising=False)
+    sc = UPLOAD_SCENES[name]()
+    nf = sc["indices"].shape[0]
+    r = F.Renderer(0)
+    r.load_scene(sc)
+    got = _scene_readbacks(r, nf)
+    r.close()
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scene_upload_parent.npz"))
+    for key, value in got.items():
+        assert value.dtype == want[f"{name}.{key}"].dtype and np.array_equal(value, want[f"{name}.{key}"]), key
+    if name == "fence":  # the fixture is about something: faces of every opacity class, micromaps, both texture slots
+        assert nf >= 400 and got["alpha_face_counts"].min() > 0 and got["alpha_cell_counts"].min() > 0 and got["alpha_records"][:, 16:].any()
+        assert {int(f) & 3 for f in got["alpha_records"][:, 6]} == {0, 1, 2} and got["alpha_records"][:, [8, 12]].max() > 0
+    else:  # eight classes, the last one generic and shared by two materials; two emissive faces
+        assert nf == 24 and (got["face_classes"] & 0x1F).max() == 7 and int(((got["face_classes"] & 0x1F) == 7).sum()) == 4 and got["n_lights"][0] == 2
+        assert int((got["face_classes"] & 0x80 != 0).sum()) == 2 and not got["alpha_records"].any()
+
+
+def test_refused_uploads_leave_the_context_as_it_was():
+    """Every refusal of fh_scene_upload's arguments comes before the context is touched: the scene, its textures, its tree and its counters stay, and the next render
+    gives the bits it gave before.  The last case is the one that used to leave a context behind whose materials pointed past a shorter texture table."""
+    sc = scenes.textured_cornell_box()
+    nf, nv, nm = sc["indices"].shape[0], sc["vertices"].shape[0], sc["materials"].shape[0]
+    r = F.Renderer(0)
+    r.load_scene(sc)
+    r.build_ias()
+    w, h = 48, 36
+    r.set_resolution(w, h)
+    cam = F.Camera(**scenes.CORNELL_CAMERA)
+    L = F.RenderLayer(r, w, h)
+
+    def frame():
+        r.init_render_states()
+        L.clear()
+        r.render(cam, (0.0, 0.0, 0.0), L, 2, 3)
+        r.wait_for_completion()
+        return {n: L.download(n) for n in F.RenderLayer.NAMES}
+
+    before, counts, lights = frame(), r.alpha_face_counts(), r.n_lights()
+    assert counts[0] > 0 and np.isfinite(before["beauty"]).all() and before["beauty"][..., :3].mean() > 0.01
+
+    def changed(**kw):
+        return dict(sc, **{k: np.array(v, copy=True) if isinstance(v, np.ndarray) else v for k, v in kw.items()})
+
+    bad_vertex = changed(indices=sc["indices"])
+    bad_vertex["indices"][nf // 2, 1] = nv
+    bad_material = changed(material_ids=sc["material_ids"])
+    bad_material["material_ids"][3] = nm
+    one = np.array([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]], np.float32)
+    bad_instance = changed(instance_ids=np.zeros(nf, np.uint32), object_to_world=one, world_to_object=one)
+    bad_instance["instance_ids"][nf - 2] = 1
+    empty_texture = changed(textures=[dict(t) for t in sc["textures"]])
+    empty_texture["textures"][2]["rgba8"] = np.zeros((4, 0, 4), np.uint8)
+    # one texture fewer (the last one, which only the last material's alpha slot names), and a bad index in the last face
+    fewer = changed(textures=list(sc["textures"][:-1]), materials=sc["materials"], indices=sc["indices"])
+    assert fewer["materials"]["alpha_texture_id"][nm - 1] == len(sc["textures"]) - 1
+    fewer["materials"]["alpha_texture_id"][nm - 1] = -1
+    fewer["indices"][nf - 1, 2] = nv
+    cases = [(bad_vertex, "vertex index out of range"), (bad_material, "material id out of range"), (bad_instance, "instance id out of range"),
+             (empty_texture, "fh_scene_upload: empty texture"), (fewer, "vertex index out of range")]
+    for bad, message in cases:
+        with pytest.raises(F.FredholmError) as e:
+            r.load_scene(bad)
+        assert str(e.value) == f"fh_scene_upload failed (-1): {message}"  # FH_E_INVALID
+        assert r.alpha_face_counts() == counts and r.n_lights() == lights
+        after = frame()
+        for name in F.RenderLayer.NAMES:
+            assert _same(after[name], before[name]), (message, name)
+    r.close()
 
 
 def test_image_based_lighting_matches_checker(oracle):
