@@ -770,6 +770,13 @@ int fh_sync(fh_ctx* ctx)
       return fail(ctx, FH_E_HIP, "sky-pixel split: " + std::to_string(violations) + " pixels classified as sky have rays that reach the scene bounds (set FH_SKY_SPLIT=0 and report)");
     }
   }
+#if defined(FH_CHECK_DIV_RANGES)
+  {
+    uint64_t n = 0;  // (every call on this device since the library was loaded, whichever context made it: the test reads it from a context of its own)
+    if (const int rc = div_range_violations_read(ctx, &n)) return rc;
+    ctx->stats.div_range_violations = n;
+  }
+#endif
   if (ctx->flags & FH_FLAG_TIME_KERNELS) {  // shader cycles and 100 MHz ticks the waves of the streaming traversal kernels have summed up (fh_device.h: ClockStamp)
     unsigned long long c[4];
     FH_HIP(hipMemcpy(c, ctx->d_trace_counters + 27, sizeof c, hipMemcpyDeviceToHost));

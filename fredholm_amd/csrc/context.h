@@ -345,6 +345,9 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity);   // render.hip
 uint64_t pool_bytes_per_path(const fh_ctx* ctx);            // capi.hip
 void pool_release(fh_ctx* ctx);
 int kernel_info(fh_ctx* ctx, int which, uint32_t out[6]);   // render.hip
+#if defined(FH_CHECK_DIV_RANGES)
+int div_range_violations_read(fh_ctx* ctx, uint64_t* n);  // render.hip: the counter of its kernels (fh_vec.h: div_r), which belongs to the device's code object, not to a context
+#endif
 int post_process_submit(fh_ctx* ctx, const float* in, float* hi, float* tmp, int w, int h, const fh_post_params* pp, float* out);  // post.hip
 // post.hip, auto-exposure (arguments checked by the caller): the switch with its device state; metering + resolve of one image; frames = 0; synchronising read-backs
 int auto_exposure_set(fh_ctx* ctx, const fh_auto_exposure_params* params);

@@ -205,7 +205,8 @@ FH_HD f2 concentric_disk(f2 u)
   if (u0.x == 0.0f && u0.y == 0.0f) return mk2(0.0f, 0.0f);
   const bool xdom = fabsf(u0.x) > fabsf(u0.y);
   const float r = xdom ? u0.x : u0.y;
-  const float theta = xdom ? 0.25f * kPi * u0.y / u0.x : 0.5f * kPi - 0.25f * kPi * u0.x / u0.y;
+  // u is a draw in [0, 1]: a component of 2u - 1 is +0 or at least 2^-24 (2u - 1 is exact for u >= 1/4) and at most 1; the divisor is the larger of the two, and both are not zero
+  const float theta = xdom ? div_r_nofix<-26, 0, -24, 0>(0.25f * kPi * u0.y, u0.x) : 0.5f * kPi - div_r_nofix<-26, 0, -24, 0>(0.25f * kPi * u0.x, u0.y);
   float s, c;
   fhe_sincos(theta, &s, &c);
   return mk2(r * c, r * s);

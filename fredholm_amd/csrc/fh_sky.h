@@ -62,8 +62,12 @@ FH_HD f3 hosek_radiance_form(const HosekSky& st, f3 sun_dir, float intensity, f3
   auto channel = [&](int ch) {
     const float* c = st.cfg[ch];
     const float expM = fhe_exp(c[4] * gamma);
-    const float mieM = (1.0f + cg * cg) / fhe_pow1p5(1.0f + c[8] * c[8] - 2.0f * c[8] * cg);  // arhosek.cu:109-110: pow(x, 1.5)
-    return (1.0f + c[0] * fhe_exp(c[1] / (ct + 0.01f))) * (c[2] + c[3] * expM + c[5] * rayM + c[6] * mieM + c[7] * zenith) * st.rad[ch];
+    // Short divisions (fh_vec.h: div_r; the claims are binary exponents), both with the fix-up: either divisor can be zero.  The coefficients are blends of the model's
+    // table, of the order of one: |c[1]| in [2^-40, 2^20], |c[8]| <= 2^9.
+    // mie: 1 <= 1 + cg^2 <= 2; x = 1 + c8^2 - 2 c8 cg is zero (or below: NaN) or, a difference of floats of at least 1, at least 2^-24: x^1.5 in [2^-36, 2^30]
+    const float mieM = div_r<0, 1, -40, 30>(1.0f + cg * cg, fhe_pow1p5(1.0f + c[8] * c[8] - 2.0f * c[8] * cg));  // arhosek.cu:109-110: pow(x, 1.5)
+    // horizon: |ct| <= 1, and ct + 0.01 is zero or a multiple of ulp(0.01) = 2^-30
+    return (1.0f + c[0] * fhe_exp(div_r<-40, 20, -31, 1>(c[1], ct + 0.01f))) * (c[2] + c[3] * expM + c[5] * rayM + c[6] * mieM + c[7] * zenith) * st.rad[ch];
   };
   if constexpr (ROLLED) {
     float r = 0.0f, g = 0.0f, b = 0.0f;  // (selects, not an indexed array: that would live in scratch memory)

@@ -31,6 +31,13 @@ FH_D f3 safe_reciprocal(f3 d)
              1.0f / (fabsf(d.z) < 1e-20f ? copysignf(1e-20f, d.z) : d.z));
 }
 
+// the same for a camera ray: its direction is a unit vector through the camera's transform (render.hip: camera_ray), so a component is 1e-20 > 2^-67 at least and 3 x 2^20 at most
+FH_D f3 safe_reciprocal_r(f3 d)
+{
+  return mk3(div_r<0, 0, -67, 22>(1.0f, fabsf(d.x) < 1e-20f ? copysignf(1e-20f, d.x) : d.x), div_r<0, 0, -67, 22>(1.0f, fabsf(d.y) < 1e-20f ? copysignf(1e-20f, d.y) : d.y),
+             div_r<0, 0, -67, 22>(1.0f, fabsf(d.z) < 1e-20f ? copysignf(1e-20f, d.z) : d.z));
+}
+
 FH_D RayPre ray_prepare(f3 o, f3 d)
 {
   RayPre r;

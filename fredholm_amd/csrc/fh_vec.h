@@ -48,10 +48,54 @@ FH_HD f3& operator*=(f3& a, f3 b) { a = a * b; return a; }
 // correctly rounded square root (include/fh_elementary.h: the short device sequence, bit-identical to sqrtf)
 FH_HD float sqrt_cr(float x) { return fhe_sqrt(x); }
 
+// ---- divisions at sites whose operand ranges are argued where they stand (include/fh_elementary.h: fhe_div and its conditions).  The claim is part of the call:
+// |a| in {0} u [2^ALO, 2^AHI] and |b| in [2^BLO, 2^BHI], and it must imply the conditions -- else the site does not compile.
+//   div_r       ending (a): zeros, infinities and NaN on either side are answered by the hardware's fix-up as IEEE answers them and are outside the claim
+//   div_r_nofix ending (b): the claim also says a is +0 or in range (never -0, infinite or NaN) and b is in range (never zero, infinite or NaN)
+// -DFH_CHECK_DIV_RANGES (tools/build_variant_all.sh; never in the default build) counts every call whose operands leave the claim.  The counter is per translation
+// unit; render.hip's, which holds every kernel of fh_render, is what fh_stats.div_range_violations reports (tests/test_gpu_div_ranges.py).
+#if defined(FH_CHECK_DIV_RANGES)
+static __device__ unsigned int fh_div_range_violations;
+#endif
+template <int ALO, int AHI, int BLO, int BHI>
+constexpr bool div_claim_ok()
+{
+  return ALO <= AHI && BLO <= BHI && ALO >= -100 && BLO >= -126 && BHI <= 126 && ALO - BHI >= -124 && AHI - BLO <= 125;  // (|a / b| in [2^(ALO-BHI), 2^(AHI-BLO)], a margin of one binade inside the conditions)
+}
+template <int LO, int HI>
+FH_HD bool in_pow2_range(float x)
+{
+  const uint32_t m = fhe_f2u(x) & 0x7fffffffu;
+  return m >= ((uint32_t)(LO + 127) << 23) && m <= ((uint32_t)(HI + 127) << 23);
+}
+template <int ALO, int AHI, int BLO, int BHI>
+FH_HD float div_r(float a, float b)
+{
+  static_assert(div_claim_ok<ALO, AHI, BLO, BHI>(), "the claimed ranges do not imply fhe_div's conditions");
+#if defined(FH_CHECK_DIV_RANGES) && defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t ma = fhe_f2u(a) & 0x7fffffffu, mb = fhe_f2u(b) & 0x7fffffffu;
+  const bool a_ok = ma == 0u || ma >= 0x7f800000u || in_pow2_range<ALO, AHI>(a), b_ok = mb == 0u || mb >= 0x7f800000u || in_pow2_range<BLO, BHI>(b);
+  if (!(a_ok && b_ok)) atomicAdd(&fh_div_range_violations, 1u);
+#endif
+  return fhe_div(a, b);
+}
+template <int ALO, int AHI, int BLO, int BHI>
+FH_HD float div_r_nofix(float a, float b)
+{
+  static_assert(div_claim_ok<ALO, AHI, BLO, BHI>(), "the claimed ranges do not imply fhe_div's conditions");
+#if defined(FH_CHECK_DIV_RANGES) && defined(__HIP_DEVICE_COMPILE__)
+  if (!((fhe_f2u(a) == 0u || in_pow2_range<ALO, AHI>(a)) && in_pow2_range<BLO, BHI>(b))) atomicAdd(&fh_div_range_violations, 1u);
+#endif
+  return fhe_div_nofix(a, b);
+}
+
 FH_HD float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 FH_HD f3 cross(f3 a, f3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 FH_HD float length(f3 a) { return sqrt_cr(dot(a, a)); }
 FH_HD f3 normalize(f3 a) { const float inv = 1.0f / sqrt_cr(dot(a, a)); return a * inv; }
+// normalize for a caller that can say how long its vector is: 2^LO <= |a| <= 2^HI (a zero, infinite or NaN length is answered as normalize answers it)
+template <int LO, int HI>
+FH_HD f3 normalize_r(f3 a) { const float inv = div_r<0, 0, LO, HI>(1.0f, sqrt_cr(dot(a, a))); return a * inv; }
 FH_HD float clampf(float f, float a, float b) { return fmaxf(a, fminf(f, b)); }
 FH_HD int clampi(int f, int a, int b) { return f < a ? a : (f > b ? b : f); }
 FH_HD f3 clamp01(f3 v) { return {clampf(v.x, 0.0f, 1.0f), clampf(v.y, 0.0f, 1.0f), clampf(v.z, 0.0f, 1.0f)}; }

@@ -423,7 +423,7 @@ int group_get_stats(fh_ctx* g, fh_stats* out)
     a.n_generate_launches += s.n_generate_launches; a.n_accumulate_launches += s.n_accumulate_launches; a.n_shade_launches += s.n_shade_launches; a.n_tail_launches += s.n_tail_launches;
     a.shaded_hits += s.shaded_hits; a.n_post_launches += s.n_post_launches;
     a.clk_cycles_closest += s.clk_cycles_closest; a.clk_ticks_closest += s.clk_ticks_closest; a.clk_cycles_shadow += s.clk_cycles_shadow; a.clk_ticks_shadow += s.clk_ticks_shadow;
-    a.n_passes += s.n_passes; a.sky_pixel_samples += s.sky_pixel_samples;
+    a.n_passes += s.n_passes; a.sky_pixel_samples += s.sky_pixel_samples; a.div_range_violations += s.div_range_violations;
   }
   *out = a;
   return FH_OK;

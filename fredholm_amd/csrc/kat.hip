@@ -282,6 +282,13 @@ __global__ void k_sqrt_some(uint32_t n, const float* in, float* out)
   if (i < n) out[i] = fhe_sqrt(in[i]);
 }
 
+// both endings of the short division (include/fh_elementary.h), as the kernels call them
+__global__ void k_div_some(uint32_t n, const float* a, const float* b, float* q_fixup, float* q_nofix)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { q_fixup[i] = fhe_div(a[i], b[i]); q_nofix[i] = fhe_div_nofix(a[i], b[i]); }
+}
+
 // fh_set_env_sampling: the draw of the sky slot, the evaluator, and the environment as the table weighs it.  The frame is the one shade_hit builds round a normal
 __global__ void k_env_sample(EnvTable t, uint32_t n, const float* u2, const float* n3, float* dir3, float* pdf, uint32_t* cell)
 {
@@ -568,6 +575,17 @@ int fh_kat_sqrt(fh_ctx* ctx, unsigned long long* mismatches_over_all_inputs, uin
   FH_HIP(hipStreamSynchronize(ctx->stream));
   FH_HIP(down(bad, mismatches_over_all_inputs));
   if (n_sample) FH_HIP(down(o, sample_out));
+  return FH_OK;
+}
+int fh_kat_div(fh_ctx* ctx, uint32_t n, const float* a, const float* b, float* q_fixup, float* q_nofix)
+{
+  KCTX(ctx);
+  if (n == 0 || !a || !b || !q_fixup || !q_nofix) return fail(ctx, FH_E_INVALID, "fh_kat_div: null argument");
+  DeviceBuffer<float> da, db, d1, d2;
+  FH_HIP(up(da, a, n)); FH_HIP(up(db, b, n)); FH_HIP(up(d1, nullptr, n)); FH_HIP(up(d2, nullptr, n));
+  hipLaunchKernelGGL(k_div_some, dim3(blocks(n)), dim3(256), 0, ctx->stream, n, da.get(), db.get(), d1.get(), d2.get());
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(down(d1, q_fixup)); FH_HIP(down(d2, q_nofix));
   return FH_OK;
 }
 int fh_kat_math(fh_ctx* ctx, int kind, uint32_t n, const float* in, float* out)

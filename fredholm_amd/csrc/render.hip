@@ -118,8 +118,16 @@ FH_D bool camera_sample(const FrameDev& fr, const uint32_t* sobol_dim1, uint32_t
 // (u, u_lens: CMJ slots 0 and 1 of the sample)
 FH_D bool camera_ray(const FrameDev& fr, const uint32_t* sobol_dim1, uint32_t image_idx, uint32_t px, uint32_t py, uint32_t n_spp, f2 u, f2 u_lens, f3& org, f3& dir)
 {
-  float uvx = (2.0f * (px + u.x) - fr.width) / fr.height;
-  const float uvy = (2.0f * (py + u.y) - fr.height) / fr.height;
+  // Divisions in their short form (fh_vec.h: div_r, div_r_nofix; the claims are binary exponents).  The camera's own numbers are the caller's and are not validated, so
+  // the sites they reach keep the fix-up, and their claims hold for 2^-20 <= 1 / tan(fov / 2) <= 2^20, 2^-40 <= |a + b| <= 2^40, a lens radius and a transform
+  // of at most 2^20 (an image is at most 65535 pixels a side: the pixel lists pack x and y into 16 bits each).
+  // uv: the numerator is a difference of floats below 2^18 that carry at most 24 bits -- +0 (x - x rounds to +0, never -0) or at least 2^-24 of the larger -- over 1 <= height < 2^16
+  // (the divisor is re-read per sample behind an empty asm: left to itself the compiler keeps the refined reciprocal of the frame's height, and what goes with it, live across
+  // the whole sample loop -- five more scalar spills in k_sky_pixels<true>, which then needs scratch memory; the reciprocal's three instructions per sample cost less)
+  float height = fr.height;
+  asm volatile("" : "+v"(height));
+  float uvx = div_r_nofix<-40, 18, 0, 16>(2.0f * (px + u.x) - fr.width, height);
+  const float uvy = div_r_nofix<-40, 18, 0, 16>(2.0f * (py + u.y) - fr.height, height);
   uvx = -uvx;
   u = u_lens;
   // thin lens (camera.cu:24-53); a + b and the lens radius are the same for every ray: computed once on the host, in fp32 with the reference's operations
@@ -128,10 +136,10 @@ FH_D bool camera_ray(const FrameDev& fr, const uint32_t* sobol_dim1, uint32_t im
   const f3 p_lens_center = mk3(0.0f, 0.0f, f);
   const f2 pd = fr.cam_lens_radius * concentric_disk(u);
   const f3 p_lens = p_lens_center + mk3(pd.x, pd.y, 0.0f);
-  const f3 s2c = normalize(p_lens_center - p_sensor);
-  const f3 p_object = p_sensor + (fr.cam_a_plus_b / s2c.z) * s2c;
+  const f3 s2c = normalize_r<-20, 21>(p_lens_center - p_sensor);  // f <= |(-uvx, -uvy, f)| <= f + 2^19: |uv| <= 2 x 65535 each
+  const f3 p_object = p_sensor + div_r<-40, 40, -41, 1>(fr.cam_a_plus_b, s2c.z) * s2c;  // s2c.z = f x RN(1 / |.|): at least 2^-20 / 2^21, at most 1 and a rounding
   org = xform_point(fr.cam_xf, p_lens);
-  f3 d = normalize(p_object - p_lens);
+  f3 d = normalize_r<-42, 84>(p_object - p_lens);  // the object point lies |a + b| / s2c.z <= 2^81 along s2c, the lens point within 2^21 of the sensor's; along the axis they are a + b - f apart, taken to be 2^-42 at least
   d.z *= -1.0f;
   dir = xform_dir(fr.cam_xf, d);
   const uint32_t sidx = image_idx + n_spp * fr.width * fr.height;
@@ -178,7 +186,7 @@ __global__ void __launch_bounds__(kBlock) k_generate(FrameDev fr, PoolDev pool, 
       // bounce 0 only hold rays that enter the scene and no path state is written for the others
       RayPre rp;  // (only what the slab test reads: origin and reciprocal direction, as ray_prepare forms them)
       rp.o = org;
-      rp.inv = safe_reciprocal(dir);
+      rp.inv = safe_reciprocal_r(dir);
       float tn;
       enter = alive && slab_test(rp, fr.scene_lo.x, fr.scene_lo.y, fr.scene_lo.z, fr.scene_hi.x, fr.scene_hi.y, fr.scene_hi.z, 1e9f, tn);
       if (enter) {
@@ -412,12 +420,12 @@ __global__ void __launch_bounds__(kBlock, kSkyWaves) k_sky_pixels(FrameDev fr, L
       const bool alive = camera_ray(fr, rows.m[0], image_idx, xy & 0xffffu, xy >> 16, n, cmj_draw_in_block(b0, n), cmj_draw_in_block(b1, n), org, dir);
       RayPre rp;
       rp.o = org;
-      rp.inv = safe_reciprocal(dir);
+      rp.inv = safe_reciprocal_r(dir);
       float tn;
       violated = violated || (alive && slab_test(rp, fr.scene_lo.x, fr.scene_lo.y, fr.scene_lo.z, fr.scene_hi.x, fr.scene_hi.y, fr.scene_hi.z, 1e9f, tn));
       const f3 L = alive ? mk3(0.0f) + mk3(1.0f) * env_radiance<true>(fr, dir) : mk3(0.0f);  // (k_generate: radiance of a path that ends at the scene bounds)
       const f3 radiance = bad3(L) ? mk3(0.0f) : L;                                            // (k_accumulate: NaN guard, then the running means; a sky sample has no AOVs)
-      const float coef = 1.0f / (n_spp + 1.0f);
+      const float coef = div_r_nofix<0, 0, 0, 32>(1.0f, n_spp + 1.0f);  // a count below 2^32, plus one
       const float fn = (float)n_spp;
       beauty = coef * (fn * beauty + radiance);
       if constexpr (ADAPTIVE) moments_update(m.x, m.y, coef, fn, radiance);
@@ -440,7 +448,7 @@ __global__ void __launch_bounds__(kBlock, kSkyWaves) k_sky_pixels(FrameDev fr, L
       uint32_t n_aov = n_spp - taken;
 #pragma unroll 1
       for (uint32_t k = 0; k < taken; ++k) {
-        const float coef = 1.0f / (n_aov + 1.0f);
+        const float coef = div_r_nofix<0, 0, 0, 32>(1.0f, n_aov + 1.0f);
         const float fn = (float)n_aov;
         position = coef * (fn * position + mk3(0.0f));
         normal = coef * (fn * normal + mk3(0.0f));
@@ -1655,7 +1663,7 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(PoolDev pool, LayersDev l
         const float4 td = pool.aov_texdepth[p];
         au = td.x; av = td.y; ad = td.z;
       }
-      const float coef = 1.0f / (n_spp + 1.0f);
+      const float coef = div_r_nofix<0, 0, 0, 32>(1.0f, n_spp + 1.0f);  // a count below 2^32, plus one
       const float fn = (float)n_spp;
       beauty = coef * (fn * beauty + radiance);
       position = coef * (fn * position + apos);
@@ -1828,6 +1836,15 @@ SceneDev scene_dev(const fh_ctx* ctx)
   return s;
 }
 
+#if defined(FH_CHECK_DIV_RANGES)
+int div_range_violations_read(fh_ctx* ctx, uint64_t* n)
+{
+  unsigned int v = 0;
+  FH_HIP(hipMemcpyFromSymbol(&v, HIP_SYMBOL(fh::fh_div_range_violations), sizeof v));
+  *n = v;
+  return FH_OK;
+}
+#endif
 // fh_kernel_info: registers / static LDS / scratch of the streaming kernel variant this scene is traced by, and how it is launched
 int kernel_info(fh_ctx* ctx, int which, uint32_t out[6])
 {

@@ -1,6 +1,8 @@
 // render_shade_body.inc -- the body of k_shade and k_shade_env (render.hip includes it into both).  In scope: sc, fr, pool, cls, depth; ENV and env
 // It is text, not a function: it reads the names sc, fr, pool, ENV and env of the kernel it is included into.  The plain k_shade must keep its instruction stream, so after ANY
 // edit here compare a device listing of render.hip with the one before the edit (tools/kernel_asm_diff.py): k_shade<...> may differ in nothing.
+// (One change altered that stream on purpose, from outside this file: the divisions of concentric_disk and of the Hosek sky took their short form -- fh_vec.h: div_r.  The
+// listing to compare with is the one from after it.)
   pass_priority();
   // (the grid is sized for every path of the pass; the blocks beyond this class's queue leave before they stage anything)
   if (blockIdx.x * blockDim.x >= pool.counters[depth * kCounterStride + CNT_CLS + cls]) return;

@@ -91,7 +91,7 @@ class StatsC(C.Structure):
                 ("n_generate_launches", C.c_uint64), ("n_accumulate_launches", C.c_uint64), ("n_shade_launches", C.c_uint64), ("n_tail_launches", C.c_uint64),
                 ("shaded_hits", C.c_uint64), ("bvh_depth", C.c_uint64), ("post_ms", C.c_double), ("n_post_launches", C.c_uint64),
                 ("clk_cycles_closest", C.c_uint64), ("clk_ticks_closest", C.c_uint64), ("clk_cycles_shadow", C.c_uint64), ("clk_ticks_shadow", C.c_uint64),
-                ("n_passes", C.c_uint64), ("sky_pixel_samples", C.c_uint64)]
+                ("n_passes", C.c_uint64), ("sky_pixel_samples", C.c_uint64), ("div_range_violations", C.c_uint64)]
 
     def as_dict(self):
         return {k: (list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k)) for k, _ in self._fields_}
@@ -109,7 +109,7 @@ EXPORTS = [
     "fh_pack_owned", "fh_unpack_shard", "fh_unpack_shards", "fh_render", "fh_sync", "fh_get_stats", "fh_reset_stats", "fh_post_process", "fh_denoise", "fh_gl_register_buffer", "fh_gl_unregister_buffer", "fh_malloc",
     "fh_free", "fh_memset", "fh_copy_to_device", "fh_copy_to_host", "fh_copy_on_device", "fh_image_load_rgba8", "fh_image_free", "fh_stream", "fh_trace_rays", "fh_kernel_info", "fh_kat_hash", "fh_kat_cmj",
     "fh_kat_sobol", "fh_kat_elementary", "fh_kat_warp", "fh_kat_bsdf", "fh_kat_bsdf_lobes", "fh_kat_bsdf_ior", "fh_kat_sky", "fh_kat_hosek_state", "fh_kat_camera",
-    "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
+    "fh_kat_offset_origin", "fh_kat_math", "fh_kat_sqrt", "fh_kat_div", "fh_kat_tex2d", "fh_kat_face_classes", "fh_kat_alpha_records", "fh_kat_ray_start", "fh_kat_set_sample_counts", "fh_kat_sample_counts", "fh_measure_bandwidth",
     "fh_set_adaptive_sampling", "fh_get_adaptive_sampling", "fh_get_sample_counts", "fh_get_luminance_moments", "fh_active_pixel_count", "fh_kat_set_issued", "fh_kat_live_allocations",
     "fh_set_adaptive_policy", "fh_get_adaptive_policy", "fh_adaptive_next_boundary",
     "fh_denoise_guided", "fh_denoise_temporal", "fh_denoise_history_reset", "fh_denoise_history_info",

@@ -52,6 +52,58 @@ FHE_FN float fhe_sqrt(float x)
   return sqrtf(x);
 }
 
+/* a / b, correctly rounded, for operands whose RANGE THE CALLER HAS PROVEN.  On the host: a / b.  On gfx950 the compiler's IEEE division is v_div_scale (x2), v_rcp,
+ * ten-odd fused multiply-adds, v_div_fmas and v_div_fixup: five instructions of the slow issue class.  Where no scaling is needed the quotient needs only
+ *   y0 = rcp(b)                         (hardware, within 1 ulp of 1/b)
+ *   e  = fma(-b, y0, 1);  y = fma(e, y0, y0)   one Newton step: y = RN(1/b)
+ *   q0 = a * y                                  within 1 ulp of a/b
+ *   r  = fma(-b, q0, a)                         the residual, EXACT (a and b * q0 agree in their leading bits)
+ *   q  = fma(r, y, q0)                          Markstein's correction
+ * Theorem (Markstein, "Computation of elementary functions on the IBM RISC System/6000 processor", 1990, Thm 8.4/8.5; Cornea, Harrison, Tang, "Scientific computing on
+ * Itanium", 2002, ch. 8): if y is the correctly rounded reciprocal of b and q0 is within one ulp of a/b, then q = RN(q0 + r * y) is the correctly rounded quotient in
+ * every rounding-relevant case, provided nothing on the way underflows or overflows.  One Newton step from a 1-ulp start gives y = RN(1/b) for every divisor EXCEPT one
+ * mantissa: all ones (b = 2^k (2 - 2^-23)), where 1/b lies 2^-48 (relative) above a rounding midpoint and the step, started one ulp off, lands on the wrong neighbour -- and
+ * then no later correction of the quotient recovers (a = 2^j gives the neighbour's quotient; the compiler's own two-correction sequence fails the same way from such a
+ * start).  That case is covered by the START, not by a second step: v_rcp_f32 returns the correctly rounded reciprocal for the all-ones mantissa (the exponent does not
+ * enter its mantissa path), from which the Newton step reproduces it (e = -2^-24 + 2^-47 exactly, y0 + e y0 = 2^-k-1 (1 + 2^-24 + 2^-70): rounds up, to y0).
+ * fh_kat_div compares both endings with the IEEE quotient on the device for all-ones, all-zeros and neighbouring mantissas at every exponent the sites claim
+ * (tests/test_gpu_div_exact.py), with numerators one ulp either side of b x (a rounding midpoint) -- the cases a wrong correction misses; on the host the five operations
+ * were run against a / b over 1.2e8 such pairs with y0 displaced by -1, 0, +1 ulp: no mismatch for any mantissa but all ones.
+ *
+ * What "nothing underflows or overflows" asks of a site (its one-line range argument; |.| throughout, a == 0 is always allowed):
+ *   2^-126 <= b <= 2^126            rcp(b) is normal
+ *   a == 0 or a >= 2^-100           the residual's last bit, 2^-46 ulp-units below a, is no subnormal
+ *   a != 0: 2^-125 <= a / b < 2^127 q0 and q are normal and finite
+ * Two endings:
+ *   fhe_div (a):       q goes through v_div_fixup_f32 with the original operands, which answers +-0, +-inf and NaN operands as IEEE does (two slow-class instructions).
+ *                      The site's argument bounds the magnitudes of its FINITE NON-ZERO operands only.
+ *   fhe_div_nofix (b): no fix-up (one slow-class instruction): the site's argument also excludes infinite and NaN operands and b == 0.  A zero numerator needs no fix-up
+ *                      but for one sign: q0 = a * y carries the quotient's sign, r = fma(-b, q0, a) is +0 (two zeros of either sign sum to +0 unless both are -0, and
+ *                      they never are: -b q0 = -a), and q = fma(+0, y, q0) is q0 when y > 0 or q0 is -0 -- that is +0 / b, +-0 / -b -- but -0 / b with b > 0 gives
+ *                      (+0) + (-0) = +0 where IEEE gives -0.  Ending (b) is therefore only for sites whose numerator cannot be -0; each says why. */
+FHE_FN float fhe_div(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float y0 = __builtin_amdgcn_rcpf(b);
+  const float y = fmaf(fmaf(-b, y0, 1.0f), y0, y0);
+  const float q0 = a * y;
+  return __builtin_amdgcn_div_fixupf(fmaf(fmaf(-b, q0, a), y, q0), b, a);
+#else
+  return a / b;
+#endif
+}
+FHE_FN float fhe_div_nofix(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float y0 = __builtin_amdgcn_rcpf(b);
+  const float y = fmaf(fmaf(-b, y0, 1.0f), y0, y0);
+  const float q0 = a * y;
+  return fmaf(fmaf(-b, q0, a), y, q0);
+#else
+  return a / b;
+#endif
+}
+
 /* round to nearest even, valid for |x| < 2^22 (magic-number trick: exact in IEEE fp32) */
 FHE_FN float fhe_rint(float x)
 {

@@ -124,6 +124,8 @@ typedef struct fh_stats {
   uint64_t clk_cycles_closest, clk_ticks_closest, clk_cycles_shadow, clk_ticks_shadow;
   uint64_t n_passes;          /* passes of the path pools submitted */
   uint64_t sky_pixel_samples; /* camera samples (counted in `paths`) rendered by the sky-pixel kernel: samples of pixels no ray of which can reach the scene's bounds */
+  uint64_t div_range_violations; /* libraries built with -DFH_CHECK_DIV_RANGES only (else 0): short divisions (fh_elementary.h: fhe_div) whose operands left the range their
+                                    site claims, on this device since the library was loaded (by any context), as of the last fh_sync */
 } fh_stats;
 
 #define FH_FLAG_TIME_KERNELS 1u    /* bracket traversal/shade launches with HIP events (fh_stats *_ms) */

@@ -49,6 +49,9 @@ int fh_kat_math(fh_ctx* ctx, int kind, uint32_t n, const float* in, float* out);
 /* the device's short correctly rounded square root (include/fh_elementary.h: fhe_sqrt) against the compiler's IEEE sqrtf over all 2^32 float bit patterns
  * (number of disagreeing inputs; 0 expected), plus its results on `n_sample` given inputs for a comparison with the host's sqrtf */
 int fh_kat_sqrt(fh_ctx* ctx, unsigned long long* mismatches_over_all_inputs, uint32_t n_sample, const float* sample_in, float* sample_out);
+/* the device's short correctly rounded division (include/fh_elementary.h) on n pairs (a, b): fhe_div (the ending with the hardware's fix-up) and fhe_div_nofix
+ * (the ending without), for a bit-for-bit comparison with IEEE a / b over the operand ranges the converted sites claim */
+int fh_kat_div(fh_ctx* ctx, uint32_t n, const float* a, const float* b, float* q_fixup, float* q_nofix);
 int fh_kat_tex2d(fh_ctx* ctx, const uint8_t* rgba8, const float* rgba32f, uint32_t width, uint32_t height, int srgb, uint32_t n, const float* uv2, float* out4);
 /* the class byte of every face of the uploaded scene (n = faces): bits 0-4 shading class, 0x20 a cut-out face whose any-hit test can never pass (no ray hits it),
    0x40 the any-hit test runs for candidate hits on this face, 0x80 emissive.  A face of a material whose textures can cut with neither 0x20 nor 0x40 was

@@ -7,9 +7,10 @@ cd "$(dirname "$0")/../fredholm_amd/csrc"
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function -Wno-unused-result"
 mkdir -p /tmp/fhv_$name
 [ -f gen/tables.inc ] || make gen/tables.inc
-for f in capi render bvh_build kat post; do
+SRCS="capi scene render bvh_build kat post denoise motion group envmap"  # (fredholm_amd/csrc/Makefile: SRCS)
+for f in $SRCS; do
   /opt/rocm/bin/hipcc $FLAGS "$@" -c $f.hip -o /tmp/fhv_$name/$f.o &
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../libfredholm_hip_$name.so /tmp/fhv_$name/capi.o /tmp/fhv_$name/render.o /tmp/fhv_$name/bvh_build.o /tmp/fhv_$name/kat.o /tmp/fhv_$name/post.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../libfredholm_hip_$name.so $(for f in $SRCS; do echo /tmp/fhv_$name/$f.o; done)
 ls -la ../libfredholm_hip_$name.so
