@@ -461,6 +461,23 @@ int fh_get_env_sampling(fh_ctx* ctx, int* on, fh_env_sampling_params* params)
   return FH_OK;
 }
 
+// sampling of area lights by power (lights.hip, fh_lights.h): refused from the arguments alone; a scene call
+int fh_set_light_sampling(fh_ctx* ctx, const fh_light_sampling_params* params)
+{
+  if (const char* why = light_sampling_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_light_sampling: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_light_sampling(m_, params));
+  CTX_CHECK(ctx);
+  return light_sampling_set(ctx, params);
+}
+int fh_get_light_sampling(fh_ctx* ctx, int* on, fh_light_sampling_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->light_sampling;
+  if (params) params->uniform_fraction = ctx->light_uniform_fraction;
+  return FH_OK;
+}
+
 // the moments of adaptive sampling start at sample 0: allocated and cleared whenever the mode is on and the counters are reset (0 * inf would poison a reset's
 // running means otherwise), and when the mode is turned on
 static int adaptive_reset(fh_ctx* ctx)

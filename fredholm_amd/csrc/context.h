@@ -11,6 +11,7 @@
 #include "../../include/fredholm_hip.h"
 #include "fh_device.h"
 #include "fh_envmap.h"
+#include "fh_lights.h"
 #include "fh_memory.h"
 
 struct fh_group;  // group.hip
@@ -152,6 +153,15 @@ struct fh_ctx {
   fh::DeviceBuffer<uint32_t> d_env_q;      // integer weights, then the 256 row sums
   fh::DeviceBuffer<unsigned long long> d_env_total;
   fh::DeviceBuffer<float> d_env_cdf_row, d_env_cdf_m, d_env_cell_p;
+  // fh_set_light_sampling (lights.hip, fh_lights.h): the table of the emitters' power the area shadow rays pick from.  Sized for the scene by the rebuild;
+  // light_stale: the scene, its transforms or the uniform share changed since it was built (the next fh_render of a scene with emitters rebuilds it on the context stream)
+  int light_sampling = 0;
+  float light_uniform_fraction = FH_LIGHT_UNIFORM_FRACTION_DEFAULT;
+  bool light_stale = true;
+  fh::DeviceBuffer<float> d_light_w;                    // weights, then one word: the bits of their maximum
+  fh::DeviceBuffer<uint32_t> d_light_q;                 // integer weights, then the sums of the chunks of 256
+  fh::DeviceBuffer<unsigned long long> d_light_offsets; // exclusive scan of the chunk sums, then the total
+  fh::DeviceBuffer<float> d_light_cdf, d_light_pick_p;  // [n_lights + 1]; [n_faces]
 
   // path pools: one per pass in flight (pass j uses slot j % n_slots and the stream of that slot); allocated on first use
   fh::PoolDev pool[3] = {};
@@ -334,6 +344,7 @@ uint32_t owned_count(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, 
 Event take_event(fh_ctx* ctx);  // render.hip: a timing event from ctx->event_pool, or a new one
 SceneDev scene_dev(const fh_ctx* ctx);
 inline EnvTable env_table_dev(const fh_ctx* ctx) { return EnvTable{ctx->d_env_cdf_row, ctx->d_env_cdf_m, ctx->d_env_cell_p, ctx->env_cosine_fraction}; }
+inline LightTable light_table_dev(const fh_ctx* ctx) { return LightTable{ctx->d_light_cdf, ctx->d_light_pick_p, ctx->light_uniform_fraction}; }
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip
 void reset_tree_measurements(fh_ctx* ctx);         // bvh_build.hip: a new tree; what the render path has measured on the old one (bu_*, survival) starts again
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);  // render.hip
@@ -367,6 +378,9 @@ int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* 
 // envmap.hip: the switch with its device memory (arguments checked by the caller); the rebuild of a stale table, queued on the context stream
 int env_sampling_set(fh_ctx* ctx, const fh_env_sampling_params* params);
 int env_table_ensure(fh_ctx* ctx);
+// lights.hip: the switch (arguments checked by the caller); the rebuild of a stale table, queued on the context stream (nothing for a scene without emitters)
+int light_sampling_set(fh_ctx* ctx, const fh_light_sampling_params* params);
+int light_table_ensure(fh_ctx* ctx);
 FrameDev env_frame(const fh_ctx* ctx);  // the environment as the table weighs it: sky intensity 1, a white background
 int primary_instances_submit(fh_ctx* ctx, const fh_camera* cam, uint32_t w, uint32_t h, uint32_t* ids);  // motion.hip (arguments checked by the caller)
 }  // namespace fh

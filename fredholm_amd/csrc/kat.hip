@@ -314,6 +314,16 @@ __global__ void k_env_radiance(FrameDev fr, uint32_t n, const float* d3, float* 
   out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
 }
 
+// fh_set_light_sampling: the pick of the area shadow ray as shade_hit<., ., true> makes it -- the emitter by light_pick, the probability from its face's entry
+__global__ void k_light_pick(LightTable t, const AreaLightDev* lights, uint32_t n_lights, uint32_t n, const float* u1, uint32_t* index, float* p)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t li = light_pick(t.cdf, n_lights, t.uniform, u1[i]);
+  index[i] = li;
+  p[i] = t.pick_p[lights[li].face];
+}
+
 uint32_t blocks(uint32_t n) { return (n + 255) / 256; }
 
 }  // namespace
@@ -505,6 +515,49 @@ int fh_kat_env_radiance(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3
   hipLaunchKernelGGL(k_env_radiance, dim3(blocks(n)), dim3(256), 0, ctx->stream, env_frame(ctx), n, a.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
   FH_HIP(down(o, out3));
+  return FH_OK;
+}
+// the hooks of fh_set_light_sampling work on the CURRENT table: a stale one is rebuilt first, as fh_render would
+static int kat_light_table(fh_ctx* ctx, const char* who)
+{
+  if (!ctx->light_sampling) return fail(ctx, FH_E_INVALID, std::string(who) + ": light sampling is off (fh_set_light_sampling)");
+  if (!ctx->scene_loaded || ctx->n_lights == 0) return fail(ctx, FH_E_INVALID, std::string(who) + ": the scene has no emitters");
+  return light_table_ensure(ctx);
+}
+int fh_kat_light_table(fh_ctx* ctx, uint32_t* q, float* cdf, float* pick_p_per_light, uint64_t* total)
+{
+  KCTX(ctx);
+  if (const int rc = kat_light_table(ctx, "fh_kat_light_table")) return rc;
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  const uint32_t n = ctx->n_lights, n_chunks = (n + 255u) / 256u;
+  if (q) FH_HIP(hipMemcpy(q, ctx->d_light_q, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  if (cdf) FH_HIP(hipMemcpy(cdf, ctx->d_light_cdf, sizeof(float) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+  if (total) {
+    unsigned long long t = 0;
+    FH_HIP(hipMemcpy(&t, ctx->d_light_offsets + n_chunks, sizeof t, hipMemcpyDeviceToHost));
+    *total = t;
+  }
+  if (pick_p_per_light) {  // the table keeps them per face: gathered here in light order
+    std::vector<float> per_face(ctx->n_faces);
+    std::vector<AreaLightDev> lights(n);
+    FH_HIP(hipMemcpy(per_face.data(), ctx->d_light_pick_p, sizeof(float) * ctx->n_faces, hipMemcpyDeviceToHost));
+    FH_HIP(hipMemcpy(lights.data(), ctx->d_lights, sizeof(AreaLightDev) * n, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < n; ++k) pick_p_per_light[k] = lights[k].face < ctx->n_faces ? per_face[lights[k].face] : 0.0f;
+  }
+  return FH_OK;
+}
+int fh_kat_light_pick(fh_ctx* ctx, uint32_t n, const float* u1, uint32_t* index, float* p)
+{
+  KCTX(ctx);
+  if (!u1 || !index || !p) return fail(ctx, FH_E_INVALID, "fh_kat_light_pick: null argument");
+  if (const int rc = kat_light_table(ctx, "fh_kat_light_pick")) return rc;
+  if (n == 0) return FH_OK;  // (nothing to pick: a launch of no workgroups is an error)
+  DeviceBuffer<float> a, o;
+  DeviceBuffer<uint32_t> idx;
+  FH_HIP(up(a, u1, n)); FH_HIP(up(idx, nullptr, n)); FH_HIP(up(o, nullptr, n));
+  hipLaunchKernelGGL(k_light_pick, dim3(blocks(n)), dim3(256), 0, ctx->stream, light_table_dev(ctx), (const AreaLightDev*)ctx->d_lights.get(), ctx->n_lights, n, a.get(), idx.get(), o.get());
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(down(idx, index)); FH_HIP(down(o, p));
   return FH_OK;
 }
 int fh_kat_hosek_state(fh_ctx* ctx, float* out30)

@@ -961,9 +961,11 @@ struct PoolSink {      // memory sink (k_shade): path slot p of the pool
 
 // ENV (fh_set_env_sampling): the sky ray is drawn from the mixture of fh_envmap.h and the two light-ray weights that stand against it use that density; `env` is read
 // by these variants only, and nothing else of the hit differs
-template <uint32_t LOBES, bool ENV = false, class Sink>
+// LT (fh_set_light_sampling): the emitter of the area shadow ray is picked from the table of fh_lights.h and its density is the pick's probability over the area; `ltab`
+// is read by these variants only.  (The BSDF-sampled light ray's side of it is resolve_light_ray<true>.)
+template <uint32_t LOBES, bool ENV = false, bool LT = false, class Sink>
 FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& rows, const BounceSlots& bs, uint32_t depth, float4 hit, f3 rd, f3 T, f3 L, uint32_t image_idx, uint32_t n_spp,
-                    Sink& out, bool first = true, const EnvTable* env = nullptr)
+                    Sink& out, bool first = true, const EnvTable* env = nullptr, const LightTable* ltab = nullptr)
 {
   const uint32_t has_lights = bs.has_lights;
   const uint32_t prim = __float_as_uint(hit.w);
@@ -1068,8 +1070,13 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
   if (has_lights) {
     const float u1 = sobol_draw_bytes(rows.m[0], sidx, bs.dim_area, fr.seed_hash);
     const f2 u2 = cmj_draw(n_spp, image_idx, bs.slot_area, fr.seed_hash);
-    uint32_t li = (uint32_t)(u1 * sc.n_lights);
-    li = li < sc.n_lights - 1u ? li : sc.n_lights - 1u;
+    uint32_t li;
+    if constexpr (LT) {
+      li = light_pick(ltab->cdf, sc.n_lights, ltab->uniform, u1);
+    } else {
+      li = (uint32_t)(u1 * sc.n_lights);
+      li = li < sc.n_lights - 1u ? li : sc.n_lights - 1u;
+    }
     const AreaLightDev lt = sc.lights[li];
     const f2 bc = triangle_barycentric(u2);
     const float4 l0 = sc.face_rec[kFaceRec * (size_t)lt.face], l1 = sc.face_rec[kFaceRec * (size_t)lt.face + 1], l2 = sc.face_rec[kFaceRec * (size_t)lt.face + 2];
@@ -1080,7 +1087,9 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
     const float area = 0.5f * length(cross(mk3(l1) - mk3(l0), mk3(l2) - mk3(l0)));
     const MaterialDev& lm = sc.materials[lt.material];
     const f3 le = emission_of(sc, lm, lw * l0.w + bc.x * l2.w + bc.y * l4.w, lw * l1.w + bc.x * l3.w + bc.y * l5.w);
-    const float pdf_area = 1.0f / (sc.n_lights * area);
+    float pdf_area;
+    if constexpr (LT) pdf_area = ltab->pick_p[lt.face] / area;
+    else pdf_area = 1.0f / (sc.n_lights * area);
     const f3 sd = normalize(lp - so);
     const float r = length(lp - so);
     const bool facing = dot(-sd, ln) > 0.0f;
@@ -1223,27 +1232,40 @@ __global__ void __launch_bounds__(kSortBlock) k_cell_scatter(const uint32_t* cou
 
 // k_shade and k_shade_env, its twin that takes the environment table (fh_set_env_sampling), share ONE body text, render_shade_body.inc, included into both: a device
 // function called by both was tried first and changed the plain kernels' instruction streams (registers allocated differently in 15 of them), and the plain kernels
-// must stay what they are.  The body reads ENV and env.
+// must stay what they are.  The body reads ENV and env, LT and ltab.
 template <uint32_t LOBES, int BLOCKS = FH_SHADE_BLOCKS>
 __global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : BLOCKS)) k_shade(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth)
 {
-  constexpr bool ENV = false;
+  constexpr bool ENV = false, LT = false;
   const EnvTable* const env = nullptr;
+  const LightTable* const ltab = nullptr;
 #include "render_shade_body.inc"
 }
 // compiled for the lobe sets of the fused tail (TailLobes), two workgroups per CU
 template <uint32_t LOBES>
 __global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : FH_SHADE_BLOCKS)) k_shade_env(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth, EnvTable env_table)
 {
-  constexpr bool ENV = true;
+  constexpr bool ENV = true, LT = false;
   const EnvTable* const env = &env_table;
+  const LightTable* const ltab = nullptr;
+#include "render_shade_body.inc"
+}
+// the twin that takes the light table (fh_set_light_sampling), with and without the environment table read: the same lobe sets, the same workgroups per CU
+template <uint32_t LOBES, bool ENV_ON>
+__global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : FH_SHADE_BLOCKS)) k_shade_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth, EnvTable env_table, LightTable light_table)
+{
+  constexpr bool ENV = ENV_ON, LT = true;
+  const EnvTable* const env = &env_table;
+  const LightTable* const ltab = &light_table;
 #include "render_shade_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
 // Finish the BSDF-sampled light ray of a scene with emitters once its closest hit is known
 // (pt.cu:952-999 closest-hit light, :531-543 miss light, :910-924 MIS weight).
-FH_D f3 resolve_light_ray(const SceneDev& sc, const FrameDev& fr, f3 T, float cosw, f3 f, float pdf, f3 ro, f3 ld, bool hit, const HitRec& h)
+// LT (fh_set_light_sampling): the emitter's density is its pick probability over its area; pick_p (fh_lights.h: per face) is read by that variant only
+template <bool LT = false>
+FH_D f3 resolve_light_ray(const SceneDev& sc, const FrameDev& fr, f3 T, float cosw, f3 f, float pdf, f3 ro, f3 ld, bool hit, const HitRec& h, const float* pick_p = nullptr)
 {
   f3 le = mk3(0.0f);
   float pdf_light = cosw / kPi;
@@ -1261,7 +1283,9 @@ FH_D f3 resolve_light_ray(const SceneDev& sc, const FrameDev& fr, f3 T, float co
         const float area = 0.5f * length(cross(mk3(l1) - mk3(l0), mk3(l2) - mk3(l0)));
         const f3 dl = lp - ro;
         const float r2 = dot(dl, dl);
-        const float pdf_area = 1.0f / (sc.n_lights * area);
+        float pdf_area;
+        if constexpr (LT) pdf_area = pick_p[h.prim] / area;
+        else pdf_area = 1.0f / (sc.n_lights * area);
         pdf_light = r2 / fabsf(dot(-ld, ln)) * pdf_area;
         add = true;
       }
@@ -1279,49 +1303,21 @@ FH_D f3 resolve_light_ray(const SceneDev& sc, const FrameDev& fr, f3 T, float co
 template <bool COUNT, bool WIDE, bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock) k_trace_secondary_static(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc)
 {
-  pass_priority();
-  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
-  __shared__ HosekSky s_sky;  // (light rays that escape see the sky: resolve_light_ray)
-  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
-  const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
-  constexpr bool has_lights = LIGHTS;
-  uint32_t nn = 0, nt = 0, nr = 0;
-  WaveSteps ws;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-    const uint32_t p = pool.q_sec[i];
-    f3 L = mk3(pool.rad[p]);
-#pragma unroll
-    for (uint32_t slot = SEC_DIR; slot <= SEC_LIGHT; ++slot) {
-      if (slot == SEC_DIR && !fr.has_dir) continue;
-      if (slot == SEC_AREA && !has_lights) continue;
-      const size_t k = pool.sec_at(slot, p);
-      const float4 d = pool.sec[k + 1];
-      if (!sec_present(d)) continue;
-      const float4 o = pool.sec[k];
-      HitRec h;
-      if (COUNT) nr++;
-      if (slot == SEC_LIGHT && has_lights) {
-        const bool hit = WIDE ? traverse_bvh8<false, COUNT, true, ALPHA>(sc.bvh8, mk3(o), mk3(d), o.w, h, nn, nt, &ws, lds_stack, (int)sc.bvh8.depth, &sc)
-                              : traverse_bvh2<false, COUNT, ALPHA>(sc.bvh2, mk3(o), mk3(d), o.w, h, nn, nt, &sc);
-        const float4 la = pool.lp_a[p], lb = pool.lp_b[p];
-        L += resolve_light_ray(sc, fr, mk3(la), la.w, mk3(lb), lb.w, mk3(o), mk3(d), hit, h);
-      } else {
-        const uint32_t nn0 = nn;
-        const bool occluded = WIDE ? traverse_bvh8<true, COUNT, true, ALPHA>(sc.bvh8, mk3(o), mk3(d), o.w, h, nn, nt, &ws, lds_stack, (int)sc.bvh8.depth, &sc)
-                                   : traverse_bvh2<true, COUNT, ALPHA>(sc.bvh2, mk3(o), mk3(d), o.w, h, nn, nt, &sc);
-        if (COUNT) { const uint32_t kk = nn - nn0; int b = 0; while (b < 7 && kk > (8u << b)) ++b; atomicAdd(tc.hist + b, 1ull); }
-        if (!occluded) L += mk3(pool.sec[k + 2]);
-      }
-    }
-    pool.rad[p] = mk4(L, 0.0f);
-  }
-  if (COUNT) {
-    atomicAdd(tc.nodes, (unsigned long long)nn);
-    atomicAdd(tc.tris, (unsigned long long)nt);
-    atomicAdd(tc.rays, (unsigned long long)nr);
-    if (ws.node) atomicAdd(tc.wave_nodes, (unsigned long long)ws.node);
-    if (ws.tri) atomicAdd(tc.wave_tris, (unsigned long long)ws.tri);
-  }
+  constexpr bool LT = false;
+  const float* const pick_p = nullptr;
+#define FH_BODY_STATIC
+#include "render_secondary_body.inc"
+#undef FH_BODY_STATIC
+}
+// The twins of the four secondary-ray kernels that take the light table (fh_set_light_sampling): pick_p is one more argument, LIGHTS is always true -- without emitters
+// the mode does nothing -- and the body text is shared (render_secondary_body.inc), as the shade kernels share theirs.
+template <bool COUNT, bool WIDE, bool ALPHA>
+__global__ void __launch_bounds__(kBlock) k_trace_secondary_static_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, const float* pick_p)
+{
+  constexpr bool LT = true, LIGHTS = true;
+#define FH_BODY_STATIC
+#include "render_secondary_body.inc"
+#undef FH_BODY_STATIC
 }
 
 // secondary rays over the 8-wide BVH with wave-cooperative triangle tests: a lane owns one shaded path and walks its
@@ -1329,61 +1325,27 @@ __global__ void __launch_bounds__(kBlock) k_trace_secondary_static(SceneDev sc, 
 template <bool COUNT, bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? 5 : 6)) k_trace_secondary_coop(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush)
 {
-  pass_priority();
-  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
-  __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
-  const CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
-  __shared__ HosekSky s_sky;  // (light rays that escape see the sky: resolve_light_ray)
-  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
-  const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
-  constexpr bool has_lights = LIGHTS;
-  uint32_t nn = 0, nt = 0, nr = 0;
-  WaveSteps ws;
-  for (uint32_t base = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < count; base += gridDim.x * blockDim.x) {
-    const uint32_t i = base + (threadIdx.x & 63u);
-    const bool in_range = i < count;
-    const uint32_t p = in_range ? pool.q_sec[i] : 0u;
-    f3 L = in_range ? mk3(pool.rad[p]) : mk3(0.0f);
-#pragma unroll
-    for (uint32_t slot = SEC_DIR; slot <= SEC_LIGHT; ++slot) {
-      if (slot == SEC_DIR && !fr.has_dir) continue;
-      if (slot == SEC_AREA && !has_lights) continue;
-      const size_t k = pool.sec_at(slot, p);
-      const float4 d = in_range ? pool.sec[k + 1] : make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-      const bool valid = in_range && sec_present(d);
-      if (__ballot(valid) == 0ull) continue;
-      const float4 o = valid ? pool.sec[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      HitRec h;
-      if (COUNT && valid) nr++;
-      if (slot == SEC_LIGHT && has_lights) {
-        const bool hit = traverse_bvh8_coop<false, COUNT, true, ALPHA>(sc.bvh8, valid, mk3(o), mk3(d), o.w, h, nn, nt, &ws, cl, flush, lds_stack, (int)sc.bvh8.depth, &sc);
-        if (valid) {
-          const float4 la = pool.lp_a[p], lb = pool.lp_b[p];
-          L += resolve_light_ray(sc, fr, mk3(la), la.w, mk3(lb), lb.w, mk3(o), mk3(d), hit, h);
-        }
-      } else {
-        const uint32_t nn0 = nn;
-        const bool occluded = traverse_bvh8_coop<true, COUNT, true, ALPHA>(sc.bvh8, valid, mk3(o), mk3(d), o.w, h, nn, nt, &ws, cl, flush, lds_stack, (int)sc.bvh8.depth, &sc);
-        if (COUNT && valid) { const uint32_t kk = nn - nn0; int b = 0; while (b < 7 && kk > (8u << b)) ++b; atomicAdd(tc.hist + b, 1ull); }
-        if (valid && !occluded) L += mk3(pool.sec[k + 2]);
-      }
-    }
-    if (in_range) pool.rad[p] = mk4(L, 0.0f);
-  }
-  if (COUNT) {
-    atomicAdd(tc.nodes, (unsigned long long)nn);
-    atomicAdd(tc.tris, (unsigned long long)nt);
-    atomicAdd(tc.rays, (unsigned long long)nr);
-    if (ws.node) atomicAdd(tc.wave_nodes, (unsigned long long)ws.node);
-    if (ws.tri) atomicAdd(tc.wave_tris, (unsigned long long)ws.tri);
-  }
+  constexpr bool LT = false;
+  const float* const pick_p = nullptr;
+#define FH_BODY_COOP
+#include "render_secondary_body.inc"
+#undef FH_BODY_COOP
+}
+template <bool COUNT, bool ALPHA>
+__global__ void __launch_bounds__(kBlock, COUNT ? 1 : 5) k_trace_secondary_coop_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, const float* pick_p)
+{
+  constexpr bool LT = true, LIGHTS = true;
+#define FH_BODY_COOP
+#include "render_secondary_body.inc"
+#undef FH_BODY_COOP
 }
 
 // secondary rays, streaming: a lane's item is one shaded path; its secondary-ray slots are traced one after the other by the
 // same lane, so the additions into the path's radiance keep the reference's order (directional, sky, area, BSDF-sampled)
 // (Items that are single RAYS instead of paths -- so that a small launch would end in its longest ray, not in its longest path -- were built and measured in round 6, bit-identical
 // and SLOWER: the rays of a path share their first nodes, and the launches of one-pass calls are not bound by a lane's chain.  tools/patches/r6_ray_items.patch, profiles/README.md r6-8.)
-template <bool COUNT, bool LIGHTS>
+// LT (fh_set_light_sampling): the light rays are finished by resolve_light_ray<true>, which reads pick_p
+template <bool COUNT, bool LIGHTS, bool LT = false>
 struct SecondaryStream {
   static constexpr bool all_any = !LIGHTS;  // without emitters every secondary ray stops at its first hit
   static constexpr bool can_climb = true;   // first-hit rays may start at the node of the face they leave (fh_trace.h: bottom-up start)
@@ -1398,7 +1360,9 @@ struct SecondaryStream {
   uint32_t n_rays = 0;
   unsigned long long* hist;
   HistPack hp;
-  FH_D SecondaryStream(const SceneDev& s, const FrameDev& f, const PoolDev& pl, const ChunkFeed& cf, unsigned long long* hs) : sc(s), fr(f), pool(pl), feed(cf), L(mk3(0.0f)), hist(hs) {}
+  const float* pick_p;
+  FH_D SecondaryStream(const SceneDev& s, const FrameDev& f, const PoolDev& pl, const ChunkFeed& cf, unsigned long long* hs, const float* pp = nullptr)
+      : sc(s), fr(f), pool(pl), feed(cf), L(mk3(0.0f)), hist(hs), pick_p(pp) {}
   // first slot >= from of path p that holds a ray
   FH_D bool scan(uint32_t from, f3& o, f3& d, float& tmax, bool& any)
   {
@@ -1446,7 +1410,7 @@ struct SecondaryStream {
     if (slot == SEC_LIGHT && LIGHTS) {
       const float4 o = pool.sec[k], d = pool.sec[k + 1];
       const float4 la = pool.lp_a[p], lb = pool.lp_b[p];
-      L += resolve_light_ray(sc, fr, mk3(la), la.w, mk3(lb), lb.w, mk3(o), mk3(d), hit, h);
+      L += resolve_light_ray<LT>(sc, fr, mk3(la), la.w, mk3(lb), lb.w, mk3(o), mk3(d), hit, h, pick_p);
     } else {
       if (COUNT) hp.add(nodes);
       if (!hit) L += mk3(pool.sec[k + 2]);
@@ -1460,33 +1424,19 @@ struct SecondaryStream {
 template <bool COUNT, bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS))) k_trace_secondary_stream(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill)
 {
-  pass_priority();
-  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
-  __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
-  const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
-  if (stream_block_idle(count, min_rays)) return;
-  __shared__ HosekSky s_sky;  // (light rays that escape see the sky: resolve_light_ray)
-  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
-  const ClockStamp stamp;
-  CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
-  AlphaLds<AlphaDefer<true, ALPHA>::value>::attach(cl);  // candidates waiting for their any-hit test (fh_trace.h: alpha_ring): LDS of the kernels with the test compiled in only
-  uint32_t nn = 0, nt = 0;
-  WaveSteps ws;
-  SecondaryStream<COUNT, LIGHTS> pol(sc, fr, pool, ChunkFeed(pool.counters + depth * kCounterStride + CNT_CUR_SEC, count, stream_chunk_for(count, chunk)), tc.hist);
-  __shared__ uint4 lds_top[kTopNodes * 4];
-  stage_top_nodes(sc.bvh8, lds_top);
-  traverse_stream<true, COUNT, true, ALPHA>(sc.bvh8, pol, nn, nt, &ws, cl, flush, refill, lds_stack, (int)sc.bvh8.depth, &sc, spill, lds_top,
-                                            spill.probe ? pool.counters + depth * kCounterStride + CNT_COST_NODE : nullptr);
-  pol.finish();
-  stamp.commit(tc.clk);
-  if (COUNT) {
-    atomicAdd(tc.nodes, (unsigned long long)nn);
-    atomicAdd(tc.tris, (unsigned long long)nt);
-    atomicAdd(tc.rays, (unsigned long long)pol.n_rays);
-    pol.hp.flush(tc.hist);
-    if (ws.node) atomicAdd(tc.wave_nodes, (unsigned long long)ws.node);
-    if (ws.tri) atomicAdd(tc.wave_tris, (unsigned long long)ws.tri);
-  }
+  constexpr bool LT = false;
+  const float* const pick_p = nullptr;
+#define FH_BODY_STREAM
+#include "render_secondary_body.inc"
+#undef FH_BODY_STREAM
+}
+template <bool COUNT, bool ALPHA>
+__global__ void __launch_bounds__(kBlock, COUNT ? 1 : FH_SECONDARY_BLOCKS_HEAVY) k_trace_secondary_stream_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill, const float* pick_p)
+{
+  constexpr bool LT = true, LIGHTS = true;
+#define FH_BODY_STREAM
+#include "render_secondary_body.inc"
+#undef FH_BODY_STREAM
 }
 
 // One launch for the secondary rays of bounce b AND the closest-hit rays of bounce b + 1 (calls of ONE pass: the reference's 1- and 16-sample calls).  The two do not
@@ -1494,11 +1444,11 @@ __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLO
 // launches each of them ends in its own few long rays with most of the chip idle.  Here the wave's work queue is the secondary queue followed by the next bounce's radiance
 // queue (one cursor over both): a lane holds either a path with its secondary rays or one closest-hit ray, every ray stops at its first hit or not as its kind says
 // (traverse_stream's per-lane flag), and the launch has ONE end.  Same device functions, same per-path order of operations: the bits do not change.
-template <bool LIGHTS>
+template <bool LIGHTS, bool LT = false>
 struct MergedStream {
   static constexpr bool all_any = false;
   static constexpr bool can_climb = false;
-  SecondaryStream<false, LIGHTS> sec;
+  SecondaryStream<false, LIGHTS, LT> sec;
   const PoolDev& next;        // the view whose radiance queue of bounce b + 1 is traced
   const uint32_t* q_closest;
   uint32_t n_sec;
@@ -1506,8 +1456,8 @@ struct MergedStream {
   uint32_t pc = 0, qc = 0;    // path slot and entry (in the next bounce's radiance queue) of the lane's closest-hit ray
   uint32_t start_closest = 0;
   bool closest = false;       // the lane's current item is a closest-hit ray
-  FH_D MergedStream(const SceneDev& s, const FrameDev& f, const PoolDev& ps, const PoolDev& pn, const uint32_t* qc, uint32_t ns, const ChunkFeed& cf)
-      : sec(s, f, ps, cf, nullptr), next(pn), q_closest(qc), n_sec(ns), feed(cf) {}
+  FH_D MergedStream(const SceneDev& s, const FrameDev& f, const PoolDev& ps, const PoolDev& pn, const uint32_t* qc, uint32_t ns, const ChunkFeed& cf, const float* pp = nullptr)
+      : sec(s, f, ps, cf, nullptr, pp), next(pn), q_closest(qc), n_sec(ns), feed(cf) {}
   FH_D bool advance(f3& o, f3& d, float& tmax, bool& any) { return closest ? false : sec.advance(o, d, tmax, any); }
   FH_D bool take(uint32_t i, f3& o, f3& d, float& tmax, bool& any)
   {
@@ -1534,25 +1484,19 @@ struct MergedStream {
 template <bool LIGHTS, bool ALPHA>
 __global__ void __launch_bounds__(kBlock, LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS)) k_trace_merged_stream(SceneDev sc, FrameDev fr, PoolDev ps, PoolDev pn, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill)
 {
-  pass_priority();
-  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];
-  __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
-  const uint32_t n_sec = ps.counters[depth * kCounterStride + CNT_SEC], n_closest = ps.counters[(depth + 1u) * kCounterStride + CNT_RAD];
-  const uint32_t count = n_sec + n_closest;
-  if (stream_block_idle(count, min_rays)) return;
-  __shared__ HosekSky s_sky;
-  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
-  const ClockStamp stamp;
-  CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
-  AlphaLds<AlphaDefer<true, ALPHA>::value>::attach(cl);  // candidates waiting for their any-hit test (fh_trace.h: alpha_ring): LDS of the kernels with the test compiled in only
-  uint32_t nn = 0, nt = 0;
-  MergedStream<LIGHTS> pol(sc, fr, ps, pn, pn.q_rad[(depth + 1u) & 1u], n_sec, ChunkFeed(ps.counters + depth * kCounterStride + CNT_CUR_SEC, count, stream_chunk_for(count, chunk)));
-  __shared__ uint4 lds_top[kTopNodes * 4];
-  stage_top_nodes(sc.bvh8, lds_top);
-  traverse_stream<true, false, true, ALPHA>(sc.bvh8, pol, nn, nt, nullptr, cl, flush, refill, lds_stack, (int)sc.bvh8.depth, &sc, spill, lds_top,
-                                            spill.probe ? ps.counters + depth * kCounterStride + CNT_COST_NODE : nullptr);
-  pol.sec.finish();
-  stamp.commit(tc.clk);
+  constexpr bool LT = false;
+  const float* const pick_p = nullptr;
+#define FH_BODY_MERGED
+#include "render_secondary_body.inc"
+#undef FH_BODY_MERGED
+}
+template <bool ALPHA>
+__global__ void __launch_bounds__(kBlock, FH_SECONDARY_BLOCKS_HEAVY) k_trace_merged_stream_lt(SceneDev sc, FrameDev fr, PoolDev ps, PoolDev pn, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill, const float* pick_p)
+{
+  constexpr bool LT = true, LIGHTS = true;
+#define FH_BODY_MERGED
+#include "render_secondary_body.inc"
+#undef FH_BODY_MERGED
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1588,15 +1532,26 @@ struct TailRay { bool has = false; bool any = true; f3 o = mk3(0.0f), d = mk3(0.
 template <uint32_t LOBES>
 __global__ void __launch_bounds__(kBlock, LOBES == L_ALL ? 1 : 2) k_tail(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t first_depth, uint32_t coop_flush)
 {
-  constexpr bool ENV = false;
+  constexpr bool ENV = false, LT = false;
   const EnvTable* const env = nullptr;
+  const LightTable* const ltab = nullptr;
 #include "render_tail_body.inc"
 }
 template <uint32_t LOBES>
 __global__ void __launch_bounds__(kBlock, LOBES == L_ALL ? 1 : 2) k_tail_env(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t first_depth, uint32_t coop_flush, EnvTable env_table)
 {
-  constexpr bool ENV = true;
+  constexpr bool ENV = true, LT = false;
   const EnvTable* const env = &env_table;
+  const LightTable* const ltab = nullptr;
+#include "render_tail_body.inc"
+}
+// (fh_set_light_sampling: the tail shades and resolves its light rays inline, so its twin reads the table at both sites)
+template <uint32_t LOBES, bool ENV_ON>
+__global__ void __launch_bounds__(kBlock, LOBES == L_ALL ? 1 : 2) k_tail_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t first_depth, uint32_t coop_flush, EnvTable env_table, LightTable light_table)
+{
+  constexpr bool ENV = ENV_ON, LT = true;
+  const EnvTable* const env = &env_table;
+  const LightTable* const ltab = &light_table;
 #include "render_tail_body.inc"
 }
 
@@ -1733,8 +1688,15 @@ void with_compiled_lobes(uint32_t lobes, LobeSet<V, Rest...>, F&& f)
   else with_compiled_lobes(lobes, LobeSet<Rest...>{}, f);
 }
 
-void dispatch_shade(hipStream_t st, uint32_t grid, uint32_t lobes, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three, const EnvTable* env)
+void dispatch_shade(hipStream_t st, uint32_t grid, uint32_t lobes, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three, const EnvTable* env,
+                    const EnvTable& env_table, const LightTable* lt)
 {
+  if (lt) {  // fh_set_light_sampling: the twins that take the light table, with the environment table read or not
+    with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { with_bool(env != nullptr, [&](auto E) {
+      hipLaunchKernelGGL((k_shade_lt<decltype(V)::value, decltype(E)::value>), dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, env_table, *lt);
+    }); });
+    return;
+  }
   if (env) {
     with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_shade_env<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, *env); });
     return;
@@ -1995,6 +1957,24 @@ int configure_traversal_lds(fh_ctx* ctx, uint32_t stack_bytes)
   set((const void*)k_tail_env<L_METAL | L_SPEC | L_DIFF>);
   set((const void*)k_tail_env<L_COAT | L_METAL | L_SPEC | L_DIFF>);
   set((const void*)k_tail_env<L_ALL>);
+  for (int e = 0; e < 2; ++e)
+    with_bool(e != 0, [&](auto E) {
+      set((const void*)k_tail_lt<L_DIFF, decltype(E)::value>);
+      set((const void*)k_tail_lt<L_METAL | L_SPEC | L_DIFF, decltype(E)::value>);
+      set((const void*)k_tail_lt<L_COAT | L_METAL | L_SPEC | L_DIFF, decltype(E)::value>);
+      set((const void*)k_tail_lt<L_ALL, decltype(E)::value>);
+    });
+  for (int a = 0; a < 2; ++a)
+    with_bool(a != 0, [&](auto A) {
+      set((const void*)k_trace_merged_stream_lt<decltype(A)::value>);
+      for (int c = 0; c < 2; ++c)
+        with_bool(c != 0, [&](auto C) {
+          set((const void*)k_trace_secondary_stream_lt<decltype(C)::value, decltype(A)::value>);
+          set((const void*)k_trace_secondary_coop_lt<decltype(C)::value, decltype(A)::value>);
+          set((const void*)k_trace_secondary_static_lt<decltype(C)::value, true, decltype(A)::value>);
+          set((const void*)k_trace_secondary_static_lt<decltype(C)::value, false, decltype(A)::value>);
+        });
+    });
   if (err != hipSuccess) return fail(ctx, FH_E_HIP, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(err));
   ctx->lds_configured_bytes = stack_bytes;
   ctx->lds_static_max = max_static;
@@ -2414,6 +2394,8 @@ struct Call {
   StreamPlan plan;
   EnvTable env;  // fh_set_env_sampling; env_on: the shade kernels and the fused tail of this call are the ENV variants
   bool env_on;
+  LightTable lt;  // fh_set_light_sampling; lt_on (the switch is on AND the scene has emitters): the shade, tail and secondary-ray kernels of this call are the twins that take it
+  bool lt_on;
 };
 
 // one pass: its pool slot and streams, and what was chosen for it
@@ -2508,7 +2490,23 @@ void launch_secondary(const Call& c, const Pass& p, const PoolDev& ps, uint32_t 
   const StreamPlan& pl = c.plan;
   const SceneDev& sc = p.sc;
   Span sp(ctx, p.sb, 1);
-  if (pl.stream) {
+  if (c.lt_on) {  // (the scene has emitters: the LIGHTS forms)
+    if (pl.stream) {
+      with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
+        hipLaunchKernelGGL((k_trace_secondary_stream_lt<decltype(C)::value, decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.sb, sc, c.fr, ps, depth,
+                           c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u), c.lt.pick_p);
+      }); });
+    } else if (pl.coop) {
+      with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
+        hipLaunchKernelGGL((k_trace_secondary_coop_lt<decltype(C)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps, depth, c.tc_shadow, p.coop_flush, c.lt.pick_p);
+      }); });
+    } else {
+      with_bool(c.count, [&](auto C) { with_bool(sc.use_bvh8 != 0, [&](auto W) { with_bool(sc.has_alpha != 0, [&](auto A) {
+        hipLaunchKernelGGL((k_trace_secondary_static_lt<decltype(C)::value, decltype(W)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps, depth, c.tc_shadow,
+                           c.lt.pick_p);
+      }); }); });
+    }
+  } else if (pl.stream) {
     with_secondary_stream(c.count, sc.n_lights > 0, sc.has_alpha != 0, [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.sb, sc, c.fr, ps, depth, c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1],
                          ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u));
@@ -2534,7 +2532,11 @@ void launch_merged(const Call& c, const Pass& p, const PoolDev& ps, const PoolDe
   const StreamPlan& pl = c.plan;
   const SceneDev& sc = p.sc;
   Span sp(ctx, p.st, 1);
-  with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
+  if (c.lt_on) with_bool(sc.has_alpha != 0, [&](auto A) {
+    hipLaunchKernelGGL((k_trace_merged_stream_lt<decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.st, sc, c.fr, ps, pd, depth,
+                       c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u), c.lt.pick_p);
+  });
+  else with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
     hipLaunchKernelGGL((k_trace_merged_stream<decltype(Li)::value, decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.st, sc, c.fr, ps, pd, depth,
                        c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u));
   }); });
@@ -2551,7 +2553,10 @@ void launch_tail(const Call& c, const Pass& p, const PoolDev& pd, uint32_t n_pat
   for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) lobes |= ctx->class_lobes[cls];
   const dim3 tg(grid_for(n_paths / 16 + 1)), tb(kBlock);
   const uint32_t tl = p.sc.use_bvh8 ? c.plan.stack_bytes : 0u, tf = c.plan.coop ? p.coop_flush : 0u;
-  if (c.env_on) with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_tail_env<decltype(V)::value>, tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf, c.env); });
+  if (c.lt_on) with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { with_bool(c.env_on, [&](auto E) {
+    hipLaunchKernelGGL((k_tail_lt<decltype(V)::value, decltype(E)::value>), tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf, c.env, c.lt);
+  }); });
+  else if (c.env_on) with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_tail_env<decltype(V)::value>, tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf, c.env); });
   else with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_tail<decltype(V)::value>, tg, tb, tl, p.st, p.sc, c.fr, pd, p.wave_depth, tf); });
   ctx->stats.n_tail_launches++;
 }
@@ -2661,7 +2666,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
     if (p.overlap && depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (depth - 1u) + 1u], 0));  // the secondary launch of the bounce before reads what the shade kernels and the sorts below overwrite
     {
       Span sp(ctx, st, 2);
-      for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) dispatch_shade(st, p.grid, ctx->class_lobes[cls], p.sc, c.fr, pd, cls, depth, c.plan.shade_three, c.env_on ? &c.env : nullptr);
+      for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) dispatch_shade(st, p.grid, ctx->class_lobes[cls], p.sc, c.fr, pd, cls, depth, c.plan.shade_three, c.env_on ? &c.env : nullptr, c.env, c.lt_on ? &c.lt : nullptr);
       if (depth == 0) hipLaunchKernelGGL(k_miss_primary, dim3(p.grid), dim3(kBlock), 0, st, c.fr, pd);
       ctx->stats.n_shade_launches += ctx->n_classes;
     }
@@ -2739,7 +2744,8 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   const bool clocks = (ctx->flags & FH_FLAG_TIME_KERNELS) != 0;
   Call c{ctx, frame_dev(ctx, cam, bg, seed, max_depth), layers_dev(ctx, layers), SceneDev{},
          TraceCounters{tc, tc + 1, tc + 2, tc + 6, tc + 7, tc + 10, clocks ? tc + 27 : nullptr}, TraceCounters{tc + 3, tc + 4, tc + 5, tc + 8, tc + 9, tc + 18, clocks ? tc + 29 : nullptr},
-         max_depth, adaptive, quirk, count, StreamPlan{}, env_table_dev(ctx), ctx->env_sampling != 0};
+         max_depth, adaptive, quirk, count, StreamPlan{}, env_table_dev(ctx), ctx->env_sampling != 0, light_table_dev(ctx), ctx->light_sampling != 0 && ctx->n_lights > 0};
+  if (c.lt_on) { const int rc = light_table_ensure(ctx); if (rc) return rc; c.lt = light_table_dev(ctx); }  // (as the environment's, below: rebuilt on the main stream ahead of everything this call queues; the rebuild may allocate)
   if (c.env_on) { const int rc = env_table_ensure(ctx); if (rc) return rc; }  // (a stale table is rebuilt on the main stream, ahead of everything this call queues)
   PixelLists base;  // the pixels of the call
   { const int rc = choose_pixels(ctx, cam, c.fr, n_samples, quirk, base); if (rc) return rc; }

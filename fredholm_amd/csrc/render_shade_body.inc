@@ -1,5 +1,5 @@
-// render_shade_body.inc -- the body of k_shade and k_shade_env (render.hip includes it into both).  In scope: sc, fr, pool, cls, depth; ENV and env
-// It is text, not a function: it reads the names sc, fr, pool, ENV and env of the kernel it is included into.  The plain k_shade must keep its instruction stream, so after ANY
+// render_shade_body.inc -- the body of k_shade, k_shade_env and k_shade_lt (render.hip includes it into all three).  In scope: sc, fr, pool, cls, depth; ENV and env; LT and ltab
+// It is text, not a function: it reads the names sc, fr, pool, ENV, env, LT and ltab of the kernel it is included into.  The plain k_shade must keep its instruction stream, so after ANY
 // edit here compare a device listing of render.hip with the one before the edit (tools/kernel_asm_diff.py): k_shade<...> may differ in nothing.
 // (One change altered that stream on purpose, from outside this file: the divisions of concentric_disk and of the Hosek sky took their short form -- fh_vec.h: div_r.  The
 // listing to compare with is the one from after it.)
@@ -51,7 +51,7 @@
       PoolSink o(pool, p, hit.x);
       const bool first = depth != 0 || (pool.flags[p] & 4u) == 0u;
       const f3 L = depth == 0u ? mk3(pool.rad[p]) : mk3(0.0f);  // the radiance so far only enters at a directly visible emitter (first hit): later bounces skip the load
-      shade_hit<LOBES, ENV>(sc, fr, rows, bs, depth, hit, mk3(pool.ray_d[p]), mk3(pool.thr[p]), L, pool.pixel[p], pool.nspp[p], o, first, env);
+      shade_hit<LOBES, ENV, LT>(sc, fr, rows, bs, depth, hit, mk3(pool.ray_d[p]), mk3(pool.thr[p]), L, pool.pixel[p], pool.nspp[p], o, first, env, ltab);
       shaded = o.shaded;
       cont = o.cont;
       if (shaded || cont) cell = cell_of(fr, o.origin);

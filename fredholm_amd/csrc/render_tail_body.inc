@@ -1,5 +1,5 @@
-// render_tail_body.inc -- the body of k_tail and k_tail_env (render.hip includes it into both).  In scope: sc, fr, pool, first_depth, coop_flush; ENV and env
-// It is text, not a function: it reads the names sc, fr, pool, ENV and env of the kernel it is included into.  The plain k_tail must keep its instruction stream, so after ANY
+// render_tail_body.inc -- the body of k_tail, k_tail_env and k_tail_lt (render.hip includes it into all three).  In scope: sc, fr, pool, first_depth, coop_flush; ENV and env; LT and ltab
+// It is text, not a function: it reads the names sc, fr, pool, ENV, env, LT and ltab of the kernel it is included into.  The plain k_tail must keep its instruction stream, so after ANY
 // edit here compare a device listing of render.hip with the one before the edit (tools/kernel_asm_diff.py): k_tail<...> may differ in nothing.
   pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // traversal stack of every lane ([entry][thread], as in the streaming kernels): a private array lands in scratch
@@ -100,7 +100,7 @@
       ShadeOut o;
       if (alive) {
         if (!hit) alive = false;  // pt.cu:504-523 with firsthit == false: nothing added
-        else shade_hit<LOBES, ENV>(sc, fr, rows, bs, depth, make_float4(h.t, h.u, h.v, __uint_as_float(h.prim)), rd, T, L, image_idx, n_spp, o, true, env);
+        else shade_hit<LOBES, ENV, LT>(sc, fr, rows, bs, depth, make_float4(h.t, h.u, h.v, __uint_as_float(h.prim)), rd, T, L, image_idx, n_spp, o, true, env, ltab);
       }
       TailRay rays[kTailRays];
 #pragma unroll
@@ -117,7 +117,7 @@
 #pragma unroll
       for (uint32_t slot = SEC_DIR; slot <= SEC_LIGHT; ++slot) {
         if (!rays[slot].has) continue;
-        if (slot == SEC_LIGHT && has_lights) L += resolve_light_ray(sc, fr, o.lp_T, o.lp_cos, o.lp_f, o.lp_pdf, o.sec[slot].o, o.sec[slot].d, rays[slot].hit, rays[slot].h);
+        if (slot == SEC_LIGHT && has_lights) L += resolve_light_ray<LT>(sc, fr, o.lp_T, o.lp_cos, o.lp_f, o.lp_pdf, o.sec[slot].o, o.sec[slot].d, rays[slot].hit, rays[slot].h, LT ? ltab->pick_p : nullptr);
         else if (!rays[slot].hit) L += o.sec[slot].c;
       }
       if (alive) {

@@ -68,6 +68,7 @@ int transform_faces(fh_ctx* ctx)
   FH_HIP(hipGetLastError());
   FH_HIP(hipStreamSynchronize(ctx->stream));  // the host copies of the transforms may change right after this call
   ctx->bvh_valid = false;
+  ctx->light_stale = true;  // (fh_set_light_sampling: areas, and after an upload the emitters themselves, are new)
   return FH_OK;
 }
 

@@ -119,6 +119,7 @@ EXPORTS = [
     "fh_set_auto_exposure", "fh_get_auto_exposure", "fh_auto_exposure_reset", "fh_meter_exposure", "fh_get_auto_exposure_state", "fh_get_luminance_histogram",
     "fh_set_local_exposure", "fh_get_local_exposure", "fh_local_exposure_analyse", "fh_get_local_exposure_base",
     "fh_set_env_sampling", "fh_get_env_sampling", "fh_kat_env_table", "fh_kat_env_sample", "fh_kat_env_pdf", "fh_kat_env_radiance",
+    "fh_set_light_sampling", "fh_get_light_sampling", "fh_kat_light_table", "fh_kat_light_pick",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -186,6 +187,14 @@ class EnvSamplingParamsC(C.Structure):
 ENV_COSINE_FRACTION_DEFAULT = 0.5  # FH_ENV_COSINE_FRACTION_DEFAULT
 
 
+class LightSamplingParamsC(C.Structure):
+    """fh_light_sampling_params (include/fredholm_hip.h)"""
+    _fields_ = [("uniform_fraction", C.c_float)]
+
+
+LIGHT_UNIFORM_FRACTION_DEFAULT = 0.0625  # FH_LIGHT_UNIFORM_FRACTION_DEFAULT
+
+
 class AutoExposureStateC(C.Structure):
     """fh_auto_exposure_state (include/fredholm_hip.h)"""
     _fields_ = [("ev", C.c_float), ("target_ev", C.c_float), ("mean_log2", C.c_float), ("metered", C.c_uint32), ("unmetered", C.c_uint32), ("frames", C.c_uint32)]
@@ -235,6 +244,10 @@ SIGNATURES = {
     "fh_kat_env_sample": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fh_kat_env_pdf": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fh_kat_env_radiance": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "fh_set_light_sampling": [C.c_void_p, C.POINTER(LightSamplingParamsC)],
+    "fh_get_light_sampling": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(LightSamplingParamsC)],
+    "fh_kat_light_table": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)],
+    "fh_kat_light_pick": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
     "fh_kat_chief_rays": [C.c_void_p, C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_void_p],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],

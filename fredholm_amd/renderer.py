@@ -532,6 +532,24 @@ class Renderer:
         self._ck(N.lib().fh_get_env_sampling(self._ctx, C.byref(on), C.byref(p)), "fh_get_env_sampling")
         return bool(on.value), float(p.cosine_fraction)
 
+    # -- sampling of area lights by power (fh_set_light_sampling)
+    def set_light_sampling(self, uniform_fraction=N.LIGHT_UNIFORM_FRACTION_DEFAULT):
+        """fh_set_light_sampling: while on, the emitter of every area shadow ray is picked from a table of the emitters' power (area x luminance of the emission) mixed
+        with the uniform pick (share `uniform_fraction`, in (0, 1]), and the BSDF-sampled light ray that finds an emitter is weighed against that pick.  The table is
+        rebuilt by the next render after the scene or its transforms change.  Nothing else of a frame changes; off (the default) keeps every bit"""
+        p = N.LightSamplingParamsC(float(uniform_fraction))
+        self._ck(N.lib().fh_set_light_sampling(self._ctx, C.byref(p)), "fh_set_light_sampling")
+
+    def clear_light_sampling(self):
+        """off: the uniform pick of the reference"""
+        self._ck(N.lib().fh_set_light_sampling(self._ctx, None), "fh_set_light_sampling")
+
+    def get_light_sampling(self):
+        """(on, uniform_fraction): the switch and the fraction last set (the default before any)"""
+        on, p = C.c_int(0), N.LightSamplingParamsC()
+        self._ck(N.lib().fh_get_light_sampling(self._ctx, C.byref(on), C.byref(p)), "fh_get_light_sampling")
+        return bool(on.value), float(p.uniform_fraction)
+
     # -- auto-exposure of the post chain (fh_set_auto_exposure)
     def set_auto_exposure(self, key=0.18, compensation_ev=0.0, min_ev=-16.0, max_ev=16.0, low=0.10, high=0.90, speed_up=3.0, speed_down=1.0, frame_time=1.0 / 30.0,
                           log2_lo=-16.0, log2_hi=16.0, bloom_relative=False):

@@ -31,8 +31,18 @@ class Renderer
  public:
   // FH_ENV_SAMPLING gives an application that is not edited importance sampling of the environment (fh_set_env_sampling): unset or 0: off; 1: on with the
   // library's cosine fraction; any other number: on with that fraction (one the library refuses throws here).  set_env_sampling / clear_env_sampling win.
+  // FH_LIGHT_SAMPLING does the same for the sampling of area lights by power (fh_set_light_sampling): unset or 0: off; 1: on with the library's uniform fraction (a
+  // fraction of 1 -- all picks uniform -- is spelt 1.0 like any other and means the library's all the same: ask for it with set_light_sampling(1.0f)); any other
+  // number: on with that fraction.
   explicit Renderer(const OptixDeviceContext& context) : m_ctx(context)
   {
+    if (const char* e = std::getenv("FH_LIGHT_SAMPLING")) {
+      char* end = nullptr;
+      const float v = std::strtof(e, &end);
+      if (end == e || *end != '\0') throw std::runtime_error("FH_LIGHT_SAMPLING: not a number");
+      if (v == 1.0f) set_light_sampling();
+      else if (v != 0.0f) set_light_sampling(v);
+    }
     if (const char* e = std::getenv("FH_ENV_SAMPLING")) {
       char* end = nullptr;
       const float v = std::strtof(e, &end);
@@ -87,6 +97,14 @@ class Renderer
     cwl::check(m_ctx, fh_set_env_sampling(m_ctx, &p), "fh_set_env_sampling");
   }
   void clear_env_sampling() { cwl::check(m_ctx, fh_set_env_sampling(m_ctx, nullptr), "fh_set_env_sampling"); }
+  // sampling of area lights by power for the area shadow rays (no counterpart in the reference, pt.cu:860-889); without an argument: the library's uniform fraction
+  void set_light_sampling() { set_light_sampling(FH_LIGHT_UNIFORM_FRACTION_DEFAULT); }
+  void set_light_sampling(float uniform_fraction)
+  {
+    const fh_light_sampling_params p = {uniform_fraction};
+    cwl::check(m_ctx, fh_set_light_sampling(m_ctx, &p), "fh_set_light_sampling");
+  }
+  void clear_light_sampling() { cwl::check(m_ctx, fh_set_light_sampling(m_ctx, nullptr), "fh_set_light_sampling"); }
 
   void set_time(float time)  // renderer.h:614-640: animation update, transform re-upload, acceleration-structure rebuild
   {

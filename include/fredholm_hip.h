@@ -678,7 +678,7 @@ int fh_get_local_exposure_base(fh_ctx* ctx, float* base, uint32_t* w4, uint32_t*
  *       cos' = PI * p(d) and f' = f * |cos| / cos', which makes the miss density p(d) and leaves the product T * w * f * |cos| / pdf in both branches.
  * The table is rebuilt, on the context stream and without a host synchronisation, by the first fh_render after fh_load_ibl, fh_clear_ibl, fh_load_arhosek_sky,
  * fh_clear_arhosek_sky or a call of this function that turns the switch on; a change of cosine_fraction alone keeps it.
- * Not covered: sampling the product of BSDF and environment, a table resolution parameter, sampling area lights by power. */
+ * Not covered: sampling the product of BSDF and environment, a table resolution parameter.  (Sampling area lights by power: fh_set_light_sampling, below.) */
 #define FH_ENV_COSINE_FRACTION_DEFAULT 0.5f
 typedef struct fh_env_sampling_params {
   float cosine_fraction; /* B: share of sky rays drawn cosine-distributed, in [0, 1); default FH_ENV_COSINE_FRACTION_DEFAULT (DESIGN.md 4 has the rule that chose it) */
@@ -688,6 +688,49 @@ typedef struct fh_env_sampling_params {
 int fh_set_env_sampling(fh_ctx* ctx, const fh_env_sampling_params* params);
 /* *on = 0 or 1; params (may be NULL) receives the fraction last set (the default before any) */
 int fh_get_env_sampling(fh_ctx* ctx, int* on, fh_env_sampling_params* params);
+
+/* -- sampling of area lights by power for the area next-event ray (opt-in, default off; with it off every render keeps its bits, its launches and its kernels).
+ * The emissive triangle of a shaded hit's area shadow ray is picked uniformly among the scene's n emitters (pt.cu:860-889), and the BSDF-sampled light ray that finds
+ * an emitter is weighed against that density, 1 / (n * area).  While this switch is on the pick follows a table of the emitters' power, mixed with the uniform pick
+ * (share uniform_fraction = U), and both sites use the pick's probability P: pdf_area = P / area.  Nothing else of a frame changes: the pick is made from the same
+ * Sobol' dimension, and every other draw, slot, kernel and layer is as it is with the switch off.  A scene without emitters builds nothing and renders with the
+ * plain kernels.
+ * All of it is fp32 without contraction, / and sqrt correctly rounded, sums in the order written; fmax / fmin are C's (a NaN operand loses).
+ *   Emitter k is the k-th emissive face in face order (f its face, m its material), as the uniform pick numbers them.
+ *   area = 0.5f * length(cross(p1 - p0, p2 - p0)) of the world-space corners, the expression of the shadow ray's density.
+ *   e = m's emission colour; when m has an emission texture, per channel the serial sum over s = 0 .. 15 of the texture's fetch at the texture coordinate of the
+ *     barycentric point (bu, bv)_s, divided by 16.0f.  The points are the centroids of the 16 congruent triangles the face splits into:
+ *       s = 0 .. 9:   rows j = 0 .. 3 of 4 - j points i = 0 .. 3 - j (j outer, i inner): bu = (float)(3 i + 1) / 12.0f, bv = (float)(3 j + 1) / 12.0f;
+ *       s = 10 .. 15: rows j = 0 .. 2 of 3 - j points i = 0 .. 2 - j:                    bu = (float)(3 i + 2) / 12.0f, bv = (float)(3 j + 2) / 12.0f;
+ *     bw = 1.0f - bu - bv and the coordinate is (bw * t0 + bu * t1) + bv * t2 per component, t0, t1, t2 the corners' -- what the shadow ray's sample forms.
+ *   l = fmax((finite(e.r) * 0.2126729f + finite(e.g) * 0.7151522f) + finite(e.b) * 0.0721750f, 0), finite(x) = 0 for a NaN or |x| > 3e38, else x.
+ *   w = fmin(area * l, 3e38f).  (The `emission` scalar of fh_material is not part of it: the emission the kernels add does not read it.)
+ *   Quantisation: w_max = the largest w;  q_k = max(1, (uint32)((w_k / w_max) * 1048576.0f)), and q_k = 1 for every k when w_max == 0.  So black emitters,
+ *     zero-area ones, NaN texels and those below 2^-20 of the maximum all keep a positive weight.  T = sum of q_k, 64 bits: exact, independent of the order.
+ *   Stored: q[n];  cdf[k] = (float)((double)(q_0 + .. + q_(k - 1)) / (double)T), k = 0 .. n (first 0, last 1);
+ *     P_k = (1 - U) * (float)((double)q_k / (double)T) + U / (float)n, kept per FACE: pick_p[f] = P_k for the emitter's face, 0 for a face that does not emit.
+ *   The pick, from the draw u1 in [0, 1) of the area dimension:  u1 < U: u = u1 / U and k = min((uint32)(u * n), n - 1), today's pick;
+ *     otherwise u = fmin((u1 - U) / (1 - U), 0.99999994f) and k = lo after  lo = 0, hi = n; while (hi - lo > 1) { mid = (lo + hi) >> 1; if (cdf[mid] <= u) lo = mid;
+ *     else hi = mid; }.  The reported probability is P_k in both branches: the true mixture.
+ *   The two sites: the area shadow ray uses pdf_area = P_k / area in place of 1 / (n * area); the BSDF-sampled light ray whose closest hit is an emitter uses
+ *     pdf_area = pick_p[face hit] / area.  r^2 / |cos|, the facing test, the clamp and the order of additions are untouched, and so is what fh_set_env_sampling hands
+ *     to that ray while both switches are on.
+ *   U guards against a textured emitter whose 16 points misjudge it and against CDF intervals that round to nothing in fp32 among millions of emitters: whatever the
+ *     table says, every emitter is picked with at least U / n.
+ * The table is rebuilt, on the context stream, by the first fh_render after fh_scene_upload, fh_set_transforms (areas change) or a call of this function that turns
+ * the switch on or changes uniform_fraction (everything is rebuilt, not pick_p alone).  The rebuild synchronises with the host only where it has to allocate: after an
+ * upload that changed the number of emitters or faces.
+ * Where the clamp binds (glossy lobes: T * w * f * |cos| / pdf above 1) the expectation depends on the pick distribution, as it depends on n today.
+ * Not covered: a light hierarchy or any pick that depends on the shaded point, sampling the product with the BSDF. */
+#define FH_LIGHT_UNIFORM_FRACTION_DEFAULT 0.0625f
+typedef struct fh_light_sampling_params {
+  float uniform_fraction; /* U: share of picks that stay uniform, in (0, 1]; default FH_LIGHT_UNIFORM_FRACTION_DEFAULT (DESIGN.md 4 has the rule that chose it) */
+} fh_light_sampling_params;
+/* params == NULL: off.  A scene call: on a group it reaches every member.  FH_E_INVALID, decided from the arguments alone before the context is looked at, for a
+ * uniform_fraction outside (0, 1] or NaN; the switch then stays as it was. */
+int fh_set_light_sampling(fh_ctx* ctx, const fh_light_sampling_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the fraction last set (the default before any) */
+int fh_get_light_sampling(fh_ctx* ctx, int* on, fh_light_sampling_params* params);
 
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */

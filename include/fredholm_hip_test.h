@@ -87,6 +87,12 @@ int fh_kat_env_sample(fh_ctx* ctx, uint32_t n, const float* u2, const float* nor
 int fh_kat_env_pdf(fh_ctx* ctx, uint32_t n, const float* dirs3, const float* normal3, float* pdf, uint32_t* cell);
 /* the environment along n directions as the table weighs it -- the image, else the Hosek dome, else white, at sky intensity 1; works with the switch off */
 int fh_kat_env_radiance(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3);
+/* fh_set_light_sampling (include/fredholm_hip.h), on the context's CURRENT table (a stale one is rebuilt first, as fh_render does); FH_E_INVALID while the switch is
+ * off or the scene has no emitters.  n_lights: fh_scene_n_lights.
+ * fh_kat_light_table: the integer weights q [n_lights], cdf [n_lights + 1], the pick probabilities in LIGHT order [n_lights] and the total; any pointer may be NULL.
+ * fh_kat_light_pick: n draws u1 of the area dimension -> the emitter's index in light order and the reported probability, exactly as shade_hit picks. */
+int fh_kat_light_table(fh_ctx* ctx, uint32_t* q, float* cdf, float* pick_p_per_light, uint64_t* total);
+int fh_kat_light_pick(fh_ctx* ctx, uint32_t n, const float* u1, uint32_t* index, float* p);
 
 #ifdef __cplusplus
 }
