@@ -27,6 +27,8 @@
 //                                         the cosine lobe at share B in [0, 1) (default: the library's); without it they are cosine-distributed as in the reference)
 //          [--light-sampling [--light-uniform-fraction U]]   (the emitter of every area shadow ray is picked by power -- area x luminance of its emission -- mixed with the
 //                                         uniform pick at share U in (0, 1] (default: the library's); without it the pick is uniform as in the reference)
+//          [--light-resampling [M]]   (with --light-sampling: M candidates of the table -- 1, 2, 4, 8 or 16, default: the library's -- are drawn for every area shadow ray
+//                                         and one is chosen by its distance and facing from the shaded point)
 //          [--devices 0,1,...]   (every frame split by pixel tile across these GPUs: the same meaning as the FH_DEVICES variable, and the flag wins; an index may repeat)
 #include <chrono>
 #include <cmath>
@@ -75,6 +77,8 @@ int main(int argc, char** argv)
   float env_fraction = FH_ENV_COSINE_FRACTION_DEFAULT;
   bool light_sampling = false, light_fraction_given = false;  // --light-sampling, --light-uniform-fraction (with --light-sampling only)
   float light_fraction = FH_LIGHT_UNIFORM_FRACTION_DEFAULT;
+  bool light_resampling = false;  // --light-resampling [M] (with --light-sampling only)
+  int light_candidates = FH_LIGHT_CANDIDATES_DEFAULT;
   std::vector<int> devices;  // --devices: empty = FH_DEVICES, or device 0
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -115,6 +119,14 @@ int main(int argc, char** argv)
     else if (a == "--env-cosine-fraction") { env_fraction = float(std::atof(next())); env_fraction_given = true; }
     else if (a == "--light-sampling") light_sampling = true;
     else if (a == "--light-uniform-fraction") { light_fraction = float(std::atof(next())); light_fraction_given = true; }
+    else if (a == "--light-resampling") {
+      light_resampling = true;
+      if (i + 1 < argc && argv[i + 1][0] != '-') {  // the count is optional
+        char* end = nullptr;
+        const long m = std::strtol(argv[++i], &end, 10);
+        light_candidates = (*end == '\0' && end != argv[i] && m >= 0 && m <= 1000) ? int(m) : 0;
+      }
+    }
     else if (a == "--exposure-key") { exposure.key = float(std::atof(next())); if (!exposure_flag) exposure_flag = "--exposure-key"; }
     else if (a == "--exposure-comp") { exposure.compensation_ev = float(std::atof(next())); if (!exposure_flag) exposure_flag = "--exposure-comp"; }
     else if (a == "--exposure-speed") { exposure.speed_up = float(std::atof(next())); exposure.speed_down = float(std::atof(next())); if (!exposure_flag) exposure_flag = "--exposure-speed"; }
@@ -124,7 +136,7 @@ int main(int argc, char** argv)
     }
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]] [--auto-exposure [--exposure-key K] [--exposure-comp EV] [--exposure-speed UP DOWN] [--bloom-relative]] [--local-exposure [--local-highlights H] [--local-shadows S] [--local-sigma R] [--local-passes P]] [--env-sampling [--env-cosine-fraction B]] [--light-sampling [--light-uniform-fraction U]] [--devices 0,1,...]\n", argv[0]); return 2; }
+  if (scene_files.empty()) { std::fprintf(stderr, "usage: %s --scene file.obj|file.gltf [--scene ...] [--out DIR] [--width W --height H --spp N --depth D] [--fps F --max-time T] [--bloom] [--sun] [--sky] [--ibl env.hdr] [--noise-threshold T [--min-spp M --adaptive-step S --adaptive-block G --adaptive-growth K]] [--denoiser atrous|guided|temporal|temporal-motion|temporal-response|temporal-motion-response|temporal-response-noise|temporal-motion-response-noise] [--denoise-gamma G] [--denoise-kappa K] [--denoise-temporal-moments [--denoise-min-history H]] [--auto-exposure [--exposure-key K] [--exposure-comp EV] [--exposure-speed UP DOWN] [--bloom-relative]] [--local-exposure [--local-highlights H] [--local-shadows S] [--local-sigma R] [--local-passes P]] [--env-sampling [--env-cosine-fraction B]] [--light-sampling [--light-uniform-fraction U] [--light-resampling [M]]] [--devices 0,1,...]\n", argv[0]); return 2; }
   if (noise_threshold >= 0.0f && (min_spp < 2 || adaptive_step < 1)) { std::fprintf(stderr, "--min-spp must be >= 2 and --adaptive-step >= 1\n"); return 2; }
   if (adaptive_block != 1 && adaptive_block != 2 && adaptive_block != 4 && adaptive_block != 8) { std::fprintf(stderr, "--adaptive-block must be 1, 2, 4 or 8\n"); return 2; }
   if (adaptive_growth != 1 && adaptive_growth != 2) { std::fprintf(stderr, "--adaptive-growth must be 1 or 2\n"); return 2; }
@@ -153,6 +165,8 @@ int main(int argc, char** argv)
   if (!(env_fraction >= 0.0f && env_fraction < 1.0f)) { std::fprintf(stderr, "--env-cosine-fraction must be in [0, 1)\n"); return 2; }
   if (light_fraction_given && !light_sampling) { std::fprintf(stderr, "--light-uniform-fraction goes with --light-sampling\n"); return 2; }
   if (!(light_fraction > 0.0f && light_fraction <= 1.0f)) { std::fprintf(stderr, "--light-uniform-fraction must be in (0, 1]\n"); return 2; }
+  if (light_resampling && !light_sampling) { std::fprintf(stderr, "--light-resampling goes with --light-sampling\n"); return 2; }
+  if (light_candidates != 1 && light_candidates != 2 && light_candidates != 4 && light_candidates != 8 && light_candidates != 16) { std::fprintf(stderr, "--light-resampling takes 1, 2, 4, 8 or 16\n"); return 2; }
   if (auto_exposure && !(fps > 0.0f)) { std::fprintf(stderr, "--auto-exposure needs --fps > 0\n"); return 2; }
   const bool guided = denoiser_name == "guided" || temporal;  // (temporal: the same guides)
   const float time_step = 1.0f / fps;
@@ -170,6 +184,7 @@ int main(int argc, char** argv)
     if (reference_launches) renderer.set_reference_launch_semantics(true);
     if (env_sampling) renderer.set_env_sampling(env_fraction);
     if (light_sampling) renderer.set_light_sampling(light_fraction);
+    if (light_resampling) renderer.set_light_resampling(light_candidates);
 
     const size_t n_px = size_t(width) * size_t(height);
     cwl::CUDABuffer<float4> layer_beauty(n_px), layer_position(n_px), layer_normal(n_px), layer_texcoord(n_px), layer_albedo(n_px), layer_denoised(n_px);

@@ -477,6 +477,25 @@ int fh_get_light_sampling(fh_ctx* ctx, int* on, fh_light_sampling_params* params
   if (params) params->uniform_fraction = ctx->light_uniform_fraction;
   return FH_OK;
 }
+// resampling of the table's picks (fh_lights.h): refused from the arguments alone; a scene call.  Nothing is rebuilt and nothing waited for: the proxies exist whenever
+// the table does, and M reaches the kernels by value
+int fh_set_light_resampling(fh_ctx* ctx, const fh_light_resampling_params* params)
+{
+  if (const char* why = light_resampling_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_light_resampling: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_light_resampling(m_, params));
+  CTX_CHECK(ctx);
+  ctx->light_resampling = params ? 1 : 0;
+  if (params) ctx->light_candidates = params->candidates;
+  return FH_OK;
+}
+int fh_get_light_resampling(fh_ctx* ctx, int* on, fh_light_resampling_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->light_resampling;
+  if (params) params->candidates = ctx->light_candidates;
+  return FH_OK;
+}
 
 // the moments of adaptive sampling start at sample 0: allocated and cleared whenever the mode is on and the counters are reset (0 * inf would poison a reset's
 // running means otherwise), and when the mode is turned on

@@ -162,6 +162,10 @@ struct fh_ctx {
   fh::DeviceBuffer<uint32_t> d_light_q;                 // integer weights, then the sums of the chunks of 256
   fh::DeviceBuffer<unsigned long long> d_light_offsets; // exclusive scan of the chunk sums, then the total
   fh::DeviceBuffer<float> d_light_cdf, d_light_pick_p;  // [n_lights + 1]; [n_faces]
+  // fh_set_light_resampling: acts while light_sampling is on.  The proxies are built and rebuilt with the table, so the switch and M alone rebuild nothing
+  int light_resampling = 0;
+  int light_candidates = FH_LIGHT_CANDIDATES_DEFAULT;
+  fh::DeviceBuffer<fh::LightProxy> d_light_proxy;       // [n_lights]
 
   // path pools: one per pass in flight (pass j uses slot j % n_slots and the stream of that slot); allocated on first use
   fh::PoolDev pool[3] = {};
@@ -344,7 +348,10 @@ uint32_t owned_count(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, 
 Event take_event(fh_ctx* ctx);  // render.hip: a timing event from ctx->event_pool, or a new one
 SceneDev scene_dev(const fh_ctx* ctx);
 inline EnvTable env_table_dev(const fh_ctx* ctx) { return EnvTable{ctx->d_env_cdf_row, ctx->d_env_cdf_m, ctx->d_env_cell_p, ctx->env_cosine_fraction}; }
-inline LightTable light_table_dev(const fh_ctx* ctx) { return LightTable{ctx->d_light_cdf, ctx->d_light_pick_p, ctx->light_uniform_fraction}; }
+inline LightTable light_table_dev(const fh_ctx* ctx)
+{
+  return LightTable{ctx->d_light_cdf, ctx->d_light_pick_p, ctx->light_uniform_fraction, ctx->d_light_proxy, ctx->light_resampling ? (uint32_t)ctx->light_candidates : 1u};
+}
 int bvh_build_device(fh_ctx* ctx);                 // bvh_build.hip
 void reset_tree_measurements(fh_ctx* ctx);         // bvh_build.hip: a new tree; what the render path has measured on the old one (bu_*, survival) starts again
 int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_render_layers* layers, uint32_t n_samples, uint32_t max_depth, uint32_t seed);  // render.hip

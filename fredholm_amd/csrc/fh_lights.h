@@ -20,7 +20,21 @@ struct LightTable {
   const float* cdf;      // [n_lights + 1]  ascending, first 0, last 1
   const float* pick_p;   // [n_faces]       the pick probability P of the emitter that is this face; 0 for a face that does not emit
   float uniform;         // U: share of the picks that stay uniform
+  // fh_set_light_resampling: the emitters' proxies [n_lights], built with the table, and M (1: no resampling, the table's pick as it is)
+  const struct LightProxy* proxy = nullptr;
+  uint32_t candidates = 1;
 };
+
+// what the resampling knows of an emitter: two float4 -- (centroid, area) and (mean shading normal or the zero vector, 0)
+struct alignas(16) LightProxy {
+  float cx, cy, cz, area;
+  float mx, my, mz, pad;
+};
+static_assert(sizeof(LightProxy) == 32, "two float4 per emitter");
+
+constexpr uint32_t kLightCandidatesMax = 16;
+constexpr float kLightFloor = 0.0625f;                       // 1/16: added to both clamped cosines of the geometric weight
+constexpr float kLightGeomMin = 1e-30f, kLightGeomMax = 1e30f;
 
 // point s of the set, s in [0, 16): the centroids of the 16 congruent triangles a triangle splits into with four segments per edge -- the ten that point the way
 // it does (s = 0..9: rows j = 0..3 of 4 - j points, (3 i + 1, 3 j + 1) / 12), then the six that point the other way (s = 10..15: rows j = 0..2 of 3 - j, (3 i + 2, 3 j + 2) / 12)
@@ -62,6 +76,70 @@ FH_EV uint32_t light_pick(const float* cdf, uint32_t n, float uniform, float u1)
   return light_search(cdf, n, u);
 }
 
+// ---- fh_set_light_resampling: the proxy of an emitter, the geometric weight of a proxy seen from a point, and the choice among M candidates of the table
+// the proxy from the world-space corners p0, p1, p2, the corners' shading normals n0, n1, n2 (three floats each) and the area the table computed
+FH_EV LightProxy light_proxy(const float* p0, const float* p1, const float* p2, const float* n0, const float* n1, const float* n2, float area)
+{
+  LightProxy pr;
+  pr.cx = ((p0[0] + p1[0]) + p2[0]) / 3.0f;
+  pr.cy = ((p0[1] + p1[1]) + p2[1]) / 3.0f;
+  pr.cz = ((p0[2] + p1[2]) + p2[2]) / 3.0f;
+  pr.area = area;
+  const float sx = (n0[0] + n1[0]) + n2[0], sy = (n0[1] + n1[1]) + n2[1], sz = (n0[2] + n1[2]) + n2[2];
+  const float len = sqrtf((sx * sx + sy * sy) + sz * sz);
+  const bool ok = len > 0.0f && len <= 3.0e38f;  // (false for 0, infinity and NaN)
+  pr.mx = ok ? sx / len : 0.0f;
+  pr.my = ok ? sy / len : 0.0f;
+  pr.mz = ok ? sz / len : 0.0f;
+  pr.pad = 0.0f;
+  return pr;
+}
+// G of a proxy seen from so with shading normal ns: positive and finite whatever the operands
+FH_EV float light_geom(const LightProxy& pr, float sox, float soy, float soz, float nsx, float nsy, float nsz)
+{
+  const float vx = pr.cx - sox, vy = pr.cy - soy, vz = pr.cz - soz;
+  const float r2 = (vx * vx + vy * vy) + vz * vz;
+  const float r = sqrtf(r2);
+  const float dx = vx / r, dy = vy / r, dz = vz / r;
+  const float cs = fmaxf((nsx * dx + nsy * dy) + nsz * dz, 0.0f) + kLightFloor;
+  const float cl = fmaxf(-((pr.mx * dx + pr.my * dy) + pr.mz * dz), 0.0f) + kLightFloor;
+  const float g = cs * cl / (r2 + pr.area);
+  return fminf(fmaxf(g, kLightGeomMin), kLightGeomMax);  // (fmaxf first: a NaN goes to the lower bound)
+}
+// candidate k of M from the one draw: t = u1 * M, j = min((uint32)t, M - 1), v = t - j; u_k = min((k + v) / M, below one)
+FH_EV float light_candidate_v(float u1, uint32_t m)
+{
+  const float t = u1 * (float)m;
+  const uint32_t j = (uint32_t)t < m - 1u ? (uint32_t)t : m - 1u;
+  return t - (float)j;
+}
+FH_EV float light_candidate_u(uint32_t k, float v, uint32_t m) { return fminf(((float)k + v) / (float)m, kLightBelowOne); }
+
+struct LightChoice {
+  uint32_t index;  // the chosen emitter, in light order
+  float ratio;     // G_y / (S / (float)M): what pdf_area is multiplied by in the division of the shadow ray's contribution
+  float sum;       // S
+};
+// The choice among the t.candidates candidates.  Two passes over the candidates, the second repeating the first's arithmetic (the same operands give the same bits):
+// nothing per candidate is kept in registers between them, which the fused tail has none to spare for.
+FH_EV LightChoice light_resample(const LightTable& t, uint32_t n, float u1, float u_sel, float sox, float soy, float soz, float nsx, float nsy, float nsz)
+{
+  const uint32_t m = t.candidates;
+  const float v = light_candidate_v(u1, m);
+  float sum = 0.0f;
+  for (uint32_t k = 0; k < m; ++k) sum += light_geom(t.proxy[light_pick(t.cdf, n, t.uniform, light_candidate_u(k, v, m))], sox, soy, soz, nsx, nsy, nsz);
+  const float thr = u_sel * sum;
+  float run = 0.0f, g = 0.0f;
+  uint32_t y = 0;
+  for (uint32_t k = 0; k < m; ++k) {
+    y = light_pick(t.cdf, n, t.uniform, light_candidate_u(k, v, m));
+    g = light_geom(t.proxy[y], sox, soy, soz, nsx, nsy, nsz);
+    run += g;
+    if (run > thr) break;
+  }
+  return LightChoice{y, g / (sum / (float)m), sum};
+}
+
 // ---- host only
 // the whole build as the kernels of lights.hip run it in parallel, in a loop: w = the n weights; out: q [n], cdf [n + 1], p [n] (per light), the total
 inline void light_build_host(const float* w, uint32_t n, float uniform, uint32_t* q, float* cdf, float* p, uint64_t* total_out)
@@ -88,4 +166,25 @@ inline const char* light_sampling_refusal(const fh_light_sampling_params* p)
   return nullptr;
 }
 
+// nullptr: acceptable (params == nullptr switches off)
+inline const char* light_resampling_refusal(const fh_light_resampling_params* p)
+{
+  if (!p) return nullptr;
+  const int m = p->candidates;
+  if (!(m == 1 || m == 2 || m == 4 || m == 8 || m == 16)) return "candidates must be 1, 2, 4, 8 or 16";
+  return nullptr;
+}
+
 }  // namespace fh
+
+#if defined(__HIPCC__)
+#include "fh_sampler.h"
+namespace fh {
+constexpr uint32_t kLightSelSalt = 0x9e3779b9u;  // include/fredholm_hip.h prints it
+// u_sel of a shaded hit: a hash of what identifies the hit's area draw, NOT a function of that draw
+FH_HD float light_usel(uint32_t image_idx, uint32_t n_spp, uint32_t dim_area, uint32_t seed_hash)
+{
+  return (float)(xxhash32(image_idx, n_spp, dim_area, seed_hash ^ kLightSelSalt) >> 8) * 5.9604644775390625e-8f;  // 2^-24
+}
+}  // namespace fh
+#endif

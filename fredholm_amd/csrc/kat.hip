@@ -324,6 +324,16 @@ __global__ void k_light_pick(LightTable t, const AreaLightDev* lights, uint32_t 
   p[i] = t.pick_p[lights[li].face];
 }
 
+// fh_set_light_resampling: the choice as shade_hit<., ., true> makes it, with the u_sel it is handed
+__global__ void k_light_resample(LightTable t, uint32_t n_lights, uint32_t n, const float* so3, const float* ns3, const float* u1, const float* u_sel, uint32_t* index, float* ratio)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const LightChoice ch = light_resample(t, n_lights, u1[i], u_sel[i], so3[3 * i], so3[3 * i + 1], so3[3 * i + 2], ns3[3 * i], ns3[3 * i + 1], ns3[3 * i + 2]);
+  index[i] = ch.index;
+  ratio[i] = ch.ratio;
+}
+
 uint32_t blocks(uint32_t n) { return (n + 255) / 256; }
 
 }  // namespace
@@ -558,6 +568,35 @@ int fh_kat_light_pick(fh_ctx* ctx, uint32_t n, const float* u1, uint32_t* index,
   hipLaunchKernelGGL(k_light_pick, dim3(blocks(n)), dim3(256), 0, ctx->stream, light_table_dev(ctx), (const AreaLightDev*)ctx->d_lights.get(), ctx->n_lights, n, a.get(), idx.get(), o.get());
   FH_HIP(hipStreamSynchronize(ctx->stream));
   FH_HIP(down(idx, index)); FH_HIP(down(o, p));
+  return FH_OK;
+}
+int fh_kat_light_proxies(fh_ctx* ctx, float* proxies8)
+{
+  KCTX(ctx);
+  if (!proxies8) return fail(ctx, FH_E_INVALID, "fh_kat_light_proxies: null argument");
+  if (const int rc = kat_light_table(ctx, "fh_kat_light_proxies")) return rc;
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(hipMemcpy(proxies8, ctx->d_light_proxy, sizeof(LightProxy) * ctx->n_lights, hipMemcpyDeviceToHost));
+  return FH_OK;
+}
+int fh_kat_light_resample(fh_ctx* ctx, uint32_t n, const float* so3, const float* ns3, const float* u1, const float* u_sel, uint32_t* index, float* ratio)
+{
+  KCTX(ctx);
+  if (!so3 || !ns3 || !u1 || !u_sel || !index || !ratio) return fail(ctx, FH_E_INVALID, "fh_kat_light_resample: null argument");
+  if (const int rc = kat_light_table(ctx, "fh_kat_light_resample")) return rc;
+  if (n == 0) return FH_OK;
+  DeviceBuffer<float> a, b, c, d, o;
+  DeviceBuffer<uint32_t> idx;
+  FH_HIP(up(a, so3, 3ull * n)); FH_HIP(up(b, ns3, 3ull * n)); FH_HIP(up(c, u1, n)); FH_HIP(up(d, u_sel, n)); FH_HIP(up(idx, nullptr, n)); FH_HIP(up(o, nullptr, n));
+  hipLaunchKernelGGL(k_light_resample, dim3(blocks(n)), dim3(256), 0, ctx->stream, light_table_dev(ctx), ctx->n_lights, n, a.get(), b.get(), c.get(), d.get(), idx.get(), o.get());
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  FH_HIP(down(idx, index)); FH_HIP(down(o, ratio));
+  return FH_OK;
+}
+int fh_kat_light_usel(uint32_t n, const uint32_t* image_idx, const uint32_t* n_spp, uint32_t dim_area, uint32_t seed_hash, float* u_sel)
+{
+  if (!image_idx || !n_spp || !u_sel) return FH_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i) u_sel[i] = light_usel(image_idx[i], n_spp[i], dim_area, seed_hash);
   return FH_OK;
 }
 int fh_kat_hosek_state(fh_ctx* ctx, float* out30)

@@ -1,10 +1,11 @@
 // lights.hip -- the table behind fh_set_light_sampling: the emitters' weights (area x luminance of the emission), quantised to integers, with the CDF the shade kernels
-// pick from and the pick probability of every face (fh_lights.h has the arithmetic, include/fredholm_hip.h states it).  One clear and four launches on the context
+// pick from and the pick probability of every face (fh_lights.h has the arithmetic, include/fredholm_hip.h states it).  One clear and five launches on the context
 // stream, no host synchronisation once the buffers have their size:
 //   k_light_weights  one lane per emitter: its weight, and the table's maximum (a max of non-negative floats, as bits: one atomicMax per workgroup)
 //   k_light_chunks   one workgroup per chunk of kBlock emitters: the integer weights and the chunk's sum
 //   k_light_offsets  one workgroup: the exclusive scan of the chunk sums (kBlock at a time, carrying the running sum) and the total
 //   k_light_write    one workgroup per chunk: the scan inside the chunk, the CDF entries and the pick probabilities of the emitters' faces
+//   k_light_proxies  one lane per emitter: centroid, area and mean shading normal, what fh_set_light_resampling weighs a candidate by (two float4 stores)
 // Everything after the maximum is integer arithmetic, so no result depends on the order the lanes run in.
 #include <hip/hip_runtime.h>
 
@@ -126,6 +127,26 @@ __global__ void __launch_bounds__(kBlock) k_light_write(const uint32_t* q, const
   if (face < n_faces) pick_p[face] = light_pick_p(qk, total, n, uniform);
 }
 
+// the proxies of fh_set_light_resampling, in emitter order.  The area is k_light_weights' expression
+__global__ void __launch_bounds__(kBlock) k_light_proxies(SceneDev sc, uint32_t n_faces, LightProxy* proxy)
+{
+  const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= sc.n_lights) return;
+  LightProxy pr = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  const uint32_t face = sc.lights[k].face;
+  if (face < n_faces) {
+    const size_t fb = kFaceRec * (size_t)face;
+    const float4 l0 = sc.face_rec[fb], l1 = sc.face_rec[fb + 1], l2 = sc.face_rec[fb + 2], l3 = sc.face_rec[fb + 3], l4 = sc.face_rec[fb + 4], l5 = sc.face_rec[fb + 5];
+    const float area = 0.5f * length(cross(mk3(l1) - mk3(l0), mk3(l2) - mk3(l0)));
+    const float p0[3] = {l0.x, l0.y, l0.z}, p1[3] = {l1.x, l1.y, l1.z}, p2[3] = {l2.x, l2.y, l2.z};
+    const float n0[3] = {l3.x, l3.y, l3.z}, n1[3] = {l4.x, l4.y, l4.z}, n2[3] = {l5.x, l5.y, l5.z};
+    pr = light_proxy(p0, p1, p2, n0, n1, n2, area);
+  }
+  float4* const out = reinterpret_cast<float4*>(proxy + k);
+  out[0] = make_float4(pr.cx, pr.cy, pr.cz, pr.area);
+  out[1] = make_float4(pr.mx, pr.my, pr.mz, pr.pad);
+}
+
 uint32_t chunks_of(uint32_t n) { return (n + (uint32_t)kBlock - 1u) / (uint32_t)kBlock; }
 
 }  // namespace
@@ -156,6 +177,7 @@ int light_table_ensure(fh_ctx* ctx)
     FH_HIP(ctx->d_light_offsets.alloc((size_t)n_chunks + 1));
     FH_HIP(ctx->d_light_cdf.alloc((size_t)n + 1));
     FH_HIP(ctx->d_light_pick_p.alloc((size_t)n_faces));
+    FH_HIP(ctx->d_light_proxy.alloc((size_t)n));
   }
   float* const w = ctx->d_light_w;
   uint32_t* const max_bits = reinterpret_cast<uint32_t*>(w + n);
@@ -168,6 +190,7 @@ int light_table_ensure(fh_ctx* ctx)
   hipLaunchKernelGGL(k_light_offsets, dim3(1), dim3(kBlock), 0, st, (const uint32_t*)chunk_sum, n_chunks, ctx->d_light_offsets.get());
   hipLaunchKernelGGL(k_light_write, dim3(n_chunks), dim3(kBlock), 0, st, (const uint32_t*)q, (const unsigned long long*)ctx->d_light_offsets.get(), n_chunks,
                      (const AreaLightDev*)ctx->d_lights.get(), n, n_faces, ctx->light_uniform_fraction, ctx->d_light_cdf.get(), ctx->d_light_pick_p.get());
+  hipLaunchKernelGGL(k_light_proxies, dim3(n_chunks), dim3(kBlock), 0, st, scene_dev(ctx), n_faces, ctx->d_light_proxy.get());
   FH_HIP(hipGetLastError());
   ctx->light_stale = false;
   return FH_OK;

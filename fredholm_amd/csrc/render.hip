@@ -1071,8 +1071,15 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
     const float u1 = sobol_draw_bytes(rows.m[0], sidx, bs.dim_area, fr.seed_hash);
     const f2 u2 = cmj_draw(n_spp, image_idx, bs.slot_area, fr.seed_hash);
     uint32_t li;
+    float ris = 1.0f;  // fh_set_light_resampling: G_y / (S / M) of the chosen candidate (a run-time branch of the LT twins, not a third axis of them)
     if constexpr (LT) {
-      li = light_pick(ltab->cdf, sc.n_lights, ltab->uniform, u1);
+      if (ltab->candidates > 1u) {
+        const LightChoice ch = light_resample(*ltab, sc.n_lights, u1, light_usel(image_idx, n_spp, bs.dim_area, fr.seed_hash), so.x, so.y, so.z, ns.x, ns.y, ns.z);
+        li = ch.index;
+        ris = ch.ratio;
+      } else {
+        li = light_pick(ltab->cdf, sc.n_lights, ltab->uniform, u1);
+      }
     } else {
       li = (uint32_t)(u1 * sc.n_lights);
       li = li < sc.n_lights - 1u ? li : sc.n_lights - 1u;
@@ -1096,8 +1103,12 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
     const f3 wi = to_local(sd, tangent, ns, bitangent);
     const f3 f = bsdf.eval(wo, wi);
     const float pdf = r * r / fabsf(dot(-sd, ln)) * pdf_area;
-    const float w = pdf / (pdf + bsdf.eval_pdf(wo, wi));
-    const f3 c = clamp01(T * w * f * abs_cos(wi) / pdf) * le;
+    const float w = pdf / (pdf + bsdf.eval_pdf(wo, wi));  // (the table's density, resampled or not: what resolve_light_ray<true> weighs the other site with)
+    float pdf_div = pdf;
+    if constexpr (LT) {
+      if (ltab->candidates > 1u) pdf_div = r * r / fabsf(dot(-sd, ln)) * (pdf_area * ris);
+    }
+    const f3 c = clamp01(T * w * f * abs_cos(wi) / pdf_div) * le;
     out.secondary(SEC_AREA, so, r - 0.001f, sd, facing && contributes(c), c);
   }
   // BSDF-sampled light ray (pt.cu:893-925)

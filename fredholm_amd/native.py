@@ -120,6 +120,7 @@ EXPORTS = [
     "fh_set_local_exposure", "fh_get_local_exposure", "fh_local_exposure_analyse", "fh_get_local_exposure_base",
     "fh_set_env_sampling", "fh_get_env_sampling", "fh_kat_env_table", "fh_kat_env_sample", "fh_kat_env_pdf", "fh_kat_env_radiance",
     "fh_set_light_sampling", "fh_get_light_sampling", "fh_kat_light_table", "fh_kat_light_pick",
+    "fh_set_light_resampling", "fh_get_light_resampling", "fh_kat_light_proxies", "fh_kat_light_resample", "fh_kat_light_usel",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -195,6 +196,15 @@ class LightSamplingParamsC(C.Structure):
 LIGHT_UNIFORM_FRACTION_DEFAULT = 0.0625  # FH_LIGHT_UNIFORM_FRACTION_DEFAULT
 
 
+class LightResamplingParamsC(C.Structure):
+    """fh_light_resampling_params (include/fredholm_hip.h)"""
+    _fields_ = [("candidates", C.c_int)]
+
+
+LIGHT_CANDIDATES_DEFAULT = 4  # FH_LIGHT_CANDIDATES_DEFAULT
+LIGHT_CANDIDATES = (1, 2, 4, 8, 16)
+
+
 class AutoExposureStateC(C.Structure):
     """fh_auto_exposure_state (include/fredholm_hip.h)"""
     _fields_ = [("ev", C.c_float), ("target_ev", C.c_float), ("mean_log2", C.c_float), ("metered", C.c_uint32), ("unmetered", C.c_uint32), ("frames", C.c_uint32)]
@@ -248,6 +258,11 @@ SIGNATURES = {
     "fh_get_light_sampling": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(LightSamplingParamsC)],
     "fh_kat_light_table": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)],
     "fh_kat_light_pick": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fh_set_light_resampling": [C.c_void_p, C.POINTER(LightResamplingParamsC)],
+    "fh_get_light_resampling": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(LightResamplingParamsC)],
+    "fh_kat_light_proxies": [C.c_void_p, C.c_void_p],
+    "fh_kat_light_resample": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fh_kat_light_usel": [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "fh_kat_chief_rays": [C.c_void_p, C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_void_p],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],

@@ -550,6 +550,24 @@ class Renderer:
         self._ck(N.lib().fh_get_light_sampling(self._ctx, C.byref(on), C.byref(p)), "fh_get_light_sampling")
         return bool(on.value), float(p.uniform_fraction)
 
+    # -- resampling of the table's picks by distance and facing (fh_set_light_resampling)
+    def set_light_resampling(self, candidates=N.LIGHT_CANDIDATES_DEFAULT):
+        """fh_set_light_resampling: acts while light sampling is on.  The area shadow ray draws `candidates` (1, 2, 4, 8 or 16) emitters from the table and chooses
+        one in proportion to a geometric weight of the emitter seen from the shaded point: facing at both ends over the squared distance.  No further random
+        dimension is used and the MIS weights stay the table's; off (the default), or candidates = 1, keeps every bit"""
+        p = N.LightResamplingParamsC(int(candidates))
+        self._ck(N.lib().fh_set_light_resampling(self._ctx, C.byref(p)), "fh_set_light_resampling")
+
+    def clear_light_resampling(self):
+        """off: the table's pick as it is"""
+        self._ck(N.lib().fh_set_light_resampling(self._ctx, None), "fh_set_light_resampling")
+
+    def get_light_resampling(self):
+        """(on, candidates): the switch and the count last set (the default before any)"""
+        on, p = C.c_int(0), N.LightResamplingParamsC()
+        self._ck(N.lib().fh_get_light_resampling(self._ctx, C.byref(on), C.byref(p)), "fh_get_light_resampling")
+        return bool(on.value), int(p.candidates)
+
     # -- auto-exposure of the post chain (fh_set_auto_exposure)
     def set_auto_exposure(self, key=0.18, compensation_ev=0.0, min_ev=-16.0, max_ev=16.0, low=0.10, high=0.90, speed_up=3.0, speed_down=1.0, frame_time=1.0 / 30.0,
                           log2_lo=-16.0, log2_hi=16.0, bloom_relative=False):

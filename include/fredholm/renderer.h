@@ -34,6 +34,9 @@ class Renderer
   // FH_LIGHT_SAMPLING does the same for the sampling of area lights by power (fh_set_light_sampling): unset or 0: off; 1: on with the library's uniform fraction (a
   // fraction of 1 -- all picks uniform -- is spelt 1.0 like any other and means the library's all the same: ask for it with set_light_sampling(1.0f)); any other
   // number: on with that fraction.
+  // FH_LIGHT_RESAMPLING turns on the resampling of those picks by distance and facing (fh_set_light_resampling): unset or 0: off; 1: on with the library's number of
+  // candidates; 2, 4, 8 or 16: on with that many (another number is the library's refusal, thrown here).  It implies light sampling, with FH_LIGHT_SAMPLING's
+  // fraction where that variable turns it on and the library's otherwise.
   explicit Renderer(const OptixDeviceContext& context) : m_ctx(context)
   {
     if (const char* e = std::getenv("FH_LIGHT_SAMPLING")) {
@@ -42,6 +45,18 @@ class Renderer
       if (end == e || *end != '\0') throw std::runtime_error("FH_LIGHT_SAMPLING: not a number");
       if (v == 1.0f) set_light_sampling();
       else if (v != 0.0f) set_light_sampling(v);
+    }
+    if (const char* e = std::getenv("FH_LIGHT_RESAMPLING")) {
+      char* end = nullptr;
+      const long v = std::strtol(e, &end, 10);
+      if (end == e || *end != '\0') throw std::runtime_error("FH_LIGHT_RESAMPLING: not a number");
+      if (v != 0) {
+        int on = 0;
+        cwl::check(m_ctx, fh_get_light_sampling(m_ctx, &on, nullptr), "fh_get_light_sampling");
+        if (!on) set_light_sampling();
+        if (v == 1) set_light_resampling();
+        else set_light_resampling(int(v));
+      }
     }
     if (const char* e = std::getenv("FH_ENV_SAMPLING")) {
       char* end = nullptr;
@@ -105,6 +120,14 @@ class Renderer
     cwl::check(m_ctx, fh_set_light_sampling(m_ctx, &p), "fh_set_light_sampling");
   }
   void clear_light_sampling() { cwl::check(m_ctx, fh_set_light_sampling(m_ctx, nullptr), "fh_set_light_sampling"); }
+  // resampling of those picks by distance and facing from the shaded point; acts while light sampling is on; without an argument: the library's number of candidates
+  void set_light_resampling() { set_light_resampling(FH_LIGHT_CANDIDATES_DEFAULT); }
+  void set_light_resampling(int candidates)
+  {
+    const fh_light_resampling_params p = {candidates};
+    cwl::check(m_ctx, fh_set_light_resampling(m_ctx, &p), "fh_set_light_resampling");
+  }
+  void clear_light_resampling() { cwl::check(m_ctx, fh_set_light_resampling(m_ctx, nullptr), "fh_set_light_resampling"); }
 
   void set_time(float time)  // renderer.h:614-640: animation update, transform re-upload, acceleration-structure rebuild
   {

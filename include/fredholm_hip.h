@@ -721,7 +721,7 @@ int fh_get_env_sampling(fh_ctx* ctx, int* on, fh_env_sampling_params* params);
  * the switch on or changes uniform_fraction (everything is rebuilt, not pick_p alone).  The rebuild synchronises with the host only where it has to allocate: after an
  * upload that changed the number of emitters or faces.
  * Where the clamp binds (glossy lobes: T * w * f * |cos| / pdf above 1) the expectation depends on the pick distribution, as it depends on n today.
- * Not covered: a light hierarchy or any pick that depends on the shaded point, sampling the product with the BSDF. */
+ * Not covered: a light hierarchy, product sampling with the BSDF.  (A pick that depends on the shaded point: fh_set_light_resampling, below.) */
 #define FH_LIGHT_UNIFORM_FRACTION_DEFAULT 0.0625f
 typedef struct fh_light_sampling_params {
   float uniform_fraction; /* U: share of picks that stay uniform, in (0, 1]; default FH_LIGHT_UNIFORM_FRACTION_DEFAULT (DESIGN.md 4 has the rule that chose it) */
@@ -731,6 +731,47 @@ typedef struct fh_light_sampling_params {
 int fh_set_light_sampling(fh_ctx* ctx, const fh_light_sampling_params* params);
 /* *on = 0 or 1; params (may be NULL) receives the fraction last set (the default before any) */
 int fh_get_light_sampling(fh_ctx* ctx, int* on, fh_light_sampling_params* params);
+
+/* -- resampling of the table's picks by distance and facing (opt-in, default off; acts only while fh_set_light_sampling is on; with it off, or with candidates = 1,
+ * every render keeps its bits, today's light-sampling mode included).  The table above knows nothing of the shaded point.  While this switch is on, the area shadow
+ * ray draws M candidates from the table and chooses one of them in proportion to a geometric weight G of the emitter seen from the point (resampled importance
+ * sampling).  No Sobol' dimension or CMJ slot is added: every other draw of the frame is where it was.
+ * All of it is fp32 without contraction, / and sqrt correctly rounded, in the order written; fmax / fmin are C's (a NaN operand loses).
+ *   Proxy of emitter i, two float4, built with the table (one more kernel, one thread per emitter, in emitter order) and rebuilt exactly when the table is:
+ *     c = ((p0 + p1) + p2) / 3.0f per component, of the world-space corners;
+ *     s = (n0 + n1) + n2 of the corners' world-space shading normals, len = sqrt((s.x * s.x + s.y * s.y) + s.z * s.z), m = s / len per component, and m = 0 where len
+ *       is 0 or not finite;
+ *     a = area, the table's expression.                                        Stored: (c.x, c.y, c.z, a), (m.x, m.y, m.z, 0).
+ *   Geometric weight, from the shadow ray's origin so and the hit's shading normal ns (after the maps, turned to the side the ray came from):
+ *     v = c - so;  r2 = (v.x * v.x + v.y * v.y) + v.z * v.z;  d = v / sqrt(r2) per component;  dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z;
+ *     G = (fmax(dot(ns, d), 0) + 0.0625f) * (fmax(-dot(m, d), 0) + 0.0625f) / (r2 + a), then G = fmin(fmax(G, 1e-30f), 1e30f): a NaN becomes 1e-30f.
+ *     The floors 1/16 keep every emitter's weight positive -- the choice may then never exclude an emitter the table can pick -- and a bounds G next to a large
+ *     emitter.  The centroid may misjudge a triangle: a long emitter whose near end lights the point, one that faces the point only with part of its normals, one
+ *     hidden behind an occluder.  G then prefers the wrong candidate more often than it should; the division below is by the density the choice really had, so this
+ *     costs variance, never bias -- as a misjudged weight does under U.
+ *   Candidates, from the one draw u1 of the area dimension, M = candidates:  t = u1 * (float)M;  j = min((uint32)t, M - 1);  v = t - (float)j;
+ *     u_k = fmin(((float)k + v) / (float)M, 0.99999994f) and i_k = the table's pick from u_k, k = 0 .. M - 1.  Each u_k is uniform on its stratum.
+ *   Selection:  S = G_(i_0) + .. + G_(i_(M - 1)), summed serially in k order;  thr = u_sel * S;  the chosen emitter y is the i_k of the smallest k whose running
+ *     sum (the same serial sum) exceeds thr, the last i_k if none does.
+ *     u_sel = (float)(xxhash32(image_idx, n_spp, dim_area, seed_hash ^ 0x9e3779b9) >> 8) * 2^-24: the pixel, the sample, the Sobol' dimension of the area draw and
+ *     the frame's seed hash.  It is not derived from u1: a choice that is a function of the candidates' own draw is not a random choice.
+ *   The two densities of the area shadow ray.  The point on y comes from the same CMJ slot as before.  pdf_area = pick_p[face] / area is unchanged and still enters
+ *     the MIS weight w;  pdf_area_ris = pdf_area * (G_y / (S / (float)M)) takes its place only in the division of T * w * f * |cos| / pdf.  r^2 / |cos|, the facing
+ *     test, the clamp and the order of operations stay.
+ *   MIS.  The BSDF-sampled light ray is untouched: both sites weigh with the TABLE's density, which is the same function of the light point on both sides, so the
+ *     two weights add to 1 and the sum stays unbiased.  The weights are deliberately those of the table and not of the resampled pick, whose marginal density has
+ *     no closed form.
+ * Changing candidates alone rebuilds nothing.  Where the clamp binds the expectation depends on M as it depends on the pick distribution.
+ * Not covered: a light hierarchy, the BSDF in the target, reuse of picks across pixels or frames, resampled densities in the MIS weights. */
+#define FH_LIGHT_CANDIDATES_DEFAULT 4
+typedef struct fh_light_resampling_params {
+  int candidates; /* M: 1, 2, 4, 8 or 16; default FH_LIGHT_CANDIDATES_DEFAULT (DESIGN.md 4 has the rule that chose it) */
+} fh_light_resampling_params;
+/* params == NULL: off.  A scene call: on a group it reaches every member.  FH_E_INVALID, decided from the arguments alone before the context is looked at, for
+ * candidates outside {1, 2, 4, 8, 16}; the switch then stays as it was. */
+int fh_set_light_resampling(fh_ctx* ctx, const fh_light_resampling_params* params);
+/* *on = 0 or 1; params (may be NULL) receives the count last set (the default before any) */
+int fh_get_light_resampling(fh_ctx* ctx, int* on, fh_light_resampling_params* params);
 
 /* OpenGL interop for display (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143): register an OpenGL buffer object, map it and return the
  * device pointer the renderer can write AOVs to; unregister unmaps.  A current OpenGL context is required on the calling thread. */

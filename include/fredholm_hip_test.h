@@ -93,6 +93,14 @@ int fh_kat_env_radiance(fh_ctx* ctx, uint32_t n, const float* dirs3, float* out3
  * fh_kat_light_pick: n draws u1 of the area dimension -> the emitter's index in light order and the reported probability, exactly as shade_hit picks. */
 int fh_kat_light_table(fh_ctx* ctx, uint32_t* q, float* cdf, float* pick_p_per_light, uint64_t* total);
 int fh_kat_light_pick(fh_ctx* ctx, uint32_t n, const float* u1, uint32_t* index, float* p);
+/* fh_set_light_resampling (include/fredholm_hip.h), under the same conditions as the two above.
+ * fh_kat_light_proxies: the proxies in light order, eight floats each: (c.x, c.y, c.z, a), (m.x, m.y, m.z, 0).
+ * fh_kat_light_resample: n shaded points (shadow-ray origin, shading normal, u1, u_sel) -> the chosen emitter in light order and G_y / (S / M), by the function
+ *   shade_hit calls, in a kernel, with the context's table and M (1 while resampling is off).
+ * fh_kat_light_usel: u_sel for n (image_idx, n_spp) pairs; computed on the host by the function the kernels call; needs no context. */
+int fh_kat_light_proxies(fh_ctx* ctx, float* proxies8);
+int fh_kat_light_resample(fh_ctx* ctx, uint32_t n, const float* so3, const float* ns3, const float* u1, const float* u_sel, uint32_t* index, float* ratio);
+int fh_kat_light_usel(uint32_t n, const uint32_t* image_idx, const uint32_t* n_spp, uint32_t dim_area, uint32_t seed_hash, float* u_sel);
 
 #ifdef __cplusplus
 }
