@@ -40,6 +40,23 @@ FH_TM float uchimura1(float x)
 }
 FH_TM float srgb1(float x) { return x < 0.0031308 ? (float)(12.92 * x) : (float)(1.055 * fhe_pow(x, 1.0f / 2.4f) - 0.055); }
 FH_TM float clamp01f(float v) { return fmaxf(0.0f, fminf(v, 1.0f)); }
+// The three gather addresses of the tone map's chromatic aberration for output pixel (i, j): tone_mapping_kernel's arithmetic (post-process.cu:122-136: the offset
+// is divided by w * h; fp32, no contraction, the float sum truncated to int), then each address limited to the last pixel.  The clamped coordinates can be exactly
+// 1 -- a negative ca of about a quarter of the width, any ca >= w * h, +-inf, NaN (clamp01f(NaN) is 1) -- and the sum then reaches up to w * h + w, where the
+// reference reads past its image.  The coordinates are never negative, so neither is an address.
+struct TonemapFetch { int r, g, b; };
+FH_TM TonemapFetch tonemap_fetch(int i, int j, int w, int h, float ca)
+{
+  const float uvx = (float)i / w, uvy = (float)j / h;
+  const float inv = 1.0f / (float)(w * h);
+  const float dx = (uvx - 0.5f) * inv * ca, dy = (uvy - 0.5f) * inv * ca;
+  const float rx = clamp01f(uvx - 0.0f * dx), ry = clamp01f(uvy - 0.0f * dy);
+  const float gx = clamp01f(uvx - 1.0f * dx), gy = clamp01f(uvy - 1.0f * dy);
+  const float bx = clamp01f(uvx - 2.0f * dx), by = clamp01f(uvy - 2.0f * dy);
+  const int ir = (int)(rx * w + w * (ry * h)), ig = (int)(gx * w + w * (gy * h)), ib = (int)(bx * w + w * (by * h));
+  const int last = w * h - 1;
+  return {ir < last ? ir : last, ig < last ? ig : last, ib < last ? ib : last};
+}
 FH_TM float ev100_of(float aperture, float shutter, float iso) { return fhe_log2((float)(aperture * aperture / shutter * 100.0 / iso)); }
 FH_TM float exposure_from_ev100(float ev100)
 {

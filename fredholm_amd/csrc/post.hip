@@ -5,7 +5,7 @@
 // helpers fredholm/kernels/include/kernels/post-process.h:13-124.
 // Kept quirks: the launch grid is floor(W/16) x floor(H/16) blocks of 16x16, so rows/columns past the
 // last full block are never written (:9-11); the blur weight is exp(-d^2 / (2*bloom_sigma)) (:97-98);
-// the chromatic-aberration offset is divided by W*H (:124-125).
+// the chromatic-aberration offset is divided by W*H (:124-125).  Not kept: a fetch address past the last pixel (:134-139, undefined there) reads the last pixel.
 // The 33x33 blur reads its 48x48 source tile through LDS once per block instead of 1089 global
 // loads per pixel; taps are summed in the reference's (v outer, u inner) order so results match
 // the checker bit for bit.
@@ -72,14 +72,8 @@ __global__ void __launch_bounds__(256) k_tone_map(const float4* in, int w, int h
 {
   const int i = blockIdx.x * kT + threadIdx.x, j = blockIdx.y * kT + threadIdx.y;
   if (i >= gw || j >= gh) return;
-  const float uvx = (float)i / w, uvy = (float)j / h;
-  const float inv = 1.0f / (float)(w * h);
-  const float dx = (uvx - 0.5f) * inv * ca, dy = (uvy - 0.5f) * inv * ca;
-  const float rx = clamp01f(uvx - 0.0f * dx), ry = clamp01f(uvy - 0.0f * dy);
-  const float gx = clamp01f(uvx - 1.0f * dx), gy = clamp01f(uvy - 1.0f * dy);
-  const float bx = clamp01f(uvx - 2.0f * dx), by = clamp01f(uvy - 2.0f * dy);
-  const int ir = (int)(rx * w + w * (ry * h)), ig = (int)(gx * w + w * (gy * h)), ib = (int)(bx * w + w * (by * h));
-  float r = in[ir].x, g = in[ig].y, b = in[ib].z;
+  const TonemapFetch f = tonemap_fetch(i, j, w, h, ca);  // chromatic aberration: fh_tonemap.h
+  float r = in[f.r].x, g = in[f.g].y, b = in[f.b].z;
   r *= exposure; g *= exposure; b *= exposure;
   r = srgb1(uchimura1(r)); g = srgb1(uchimura1(g)); b = srgb1(uchimura1(b));
   out[i + w * j] = make_float4(r, g, b, 1.0f);
@@ -223,14 +217,8 @@ __global__ void __launch_bounds__(256) k_tone_map_metered(const float4* in, int 
   const int i = blockIdx.x * kT + threadIdx.x, j = blockIdx.y * kT + threadIdx.y;
   if (i >= gw || j >= gh) return;
   const float exposure = md->st.frames != 0u ? md->exposure : iso_exposure;
-  const float uvx = (float)i / w, uvy = (float)j / h;
-  const float inv = 1.0f / (float)(w * h);
-  const float dx = (uvx - 0.5f) * inv * ca, dy = (uvy - 0.5f) * inv * ca;
-  const float rx = clamp01f(uvx - 0.0f * dx), ry = clamp01f(uvy - 0.0f * dy);
-  const float gx = clamp01f(uvx - 1.0f * dx), gy = clamp01f(uvy - 1.0f * dy);
-  const float bx = clamp01f(uvx - 2.0f * dx), by = clamp01f(uvy - 2.0f * dy);
-  const int ir = (int)(rx * w + w * (ry * h)), ig = (int)(gx * w + w * (gy * h)), ib = (int)(bx * w + w * (by * h));
-  float r = in[ir].x, g = in[ig].y, b = in[ib].z;
+  const TonemapFetch f = tonemap_fetch(i, j, w, h, ca);  // chromatic aberration: fh_tonemap.h
+  float r = in[f.r].x, g = in[f.g].y, b = in[f.b].z;
   r *= exposure; g *= exposure; b *= exposure;
   r = srgb1(uchimura1(r)); g = srgb1(uchimura1(g)); b = srgb1(uchimura1(b));
   out[i + w * j] = make_float4(r, g, b, 1.0f);
@@ -285,14 +273,8 @@ __global__ void __launch_bounds__(256) k_tone_map_local(const float4* in, const 
   if (i >= gw || j >= gh) return;
   const float exposure = (md && md->st.frames != 0u) ? md->exposure : iso_exposure;
   const float gain = lx_gain(lx_upsample(base, w4, h4, i, j, logi[i + w * j], lx.inv_sr), exposure, lx);
-  const float uvx = (float)i / w, uvy = (float)j / h;
-  const float inv = 1.0f / (float)(w * h);
-  const float dx = (uvx - 0.5f) * inv * ca, dy = (uvy - 0.5f) * inv * ca;
-  const float rx = clamp01f(uvx - 0.0f * dx), ry = clamp01f(uvy - 0.0f * dy);
-  const float gx = clamp01f(uvx - 1.0f * dx), gy = clamp01f(uvy - 1.0f * dy);
-  const float bx = clamp01f(uvx - 2.0f * dx), by = clamp01f(uvy - 2.0f * dy);
-  const int ir = (int)(rx * w + w * (ry * h)), ig = (int)(gx * w + w * (gy * h)), ib = (int)(bx * w + w * (by * h));
-  float r = in[ir].x, g = in[ig].y, b = in[ib].z;
+  const TonemapFetch f = tonemap_fetch(i, j, w, h, ca);  // chromatic aberration: fh_tonemap.h
+  float r = in[f.r].x, g = in[f.g].y, b = in[f.b].z;
   r *= gain; g *= gain; b *= gain;
   r = srgb1(uchimura1(r)); g = srgb1(uchimura1(g)); b = srgb1(uchimura1(b));
   out[i + w * j] = make_float4(r, g, b, 1.0f);

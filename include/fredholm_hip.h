@@ -288,7 +288,10 @@ int fh_get_luminance_moments(fh_ctx* ctx, float* moments);
 /* synchronising: the owned pixels the next fh_render would sample (all of them while the mode is off) */
 int fh_active_pixel_count(fh_ctx* ctx, uint32_t* out);
 
-/* -- post chain: post_process_kernel_launch (fredholm/kernels/src/post-process.cu:5-35); all device pointers, float4 images */
+/* -- post chain: post_process_kernel_launch (fredholm/kernels/src/post-process.cu:5-35); all device pointers, float4 images.
+ * The tone map fetches r, g and b of an output pixel from three addresses of beauty_temp that chromatic_aberration moves apart (post-process.cu:122-136).  A fetch
+ * address past the last pixel reads the last pixel; the reference leaves this undefined.  (It happens when a clamped coordinate is exactly 1: a negative
+ * chromatic_aberration of about a quarter of the width, any value >= width * height, +-inf, NaN.)  Every address in range is the reference's. */
 int fh_post_process(fh_ctx* ctx, const float* beauty_in, float* beauty_high_luminance, float* beauty_temp, int width, int height, const fh_post_params* params, float* beauty_out);
 
 /* Denoiser slot (Denoiser::denoise, fredholm/include/fredholm/denoiser.h:87-95).  The reference invokes NVIDIA's OptiX AI denoiser (HDR model with

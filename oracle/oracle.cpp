@@ -789,7 +789,9 @@ static void post_process(const float* in, float* hi, float* tmp, int w, int h, c
       const float inv = 1.0f / (float)(w * h);
       const V2 d = v2(uvc.x * inv * pp.chromatic_aberration, uvc.y * inv * pp.chromatic_aberration);
       const V2 ur = clamp2(uv - 0.0f * d, v2(0.0f), v2(1.0f)), ug = clamp2(uv - 1.0f * d, v2(0.0f), v2(1.0f)), ub = clamp2(uv - 2.0f * d, v2(0.0f), v2(1.0f));
-      const int ir = (int)(ur.x * w + w * (ur.y * h)), ig = (int)(ug.x * w + w * (ug.y * h)), ib = (int)(ub.x * w + w * (ub.y * h));
+      // a clamped coordinate of exactly 1 puts the address up to w pixels past the image (undefined in the reference, post-process.cu:134-139): it reads the last pixel
+      const int last = w * h - 1;
+      const int ir = std::min((int)(ur.x * w + w * (ur.y * h)), last), ig = std::min((int)(ug.x * w + w * (ug.y * h)), last), ib = std::min((int)(ub.x * w + w * (ub.y * h)), last);
       V3 c = v3(tmp[4 * ir], tmp[4 * ig + 1], tmp[4 * ib + 2]);
       c *= exposure;
       c = v3(uchimura1(c.x), uchimura1(c.y), uchimura1(c.z));

@@ -282,14 +282,13 @@ def camera_rays(cam15, width, height, seed, pixel_idx, n_spp):
     return out
 
 
-def post_process(img, use_bloom, threshold, sigma, iso, ca):
+def post_process(img, use_bloom, threshold, sigma, iso, ca, hi=None, tmp=None, out=None, full=False):
+    """the checker's chain.  hi / tmp / out: what the three buffers hold before the call (zeros when not given); full: return (out, tmp, hi), not out alone"""
     img = np.ascontiguousarray(img, dtype=np.float32)
     h, w = img.shape[:2]
-    hi = np.zeros_like(img)
-    tmp = np.zeros_like(img)
-    out = np.zeros_like(img)
+    hi, tmp, out = (np.zeros_like(img) if b is None else np.array(b, dtype=np.float32, order="C").reshape(img.shape) for b in (hi, tmp, out))
     lib().orc_post_process(_p(img), _p(hi), _p(tmp), int(w), int(h), int(bool(use_bloom)), C.c_float(threshold), C.c_float(sigma), C.c_float(iso), C.c_float(ca), _p(out))
-    return out
+    return (out, tmp, hi) if full else out
 
 
 def tex2d(rgba8, srgb, uv):

@@ -189,7 +189,7 @@ def tone_map(oracle, tmp, x, ca):
     cols = []
     for k in range(3):
         cx, cy = c01(uvx - f32(k) * dx), c01(uvy - f32(k) * dy)
-        idx = (cx * f32(w) + f32(w) * (cy * f32(h))).astype(np.int32)
+        idx = np.minimum((cx * f32(w) + f32(w) * (cy * f32(h))).astype(np.int32), w * h - 1)  # an address past the last pixel reads the last pixel (fredholm_hip.h)
         with np.errstate(all="ignore"):
             cols.append(flat[idx.reshape(-1), k].reshape(h, w) * np.asarray(x, np.float32))
     rgb = np.stack(cols, axis=-1).reshape(-1, 3)
