@@ -54,7 +54,7 @@ FH_EV uint32_t light_quantise(float w, float w_max) { return env_quantise(w, w_m
 // P_k of an emitter with integer weight q among n, the integer total being `total`
 FH_EV float light_pick_p(uint32_t q, uint64_t total, uint32_t n, float uniform) { return (1.0f - uniform) * env_ratio(q, total) + uniform / (float)n; }
 // the interval of `cdf` (n + 1 ascending entries, cdf[0] = 0, cdf[n] = 1) that holds u in [0, 1): the largest k with cdf[k] <= u, by bisection.  env_search restated
-// with unsigned indices, not called: a second caller of that function changed the instruction streams of the kernels that already call it (k_shade_env, k_tail_env)
+// with unsigned indices, not called: a second caller of that function changed the instruction streams of the kernels that already call it (k_shade and k_tail with the environment table)
 FH_EV uint32_t light_search(const float* cdf, uint32_t n, float u)
 {
   uint32_t lo = 0, hi = n;

@@ -1071,7 +1071,7 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
     const float u1 = sobol_draw_bytes(rows.m[0], sidx, bs.dim_area, fr.seed_hash);
     const f2 u2 = cmj_draw(n_spp, image_idx, bs.slot_area, fr.seed_hash);
     uint32_t li;
-    float ris = 1.0f;  // fh_set_light_resampling: G_y / (S / M) of the chosen candidate (a run-time branch of the LT twins, not a third axis of them)
+    float ris = 1.0f;  // fh_set_light_resampling: G_y / (S / M) of the chosen candidate (a run-time branch of the LT forms, not a third axis of them)
     if constexpr (LT) {
       if (ltab->candidates > 1u) {
         const LightChoice ch = light_resample(*ltab, sc.n_lights, u1, light_usel(image_idx, n_spp, bs.dim_area, fr.seed_hash), so.x, so.y, so.z, ns.x, ns.y, ns.z);
@@ -1241,34 +1241,91 @@ __global__ void __launch_bounds__(kSortBlock) k_cell_scatter(const uint32_t* cou
   }
 }
 
-// k_shade and k_shade_env, its twin that takes the environment table (fh_set_env_sampling), share ONE body text, render_shade_body.inc, included into both: a device
-// function called by both was tried first and changed the plain kernels' instruction streams (registers allocated differently in 15 of them), and the plain kernels
-// must stay what they are.  The body reads ENV and env, LT and ltab.
-template <uint32_t LOBES, int BLOCKS = FH_SHADE_BLOCKS>
-__global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : BLOCKS)) k_shade(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth)
+// The opt-in sampling modes hand their tables to k_shade and to the secondary-ray kernels as a trailing parameter pack: empty for the plain kernel, (EnvTable) for
+// fh_set_env_sampling, (UnreadEnvTable, LightTable) or (EnvTable, LightTable) for fh_set_light_sampling; the secondary-ray kernels take nothing or (pick_p).  A pack, not a
+// device function shared by several kernels: the body stays inside the kernel and a plain instantiation keeps its name, its arguments and its instruction stream -- after
+// ANY edit of these bodies compare a device listing of render.hip with the one before it (tools/kernel_asm_diff.py): the plain kernels may differ in nothing.
+struct UnreadEnvTable { EnvTable t; };  // holds the place, and the kernarg offsets, of the environment table in the (-, LightTable) forms: table_of<EnvTable> does not find it
+template <class T>
+FH_D const T* table_of() { return nullptr; }
+template <class T, class First, class... Rest>
+FH_D const T* table_of(const First& f, const Rest&... r)
 {
-  constexpr bool ENV = false, LT = false;
-  const EnvTable* const env = nullptr;
-  const LightTable* const ltab = nullptr;
-#include "render_shade_body.inc"
+  if constexpr (std::is_same<T, First>::value) return &f;
+  else return table_of<T>(r...);
 }
-// compiled for the lobe sets of the fused tail (TailLobes), two workgroups per CU
-template <uint32_t LOBES>
-__global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : FH_SHADE_BLOCKS)) k_shade_env(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth, EnvTable env_table)
+FH_D const float* pick_p_of() { return nullptr; }
+FH_D const float* pick_p_of(const float* pick_p) { return pick_p; }
+
+// (with tables: compiled for the lobe sets of the fused tail (TailLobes), FH_SHADE_BLOCKS workgroups per CU)
+template <uint32_t LOBES, int BLOCKS = FH_SHADE_BLOCKS, class... Tables>
+__global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : BLOCKS)) k_shade(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth, Tables... tables)
 {
-  constexpr bool ENV = true, LT = false;
-  const EnvTable* const env = &env_table;
-  const LightTable* const ltab = nullptr;
-#include "render_shade_body.inc"
-}
-// the twin that takes the light table (fh_set_light_sampling), with and without the environment table read: the same lobe sets, the same workgroups per CU
-template <uint32_t LOBES, bool ENV_ON>
-__global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : FH_SHADE_BLOCKS)) k_shade_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth, EnvTable env_table, LightTable light_table)
-{
-  constexpr bool ENV = ENV_ON, LT = true;
-  const EnvTable* const env = &env_table;
-  const LightTable* const ltab = &light_table;
-#include "render_shade_body.inc"
+  constexpr bool ENV = (std::is_same<Tables, EnvTable>::value || ...), LT = (std::is_same<Tables, LightTable>::value || ...);
+  const EnvTable* const env = table_of<EnvTable>(tables...);
+  const LightTable* const ltab = table_of<LightTable>(tables...);
+  pass_priority();
+  // (the grid is sized for every path of the pass; the blocks beyond this class's queue leave before they stage anything)
+  if (blockIdx.x * blockDim.x >= pool.counters[depth * kCounterStride + CNT_CLS + cls]) return;
+  __shared__ SobolRows<4> rows;
+  // the shade kernels run one wave per SIMD (512 registers per lane), so nothing hides a dependent global load: the small tables every
+  // hit reads -- the two albedo LUTs and, when there are few of them, the material records -- are staged in LDS once per workgroup
+  __shared__ float s_lut[kLutReflFloats + kLutSheenFloats];
+  __shared__ MaterialDev s_mat[kMatLds];
+  for (uint32_t i = threadIdx.x; i < kLutReflFloats; i += blockDim.x) s_lut[i] = fr.lut.reflection[i];
+  for (uint32_t i = threadIdx.x; i < kLutSheenFloats; i += blockDim.x) s_lut[kLutReflFloats + i] = fr.lut.sheen[i];
+  fr.lut.reflection = s_lut;
+  fr.lut.sheen = s_lut + kLutReflFloats;
+  if (sc.n_materials <= kMatLds) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(sc.materials);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(s_mat);
+    for (uint32_t i = threadIdx.x; i < sc.n_materials * (uint32_t)(sizeof(MaterialDev) / 4); i += blockDim.x) dst[i] = src[i];
+    sc.materials = s_mat;
+  }
+  __shared__ float s_srgb[256];  // the sRGB decode table: twelve lookups per fetch of a colour texture
+  if (sc.n_textures) {
+    s_srgb[threadIdx.x] = sc.srgb_lut[threadIdx.x];
+    sc.srgb_lut = s_srgb;
+  }
+  __shared__ HosekSky s_sky;
+  stage_sky(fr, s_sky);
+  BounceSlots bs;
+  bs.set(fr, sc.n_lights, depth);
+  bs.load_rows(rows, fr.sobol_bytes);  // (ends with the workgroup barrier that also publishes the tables above)
+
+  uint32_t* cnt = pool.counters + depth * kCounterStride;
+  uint32_t* cnt_next = cnt + kCounterStride;
+  const uint32_t count = cnt[CNT_CLS + cls];
+  const uint32_t* q = pool.q_cls + (size_t)cls * pool.capacity;
+  const uint32_t qnext = (depth + 1u) & 1u;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  __shared__ uint32_t s_reserve[2][10];  // (two areas, used alternately: block_queue_reserve)
+  uint32_t iter = 0;
+  for (uint32_t base = blockIdx.x * blockDim.x; base < count; base += stride) {
+    const uint32_t i = base + threadIdx.x;
+    const bool valid = i < count;
+    bool shaded = false, cont = false;
+    uint32_t p = 0, cell = 0;
+    if (valid) {
+      p = q[i];
+      const float4 hit = pool.hit[p];
+      PoolSink o(pool, p, hit.x);
+      const bool first = depth != 0 || (pool.flags[p] & 4u) == 0u;
+      const f3 L = depth == 0u ? mk3(pool.rad[p]) : mk3(0.0f);  // the radiance so far only enters at a directly visible emitter (first hit): later bounces skip the load
+      shade_hit<LOBES, ENV, LT>(sc, fr, rows, bs, depth, hit, mk3(pool.ray_d[p]), mk3(pool.thr[p]), L, pool.pixel[p], pool.nspp[p], o, first, env, ltab);
+      shaded = o.shaded;
+      cont = o.cont;
+      if (shaded || cont) cell = cell_of(fr, o.origin);
+    }
+    // queue positions of both appends: one returning atomic per workgroup and queue (fh_device.h: block_queue_reserve)
+    uint32_t* const counters2[2] = {&cnt[CNT_SEC], &cnt_next[CNT_RAD]};
+    const bool act[2] = {shaded, cont};
+    uint32_t pos[2];
+    block_queue_reserve<2>(counters2, act, pos, s_reserve[iter & 1u]);
+    ++iter;
+    if (shaded) { pool.q_sec[pos[0]] = p; pool.key_sec[pos[0]] = (uint16_t)cell; }
+    if (cont) { pool.q_rad[qnext][pos[1]] = p; pool.key_rad[pos[1]] = (uint16_t)cell; }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1311,44 +1368,115 @@ FH_D f3 resolve_light_ray(const SceneDev& sc, const FrameDev& fr, f3 T, float co
 }
 
 // secondary rays, binary-BVH fallback: one thread per shaded path, its rays in the reference's order
-template <bool COUNT, bool WIDE, bool LIGHTS, bool ALPHA>
-__global__ void __launch_bounds__(kBlock) k_trace_secondary_static(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc)
+// PickP (fh_set_light_sampling), here and in the three kernels below: nothing, or the table's pick probabilities per face, which resolve_light_ray<true> reads.  The
+// forms that take them are compiled with LIGHTS only: without emitters the mode does nothing.
+template <bool COUNT, bool WIDE, bool LIGHTS, bool ALPHA, class... PickP>
+__global__ void __launch_bounds__(kBlock) k_trace_secondary_static(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, PickP... pp)
 {
-  constexpr bool LT = false;
-  const float* const pick_p = nullptr;
-#define FH_BODY_STATIC
-#include "render_secondary_body.inc"
-#undef FH_BODY_STATIC
-}
-// The twins of the four secondary-ray kernels that take the light table (fh_set_light_sampling): pick_p is one more argument, LIGHTS is always true -- without emitters
-// the mode does nothing -- and the body text is shared (render_secondary_body.inc), as the shade kernels share theirs.
-template <bool COUNT, bool WIDE, bool ALPHA>
-__global__ void __launch_bounds__(kBlock) k_trace_secondary_static_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, const float* pick_p)
-{
-  constexpr bool LT = true, LIGHTS = true;
-#define FH_BODY_STATIC
-#include "render_secondary_body.inc"
-#undef FH_BODY_STATIC
+  constexpr bool LT = sizeof...(PickP) != 0;
+  static_assert(LIGHTS || !LT, "pick probabilities without emitters");
+  const float* const pick_p = pick_p_of(pp...);
+  pass_priority();
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
+  __shared__ HosekSky s_sky;  // (light rays that escape see the sky: resolve_light_ray)
+  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
+  const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
+  constexpr bool has_lights = LIGHTS;
+  uint32_t nn = 0, nt = 0, nr = 0;
+  WaveSteps ws;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+    const uint32_t p = pool.q_sec[i];
+    f3 L = mk3(pool.rad[p]);
+#pragma unroll
+    for (uint32_t slot = SEC_DIR; slot <= SEC_LIGHT; ++slot) {
+      if (slot == SEC_DIR && !fr.has_dir) continue;
+      if (slot == SEC_AREA && !has_lights) continue;
+      const size_t k = pool.sec_at(slot, p);
+      const float4 d = pool.sec[k + 1];
+      if (!sec_present(d)) continue;
+      const float4 o = pool.sec[k];
+      HitRec h;
+      if (COUNT) nr++;
+      if (slot == SEC_LIGHT && has_lights) {
+        const bool hit = WIDE ? traverse_bvh8<false, COUNT, true, ALPHA>(sc.bvh8, mk3(o), mk3(d), o.w, h, nn, nt, &ws, lds_stack, (int)sc.bvh8.depth, &sc)
+                              : traverse_bvh2<false, COUNT, ALPHA>(sc.bvh2, mk3(o), mk3(d), o.w, h, nn, nt, &sc);
+        const float4 la = pool.lp_a[p], lb = pool.lp_b[p];
+        L += resolve_light_ray<LT>(sc, fr, mk3(la), la.w, mk3(lb), lb.w, mk3(o), mk3(d), hit, h, pick_p);
+      } else {
+        const uint32_t nn0 = nn;
+        const bool occluded = WIDE ? traverse_bvh8<true, COUNT, true, ALPHA>(sc.bvh8, mk3(o), mk3(d), o.w, h, nn, nt, &ws, lds_stack, (int)sc.bvh8.depth, &sc)
+                                   : traverse_bvh2<true, COUNT, ALPHA>(sc.bvh2, mk3(o), mk3(d), o.w, h, nn, nt, &sc);
+        if (COUNT) { const uint32_t kk = nn - nn0; int b = 0; while (b < 7 && kk > (8u << b)) ++b; atomicAdd(tc.hist + b, 1ull); }
+        if (!occluded) L += mk3(pool.sec[k + 2]);
+      }
+    }
+    pool.rad[p] = mk4(L, 0.0f);
+  }
+  if (COUNT) {
+    atomicAdd(tc.nodes, (unsigned long long)nn);
+    atomicAdd(tc.tris, (unsigned long long)nt);
+    atomicAdd(tc.rays, (unsigned long long)nr);
+    if (ws.node) atomicAdd(tc.wave_nodes, (unsigned long long)ws.node);
+    if (ws.tri) atomicAdd(tc.wave_tris, (unsigned long long)ws.tri);
+  }
 }
 
 // secondary rays over the 8-wide BVH with wave-cooperative triangle tests: a lane owns one shaded path and walks its
 // secondary-ray slots in the reference's order; a slot is traversed by the whole wave when any lane has a ray in it
-template <bool COUNT, bool LIGHTS, bool ALPHA>
-__global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? 5 : 6)) k_trace_secondary_coop(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush)
+template <bool COUNT, bool LIGHTS, bool ALPHA, class... PickP>
+__global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? 5 : 6)) k_trace_secondary_coop(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, PickP... pp)
 {
-  constexpr bool LT = false;
-  const float* const pick_p = nullptr;
-#define FH_BODY_COOP
-#include "render_secondary_body.inc"
-#undef FH_BODY_COOP
-}
-template <bool COUNT, bool ALPHA>
-__global__ void __launch_bounds__(kBlock, COUNT ? 1 : 5) k_trace_secondary_coop_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, const float* pick_p)
-{
-  constexpr bool LT = true, LIGHTS = true;
-#define FH_BODY_COOP
-#include "render_secondary_body.inc"
-#undef FH_BODY_COOP
+  constexpr bool LT = sizeof...(PickP) != 0;
+  static_assert(LIGHTS || !LT, "pick probabilities without emitters");
+  const float* const pick_p = pick_p_of(pp...);
+  pass_priority();
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
+  __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
+  const CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
+  __shared__ HosekSky s_sky;  // (light rays that escape see the sky: resolve_light_ray)
+  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
+  const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
+  constexpr bool has_lights = LIGHTS;
+  uint32_t nn = 0, nt = 0, nr = 0;
+  WaveSteps ws;
+  for (uint32_t base = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < count; base += gridDim.x * blockDim.x) {
+    const uint32_t i = base + (threadIdx.x & 63u);
+    const bool in_range = i < count;
+    const uint32_t p = in_range ? pool.q_sec[i] : 0u;
+    f3 L = in_range ? mk3(pool.rad[p]) : mk3(0.0f);
+#pragma unroll
+    for (uint32_t slot = SEC_DIR; slot <= SEC_LIGHT; ++slot) {
+      if (slot == SEC_DIR && !fr.has_dir) continue;
+      if (slot == SEC_AREA && !has_lights) continue;
+      const size_t k = pool.sec_at(slot, p);
+      const float4 d = in_range ? pool.sec[k + 1] : make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+      const bool valid = in_range && sec_present(d);
+      if (__ballot(valid) == 0ull) continue;
+      const float4 o = valid ? pool.sec[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      HitRec h;
+      if (COUNT && valid) nr++;
+      if (slot == SEC_LIGHT && has_lights) {
+        const bool hit = traverse_bvh8_coop<false, COUNT, true, ALPHA>(sc.bvh8, valid, mk3(o), mk3(d), o.w, h, nn, nt, &ws, cl, flush, lds_stack, (int)sc.bvh8.depth, &sc);
+        if (valid) {
+          const float4 la = pool.lp_a[p], lb = pool.lp_b[p];
+          L += resolve_light_ray<LT>(sc, fr, mk3(la), la.w, mk3(lb), lb.w, mk3(o), mk3(d), hit, h, pick_p);
+        }
+      } else {
+        const uint32_t nn0 = nn;
+        const bool occluded = traverse_bvh8_coop<true, COUNT, true, ALPHA>(sc.bvh8, valid, mk3(o), mk3(d), o.w, h, nn, nt, &ws, cl, flush, lds_stack, (int)sc.bvh8.depth, &sc);
+        if (COUNT && valid) { const uint32_t kk = nn - nn0; int b = 0; while (b < 7 && kk > (8u << b)) ++b; atomicAdd(tc.hist + b, 1ull); }
+        if (valid && !occluded) L += mk3(pool.sec[k + 2]);
+      }
+    }
+    if (in_range) pool.rad[p] = mk4(L, 0.0f);
+  }
+  if (COUNT) {
+    atomicAdd(tc.nodes, (unsigned long long)nn);
+    atomicAdd(tc.tris, (unsigned long long)nt);
+    atomicAdd(tc.rays, (unsigned long long)nr);
+    if (ws.node) atomicAdd(tc.wave_nodes, (unsigned long long)ws.node);
+    if (ws.tri) atomicAdd(tc.wave_tris, (unsigned long long)ws.tri);
+  }
 }
 
 // secondary rays, streaming: a lane's item is one shaded path; its secondary-ray slots are traced one after the other by the
@@ -1432,22 +1560,39 @@ struct SecondaryStream {
   FH_D uint32_t start_node() const { return start; }
 };
 
-template <bool COUNT, bool LIGHTS, bool ALPHA>
-__global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS))) k_trace_secondary_stream(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill)
+template <bool COUNT, bool LIGHTS, bool ALPHA, class... PickP>
+__global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS))) k_trace_secondary_stream(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill, PickP... pp)
 {
-  constexpr bool LT = false;
-  const float* const pick_p = nullptr;
-#define FH_BODY_STREAM
-#include "render_secondary_body.inc"
-#undef FH_BODY_STREAM
-}
-template <bool COUNT, bool ALPHA>
-__global__ void __launch_bounds__(kBlock, COUNT ? 1 : FH_SECONDARY_BLOCKS_HEAVY) k_trace_secondary_stream_lt(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill, const float* pick_p)
-{
-  constexpr bool LT = true, LIGHTS = true;
-#define FH_BODY_STREAM
-#include "render_secondary_body.inc"
-#undef FH_BODY_STREAM
+  constexpr bool LT = sizeof...(PickP) != 0;
+  static_assert(LIGHTS || !LT, "pick probabilities without emitters");
+  const float* const pick_p = pick_p_of(pp...);
+  pass_priority();
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
+  __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
+  const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
+  if (stream_block_idle(count, min_rays)) return;
+  __shared__ HosekSky s_sky;  // (light rays that escape see the sky: resolve_light_ray)
+  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
+  const ClockStamp stamp;
+  CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
+  AlphaLds<AlphaDefer<true, ALPHA>::value>::attach(cl);  // candidates waiting for their any-hit test (fh_trace.h: alpha_ring): LDS of the kernels with the test compiled in only
+  uint32_t nn = 0, nt = 0;
+  WaveSteps ws;
+  SecondaryStream<COUNT, LIGHTS, LT> pol(sc, fr, pool, ChunkFeed(pool.counters + depth * kCounterStride + CNT_CUR_SEC, count, stream_chunk_for(count, chunk)), tc.hist, pick_p);
+  __shared__ uint4 lds_top[kTopNodes * 4];
+  stage_top_nodes(sc.bvh8, lds_top);
+  traverse_stream<true, COUNT, true, ALPHA>(sc.bvh8, pol, nn, nt, &ws, cl, flush, refill, lds_stack, (int)sc.bvh8.depth, &sc, spill, lds_top,
+                                            spill.probe ? pool.counters + depth * kCounterStride + CNT_COST_NODE : nullptr);
+  pol.finish();
+  stamp.commit(tc.clk);
+  if (COUNT) {
+    atomicAdd(tc.nodes, (unsigned long long)nn);
+    atomicAdd(tc.tris, (unsigned long long)nt);
+    atomicAdd(tc.rays, (unsigned long long)pol.n_rays);
+    pol.hp.flush(tc.hist);
+    if (ws.node) atomicAdd(tc.wave_nodes, (unsigned long long)ws.node);
+    if (ws.tri) atomicAdd(tc.wave_tris, (unsigned long long)ws.tri);
+  }
 }
 
 // One launch for the secondary rays of bounce b AND the closest-hit rays of bounce b + 1 (calls of ONE pass: the reference's 1- and 16-sample calls).  The two do not
@@ -1492,22 +1637,31 @@ struct MergedStream {
   FH_D bool followup() const { return !closest && sec.followup(); }
 };
 
-template <bool LIGHTS, bool ALPHA>
-__global__ void __launch_bounds__(kBlock, LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS)) k_trace_merged_stream(SceneDev sc, FrameDev fr, PoolDev ps, PoolDev pn, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill)
+template <bool LIGHTS, bool ALPHA, class... PickP>
+__global__ void __launch_bounds__(kBlock, LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS)) k_trace_merged_stream(SceneDev sc, FrameDev fr, PoolDev ps, PoolDev pn, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill, PickP... pp)
 {
-  constexpr bool LT = false;
-  const float* const pick_p = nullptr;
-#define FH_BODY_MERGED
-#include "render_secondary_body.inc"
-#undef FH_BODY_MERGED
-}
-template <bool ALPHA>
-__global__ void __launch_bounds__(kBlock, FH_SECONDARY_BLOCKS_HEAVY) k_trace_merged_stream_lt(SceneDev sc, FrameDev fr, PoolDev ps, PoolDev pn, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill, const float* pick_p)
-{
-  constexpr bool LT = true, LIGHTS = true;
-#define FH_BODY_MERGED
-#include "render_secondary_body.inc"
-#undef FH_BODY_MERGED
+  constexpr bool LT = sizeof...(PickP) != 0;
+  static_assert(LIGHTS || !LT, "pick probabilities without emitters");
+  const float* const pick_p = pick_p_of(pp...);
+  pass_priority();
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];
+  __shared__ __attribute__((aligned(16))) unsigned char lds[(kBlock / 64) * kCoopLdsBytesPerWave];
+  const uint32_t n_sec = ps.counters[depth * kCounterStride + CNT_SEC], n_closest = ps.counters[(depth + 1u) * kCounterStride + CNT_RAD];
+  const uint32_t count = n_sec + n_closest;
+  if (stream_block_idle(count, min_rays)) return;
+  __shared__ HosekSky s_sky;
+  if (LIGHTS) { stage_sky(fr, s_sky); __syncthreads(); }
+  const ClockStamp stamp;
+  CoopLds cl = coop_lds(lds, threadIdx.x >> 6);
+  AlphaLds<AlphaDefer<true, ALPHA>::value>::attach(cl);  // candidates waiting for their any-hit test (fh_trace.h: alpha_ring): LDS of the kernels with the test compiled in only
+  uint32_t nn = 0, nt = 0;
+  MergedStream<LIGHTS, LT> pol(sc, fr, ps, pn, pn.q_rad[(depth + 1u) & 1u], n_sec, ChunkFeed(ps.counters + depth * kCounterStride + CNT_CUR_SEC, count, stream_chunk_for(count, chunk)), pick_p);
+  __shared__ uint4 lds_top[kTopNodes * 4];
+  stage_top_nodes(sc.bvh8, lds_top);
+  traverse_stream<true, false, true, ALPHA>(sc.bvh8, pol, nn, nt, nullptr, cl, flush, refill, lds_stack, (int)sc.bvh8.depth, &sc, spill, lds_top,
+                                            spill.probe ? ps.counters + depth * kCounterStride + CNT_COST_NODE : nullptr);
+  pol.sec.finish();
+  stamp.commit(tc.clk);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1539,7 +1693,9 @@ __device__ __attribute__((noinline)) bool tail_trace_lane(const SceneDev& sc, ui
 }
 struct TailRay { bool has = false; bool any = true; f3 o = mk3(0.0f), d = mk3(0.0f, 0.0f, 1.0f); float tmax = 0.0f; HitRec h = HitRec{0.0f, 0.0f, 0.0f, 0xffffffffu}; bool hit = false; };  // (no indeterminate field: r6-13)
 
-// (k_tail and k_tail_env share render_tail_body.inc the way the shade kernels share theirs)
+// k_tail keeps three kernel NAMES over one body text, render_tail_body.inc, and is not a pack template as k_shade is: it calls tail_trace_lane out of line, so every tail
+// kernel carries the LDS-kernel id the compiler numbers such kernels by, in the order of their mangled names (s_mov_b32 s15, <id> before each call).  As
+// k_tail<LOBES, Tables...> the forms of one lobe set sort next to each other and the plain kernels get other ids: 15 of the 16 listings then differ.
 template <uint32_t LOBES>
 __global__ void __launch_bounds__(kBlock, LOBES == L_ALL ? 1 : 2) k_tail(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t first_depth, uint32_t coop_flush)
 {
@@ -1678,11 +1834,27 @@ uint32_t grid_for(uint32_t n)  // multiple of 8 (one share per XCD), at most 819
   return b < 8 ? 8 : (b > 8192 ? 8192 : b);
 }
 
-template <uint32_t LOBES>
-void launch_shade(hipStream_t st, uint32_t grid, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three)
+// A kernel template that ends in a pack of tables is named as a value (its address for the runtime's queries) through the pointer type of the instantiation that is meant;
+// a launch deduces the pack from its arguments.
+template <class... Tables>
+using ShadeFn = void (*)(SceneDev, FrameDev, PoolDev, uint32_t, uint32_t, Tables...);
+template <class... PickP>
+using SecondaryStaticFn = void (*)(SceneDev, FrameDev, PoolDev, uint32_t, TraceCounters, PickP...);
+template <class... PickP>
+using SecondaryCoopFn = void (*)(SceneDev, FrameDev, PoolDev, uint32_t, TraceCounters, uint32_t, PickP...);
+template <class... PickP>
+using SecondaryStreamFn = void (*)(SceneDev, FrameDev, PoolDev, uint32_t, TraceCounters, uint32_t, uint32_t, uint32_t, uint32_t, StackSpill, PickP...);
+template <class... PickP>
+using MergedStreamFn = void (*)(SceneDev, FrameDev, PoolDev, PoolDev, uint32_t, TraceCounters, uint32_t, uint32_t, uint32_t, uint32_t, StackSpill, PickP...);
+
+// The trailing arguments of a call's k_shade launches (fh_set_env_sampling, fh_set_light_sampling): none, (env), (env that is not read, lt) or (env, lt)
+template <typename F>
+void with_tables(bool env_on, const EnvTable& env, const LightTable* lt, F&& f)
 {
-  if (three && LOBES != L_ALL) hipLaunchKernelGGL((k_shade<LOBES, (LOBES == L_ALL ? FH_SHADE_BLOCKS : 3)>), dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth);
-  else hipLaunchKernelGGL(k_shade<LOBES>, dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth);
+  if (lt && env_on) f(env, *lt);
+  else if (lt) f(UnreadEnvTable{env}, *lt);
+  else if (env_on) f(env);
+  else f();
 }
 
 // The lobe ladder: of the variants a kernel is compiled in, most specific first, the first that contains every lobe of `lobes`; the last one is taken when none does
@@ -1702,20 +1874,20 @@ void with_compiled_lobes(uint32_t lobes, LobeSet<V, Rest...>, F&& f)
 void dispatch_shade(hipStream_t st, uint32_t grid, uint32_t lobes, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three, const EnvTable* env,
                     const EnvTable& env_table, const LightTable* lt)
 {
-  if (lt) {  // fh_set_light_sampling: the twins that take the light table, with the environment table read or not
-    with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { with_bool(env != nullptr, [&](auto E) {
-      hipLaunchKernelGGL((k_shade_lt<decltype(V)::value, decltype(E)::value>), dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, env_table, *lt);
-    }); });
-    return;
-  }
-  if (env) {
-    with_compiled_lobes(lobes, TailLobes{}, [&](auto V) { hipLaunchKernelGGL(k_shade_env<decltype(V)::value>, dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, *env); });
-    return;
-  }
-  with_compiled_lobes(lobes, ShadeLobes{}, [&](auto V) { launch_shade<decltype(V)::value>(st, grid, sc, fr, pool, cls, depth, three); });
+  with_tables(env != nullptr, env_table, lt, [&](auto... tables) {
+    constexpr bool plain = sizeof...(tables) == 0;  // the forms that take tables are compiled for the tail's lobe sets, and at FH_SHADE_BLOCKS only
+    with_compiled_lobes(lobes, std::conditional_t<plain, ShadeLobes, TailLobes>{}, [&](auto V) {
+      constexpr uint32_t LOBES = decltype(V)::value;
+      if constexpr (plain && LOBES != L_ALL) {
+        if (three) { hipLaunchKernelGGL((k_shade<LOBES, 3>), dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth); return; }
+      }
+      hipLaunchKernelGGL(k_shade<LOBES>, dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, tables...);
+    });
+  });
 }
 
-// The streaming trace kernels a scene is traced by, each ladder stated once: a launch takes the typed kernel, the runtime queries (occupancy, fh_kernel_info) its address
+// The streaming trace kernels a scene is traced by, typed: the runtime queries (occupancy, fh_kernel_info) take the address, launch_closest launches what it is handed.
+// (Of the secondary-ray kernel this is the form without pick_p, which is the one the queries have always asked about; launch_secondary names the template itself.)
 template <typename F>
 void with_closest_stream(bool count, bool alpha, F&& f)
 {
@@ -1725,7 +1897,7 @@ template <typename F>
 void with_secondary_stream(bool count, bool lights, bool alpha, F&& f)
 {
   with_bool(count, [&](auto C) { with_bool(lights, [&](auto Li) { with_bool(alpha, [&](auto A) {
-    f(k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>);
+    f(SecondaryStreamFn<>(k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>));
   }); }); });
 }
 const void* stream_kernel(bool secondary, bool count, bool lights, bool alpha)
@@ -1740,11 +1912,10 @@ const void* stream_kernel(bool secondary, bool count, bool lights, bool alpha)
 template <uint32_t LOBES>
 hipError_t shade_attributes_of(bool three, hipFuncAttributes& at, int& blocks)
 {
-  const void* fn = (three && LOBES != L_ALL) ? (const void*)k_shade<LOBES, (LOBES == L_ALL ? FH_SHADE_BLOCKS : 3)> : (const void*)k_shade<LOBES>;
-  const hipError_t e = hipFuncGetAttributes(&at, fn);
+  const ShadeFn<> fn = (three && LOBES != L_ALL) ? ShadeFn<>(k_shade<LOBES, (LOBES == L_ALL ? FH_SHADE_BLOCKS : 3)>) : ShadeFn<>(k_shade<LOBES>);
+  const hipError_t e = hipFuncGetAttributes(&at, (const void*)fn);
   if (e != hipSuccess) return e;
-  if (three && LOBES != L_ALL) return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_shade<LOBES, (LOBES == L_ALL ? FH_SHADE_BLOCKS : 3)>, kBlock, 0);
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_shade<LOBES>, kBlock, 0);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, kBlock, 0);
 }
 hipError_t shade_attributes(uint32_t lobes, bool three, hipFuncAttributes& at, int& blocks, uint32_t& compiled_lobes)
 {
@@ -1953,11 +2124,11 @@ int configure_traversal_lds(fh_ctx* ctx, uint32_t stack_bytes)
         set((const void*)k_trace_closest_coop<decltype(C)::value, decltype(A)::value>);
         for (int l = 0; l < 2; ++l)
           with_bool(l != 0, [&](auto Li) {
-            set((const void*)k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>);
-            set((const void*)k_trace_merged_stream<decltype(Li)::value, decltype(A)::value>);
-            set((const void*)k_trace_secondary_coop<decltype(C)::value, decltype(Li)::value, decltype(A)::value>);
-            set((const void*)k_trace_secondary_static<decltype(C)::value, true, decltype(Li)::value, decltype(A)::value>);
-            set((const void*)k_trace_secondary_static<decltype(C)::value, false, decltype(Li)::value, decltype(A)::value>);
+            set((const void*)SecondaryStreamFn<>(k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>));
+            set((const void*)MergedStreamFn<>(k_trace_merged_stream<decltype(Li)::value, decltype(A)::value>));
+            set((const void*)SecondaryCoopFn<>(k_trace_secondary_coop<decltype(C)::value, decltype(Li)::value, decltype(A)::value>));
+            set((const void*)SecondaryStaticFn<>(k_trace_secondary_static<decltype(C)::value, true, decltype(Li)::value, decltype(A)::value>));
+            set((const void*)SecondaryStaticFn<>(k_trace_secondary_static<decltype(C)::value, false, decltype(Li)::value, decltype(A)::value>));
           });
       }); });
   set((const void*)k_tail<L_DIFF>);
@@ -1975,15 +2146,15 @@ int configure_traversal_lds(fh_ctx* ctx, uint32_t stack_bytes)
       set((const void*)k_tail_lt<L_COAT | L_METAL | L_SPEC | L_DIFF, decltype(E)::value>);
       set((const void*)k_tail_lt<L_ALL, decltype(E)::value>);
     });
-  for (int a = 0; a < 2; ++a)
+  for (int a = 0; a < 2; ++a)  // fh_set_light_sampling: the forms that take pick_p, compiled with LIGHTS only
     with_bool(a != 0, [&](auto A) {
-      set((const void*)k_trace_merged_stream_lt<decltype(A)::value>);
+      set((const void*)MergedStreamFn<const float*>(k_trace_merged_stream<true, decltype(A)::value>));
       for (int c = 0; c < 2; ++c)
         with_bool(c != 0, [&](auto C) {
-          set((const void*)k_trace_secondary_stream_lt<decltype(C)::value, decltype(A)::value>);
-          set((const void*)k_trace_secondary_coop_lt<decltype(C)::value, decltype(A)::value>);
-          set((const void*)k_trace_secondary_static_lt<decltype(C)::value, true, decltype(A)::value>);
-          set((const void*)k_trace_secondary_static_lt<decltype(C)::value, false, decltype(A)::value>);
+          set((const void*)SecondaryStreamFn<const float*>(k_trace_secondary_stream<decltype(C)::value, true, decltype(A)::value>));
+          set((const void*)SecondaryCoopFn<const float*>(k_trace_secondary_coop<decltype(C)::value, true, decltype(A)::value>));
+          set((const void*)SecondaryStaticFn<const float*>(k_trace_secondary_static<decltype(C)::value, true, true, decltype(A)::value>));
+          set((const void*)SecondaryStaticFn<const float*>(k_trace_secondary_static<decltype(C)::value, false, true, decltype(A)::value>));
         });
     });
   if (err != hipSuccess) return fail(ctx, FH_E_HIP, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(err));
@@ -2405,7 +2576,7 @@ struct Call {
   StreamPlan plan;
   EnvTable env;  // fh_set_env_sampling; env_on: the shade kernels and the fused tail of this call are the ENV variants
   bool env_on;
-  LightTable lt;  // fh_set_light_sampling; lt_on (the switch is on AND the scene has emitters): the shade, tail and secondary-ray kernels of this call are the twins that take it
+  LightTable lt;  // fh_set_light_sampling; lt_on (the switch is on AND the scene has emitters): the shade, tail and secondary-ray kernels of this call are the forms that take it
   bool lt_on;
 };
 
@@ -2495,44 +2666,35 @@ void launch_closest(const Call& c, const Pass& p, const PoolDev& pd, uint32_t de
   ctx->stats.n_closest_launches++;
 }
 
+// The LIGHTS flag of a call's secondary-ray kernels and what its launches append for fh_set_light_sampling: (false), (true) or (true, pick_p) -- lt_on means emitters,
+// and no kernel is compiled for (false, pick_p)
+template <typename F>
+void with_lights(const Call& c, const SceneDev& sc, F&& f)
+{
+  if (c.lt_on) f(std::true_type{}, c.lt.pick_p);
+  else with_bool(sc.n_lights > 0, f);
+}
+
 void launch_secondary(const Call& c, const Pass& p, const PoolDev& ps, uint32_t depth)
 {
   fh_ctx* const ctx = c.ctx;
   const StreamPlan& pl = c.plan;
   const SceneDev& sc = p.sc;
   Span sp(ctx, p.sb, 1);
-  if (c.lt_on) {  // (the scene has emitters: the LIGHTS forms)
+  with_lights(c, sc, [&](auto Li, auto... pick_p) { with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
     if (pl.stream) {
-      with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
-        hipLaunchKernelGGL((k_trace_secondary_stream_lt<decltype(C)::value, decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.sb, sc, c.fr, ps, depth,
-                           c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u), c.lt.pick_p);
-      }); });
+      hipLaunchKernelGGL((k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.sb, sc, c.fr, ps,
+                         depth, c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u), pick_p...);
     } else if (pl.coop) {
-      with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
-        hipLaunchKernelGGL((k_trace_secondary_coop_lt<decltype(C)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps, depth, c.tc_shadow, p.coop_flush, c.lt.pick_p);
-      }); });
-    } else {
-      with_bool(c.count, [&](auto C) { with_bool(sc.use_bvh8 != 0, [&](auto W) { with_bool(sc.has_alpha != 0, [&](auto A) {
-        hipLaunchKernelGGL((k_trace_secondary_static_lt<decltype(C)::value, decltype(W)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps, depth, c.tc_shadow,
-                           c.lt.pick_p);
-      }); }); });
-    }
-  } else if (pl.stream) {
-    with_secondary_stream(c.count, sc.n_lights > 0, sc.has_alpha != 0, [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.sb, sc, c.fr, ps, depth, c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1],
-                         ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u));
-    });
-  } else if (pl.coop) {
-    with_bool(c.count, [&](auto C) { with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
       hipLaunchKernelGGL((k_trace_secondary_coop<decltype(C)::value, decltype(Li)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps, depth, c.tc_shadow,
-                         p.coop_flush);
-    }); }); });
-  } else {
-    with_bool(c.count, [&](auto C) { with_bool(sc.use_bvh8 != 0, [&](auto W) { with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
-      hipLaunchKernelGGL((k_trace_secondary_static<decltype(C)::value, decltype(W)::value, decltype(Li)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps,
-                         depth, c.tc_shadow);
-    }); }); }); });
-  }
+                         p.coop_flush, pick_p...);
+    } else {
+      with_bool(sc.use_bvh8 != 0, [&](auto W) {
+        hipLaunchKernelGGL((k_trace_secondary_static<decltype(C)::value, decltype(W)::value, decltype(Li)::value, decltype(A)::value>), dim3(p.grid), dim3(kBlock), pl.stack_bytes, p.sb, sc, c.fr, ps,
+                           depth, c.tc_shadow, pick_p...);
+      });
+    }
+  }); }); });
   ctx->stats.n_shadow_launches++;
 }
 
@@ -2543,13 +2705,9 @@ void launch_merged(const Call& c, const Pass& p, const PoolDev& ps, const PoolDe
   const StreamPlan& pl = c.plan;
   const SceneDev& sc = p.sc;
   Span sp(ctx, p.st, 1);
-  if (c.lt_on) with_bool(sc.has_alpha != 0, [&](auto A) {
-    hipLaunchKernelGGL((k_trace_merged_stream_lt<decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.st, sc, c.fr, ps, pd, depth,
-                       c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u), c.lt.pick_p);
-  });
-  else with_bool(sc.n_lights > 0, [&](auto Li) { with_bool(sc.has_alpha != 0, [&](auto A) {
+  with_lights(c, sc, [&](auto Li, auto... pick_p) { with_bool(sc.has_alpha != 0, [&](auto A) {
     hipLaunchKernelGGL((k_trace_merged_stream<decltype(Li)::value, decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.st, sc, c.fr, ps, pd, depth,
-                       c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u));
+                       c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u), pick_p...);
   }); });
   ctx->stats.n_shadow_launches++;
   ctx->stats.n_closest_launches++;

@@ -15,10 +15,11 @@ interior, lit by a generated 2048 x 1024 sun-and-sky image in place of its Hosek
   trace  python3 tools/env_sampling_bench.py trace [--width 960 --height 540 --spp 16 --frames 8]
          One process that renders nothing but `frames` frames with the switch off and then `frames` with it on.  Run it under
              rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python3 tools/env_sampling_bench.py trace ...
-         (no counters): DIR/.../NAME_kernel_stats.csv then has the k_shade launches of the off frames and the k_shade_env launches of the on frames, in one trace.
+         (no counters): DIR/.../NAME_kernel_stats.csv then has the k_shade launches of the off frames and the k_shade<..., fh::EnvTable> launches of the on frames, in one trace.
   merge  python3 tools/env_sampling_bench.py merge --legs FILE.json --stats STATS.csv --frames 8 --out profiles/env_sampling_bench.json   (no GPU)
          The leg's record with the summed time of the k_shade and of the k_shade_env launches of the trace per shaded hit (the two modes shade the same hits: the
-         next direction of a path does not depend on how its sky ray was drawn), and the table's build kernels.
+         next direction of a path does not depend on how its sky ray was drawn), and the table's build kernels.  The launches with the table count under the record's
+         key k_shade_env (kernel_families.py), as when they were a kernel of that name.
 """
 import argparse
 import csv
@@ -32,6 +33,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from kernel_families import family  # noqa: E402
 
 
 def sun_and_sky(w=2048, h=1024):
@@ -147,10 +151,11 @@ def kernel_rows(path):
     """summed over the instantiations: (calls, total ns) of k_shade and of k_shade_env; the table's build kernels one by one"""
     rows = {}
     for row in csv.DictReader(open(path)):
-        m = re.search(r"(k_shade_env|k_shade|k_tail_env|k_tail|k_env_weights|k_env_rows|k_env_marginal|k_env_cells)", row["Name"])
-        if not m:
+        m = re.search(r"(k_env_weights|k_env_rows|k_env_marginal|k_env_cells)", row["Name"])
+        fam = m.group(1) if m else family(row["Name"])  # (the forms with the table: kernel_families.py)
+        if fam not in ("k_shade_env", "k_shade", "k_tail_env", "k_tail", "k_env_weights", "k_env_rows", "k_env_marginal", "k_env_cells"):
             continue
-        c = rows.setdefault(m.group(1), {"calls": 0, "total_ns": 0})
+        c = rows.setdefault(fam, {"calls": 0, "total_ns": 0})
         c["calls"] += int(row["Calls"])
         c["total_ns"] += int(row["TotalDurationNs"])
     return rows

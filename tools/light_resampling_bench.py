@@ -12,7 +12,7 @@
          (no counters): NAME_kernel_trace.csv then holds every dispatch with its start and end.
   merge  python3 tools/light_resampling_bench.py merge --legs FILE.json --trace TRACE.csv --frames 8 [--resources FILE.json] [--bench FILE.json]
              --out profiles/light_resampling_bench.json   (no GPU)
-         k_shade_lt, k_tail_lt and all kernels together per frame and mode from the trace, cut at the separators.
+         k_shade_lt (the k_shade<..., fh::LightTable> launches: kernel_families.py), k_tail_lt and all kernels together per frame and mode from the trace, cut at the separators.
 """
 import argparse
 import csv
@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import light_sampling_bench as LB  # noqa: E402
+from kernel_families import family  # noqa: E402
 
 MS = (4, 8, 16)
 MODES = ["table"] + ["resampled_%d" % m for m in MS] + ["off"]
@@ -148,12 +149,9 @@ def trace_segments(path, frames):
             continue
         c = out.setdefault(MODES[seg], {"k_shade_lt_us_per_frame": 0.0, "k_tail_lt_us_per_frame": 0.0, "k_shade_us_per_frame": 0.0, "k_tail_us_per_frame": 0.0, "all_kernels_us_per_frame": 0.0})
         c["all_kernels_us_per_frame"] += dur / 1e3 / frames
-        for fam in ("k_shade_lt", "k_tail_lt"):
-            if fam + "<" in name or fam + "I" in name:
-                c[fam + "_us_per_frame"] += dur / 1e3 / frames
-        for fam in ("k_shade", "k_tail"):
-            if (fam + "<" in name or fam + "I" in name) and "_lt" not in name and "_env" not in name:
-                c[fam + "_us_per_frame"] += dur / 1e3 / frames
+        fam = family(name)  # (the forms with the light table count as k_shade_lt, k_tail_lt: kernel_families.py)
+        if fam in ("k_shade_lt", "k_tail_lt", "k_shade", "k_tail"):
+            c[fam + "_us_per_frame"] += dur / 1e3 / frames
     return {m: {k: round(v, 2) for k, v in c.items()} for m, c in out.items()}
 
 

@@ -10,7 +10,8 @@
   trace  python3 tools/light_sampling_bench.py trace [--width 240 --height 135 --spp 16 --frames 8]
          One process: the three table builds, then `frames` frames of the interior with the switch off and `frames` with it on.  Run it under
              rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python3 tools/light_sampling_bench.py trace ...
-         (no counters): NAME_kernel_stats.csv then has the plain kernels of the off frames and the _lt twins of the on frames in one trace.
+         (no counters): NAME_kernel_stats.csv then has the plain kernels of the off frames and, of the on frames, the forms that take the light table or pick_p
+         (kernel_families.py: counted under the record's keys k_shade_lt, k_trace_secondary_stream_lt ...) in one trace.
   merge  python3 tools/light_sampling_bench.py merge --legs FILE.json --stats STATS.csv --frames 8 [--listing render.s] --out profiles/light_sampling_bench.json   (no GPU)
          (b) summed time of the shade, tail and secondary-ray kernels per shaded hit, plain against _lt; (a) the build kernels one by one;
          (c) registers, scratch and LDS of the new instantiations from the metadata of a device listing (hipcc -S --cuda-device-only render.hip).
@@ -21,7 +22,6 @@ import json
 import os
 import re
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
@@ -29,6 +29,10 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from kernel_families import family, template_id  # noqa: E402
+
 STRIPS = (2, 1025, 1000000)
 
 
@@ -160,12 +164,13 @@ FAMILIES = ("k_shade_lt", "k_shade_env", "k_shade", "k_tail_lt", "k_tail_env", "
 
 def kernel_rows(path):
     rows = {}
-    pat = re.compile(r"\b(" + "|".join(FAMILIES) + r")\b")
+    pat = re.compile(r"\b(k_light_\w+)\b")
     for row in csv.DictReader(open(path)):
         m = pat.search(row["Name"])
-        if not m:
+        fam = m.group(1) if m else family(row["Name"])  # (the forms with a table: kernel_families.py)
+        if fam not in FAMILIES:
             continue
-        c = rows.setdefault(m.group(1), {"calls": 0, "total_ns": 0})
+        c = rows.setdefault(fam, {"calls": 0, "total_ns": 0})
         c["calls"] += int(row["Calls"])
         c["total_ns"] += int(row["TotalDurationNs"])
     return rows
@@ -176,10 +181,8 @@ def listing_metadata(path):
     out = {}
     for m in re.finditer(r"\.group_segment_fixed_size: (\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size: (\d+).*?\.vgpr_count:\s+(\d+)", s, re.S):
         lds, name, scratch, vgpr = m.groups()
-        d = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout
-        d = d.split("(anonymous namespace)::")[-1].split("(")[0]
-        if "_lt<" in d:
-            out[d] = {"vgprs": int(vgpr), "scratch_bytes": int(scratch), "lds_bytes": int(lds)}
+        if (family(name) or "").endswith("_lt"):
+            out[template_id(name)[1]] = {"vgprs": int(vgpr), "scratch_bytes": int(scratch), "lds_bytes": int(lds)}
     return out
 
 
