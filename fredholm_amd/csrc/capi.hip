@@ -141,12 +141,13 @@ using namespace fh;
 
 namespace fh {
 // render.hip: pool_ensure -- path record 64, radiance 16, identity 8, flags 4, first-hit AOVs 64, a 48-byte place per kind of secondary ray, the pending
-// light ray 32 (emitters only); queues: two radiance + one spare + secondary + its sorted copy 5 x 4, two 16-bit keys, one entry per shading class
+// light ray 32 (emitters only); queues: two radiance + one spare + secondary + its sorted copy 5 x 4, two 16-bit keys, one entry per shading class; the escape
+// mask of the secondary queue's entries 1 (k_sky_resolve)
 uint64_t pool_bytes_per_path(const fh_ctx* ctx)
 {
   const uint32_t sec = 2u + (ctx->has_dir ? 1u : 0u) + (ctx->n_lights > 0 ? 1u : 0u);
   const uint32_t classes = ctx->n_classes < 1u ? 1u : ctx->n_classes;
-  return 64u + 16u + 8u + 4u + 64u + 48u * sec + (ctx->n_lights > 0 ? 32u : 0u) + 20u + 4u + 4u + 4u * classes;  // (... + queue keys and sorted queues 20, q_sec 4, q_prim 4, class queues)
+  return 64u + 16u + 8u + 4u + 64u + 48u * sec + (ctx->n_lights > 0 ? 32u : 0u) + 20u + 4u + 4u + 4u * classes + 1u;  // (... + queue keys and sorted queues 20, q_sec 4, q_prim 4, class queues, escape masks)
 }
 }  // namespace fh
 
@@ -231,6 +232,7 @@ int fh_ctx_create(int device, fh_ctx** out)
     env_off("FH_SORT", t.sort_queues);
     env_uint("FH_SORT_ONEPASS", 0, 2, t.sort_onepass);
     env_uint("FH_BOTTOM_UP", 0, 2, t.bottom_up);
+    env_uint("FH_SKY_DEFER", 0, 1, t.sky_defer);
     t.debug_tail = getenv("FH_DEBUG_TAIL") != nullptr;
     if (const char* e = getenv("FH_FORCE_ALPHA")) t.force_alpha = e[0] == '1';
   }

@@ -169,6 +169,8 @@ struct fh_ctx {
 
   // path pools: one per pass in flight (pass j uses slot j % n_slots and the stream of that slot); allocated on first use
   fh::PoolDev pool[3] = {};
+  fh::DeviceBuffer<unsigned long long> d_resolve_dbg;  // FH_DEBUG_TAIL: escaped sky and light rays, and the queue entries k_sky_resolve saw, of the call being submitted
+  uint8_t* pool_esc[3] = {nullptr, nullptr, nullptr};  // per pool, one byte per ENTRY of the secondary queue: the slots whose shadow ray escaped (render.hip: k_sky_resolve).  Not a PoolDev member: that is a kernel argument of every pass kernel
   struct PoolShape { bool dir = false, lights = false; uint32_t classes = 0; };  // what the records of a pool have room for (render.hip: pool_ensure)
   PoolShape pool_shape[3];
   std::vector<fh::DeviceBuffer<uint8_t>> pool_allocs[3];
@@ -238,6 +240,8 @@ struct fh_ctx {
                                     // they leave and climb; default (2): the first passes after a build try both and the counted test rounds per shaded path decide (render.hip)
     bool sort_queues = true;        // FH_SORT=0: trace the bounce queues in emission order
     uint32_t sort_onepass = 2;      // FH_SORT_ONEPASS: cell sorts in calls of ONE pass -- 0 none, 1 all (as in multi-pass calls), 2 only the queue the fused tail takes over
+    uint32_t sky_defer = 2;         // FH_SKY_DEFER=0|1: shadow rays of the sky and light slots carry weights and k_sky_resolve evaluates the environment for those that escape -- never / wherever
+                                    // a pass is eligible (render_plan_host.h: sky_defer_verdict); default (2): the library's own choice
     bool debug_tail = false;        // FH_DEBUG_TAIL
     bool force_alpha = false;       // FH_FORCE_ALPHA=1 (timing experiments): the kernels with the any-hit path compiled in, whatever the scene
   } tun;

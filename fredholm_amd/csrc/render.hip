@@ -852,13 +852,16 @@ FH_D f3 emission_of(const SceneDev& sc, const MaterialDev& m, float tu, float tv
 
 // (direction.w of a ray record: 0 = no ray in this place; otherwise 1 + the wide node the ray starts its traversal at -- the node that holds the face it leaves, fh_trace.h:
 // bottom-up start -- or 1 = the root.  Read as BITS everywhere: small integers are denormal floats.)
-FH_D void store_secondary(const PoolDev& pool, uint32_t slot, uint32_t p, f3 o, float tmax, f3 d, bool active, f3 c, uint32_t start_bits = 1u)
+// (contribution.w, read as bits: 0 = the ray's final contribution; kSecWeight = a WEIGHT, to be multiplied by the environment's radiance along the ray's direction
+// if the ray escapes -- the deferred mode of the sky and light slots, k_sky_resolve)
+constexpr uint32_t kSecWeight = 1u;
+FH_D void store_secondary(const PoolDev& pool, uint32_t slot, uint32_t p, f3 o, float tmax, f3 d, bool active, f3 c, uint32_t start_bits = 1u, uint32_t marker = 0u)
 {
   const size_t k = pool.sec_at(slot, p);
   pool.sec[k + 1] = mk4(d, __uint_as_float(active ? start_bits : 0u));
   if (!active) return;  // (nobody reads origin or contribution of a place without a ray)
   pool.sec[k] = mk4(o, tmax);
-  pool.sec[k + 2] = mk4(c, 0.0f);
+  pool.sec[k + 2] = mk4(c, __uint_as_float(marker));
 }
 
 
@@ -948,6 +951,13 @@ struct PoolSink {      // memory sink (k_shade): path slot p of the pool
     if (!shaded) origin = o;  // all rays of a path leave (almost) the same point
     shaded = true;
   }
+  // (deferred mode: the ray carries its weight w; what it adds if it escapes, w * env_radiance(d), is formed by k_sky_resolve)
+  FH_D void secondary_weight(uint32_t slot, f3 o, float tmax, f3 d, f3 w)
+  {
+    store_secondary(pool, slot, p, o, tmax, d, true, w, start_bits, kSecWeight);
+    if (!shaded) origin = o;
+    shaded = true;
+  }
   FH_D void light_pending(f3 t, float c, f3 f, float pdf) { pool.lp_a[p] = mk4(t, c); pool.lp_b[p] = mk4(f, pdf); }
   FH_D void next(f3 o, f3 d, f3 t)
   {
@@ -963,10 +973,15 @@ struct PoolSink {      // memory sink (k_shade): path slot p of the pool
 // by these variants only, and nothing else of the hit differs
 // LT (fh_set_light_sampling): the emitter of the area shadow ray is picked from the table of fh_lights.h and its density is the pick's probability over the area; `ltab`
 // is read by these variants only.  (The BSDF-sampled light ray's side of it is resolve_light_ray<true>.)
-template <uint32_t LOBES, bool ENV = false, bool LT = false, class Sink>
+// DEFER (PoolSink, scenes without emitters, no ENV / LT): the sky ray and the light ray are stored with their WEIGHT and the environment is evaluated by k_sky_resolve for
+// the rays that escape -- four of five do not.  A weight of exactly zero keeps today's path, because its ray is traced today only when the radiance is NaN (every
+// direction below the Hosek horizon) and that NaN must reach the sample: the environment is evaluated here and the product stored as final.  A non-zero weight whose
+// product would have been +-0 is now traced and adds +-0, which changes no bit (above `contributes`).
+template <uint32_t LOBES, bool ENV = false, bool LT = false, bool DEFER = false, class Sink>
 FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& rows, const BounceSlots& bs, uint32_t depth, float4 hit, f3 rd, f3 T, f3 L, uint32_t image_idx, uint32_t n_spp,
                     Sink& out, bool first = true, const EnvTable* env = nullptr, const LightTable* ltab = nullptr)
 {
+  static_assert(!DEFER || (!ENV && !LT), "the deferred slots are those of the plain draw");
   const uint32_t has_lights = bs.has_lights;
   const uint32_t prim = __float_as_uint(hit.w);
   const float bu = hit.y, bv = hit.z;
@@ -1063,8 +1078,17 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
     const f3 f = bsdf.eval(wo, wi);
     const float pdf = abs_cos(wi) / kPi;
     const float w = pdf / (pdf + bsdf.eval_pdf(wo, wi));
-    const f3 c = clamp01(T * w * f * abs_cos(wi) / pdf) * env_radiance(fr, sd);
-    out.secondary(SEC_SKY, so, 1e9f - 0.001f, sd, contributes(c), c);
+    if constexpr (DEFER) {
+      const f3 cw = clamp01(T * w * f * abs_cos(wi) / pdf);
+      if (contributes(cw)) out.secondary_weight(SEC_SKY, so, 1e9f - 0.001f, sd, cw);
+      else {
+        const f3 c = cw * env_radiance(fr, sd);
+        out.secondary(SEC_SKY, so, 1e9f - 0.001f, sd, contributes(c), c);
+      }
+    } else {
+      const f3 c = clamp01(T * w * f * abs_cos(wi) / pdf) * env_radiance(fr, sd);
+      out.secondary(SEC_SKY, so, 1e9f - 0.001f, sd, contributes(c), c);
+    }
   }
   // area lights (pt.cu:860-889, :282-322)
   if (has_lights) {
@@ -1137,8 +1161,17 @@ FH_D void shade_hit(const SceneDev& sc, const FrameDev& fr, const SobolRows<4>& 
       float pdf_light = abs_cos(wi) / kPi;
       if constexpr (ENV) pdf_light = env_pdf(*env, env_dir(ld), env_dir(ns), nullptr);
       const float w = pdf / (pdf + pdf_light);
-      const f3 c = clamp01(T * w * f * abs_cos(wi) / pdf) * env_radiance(fr, ld);
-      out.secondary(SEC_LIGHT, lo, 1e9f, ld, contributes(c), c);
+      if constexpr (DEFER) {
+        const f3 cw = clamp01(T * w * f * abs_cos(wi) / pdf);
+        if (contributes(cw)) out.secondary_weight(SEC_LIGHT, lo, 1e9f, ld, cw);
+        else {
+          const f3 c = cw * env_radiance(fr, ld);
+          out.secondary(SEC_LIGHT, lo, 1e9f, ld, contributes(c), c);
+        }
+      } else {
+        const f3 c = clamp01(T * w * f * abs_cos(wi) / pdf) * env_radiance(fr, ld);
+        out.secondary(SEC_LIGHT, lo, 1e9f, ld, contributes(c), c);
+      }
     }
   }
   // next direction (pt.cu:928-943) and the next bounce's Russian roulette (pt.cu:457-471)
@@ -1246,6 +1279,7 @@ __global__ void __launch_bounds__(kSortBlock) k_cell_scatter(const uint32_t* cou
 // device function shared by several kernels: the body stays inside the kernel and a plain instantiation keeps its name, its arguments and its instruction stream -- after
 // ANY edit of these bodies compare a device listing of render.hip with the one before it (tools/kernel_asm_diff.py): the plain kernels may differ in nothing.
 struct UnreadEnvTable { EnvTable t; };  // holds the place, and the kernarg offsets, of the environment table in the (-, LightTable) forms: table_of<EnvTable> does not find it
+struct DeferSky {};  // k_shade's pack of the deferred mode (shade_hit<..., DEFER>): no table, only the name of the form.  The secondary-ray kernel's is (esc), the escape masks it writes
 template <class T>
 FH_D const T* table_of() { return nullptr; }
 template <class T, class First, class... Rest>
@@ -1256,12 +1290,17 @@ FH_D const T* table_of(const First& f, const Rest&... r)
 }
 FH_D const float* pick_p_of() { return nullptr; }
 FH_D const float* pick_p_of(const float* pick_p) { return pick_p; }
+FH_D const float* pick_p_of(uint8_t*) { return nullptr; }
+FH_D uint8_t* esc_of() { return nullptr; }
+FH_D uint8_t* esc_of(const float*) { return nullptr; }
+FH_D uint8_t* esc_of(uint8_t* esc) { return esc; }
 
 // (with tables: compiled for the lobe sets of the fused tail (TailLobes), FH_SHADE_BLOCKS workgroups per CU)
 template <uint32_t LOBES, int BLOCKS = FH_SHADE_BLOCKS, class... Tables>
 __global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : BLOCKS)) k_shade(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t cls, uint32_t depth, Tables... tables)
 {
   constexpr bool ENV = (std::is_same<Tables, EnvTable>::value || ...), LT = (std::is_same<Tables, LightTable>::value || ...);
+  constexpr bool DEFER = (std::is_same<Tables, DeferSky>::value || ...);
   const EnvTable* const env = table_of<EnvTable>(tables...);
   const LightTable* const ltab = table_of<LightTable>(tables...);
   pass_priority();
@@ -1312,7 +1351,7 @@ __global__ void __launch_bounds__(kBlock, (LOBES == L_ALL ? 1 : BLOCKS)) k_shade
       PoolSink o(pool, p, hit.x);
       const bool first = depth != 0 || (pool.flags[p] & 4u) == 0u;
       const f3 L = depth == 0u ? mk3(pool.rad[p]) : mk3(0.0f);  // the radiance so far only enters at a directly visible emitter (first hit): later bounces skip the load
-      shade_hit<LOBES, ENV, LT>(sc, fr, rows, bs, depth, hit, mk3(pool.ray_d[p]), mk3(pool.thr[p]), L, pool.pixel[p], pool.nspp[p], o, first, env, ltab);
+      shade_hit<LOBES, ENV, LT, DEFER>(sc, fr, rows, bs, depth, hit, mk3(pool.ray_d[p]), mk3(pool.thr[p]), L, pool.pixel[p], pool.nspp[p], o, first, env, ltab);
       shaded = o.shaded;
       cont = o.cont;
       if (shaded || cont) cell = cell_of(fr, o.origin);
@@ -1484,8 +1523,11 @@ __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? 5 : 6)) k_trace_
 // (Items that are single RAYS instead of paths -- so that a small launch would end in its longest ray, not in its longest path -- were built and measured in round 6, bit-identical
 // and SLOWER: the rays of a path share their first nodes, and the launches of one-pass calls are not bound by a lane's chain.  tools/patches/r6_ray_items.patch, profiles/README.md r6-8.)
 // LT (fh_set_light_sampling): the light rays are finished by resolve_light_ray<true>, which reads pick_p
-template <bool COUNT, bool LIGHTS, bool LT = false>
+// DEFER (no emitters): the lane does not carry the path's radiance.  It notes which slots' rays escaped and leaves that mask, one byte, at the QUEUE POSITION of its
+// item (esc[i]: dense, read back coalesced); k_sky_resolve adds what the escaped rays contribute, in the same slot order.  Neither pool.rad nor the contributions are touched here.
+template <bool COUNT, bool LIGHTS, bool LT = false, bool DEFER = false>
 struct SecondaryStream {
+  static_assert(!DEFER || !LIGHTS, "light rays that find an emitter are finished in the commit");
   static constexpr bool all_any = !LIGHTS;  // without emitters every secondary ray stops at its first hit
   static constexpr bool can_climb = true;   // first-hit rays may start at the node of the face they leave (fh_trace.h: bottom-up start)
   const SceneDev& sc;
@@ -1500,8 +1542,10 @@ struct SecondaryStream {
   unsigned long long* hist;
   HistPack hp;
   const float* pick_p;
-  FH_D SecondaryStream(const SceneDev& s, const FrameDev& f, const PoolDev& pl, const ChunkFeed& cf, unsigned long long* hs, const float* pp = nullptr)
-      : sc(s), fr(f), pool(pl), feed(cf), L(mk3(0.0f)), hist(hs), pick_p(pp) {}
+  uint32_t item = 0, escaped = 0;  // DEFER: queue position of the lane's item; bit s: the ray of slot s escaped
+  uint8_t* esc;
+  FH_D SecondaryStream(const SceneDev& s, const FrameDev& f, const PoolDev& pl, const ChunkFeed& cf, unsigned long long* hs, const float* pp = nullptr, uint8_t* es = nullptr)
+      : sc(s), fr(f), pool(pl), feed(cf), L(mk3(0.0f)), hist(hs), pick_p(pp), esc(es) {}
   // first slot >= from of path p that holds a ray
   FH_D bool scan(uint32_t from, f3& o, f3& d, float& tmax, bool& any)
   {
@@ -1521,7 +1565,13 @@ struct SecondaryStream {
     }
     return false;
   }
-  FH_D void finish() { if (active) { pool.rad[p] = mk4(L, 0.0f); active = false; } }
+  FH_D void finish()
+  {
+    if (!active) return;
+    if constexpr (DEFER) esc[item] = (uint8_t)escaped;
+    else pool.rad[p] = mk4(L, 0.0f);
+    active = false;
+  }
   FH_D bool advance(f3& o, f3& d, float& tmax, bool& any)
   {
     if (!active) return false;
@@ -1537,10 +1587,12 @@ struct SecondaryStream {
   FH_D bool take_item(uint32_t i, f3& o, f3& d, float& tmax, bool& any)
   {
     p = pool.q_sec[i];
-    L = mk3(pool.rad[p]);
+    if constexpr (DEFER) { item = i; escaped = 0u; }
+    else L = mk3(pool.rad[p]);
     active = true;
     if (scan(0u, o, d, tmax, any)) return true;
     active = false;  // a path without secondary rays: its radiance stays as it is
+    if constexpr (DEFER) esc[i] = 0u;  // (every entry of the queue reads back: nothing escaped)
     return false;
   }
   FH_D void commit(bool hit, const HitRec& h, uint32_t nodes)
@@ -1552,7 +1604,8 @@ struct SecondaryStream {
       L += resolve_light_ray<LT>(sc, fr, mk3(la), la.w, mk3(lb), lb.w, mk3(o), mk3(d), hit, h, pick_p);
     } else {
       if (COUNT) hp.add(nodes);
-      if (!hit) L += mk3(pool.sec[k + 2]);
+      if constexpr (DEFER) { if (!hit) escaped |= 1u << slot; }
+      else if (!hit) L += mk3(pool.sec[k + 2]);
     }
   }
   FH_D bool drained() const { return feed.drained(); }
@@ -1563,8 +1616,9 @@ struct SecondaryStream {
 template <bool COUNT, bool LIGHTS, bool ALPHA, class... PickP>
 __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLOCKS_HEAVY : (ALPHA ? FH_STREAM_BLOCKS_ALPHA : FH_STREAM_BLOCKS))) k_trace_secondary_stream(SceneDev sc, FrameDev fr, PoolDev pool, uint32_t depth, TraceCounters tc, uint32_t flush, uint32_t refill, uint32_t chunk, uint32_t min_rays, StackSpill spill, PickP... pp)
 {
-  constexpr bool LT = sizeof...(PickP) != 0;
+  constexpr bool LT = (std::is_same<PickP, const float*>::value || ...), DEFER = (std::is_same<PickP, uint8_t*>::value || ...);  // the pack: nothing, (pick_p) or (esc)
   static_assert(LIGHTS || !LT, "pick probabilities without emitters");
+  static_assert(!LIGHTS || !DEFER, "escape masks with emitters");
   const float* const pick_p = pick_p_of(pp...);
   pass_priority();
   extern __shared__ __attribute__((aligned(16))) uint2 lds_stack[];  // [entry][thread], sized by the launcher for the depth of the BVH
@@ -1578,7 +1632,7 @@ __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLO
   AlphaLds<AlphaDefer<true, ALPHA>::value>::attach(cl);  // candidates waiting for their any-hit test (fh_trace.h: alpha_ring): LDS of the kernels with the test compiled in only
   uint32_t nn = 0, nt = 0;
   WaveSteps ws;
-  SecondaryStream<COUNT, LIGHTS, LT> pol(sc, fr, pool, ChunkFeed(pool.counters + depth * kCounterStride + CNT_CUR_SEC, count, stream_chunk_for(count, chunk)), tc.hist, pick_p);
+  SecondaryStream<COUNT, LIGHTS, LT, DEFER> pol(sc, fr, pool, ChunkFeed(pool.counters + depth * kCounterStride + CNT_CUR_SEC, count, stream_chunk_for(count, chunk)), tc.hist, pick_p, esc_of(pp...));
   __shared__ uint4 lds_top[kTopNodes * 4];
   stage_top_nodes(sc.bvh8, lds_top);
   traverse_stream<true, COUNT, true, ALPHA>(sc.bvh8, pol, nn, nt, &ws, cl, flush, refill, lds_stack, (int)sc.bvh8.depth, &sc, spill, lds_top,
@@ -1592,6 +1646,90 @@ __global__ void __launch_bounds__(kBlock, COUNT ? 1 : (LIGHTS ? FH_SECONDARY_BLO
     pol.hp.flush(tc.hist);
     if (ws.node) atomicAdd(tc.wave_nodes, (unsigned long long)ws.node);
     if (ws.tri) atomicAdd(tc.wave_tris, (unsigned long long)ws.tri);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The deferred mode's second half, one launch per bounce behind k_trace_secondary_stream<..., esc>: what the escaped shadow rays add to their paths.
+// A workgroup takes kResolveItems consecutive entries of the secondary queue per round, four per thread:
+//   (a) every thread reads the escape masks of its entries and counts their escaped sky and light rays; a block scan gives each of them a place in a dense list
+//       (entry of the round, slot) that lives in LDS;
+//   (b) the threads walk the list densely -- no lane idles beside an occluded ray, which is what an evaluation inside the traversal's commit would cost -- read the ray's
+//       direction and weight, and leave w * env_radiance(d) in LDS at the ray's place in the list (a contribution stored as final, marker 0, is passed through);
+//   (c) the owner of an entry with a non-zero mask adds to its path's radiance in slot order: the directional light's contribution from the record, sky and light from LDS.
+// Same functions, same operand values and the same order of additions as SecondaryStream::commit / finish without DEFER: every bit stays.  No global atomics.
+// dbg (FH_DEBUG_TAIL, else null): [0] += escaped sky and light rays, [1] += queue entries seen.
+constexpr uint32_t kResolveItems = 4u * kBlock;
+__global__ void __launch_bounds__(kBlock) k_sky_resolve(FrameDev fr, PoolDev pool, const uint8_t* esc, uint32_t depth, unsigned long long* dbg)
+{
+  const uint32_t count = pool.counters[depth * kCounterStride + CNT_SEC];
+  if (blockIdx.x * kResolveItems >= count) return;
+  __shared__ HosekSky s_sky;
+  stage_sky(fr, s_sky);  // (published by the first barrier of the scan)
+  __shared__ uint32_t s_p[kResolveItems];           // path slot of the round's entries that have an escaped ray
+  __shared__ uint16_t s_list[2u * kResolveItems];   // entry of the round << 2 | slot
+  __shared__ float s_c[3][2u * kResolveItems];      // contribution of list entry e
+  __shared__ uint32_t s_wave[kBlock / 64];
+  constexpr uint32_t kDeferred = (1u << SEC_SKY) | (1u << SEC_LIGHT);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (uint32_t tile = blockIdx.x * kResolveItems; tile < count; tile += gridDim.x * kResolveItems) {
+    uint32_t m[4], n = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; ++r) {
+      const uint32_t li = r * kBlock + threadIdx.x, i = tile + li;
+      m[r] = i < count ? esc[i] : 0u;
+      if (m[r]) s_p[li] = pool.q_sec[i];
+      n += (uint32_t)__popc(m[r] & kDeferred);
+    }
+    uint32_t incl = n;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t v = __shfl_up(incl, d);
+      if (lane >= d) incl += v;
+    }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t base = incl - n, total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBlock / 64u; ++w) {
+      const uint32_t v = s_wave[w];
+      if (w < wave) base += v;
+      total += v;
+    }
+    {
+      uint32_t pos = base;
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; ++r) {
+        const uint32_t li = r * kBlock + threadIdx.x;
+        if (m[r] & (1u << SEC_SKY)) s_list[pos++] = (uint16_t)(li << 2 | SEC_SKY);
+        if (m[r] & (1u << SEC_LIGHT)) s_list[pos++] = (uint16_t)(li << 2 | SEC_LIGHT);
+      }
+    }
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < total; e += kBlock) {
+      const uint32_t entry = s_list[e];
+      const size_t k = pool.sec_at(entry & 3u, s_p[entry >> 2]);
+      const float4 d4 = pool.sec[k + 1], c4 = pool.sec[k + 2];
+      f3 c = mk3(c4);
+      if (__float_as_uint(c4.w) == kSecWeight) c = c * env_radiance(fr, mk3(d4));
+      s_c[0][e] = c.x; s_c[1][e] = c.y; s_c[2][e] = c.z;
+    }
+    __syncthreads();
+    {
+      uint32_t pos = base;
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; ++r) {
+        if (!m[r]) continue;
+        const uint32_t p = s_p[r * kBlock + threadIdx.x];
+        f3 L = mk3(pool.rad[p]);
+        if (m[r] & (1u << SEC_DIR)) L += mk3(pool.sec[pool.sec_at(SEC_DIR, p) + 2]);
+        if (m[r] & (1u << SEC_SKY)) { L += mk3(s_c[0][pos], s_c[1][pos], s_c[2][pos]); ++pos; }
+        if (m[r] & (1u << SEC_LIGHT)) { L += mk3(s_c[0][pos], s_c[1][pos], s_c[2][pos]); ++pos; }
+        pool.rad[p] = mk4(L, 0.0f);
+      }
+    }
+    if (dbg && threadIdx.x == 0u) { atomicAdd(dbg, (unsigned long long)total); atomicAdd(dbg + 1, (unsigned long long)(count - tile < kResolveItems ? count - tile : kResolveItems)); }
+    __syncthreads();  // (the next round reuses the lists)
   }
 }
 
@@ -1872,13 +2010,15 @@ void with_compiled_lobes(uint32_t lobes, LobeSet<V, Rest...>, F&& f)
 }
 
 void dispatch_shade(hipStream_t st, uint32_t grid, uint32_t lobes, const SceneDev& sc, const FrameDev& fr, const PoolDev& pool, uint32_t cls, uint32_t depth, bool three, const EnvTable* env,
-                    const EnvTable& env_table, const LightTable* lt)
+                    const EnvTable& env_table, const LightTable* lt, bool defer = false)
 {
   with_tables(env != nullptr, env_table, lt, [&](auto... tables) {
     constexpr bool plain = sizeof...(tables) == 0;  // the forms that take tables are compiled for the tail's lobe sets, and at FH_SHADE_BLOCKS only
     with_compiled_lobes(lobes, std::conditional_t<plain, ShadeLobes, TailLobes>{}, [&](auto V) {
       constexpr uint32_t LOBES = decltype(V)::value;
       if constexpr (plain && LOBES != L_ALL) {
+        // (the deferred forms exist in the three-workgroup set only; a class of the generic kernel stores final contributions, which k_sky_resolve passes through)
+        if (three && defer) { hipLaunchKernelGGL((k_shade<LOBES, 3>), dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, DeferSky{}); return; }
         if (three) { hipLaunchKernelGGL((k_shade<LOBES, 3>), dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth); return; }
       }
       hipLaunchKernelGGL(k_shade<LOBES>, dim3(grid), dim3(kBlock), 0, st, sc, fr, pool, cls, depth, tables...);
@@ -2027,6 +2167,7 @@ void pool_release(fh_ctx* ctx)
     ctx->pool_allocs[k].clear();
     ctx->pool_alloc_bytes[k] = 0;
     ctx->pool[k] = PoolDev{};
+    ctx->pool_esc[k] = nullptr;
     ctx->pool_shape[k] = fh_ctx::PoolShape{};
     ctx->counters_in_flight[k] = false;
   }
@@ -2050,6 +2191,7 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
     if (ctx->pool_target_by_caller && ctx->pool[slot].capacity > capacity) capacity = ctx->pool[slot].capacity;  // (a default-sized pool is re-made at the size the memory cap of this call allows)
     need.dir = need.dir || have.dir; need.lights = need.lights || have.lights; need.classes = need.classes > have.classes ? need.classes : have.classes;
     ctx->pool[slot] = PoolDev{};
+    ctx->pool_esc[slot] = nullptr;
     have = fh_ctx::PoolShape{};
     ctx->counters_in_flight[slot] = false;
   }
@@ -2084,6 +2226,7 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
     FH_POOL(P.counters, (size_t)kCounterStride * 66);  // up to 65 bounces per pass
     FH_POOL(P.key_sec, n); FH_POOL(P.key_rad, n); FH_POOL(P.q_tmp, n); FH_POOL(P.q_sec_sorted, n);
     FH_POOL(P.bins, (size_t)2 * kCells);
+    FH_POOL(ctx->pool_esc[slot], n);  // (every entry a deferred secondary launch takes is written by it before k_sky_resolve reads it: no fill)
 #undef FH_POOL
     // (on the stream this slot's passes run on, where the sorts that use the bins follow it: hipMemset on the null stream returns before the fill has run and is ordered
     // with NOTHING on a non-blocking stream -- a pass whose first sort overtook the fill counted into whatever the allocation held, turned that into scatter cursors and wrote
@@ -2095,6 +2238,7 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
     ctx->pool_allocs[slot].clear();
     ctx->pool_alloc_bytes[slot] = 0;
     P = PoolDev{};
+    ctx->pool_esc[slot] = nullptr;
     return fail(ctx, FH_E_HIP, std::string("path pool allocation: ") + hipGetErrorString(e));
   }
   P.capacity = capacity;
@@ -2122,6 +2266,7 @@ int configure_traversal_lds(fh_ctx* ctx, uint32_t stack_bytes)
       with_bool(c != 0, [&](auto C) { with_bool(a != 0, [&](auto A) {
         set((const void*)k_trace_closest_stream<decltype(C)::value, decltype(A)::value>);
         set((const void*)k_trace_closest_coop<decltype(C)::value, decltype(A)::value>);
+        set((const void*)SecondaryStreamFn<uint8_t*>(k_trace_secondary_stream<decltype(C)::value, false, decltype(A)::value>));  // (the deferred mode's form: it leaves escape masks)
         for (int l = 0; l < 2; ++l)
           with_bool(l != 0, [&](auto Li) {
             set((const void*)SecondaryStreamFn<>(k_trace_secondary_stream<decltype(C)::value, decltype(Li)::value, decltype(A)::value>));
@@ -2564,6 +2709,9 @@ int stream_plan(fh_ctx* ctx, const SceneDev& sc, bool count, bool filler, Stream
   return FH_OK;
 }
 
+// The deferred mode of the sky and light slots where a pass is eligible and FH_SKY_DEFER says nothing (profiles/README.md, profiles/sky_defer_bench.json)
+constexpr bool kSkyDeferByDefault = true;
+
 // what every pass of one fh_render call shares
 struct Call {
   fh_ctx* ctx;
@@ -2587,6 +2735,7 @@ struct Pass {
   hipStream_t st, sb;  // the pass's stream; the stream of its secondary launches (the same, but for the overlap form of a one-pass call)
   uint32_t grid, coop_flush, wave_depth;
   bool single_pass, merge, overlap;
+  bool defer;          // the sky and light slots carry weights; k_sky_resolve follows every secondary launch (render_plan_host.h: sky_defer_verdict)
 };
 
 // the counter snapshots of earlier passes that have arrived: the share of a pass's paths alive at each depth (context.h: survival) and, while the scene's ray start is
@@ -2680,6 +2829,21 @@ void launch_secondary(const Call& c, const Pass& p, const PoolDev& ps, uint32_t 
   fh_ctx* const ctx = c.ctx;
   const StreamPlan& pl = c.plan;
   const SceneDev& sc = p.sc;
+  if (p.defer) {  // (sky_defer_verdict: no emitters, the streaming kernel) -- the form that leaves escape masks, and right behind it, on the same stream, what they add
+    uint8_t* const esc = ctx->pool_esc[p.slot];
+    {
+      Span sp(ctx, p.sb, 1);
+      with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
+        hipLaunchKernelGGL((k_trace_secondary_stream<decltype(C)::value, false, decltype(A)::value>), dim3(p.grid < pl.grid[1] ? p.grid : pl.grid[1]), dim3(kBlock), pl.lds_bytes[1], p.sb, sc, c.fr, ps,
+                           depth, c.tc_shadow, p.coop_flush, ctx->tun.stream_refill, pl.chunk[1], ctx->tun.stream_min_rays, stack_spill(c, p, 1, p.probe >= 0 ? 1u : 0u), esc);
+      }); });
+    }
+    Span sp(ctx, p.sb, 2);  // (the part of shading that moved)
+    // (p.grid: a workgroup per 256 paths of the pass, at most 8192; grid-stride beyond, and the workgroups past the queue's end leave at once)
+    hipLaunchKernelGGL(k_sky_resolve, dim3((p.grid + kResolveItems / kBlock - 1u) / (kResolveItems / kBlock)), dim3(kBlock), 0, p.sb, c.fr, ps, (const uint8_t*)esc, depth, ctx->tun.debug_tail ? ctx->d_resolve_dbg.get() : nullptr);
+    ctx->stats.n_shadow_launches++;
+    return;
+  }
   Span sp(ctx, p.sb, 1);
   with_lights(c, sc, [&](auto Li, auto... pick_p) { with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
     if (pl.stream) {
@@ -2786,6 +2950,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
   // ... or, where the streaming kernels trace the scene, both in ONE launch (k_trace_merged_stream): one end instead of two, no second stream (FH_MERGE=0: the two-stream form)
   p.merge = p.single_pass && c.plan.stream && !c.count && tun.merge_trace;
   p.overlap = p.single_pass && tun.overlap_secondary && !p.merge;
+  p.defer = sky_defer_verdict(c.sc.n_lights > 0, c.fr.has_hosek != 0, c.fr.has_ibl != 0, c.env_on, c.lt_on, c.plan.stream, p.merge, c.plan.shade_three, tun.sky_defer, kSkyDeferByDefault);
   p.sb = st;
   if (p.overlap) {
     p.sb = (st == ctx->aux_stream[0]) ? ctx->aux_stream[1] : ctx->aux_stream[0];
@@ -2835,7 +3000,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
     if (p.overlap && depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (depth - 1u) + 1u], 0));  // the secondary launch of the bounce before reads what the shade kernels and the sorts below overwrite
     {
       Span sp(ctx, st, 2);
-      for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) dispatch_shade(st, p.grid, ctx->class_lobes[cls], p.sc, c.fr, pd, cls, depth, c.plan.shade_three, c.env_on ? &c.env : nullptr, c.env, c.lt_on ? &c.lt : nullptr);
+      for (uint32_t cls = 0; cls < ctx->n_classes; ++cls) dispatch_shade(st, p.grid, ctx->class_lobes[cls], p.sc, c.fr, pd, cls, depth, c.plan.shade_three, c.env_on ? &c.env : nullptr, c.env, c.lt_on ? &c.lt : nullptr, p.defer);
       if (depth == 0) hipLaunchKernelGGL(k_miss_primary, dim3(p.grid), dim3(kBlock), 0, st, c.fr, pd);
       ctx->stats.n_shade_launches += ctx->n_classes;
     }
@@ -2937,6 +3102,12 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
     }
   }
   { const int rc = stream_plan(ctx, c.sc, count, base.n_sky && sky.filler_wgs, c.plan); if (rc) return rc; }
+  if (ctx->tun.debug_tail) {  // (k_sky_resolve's list lengths of this call, printed below)
+    if (!ctx->d_resolve_dbg) FH_HIP(ctx->d_resolve_dbg.alloc(2));
+    FH_HIP(hipMemsetAsync(ctx->d_resolve_dbg, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    FH_HIP(hipEventRecord(ctx->ev_enter, ctx->stream));
+    for (int k = 0; k + 1 < ctx->n_slots; ++k) FH_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->ev_enter, 0));
+  }
 
   // (Small calls -- the reference's callers: 1 sample per call in the GUI, controller.cpp:224, 16 in rtcamp8, rtcamp8.cpp:183-189 -- cut into PIXEL sub-passes, each a pass of
   // its own in its own pool on its own stream, were built and measured in round 5: slower, configs[3] 1 spp 6.45 -> 8.24 ms.  tools/patches/r6_pruned_switches.patch, r5-4.)
@@ -2976,6 +3147,12 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   sky.end();
   if (base.n_sky && sky.st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky.st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
   FH_HIP(hipGetLastError());
+  if (ctx->tun.debug_tail) {  // (a debug switch: this waits for the call)
+    unsigned long long dbg[2] = {0ull, 0ull};
+    FH_HIP(hipStreamSynchronize(ctx->stream));
+    FH_HIP(hipMemcpy(dbg, ctx->d_resolve_dbg, sizeof(dbg), hipMemcpyDeviceToHost));
+    if (dbg[1]) fprintf(stderr, "[sky-resolve] %llu queue entries, %llu escaped sky / light rays: %.4f per entry\n", dbg[1], dbg[0], (double)dbg[0] / (double)dbg[1]);
+  }
   return FH_OK;
 }
 

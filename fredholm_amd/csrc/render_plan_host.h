@@ -138,4 +138,17 @@ inline void lens_values(float inv_tan, float focus, float F, float* a_plus_b, fl
   *lens_radius = lr;
 }
 
+// Whether a pass stores the sky and light slots of its shadow rays as WEIGHTS and k_sky_resolve evaluates the environment for the rays that escaped (render.hip):
+// only where the environment is worth deferring (Hosek sky or IBL; a constant background is one multiply and keeps its zero-contribution pruning), where nothing else
+// finishes those slots (emitters: resolve_light_ray; env / light-table sampling: their own weights) and where the kernels that know the mode run -- the streaming
+// secondary-ray launch of its own (not the merged launch of a one-pass call, not the fixed-batch kernels) after the three-workgroup shade set.
+// forced (FH_SKY_DEFER): 0 off, 1 on where eligible, anything else: `by_default`.
+inline bool sky_defer_verdict(bool emitters, bool hosek, bool ibl, bool env_sampling, bool light_tables, bool stream_secondary, bool merged, bool shade_three, uint32_t forced, bool by_default)
+{
+  const bool eligible = !emitters && (hosek || ibl) && !env_sampling && !light_tables && stream_secondary && !merged && shade_three;
+  if (forced == 0u) return false;
+  if (forced == 1u) return eligible;
+  return eligible && by_default;
+}
+
 }  // namespace fh
