@@ -1280,8 +1280,9 @@ int keep_for_refit(fh_ctx* ctx, uint32_t n, uint32_t nr, float pad, NewTree& t)
 
 void reset_tree_measurements(fh_ctx* ctx)
 {
-  ctx->bu_choice = 0; ctx->bu_toggle = 0; ctx->bu_cost[0] = ctx->bu_cost[1] = ctx->bu_items[0] = ctx->bu_items[1] = 0.0;  // a new tree: where its rays should start is measured again (render.hip)
-  ctx->survival_n = 0;  // ... and how long its paths live is not known yet (context.h: survival)
+  // a new tree: where its rays should start is measured again (render.hip), and how long its paths live is not known yet.  (This also zeroes survival[], which nobody can
+  // see: survival_n gates every read.)  Known gap, ADVICE.md finding 1: a counter snapshot recorded before the rebuild still refills the shares when it arrives afterwards
+  ctx->tree = {};
 }
 
 int bvh_build_device(fh_ctx* ctx)

@@ -188,11 +188,11 @@ int fh_ctx_create(int device, fh_ctx** out)
   if (hipMemcpy(ctx->d_lut_refl, kLutReflection, kLutReflectionBytes, hipMemcpyHostToDevice) != hipSuccess) return bail("table upload failed");
   if (hipMemcpy(ctx->d_lut_sheen, kLutSheen, kLutSheenBytes, hipMemcpyHostToDevice) != hipSuccess) return bail("table upload failed");
   (void)hipMemsetAsync(ctx->d_trace_counters, 0, 32 * sizeof(unsigned long long), ctx->stream);  // (never hipMemset: it is asynchronous and ordered with nothing on a non-blocking stream)
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < fh::kPassSlots - 1; ++k)
     if (ctx->aux_stream[k].create(hipStreamNonBlocking) != hipSuccess) return bail("stream creation failed");
-  for (int k = 0; k < 3; ++k) {
-    if (ctx->h_counters[k].alloc((size_t)fh::kCounterStride * 66) != hipSuccess) return bail("pinned allocation failed");
-    if (ctx->ev_counters[k].create() != hipSuccess || ctx->ev_gen[k].create(hipEventDisableTiming) != hipSuccess || ctx->ev_acc[k].create(hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
+  for (fh_ctx::PassSlot& s : ctx->slot) {
+    if (s.snapshot.h.alloc((size_t)fh::kCounterStride * 66) != hipSuccess) return bail("pinned allocation failed");
+    if (s.snapshot.ev.create() != hipSuccess || s.ev_gen.create(hipEventDisableTiming) != hipSuccess || s.ev_acc.create(hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
   }
   if (ctx->ev_enter.create(hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
   if (const char* e = getenv("FH_PIPELINE")) ctx->n_slots = e[0] == '0' ? 1 : (e[0] == '2' ? 2 : 3);
@@ -257,7 +257,7 @@ int fh_ctx_destroy(fh_ctx* ctx)
   FH_GROUP(ctx, group_destroy(ctx));
   if (!ctx) return FH_E_INVALID;
   (void)hipSetDevice(ctx->device);
-  for (const Stream* st : {std::addressof(ctx->stream), std::addressof(ctx->aux_stream[0]), std::addressof(ctx->aux_stream[1]), std::addressof(ctx->sky_stream)}) (void)hipStreamSynchronize(*st);
+  (void)drain_passes(ctx, true);
   delete ctx;  // (the members release themselves, the streams last: context.h)
   return FH_OK;
 }
@@ -345,7 +345,7 @@ int fh_path_pool_allocated(fh_ctx* ctx, uint64_t* bytes, uint64_t* paths)
   CTX_CHECK(ctx);
   if (!bytes || !paths) return fail(ctx, FH_E_INVALID, "fh_path_pool_allocated: null argument");
   *bytes = 0; *paths = 0;
-  for (int k = 0; k < 3; ++k) { *bytes += ctx->pool_alloc_bytes[k]; *paths += ctx->pool[k].capacity; }
+  for (const fh_ctx::PassSlot& s : ctx->slot) { *bytes += s.alloc_bytes; *paths += s.pool.capacity; }
   return FH_OK;
 }
 
@@ -853,7 +853,7 @@ int fh_kat_ray_start(fh_ctx* ctx, double out[5])
   FH_GROUP_REFUSE(ctx, "fh_kat_ray_start");
   CTX_CHECK(ctx);
   if (!out) return fail(ctx, FH_E_INVALID, "fh_kat_ray_start: null argument");
-  out[0] = (double)ctx->bu_choice; out[1] = ctx->bu_items[0]; out[2] = ctx->bu_items[1]; out[3] = ctx->bu_cost[0]; out[4] = ctx->bu_cost[1];
+  out[0] = (double)ctx->tree.bu_choice; out[1] = ctx->tree.bu_items[0]; out[2] = ctx->tree.bu_items[1]; out[3] = ctx->tree.bu_cost[0]; out[4] = ctx->tree.bu_cost[1];
   return FH_OK;
 }
 int fh_reset_stats(fh_ctx* ctx)

@@ -16,6 +16,8 @@
 
 struct fh_group;  // group.hip
 
+namespace fh { constexpr int kPassSlots = 3; }  // passes of fh_render in flight at most: path pools, pass streams (the main stream and kPassSlots - 1 more), 2 * kPassSlots regions of d_stack_spill
+
 struct fh_ctx {
   // a handle made by fh_ctx_create_group(n > 1) holds nothing but `group` and the lead's device; its members are plain contexts that name it as their `owner`
   fh_group* group = nullptr;
@@ -24,7 +26,7 @@ struct fh_ctx {
   int device = 0;
   // the streams come first: members are destroyed in reverse order, so whatever may be in flight on a stream is released before the stream itself
   fh::Stream stream;   // main stream: everything the caller can observe is ordered on it
-  fh::Stream aux_stream[2];  // passes j % n_slots != 0 of fh_render run here, overlapping the latency-bound ends of the passes before
+  fh::Stream aux_stream[fh::kPassSlots - 1];  // passes j % n_slots != 0 of fh_render run here, overlapping the latency-bound ends of the passes before
   fh::Stream sky_stream;
   std::string err;
   uint32_t flags = 0;
@@ -91,7 +93,7 @@ struct fh_ctx {
   uint32_t info_blocks[2] = {0, 0}, info_entries[2] = {0, 0};  // the same two facts for the uninstrumented closest-hit / secondary kernels as last launched (fh_kernel_info)
   uint32_t lds_configured_bytes = 0;  // dynamic-LDS size the traversal kernels were last configured for (render.hip)
   uint32_t stream_lds_entries = 0, stream_lds_entries_secondary = 0;    // stack levels the closest-hit / secondary streaming kernel keeps in LDS (the rest spills to d_stack_spill)
-  fh::DeviceBuffer<uint2> d_stack_spill;  // [6 launches in flight][entry beyond the LDS part][thread of the launch]
+  fh::DeviceBuffer<uint2> d_stack_spill;  // [2 * kPassSlots launches in flight][entry beyond the LDS part][thread of the launch]
   uint32_t lds_static_max = 0;        // largest static LDS of a kernel that keeps its traversal stack in dynamic LDS (hipFuncGetAttributes; render.hip: configure_traversal_lds)
   bool use_bvh8 = false;
   int builder_choice = 0;  // 0 = not decided for this scene, 1 = radix tree (LBVH), 2 = PLOC; decided at the first build after an upload
@@ -167,14 +169,29 @@ struct fh_ctx {
   int light_candidates = FH_LIGHT_CANDIDATES_DEFAULT;
   fh::DeviceBuffer<fh::LightProxy> d_light_proxy;       // [n_lights]
 
-  // path pools: one per pass in flight (pass j uses slot j % n_slots and the stream of that slot); allocated on first use
-  fh::PoolDev pool[3] = {};
-  fh::DeviceBuffer<unsigned long long> d_resolve_dbg;  // FH_DEBUG_TAIL: escaped sky and light rays, and the queue entries k_sky_resolve saw, of the call being submitted
-  uint8_t* pool_esc[3] = {nullptr, nullptr, nullptr};  // per pool, one byte per ENTRY of the secondary queue: the slots whose shadow ray escaped (render.hip: k_sky_resolve).  Not a PoolDev member: that is a kernel argument of every pass kernel
+  // path pools: one per pass in flight (pass j uses slot j % n_slots and the stream of that slot: pass_stream); allocated on first use
   struct PoolShape { bool dir = false, lights = false; uint32_t classes = 0; };  // what the records of a pool have room for (render.hip: pool_ensure)
-  PoolShape pool_shape[3];
-  std::vector<fh::DeviceBuffer<uint8_t>> pool_allocs[3];
-  unsigned long long pool_alloc_bytes[3] = {0, 0, 0};  // device memory the allocations of each pool hold (fh_path_pool_allocated)
+  struct PassSlot {  // everything a pass in flight owns
+    fh::PoolDev pool{};
+    uint8_t* esc = nullptr;  // one byte per ENTRY of the secondary queue: the slots whose shadow ray escaped (render.hip: k_sky_resolve).  Not a PoolDev member: that is a kernel argument of every pass kernel
+    PoolShape shape;
+    std::vector<fh::DeviceBuffer<uint8_t>> allocs;
+    unsigned long long alloc_bytes = 0;  // device memory the allocations hold (fh_path_pool_allocated)
+    // the per-bounce counters of a finished pass on their way to the host (render.hip: harvest_counters)
+    struct Snapshot {
+      fh::PinnedBuffer<uint32_t> h;
+      fh::Event ev;
+      bool in_flight = false;
+      uint32_t wave_depth = 0, paths = 0;  // wave depth used by the pass the snapshot comes from, and the paths it started
+      int bu = -1;              // ... and, while the scene is being probed, where its first-hit rays started (0: the root, 1: the node of their face; -1: not a probing pass)
+    } snapshot;
+    fh::Event ev_gen, ev_acc;  // the pass's k_generate / k_accumulate has been queued: what the pass after it, on another stream, orders its own after
+    bool gen_valid = false, acc_valid = false;
+    // the one place that empties the pool (the caller has made sure nothing runs out of it): the next pool_ensure starts from scratch
+    void release() { allocs.clear(); alloc_bytes = 0; pool = fh::PoolDev{}; esc = nullptr; shape = PoolShape{}; snapshot.in_flight = false; }
+  };
+  PassSlot slot[fh::kPassSlots];
+  fh::DeviceBuffer<unsigned long long> d_resolve_dbg;  // FH_DEBUG_TAIL: escaped sky and light rays, and the queue entries k_sky_resolve saw, of the call being submitted
   // 32 Mi path slots per pool: 16 samples per pixel per pass at 1080p.  Three pools (one per pass in flight) of 284-436 bytes per path are 27-42 GB when a call brings enough
   // samples to fill them; unless the caller chose the size (fh_set_path_pool), fh_render keeps all pools together within half of the device memory that is free when the first one is made
   uint32_t pool_target_default = 1u << 25, pool_target = 1u << 25;  // (pool_target: the default as capped by the free device memory whenever a pool is (re)allocated, or the caller's size)
@@ -182,26 +199,22 @@ struct fh_ctx {
   uint32_t pool_share = 1;          // contexts of one group on this device: each takes its share of the default cap (group.hip)
   uint32_t tail_depth = 0;          // bounces run as wavefront kernels before k_tail finishes the survivors; 0 = adaptive
   uint32_t auto_wave_depth = 2;     // adaptive choice of the pass submitted last (kept for the debug print)
-  // the adaptive choice is made per pass from the SHARE of a pass's paths still alive at each depth, taken from the newest snapshot of an earlier pass's counters: a share is a
-  // property of the scene and the camera, not of the pass, so a call of another size (one final frame of 4096 spp after a session of 1-spp calls, or the other way round)
-  // picks its depth right from its first pass.  (Up to round 5 the DEPTH picked for the earlier pass was carried over: the first 16-spp passes after small calls handed
-  // millions of paths to the fused tail, 300 ms each on configs[3].)  survival_n = 0: nothing known yet (a new tree: bvh_build.hip); entries deeper than the newest
-  // snapshot's wavefront bounces are an earlier pass's.
-  double survival[66] = {};
-  uint32_t survival_n = 0;
-  fh::PinnedBuffer<uint32_t> h_counters[3];  // pinned snapshots of the per-bounce counters of a finished pass
-  fh::Event ev_counters[3];
-  bool counters_in_flight[3] = {false, false, false};
-  uint32_t counters_wave_depth[3] = {0, 0, 0};  // wave depth used by the pass the snapshot comes from
-  uint32_t counters_paths[3] = {0, 0, 0};       // ... and the paths it started
-  int counters_bu[3] = {-1, -1, -1};            // ... and, while the scene is being probed, where its first-hit rays started (0: the root, 1: the node of their face; -1: not a probing pass)
-  int bu_choice = 0;                            // 0: probing, 1: rays start at the root, 2: first-hit rays start at the node of the face they leave (render.hip; reset by every full BVH build)
-  uint32_t bu_toggle = 0;
-  double bu_cost[2] = {0.0, 0.0}, bu_items[2] = {0.0, 0.0};
+  // what the render path has measured on the current tree; a new tree starts it again (bvh_build.hip: reset_tree_measurements)
+  struct TreeMeasurements {
+    // the adaptive choice is made per pass from the SHARE of a pass's paths still alive at each depth, taken from the newest snapshot of an earlier pass's counters: a share is a
+    // property of the scene and the camera, not of the pass, so a call of another size (one final frame of 4096 spp after a session of 1-spp calls, or the other way round)
+    // picks its depth right from its first pass.  (Up to round 5 the DEPTH picked for the earlier pass was carried over: the first 16-spp passes after small calls handed
+    // millions of paths to the fused tail, 300 ms each on configs[3].)  survival_n = 0: nothing known yet; entries deeper than the newest snapshot's wavefront bounces are
+    // an earlier pass's.
+    double survival[66] = {};
+    uint32_t survival_n = 0;
+    int bu_choice = 0;  // 0: probing, 1: rays start at the root, 2: first-hit rays start at the node of the face they leave (render.hip)
+    uint32_t bu_toggle = 0;
+    double bu_cost[2] = {0.0, 0.0}, bu_items[2] = {0.0, 0.0};
+  } tree;
   unsigned long long pass_seq = 0;           // passes submitted so far
-  fh::Event ev_gen[3], ev_acc[3], ev_enter;
-  bool gen_valid[3] = {false, false, false}, acc_valid[3] = {false, false, false};
-  int n_slots = 3;  // passes in flight (FH_PIPELINE=0: 1, every pass on the main stream; =2: two).  Three against two: +2.3 % on configs[2], +0.3-0.9 % on the others, one more path pool
+  fh::Event ev_enter;
+  int n_slots = fh::kPassSlots;  // passes in flight (FH_PIPELINE=0: 1, every pass on the main stream; =2: two).  Three against two: +2.3 % on configs[2], +0.3-0.9 % on the others, one more path pool
   int last_slot_used = 0;  // slot of the pass submitted last (what the next pass orders itself after)
   std::vector<fh::Event> ev_bounce;  // single-pass calls: (shade done, secondary done) per bounce, for the secondary launch on a second stream (render.hip)
   // FH_FLAG_REFERENCE_FIRSTHIT (render.hip: k_firsthit_scan): per-pixel "a sample of this launch has hit something" + the AOVs of that hit
@@ -366,6 +379,16 @@ uint32_t adaptive_to_boundary(const fh_ctx* ctx);  // render.hip: samples from a
 int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity);   // render.hip
 uint64_t pool_bytes_per_path(const fh_ctx* ctx);            // capi.hip
 void pool_release(fh_ctx* ctx);
+// the stream the passes of a pool slot run on: slot 0's is the main stream
+inline hipStream_t pass_stream(const fh_ctx* ctx, int slot) { return slot ? ctx->aux_stream[slot - 1] : ctx->stream; }
+// waits until no pass is running: the main stream, then every aux stream, then (with_sky) the sky stream if there is one.  The first error
+inline hipError_t drain_passes(fh_ctx* ctx, bool with_sky)
+{
+  hipError_t first = hipStreamSynchronize(ctx->stream);
+  for (int k = 0; k < kPassSlots - 1; ++k) { const hipError_t e = hipStreamSynchronize(ctx->aux_stream[k]); if (first == hipSuccess) first = e; }
+  if (with_sky && ctx->sky_stream) { const hipError_t e = hipStreamSynchronize(ctx->sky_stream); if (first == hipSuccess) first = e; }
+  return first;
+}
 int kernel_info(fh_ctx* ctx, int which, uint32_t out[6]);   // render.hip
 #if defined(FH_CHECK_DIV_RANGES)
 int div_range_violations_read(fh_ctx* ctx, uint64_t* n);  // render.hip: the counter of its kernels (fh_vec.h: div_r), which belongs to the device's code object, not to a context

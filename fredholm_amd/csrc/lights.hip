@@ -156,8 +156,7 @@ int light_sampling_set(fh_ctx* ctx, const fh_light_sampling_params* params)
   if (!params) { ctx->light_sampling = 0; return FH_OK; }
   if (!ctx->light_sampling || ctx->light_uniform_fraction != params->uniform_fraction) {
     // a pass of an earlier call may still be reading the table the next call rebuilds
-    FH_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2; ++k) FH_HIP(hipStreamSynchronize(ctx->aux_stream[k]));
+    FH_HIP(drain_passes(ctx, false));
     ctx->light_stale = true;
   }
   ctx->light_sampling = 1;

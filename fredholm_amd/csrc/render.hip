@@ -2160,17 +2160,8 @@ int kernel_info(fh_ctx* ctx, int which, uint32_t out[6])
 
 void pool_release(fh_ctx* ctx)
 {
-  (void)hipStreamSynchronize(ctx->stream);  // nothing may still be running out of the buffers (the counter snapshots trail the accumulate)
-  for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(ctx->aux_stream[k]);
-  if (ctx->sky_stream) (void)hipStreamSynchronize(ctx->sky_stream);
-  for (int k = 0; k < 3; ++k) {
-    ctx->pool_allocs[k].clear();
-    ctx->pool_alloc_bytes[k] = 0;
-    ctx->pool[k] = PoolDev{};
-    ctx->pool_esc[k] = nullptr;
-    ctx->pool_shape[k] = fh_ctx::PoolShape{};
-    ctx->counters_in_flight[k] = false;
-  }
+  (void)drain_passes(ctx, true);  // nothing may still be running out of the buffers (the counter snapshots trail the accumulate)
+  for (fh_ctx::PassSlot& s : ctx->slot) s.release();
 }
 
 int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
@@ -2181,28 +2172,24 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
   need.dir = ctx->has_dir;
   need.lights = ctx->n_lights > 0;
   need.classes = ctx->n_classes < 1u ? 1u : ctx->n_classes;
-  fh_ctx::PoolShape& have = ctx->pool_shape[slot];
-  if (ctx->pool[slot].capacity >= capacity && (have.dir || !need.dir) && (have.lights || !need.lights) && have.classes >= need.classes) return FH_OK;
-  if (ctx->pool[slot].capacity) {  // growing: nothing may still be running out of the old buffers
-    FH_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2; ++k) FH_HIP(hipStreamSynchronize(ctx->aux_stream[k]));
-    ctx->pool_allocs[slot].clear();
-    ctx->pool_alloc_bytes[slot] = 0;
-    if (ctx->pool_target_by_caller && ctx->pool[slot].capacity > capacity) capacity = ctx->pool[slot].capacity;  // (a default-sized pool is re-made at the size the memory cap of this call allows)
+  fh_ctx::PassSlot& S = ctx->slot[slot];
+  const fh_ctx::PoolShape& have = S.shape;
+  if (S.pool.capacity >= capacity && (have.dir || !need.dir) && (have.lights || !need.lights) && have.classes >= need.classes) return FH_OK;
+  if (S.pool.capacity) {  // growing: nothing may still be running out of the old buffers
+    FH_HIP(drain_passes(ctx, false));
+    if (ctx->pool_target_by_caller && S.pool.capacity > capacity) capacity = S.pool.capacity;  // (a default-sized pool is re-made at the size the memory cap of this call allows)
     need.dir = need.dir || have.dir; need.lights = need.lights || have.lights; need.classes = need.classes > have.classes ? need.classes : have.classes;
-    ctx->pool[slot] = PoolDev{};
-    ctx->pool_esc[slot] = nullptr;
-    have = fh_ctx::PoolShape{};
-    ctx->counters_in_flight[slot] = false;
+    S.release();
   }
-  PoolDev& P = ctx->pool[slot];
+  PoolDev& P = S.pool;
+  const hipStream_t st = pass_stream(ctx, slot);
   auto alloc = [&](auto*& ptr, size_t count) -> hipError_t {
     DeviceBuffer<uint8_t> buf;
     hipError_t e = buf.alloc(count * sizeof(*ptr));
     void* const raw = buf.get();
-    if (e == hipSuccess) { ctx->pool_allocs[slot].push_back(std::move(buf)); ctx->pool_alloc_bytes[slot] += count * sizeof(*ptr); ptr = (decltype(ptr))raw; }
+    if (e == hipSuccess) { S.allocs.push_back(std::move(buf)); S.alloc_bytes += count * sizeof(*ptr); ptr = (decltype(ptr))raw; }
     // FH_POISON=1 (tests): a new pool starts out full of 0xa5 instead of whatever the allocation held, so a kernel that reads a record or a queue entry nobody wrote shows at once
-    if (e == hipSuccess && ctx->tun.poison_pools) e = hipMemsetAsync(raw, 0xa5, count * sizeof(*ptr), slot ? ctx->aux_stream[slot - 1] : ctx->stream);
+    if (e == hipSuccess && ctx->tun.poison_pools) e = hipMemsetAsync(raw, 0xa5, count * sizeof(*ptr), st);
     return e;
   };
   const size_t n = capacity;
@@ -2226,23 +2213,20 @@ int pool_ensure(fh_ctx* ctx, int slot, uint32_t capacity)
     FH_POOL(P.counters, (size_t)kCounterStride * 66);  // up to 65 bounces per pass
     FH_POOL(P.key_sec, n); FH_POOL(P.key_rad, n); FH_POOL(P.q_tmp, n); FH_POOL(P.q_sec_sorted, n);
     FH_POOL(P.bins, (size_t)2 * kCells);
-    FH_POOL(ctx->pool_esc[slot], n);  // (every entry a deferred secondary launch takes is written by it before k_sky_resolve reads it: no fill)
+    FH_POOL(S.esc, n);  // (every entry a deferred secondary launch takes is written by it before k_sky_resolve reads it: no fill)
 #undef FH_POOL
     // (on the stream this slot's passes run on, where the sorts that use the bins follow it: hipMemset on the null stream returns before the fill has run and is ordered
     // with NOTHING on a non-blocking stream -- a pass whose first sort overtook the fill counted into whatever the allocation held, turned that into scatter cursors and wrote
     // queue entries gigabytes away: the memory fault of profiles/README.md r4-10)
-    return hipMemsetAsync(P.bins, 0, sizeof(uint32_t) * 2 * kCells, slot ? ctx->aux_stream[slot - 1] : ctx->stream);
+    return hipMemsetAsync(P.bins, 0, sizeof(uint32_t) * 2 * kCells, st);
   };
   const hipError_t e = all();
   if (e != hipSuccess) {  // leave the slot empty rather than half allocated: the next call starts from scratch
-    ctx->pool_allocs[slot].clear();
-    ctx->pool_alloc_bytes[slot] = 0;
-    P = PoolDev{};
-    ctx->pool_esc[slot] = nullptr;
+    S.release();
     return fail(ctx, FH_E_HIP, std::string("path pool allocation: ") + hipGetErrorString(e));
   }
   P.capacity = capacity;
-  have = need;
+  S.shape = need;
   return FH_OK;
 }
 
@@ -2336,9 +2320,7 @@ static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
     for (int k = 0; k < 4; ++k) FH_HIP(ctx->d_split[k].alloc(ctx->n_owned));
   }
   // no launch of an earlier call may still read the lists that are rewritten here
-  FH_HIP(hipStreamSynchronize(ctx->stream));
-  for (int k = 0; k < 2; ++k) FH_HIP(hipStreamSynchronize(ctx->aux_stream[k]));
-  FH_HIP(hipStreamSynchronize(ctx->sky_stream));
+  FH_HIP(drain_passes(ctx, true));
   SplitDev sp{};
   const float c[3] = {0.5f * (ctx->scene_lo[0] + ctx->scene_hi[0]), 0.5f * (ctx->scene_lo[1] + ctx->scene_hi[1]), 0.5f * (ctx->scene_lo[2] + ctx->scene_hi[2])};
   const float w[3] = {c[0] - t[3], c[1] - t[7], c[2] - t[11]};
@@ -2475,9 +2457,9 @@ void cap_pool_target(fh_ctx* ctx)
   bool allocating = false;
   unsigned long long held = 0;
   for (int k = 0; k < (((ctx->flags & FH_FLAG_SERIAL_PASSES) != 0) ? 1 : ctx->n_slots); ++k) {
-    const fh_ctx::PoolShape& have = ctx->pool_shape[k];
-    if (ctx->pool[k].capacity == 0 || (ctx->has_dir && !have.dir) || (ctx->n_lights > 0 && !have.lights) || have.classes < (ctx->n_classes < 1u ? 1u : ctx->n_classes)) allocating = true;
-    held += (unsigned long long)ctx->pool[k].capacity * pool_bytes_per_path(ctx);
+    const fh_ctx::PoolShape& have = ctx->slot[k].shape;
+    if (ctx->slot[k].pool.capacity == 0 || (ctx->has_dir && !have.dir) || (ctx->n_lights > 0 && !have.lights) || have.classes < (ctx->n_classes < 1u ? 1u : ctx->n_classes)) allocating = true;
+    held += (unsigned long long)ctx->slot[k].pool.capacity * pool_bytes_per_path(ctx);
   }
   if (!allocating) return;
   size_t free_b = 0, total_b = 0;
@@ -2694,9 +2676,9 @@ int stream_plan(fh_ctx* ctx, const SceneDev& sc, bool count, bool filler, Stream
   // spill area of the streaming launches: [launch in flight: pass slot x (closest, secondary)][entry beyond the LDS part][thread of the launch]
   const size_t spill_threads = (size_t)(p.grid[0] > p.grid[1] ? p.grid[0] : p.grid[1]) * kBlock;
   p.spill_region = (size_t)(p.spill_entries[0] > p.spill_entries[1] ? p.spill_entries[0] : p.spill_entries[1]) * spill_threads;  // uint2 each
-  if (p.spill_region * 6u > ctx->d_stack_spill.size()) {
+  if (p.spill_region * (2u * kPassSlots) > ctx->d_stack_spill.size()) {
     FH_HIP(hipDeviceSynchronize());  // (launches of earlier calls may still use the old area)
-    FH_HIP(ctx->d_stack_spill.alloc(p.spill_region * 6u));
+    FH_HIP(ctx->d_stack_spill.alloc(p.spill_region * (2u * kPassSlots)));
   }
   const uint32_t chunk_max = stream_chunk_max(tun.stream_chunk_fixed, tun.stream_chunk, ctx->bvh8_n_nodes);
   p.chunk[1] = stream_chunk_word(tun.stream_chunk, chunk_max);
@@ -2742,30 +2724,25 @@ struct Pass {
 // being probed, what the secondary launches cost (no host/device synchronisation: a snapshot is looked at when its event has passed)
 void harvest_counters(fh_ctx* ctx)
 {
-  for (int k = 0; k < 3; ++k) {
-    if (!(ctx->counters_in_flight[k] && hipEventQuery(ctx->ev_counters[k]) == hipSuccess)) continue;
-    ctx->counters_in_flight[k] = false;
-    const uint32_t wd = ctx->counters_wave_depth[k];
-    const uint32_t* hc = ctx->h_counters[k];
-    if (ctx->counters_paths[k]) {  // the share of the pass's paths alive at each depth it ran as a wavefront (context.h: survival)
-      const uint32_t n = wd < 65u ? wd : 65u;
-      for (uint32_t d = 0; d <= n; ++d) ctx->survival[d] = (double)hc[d * kCounterStride + CNT_RAD] / (double)ctx->counters_paths[k];
-      if (ctx->survival_n < n + 1u) ctx->survival_n = n + 1u;  // (a pass the tail took over early says nothing about the deeper shares: what an earlier pass of this scene measured stays)
-    }
-    if (ctx->counters_bu[k] >= 0 && ctx->bu_choice == 0) {  // (a pass of the scene's probing phase: what its secondary launches cost, by the issue model's weights)
-      double cost = 0.0, items = 0.0;
-      for (uint32_t d = 0; d < wd; ++d) { cost += 510.0 * hc[d * kCounterStride + CNT_COST_NODE] + 175.0 * hc[d * kCounterStride + CNT_COST_TRI]; items += hc[d * kCounterStride + CNT_SEC]; }
-      ctx->bu_cost[ctx->counters_bu[k]] += cost; ctx->bu_items[ctx->counters_bu[k]] += items;
-      const int verdict = bottom_up_verdict(ctx->bu_cost, ctx->bu_items);
+  fh_ctx::TreeMeasurements& t = ctx->tree;
+  for (int k = 0; k < kPassSlots; ++k) {
+    fh_ctx::PassSlot::Snapshot& s = ctx->slot[k].snapshot;
+    if (!(s.in_flight && hipEventQuery(s.ev) == hipSuccess)) continue;
+    s.in_flight = false;
+    const uint32_t* hc = s.h;
+    t.survival_n = fold_survival(hc, kCounterStride, CNT_RAD, s.wave_depth, s.paths, t.survival, t.survival_n);  // the share of the pass's paths alive at each depth it ran as a wavefront (context.h: survival)
+    if (s.bu >= 0 && t.bu_choice == 0) {  // (a pass of the scene's probing phase: what its secondary launches cost)
+      fold_probe_cost(hc, kCounterStride, CNT_COST_NODE, CNT_COST_TRI, CNT_SEC, s.wave_depth, &t.bu_cost[s.bu], &t.bu_items[s.bu]);
+      const int verdict = bottom_up_verdict(t.bu_cost, t.bu_items);
       if (verdict) {
-        ctx->bu_choice = verdict;
+        t.bu_choice = verdict;
         if (getenv("FH_DEBUG_BVH"))
-          fprintf(stderr, "[trace] rays that leave a surface start at %s: %.0f against %.0f SIMD cycles of tests per shaded path (from the root / from the face)\n", ctx->bu_choice == 2 ? "the node of their face" : "the root",
-                  ctx->bu_cost[0] / ctx->bu_items[0], ctx->bu_cost[1] / ctx->bu_items[1]);
+          fprintf(stderr, "[trace] rays that leave a surface start at %s: %.0f against %.0f SIMD cycles of tests per shaded path (from the root / from the face)\n", t.bu_choice == 2 ? "the node of their face" : "the root",
+                  t.bu_cost[0] / t.bu_items[0], t.bu_cost[1] / t.bu_items[1]);
       }
     }
-    ctx->counters_bu[k] = -1;
-    if (ctx->tun.debug_tail) { fprintf(stderr, "[tail] slot %d wd %u paths %u survivors:", k, wd, ctx->counters_paths[k]); for (uint32_t d = 0; d <= wd; ++d) fprintf(stderr, " %u", ctx->h_counters[k][d * kCounterStride + CNT_RAD]); fprintf(stderr, "\n"); }
+    s.bu = -1;
+    if (ctx->tun.debug_tail) { fprintf(stderr, "[tail] slot %d wd %u paths %u survivors:", k, s.wave_depth, s.paths); for (uint32_t d = 0; d <= s.wave_depth; ++d) fprintf(stderr, " %u", hc[d * kCounterStride + CNT_RAD]); fprintf(stderr, "\n"); }
   }
 }
 
@@ -2780,11 +2757,11 @@ bool start_at_faces(const Call& c, bool merge, int& probe)
   if (ctx->tun.bottom_up != 2u) return false;
   // (only a pass whose secondary launch can climb is a probe: the merged launch of a one-pass call walks from the root whatever the pass says and counts no test
   // rounds, so counting it would fill one side of the comparison with cost 0 and fix the choice at "root" -- the reference's 1- and 16-sample calls come first in a GUI)
-  if (ctx->bu_choice == 0 && !c.count && !merge && !c.sc.has_alpha) {
-    probe = (ctx->bu_toggle++ & 1u) != 0u ? 1 : 0;
+  if (ctx->tree.bu_choice == 0 && !c.count && !merge && !c.sc.has_alpha) {
+    probe = (ctx->tree.bu_toggle++ & 1u) != 0u ? 1 : 0;
     return probe == 1;
   }
-  return ctx->bu_choice == 2;
+  return ctx->tree.bu_choice == 2;
 }
 
 StackSpill stack_spill(const Call& c, const Pass& p, int k, uint32_t probe_flag)
@@ -2830,7 +2807,7 @@ void launch_secondary(const Call& c, const Pass& p, const PoolDev& ps, uint32_t 
   const StreamPlan& pl = c.plan;
   const SceneDev& sc = p.sc;
   if (p.defer) {  // (sky_defer_verdict: no emitters, the streaming kernel) -- the form that leaves escape masks, and right behind it, on the same stream, what they add
-    uint8_t* const esc = ctx->pool_esc[p.slot];
+    uint8_t* const esc = ctx->slot[p.slot].esc;
     {
       Span sp(ctx, p.sb, 1);
       with_bool(c.count, [&](auto C) { with_bool(sc.has_alpha != 0, [&](auto A) {
@@ -2940,7 +2917,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
   ctx->pass_seq++;
   ctx->stats.n_passes++;
   ctx->last_slot_used = slot;
-  const hipStream_t st = p.st = slot ? ctx->aux_stream[slot - 1] : ctx->stream;
+  const hipStream_t st = p.st = pass_stream(ctx, slot);
   last_slot = slot;
   // A call that is ONE pass (the reference's callers: 1 or 16 samples per call) has no other pass to share the GPU with, and its bounces are chains of launches that
   // each end in a few long rays.  The secondary rays of bounce b and the closest-hit launch of bounce b + 1 do not depend on each other -- the secondary launch reads the
@@ -2963,19 +2940,20 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
   // (The shade side of every bounce -- routing, shade kernels, queue sorts -- on a stream of its own, optionally of high priority, with the pass streams kept off some CUs,
   // was measured in round 4 and is slower: r4-6, tools/patches/r6_pruned_switches.patch.)
   { const int rc = pool_ensure(ctx, slot, n_px * batch); if (rc) return rc; }
-  const PoolDev& pool = ctx->pool[slot];
+  fh_ctx::PassSlot& S = ctx->slot[slot];
+  const PoolDev& pool = S.pool;
   FH_HIP(hipMemsetAsync(pool.counters, 0, sizeof(uint32_t) * kCounterStride * (max_depth + 1), st));
   p.sc = c.sc;
   if (!start_at_faces(c, p.merge, p.probe)) { p.sc.bvh8.parent = nullptr; p.sc.face_node = nullptr; }
-  if (prev != slot && ctx->gen_valid[prev]) FH_HIP(hipStreamWaitEvent(st, ctx->ev_gen[prev], 0));
+  if (prev != slot && ctx->slot[prev].gen_valid) FH_HIP(hipStreamWaitEvent(st, ctx->slot[prev].ev_gen, 0));
   {
     Span sp(ctx, st, 4);
     hipLaunchKernelGGL(k_generate, dim3(grid_for((n_px + kGenChunks - 1) / kGenChunks), nb), dim3(kBlock), 0, st, c.fr, pool, ctx->d_sample_issued, px.px, px.xy, n_px);
     hipLaunchKernelGGL(k_bump_issued, dim3((n_px + kBlock - 1) / kBlock), dim3(kBlock), 0, st, ctx->d_sample_issued, px.px, n_px, nb);
     ctx->stats.n_generate_launches++;
   }
-  FH_HIP(hipEventRecord(ctx->ev_gen[slot], st));
-  ctx->gen_valid[slot] = true;
+  FH_HIP(hipEventRecord(S.ev_gen, st));
+  S.gen_valid = true;
   ctx->stats.paths += n_paths;
   // bounces run as bounce-synchronous wavefront kernels; the survivors are finished by k_tail.  Adaptive mode picks the
   // first depth at which an earlier pass had at most tail_paths survivors (counts come from an asynchronous snapshot of
@@ -2986,7 +2964,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
   // against their six, and more paths in it cost 0-1 %)
   const uint32_t tail_paths = tun.tail_paths ? tun.tail_paths : (n_paths <= (1u << 22) ? 262144u : 65536u);
   harvest_counters(ctx);
-  p.wave_depth = tail_wave_depth(ctx->survival, ctx->survival_n, n_paths, tail_paths, max_depth, ctx->tail_depth, tun.tail_depth, &ctx->auto_wave_depth);
+  p.wave_depth = tail_wave_depth(ctx->tree.survival, ctx->tree.survival_n, n_paths, tail_paths, max_depth, ctx->tail_depth, tun.tail_depth, &ctx->auto_wave_depth);
   PoolDev pd = pool, ps = pool;  // per-bounce views: pd rotates the radiance queues through the sorted buffers, ps reads the sorted secondary queue
   uint32_t* q_spare = pool.q_tmp;
   const uint32_t sort_blocks = n_paths / 16384u < 1u ? 1u : (n_paths / 16384u > 512u ? 512u : n_paths / 16384u);
@@ -3014,7 +2992,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
   }
   if (p.overlap && p.wave_depth > 0) FH_HIP(hipStreamWaitEvent(st, ctx->ev_bounce[2u * (p.wave_depth - 1u) + 1u], 0));  // the tail and the accumulate read the radiance the last secondary launch completes
   if (p.wave_depth < max_depth) launch_tail(c, p, pd, n_paths);
-  if (prev != slot && ctx->acc_valid[prev]) FH_HIP(hipStreamWaitEvent(st, ctx->ev_acc[prev], 0));
+  if (prev != slot && ctx->slot[prev].acc_valid) FH_HIP(hipStreamWaitEvent(st, ctx->slot[prev].ev_acc, 0));
   {
     Span sp(ctx, st, 5);
     if (c.quirk) hipLaunchKernelGGL((k_accumulate<true>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, c.L, px.px, n_px, nb, ctx->d_quirk_aov);
@@ -3022,15 +3000,16 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
     else hipLaunchKernelGGL((k_accumulate<false>), dim3(grid_for(n_px)), dim3(kBlock), 0, st, pool, c.L, px.px, n_px, nb, (float4*)nullptr);
     ctx->stats.n_accumulate_launches++;
   }
-  FH_HIP(hipEventRecord(ctx->ev_acc[slot], st));
-  ctx->acc_valid[slot] = true;
-  if (!ctx->counters_in_flight[slot] && ctx->h_counters[slot]) {
-    FH_HIP(hipMemcpyAsync(ctx->h_counters[slot], pool.counters, sizeof(uint32_t) * kCounterStride * (max_depth + 1), hipMemcpyDeviceToHost, st));
-    FH_HIP(hipEventRecord(ctx->ev_counters[slot], st));
-    ctx->counters_in_flight[slot] = true;
-    ctx->counters_wave_depth[slot] = p.wave_depth;
-    ctx->counters_paths[slot] = n_paths;
-    ctx->counters_bu[slot] = p.probe;
+  FH_HIP(hipEventRecord(S.ev_acc, st));
+  S.acc_valid = true;
+  fh_ctx::PassSlot::Snapshot& snap = S.snapshot;
+  if (!snap.in_flight && snap.h) {
+    FH_HIP(hipMemcpyAsync(snap.h, pool.counters, sizeof(uint32_t) * kCounterStride * (max_depth + 1), hipMemcpyDeviceToHost, st));
+    FH_HIP(hipEventRecord(snap.ev, st));
+    snap.in_flight = true;
+    snap.wave_depth = p.wave_depth;
+    snap.paths = n_paths;
+    snap.bu = p.probe;
   }
   return FH_OK;
 }
@@ -3040,7 +3019,7 @@ int submit_pass(Call& c, const PixelLists& px, uint32_t nb, uint32_t batch, uint
 int select_round(const Call& c, SkyLaunches& sky, const PixelLists& base, bool guard_blocks, int wait_slot, uint32_t n_round, PixelLists& act, bool& sky_ran)
 {
   fh_ctx* const ctx = c.ctx;
-  if (wait_slot != 0) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[wait_slot], 0));
+  if (wait_slot != 0) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->slot[wait_slot].ev_acc, 0));
   if (guard_blocks) sky.end();  // (the round's own sky launch: the next selection reads what it writes)
   if (sky_ran && sky.st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky.st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
   act.n_sky = 0;
@@ -3143,7 +3122,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
   }
   // join: later work on the main stream (pack, post-process, copies, the caller's clears) sees every pass of this call
   // (the accumulates form a chain across the streams, so the last one implies all the others)
-  if (last_slot != 0 && ran) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_acc[last_slot], 0));
+  if (last_slot != 0 && ran) FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->slot[last_slot].ev_acc, 0));
   sky.end();
   if (base.n_sky && sky.st != ctx->stream) { FH_HIP(hipEventRecord(ctx->ev_sky, sky.st)); FH_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_sky, 0)); }
   FH_HIP(hipGetLastError());

@@ -113,6 +113,26 @@ inline uint32_t tail_wave_depth(const double* survival, uint32_t survival_n, uin
   return wave_depth;
 }
 
+// A counter snapshot of a finished pass (`stride` words per bounce, word `rad_index` of each: the entries of the radiance queue the bounce consumed) folded into the
+// shares alive per depth: entries 0 .. min(wave_depth, 65) are overwritten, and a shallower snapshot does not shorten what is known (a pass the tail took over early
+// says nothing about the deeper shares: what an earlier pass of this scene measured stays).  Returns the new survival_n; a snapshot of no paths changes nothing.
+inline uint32_t fold_survival(const uint32_t* counters, uint32_t stride, uint32_t rad_index, uint32_t wave_depth, uint32_t paths, double* survival, uint32_t survival_n)
+{
+  if (!paths) return survival_n;
+  const uint32_t n = wave_depth < 65u ? wave_depth : 65u;
+  for (uint32_t d = 0; d <= n; ++d) survival[d] = (double)counters[d * stride + rad_index] / (double)paths;
+  return survival_n < n + 1u ? n + 1u : survival_n;
+}
+
+// What the secondary launches of a probing pass cost, added to *cost, and the shaded paths they served, added to *items, over the pass's wavefront bounces
+inline void fold_probe_cost(const uint32_t* counters, uint32_t stride, uint32_t node_index, uint32_t tri_index, uint32_t sec_index, uint32_t wave_depth, double* cost, double* items)
+{
+  constexpr double kNodeRoundCycles = 510.0, kTriRoundCycles = 175.0;  // SIMD cycles of a wave-level node-test / triangle-test round: the issue model's weights
+  double c = 0.0, n = 0.0;
+  for (uint32_t d = 0; d < wave_depth; ++d) { c += kNodeRoundCycles * counters[d * stride + node_index] + kTriRoundCycles * counters[d * stride + tri_index]; n += counters[d * stride + sec_index]; }
+  *cost += c; *items += n;
+}
+
 // Where the first-hit rays of a scene start, from what the probing passes cost (SIMD cycles of tests, by the issue model's weights) per shaded path:
 // 0: keep probing (under 65536 items on either side), 1: at the root, 2: at the node of the face they leave -- only where that is at least 5 % cheaper
 inline int bottom_up_verdict(const double cost[2], const double items[2])

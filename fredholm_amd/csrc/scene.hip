@@ -244,8 +244,7 @@ int fh_set_transforms(fh_ctx* ctx, uint32_t n, const float* o2w, const float* w2
   if (ctx->h_o2w.size() == 12ull * n && ctx->h_w2o.size() == 12ull * n && std::memcmp(ctx->h_o2w.data(), o2w, 48ull * n) == 0 &&
       std::memcmp(ctx->h_w2o.data(), w2o, 48ull * n) == 0)
     return FH_OK;
-  (void)hipStreamSynchronize(ctx->stream);
-  for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(ctx->aux_stream[k]);  // no pass may still be reading the face records
+  (void)drain_passes(ctx, false);  // no pass may still be reading the face records
   uint32_t max_inst = 0;
   for (uint32_t i : ctx->h_instance_ids) max_inst = i > max_inst ? i : max_inst;
   if (max_inst >= n) return fail(ctx, FH_E_INVALID, "fh_set_transforms: fewer transforms than the scene has instances");

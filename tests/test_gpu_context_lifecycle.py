@@ -129,6 +129,90 @@ def test_a_group_of_two_on_one_device_gives_back_all_it_took():
     assert live() == before
 
 
+def test_pools_that_grow_render_the_bits_of_pools_that_never_had_to(monkeypatch):
+    """render.hip: pool_ensure.  A pool slot is re-made when a pass needs more paths than it holds or a kind of record it has no room for.  One context, its new pools
+    full of 0xa5 (FH_POISON=1), meets every reason in turn -- more paths, the directional light's slot, the light record of a scene with emitters over one without --
+    and renders the bits of a context whose pools had the largest shape and size before its first frame.  Pass j of a context runs in slot j % 3, so every step is
+    three one-pass calls: each slot meets each reason.  fh_path_pool_allocated grows with every step, and fh_set_path_pool gives everything back."""
+    w, h, depth = 64, 48, 4
+    cam = F.Camera(**scenes.CORNELL_CAMERA)
+    sky = (0.5, 0.6, 0.8)  # (the dark box is lit through its open front)
+    lit = scenes.cornell_box()
+    dark = dict(scenes.cornell_box())
+    dark["materials"] = dark["materials"].copy()
+    dark["materials"]["emission"][:] = 0.0
+    dark["materials"]["emission_color"][:] = 0.0
+
+    def steps(r, L):
+        frames, held = [], []
+
+        def calls(n_samples):
+            for _ in range(3):
+                r.render(cam, sky, L, n_samples, depth)
+                r.wait_for_completion()
+                frames.append({n: L.download(n).view(np.uint32) for n in F.RenderLayer.NAMES})
+            held.append(r.path_pool_allocated())
+
+        calls(1)
+        calls(6)  # more paths
+        r.set_directional_light((3.0, 3.0, 3.0), (0.2, 1.0, 0.9), 0.0)
+        calls(6)  # the directional light's shadow ray
+        r.load_scene(lit)
+        r.build_ias()
+        assert r.n_lights() == 2
+        calls(6)  # the pending light-ray record
+        return frames, held
+
+    before = live()
+    monkeypatch.setenv("FH_POISON", "1")
+    r = F.Renderer(0)
+    try:
+        r.load_scene(dark)
+        r.build_ias()
+        assert r.n_lights() == 0
+        r.set_resolution(w, h)
+        L = F.RenderLayer(r, w, h)
+        grown, held = steps(r, L)
+        r.set_path_pool(4096)
+        released = r.path_pool_allocated()
+        L.free()
+    finally:
+        r.close()
+    assert live() == before
+    monkeypatch.delenv("FH_POISON")
+    r = F.Renderer(0)
+    try:
+        r.load_scene(lit)
+        r.build_ias()
+        r.set_directional_light((3.0, 3.0, 3.0), (0.2, 1.0, 0.9), 0.0)
+        r.set_resolution(w, h)
+        L = F.RenderLayer(r, w, h)
+        for _ in range(3):  # every slot: six samples of the largest shape
+            r.render(cam, sky, L, 6, depth)
+        r.wait_for_completion()
+        roomy = r.path_pool_allocated()
+        r.clear_directional_light()
+        r.load_scene(dark)
+        r.build_ias()
+        r.init_render_states()
+        L.clear()
+        fitted, held_fitted = steps(r, L)
+        L.free()
+    finally:
+        r.close()
+    assert live() == before
+    n_px = w * h
+    assert [p for _, p in held] == [3 * n_px, 18 * n_px, 18 * n_px, 18 * n_px]
+    assert all(a[0] < b[0] for a, b in zip(held, held[1:])), held
+    assert released == (0, 0)
+    assert held[-1] == roomy and held_fitted == [roomy] * 4  # (the second context never re-made a pool)
+    assert len(grown) == len(fitted) == 12
+    assert all(f["beauty"].view(np.float32)[..., :3].mean() > 0.01 for f in grown)  # (pictures, not cleared buffers)
+    for k, (a, b) in enumerate(zip(grown, fitted)):
+        for name in F.RenderLayer.NAMES:
+            assert np.array_equal(a[name], b[name]), (k, name)
+
+
 def _six_layers(r, cam, w, h):
     L = F.RenderLayer(r, w, h)
     r.render(cam, BG, L, 2, 4)

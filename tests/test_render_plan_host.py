@@ -20,7 +20,8 @@ def test_render_plan_check_program_passes(tmp_path):
     # the program replayed every row of the table, and the table has rows for every function of the header
     rows = json.load(open(cases))
     assert "(%d cases)" % len(rows) in run.stdout, run.stdout
-    assert {r["fn"] for r in rows} == {"pool_target_cap", "samples_per_pass", "stream_lds_entries", "stream_wgs", "stream_chunk", "tail_wave_depth", "bottom_up_verdict", "lens_values"}
+    assert {r["fn"] for r in rows} == {"pool_target_cap", "samples_per_pass", "stream_lds_entries", "stream_wgs", "stream_chunk", "tail_wave_depth", "fold_survival", "fold_probe_cost",
+                                      "bottom_up_verdict", "lens_values"}
     # a table it cannot read, or one whose expected value is off by one bit, fails
     assert subprocess.run([str(exe), str(tmp_path / "missing.json")], capture_output=True, text=True).returncode != 0
     k = next(i for i, r in enumerate(rows) if r["fn"] == "lens_values")

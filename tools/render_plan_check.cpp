@@ -19,6 +19,7 @@ static int failures = 0;
 typedef unsigned long long u64;
 static double as_double(u64 bits) { double d; std::memcpy(&d, &bits, 8); return d; }
 static float as_float(u64 bits) { const uint32_t u = (uint32_t)bits; float f; std::memcpy(&f, &u, 4); return f; }
+static u64 double_bits(double d) { u64 b; std::memcpy(&b, &d, 8); return b; }
 static u64 float_bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
 static uint32_t passes_of(uint32_t n_samples, uint32_t batch) { return (n_samples + batch - 1u) / batch; }
@@ -67,6 +68,43 @@ static void hand_derived()
   EXPECT(fh::bottom_up_verdict(c_on, it) == 2);
   EXPECT(fh::bottom_up_verdict(c_edge, it) == 1);
   EXPECT(fh::bottom_up_verdict(c_off, it) == 1);
+  // the shares alive per depth, from counter snapshots of 16 words per bounce whose word 0 is the bounce's radiance-queue entries: a snapshot of wave depth 7 fills
+  // entries 0 .. 7; one of wave depth 2 after it overwrites entries 0 .. 2 only and does not shorten what is known
+  {
+    std::vector<uint32_t> deep(8 * 16, 0u), shallow(3 * 16, 0u), none(6 * 16, 77u), full(66 * 16, 0u);
+    for (uint32_t d = 0; d < 8u; ++d) deep[d * 16u] = 1024u >> d;
+    for (uint32_t d = 0; d < 3u; ++d) shallow[d * 16u] = 300u - 100u * d;
+    double sv[66] = {};
+    uint32_t n = fh::fold_survival(deep.data(), 16u, 0u, 7u, 1024u, sv, 0u);
+    EXPECT(n == 8u);
+    for (uint32_t d = 0; d < 8u; ++d) EXPECT(sv[d] == 1.0 / (double)(1u << d));
+    EXPECT(sv[8] == 0.0);
+    n = fh::fold_survival(shallow.data(), 16u, 0u, 2u, 400u, sv, n);
+    EXPECT(n == 8u && sv[0] == 0.75 && sv[1] == 0.5 && sv[2] == 0.25);
+    for (uint32_t d = 3; d < 8u; ++d) EXPECT(sv[d] == 1.0 / (double)(1u << d));
+    // a snapshot of a pass that started no paths changes nothing
+    double before[66];
+    std::memcpy(before, sv, sizeof sv);
+    EXPECT(fh::fold_survival(none.data(), 16u, 0u, 5u, 0u, sv, n) == 8u && std::memcmp(before, sv, sizeof sv) == 0);
+    // a wave depth above 65 is capped: 66 entries, the table's size (the snapshot buffer holds 66 bounces)
+    for (uint32_t d = 0; d < 66u; ++d) full[d * 16u] = 66u - d;
+    double capped[66] = {};
+    EXPECT(fh::fold_survival(full.data(), 16u, 0u, 1000u, 66u, capped, 0u) == 66u && capped[0] == 1.0 && capped[65] == 1.0 / 66.0);
+    EXPECT(fh::fold_survival(full.data(), 16u, 0u, 65u, 66u, capped, 3u) == 66u && fh::fold_survival(full.data(), 16u, 0u, 64u, 66u, capped, 3u) == 65u);
+  }
+  // the probe cost of a two-bounce table: 510 cycles per node-test round (word 12), 175 per triangle-test round (word 13), per shaded path with secondary rays (word 1);
+  // added to what the side has already, and a third bounce in the buffer that the pass did not run as a wavefront is not counted
+  {
+    std::vector<uint32_t> t(3 * 16, 0u);
+    t[12] = 10u; t[13] = 4u; t[1] = 100u;
+    t[16 + 12] = 3u; t[16 + 13] = 2u; t[16 + 1] = 50u;
+    t[32 + 12] = 999u; t[32 + 13] = 999u; t[32 + 1] = 999u;
+    double cost = 1000.0, items = 7.0;
+    fh::fold_probe_cost(t.data(), 16u, 12u, 13u, 1u, 2u, &cost, &items);
+    EXPECT(cost == 1000.0 + (510.0 * 10.0 + 175.0 * 4.0) + (510.0 * 3.0 + 175.0 * 2.0) && cost == 8680.0 && items == 157.0);
+    fh::fold_probe_cost(t.data(), 16u, 12u, 13u, 1u, 0u, &cost, &items);  // (no wavefront bounce: nothing)
+    EXPECT(cost == 8680.0 && items == 157.0);
+  }
   // the pools together stay within a quarter of the free memory; never under one path per owned pixel; the default where it fits
   EXPECT(fh::pool_target_cap(12ull << 30, 0ull, 1u, 3, 256ull, 1u << 25, 3072u) == (1u << 22));
   EXPECT(fh::pool_target_cap(1ull << 20, 0ull, 1u, 3, 256ull, 1u << 25, 3072u) == 3072u);
@@ -153,6 +191,22 @@ static bool replay(const Row& r)
     const double cost[2] = {as_double(in[0]), as_double(in[1])}, items[2] = {as_double(in[2]), as_double(in[3])};
     return (u64)fh::bottom_up_verdict(cost, items) == out[0];
   }
+  if (r.fn == "fold_survival") {  // stride, index of the radiance word, wave depth, paths, survival_n, the counter words (their number first), the 66 shares; out: survival_n, the 66 shares
+    if (in.size() < 6 || in.size() != 6 + in[5] + 66 || in[4] > 66 || out.size() != 67) return false;
+    const std::vector<uint32_t> counters(in.begin() + 6, in.begin() + 6 + (long)in[5]);  // (exactly the words the row holds: a read past them is the sanitizer's)
+    std::vector<double> survival(66);
+    for (size_t d = 0; d < 66; ++d) survival[d] = as_double(in[6 + in[5] + d]);
+    bool same = fh::fold_survival(counters.data(), (uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], survival.data(), (uint32_t)in[4]) == out[0];
+    for (size_t d = 0; d < 66; ++d) same = same && double_bits(survival[d]) == out[1 + d];
+    return same;
+  }
+  if (r.fn == "fold_probe_cost") {  // stride, indices of the node-round, triangle-round and shaded-path words, wave depth, cost and items so far, the counter words (their number first)
+    if (in.size() < 8 || in.size() != 8 + in[7] || out.size() != 2) return false;
+    const std::vector<uint32_t> counters(in.begin() + 8, in.end());
+    double cost = as_double(in[5]), items = as_double(in[6]);
+    fh::fold_probe_cost(counters.data(), (uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], (uint32_t)in[4], &cost, &items);
+    return double_bits(cost) == out[0] && double_bits(items) == out[1];
+  }
   if (r.fn == "lens_values") {
     if (in.size() != 3 || out.size() != 2) return false;
     float apb = 0.0f, lr = 0.0f;
@@ -173,7 +227,7 @@ int main(int argc, char** argv)
   }
   std::vector<Row> rows;
   if (!read_rows(path.c_str(), rows) || rows.size() < 100u) { std::printf("FAILED: cannot read the cases of %s\n", path.c_str()); ++failures; }
-  const char* const names[] = {"pool_target_cap", "samples_per_pass", "stream_lds_entries", "stream_wgs", "stream_chunk", "tail_wave_depth", "bottom_up_verdict", "lens_values"};
+  const char* const names[] = {"pool_target_cap", "samples_per_pass", "stream_lds_entries", "stream_wgs", "stream_chunk", "tail_wave_depth", "fold_survival", "fold_probe_cost", "bottom_up_verdict", "lens_values"};
   for (const char* name : names) {  // (a table without rows for a function would pass for nothing)
     size_t n = 0;
     for (const Row& r : rows) n += r.fn == name ? 1u : 0u;
