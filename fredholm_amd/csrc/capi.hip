@@ -15,8 +15,6 @@
 #include "fh_local_exposure.h"
 #include "fh_meter.h"
 #include "fh_trace.h"
-#include "motion_host.h"
-#include "temporal_host.h"
 
 // generated at build time from fredholm_amd/data/*.{u32,f32} by tools/gen_tables_inc.py
 #include "gen/tables.inc"
@@ -974,150 +972,7 @@ int fh_denoise(fh_ctx* ctx, uint32_t width, uint32_t height, const float* beauty
   return denoise_submit(ctx, (int)width, (int)height, beauty, normal, albedo, denoised, upscale2x ? 1 : 0);
 }
 
-// every refusal is decided from the arguments alone, before the context or the device is touched: a refused call changes nothing
-int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_denoise_params* params, float* denoised, int upscale2x)
-{
-  const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
-  const char* why = guided_refusal(width, height, in, pr, denoised);
-  if (!why && !ctx) why = "null context";
-  if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_guided: ") + why);
-  FH_GROUP_LEAD(ctx);
-  CTX_CHECK(ctx);
-  return denoise_guided_submit(ctx, (int)width, (int)height, in, &pr, denoised, upscale2x ? 1 : 0);
-}
-
-// fh_denoise_guided with the temporal stage in front of its passes; refusals as there (temporal_host.h)
-int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const fh_temporal_params* temporal,
-                        const fh_denoise_params* params, float* denoised, int upscale2x)
-{
-  const fh_temporal_params temporal_defaults = {0.2f, 32.0f, 0.5f, 0.02f};
-  const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
-  const fh_temporal_params tp = temporal ? *temporal : temporal_defaults;
-  float w2c[12], inv_tan = 0.0f;
-  const char* why = temporal_refusal(width, height, in, camera, tp, pr, denoised, w2c, &inv_tan);
-  if (!why && !ctx) why = "null context";
-  if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_temporal: ") + why);
-  FH_GROUP_LEAD(ctx);
-  CTX_CHECK(ctx);
-  if (!ctx->denoise_motion) return denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, nullptr, 0u, nullptr, denoised, upscale2x ? 1 : 0);
-  // fh_set_denoise_motion: the history is kept with the instance matrices it was written under; where they differ from the context's, the call carries the moved
-  // instances' pixels itself (motion.hip).  Everything that can fail is decided before the first launch.
-  const size_t nf = ctx->h_o2w.size();
-  const bool alive = ctx->hist_frames != 0 && ctx->hist_w == width && ctx->hist_h == height;
-  const bool moved = alive && nf != 0 && ctx->hist_o2w.size() == nf && ctx->hist_w2o.size() == nf && ctx->h_w2o.size() == nf &&
-                     (std::memcmp(ctx->hist_o2w.data(), ctx->h_o2w.data(), nf * sizeof(float)) != 0 || std::memcmp(ctx->hist_w2o.data(), ctx->h_w2o.data(), nf * sizeof(float)) != 0);
-  int rc;
-  if (!moved) {
-    rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, nullptr, 0u, nullptr, denoised, upscale2x ? 1 : 0);
-  } else {
-    if (!ctx->scene_loaded || !ctx->bvh_valid) return fail(ctx, FH_E_INVALID, "fh_denoise_temporal: instances moved and the BVH has not been built (fh_set_denoise_motion)");
-    const uint32_t ni = (uint32_t)(nf / 12);
-    std::vector<fh_motion> table(ni);
-    for (uint32_t i = 0; i < ni; ++i) {
-      motion_entry(ctx->hist_o2w.data() + 12ull * i, ctx->hist_w2o.data() + 12ull * i, ctx->h_o2w.data() + 12ull * i, ctx->h_w2o.data() + 12ull * i, &table[i]);
-      if (!motion_finite(table[i])) return fail(ctx, FH_E_INVALID, "fh_denoise_temporal: the motion of an instance is not finite (fh_set_denoise_motion)");
-    }
-    const size_t px = (size_t)width * height;
-    if (ctx->d_motion_ids.size() < px) {
-      (void)hipStreamSynchronize(ctx->stream);
-      FH_HIP(ctx->d_motion_ids.alloc(px));
-    }
-    if ((rc = primary_instances_submit(ctx, camera, width, height, ctx->d_motion_ids))) return rc;
-    rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, &tp, &pr, ctx->d_motion_ids, ni, table.data(), denoised, upscale2x ? 1 : 0);
-  }
-  if (rc == FH_OK) { ctx->hist_o2w = ctx->h_o2w; ctx->hist_w2o = ctx->h_w2o; }
-  return rc;
-}
-
-int fh_denoise_history_reset(fh_ctx* ctx)
-{
-  FH_GROUP_LEAD(ctx);
-  CTX_CHECK(ctx);
-  ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;  // (the buffers stay: the next call overwrites them without reading)
-  ctx->hist_o2w.clear(); ctx->hist_w2o.clear();
-  return FH_OK;
-}
-
-// the switch of the clipped temporal stage: broadcast on a group like fh_set_denoise_motion (the work it switches on runs on the lead)
-int fh_set_denoise_response(fh_ctx* ctx, const fh_response_params* params)
-{
-  if (const char* why = response_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_response: ") + why);
-  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_response(m_, params));
-  if (!ctx) return FH_E_INVALID;
-  ctx->denoise_response = params ? 1 : 0;
-  if (params) ctx->response_gamma = params->gamma;
-  return FH_OK;
-}
-
-int fh_get_denoise_response(fh_ctx* ctx, int* on, fh_response_params* params)
-{
-  FH_GROUP_LEAD(ctx);
-  if (!ctx || !on) return FH_E_INVALID;
-  *on = ctx->denoise_response;
-  if (params) params->gamma = ctx->response_gamma;
-  return FH_OK;
-}
-
-// the noise box of the clipped stage: stored and broadcast like the switch above, and read only while that one is on
-int fh_set_denoise_response_noise(fh_ctx* ctx, const fh_response_noise_params* params)
-{
-  if (const char* why = response_noise_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_response_noise: ") + why);
-  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_response_noise(m_, params));
-  if (!ctx) return FH_E_INVALID;
-  ctx->denoise_response_noise = params ? 1 : 0;
-  if (params) ctx->response_kappa = params->kappa;
-  return FH_OK;
-}
-
-int fh_get_denoise_response_noise(fh_ctx* ctx, int* on, fh_response_noise_params* params)
-{
-  FH_GROUP_LEAD(ctx);
-  if (!ctx || !on) return FH_E_INVALID;
-  *on = ctx->denoise_response_noise;
-  if (params) params->kappa = ctx->response_kappa;
-  return FH_OK;
-}
-
-// the moments of the temporal stage: broadcast like the switches above.  Turning it on or off drops the history (the stored history has, or lacks, the moment image);
-// the image itself is allocated by the next call (denoise.hip) and freed here when the switch goes off
-int fh_set_denoise_temporal_moments(fh_ctx* ctx, const fh_temporal_moments_params* params)
-{
-  if (const char* why = temporal_moments_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_temporal_moments: ") + why);
-  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_temporal_moments(m_, params));
-  if (!ctx) return FH_E_INVALID;
-  const int on = params ? 1 : 0;
-  if (on != ctx->denoise_temporal_moments) {
-    ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;  // fh_denoise_history_reset
-    ctx->hist_o2w.clear(); ctx->hist_w2o.clear();
-    if (!on && (ctx->d_hist_mu[0] || ctx->d_hist_mu[1])) {
-      if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, FH_E_HIP, "hipSetDevice failed");
-      (void)hipStreamSynchronize(ctx->stream);  // (a call queued earlier may still write them)
-      for (int k = 0; k < 2; ++k) ctx->d_hist_mu[k].reset();
-    }
-  }
-  ctx->denoise_temporal_moments = on;
-  if (params) ctx->moments_min_history = params->min_history;
-  return FH_OK;
-}
-
-int fh_get_denoise_temporal_moments(fh_ctx* ctx, int* on, fh_temporal_moments_params* params)
-{
-  FH_GROUP_LEAD(ctx);
-  if (!ctx || !on) return FH_E_INVALID;
-  *on = ctx->denoise_temporal_moments;
-  if (params) params->min_history = ctx->moments_min_history;
-  return FH_OK;
-}
-
-int fh_denoise_history_info(fh_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* frames)
-{
-  FH_GROUP_LEAD(ctx);
-  CTX_CHECK(ctx);
-  if (width) *width = ctx->hist_w;
-  if (height) *height = ctx->hist_h;
-  if (frames) *frames = ctx->hist_frames;
-  return FH_OK;
-}
+// fh_denoise_guided, fh_denoise_temporal, the history calls and their switches: denoise.hip
 
 // OpenGL interop (cwl::CUDAGLBuffer, cwl/include/cwl/buffer.h:88-143: cuGraphicsGLRegisterBuffer + map + mapped pointer, unmapped and
 // unregistered in the destructor).  Needs a current OpenGL context on the calling thread, like the reference.

@@ -13,6 +13,7 @@
 #include "fh_envmap.h"
 #include "fh_lights.h"
 #include "fh_memory.h"
+#include "temporal_host.h"
 
 struct fh_group;  // group.hip
 
@@ -283,21 +284,64 @@ struct fh_ctx {
   // variance-guided denoiser (denoise.hip): ping-pong (colour, variance) images and dense variance planes
   fh::DeviceBuffer<float4> d_guided_cv[2];
   fh::DeviceBuffer<float> d_guided_var[2];
-  // temporal accumulation (denoise.hip: fh_denoise_temporal): the history, double buffered -- per pixel (c_acc.rgb, v_acc), (P, h) and N -- with the camera of the
-  // call that wrote buffer `hist_cur`, that camera's world-to-camera rows and its cam_inv_tan.  hist_frames = 0: there is no history.
-  fh::DeviceBuffer<float4> d_hist_cv[2];
-  fh::DeviceBuffer<float4> d_hist_ph[2];
-  fh::DeviceBuffer<float4> d_hist_n[2];
-  uint32_t hist_w = 0, hist_h = 0, hist_frames = 0;
-  int hist_cur = 0;
-  fh_camera hist_camera{};
-  float hist_w2c[12] = {};
-  float hist_inv_tan = 0.0f;
-  // per-instance motion vectors (motion.hip, denoise.hip: k_temporal<kLookMotion, .>).  denoise_motion: fh_set_denoise_motion; hist_o2w / hist_w2o: the instance matrices the
-  // history was written under (empty: no snapshot).  The motion table of a call goes through the pinned h_motion (ev_motion: its copy has been taken) to d_motion;
-  // d_motion_ids is the id plane of the calls the context feeds itself.
+  // temporal accumulation (denoise.hip: fh_denoise_temporal): the history, double buffered -- per pixel (c_acc.rgb, v_acc), (P, h) and N, and while
+  // fh_set_denoise_temporal_moments is on the luminance moments (mu1, mu2) -- with the camera of the call that wrote buffer `cur`, that camera's world-to-camera rows and
+  // its cam_inv_tan.  frames = 0: there is no history.  o2w / w2o: the instance matrices the history was written under (fh_set_denoise_motion; empty: no snapshot).
+  // Each member function is the only place that does its job; what a call decides from these facts is temporal_host.h's temporal_call_plan.
+  struct TemporalHistory {
+    fh::DeviceBuffer<float4> d_cv[2], d_ph[2], d_n[2];
+    fh::DeviceBuffer<float2> d_mu[2];  // allocated by the first call with the switch on
+    uint32_t w = 0, h = 0, frames = 0;
+    int cur = 0;
+    fh_camera camera{};
+    float w2c[12] = {};
+    float inv_tan = 0.0f;
+    std::vector<float> o2w, w2o;
+    // pixels the buffers have room for.  ensure() allocates in order, so the last buffer tells that all were made
+    size_t capacity() const { return d_n[1].size(); }
+    size_t moment_capacity() const { return d_mu[1].size(); }
+    // the next call starts a new history.  Size and snapshot stay: fh_denoise_temporal has compared the snapshot before the call that restarts, and
+    // fh_denoise_history_info reports the size until a call has written another (denoise_temporal_submit: a call at another size, a new moment image)
+    void restart() { frames = 0; }
+    void forget_instances() { o2w.clear(); w2o.clear(); }  // another scene's instances are not these (scene.hip); fh_set_denoise_motion(0)
+    // fh_denoise_history_reset, and fh_set_denoise_temporal_moments when the switch changes.  The buffers stay: the next call overwrites them without reading
+    void drop() { restart(); w = 0; h = 0; forget_instances(); }
+    void release_moments() { for (int k = 0; k < 2; ++k) d_mu[k].reset(); }  // (the caller has made sure no call queued earlier still writes them)
+    // room for a call of px pixels (temporal_host.h: temporal_grow).  A grow frees, marks the history dropped, then allocates: after a failed allocation there is no
+    // history, the last buffer of the set is empty, so the capacity reads 0 and the next call makes the whole set again.  New main buffers forget the size as well but
+    // not the snapshot -- that is not drop(): a context driven through fh_denoise_temporal_motion keeps the snapshot its next fh_denoise_temporal compares
+    hipError_t ensure(size_t px, bool with_moments)
+    {
+      const fh::TemporalGrow grow = fh::temporal_grow(capacity(), moment_capacity(), px, with_moments);
+      if (grow.main) {
+        fh::DeviceBuffer<float4>* const bufs[3] = {d_cv, d_ph, d_n};
+        for (auto b : bufs)
+          for (int k = 0; k < 2; ++k) b[k].reset();
+        restart(); w = 0; h = 0;
+        for (auto b : bufs)
+          for (int k = 0; k < 2; ++k)
+            if (const hipError_t e = b[k].alloc(px)) return e;
+      }
+      if (grow.moments) {  // as large as the rest of the history
+        release_moments();
+        restart();
+        for (int k = 0; k < 2; ++k)
+          if (const hipError_t e = d_mu[k].alloc(capacity())) return e;
+      }
+      return hipSuccess;
+    }
+    // a call has written buffer cur ^ 1 under this camera
+    void commit(const fh_camera& cam, const float cam_w2c[12], float cam_inv_tan, uint32_t cw, uint32_t ch)
+    {
+      cur ^= 1; camera = cam; inv_tan = cam_inv_tan;
+      for (int k = 0; k < 12; ++k) w2c[k] = cam_w2c[k];
+      w = cw; h = ch;
+      if (frames != 0xffffffffu) ++frames;
+    }
+  } hist;
+  // per-instance motion vectors (motion.hip, denoise.hip: k_temporal<kLookMotion, .>).  denoise_motion: fh_set_denoise_motion.  The motion table of a call goes through
+  // the pinned h_motion (ev_motion: its copy has been taken) to d_motion; d_motion_ids is the id plane of the calls the context feeds itself.
   int denoise_motion = 0;
-  std::vector<float> hist_o2w, hist_w2o;
   fh::DeviceBuffer<fh_motion> d_motion;
   fh::PinnedBuffer<fh_motion> h_motion;
   fh::Event ev_motion;
@@ -309,10 +353,9 @@ struct fh_ctx {
   int denoise_response_noise = 0;
   float response_kappa = 6.0f;
   // fh_set_denoise_temporal_moments (k_temporal<., ., true>): while on, the history holds one more double-buffered image, the luminance moments (mu1, mu2), and a call
-  // without sample moments takes its variance from them once a pixel's history is moments_min_history long.  Allocated by the first call with the switch on.
+  // without sample moments takes its variance from them once a pixel's history is moments_min_history long (hist.d_mu).
   int denoise_temporal_moments = 0;
   float moments_min_history = 2.0f;
-  fh::DeviceBuffer<float2> d_hist_mu[2];
 
   // stats
   fh_stats stats{};

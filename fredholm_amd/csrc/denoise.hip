@@ -23,9 +23,12 @@
 
 #include <cmath>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "context.h"
 #include "fh_tonemap.h"
+#include "motion_host.h"
 
 namespace fh {
 namespace {
@@ -244,8 +247,7 @@ void launch_pass(const GuidedArgs& a, bool last, dim3 grid, hipStream_t st)
 //
 // One kernel template, k_temporal<LOOK, CLIP, MOM>, whose parts below are each written once; the host picks the instance (the choice is the same for every pixel).  The build
 // is fp32 without contraction, so a part gives the same bits in every instance it is inlined into, and the GPU suites hold each instance to the restatement's bits.
-enum { kLookNone, kLookOwn, kLookReproject, kLookMotion };  // LOOK: there is no history; the camera stood still; it moved; fh_denoise_temporal_motion with a moved instance
-enum { kClipOff, kClipColour, kClipColourNoise };          // CLIP: fh_set_denoise_response off; on; on with fh_set_denoise_response_noise and moments
+// LOOK is one of kLookNone .. kLookMotion, CLIP one of kClipOff .. kClipColourNoise (temporal_host.h, beside the plan that picks them).
 
 struct TemporalArgs {
   const float4* cv;       // (c.rgb, v) of the preparation
@@ -485,24 +487,21 @@ __global__ void __launch_bounds__(256) k_temporal(const TemporalArgs A)
 }
 
 using TemporalLaunch = void (*)(const TemporalArgs&, dim3, hipStream_t);
-template <int LOOK, int CLIP, bool MOM = false>
+template <int LOOK, int CLIP, bool MOM>
 void temporal_launch(const TemporalArgs& a, dim3 grid, hipStream_t st)
 {
   hipLaunchKernelGGL((k_temporal<LOOK, CLIP, MOM>), grid, dim3(kTW, kTH), 0, st, a);
 }
-// [LOOK][CLIP]: the ten instances in use
-constexpr TemporalLaunch kTemporalLaunch[4][3] = {
-    {temporal_launch<kLookNone, kClipOff>, nullptr, nullptr},
-    {temporal_launch<kLookOwn, kClipOff>, temporal_launch<kLookOwn, kClipColour>, temporal_launch<kLookOwn, kClipColourNoise>},
-    {temporal_launch<kLookReproject, kClipOff>, temporal_launch<kLookReproject, kClipColour>, temporal_launch<kLookReproject, kClipColourNoise>},
-    {temporal_launch<kLookMotion, kClipOff>, temporal_launch<kLookMotion, kClipColour>, temporal_launch<kLookMotion, kClipColourNoise>},
-};
-// the same ten with the moments (fh_set_denoise_temporal_moments)
-constexpr TemporalLaunch kTemporalLaunchMoments[4][3] = {
-    {temporal_launch<kLookNone, kClipOff, true>, nullptr, nullptr},
-    {temporal_launch<kLookOwn, kClipOff, true>, temporal_launch<kLookOwn, kClipColour, true>, temporal_launch<kLookOwn, kClipColourNoise, true>},
-    {temporal_launch<kLookReproject, kClipOff, true>, temporal_launch<kLookReproject, kClipColour, true>, temporal_launch<kLookReproject, kClipColourNoise, true>},
-    {temporal_launch<kLookMotion, kClipOff, true>, temporal_launch<kLookMotion, kClipColour, true>, temporal_launch<kLookMotion, kClipColourNoise, true>},
+// [MOM][LOOK][CLIP]: the twenty instances in use.  Without a history there is nothing to clip: temporal_call_plan never picks an empty entry
+constexpr TemporalLaunch kTemporalLaunch[2][4][3] = {
+    {{temporal_launch<kLookNone, kClipOff, false>, nullptr, nullptr},
+     {temporal_launch<kLookOwn, kClipOff, false>, temporal_launch<kLookOwn, kClipColour, false>, temporal_launch<kLookOwn, kClipColourNoise, false>},
+     {temporal_launch<kLookReproject, kClipOff, false>, temporal_launch<kLookReproject, kClipColour, false>, temporal_launch<kLookReproject, kClipColourNoise, false>},
+     {temporal_launch<kLookMotion, kClipOff, false>, temporal_launch<kLookMotion, kClipColour, false>, temporal_launch<kLookMotion, kClipColourNoise, false>}},
+    {{temporal_launch<kLookNone, kClipOff, true>, nullptr, nullptr},
+     {temporal_launch<kLookOwn, kClipOff, true>, temporal_launch<kLookOwn, kClipColour, true>, temporal_launch<kLookOwn, kClipColourNoise, true>},
+     {temporal_launch<kLookReproject, kClipOff, true>, temporal_launch<kLookReproject, kClipColour, true>, temporal_launch<kLookReproject, kClipColourNoise, true>},
+     {temporal_launch<kLookMotion, kClipOff, true>, temporal_launch<kLookMotion, kClipColour, true>, temporal_launch<kLookMotion, kClipColourNoise, true>}},
 };
 
 }  // namespace
@@ -589,57 +588,205 @@ int motion_upload(fh_ctx* ctx, uint32_t n, const fh_motion* motion)
   return FH_OK;
 }
 
+// the one launch between the preparation and the passes: buffer hist.cur is read, the other written (hist.commit makes it the current one)
+void temporal_stage(fh_ctx* ctx, const TemporalCallPlan& plan, int w, int h, const fh_denoise_inputs* in, const fh_temporal_params* tp, const uint32_t* ids, uint32_t n_instances)
+{
+  const fh_ctx::TemporalHistory& hist = ctx->hist;
+  const int from = hist.cur, to = from ^ 1;
+  TemporalArgs a{};
+  a.cv = ctx->d_guided_cv[0]; a.normal = (const float4*)in->normal; a.position = (const float4*)in->position; a.depth = in->depth;
+  a.h_cv = hist.d_cv[from]; a.h_ph = hist.d_ph[from]; a.h_n = hist.d_n[from];
+  a.o_cv = hist.d_cv[to]; a.o_ph = hist.d_ph[to]; a.o_n = hist.d_n[to];
+  a.vplane = ctx->d_guided_var[0];
+  a.w = w; a.h = h; a.W = (float)w; a.H = (float)h;
+  for (int k = 0; k < 12; ++k) a.m[k] = hist.w2c[k];
+  a.f = hist.inv_tan;
+  a.alpha_min = tp->alpha_min; a.max_history = tp->max_history; a.cos_min = tp->normal_cos_min; a.plane_tol = tp->plane_tol;
+  a.ids = ids; a.motion = ctx->d_motion; a.n_instances = n_instances; a.still = plan.still ? 1 : 0;
+  a.gamma = ctx->response_gamma; a.kappa = ctx->response_kappa;
+  if (plan.mom) { a.h_mu = hist.d_mu[from]; a.o_mu = hist.d_mu[to]; a.min_history = ctx->moments_min_history; a.replace_v = plan.replace_v ? 1 : 0; }
+  kTemporalLaunch[plan.mom][plan.look][plan.clip](a, dim3((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), ctx->stream);
+}
+
 }  // namespace
 
 // ids == nullptr: no motion stage (fh_denoise_temporal, or no instance moved)
 int denoise_temporal_submit(fh_ctx* ctx, int w, int h, const fh_denoise_inputs* in, const fh_camera* cam, const float w2c[12], float inv_tan, const fh_temporal_params* tp,
                             const fh_denoise_params* pr, const uint32_t* ids, uint32_t n_instances, const fh_motion* motion, float* out, int upscale)
 {
+  fh_ctx::TemporalHistory& hist = ctx->hist;
   const size_t px = (size_t)w * h;
   if (const int rc = guided_scratch(ctx, px)) return rc;
-  if (ctx->d_hist_n[1].size() < px) {  // (the last of the six, so all were made.  Growing drops the history; so does any other change of width x height, below)
-    DeviceBuffer<float4>* const bufs[3] = {ctx->d_hist_cv, ctx->d_hist_ph, ctx->d_hist_n};
-    for (auto b : bufs)
-      for (int k = 0; k < 2; ++k) b[k].reset();
-    ctx->hist_frames = 0; ctx->hist_w = 0; ctx->hist_h = 0;
-    for (auto b : bufs)
-      for (int k = 0; k < 2; ++k) FH_HIP(b[k].alloc(px));
-  }
-  const bool mom = ctx->denoise_temporal_moments != 0;
-  const size_t hist_pixels = ctx->d_hist_n[1].size();
-  if (mom && ctx->d_hist_mu[1].size() < hist_pixels) {  // (the moment image of fh_set_denoise_temporal_moments: as large as the rest of the history; a new one holds nothing)
-    for (int k = 0; k < 2; ++k) ctx->d_hist_mu[k].reset();
-    ctx->hist_frames = 0;
-    for (int k = 0; k < 2; ++k) FH_HIP(ctx->d_hist_mu[k].alloc(hist_pixels));
-  }
-  if (ctx->hist_w != (uint32_t)w || ctx->hist_h != (uint32_t)h) ctx->hist_frames = 0;
-  const bool with_motion = ids && ctx->hist_frames != 0;  // (without a history nothing is looked up: the plain first call)
-  if (with_motion)
+  // the plan is made from the history as the call finds it; ensure() acts on the same temporal_grow
+  const TemporalCallPlan plan = temporal_call_plan({hist.frames, hist.w, hist.h, hist.capacity(), hist.moment_capacity(), std::memcmp(cam, &hist.camera, sizeof(fh_camera)) == 0},
+                                                   {(uint32_t)w, (uint32_t)h, ids != nullptr, in->moments != nullptr},
+                                                   {ctx->denoise_response != 0, ctx->denoise_response_noise != 0, ctx->denoise_temporal_moments != 0});
+  FH_HIP(hist.ensure(px, plan.mom));
+  if (!plan.history_kept) hist.restart();  // (a call at another size than the history's; after a grow, ensure() has done it)
+  if (plan.with_motion)
     if (const int rc = motion_upload(ctx, n_instances, motion)) return rc;
   guided_prepare(ctx, w, h, in, pr);
-  const int from = ctx->hist_cur, to = from ^ 1;
-  TemporalArgs a{};
-  a.cv = ctx->d_guided_cv[0]; a.normal = (const float4*)in->normal; a.position = (const float4*)in->position; a.depth = in->depth;
-  a.h_cv = ctx->d_hist_cv[from]; a.h_ph = ctx->d_hist_ph[from]; a.h_n = ctx->d_hist_n[from];
-  a.o_cv = ctx->d_hist_cv[to]; a.o_ph = ctx->d_hist_ph[to]; a.o_n = ctx->d_hist_n[to];
-  a.vplane = ctx->d_guided_var[0];
-  a.w = w; a.h = h; a.W = (float)w; a.H = (float)h;
-  for (int k = 0; k < 12; ++k) a.m[k] = ctx->hist_w2c[k];
-  a.f = ctx->hist_inv_tan;
-  a.alpha_min = tp->alpha_min; a.max_history = tp->max_history; a.cos_min = tp->normal_cos_min; a.plane_tol = tp->plane_tol;
-  const bool still = std::memcmp(cam, &ctx->hist_camera, sizeof(fh_camera)) == 0;
-  a.ids = ids; a.motion = ctx->d_motion; a.n_instances = n_instances; a.still = still ? 1 : 0;
-  a.gamma = ctx->response_gamma; a.kappa = ctx->response_kappa;
-  if (mom) { a.h_mu = ctx->d_hist_mu[from]; a.o_mu = ctx->d_hist_mu[to]; a.min_history = ctx->moments_min_history; a.replace_v = in->moments ? 0 : 1; }
-  const int look = ctx->hist_frames == 0 ? kLookNone : with_motion ? kLookMotion : still ? kLookOwn : kLookReproject;
-  // fh_set_denoise_response clips whatever history the call looks up; fh_set_denoise_response_noise adds its step only with moments (the measured variance exists only then)
-  const int clip = look == kLookNone || !ctx->denoise_response ? kClipOff : ctx->denoise_response_noise && in->moments ? kClipColourNoise : kClipColour;
-  (mom ? kTemporalLaunchMoments : kTemporalLaunch)[look][clip](a, dim3((w + kTW - 1) / kTW, (h + kTH - 1) / kTH), ctx->stream);
-  ctx->hist_cur = to; ctx->hist_camera = *cam; ctx->hist_inv_tan = inv_tan;
-  for (int k = 0; k < 12; ++k) ctx->hist_w2c[k] = w2c[k];
-  ctx->hist_w = (uint32_t)w; ctx->hist_h = (uint32_t)h;
-  if (ctx->hist_frames != 0xffffffffu) ++ctx->hist_frames;
-  return guided_passes(ctx, w, h, in, pr, ctx->d_hist_cv[to], out, upscale);
+  temporal_stage(ctx, plan, w, h, in, tp, ids, n_instances);
+  hist.commit(*cam, w2c, inv_tan, (uint32_t)w, (uint32_t)h);  // (whether or not the passes then fail: the stage is queued)
+  return guided_passes(ctx, w, h, in, pr, hist.d_cv[hist.cur], out, upscale);
 }
 
+namespace {
+
+// fh_denoise_temporal after its refusals.  Under fh_set_denoise_motion the context feeds the call what fh_denoise_temporal_motion is fed by its caller: the motion table
+// from the snapshot of the instance matrices the history was written under, and the id plane of this camera.  Everything that can fail is decided before the first launch.
+int temporal_feed_motion(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const float w2c[12], float inv_tan,
+                         const fh_temporal_params* tp, const fh_denoise_params* pr, float* denoised, int upscale)
+{
+  fh_ctx::TemporalHistory& hist = ctx->hist;
+  // alive is what denoise_temporal_submit's plan will call history_kept, and the table and the id plane below are made only for a call that looks them up.  The two agree
+  // because of what the record keeps true while frames != 0: commit() follows an ensure() for w x h pixels, so capacity() >= w * h and no main grow at this size; and
+  // with the moments on, that ensure() made the moment image as large as the rest, while the switch itself drops the history whenever it changes, so no moment grow either.
+  // (tools/temporal_host_check.cpp asserts it over its cases.)
+  const bool alive = hist.frames != 0 && hist.w == width && hist.h == height;
+  const TemporalFeedPlan feed = temporal_feed_plan(ctx->denoise_motion != 0, alive, hist.o2w, hist.w2o, ctx->h_o2w, ctx->h_w2o, ctx->scene_loaded && ctx->bvh_valid);
+  if (feed.refusal) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_temporal: ") + feed.refusal);
+  std::vector<fh_motion> table;
+  const uint32_t* ids = nullptr;
+  if (feed.feed_motion) {
+    table.resize(ctx->h_o2w.size() / 12);
+    for (size_t i = 0; i < table.size(); ++i) {
+      motion_entry(hist.o2w.data() + 12 * i, hist.w2o.data() + 12 * i, ctx->h_o2w.data() + 12 * i, ctx->h_w2o.data() + 12 * i, &table[i]);
+      if (!motion_finite(table[i])) return fail(ctx, FH_E_INVALID, "fh_denoise_temporal: the motion of an instance is not finite (fh_set_denoise_motion)");
+    }
+    const size_t px = (size_t)width * height;
+    if (ctx->d_motion_ids.size() < px) {
+      (void)hipStreamSynchronize(ctx->stream);
+      FH_HIP(ctx->d_motion_ids.alloc(px));
+    }
+    if (const int rc = primary_instances_submit(ctx, camera, width, height, ctx->d_motion_ids)) return rc;
+    ids = ctx->d_motion_ids;
+  }
+  const int rc = denoise_temporal_submit(ctx, (int)width, (int)height, in, camera, w2c, inv_tan, tp, pr, ids, (uint32_t)table.size(), ids ? table.data() : nullptr, denoised, upscale);
+  if (rc == FH_OK && ctx->denoise_motion) { hist.o2w = ctx->h_o2w; hist.w2o = ctx->h_w2o; }  // the snapshot: what the next call's table is made from
+  return rc;
+}
+
+}  // namespace
 }  // namespace fh
+
+using namespace fh;
+
+extern "C" {
+
+// every refusal is decided from the arguments alone, before the context or the device is touched: a refused call changes nothing
+int fh_denoise_guided(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_denoise_params* params, float* denoised, int upscale2x)
+{
+  const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
+  const char* why = guided_refusal(width, height, in, pr, denoised);
+  if (!why && !ctx) why = "null context";
+  if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_guided: ") + why);
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  return denoise_guided_submit(ctx, (int)width, (int)height, in, &pr, denoised, upscale2x ? 1 : 0);
+}
+
+// fh_denoise_guided with the temporal stage in front of its passes; refusals as there (temporal_host.h)
+int fh_denoise_temporal(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const fh_temporal_params* temporal,
+                        const fh_denoise_params* params, float* denoised, int upscale2x)
+{
+  const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
+  const fh_temporal_params tp = temporal ? *temporal : kTemporalDefaults;
+  float w2c[12], inv_tan = 0.0f;
+  const char* why = temporal_refusal(width, height, in, camera, tp, pr, denoised, w2c, &inv_tan);
+  if (!why && !ctx) why = "null context";
+  if (why) return fail(ctx, FH_E_INVALID, std::string("fh_denoise_temporal: ") + why);
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  return temporal_feed_motion(ctx, width, height, in, camera, w2c, inv_tan, &tp, &pr, denoised, upscale2x ? 1 : 0);
+}
+
+int fh_denoise_history_reset(fh_ctx* ctx)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  ctx->hist.drop();
+  return FH_OK;
+}
+
+int fh_denoise_history_info(fh_ctx* ctx, uint32_t* width, uint32_t* height, uint32_t* frames)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (width) *width = ctx->hist.w;
+  if (height) *height = ctx->hist.h;
+  if (frames) *frames = ctx->hist.frames;
+  return FH_OK;
+}
+
+// the switch of the clipped temporal stage: broadcast on a group like fh_set_denoise_motion (the work it switches on runs on the lead)
+int fh_set_denoise_response(fh_ctx* ctx, const fh_response_params* params)
+{
+  if (const char* why = response_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_response: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_response(m_, params));
+  if (!ctx) return FH_E_INVALID;
+  ctx->denoise_response = params ? 1 : 0;
+  if (params) ctx->response_gamma = params->gamma;
+  return FH_OK;
+}
+
+int fh_get_denoise_response(fh_ctx* ctx, int* on, fh_response_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->denoise_response;
+  if (params) params->gamma = ctx->response_gamma;
+  return FH_OK;
+}
+
+// the noise box of the clipped stage: stored and broadcast like the switch above, and read only while that one is on
+int fh_set_denoise_response_noise(fh_ctx* ctx, const fh_response_noise_params* params)
+{
+  if (const char* why = response_noise_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_response_noise: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_response_noise(m_, params));
+  if (!ctx) return FH_E_INVALID;
+  ctx->denoise_response_noise = params ? 1 : 0;
+  if (params) ctx->response_kappa = params->kappa;
+  return FH_OK;
+}
+
+int fh_get_denoise_response_noise(fh_ctx* ctx, int* on, fh_response_noise_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->denoise_response_noise;
+  if (params) params->kappa = ctx->response_kappa;
+  return FH_OK;
+}
+
+// the moments of the temporal stage: broadcast like the switches above.  Turning it on or off drops the history (the stored history has, or lacks, the moment image);
+// the image itself is allocated by the next call (TemporalHistory::ensure) and freed here when the switch goes off
+int fh_set_denoise_temporal_moments(fh_ctx* ctx, const fh_temporal_moments_params* params)
+{
+  if (const char* why = temporal_moments_refusal(params)) return fail(ctx, FH_E_INVALID, std::string("fh_set_denoise_temporal_moments: ") + why);
+  FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_temporal_moments(m_, params));
+  if (!ctx) return FH_E_INVALID;
+  const int on = params ? 1 : 0;
+  if (on != ctx->denoise_temporal_moments) {
+    ctx->hist.drop();
+    if (!on && (ctx->hist.d_mu[0] || ctx->hist.d_mu[1])) {
+      if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, FH_E_HIP, "hipSetDevice failed");
+      (void)hipStreamSynchronize(ctx->stream);  // (a call queued earlier may still write them)
+      ctx->hist.release_moments();
+    }
+  }
+  ctx->denoise_temporal_moments = on;
+  if (params) ctx->moments_min_history = params->min_history;
+  return FH_OK;
+}
+
+int fh_get_denoise_temporal_moments(fh_ctx* ctx, int* on, fh_temporal_moments_params* params)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx || !on) return FH_E_INVALID;
+  *on = ctx->denoise_temporal_moments;
+  if (params) params->min_history = ctx->moments_min_history;
+  return FH_OK;
+}
+
+}  // extern "C"

@@ -107,9 +107,8 @@ int fh_motion_from_transforms(uint32_t n, const float* o2w_prev, const float* w2
 int fh_denoise_temporal_motion(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_camera* camera, const fh_temporal_params* temporal,
                                const fh_denoise_params* params, const uint32_t* instance_ids, uint32_t n_instances, const fh_motion* motion, float* denoised, int upscale2x)
 {
-  const fh_temporal_params temporal_defaults = {0.2f, 32.0f, 0.5f, 0.02f};
   const fh_denoise_params pr = params ? *params : kDenoiseDefaults;
-  const fh_temporal_params tp = temporal ? *temporal : temporal_defaults;
+  const fh_temporal_params tp = temporal ? *temporal : kTemporalDefaults;
   float w2c[12], inv_tan = 0.0f;
   bool any_moved = false;
   const char* why = temporal_refusal(width, height, in, camera, tp, pr, denoised, w2c, &inv_tan);
@@ -126,7 +125,7 @@ int fh_set_denoise_motion(fh_ctx* ctx, int on)
   FH_GROUP_EACH(ctx, kGroupCallPlain, fh_set_denoise_motion(m_, on));
   if (!ctx) return FH_E_INVALID;
   ctx->denoise_motion = on ? 1 : 0;
-  if (!on) { ctx->hist_o2w.clear(); ctx->hist_w2o.clear(); }
+  if (!on) ctx->hist.forget_instances();
   return FH_OK;
 }
 

@@ -191,7 +191,7 @@ void commit_scene(fh_ctx* ctx, const fh_scene_desc& s, HostScene& h, const Scene
   for (int k = 0; k < 3; ++k) ctx->alpha_cell_counts[k] = plan.alpha_cell_counts[k];
   ctx->refit_ok = false;  // new topology: the next build is a full one
   ctx->builder_choice = 0;  // new geometry: let the next build choose its builder again
-  ctx->hist_o2w.clear(); ctx->hist_w2o.clear();  // (fh_set_denoise_motion: another scene's instances are not these)
+  ctx->hist.forget_instances();  // (fh_set_denoise_motion: another scene's instances are not these)
   if (plan.sw.debug && plan.alpha_face_counts[0])
     fprintf(stderr, "[alpha] %u faces whose textures can cut: %u always pass, %u never pass, %u keep their any-hit test\n", plan.alpha_face_counts[0], plan.alpha_face_counts[1], plan.alpha_face_counts[2],
             plan.alpha_face_counts[3]);

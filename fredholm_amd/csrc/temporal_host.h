@@ -1,14 +1,20 @@
-// temporal_host.h -- the host-only part of fh_denoise_temporal (include/fredholm_hip.h): the refusals, which are decided from the arguments alone, and the
-// inversion of the camera.  Plain C++ without HIP, so that it also compiles into a stand-alone program (tools/temporal_host_check.cpp) for the host sanitizers.
+// temporal_host.h -- the host-only part of fh_denoise_temporal (include/fredholm_hip.h): the refusals, which are decided from the arguments alone, the
+// inversion of the camera, and the plan of a call: what becomes of the history, which of the twenty k_temporal a call launches (temporal_call_plan) and whether the
+// context feeds itself a motion table (temporal_feed_plan).  Plain C++ without HIP, so that it also compiles into a stand-alone program
+// (tools/temporal_host_check.cpp) for the host sanitizers.
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
+#include <vector>
 
 #include "../../include/fredholm_hip.h"
 
 namespace fh {
 
 constexpr fh_denoise_params kDenoiseDefaults = {2.0f, 1.0f, 0.2f, 7u, 5u};  // what a null fh_denoise_params means (the header states them)
+constexpr fh_temporal_params kTemporalDefaults = {0.2f, 32.0f, 0.5f, 0.02f};  // ... and a null fh_temporal_params
 
 // why fh_denoise_guided refuses these arguments, or nullptr (the context is not looked at)
 inline const char* guided_refusal(uint32_t width, uint32_t height, const fh_denoise_inputs* in, const fh_denoise_params& pr, const float* denoised)
@@ -81,6 +87,66 @@ inline const char* temporal_moments_refusal(const fh_temporal_moments_params* pa
 {
   if (params && (!(params->min_history >= 1.0f) || !std::isfinite(params->min_history))) return "min_history must be finite and >= 1";
   return nullptr;
+}
+
+// ---- the plan of a call (denoise.hip: denoise_temporal_submit, temporal_feed_motion) ----
+
+enum { kLookNone, kLookOwn, kLookReproject, kLookMotion };  // LOOK: there is no history; the camera stood still; it moved; fh_denoise_temporal_motion with a moved instance
+enum { kClipOff, kClipColour, kClipColourNoise };          // CLIP: fh_set_denoise_response off; on; on with fh_set_denoise_response_noise and moments
+
+// which buffers of the history a call of px pixels allocates anew: the main six where they are too small, the moment image of fh_set_denoise_temporal_moments where it is
+// smaller than the rest of the history will be (a new buffer holds nothing: either grow drops the history).  Stated here for the plan and for the record that acts on it
+// (context.h: TemporalHistory::ensure).
+struct TemporalGrow { bool main, moments; };
+inline TemporalGrow temporal_grow(size_t capacity, size_t moment_capacity, size_t px, bool with_moments)
+{
+  const bool main = capacity < px;
+  return {main, with_moments && moment_capacity < (main ? px : capacity)};
+}
+
+struct TemporalHistoryFacts {
+  uint32_t frames, w, h;             // frames = 0: there is no history
+  size_t capacity, moment_capacity;  // pixels the main buffers / the moment image have room for
+  bool same_camera;                  // the call's camera equals the history's, byte for byte
+};
+struct TemporalCallFacts { uint32_t w, h; bool has_ids, has_sample_moments; };  // has_ids: an id plane and a motion table of which at least one entry has moved
+struct TemporalSwitches { bool response, response_noise, temporal_moments; };  // fh_set_denoise_response, _response_noise, _temporal_moments
+struct TemporalCallPlan {
+  bool grow_main, grow_moments;  // temporal_grow
+  bool history_kept;             // the call looks its history up; false: it starts one
+  bool with_motion;              // the motion table is uploaded
+  int look, clip;                // k_temporal<look, clip, mom>; kLookNone goes with kClipOff only
+  bool mom, replace_v;           // replace_v: the variance comes from the history's moments where it is long enough
+  bool still;                    // same_camera as the kernel is told (kLookMotion: the pixels of unmoved instances look up their own place)
+};
+inline TemporalCallPlan temporal_call_plan(const TemporalHistoryFacts& hist, const TemporalCallFacts& call, const TemporalSwitches& on)
+{
+  TemporalCallPlan p{};
+  const TemporalGrow grow = temporal_grow(hist.capacity, hist.moment_capacity, (size_t)call.w * call.h, on.temporal_moments);
+  p.grow_main = grow.main; p.grow_moments = grow.moments;
+  // growing drops the history; so does any other change of width x height
+  p.history_kept = hist.frames != 0 && !grow.main && !grow.moments && hist.w == call.w && hist.h == call.h;
+  p.with_motion = call.has_ids && p.history_kept;  // (without a history nothing is looked up: the plain first call)
+  p.still = hist.same_camera;
+  p.look = !p.history_kept ? kLookNone : p.with_motion ? kLookMotion : p.still ? kLookOwn : kLookReproject;
+  // fh_set_denoise_response clips whatever history the call looks up; fh_set_denoise_response_noise adds its step only with moments (the measured variance exists only then)
+  p.clip = p.look == kLookNone || !on.response ? kClipOff : on.response_noise && call.has_sample_moments ? kClipColourNoise : kClipColour;
+  p.mom = on.temporal_moments; p.replace_v = p.mom && !call.has_sample_moments;
+  return p;
+}
+
+// fh_denoise_temporal under fh_set_denoise_motion: the history is kept with the instance matrices it was written under (hist_*; empty: no snapshot), and where they differ
+// from the context's (h_*) the call carries the moved instances' pixels itself.  alive: there is a history at the call's size.  refusal: why the call is refused, or nullptr
+struct TemporalFeedPlan { bool feed_motion; const char* refusal; };
+inline TemporalFeedPlan temporal_feed_plan(bool denoise_motion, bool alive, const std::vector<float>& hist_o2w, const std::vector<float>& hist_w2o, const std::vector<float>& h_o2w,
+                                           const std::vector<float>& h_w2o, bool tree_built)
+{
+  const size_t nf = h_o2w.size();
+  const bool moved = denoise_motion && alive && nf != 0 && hist_o2w.size() == nf && hist_w2o.size() == nf && h_w2o.size() == nf &&
+                     (std::memcmp(hist_o2w.data(), h_o2w.data(), nf * sizeof(float)) != 0 || std::memcmp(hist_w2o.data(), h_w2o.data(), nf * sizeof(float)) != 0);
+  if (!moved) return {false, nullptr};
+  if (!tree_built) return {false, "instances moved and the BVH has not been built (fh_set_denoise_motion)"};
+  return {true, nullptr};
 }
 
 }  // namespace fh

@@ -1,9 +1,10 @@
 """CPU tests of the interface of temporal accumulation (include/fredholm_hip.h: fh_denoise_temporal, fh_denoise_history_reset, fh_denoise_history_info): the exported
 symbols and their ctypes signatures, the layout of fh_temporal_params, the refusals -- decided from the arguments alone, before the context or the device is touched --
-the host-only check program (tools/temporal_host_check.cpp: refusals and camera inversion), and the facades: fredholm::Denoiser's Temporal mode, Renderer::set_seed,
+the host-only check program (tools/temporal_host_check.cpp: refusals, camera inversion and the plan of a call), and the facades: fredholm::Denoiser's Temporal mode, Renderer::set_seed,
 the Python methods and rtcamp's flag.  The stage itself is tested on the GPU (test_gpu_denoise_temporal.py)."""
 import ctypes as C
 import inspect
+import json
 import os
 import subprocess
 
@@ -108,13 +109,29 @@ def test_every_refusal_is_decided_before_the_context_is_touched():
 
 
 def test_host_check_program_passes(tmp_path):
-    """the refusals and the camera inversion as a stand-alone host program (the one the host sanitizers are run on); its inverse agrees with numpy's in double"""
+    """the refusals, the camera inversion and the plan of a call as a stand-alone host program (the one the host sanitizers are run on); its inverse agrees with numpy's in double"""
     exe = tmp_path / "temporal_host_check"
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-ffp-contract=off", os.path.join(ROOT, "tools", "temporal_host_check.cpp"), "-o", str(exe)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0 and "ok" in run.stdout, run.stdout
+    # the plan of a call (temporal_call_plan, temporal_feed_plan): given the table, the program replays every row of it, and the table has rows for both functions
+    cases = os.path.join(ROOT, "tests", "golden", "temporal_plan_cases.json")
+    rows = json.load(open(cases))
+    replayed = subprocess.run([str(exe), cases], capture_output=True, text=True)
+    assert replayed.returncode == 0 and "temporal_host_check: ok (%d cases)" % len(rows) in replayed.stdout and len(rows) >= 300, replayed.stdout
+    assert {r["fn"] for r in rows} == {"temporal_call_plan", "temporal_feed_plan"}
+    # a table it cannot read, or one with one expected value flipped, fails and names the case
+    assert subprocess.run([str(exe), str(tmp_path / "missing.json")], capture_output=True, text=True).returncode != 0
+    for fn, col in (("temporal_call_plan", 4), ("temporal_call_plan", 2), ("temporal_feed_plan", 0)):
+        k = max(i for i, r in enumerate(rows) if r["fn"] == fn)
+        flipped = [dict(r, out=list(r["out"])) for r in rows]
+        flipped[k]["out"][col] ^= 1
+        bad = tmp_path / "bad.json"
+        bad.write_text(json.dumps(flipped))
+        r = subprocess.run([str(exe), str(bad)], capture_output=True, text=True)
+        assert r.returncode != 0 and "temporal_host_check: 1 failures" in r.stdout and "FAILED case %d (%s)" % (k, fn) in r.stdout, r.stdout
     from fredholm_amd.renderer import look_at_transform
     t = look_at_transform((0.3, 1.1, 3.4), (0.2, -0.1, -1.0))
     out = subprocess.run([str(exe)] + [repr(float(v)) for v in t.reshape(12)] + ["1.0", "8.0", "100.0"], capture_output=True, text=True, check=True).stdout.split()

@@ -438,6 +438,41 @@ def test_first_call_equals_the_guided_filter(renderer, use_moments, upscale):
             d.free()
 
 
+@gpu
+@pytest.mark.parametrize("moments", [False, True])
+def test_history_life_cycle_on_a_fresh_context(moments):
+    """What becomes of the history from call to call, on a context that has never denoised: a larger frame makes the buffers grow (with fh_set_denoise_temporal_moments
+    on from the start, the moment image and the main buffers in one call), a frame of the same pixel count and other dimensions fits the buffers and still starts a new
+    history.  A call that starts a history gives fh_denoise_guided's bits (with sample moments also while the temporal moments are on); one that uses its history does not."""
+    r = F.Renderer(0)
+    devs = {}
+    try:
+        if moments:
+            r.set_denoise_temporal_moments()
+        cam = F.Camera(origin=(0.0, 0.0, 1.0))
+        devs = {wh: Dev(r, _random_layers(*wh, seed)) for wh, seed in (((5, 3), 6), ((8, 5), 7), ((5, 8), 8))}
+        want = {wh: d.guided() for wh, d in devs.items()}
+        assert r.denoise_history_info() == (0, 0, 0)
+
+        def call(wh, starts, frames):
+            got = devs[wh].temporal(cam)
+            assert _bits(got, want[wh]) == starts, (wh, frames)
+            assert r.denoise_history_info() == wh + (frames,)
+
+        call((5, 3), True, 1)
+        call((5, 3), False, 2)
+        call((8, 5), True, 1)   # a: the buffers grow
+        call((8, 5), False, 2)  # b: ... and hold a history after it
+        call((5, 8), True, 1)   # the same 40 pixels: no grow, another size
+        call((5, 8), False, 2)
+        call((5, 3), True, 1)   # a smaller frame within the buffers
+        call((5, 3), False, 2)
+    finally:
+        for d in devs.values():
+            d.free()
+        r.close()
+
+
 # ------------------------------------------------------------------ 2: a still camera accumulates a running mean
 @gpu
 def test_still_camera_keeps_a_running_mean(renderer, oracle):
