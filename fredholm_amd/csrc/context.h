@@ -58,6 +58,19 @@ struct fh_ctx {
   fh::DeviceBuffer<uint2> d_face_meta;  // (material id, instance id) per face
   fh::DeviceBuffer<float4> d_o2w;       // 3 rows per instance
   fh::DeviceBuffer<float4> d_w2o;
+  // fh_set_skin / fh_set_joint_matrices (scene.hip: k_skin_vertices, fh_skin.h).  Belongs to the uploaded scene: an upload drops it.  While `posed`, the face
+  // records are derived from d_vertices / d_normals (the layout of d_obj_vertices / d_obj_normals) instead of the bind arrays
+  struct Skin {
+    uint32_t n_joints = 0, n_skinned = 0;  // n_joints = 0: no skin
+    bool posed = false;
+    std::vector<float> h_palette;          // the matrices held (12 floats per joint); empty until the first fh_set_joint_matrices
+    fh::DeviceBuffer<uint2> d_joints;      // four uint16 per vertex
+    fh::DeviceBuffer<float4> d_weights;
+    fh::DeviceBuffer<float4> d_palette;    // three rows per joint
+    fh::DeviceBuffer<float> d_vertices, d_normals;
+    // (the caller has made sure nothing still reads the buffers)
+    void drop() { n_joints = 0; n_skinned = 0; posed = false; h_palette.clear(); d_joints.reset(); d_weights.reset(); d_palette.reset(); d_vertices.reset(); d_normals.reset(); }
+  } skin;
   // textures (renderer.h:372-386): one device blob of texels + descriptors + the sRGB table
   // (which textures can cut, and the opacity classes and micromaps decided from their texels, are the upload's plan: scene_plan_host.h)
   unsigned long long alpha_cell_counts[3] = {0, 0, 0};  // micromap cells of the faces that keep their test; of them: always pass, never pass (fh_alpha_cell_counts)

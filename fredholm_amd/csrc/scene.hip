@@ -1,4 +1,4 @@
-// scene.hip -- the device side of the scene: fh_scene_upload and fh_set_transforms.  An upload is a plan (scene_plan_host.h: everything decided on the host, from
+// scene.hip -- the device side of the scene: fh_scene_upload, fh_set_transforms and the skin (fh_set_skin, fh_set_joint_matrices).  An upload is a plan (scene_plan_host.h: everything decided on the host, from
 // the caller's descriptor alone), then either a refusal that leaves the context as it was or the upload steps below, then the commit.  Mirrors
 // Renderer::load_scene / set_time (fredholm/include/fredholm/renderer.h:361-432).
 #include <hip/hip_runtime.h>
@@ -9,8 +9,10 @@
 #include <utility>
 
 #include "context.h"
+#include "fh_skin.h"
 #include "fh_vec.h"
 #include "scene_plan_host.h"
+#include "skin_plan_host.h"
 
 namespace fh {
 
@@ -53,7 +55,39 @@ __global__ void __launch_bounds__(256) k_face_records(uint32_t nf, const float* 
   r[6] = make_float4(__uint_as_float(mi.x), __uint_as_float(mi.y), 0.0f, 0.0f);
 }
 
-// The world-space face records from the object-space arrays resident on the device and the context's transforms: a frame of an animation (fh_set_transforms)
+// Posed object-space position and normal of every vertex (fh_skin.h: skin_vertex) from the bind arrays, the vertex's four joints and weights and the palette of
+// joint matrices, which is read with plain loads: 48 bytes per joint, shared by every thread that names the joint
+__global__ void __launch_bounds__(256) k_skin_vertices(uint32_t nv, const float* vertices, const float* normals, const uint2* joints, const float4* weights, const float4* palette,
+                                                       float* posed_vertices, float* posed_normals)
+{
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  const float p[3] = {vertices[3 * (size_t)v], vertices[3 * (size_t)v + 1], vertices[3 * (size_t)v + 2]};
+  const float n[3] = {normals[3 * (size_t)v], normals[3 * (size_t)v + 1], normals[3 * (size_t)v + 2]};
+  const uint2 jj = joints[v];
+  const float4 ww = weights[v];
+  const uint32_t j[4] = {jj.x & 0xffffu, jj.x >> 16, jj.y & 0xffffu, jj.y >> 16};
+  const float w[4] = {ww.x, ww.y, ww.z, ww.w};
+  float po[3] = {p[0], p[1], p[2]}, no[3] = {n[0], n[1], n[2]};
+  if (!skin_unskinned(w)) {
+    float m[4][12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const float4 row = palette[3 * (size_t)j[k] + r];
+        m[k][4 * r] = row.x; m[k][4 * r + 1] = row.y; m[k][4 * r + 2] = row.z; m[k][4 * r + 3] = row.w;
+      }
+    float b[12];
+    skin_blend(m[0], m[1], m[2], m[3], w, b);
+    skin_point(b, p, po);
+    skin_normal(b, n, no);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { posed_vertices[3 * (size_t)v + k] = po[k]; posed_normals[3 * (size_t)v + k] = no[k]; }
+}
+
+// The world-space face records from the object-space arrays resident on the device (the posed ones while a skin is posed) and the context's transforms: a frame of an animation (fh_set_transforms)
 // uploads 96 bytes per instance instead of recomputing and re-uploading 112 bytes per face
 int transform_faces(fh_ctx* ctx)
 {
@@ -62,9 +96,11 @@ int transform_faces(fh_ctx* ctx)
   FH_HIP(ctx->d_w2o.ensure(3ull * ni));
   FH_HIP(hipMemcpyAsync(ctx->d_o2w, ctx->h_o2w.data(), 48ull * ni, hipMemcpyHostToDevice, ctx->stream));
   FH_HIP(hipMemcpyAsync(ctx->d_w2o, ctx->h_w2o.data(), 48ull * ni, hipMemcpyHostToDevice, ctx->stream));
+  const float* const vertices = ctx->skin.posed ? ctx->skin.d_vertices.get() : ctx->d_obj_vertices.get();
+  const float* const normals = ctx->skin.posed ? ctx->skin.d_normals.get() : ctx->d_obj_normals.get();
   if (ctx->n_faces)
-    hipLaunchKernelGGL(k_face_records, dim3((ctx->n_faces + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_faces, ctx->d_obj_vertices, ctx->d_obj_normals, ctx->d_obj_texcoords, ctx->d_obj_indices,
-                       ctx->d_face_meta, ctx->d_o2w, ctx->d_w2o, ctx->d_face_rec);
+    hipLaunchKernelGGL(k_face_records, dim3((ctx->n_faces + 255) / 256), dim3(256), 0, ctx->stream, ctx->n_faces, vertices, normals, ctx->d_obj_texcoords.get(), ctx->d_obj_indices.get(),
+                       ctx->d_face_meta.get(), ctx->d_o2w.get(), ctx->d_w2o.get(), ctx->d_face_rec.get());
   FH_HIP(hipGetLastError());
   FH_HIP(hipStreamSynchronize(ctx->stream));  // the host copies of the transforms may change right after this call
   ctx->bvh_valid = false;
@@ -206,6 +242,7 @@ int upload_scene(fh_ctx* ctx, const fh_scene_desc& s, ScenePlan& plan)
 {
   ctx->scene_loaded = false;
   ctx->bvh_valid = false;
+  ctx->skin.drop();  // (a skin belongs to the scene it was set on)
   if (const int rc = upload_textures(ctx, s, plan)) return rc;
   HostScene host = copy_host_scene(ctx, s);
   if (const int rc = upload_geometry(ctx, host, plan)) return rc;
@@ -214,6 +251,21 @@ int upload_scene(fh_ctx* ctx, const fh_scene_desc& s, ScenePlan& plan)
   if (const int rc = transform_faces(ctx)) return rc;
   ctx->scene_loaded = true;
   return FH_OK;
+}
+
+SkinFacts skin_facts(const fh_ctx* ctx) { return SkinFacts{ctx->scene_loaded, (uint32_t)(ctx->h_vertices.size() / 3), ctx->skin.n_joints}; }
+
+// the posed arrays from the bind arrays and the palette the context holds, then the face records from them
+int pose_vertices(fh_ctx* ctx)
+{
+  const uint32_t nv = (uint32_t)(ctx->h_vertices.size() / 3);
+  FH_HIP(hipMemcpyAsync(ctx->skin.d_palette, ctx->skin.h_palette.data(), 48ull * ctx->skin.n_joints, hipMemcpyHostToDevice, ctx->stream));
+  if (nv)
+    hipLaunchKernelGGL(k_skin_vertices, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, nv, ctx->d_obj_vertices.get(), ctx->d_obj_normals.get(), ctx->skin.d_joints.get(), ctx->skin.d_weights.get(),
+                       ctx->skin.d_palette.get(), ctx->skin.d_vertices.get(), ctx->skin.d_normals.get());
+  FH_HIP(hipGetLastError());
+  ctx->skin.posed = true;
+  return transform_faces(ctx);
 }
 
 }  // namespace
@@ -251,6 +303,77 @@ int fh_set_transforms(fh_ctx* ctx, uint32_t n, const float* o2w, const float* w2
   ctx->h_o2w.assign(o2w, o2w + 12ull * n);
   ctx->h_w2o.assign(w2o, w2o + 12ull * n);
   return transform_faces(ctx);  // topology, classes and lights are unchanged: only the world-space records move (and the BVH is refitted)
+}
+
+int fh_set_skin(fh_ctx* ctx, const fh_skin_desc* d)
+{
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_skin(m_, d));
+  if (!ctx) return FH_E_INVALID;
+  if (const char* why = skin_refusal(skin_facts(ctx), d)) return fail(ctx, FH_E_INVALID, why);
+  CTX_CHECK(ctx);
+  (void)drain_passes(ctx, false);  // no pass may still be reading face records that are about to return to the bind pose
+  const bool was_posed = ctx->skin.posed;
+  ctx->skin.drop();
+  // a skin alone moves nothing: the geometry is the bind pose until the first fh_set_joint_matrices, and returns to it when a posed skin goes
+  if (was_posed)
+    if (const int rc = transform_faces(ctx)) return rc;
+  if (d) {
+    fh_ctx::Skin& sk = ctx->skin;
+    const size_t nv = d->n_vertices;
+    FH_HIP(sk.d_joints.alloc(nv));
+    FH_HIP(sk.d_weights.alloc(nv));
+    FH_HIP(sk.d_palette.alloc(3ull * d->n_joints));
+    FH_HIP(sk.d_vertices.alloc(3 * nv));
+    FH_HIP(sk.d_normals.alloc(3 * nv));
+    if (nv) {
+      FH_HIP(hipMemcpy(sk.d_joints, d->joints, 8 * nv, hipMemcpyHostToDevice));
+      FH_HIP(hipMemcpy(sk.d_weights, d->weights, 16 * nv, hipMemcpyHostToDevice));
+    }
+    sk.n_joints = d->n_joints;
+    sk.n_skinned = skin_count_skinned(*d);
+  }
+  return FH_OK;
+}
+
+int fh_set_joint_matrices(fh_ctx* ctx, uint32_t n, const float* m3x4)
+{
+  FH_GROUP_EACH(ctx, kGroupCallScene, fh_set_joint_matrices(m_, n, m3x4));
+  if (!ctx) return FH_E_INVALID;
+  if (const char* why = joint_matrices_refusal(skin_facts(ctx), n, m3x4)) return fail(ctx, FH_E_INVALID, why);
+  CTX_CHECK(ctx);
+  // the pose the context already holds: keep the geometry and the acceleration structure, as fh_set_transforms does
+  if (ctx->skin.posed && ctx->skin.h_palette.size() == 12ull * n && std::memcmp(ctx->skin.h_palette.data(), m3x4, 48ull * n) == 0) return FH_OK;
+  (void)drain_passes(ctx, false);  // no pass may still be reading the face records
+  ctx->skin.h_palette.assign(m3x4, m3x4 + 12ull * n);
+  return pose_vertices(ctx);
+}
+
+int fh_get_skin_info(fh_ctx* ctx, uint32_t* n_joints, uint32_t* n_skinned_vertices, int* posed)
+{
+  FH_GROUP_LEAD(ctx);
+  if (!ctx) return FH_E_INVALID;
+  if (n_joints) *n_joints = ctx->skin.n_joints;
+  if (n_skinned_vertices) *n_skinned_vertices = ctx->skin.n_skinned;
+  if (posed) *posed = ctx->skin.posed ? 1 : 0;
+  return FH_OK;
+}
+
+int fh_get_posed_geometry(fh_ctx* ctx, float* vertices3, float* normals3)
+{
+  FH_GROUP_LEAD(ctx);
+  CTX_CHECK(ctx);
+  if (!ctx->scene_loaded || !vertices3 || !normals3) return fail(ctx, FH_E_INVALID, "fh_get_posed_geometry: no scene / null arrays");
+  const size_t bytes = ctx->h_vertices.size() * sizeof(float);
+  if (!ctx->skin.posed) {
+    std::memcpy(vertices3, ctx->h_vertices.data(), bytes);
+    std::memcpy(normals3, ctx->h_normals.data(), bytes);
+    return FH_OK;
+  }
+  if (bytes) {  // (the call that posed them has synchronised the stream)
+    FH_HIP(hipMemcpy(vertices3, ctx->skin.d_vertices, bytes, hipMemcpyDeviceToHost));
+    FH_HIP(hipMemcpy(normals3, ctx->skin.d_normals, bytes, hipMemcpyDeviceToHost));
+  }
+  return FH_OK;
 }
 
 }  // extern "C"

@@ -121,6 +121,7 @@ EXPORTS = [
     "fh_set_env_sampling", "fh_get_env_sampling", "fh_kat_env_table", "fh_kat_env_sample", "fh_kat_env_pdf", "fh_kat_env_radiance",
     "fh_set_light_sampling", "fh_get_light_sampling", "fh_kat_light_table", "fh_kat_light_pick",
     "fh_set_light_resampling", "fh_get_light_resampling", "fh_kat_light_proxies", "fh_kat_light_resample", "fh_kat_light_usel",
+    "fh_set_skin", "fh_set_joint_matrices", "fh_get_skin_info", "fh_get_posed_geometry",
     "fh_ctx_create_group", "fh_ctx_group_size", "fh_ctx_member", "fh_group_set_gather_layers", "fh_group_gather_times", "fh_group_shard_layout",
 ]
 
@@ -205,6 +206,11 @@ LIGHT_CANDIDATES_DEFAULT = 4  # FH_LIGHT_CANDIDATES_DEFAULT
 LIGHT_CANDIDATES = (1, 2, 4, 8, 16)
 
 
+class SkinDescC(C.Structure):
+    """fh_skin_desc (include/fredholm_hip.h)"""
+    _fields_ = [("n_vertices", C.c_uint32), ("n_joints", C.c_uint32), ("joints", C.c_void_p), ("weights", C.c_void_p)]
+
+
 class AutoExposureStateC(C.Structure):
     """fh_auto_exposure_state (include/fredholm_hip.h)"""
     _fields_ = [("ev", C.c_float), ("target_ev", C.c_float), ("mean_log2", C.c_float), ("metered", C.c_uint32), ("unmetered", C.c_uint32), ("frames", C.c_uint32)]
@@ -264,6 +270,10 @@ SIGNATURES = {
     "fh_kat_light_resample": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fh_kat_light_usel": [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "fh_kat_chief_rays": [C.c_void_p, C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_void_p],
+    "fh_set_skin": [C.c_void_p, C.POINTER(SkinDescC)],
+    "fh_set_joint_matrices": [C.c_void_p, C.c_uint32, C.c_void_p],
+    "fh_get_skin_info": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)],
+    "fh_get_posed_geometry": [C.c_void_p, C.c_void_p, C.c_void_p],
     "fh_ctx_create_group": [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)],
     "fh_ctx_group_size": [C.c_void_p, C.POINTER(C.c_uint32)],
     "fh_ctx_member": [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)],

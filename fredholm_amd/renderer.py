@@ -300,6 +300,14 @@ class Renderer:
         d.textures = C.cast(tex_arr, C.c_void_p) if textures else None
         self._keep = (v, n, t, idx, mid, mats, inst, o2w, w2o, tex_arr, tex_keep)
         self._ck(N.lib().fh_scene_upload(self._ctx, C.byref(d)), "fh_scene_upload")
+        if scene.get("joints") is not None:  # a skinned scene: the skin, and the pose where the scene brings one
+            jm = scene.get("joint_matrices")
+            n_joints = scene.get("n_joints")
+            if n_joints is None:
+                n_joints = np.asarray(jm).reshape(-1, 12).shape[0] if jm is not None else int(np.asarray(scene["joints"]).max()) + 1
+            self.set_skin(scene["joints"], scene["weights"], n_joints)
+            if jm is not None:
+                self.set_joint_matrices(jm)
 
     def build_gas(self):
         """renderer.h:434-496; the whole acceleration structure is built by build_ias' counterpart"""
@@ -316,6 +324,42 @@ class Renderer:
         o = np.ascontiguousarray(object_to_world, dtype=np.float32).reshape(-1, 12)
         w = np.ascontiguousarray(world_to_object, dtype=np.float32).reshape(-1, 12)
         self._ck(N.lib().fh_set_transforms(self._ctx, C.c_uint32(o.shape[0]), N.ptr(o), N.ptr(w)), "fh_set_transforms")
+
+    # -- skeletal skinning (an extension beyond the reference class; include/fredholm_hip.h: fh_skin_desc)
+    def set_skin(self, joints, weights, n_joints):
+        """four joint indices (into one palette of n_joints matrices) and four weights per vertex of the loaded scene; geometry stays in the bind pose until
+        set_joint_matrices.  Vertices whose four weights are 0 are unskinned."""
+        j = np.asarray(joints)
+        if j.size and (j.min() < 0 or j.max() > 65535):
+            raise N.FredholmError("set_skin: a joint index does not fit 16 bits")
+        j = np.ascontiguousarray(j, dtype=np.uint16).reshape(-1, 4)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 4)
+        if j.shape[0] != w.shape[0]:
+            raise N.FredholmError("set_skin: joints and weights hold four entries per vertex each")
+        d = N.SkinDescC(j.shape[0], int(n_joints), N.ptr(j), N.ptr(w))
+        self._ck(N.lib().fh_set_skin(self._ctx, C.byref(d)), "fh_set_skin")
+
+    def clear_skin(self):
+        """geometry returns to the bind pose, bit for bit"""
+        self._ck(N.lib().fh_set_skin(self._ctx, None), "fh_set_skin")
+
+    def set_joint_matrices(self, m):
+        """the pose: one row-major 3 x 4 matrix per joint of the skin, in the object space of the skinned vertices; call build_ias afterwards"""
+        m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 12)
+        self._ck(N.lib().fh_set_joint_matrices(self._ctx, C.c_uint32(m.shape[0]), N.ptr(m)), "fh_set_joint_matrices")
+
+    def skin_info(self):
+        """(n_joints, vertices with a non-zero weight, posed); n_joints 0: no skin"""
+        nj, nv, posed = C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+        self._ck(N.lib().fh_get_skin_info(self._ctx, C.byref(nj), C.byref(nv), C.byref(posed)), "fh_get_skin_info")
+        return int(nj.value), int(nv.value), bool(posed.value)
+
+    def posed_geometry(self):
+        """(vertices, normals) of the loaded scene as the face records are derived from them: [n_vertices, 3] float32 each, the bind arrays when nothing is posed"""
+        nv = self._keep[0].shape[0]
+        v, n = np.empty((nv, 3), np.float32), np.empty((nv, 3), np.float32)
+        self._ck(N.lib().fh_get_posed_geometry(self._ctx, N.ptr(v), N.ptr(n)), "fh_get_posed_geometry")
+        return v, n
 
     def n_lights(self):
         out = C.c_uint32()
@@ -388,6 +432,8 @@ class Renderer:
         self.m_scene.update_animation(time)
         o2w, w2o = self.m_scene.transforms_3x4()
         self.set_transforms(o2w, w2o)
+        if getattr(self.m_scene, "m_skins", None):
+            self.set_joint_matrices(self.m_scene.joint_matrices_3x4())
         self.build_ias()
 
     def render(self, camera, bg_color, render_layer, n_samples, max_depth):

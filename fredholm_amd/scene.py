@@ -15,6 +15,9 @@ Reference behaviours kept on purpose (each is what the reference does, file:line
     T * R * S of the interpolated keys (scene.cpp:862-893);
   * key interpolation mixes with h = t - input[idx0], NOT divided by the key interval (scene.h:164-178), with
     t = fmod(time, last key).
+Beyond the reference: a file with a non-empty `skins` array also yields per-vertex joints and weights (JOINTS_0 / WEIGHTS_0 of the primitives of nodes with `mesh`
+and `skin`), one palette over all skins (m_skins, joint_matrices_3x4) and one Animation per animated node, which may then be a joint below a root.  A file without
+`skins` loads exactly as before.
 Deviation: Node::camera_id is never initialised in the reference (scene.cpp:669-672, undefined behaviour); here it is the
 node's `camera` property or -1.
 """
@@ -101,6 +104,15 @@ class Node:
         self.transform = _identity()
         self.camera_id = -1
         self.submesh_id = -1
+        self.global_transform = _identity()  # parent chain times transform, kept by update_transform (the joints of a skin need it)
+
+
+class Skin:
+    def __init__(self):
+        self.joints = []        # Node per joint
+        self.inverse_bind = []  # 4x4 row-major nested lists (double) per joint
+        self.base = 0           # index of the skin's first joint in the scene's palette
+        self.mesh_node = None   # the first node that uses the skin: the joint matrices are in its object space
 
 
 class Animation:
@@ -135,6 +147,9 @@ class Scene:
         self.m_transforms = []         # 4x4 row-major nested lists (double)
         self.m_nodes = []
         self.m_animations = []
+        self.m_joints = np.zeros((0, 4), np.uint16)   # per vertex: indices into the palette of all skins (palette base of the skin + local index)
+        self.m_weights = np.zeros((0, 4), np.float32)  # per vertex; zero for the vertices of unskinned meshes
+        self.m_skins = []
 
     def is_valid(self):
         return len(self.m_vertices) > 0 and len(self.m_indices) > 0 and len(self.m_normals) == len(self.m_vertices)
@@ -151,8 +166,11 @@ class Scene:
         else:
             raise ValueError(f"failed to load {filepath}: unsupported extension")
 
-    def _append(self, vertices, normals, texcoords, indices, material_ids, instance_id):
+    def _append(self, vertices, normals, texcoords, indices, material_ids, instance_id, joints=None, weights=None):
         base = len(self.m_vertices)
+        n_new = len(np.asarray(vertices, np.float32).reshape(-1, 3))
+        self.m_joints = np.concatenate([self.m_joints, np.zeros((n_new, 4), np.uint16) if joints is None else np.asarray(joints, np.uint16).reshape(-1, 4)])
+        self.m_weights = np.concatenate([self.m_weights, np.zeros((n_new, 4), np.float32) if weights is None else np.asarray(weights, np.float32).reshape(-1, 4)])
         self.m_vertices = np.concatenate([self.m_vertices, np.asarray(vertices, np.float32).reshape(-1, 3)])
         self.m_normals = np.concatenate([self.m_normals, np.asarray(normals, np.float32).reshape(-1, 3)])
         self.m_texcoords = np.concatenate([self.m_texcoords, np.asarray(texcoords, np.float32).reshape(-1, 2)])
@@ -246,10 +264,41 @@ class Scene:
             image = model["images"][texture["source"]]
             self.m_textures.append({"rgba8": image_io.load_texture(os.path.join(folder, image["uri"]), flip_vertically=True), "srgb": False})
 
+        # skins: the palette bases first, so that the vertices of a skinned mesh can name their joints in the palette of all skins
+        gskins = model.get("skins", [])
+        skin_base, skin_count = [], []
+        for gs in gskins:
+            skin_base.append(sum(skin_count) + sum(len(sk.joints) for sk in self.m_skins))
+            skin_count.append(len(gs["joints"]))
+        by_idx = {}     # glTF node index -> Node, for the nodes reachable from the scene's roots
+        skin_user = {}  # skin index -> the first Node that uses it
+
+        def read_skin_attributes(prim, skin_id, n_pos):
+            attrs = prim["attributes"]
+            if ("JOINTS_0" in attrs) != ("WEIGHTS_0" in attrs):
+                raise ValueError("JOINTS_0 and WEIGHTS_0 must come together")
+            if "JOINTS_0" not in attrs:
+                raise ValueError("a primitive of a skinned node has no JOINTS_0 / WEIGHTS_0")
+            wacc = model["accessors"][attrs["WEIGHTS_0"]]
+            if wacc["componentType"] != 5126:
+                raise ValueError("normalised-integer WEIGHTS_0 is not supported")
+            wts, n_w = read(attrs["WEIGHTS_0"], np.float32, 4, 16, "weights stride is not float4")
+            jacc = model["accessors"][attrs["JOINTS_0"]]
+            if jacc["componentType"] not in (5121, 5123):
+                raise ValueError("JOINTS_0 is neither unsigned byte nor unsigned short")
+            jdt = np.uint8 if jacc["componentType"] == 5121 else np.uint16
+            jts, n_j = read(attrs["JOINTS_0"], jdt, 4, 4 * np.dtype(jdt).itemsize, "joints are not tightly packed")
+            if n_w != n_pos or n_j != n_pos:
+                raise ValueError("JOINTS_0 / WEIGHTS_0 count is not the vertex count")
+            if n_j and int(jts.max()) >= skin_count[skin_id]:
+                raise ValueError("joint index outside the skin's joints")
+            return (jts.astype(np.uint32) + np.uint32(skin_base[skin_id])).astype(np.uint16), wts
+
         def load_node(node_idx):
             node = model["nodes"][node_idx]
             n = Node()
             n.idx = node_idx
+            by_idx[node_idx] = n
             t = [float(v) for v in node.get("translation", [0, 0, 0])]
             r = node.get("rotation")
             q = [1.0, 0.0, 0.0, 0.0] if r is None else [float(r[3]), float(r[0]), float(r[1]), float(r[2])]
@@ -265,6 +314,9 @@ class Scene:
                 mesh = model["meshes"][node["mesh"]]
                 n.submesh_id = len(self.m_submesh_offsets)
                 prev = len(self.m_indices)
+                skin_id = node.get("skin", -1) if gskins else -1
+                if skin_id >= 0:
+                    skin_user.setdefault(skin_id, n)
                 for prim in mesh["primitives"]:
                     idx, n_idx = read(prim["indices"], np.uint16, 1, 2, "indices stride is not ushort")
                     attrs = prim["attributes"]
@@ -274,7 +326,8 @@ class Scene:
                     uv = np.stack([uv[:, 0], np.float32(1.0) - uv[:, 1]], axis=1)
                     tri = idx[: (n_idx // 3) * 3].astype(np.uint32).reshape(-1, 3)
                     material = np.uint32(prim.get("material", -1) & 0xFFFFFFFF) + np.uint32(mat_base if prim.get("material", -1) >= 0 else 0)
-                    self._append(pos, nrm, uv, tri, np.full(len(tri), material, np.uint32), len(self.m_submesh_offsets))
+                    jts, wts = read_skin_attributes(prim, skin_id, n_pos) if skin_id >= 0 else (None, None)
+                    self._append(pos, nrm, uv, tri, np.full(len(tri), material, np.uint32), len(self.m_submesh_offsets), jts, wts)
                 self.m_submesh_offsets.append(prev)
                 self.m_submesh_n_faces.append(len(self.m_indices) - prev)
             for child in node.get("children", []):
@@ -286,42 +339,71 @@ class Scene:
             self.m_nodes.append(load_node(node_idx))
         while len(self.m_transforms) < len(self.m_submesh_offsets):
             self.m_transforms.append(_identity())
+        joint_nodes = {}
+        for k, gs in enumerate(gskins):
+            sk = Skin()
+            sk.base = skin_base[k]
+            for j in gs["joints"]:
+                if j not in by_idx:
+                    raise ValueError("a joint of a skin is not a node of the scene")
+                sk.joints.append(by_idx[j])
+                joint_nodes[j] = by_idx[j]
+            if "inverseBindMatrices" in gs:
+                acc = model["accessors"][gs["inverseBindMatrices"]]
+                data, start, stride, count = get_buffer(gs["inverseBindMatrices"])
+                if acc["componentType"] != 5126 or acc["type"] != "MAT4" or stride != 64 or count != len(sk.joints):
+                    raise ValueError("inverseBindMatrices must be tightly packed float MAT4, one per joint")
+                ibm = np.frombuffer(data, dtype=np.float32, count=16 * count, offset=start).reshape(count, 16)  # column-major
+                sk.inverse_bind = [[[float(m[4 * c + r]) for c in range(4)] for r in range(4)] for m in ibm]
+            else:
+                sk.inverse_bind = [_identity() for _ in sk.joints]
+            sk.mesh_node = skin_user.get(k)
+            self.m_skins.append(sk)
         self.update_transform()
 
         for animation in model.get("animations", []):
-            anim = Animation()
-            target = animation["channels"][0]["target"]["node"]
-            anim.node = next((n for n in self.m_nodes[first_new_node:] if n.idx == target), None)  # root nodes only (scene.cpp:900-919)
-            if anim.node is None:
-                raise ValueError("invalid target node")
-            for channel in animation["channels"]:
-                sampler = animation["samplers"][channel["sampler"]]
-                path = channel["target"]["path"]
-                inp, n_in = read(sampler["input"], np.float32, 1, 4, "unsupported animation input")
-                data, start, stride, n_out = get_buffer(sampler["output"])
-                if n_in != n_out:
-                    raise ValueError("animation input size is not equal to output size")
-                per = {"translation": 3, "rotation": 4, "scale": 3}.get(path)
-                if per is None:
-                    continue
-                if stride != 4 * per:
-                    raise ValueError("invalid output stride")
-                out = np.frombuffer(data, dtype=np.float32, count=n_out * per, offset=start).reshape(n_out, per)
-                if path == "translation":
-                    anim.translation_input += [float(v) for v in inp]
-                    anim.translation_output += [[float(v) for v in o] for o in out]
-                elif path == "rotation":
-                    anim.rotation_input += [float(v) for v in inp]
-                    anim.rotation_output += [[float(o[3]), float(o[0]), float(o[1]), float(o[2])] for o in out]
-                else:
-                    anim.scale_input += [float(v) for v in inp]
-                    anim.scale_output += [[float(v) for v in o] for o in out]
-            self.m_animations.append(anim)
+            roots = {n.idx: n for n in reversed(self.m_nodes[first_new_node:])}
+            if gskins:  # one record per distinct target node, in order of first appearance; a target is a root node or a joint of one of the file's skins
+                targets = list(dict.fromkeys(ch["target"]["node"] for ch in animation["channels"]))
+            else:       # the node named by the FIRST channel drives them all, and must be a root node (scene.cpp:900-919)
+                targets = [animation["channels"][0]["target"]["node"]]
+            for target in targets:
+                anim = Animation()
+                anim.node = roots.get(target, joint_nodes.get(target))
+                if anim.node is None:
+                    raise ValueError("invalid target node")
+                self._read_channels(anim, [ch for ch in animation["channels"] if not gskins or ch["target"]["node"] == target], animation, read, get_buffer)
+                self.m_animations.append(anim)
+
+    def _read_channels(self, anim, channels, animation, read, get_buffer):
+        for channel in channels:
+            sampler = animation["samplers"][channel["sampler"]]
+            path = channel["target"]["path"]
+            inp, n_in = read(sampler["input"], np.float32, 1, 4, "unsupported animation input")
+            data, start, stride, n_out = get_buffer(sampler["output"])
+            if n_in != n_out:
+                raise ValueError("animation input size is not equal to output size")
+            per = {"translation": 3, "rotation": 4, "scale": 3}.get(path)
+            if per is None:
+                continue
+            if stride != 4 * per:
+                raise ValueError("invalid output stride")
+            out = np.frombuffer(data, dtype=np.float32, count=n_out * per, offset=start).reshape(n_out, per)
+            if path == "translation":
+                anim.translation_input += [float(v) for v in inp]
+                anim.translation_output += [[float(v) for v in o] for o in out]
+            elif path == "rotation":
+                anim.rotation_input += [float(v) for v in inp]
+                anim.rotation_output += [[float(o[3]), float(o[0]), float(o[1]), float(o[2])] for o in out]
+            else:
+                anim.scale_input += [float(v) for v in inp]
+                anim.scale_output += [[float(v) for v in o] for o in out]
 
     # ------------------------------------------------------------------ scene.cpp:836-898
     def update_transform(self):
         def visit(node, parent):
             m = _matmul(parent, node.transform)
+            node.global_transform = m
             if node.camera_id != -1:
                 self.m_has_camera_transform = True
                 self.m_camera_transform = m
@@ -346,6 +428,20 @@ class Scene:
         w2o = np.asarray([[affine_inverse(m)[r][c] for r in range(3) for c in range(4)] for m in self.m_transforms], dtype=np.float32).reshape(-1, 12)
         return o2w, w2o
 
+    def joint_matrices_3x4(self):
+        """the palette [joints of all skins, 12] float32: inverse(global(mesh node)) * global(joint node) * inverseBind per joint, multiplied in double and rounded
+        once.  The instance's own object_to_world stays the mesh node's global transform, so world space is global(joint) * inverseBind as glTF prescribes"""
+        rows = []
+        for sk in self.m_skins:
+            to_object = affine_inverse(sk.mesh_node.global_transform) if sk.mesh_node is not None else _identity()
+            for node, ib in zip(sk.joints, sk.inverse_bind):
+                m = _matmul(_matmul(to_object, node.global_transform), ib)
+                rows.append([m[r][c] for r in range(3) for c in range(4)])
+        return np.asarray(rows, dtype=np.float32).reshape(-1, 12)
+
+    def n_joints(self):
+        return sum(len(sk.joints) for sk in self.m_skins)
+
     def camera_transform_3x4(self):
         return np.asarray([[self.m_camera_transform[r][c] for c in range(4)] for r in range(3)], dtype=np.float32)
 
@@ -357,4 +453,6 @@ class Scene:
              "materials": self.m_materials, "instance_ids": self.m_instance_ids, "object_to_world": o2w, "world_to_object": w2o}
         if self.m_textures:
             d["textures"] = self.m_textures
+        if self.m_skins:
+            d["joints"], d["weights"], d["n_joints"], d["joint_matrices"] = self.m_joints, self.m_weights, self.n_joints(), self.joint_matrices_3x4()
         return d

@@ -135,8 +135,19 @@ class Renderer
     std::vector<float> o2w, w2o;
     m_scene.transforms_3x4(o2w, w2o);
     if (!o2w.empty()) cwl::check(m_ctx, fh_set_transforms(m_ctx, uint32_t(o2w.size() / 12), o2w.data(), w2o.data()), "fh_set_transforms");
+    if (!m_scene.m_skins.empty()) set_joint_matrices(m_scene.joint_matrices_3x4());
     build_ias();
   }
+  // skeletal skinning (no counterpart in the reference, whose glTF reader loads no skins; include/fredholm_hip.h: fh_skin_desc).  load_scene and set_time do both for a
+  // file with skins; joints / weights: four per vertex of the loaded scene, matrices: row-major 3 x 4 per joint.  Call build_ias after set_joint_matrices
+  void set_skin(const std::vector<std::array<uint16_t, 4>>& joints, const std::vector<std::array<float, 4>>& weights, uint32_t n_joints)
+  {
+    if (joints.size() != weights.size()) throw std::runtime_error("set_skin: joints and weights hold four entries per vertex each");
+    const fh_skin_desc d = {uint32_t(joints.size()), n_joints, reinterpret_cast<const uint16_t*>(joints.data()), reinterpret_cast<const float*>(weights.data())};
+    cwl::check(m_ctx, fh_set_skin(m_ctx, &d), "fh_set_skin");
+  }
+  void clear_skin() { cwl::check(m_ctx, fh_set_skin(m_ctx, nullptr), "fh_set_skin"); }
+  void set_joint_matrices(const std::vector<float>& m3x4) { cwl::check(m_ctx, fh_set_joint_matrices(m_ctx, uint32_t(m3x4.size() / 12), m3x4.data()), "fh_set_joint_matrices"); }
   void set_resolution(uint32_t width, uint32_t height)  // renderer.h:642-648
   {
     m_width = width;
@@ -247,6 +258,10 @@ class Renderer
     d.n_textures = uint32_t(tex.size());
     d.textures = tex.empty() ? nullptr : tex.data();
     cwl::check(m_ctx, fh_scene_upload(m_ctx, &d), "fh_scene_upload");
+    if (!m_scene.m_skins.empty()) {  // the skin, and the pose the nodes have now
+      set_skin(m_scene.m_joints, m_scene.m_weights, m_scene.n_joints());
+      set_joint_matrices(m_scene.joint_matrices_3x4());
+    }
   }
   fh_ctx* m_ctx = nullptr;
   uint32_t m_width = 0, m_height = 0;

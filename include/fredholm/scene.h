@@ -8,7 +8,9 @@
 // image_io.h with the reference's conventions (scene.cpp:7-37,144-153: vertical flip, one Texture per distinct file name, its
 // first use fixes COLOR / NONCOLOR).  glTF (.gltf, JSON + external or data-URI buffers) goes through json.h and follows
 // scene.cpp:445-860 including its quirks (listed in fredholm_amd/scene.py, the Python twin of this file); scene-graph math is
-// done in double and rounded to float once, identically in both front ends.  Not supported in this build: JPEG files, .glb.
+// done in double and rounded to float once, identically in both front ends.  Beyond the reference: a file with a non-empty
+// `skins` array also yields m_joints / m_weights, m_skins and joint_matrices_3x4(), and one Animation per animated node, which may
+// then be a joint below a root; a file without `skins` loads exactly as before.  Not supported in this build: JPEG files, .glb.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -131,6 +133,17 @@ struct Node {
   Mat4d transform;
   int camera_id = -1;
   int submesh_id = -1;
+  Mat4d global;  // parent chain times transform, kept by update_transform (the joints of a skin need it)
+};
+
+// where a node is: its root's index in Scene::m_nodes, then the child index at every level below
+using NodePath = std::vector<int>;
+
+struct Skin {
+  std::vector<NodePath> joints;
+  std::vector<Mat4d> inverse_bind;  // per joint
+  uint32_t base = 0;                // index of the skin's first joint in the scene's palette
+  NodePath mesh_node;               // the first node that uses the skin (empty: none): the joint matrices are in its object space
 };
 
 struct Animation {
@@ -156,6 +169,9 @@ struct Scene {
   std::vector<Mat4d> m_transforms_exact = {};  // the same matrices before rounding to float (scene-graph products are done in double)
   std::vector<Node> m_nodes = {};
   std::vector<Animation> m_animations = {};
+  std::vector<std::array<uint16_t, 4>> m_joints = {};  // per vertex: indices into the palette of all skins (palette base of the skin + local index)
+  std::vector<std::array<float, 4>> m_weights = {};    // per vertex; zero for the vertices of unskinned meshes
+  std::vector<Skin> m_skins = {};
 
   bool is_valid() const { return !m_vertices.empty() && !m_indices.empty() && !m_normals.empty() && m_vertices.size() == m_normals.size(); }
 
@@ -163,7 +179,8 @@ struct Scene {
   {
     m_vertices.clear(); m_indices.clear(); m_texcoords.clear(); m_normals.clear(); m_material_ids.clear(); m_materials.clear(); m_textures.clear();
     m_submesh_offsets.clear(); m_submesh_n_faces.clear(); m_instance_ids.clear(); m_transforms.clear(); m_transforms_exact.clear();
-    m_nodes.clear(); m_animations.clear(); m_animation_targets.clear();
+    m_nodes.clear(); m_animations.clear(); m_animation_targets.clear(); m_animation_paths.clear();
+    m_joints.clear(); m_weights.clear(); m_skins.clear();
     m_has_camera_transform = false;
     m_camera_transform = Mat4{};
   }
@@ -249,6 +266,8 @@ struct Scene {
     m_submesh_n_faces.push_back(uint(m_indices.size() - first_face));
     m_transforms.push_back(Mat4{});  // scene.cpp:419-421: one identity per shape; every .obj face uses instance 0 (:424-428)
     m_transforms_exact.push_back(Mat4d{});
+    m_joints.resize(m_vertices.size(), std::array<uint16_t, 4>{0, 0, 0, 0});
+    m_weights.resize(m_vertices.size(), std::array<float, 4>{0, 0, 0, 0});
   }
 
 
@@ -312,10 +331,55 @@ struct Scene {
         m_textures.push_back(Texture(folder / image.at("uri").string(), TextureType::NONCOLOR));  // scene.cpp:560-567
       }
 
-    std::function<Node(int)> load_node = [&](int node_idx) {
+    // skins: the palette bases first, so that the vertices of a skinned mesh can name their joints in the palette of all skins
+    const json::Value no_skins;
+    const std::vector<json::Value>& gskins = model.has("skins") ? model.at("skins").arr : no_skins.arr;
+    std::vector<uint32_t> skin_base, skin_count;
+    {
+      uint32_t next = 0;
+      for (const Skin& sk : m_skins) next += uint32_t(sk.joints.size());
+      for (const json::Value& gs : gskins) { skin_base.push_back(next); skin_count.push_back(uint32_t(gs.at("joints").arr.size())); next += skin_count.back(); }
+    }
+    std::map<int, NodePath> by_idx;     // glTF node index -> where the node is, for the nodes reachable from the scene's roots
+    std::map<int, NodePath> skin_user;  // skin index -> the first node that uses it
+    auto read_skin_attributes = [&](const json::Value& prim, int skin_id, int n_pos) {
+      const json::Value& attrs = prim.at("attributes");
+      if (attrs.has("JOINTS_0") != attrs.has("WEIGHTS_0")) throw std::runtime_error("JOINTS_0 and WEIGHTS_0 must come together");
+      if (!attrs.has("JOINTS_0")) throw std::runtime_error("a primitive of a skinned node has no JOINTS_0 / WEIGHTS_0");
+      if (model.at("accessors").at(size_t(attrs.at("WEIGHTS_0").integer())).at("componentType").integer() != 5126) throw std::runtime_error("normalised-integer WEIGHTS_0 is not supported");
+      const View wv = get_buffer(attrs.at("WEIGHTS_0").integer());
+      if (wv.stride != 16) throw std::runtime_error("weights stride is not float4");
+      const int jtype = model.at("accessors").at(size_t(attrs.at("JOINTS_0").integer())).at("componentType").integer();
+      if (jtype != 5121 && jtype != 5123) throw std::runtime_error("JOINTS_0 is neither unsigned byte nor unsigned short");
+      const int jsize = jtype == 5121 ? 1 : 2;
+      const View jv = get_buffer(attrs.at("JOINTS_0").integer());
+      if (jv.stride != 4 * jsize) throw std::runtime_error("joints are not tightly packed");
+      if (wv.count != n_pos || jv.count != n_pos) throw std::runtime_error("JOINTS_0 / WEIGHTS_0 count is not the vertex count");
+      need(wv, size_t(wv.count) * 16); need(jv, size_t(jv.count) * 4 * size_t(jsize));
+      for (int i = 0; i < 4 * jv.count; ++i) {
+        uint16_t j = jv.data[size_t(jsize) * i];
+        if (jsize == 2) std::memcpy(&j, jv.data + 2 * size_t(i), 2);
+        if (j >= skin_count[size_t(skin_id)]) throw std::runtime_error("joint index outside the skin's joints");
+      }
+      for (int i = 0; i < n_pos; ++i) {
+        std::array<uint16_t, 4> j;
+        std::array<float, 4> w;
+        for (int k = 0; k < 4; ++k) {
+          uint16_t local = jv.data[size_t(jsize) * (4 * i + k)];
+          if (jsize == 2) std::memcpy(&local, jv.data + 2 * size_t(4 * i + k), 2);
+          j[size_t(k)] = uint16_t(local + skin_base[size_t(skin_id)]);
+          std::memcpy(&w[size_t(k)], wv.data + 16 * size_t(i) + 4 * size_t(k), 4);
+        }
+        m_joints.push_back(j);
+        m_weights.push_back(w);
+      }
+    };
+
+    std::function<Node(int, const NodePath&)> load_node = [&](int node_idx, const NodePath& path) {
       const json::Value& node = model.at("nodes").at(size_t(node_idx));
       Node n;
       n.idx = node_idx;
+      by_idx[node_idx] = path;
       double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}, sc[3] = {1, 1, 1};
       if (node.has("translation")) for (int k = 0; k < 3; ++k) t[k] = double(float(node.at("translation").at(size_t(k)).number()));
       if (node.has("rotation")) {
@@ -332,8 +396,12 @@ struct Scene {
         const json::Value& mesh = model.at("meshes").at(size_t(node.at("mesh").integer()));
         n.submesh_id = int(m_submesh_offsets.size());
         const size_t prev = m_indices.size();
+        const int skin_id = gskins.empty() ? -1 : node.integer_or("skin", -1);
+        if (skin_id >= 0 && !skin_user.count(skin_id)) skin_user[skin_id] = path;
         for (const json::Value& prim : mesh.at("primitives").arr) {
           const uint base = uint(m_vertices.size());
+          m_joints.resize(base, std::array<uint16_t, 4>{0, 0, 0, 0});
+          m_weights.resize(base, std::array<float, 4>{0, 0, 0, 0});
           const View iv = get_buffer(prim.at("indices").integer());
           if (iv.stride != 2) throw std::runtime_error("indices stride is not ushort");
           need(iv, size_t(iv.count) * 2);
@@ -349,6 +417,7 @@ struct Scene {
           for (int i = 0; i < pv.count; ++i) m_vertices.push_back(make_float3(f32(pv.data + 12 * i), f32(pv.data + 12 * i + 4), f32(pv.data + 12 * i + 8)));
           for (int i = 0; i < nv.count; ++i) m_normals.push_back(make_float3(f32(nv.data + 12 * i), f32(nv.data + 12 * i + 4), f32(nv.data + 12 * i + 8)));
           for (int i = 0; i < tv.count; ++i) m_texcoords.push_back(float2{f32(tv.data + 8 * i), 1.0f - f32(tv.data + 8 * i + 4)});
+          if (skin_id >= 0) read_skin_attributes(prim, skin_id, pv.count);
           const int material = prim.integer_or("material", -1);
           for (int i = 0; i < iv.count / 3; ++i) {
             uint16_t k[3];
@@ -362,52 +431,98 @@ struct Scene {
         m_submesh_n_faces.push_back(uint(m_indices.size() - prev));
       }
       if (node.has("children"))
-        for (const json::Value& c : node.at("children").arr) n.children.push_back(load_node(c.integer()));
+        for (const json::Value& c : node.at("children").arr) {
+          NodePath child = path;
+          child.push_back(int(n.children.size()));
+          n.children.push_back(load_node(c.integer(), child));
+        }
       return n;
     };
     const size_t first_new_node = m_nodes.size();
-    for (const json::Value& root : model.at("scenes").at(0).at("nodes").arr) m_nodes.push_back(load_node(root.integer()));
+    for (const json::Value& root : model.at("scenes").at(0).at("nodes").arr) m_nodes.push_back(load_node(root.integer(), NodePath{int(m_nodes.size())}));
     m_transforms.resize(m_submesh_offsets.size());
     m_transforms_exact.resize(m_submesh_offsets.size());
+    m_joints.resize(m_vertices.size(), std::array<uint16_t, 4>{0, 0, 0, 0});
+    m_weights.resize(m_vertices.size(), std::array<float, 4>{0, 0, 0, 0});
+    std::map<int, NodePath> joint_nodes;
+    for (size_t k = 0; k < gskins.size(); ++k) {
+      const json::Value& gs = gskins[k];
+      Skin sk;
+      sk.base = skin_base[k];
+      for (const json::Value& j : gs.at("joints").arr) {
+        if (!by_idx.count(j.integer())) throw std::runtime_error("a joint of a skin is not a node of the scene");
+        sk.joints.push_back(by_idx[j.integer()]);
+        joint_nodes[j.integer()] = by_idx[j.integer()];
+      }
+      if (gs.has("inverseBindMatrices")) {
+        const json::Value& acc = model.at("accessors").at(size_t(gs.at("inverseBindMatrices").integer()));
+        const View v = get_buffer(gs.at("inverseBindMatrices").integer());
+        if (acc.at("componentType").integer() != 5126 || acc.at("type").string() != "MAT4" || v.stride != 64 || size_t(v.count) != sk.joints.size())
+          throw std::runtime_error("inverseBindMatrices must be tightly packed float MAT4, one per joint");
+        need(v, size_t(v.count) * 64);
+        for (int i = 0; i < v.count; ++i) {
+          Mat4d ib;  // column-major in the file
+          for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) { float f; std::memcpy(&f, v.data + 64 * size_t(i) + 4 * size_t(4 * c + r), 4); ib.m[r][c] = double(f); }
+          sk.inverse_bind.push_back(ib);
+        }
+      } else
+        sk.inverse_bind.assign(sk.joints.size(), Mat4d{});
+      if (skin_user.count(int(k))) sk.mesh_node = skin_user[int(k)];
+      m_skins.push_back(sk);
+    }
     update_transform();
 
     if (model.has("animations"))
       for (const json::Value& animation : model.at("animations").arr) {
-        Animation anim;
-        const int target = animation.at("channels").at(0).at("target").at("node").integer();
-        int target_root = -1;  // root nodes only (find_node_node drops the result of its recursion, scene.cpp:900-919)
-        for (size_t k = first_new_node; k < m_nodes.size(); ++k)
-          if (m_nodes[k].idx == target) { target_root = int(k); break; }
-        if (target_root < 0) throw std::runtime_error("invalid target node");
-        for (const json::Value& channel : animation.at("channels").arr) {
-          const json::Value& sampler = animation.at("samplers").at(size_t(channel.at("sampler").integer()));
-          const std::string path = channel.at("target").at("path").string();
-          const View in = get_buffer(sampler.at("input").integer());
-          if (in.stride != 4) throw std::runtime_error("unsupported animation input");
-          const View out = get_buffer(sampler.at("output").integer());
-          if (in.count != out.count) throw std::runtime_error("animation input size is not equal to output size");
-          const int per = path == "rotation" ? 4 : ((path == "translation" || path == "scale") ? 3 : 0);
-          if (per == 0) continue;
-          if (out.stride != 4 * per) throw std::runtime_error("invalid output stride");
-          need(in, size_t(in.count) * 4); need(out, size_t(out.count) * 4 * per);
-          auto f32 = [](const uint8_t* p) { float v; std::memcpy(&v, p, 4); return v; };
-          for (int i = 0; i < in.count; ++i) {
-            const float key = f32(in.data + 4 * i);
-            const uint8_t* o = out.data + size_t(4 * per) * i;
-            if (path == "translation") { anim.translation_input.push_back(key); anim.translation_output.push_back({double(f32(o)), double(f32(o + 4)), double(f32(o + 8))}); }
-            else if (path == "scale") { anim.scale_input.push_back(key); anim.scale_output.push_back({double(f32(o)), double(f32(o + 4)), double(f32(o + 8))}); }
-            else { anim.rotation_input.push_back(key); anim.rotation_output.push_back({double(f32(o + 12)), double(f32(o)), double(f32(o + 4)), double(f32(o + 8))}); }
+        // without skins the node named by the FIRST channel drives every channel and must be a root node (find_node_node drops the result of its recursion,
+        // scene.cpp:900-919); with skins: one record per distinct target node, in order of first appearance, each a root node or a joint of one of the file's skins
+        std::vector<int> targets;
+        if (gskins.empty()) targets.push_back(animation.at("channels").at(0).at("target").at("node").integer());
+        else
+          for (const json::Value& channel : animation.at("channels").arr) {
+            const int t = channel.at("target").at("node").integer();
+            if (std::find(targets.begin(), targets.end(), t) == targets.end()) targets.push_back(t);
           }
+        for (const int target : targets) {
+          Animation anim;
+          NodePath where;
+          for (size_t k = first_new_node; k < m_nodes.size(); ++k)
+            if (m_nodes[k].idx == target) { where = NodePath{int(k)}; break; }
+          if (where.empty() && joint_nodes.count(target)) where = joint_nodes[target];
+          if (where.empty()) throw std::runtime_error("invalid target node");
+          for (const json::Value& channel : animation.at("channels").arr) {
+            if (!gskins.empty() && channel.at("target").at("node").integer() != target) continue;
+            const json::Value& sampler = animation.at("samplers").at(size_t(channel.at("sampler").integer()));
+            const std::string path = channel.at("target").at("path").string();
+            const View in = get_buffer(sampler.at("input").integer());
+            if (in.stride != 4) throw std::runtime_error("unsupported animation input");
+            const View out = get_buffer(sampler.at("output").integer());
+            if (in.count != out.count) throw std::runtime_error("animation input size is not equal to output size");
+            const int per = path == "rotation" ? 4 : ((path == "translation" || path == "scale") ? 3 : 0);
+            if (per == 0) continue;
+            if (out.stride != 4 * per) throw std::runtime_error("invalid output stride");
+            need(in, size_t(in.count) * 4); need(out, size_t(out.count) * 4 * per);
+            auto f32 = [](const uint8_t* p) { float v; std::memcpy(&v, p, 4); return v; };
+            for (int i = 0; i < in.count; ++i) {
+              const float key = f32(in.data + 4 * i);
+              const uint8_t* o = out.data + size_t(4 * per) * i;
+              if (path == "translation") { anim.translation_input.push_back(key); anim.translation_output.push_back({double(f32(o)), double(f32(o + 4)), double(f32(o + 8))}); }
+              else if (path == "scale") { anim.scale_input.push_back(key); anim.scale_output.push_back({double(f32(o)), double(f32(o + 4)), double(f32(o + 8))}); }
+              else { anim.rotation_input.push_back(key); anim.rotation_output.push_back({double(f32(o + 12)), double(f32(o)), double(f32(o + 4)), double(f32(o + 8))}); }
+            }
+          }
+          m_animations.push_back(anim);
+          m_animation_targets.push_back(where[0]);  // an index, not the reference's Node*: m_nodes grows when files are appended
+          m_animation_paths.push_back(where);
         }
-        m_animations.push_back(anim);
-        m_animation_targets.push_back(target_root);  // an index, not the reference's Node*: m_nodes grows when files are appended
       }
   }
 
   // scene.cpp:836-860
   void update_transform()
   {
-    for (const Node& node : m_nodes) visit(node, Mat4d{});
+    for (Node& node : m_nodes) visit(node, Mat4d{});
   }
 
   // scene.cpp:862-898
@@ -419,12 +534,42 @@ struct Scene {
       if (!a.translation_input.empty()) { const auto v = interpolate3(a.translation_input, a.translation_output, time); for (int k = 0; k < 3; ++k) t[k] = v[size_t(k)]; }
       if (!a.rotation_input.empty()) { const auto v = interpolate4(a.rotation_input, a.rotation_output, time); for (int k = 0; k < 4; ++k) q[k] = v[size_t(k)]; }
       if (!a.scale_input.empty()) { const auto v = interpolate3(a.scale_input, a.scale_output, time); for (int k = 0; k < 3; ++k) s[k] = v[size_t(k)]; }
-      m_nodes.at(size_t(m_animation_targets.at(ai))).transform = Mat4d::trs(t, q, s);
+      node_at(m_animation_paths.at(ai)).transform = Mat4d::trs(t, q, s);
     }
     update_transform();
   }
 
-  std::vector<int> m_animation_targets;  // index into m_nodes of every animation's node
+  std::vector<int> m_animation_targets;      // index into m_nodes of the root every animation's node is, or is below
+  std::vector<NodePath> m_animation_paths;   // where every animation's node is
+
+  Node& node_at(const NodePath& path)
+  {
+    Node* n = &m_nodes.at(size_t(path.at(0)));
+    for (size_t k = 1; k < path.size(); ++k) n = &n->children.at(size_t(path[k]));
+    return *n;
+  }
+
+  // the palette as fh_set_joint_matrices takes it, 12 floats per joint of all skins: inverse(global(mesh node)) * global(joint node) * inverseBind, multiplied in
+  // double and rounded once.  The instance's own object_to_world stays the mesh node's global transform, so world space is global(joint) * inverseBind as glTF prescribes
+  std::vector<float> joint_matrices_3x4()
+  {
+    std::vector<float> out;
+    for (const Skin& sk : m_skins) {
+      const Mat4d to_object = sk.mesh_node.empty() ? Mat4d{} : node_at(sk.mesh_node).global.affine_inverse();
+      for (size_t k = 0; k < sk.joints.size(); ++k) {
+        const Mat4d m = Mat4d::mul(Mat4d::mul(to_object, node_at(sk.joints[k]).global), sk.inverse_bind[k]);
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 4; ++c) out.push_back(float(m.m[r][c]));
+      }
+    }
+    return out;
+  }
+  uint32_t n_joints() const
+  {
+    uint32_t n = 0;
+    for (const Skin& sk : m_skins) n += uint32_t(sk.joints.size());
+    return n;
+  }
 
   // instance transforms as the C ABI takes them: 3x4 row-major float, the inverse taken in double before rounding.  A matrix the
   // caller edited in m_transforms (float) wins over the stored double one.
@@ -446,12 +591,13 @@ struct Scene {
   }
 
  private:
-  void visit(const Node& node, const Mat4d& parent)
+  void visit(Node& node, const Mat4d& parent)
   {
     const Mat4d m = Mat4d::mul(parent, node.transform);
+    node.global = m;
     if (node.camera_id != -1) { m_has_camera_transform = true; m_camera_transform = m.to_float(); }
     if (node.submesh_id != -1) { m_transforms_exact[size_t(node.submesh_id)] = m; m_transforms[size_t(node.submesh_id)] = m.to_float(); }
-    for (const Node& c : node.children) visit(c, m);
+    for (Node& c : node.children) visit(c, m);
   }
   // scene.h:164-178: t = fmod(time, last key); h = t - input[idx0] (not divided by the key interval)
   static void bracket(const std::vector<float>& input, float time, size_t n_out, size_t& idx0, size_t& idx1, double& h)

@@ -218,6 +218,43 @@ int fh_bvh_build(fh_ctx* ctx);
 int fh_set_transforms(fh_ctx* ctx, uint32_t n_instances, const float* object_to_world, const float* world_to_object);
 int fh_scene_n_lights(fh_ctx* ctx, uint32_t* out);
 
+/* -- skeletal skinning (an extension beyond the reference, whose glTF reader loads no skins): linear-blend skinning of the uploaded scene's vertices on the device,
+ * one stage in front of the face records.  A skin gives every vertex four joint indices j[4] into ONE palette per scene and four weights w[4]; a pose is the palette:
+ * n_joints row-major 3 x 4 matrices J in the object space of the skinned vertices.  fh_set_transforms composes on top (posed object space first, then the instance
+ * transform); either order of the two calls gives the same bits.  Call fh_bvh_build afterwards, as after fh_set_transforms: the tree is refitted, or rebuilt when
+ * its node area has grown past 1.5 x; the light table and the light proxies are rebuilt by the next fh_render.
+ *
+ * The arithmetic (csrc/fh_skin.h), per vertex with bind position p and bind normal n, in fp32 without contraction, / and sqrt correctly rounded, every product and
+ * every sum rounded, sums taken left to right unless bracketed:
+ *   - all four weights == 0: the posed position and normal are the bind ones, bit for bit.  Otherwise
+ *   - B[e] = ((w0 * J[j0][e] + w1 * J[j1][e]) + w2 * J[j2][e]) + w3 * J[j3][e] for each of the 12 entries e.  Weights are used as given: no renormalisation.
+ *   - position: p'[r] = B[r][0] * p.x + B[r][1] * p.y + B[r][2] * p.z + B[r][3] * 1 for the rows r = 0, 1, 2.
+ *   - normal: with L0, L1, L2 the rows of B's 3 x 3 part, cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x) and
+ *     dot(a, b) = a.x * b.x + a.y * b.y + a.z * b.z: C0 = cross(L1, L2), C1 = cross(L2, L0), C2 = cross(L0, L1) (the cofactor matrix: the inverse transpose without
+ *     its division by the determinant); m = (dot(C0, n), dot(C1, n), dot(C2, n)); m is negated when dot(L0, C0) < 0; ln = sqrtf(dot(n, n)), lm = sqrtf(dot(m, m));
+ *     if lm is 0, infinite or NaN the posed normal is n; else s = ln / lm and the posed normal is (m.x * s, m.y * s, m.z * s): the bind normal's length is kept,
+ *     because emitter normals are used un-normalised.
+ * FH_E_INVALID, decided from the arguments and the context's counters before anything is changed (csrc/skin_plan_host.h): no scene loaded; n_vertices different from
+ * the uploaded scene's; null arrays; n_joints 0 or above 65536; a weight that is not finite; a joint index >= n_joints on a vertex with a non-zero weight;
+ * matrices before a skin was set; a matrix count different from n_joints; a matrix entry that is not finite.
+ * The skin and the palette belong to the uploaded scene: fh_scene_upload drops them.  A group broadcasts both setters; the two queries go to the lead.
+ * Not covered: morph targets, more than four influences per vertex, dual-quaternion blending, motion vectors for skinned pixels, per-sample motion blur. */
+typedef struct fh_skin_desc {
+  uint32_t n_vertices;    /* the uploaded scene's */
+  uint32_t n_joints;      /* 1 .. 65536 */
+  const uint16_t* joints; /* 4 per vertex */
+  const float* weights;   /* 4 per vertex */
+} fh_skin_desc;
+/* NULL clears: geometry returns to the bind pose, bit for bit.  A skin alone changes no bit of any render: geometry stays in the bind pose until the first
+ * fh_set_joint_matrices (setting a skin over a posed one returns to the bind pose as well). */
+int fh_set_skin(fh_ctx* ctx, const fh_skin_desc* skin);
+/* row-major 3 x 4 each, object space of the skinned vertices.  Matrices equal to the ones held return at once: geometry and tree stay. */
+int fh_set_joint_matrices(fh_ctx* ctx, uint32_t n, const float* m3x4);
+/* any pointer may be NULL.  n_joints 0: no skin; n_skinned_vertices: vertices with a non-zero weight */
+int fh_get_skin_info(fh_ctx* ctx, uint32_t* n_joints, uint32_t* n_skinned_vertices, int* posed);
+/* host arrays of 3 floats per vertex of the uploaded scene; the bind arrays when nothing is posed */
+int fh_get_posed_geometry(fh_ctx* ctx, float* vertices3, float* normals3);
+
 /* -- environment: renderer.h:554-612.  le/dir are float[3]; angle in degrees. */
 int fh_set_directional_light(fh_ctx* ctx, const float* le, const float* dir, float angle);
 int fh_clear_directional_light(fh_ctx* ctx);
@@ -418,7 +455,8 @@ int fh_motion_from_transforms(uint32_t n, const float* o2w_prev, const float* w2
  * When no entry has `moved` set (and when instance_ids, motion are NULL and n_instances is 0) the call is fh_denoise_temporal launch for launch and bit for bit, and
  * the id plane is never read.  FH_E_INVALID, from the arguments alone, leaving history and output alone: ids without motion or motion without ids; n_instances 0
  * with either given; a motion entry with a non-finite float; everything fh_denoise_temporal refuses.
- * Not covered: motion that is not one affine map per instance (skinning, morphs); the id is the chief ray's, so a pixel most of whose samples see another instance
+ * Not covered: motion that is not one affine map per instance (morph targets, which the glTF reader does not load; vertices moved by fh_set_joint_matrices: a skinned
+ * instance whose matrix did not change counts as unmoved and the two stops decide whether its pixels keep a history); the id is the chief ray's, so a pixel most of whose samples see another instance
  * is carried with the wrong map and the two stops decide whether it keeps a history; the lighting change a moving light or occluder causes lags unless
  * fh_set_denoise_response (below) is on, which shortens the lag and does not remove it. */
 int fh_denoise_temporal_motion(fh_ctx* ctx, uint32_t width, uint32_t height, const fh_denoise_inputs* inputs, const fh_camera* camera, const fh_temporal_params* temporal,
