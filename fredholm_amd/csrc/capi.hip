@@ -231,6 +231,7 @@ int fh_ctx_create(int device, fh_ctx** out)
     env_uint("FH_SORT_ONEPASS", 0, 2, t.sort_onepass);
     env_uint("FH_BOTTOM_UP", 0, 2, t.bottom_up);
     env_uint("FH_SKY_DEFER", 0, 1, t.sky_defer);
+    env_uint("FH_DARK_SKY", 0, 1, t.dark_sky);
     t.debug_tail = getenv("FH_DEBUG_TAIL") != nullptr;
     if (const char* e = getenv("FH_FORCE_ALPHA")) t.force_alpha = e[0] == '1';
   }
@@ -242,8 +243,8 @@ int fh_ctx_create(int device, fh_ctx** out)
     if (ctx->sky_stream.create(hipStreamNonBlocking, low ? least : 0) != hipSuccess) return bail("stream creation failed");
   }
   if (ctx->ev_sky.create(hipEventDisableTiming) != hipSuccess || ctx->ev_sky_cursor.create(hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
-  if (ctx->d_split_counters.alloc(4) != hipSuccess) return bail("device allocation failed");
-  (void)hipMemsetAsync(ctx->d_split_counters, 0, 16, ctx->stream);
+  if (ctx->d_split_counters.alloc(5) != hipSuccess) return bail("device allocation failed");
+  (void)hipMemsetAsync(ctx->d_split_counters, 0, 20, ctx->stream);
   if (ctx->ev_render_begin.create() != hipSuccess || ctx->ev_render_end.create() != hipSuccess) return bail("event creation failed");
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail("hipStreamSynchronize failed");  // the fills above are done before any upload (synchronous copies, ordered with no stream) touches what they cleared
   *out = ctx;

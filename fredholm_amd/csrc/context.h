@@ -123,9 +123,10 @@ struct fh_ctx {
   fh::DeviceBuffer<uint32_t> d_owned_xy;  // the same pixels as x | y << 16
   uint32_t n_owned = 0;
   // pixels that cannot see the scene (render.hip: k_split_pixels / k_sky_pixels): [0] / [1] image indices and x | y << 16 of the pixels the passes render, [2] / [3] of the sky pixels
-  fh::DeviceBuffer<uint32_t> d_split[4];
-  uint32_t n_wave_px = 0, n_sky_px = 0;
-  fh::DeviceBuffer<uint32_t> d_split_counters;  // wave pixels, sky pixels, bounds-test violations seen by k_sky_pixels, k_sky_pixels' cursor over the groups of its list
+  // k_sky_pixels renders, [4] / [5] of the dark sky pixels (k_dark_pixels; none unless the split was made under dark_sky_verdict, which is part of the key)
+  fh::DeviceBuffer<uint32_t> d_split[6];
+  uint32_t n_wave_px = 0, n_sky_px = 0, n_dark_px = 0;
+  fh::DeviceBuffer<uint32_t> d_split_counters;  // wave pixels, sky pixels, bounds-test violations seen by k_sky_pixels, k_sky_pixels' cursor over the groups of its list, dark sky pixels
   bool split_valid = false;
   float split_key[32] = {};              // camera, scene bounds, resolution and ownership the lists were made for
   fh::Event ev_sky;
@@ -269,6 +270,7 @@ struct fh_ctx {
     uint32_t sort_onepass = 2;      // FH_SORT_ONEPASS: cell sorts in calls of ONE pass -- 0 none, 1 all (as in multi-pass calls), 2 only the queue the fused tail takes over
     uint32_t sky_defer = 2;         // FH_SKY_DEFER=0|1: shadow rays of the sky and light slots carry weights and k_sky_resolve evaluates the environment for those that escape -- never / wherever
                                     // a pass is eligible (render_plan_host.h: sky_defer_verdict); default (2): the library's own choice
+    uint32_t dark_sky = 2;          // FH_DARK_SKY=0|1: sky pixels below the Hosek sky's horizon skip k_sky_pixels -- never / wherever a call is eligible (dark_sky_verdict), which is the default too
     bool debug_tail = false;        // FH_DEBUG_TAIL
     bool force_alpha = false;       // FH_FORCE_ALPHA=1 (timing experiments): the kernels with the any-hit path compiled in, whatever the scene
   } tun;

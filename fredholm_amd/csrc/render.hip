@@ -35,6 +35,7 @@
 
 #include "context.h"
 #include "fh_bsdf.h"
+#include "fh_dark_sky.h"
 #include "fh_envmap.h"
 #include "fh_tonemap.h"
 #include "fh_trace.h"
@@ -245,20 +246,26 @@ __global__ void __launch_bounds__(kBlock) k_bump_issued(uint32_t* issued, const 
 // pixel is sky when that exceeds the bounding sphere of the padded scene bounds with a margin (0.1 % of the radius and of the distance, far above the rounding
 // of these few operations).  k_sky_pixels still runs k_generate's own bounds test per sample and counts a violation (fh_sync reports it): the split can only
 // lose speed, never a ray that hits.
+//
+// Dark sky pixels (dark_on; render_plan_host.h: dark_sky_verdict).  Under the Hosek sky a ray that points below the horizon carries NaN, which the guard counts as zero.
+// A sky pixel whose every ray points below the horizon (fh_dark_sky.h: dark_sky_pixel, from the centre line and the family radius m formed here) goes to a third
+// list and never enters k_sky_pixels: k_dark_pixels applies the updates of the running means that samples of value zero make, and nothing else.  The per-sample bounds
+// test (`violations`) does NOT run for these pixels; they are a subset of the pixels the tests above proved to be sky, by the same geometry.
 struct SplitDev {
   f3 centre;      // bounding sphere of the padded scene bounds, camera space
   float radius;
   float far;      // distance of the farthest corner of the padded scene bounds from the lens centre
-  uint32_t* wave_px; uint32_t* wave_xy; uint32_t* sky_px; uint32_t* sky_xy;
-  uint32_t* counters;  // [0] wave pixels, [1] sky pixels, [2] bounds-test violations seen by k_sky_pixels
+  uint32_t dark_on;
+  uint32_t* wave_px; uint32_t* wave_xy; uint32_t* sky_px; uint32_t* sky_xy; uint32_t* dark_px; uint32_t* dark_xy;
+  uint32_t* counters;  // [0] wave pixels, [1] sky pixels, [2] bounds-test violations seen by k_sky_pixels, [4] dark sky pixels
 };
 __global__ void __launch_bounds__(kBlock) k_split_pixels(FrameDev fr, SplitDev sp, const uint32_t* owned, const uint32_t* owned_xy, uint32_t n_owned)
 {
-  __shared__ uint32_t s_reserve[2][10];
+  __shared__ uint32_t s_reserve[2][15];
   uint32_t iter = 0;
   for (uint32_t base = blockIdx.x * blockDim.x; base < n_owned; base += gridDim.x * blockDim.x) {
     const uint32_t i = base + threadIdx.x;
-    bool sky = false, wave = false;
+    bool sky = false, wave = false, dark = false;
     uint32_t px = 0, xy = 0;
     if (i < n_owned) {
       px = owned[i]; xy = owned_xy[i];
@@ -298,14 +305,20 @@ __global__ void __launch_bounds__(kBlock) k_split_pixels(FrameDev fr, SplitDev s
         sky = miss && dd[0] == dd[0] && dd[1] == dd[1] && dd[2] == dd[2] && d == d;
       }
       wave = !sky;
+      if (sky && sp.dark_on) {  // ab = B0 - A0 is the centre ray's direction after camera_ray's z flip; the transform is a rotation (split_pixels)
+        const f3 c = xform_dir(fr.cam_xf, (1.0f / L) * ab);
+        dark = c.x == c.x && c.z == c.z && dark_sky_pixel(c.y, m, L);
+        sky = !dark;
+      }
     }
-    uint32_t* const counters2[2] = {sp.counters, sp.counters + 1};
-    const bool act[2] = {wave, sky};
-    uint32_t pos[2];
-    block_queue_reserve<2>(counters2, act, pos, s_reserve[iter & 1u]);
+    uint32_t* const counters3[3] = {sp.counters, sp.counters + 1, sp.counters + 4};
+    const bool act[3] = {wave, sky, dark};
+    uint32_t pos[3];
+    block_queue_reserve<3>(counters3, act, pos, s_reserve[iter & 1u]);
     ++iter;
     if (wave) { sp.wave_px[pos[0]] = px; sp.wave_xy[pos[0]] = xy; }
     if (sky) { sp.sky_px[pos[1]] = px; sp.sky_xy[pos[1]] = xy; }
+    if (dark) { sp.dark_px[pos[2]] = px; sp.dark_xy[pos[2]] = xy; }
   }
 }
 
@@ -473,6 +486,59 @@ __global__ void __launch_bounds__(kBlock, kSkyWaves) k_sky_pixels(FrameDev fr, L
     if (n_taken) atomicAdd(&s_taken, n_taken);
     __syncthreads();
     if (threadIdx.x == 0u && s_taken) atomicAdd(violations_or_adaptive->taken, s_taken);
+  }
+}
+
+// all `n_samples` samples of this call for the DARK sky pixels (k_split_pixels): every one of them is zero after the NaN guard -- a path that is not alive has
+// radiance 0, and one that is looks below the horizon of the Hosek sky and carries NaN -- so what k_sky_pixels would do to such a pixel is n_samples times
+// x = coef * (fn * x + 0) on the beauty mean and on the five AOV means, and the two counts.  The same operations on the same operands, one lane per pixel; no camera,
+// no sampler, no sky.  A group of values that all hold the bit pattern +0 stays that (k_sky_pixels' own shortcut for the AOVs; it holds for the beauty mean alike).
+__global__ void __launch_bounds__(kBlock) k_dark_pixels(LayersDev layers, uint32_t* issued, const uint32_t* dark_px, uint32_t n_dark, uint32_t n_samples)
+{
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_dark; i += gridDim.x * blockDim.x) {
+    const uint32_t image_idx = dark_px[i];
+    const uint32_t first = layers.sample_count[image_idx];
+    f3 beauty = mk3(layers.beauty[image_idx]);
+    if ((__float_as_uint(beauty.x) | __float_as_uint(beauty.y) | __float_as_uint(beauty.z)) != 0u) {
+      uint32_t n_spp = first;
+#pragma unroll 1
+      for (uint32_t k = 0; k < n_samples; ++k) {
+        const float coef = div_r_nofix<0, 0, 0, 32>(1.0f, n_spp + 1.0f);
+        const float fn = (float)n_spp;
+        beauty = coef * (fn * beauty + mk3(0.0f));
+        n_spp++;
+      }
+    }
+    f3 position = mk3(layers.position[image_idx]), normal = mk3(layers.normal[image_idx]), albedo = mk3(layers.albedo[image_idx]);
+    float depth = layers.depth[image_idx];
+    const float4 tc4 = layers.texcoord[image_idx];
+    float tcx = tc4.x, tcy = tc4.y;
+    const uint32_t any_bits = __float_as_uint(position.x) | __float_as_uint(position.y) | __float_as_uint(position.z) | __float_as_uint(normal.x) | __float_as_uint(normal.y) |
+                              __float_as_uint(normal.z) | __float_as_uint(albedo.x) | __float_as_uint(albedo.y) | __float_as_uint(albedo.z) | __float_as_uint(depth) |
+                              __float_as_uint(tcx) | __float_as_uint(tcy);
+    if (any_bits != 0u) {
+      uint32_t n_aov = first;
+#pragma unroll 1
+      for (uint32_t k = 0; k < n_samples; ++k) {
+        const float coef = div_r_nofix<0, 0, 0, 32>(1.0f, n_aov + 1.0f);
+        const float fn = (float)n_aov;
+        position = coef * (fn * position + mk3(0.0f));
+        normal = coef * (fn * normal + mk3(0.0f));
+        depth = coef * (fn * depth + 0.0f);
+        tcx = coef * (fn * tcx + 0.0f);
+        tcy = coef * (fn * tcy + 0.0f);
+        albedo = coef * (fn * albedo + mk3(0.0f));
+        n_aov++;
+      }
+    }
+    issued[image_idx] += n_samples;
+    layers.sample_count[image_idx] = first + n_samples;
+    layers.beauty[image_idx] = mk4(beauty, 1.0f);
+    layers.position[image_idx] = mk4(position, 1.0f);
+    layers.normal[image_idx] = mk4(normal, 1.0f);
+    layers.depth[image_idx] = depth;
+    layers.texcoord[image_idx] = make_float4(tcx, tcy, 0.0f, 1.0f);
+    layers.albedo[image_idx] = mk4(albedo, 1.0f);
   }
 }
 
@@ -2293,7 +2359,7 @@ int configure_traversal_lds(fh_ctx* ctx, uint32_t stack_bytes)
 }
 
 // classify the owned pixels for this camera (k_split_pixels); cached until camera, resolution, ownership or scene bounds change
-static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
+static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr, bool dark)
 {
   float key[32] = {};
   for (int i = 0; i < 12; ++i) key[i] = cam->transform[i];
@@ -2301,6 +2367,7 @@ static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
   for (int i = 0; i < 3; ++i) { key[15 + i] = ctx->scene_lo[i]; key[18 + i] = ctx->scene_hi[i]; }
   key[21] = (float)ctx->width; key[22] = (float)ctx->height; key[23] = (float)ctx->n_owned; key[24] = (float)ctx->shard_rank; key[25] = (float)ctx->shard_world;
   key[26] = (float)ctx->tile_w; key[27] = (float)ctx->tile_h;
+  key[28] = dark ? 1.0f : 0.0f;  // (the lists of a split made without the dark rule hold every sky pixel in the sky list: what an adaptive call needs)
   if (ctx->split_valid && std::memcmp(key, ctx->split_key, sizeof key) == 0) return FH_OK;
   ctx->split_valid = false;
   // the bound is derived for a rigid camera transform (rotation + translation): anything else renders every pixel through the passes
@@ -2312,12 +2379,12 @@ static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
       dev = fmaxf(dev, fabsf(d - (a == b ? 1.0f : 0.0f)));
     }
   std::memcpy(ctx->split_key, key, sizeof key);
-  ctx->n_wave_px = ctx->n_owned; ctx->n_sky_px = 0;
+  ctx->n_wave_px = ctx->n_owned; ctx->n_sky_px = 0; ctx->n_dark_px = 0;
   if (!(dev < 1e-4f)) { ctx->split_valid = true; return FH_OK; }  // (valid: "no sky pixels" for this key)
-  if (ctx->d_split[3].size() < ctx->n_owned) {  // (the last of the four: all were made)
+  if (ctx->d_split[5].size() < ctx->n_owned) {  // (the last of the six: all were made)
     FH_HIP(hipDeviceSynchronize());
-    for (int k = 0; k < 4; ++k) ctx->d_split[k].reset();
-    for (int k = 0; k < 4; ++k) FH_HIP(ctx->d_split[k].alloc(ctx->n_owned));
+    for (int k = 0; k < 6; ++k) ctx->d_split[k].reset();
+    for (int k = 0; k < 6; ++k) FH_HIP(ctx->d_split[k].alloc(ctx->n_owned));
   }
   // no launch of an earlier call may still read the lists that are rewritten here
   FH_HIP(drain_passes(ctx, true));
@@ -2337,17 +2404,19 @@ static int split_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr)
     }
     sp.far = sqrtf(far2) * 1.001f;
   }
-  sp.wave_px = ctx->d_split[0]; sp.wave_xy = ctx->d_split[1]; sp.sky_px = ctx->d_split[2]; sp.sky_xy = ctx->d_split[3];
+  sp.wave_px = ctx->d_split[0]; sp.wave_xy = ctx->d_split[1]; sp.sky_px = ctx->d_split[2]; sp.sky_xy = ctx->d_split[3]; sp.dark_px = ctx->d_split[4]; sp.dark_xy = ctx->d_split[5];
+  sp.dark_on = dark ? 1u : 0u;
   sp.counters = ctx->d_split_counters;
   FH_HIP(hipMemsetAsync(ctx->d_split_counters, 0, 8, ctx->stream));  // (the violation counter, word 2, keeps counting)
+  FH_HIP(hipMemsetAsync(ctx->d_split_counters + 4, 0, 4, ctx->stream));
   hipLaunchKernelGGL(k_split_pixels, dim3(grid_for(ctx->n_owned)), dim3(kBlock), 0, ctx->stream, fr, sp, ctx->d_owned, ctx->d_owned_xy, ctx->n_owned);
-  uint32_t n[2] = {0, 0};
-  FH_HIP(hipMemcpyAsync(n, ctx->d_split_counters, 8, hipMemcpyDeviceToHost, ctx->stream));
+  uint32_t n[5] = {0, 0, 0, 0, 0};  // (words 2 and 3, the violations and the cursor, are not looked at)
+  FH_HIP(hipMemcpyAsync(n, ctx->d_split_counters, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  if (n[0] + n[1] != ctx->n_owned) return fail(ctx, FH_E_HIP, "k_split_pixels lost pixels");
-  ctx->n_wave_px = n[0]; ctx->n_sky_px = n[1];
+  if ((unsigned long long)n[0] + n[1] + n[4] != ctx->n_owned || (!dark && n[4])) return fail(ctx, FH_E_HIP, "k_split_pixels lost pixels");
+  ctx->n_wave_px = n[0]; ctx->n_sky_px = n[1]; ctx->n_dark_px = n[4];
   ctx->split_valid = true;
-  if (getenv("FH_DEBUG_BVH")) fprintf(stderr, "[split] %u of %u owned pixels cannot see the scene (bounding sphere radius %.4f at camera-space (%.3f, %.3f, %.3f))\n", n[1], ctx->n_owned, sp.radius, sp.centre.x, sp.centre.y, sp.centre.z);
+  if (getenv("FH_DEBUG_BVH")) fprintf(stderr, "[split] %u of %u owned pixels cannot see the scene, %u of them dark (bounding sphere radius %.4f at camera-space (%.3f, %.3f, %.3f))\n", n[1] + n[4], ctx->n_owned, n[4], sp.radius, sp.centre.x, sp.centre.y, sp.centre.z);
   return FH_OK;
 }
 
@@ -2517,19 +2586,22 @@ LayersDev layers_dev(const fh_ctx* ctx, const fh_render_layers* layers)
   return L;
 }
 
-// the pixels a call (in adaptive mode: a round) renders through the passes, as image indices and as x | y << 16; n_sky: the sky pixels beside them
-struct PixelLists { const uint32_t* px; const uint32_t* xy; uint32_t n_px, n_sky; };
+// the pixels a call (in adaptive mode: a round) renders through the passes, as image indices and as x | y << 16; n_sky: the sky pixels beside them that k_sky_pixels
+// renders, n_dark: the dark ones, which k_dark_pixels advances (ctx->d_split[2..5])
+struct PixelLists { const uint32_t* px; const uint32_t* xy; uint32_t n_px, n_sky, n_dark; };
 
 // ---- pixels that cannot see the scene are rendered by k_sky_pixels, the others by the passes (see k_split_pixels).  Worth its fixed cost -- one small launch and a
 // host synchronisation whenever camera, resolution or scene bounds change -- for calls of many samples only: 2^27 camera paths, 64 spp of a 1080p frame
 int choose_pixels(fh_ctx* ctx, const fh_camera* cam, const FrameDev& fr, uint32_t n_samples, bool quirk, PixelLists& out)
 {
-  out = PixelLists{ctx->d_owned, ctx->d_owned_xy, ctx->n_owned, 0u};
-  if (!(ctx->tun.sky_split && !quirk && (unsigned long long)n_samples * ctx->n_owned >= (1ull << ctx->tun.sky_split_min_log2))) return FH_OK;
-  const int rc = split_pixels(ctx, cam, fr);
+  out = PixelLists{ctx->d_owned, ctx->d_owned_xy, ctx->n_owned, 0u, 0u};
+  const bool splits = ctx->tun.sky_split && !quirk && (unsigned long long)n_samples * ctx->n_owned >= (1ull << ctx->tun.sky_split_min_log2);
+  if (!splits) return FH_OK;
+  const bool dark = dark_sky_verdict(splits, fr.has_hosek != 0, fr.has_ibl != 0, ctx->adaptive, (ctx->flags & FH_FLAG_REFERENCE_FIRSTHIT) != 0, ctx->tun.dark_sky);
+  const int rc = split_pixels(ctx, cam, fr, dark);
   if (rc) return rc;
-  if (ctx->split_valid && ctx->n_sky_px >= ctx->n_owned / 8u)  // (a handful of sky pixels is not worth a second kernel)
-    out = PixelLists{ctx->d_split[0], ctx->d_split[1], ctx->n_wave_px, ctx->n_sky_px};
+  if (ctx->split_valid && ctx->n_sky_px + ctx->n_dark_px >= ctx->n_owned / 8u)  // (a handful of sky pixels is not worth a second kernel)
+    out = PixelLists{ctx->d_split[0], ctx->d_split[1], ctx->n_wave_px, ctx->n_sky_px, ctx->n_dark_px};
   return FH_OK;
 }
 
@@ -3080,6 +3152,12 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
       ctx->stats.sky_pixel_samples += (uint64_t)base.n_sky * n_samples;
     }
   }
+  if (base.n_dark) {  // the dark sky pixels (never in an adaptive call: dark_sky_verdict), on the main stream ahead of the passes: they share no pixel with anything else of this call
+    Span sp(ctx, ctx->stream, 4);
+    hipLaunchKernelGGL(k_dark_pixels, dim3(grid_for(base.n_dark)), dim3(kBlock), 0, ctx->stream, c.L, ctx->d_sample_issued, (const uint32_t*)ctx->d_split[4].get(), base.n_dark, n_samples);
+    ctx->stats.paths += (uint64_t)base.n_dark * n_samples;  // (samples of sky pixels as before: counted, not rendered)
+    ctx->stats.sky_pixel_samples += (uint64_t)base.n_dark * n_samples;
+  }
   { const int rc = stream_plan(ctx, c.sc, count, base.n_sky && sky.filler_wgs, c.plan); if (rc) return rc; }
   if (ctx->tun.debug_tail) {  // (k_sky_resolve's list lengths of this call, printed below)
     if (!ctx->d_resolve_dbg) FH_HIP(ctx->d_resolve_dbg.alloc(2));
@@ -3130,6 +3208,7 @@ int render_submit(fh_ctx* ctx, const fh_camera* cam, const float* bg, const fh_r
     unsigned long long dbg[2] = {0ull, 0ull};
     FH_HIP(hipStreamSynchronize(ctx->stream));
     FH_HIP(hipMemcpy(dbg, ctx->d_resolve_dbg, sizeof(dbg), hipMemcpyDeviceToHost));
+    if (base.n_sky || base.n_dark) fprintf(stderr, "[dark-sky] %u of %u sky pixels are dark\n", base.n_dark, base.n_sky + base.n_dark);
     if (dbg[1]) fprintf(stderr, "[sky-resolve] %llu queue entries, %llu escaped sky / light rays: %.4f per entry\n", dbg[1], dbg[0], (double)dbg[0] / (double)dbg[1]);
   }
   return FH_OK;

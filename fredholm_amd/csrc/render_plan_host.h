@@ -171,4 +171,15 @@ inline bool sky_defer_verdict(bool emitters, bool hosek, bool ibl, bool env_samp
   return eligible && by_default;
 }
 
+// Whether k_split_pixels sets the DARK sky pixels apart -- those every ray of which points below the horizon of the Hosek sky, so that every sample is NaN and counts
+// as zero (fh_dark_sky.h) -- and k_dark_pixels advances their means without rendering a sample: only in a call that splits off its sky pixels, only where a camera
+// ray that leaves the scene sees the Hosek sky (an IBL comes first in env_radiance; a constant background is not NaN), and not in the modes that need more than the
+// means of a pixel: an adaptive call (the moments of a dark pixel would stop it at its first boundary: the old path does that bookkeeping) and FH_FLAG_REFERENCE_FIRSTHIT.
+// forced (FH_DARK_SKY): 0 off, anything else: on where eligible.
+inline bool dark_sky_verdict(bool splits_sky, bool hosek, bool ibl, bool adaptive, bool reference_firsthit, uint32_t forced)
+{
+  const bool eligible = splits_sky && hosek && !ibl && !adaptive && !reference_firsthit;
+  return forced != 0u && eligible;
+}
+
 }  // namespace fh
